@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """bench.py — frames/sec of the fused colour -> inRange -> OPEN/CLOSE 5x5 -> CCL chain at 1080p.
 
-Contract (driver): `python bench.py --gpus N --steps K --warmup W`; for N > 1 it is launched by
+Usage: `python bench.py --gpus N --steps K --warmup W`; for N > 1 it is launched by
 torch.distributed.run with one rank per GPU.  A "step" is one vp_chain_run over one batch of
 synthetic 1080p frames already resident in HBM (BASELINE.json configs[1]: preprocessor+red_buoy
 chain, S1 frames, LAB-a in [150,255], OPEN then CLOSE with a 5x5 rect, 8-connected CCL + stats).
@@ -9,9 +9,14 @@ Frames are independent, so ranks shard them with no data-path collective ("weak"
 rank processes its own batch); torch.distributed is used only for the barrier and the max over
 ranks of the timed region.
 
-Prints ONE JSON line on rank 0: metric / value / ... plus
+A plain run sets up, runs W warm-up steps, times exactly K steps in one region and prints ONE JSON
+line on rank 0: metric / value / unit / ms_per_step / ...  `--dump-outputs DIR` also writes what the
+last timed step computed (dump_outputs).  `--full` adds everything else, in further passes:
+  regions:      five timed regions of K steps, `value` from the median one
   roofline:     dominant kernel's algorithmic bytes per launch / its HIP-event duration vs 8 TB/s
+  kernels:      per-kernel HIP-event times of K more steps
   cpu_baseline: the CPU oracle (scalar C port, 1 thread) timed on a bounded sample of the same frames
+  extras:       other outputs and frame families, module / runtime / host-fed rates, N > 1 host-fed leg
 """
 import argparse
 import ctypes as C
@@ -47,13 +52,17 @@ def parse():
     ap.add_argument("--warmup", type=int, default=5)
     ap.add_argument("--batch", type=int, default=128, help="1080p frames per step per GPU")
     ap.add_argument("--distinct", type=int, default=8, help="distinct synthetic frames (tiled to the batch)")
-    ap.add_argument("--cpu-seconds", type=float, default=12.0, help="budget of the cpu_baseline leg")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-extras", action="store_true", help="skip the chain + contours side measurement")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what the headline does not need: five regions, roofline, per-kernel times, cpu_baseline, extras")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="write what the last timed step computed as DIR/<name>.npy (float32 / float64, at most 64 MB)")
+    ap.add_argument("--cpu-seconds", type=float, default=12.0, help="budget of the cpu_baseline leg (--full)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full without the cpu_baseline leg")
+    ap.add_argument("--no-extras", action="store_true", help="--full without the side measurements of `extras`")
     ap.add_argument("--max-labels", type=int, default=256)
-    ap.add_argument("--regions", type=int, default=5,
+    ap.add_argument("--regions", type=int, default=None,
                     help="timed regions of exactly --steps steps each (every one bracketed by barrier + synchronize, MAX over ranks); "
-                         "`value` comes from the median region (SURVEY 8d: median of 5)")
+                         "`value` comes from the median region.  Default 1, or 5 with --full (SURVEY 8d: median of 5)")
     ap.add_argument("--traffic-file", default=os.path.join("profiles", "r04", "traffic.json"),
                     help="rocprofv3 --pmc summary (tools/pmc_traffic.py) to take roofline.traffic from; used only when its recorded "
                          "source digest equals the running build and it holds the exact kernel instantiation that was timed")
@@ -158,6 +167,45 @@ def host_fed_leg(dist, rank, world, device, width, height, batch=32, batches=8, 
     return mine
 
 
+DUMP_LIMIT_BYTES = 64 * 10**6
+DUMP_WHOLE_BYTES = 4 * 10**6       # an output larger than this in float32 is written as two whole frames + a sample
+DUMP_SAMPLE = 1 << 18              # seeded positions of such an output, drawn over the whole batch
+
+
+def sample_positions(n, seed=0):
+    """The flat positions `<name>_sample.npy` holds, ascending: min(DUMP_SAMPLE, n) distinct ones out of n, fixed by `seed`."""
+    return np.sort(np.random.default_rng(seed).choice(n, size=min(DUMP_SAMPLE, n), replace=False))
+
+
+def dump_outputs(out_dir, outputs, seed=0):
+    """Writes the arrays of `outputs` ({name: tensor [frames, ...]}, what the caller of the timed path receives) as
+    out_dir/<name>.npy: float32 when every value is exact in it, else float64.  An output of more than DUMP_WHOLE_BYTES (an image of
+    the batch: 128 1080p frames are 265 M values) is written as <name>_frames.npy, its first and last frame whole, and
+    <name>_sample.npy, its values at sample_positions(numel, seed) over the whole batch.  -> {file name: bytes}"""
+    import torch
+    os.makedirs(out_dir, exist_ok=True)
+    written = {}
+
+    def save(name, t):
+        a = t.cpu().numpy()
+        exact32 = a.dtype == np.float32 or (a.dtype.kind in "biu" and (a.size == 0 or int(np.abs(a.astype(np.int64)).max()) < 1 << 24))
+        a = a.astype(np.float32 if exact32 else np.float64)
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+        written[name + ".npy"] = a.nbytes
+
+    for name, t in outputs.items():
+        if t.numel() * 4 <= DUMP_WHOLE_BYTES:
+            save(name, t)
+            continue
+        save(name + "_frames", t[sorted({0, t.shape[0] - 1})])
+        flat = t.reshape(-1)
+        save(name + "_sample", flat[torch.from_numpy(sample_positions(flat.numel(), seed)).to(flat.device)])
+    total = sum(written.values())
+    if total > DUMP_LIMIT_BYTES:
+        raise SystemExit(f"--dump-outputs: {total} bytes written to {out_dir}, more than the {DUMP_LIMIT_BYTES} allowed")
+    return written
+
+
 def main():
     args = parse()
     rank = int(os.environ.get("RANK", "0"))
@@ -209,16 +257,22 @@ def main():
     def sync():
         ctx.synchronize()
         torch.cuda.synchronize()
+    regions = args.regions if args.regions is not None else (5 if args.full else 1)
     region_s = [timed_steps(lambda: ctx.chain_run(desc, bufs, B), sync, args.steps, dist, device="cpu" if args.rehearse_on_one_gpu else "cuda")
-                for _ in range(max(1, args.regions))]
+                for _ in range(max(1, regions))]
     elapsed = sorted(region_s)[len(region_s) // 2]          # median region (every region is exactly K steps)
+    n_labels_seen = d_nl.cpu().numpy()
+    if args.dump_outputs and rank == 0:                     # before anything else reuses the buffers
+        dump_outputs(args.dump_outputs, {"threshed": d_thr, "cleaned": d_cln, "labels": d_lab, "stats": d_stats, "centroids": d_cent,
+                                         "nlabels": d_nl})
 
     # ---- per-kernel attribution with HIP events on the launch stream (same K steps again) ----------
-    ctx.profile_begin(args.steps * 16)
-    for _ in range(args.steps):
-        ctx.chain_run(desc, bufs, B)
-    prof = ctx.profile_end()
-    n_labels_seen = d_nl.cpu().numpy()
+    prof = {}
+    if args.full:
+        ctx.profile_begin(args.steps * 16)
+        for _ in range(args.steps):
+            ctx.chain_run(desc, bufs, B)
+        prof = ctx.profile_end()
 
     fps = n_gpus * B * args.steps / elapsed
     ms_per_step = 1e3 * elapsed / args.steps
@@ -226,7 +280,7 @@ def main():
     # ---- extra (not `value`): the same chain followed by cv2.findContours(RETR_EXTERNAL, CHAIN_APPROX_SIMPLE) on the cleaned
     # mask of every frame (modules/red_buoy.py:36-38), batch resident in HBM, rank-local rate
     extras = {}
-    if not args.no_extras:
+    if args.full and not args.no_extras:
         cdesc = _vp.make_contour_desc("cleaned", _vp.RETR_EXTERNAL, _vp.CHAIN_APPROX_SIMPLE, 64, 8192)
         carr = {"info": torch.zeros((B, 2), dtype=torch.int32, device="cuda"), "counts": torch.zeros((B, 64), dtype=torch.int32, device="cuda"),
                 "offsets": torch.zeros((B, 64), dtype=torch.int32, device="cuda"), "is_hole": torch.zeros((B, 64), dtype=torch.uint8, device="cuda"),
@@ -295,7 +349,7 @@ def main():
 
     # ---- the rates a module sees (not `value`; PCIe and Python inclusive): module bodies through the per-operator mirror, a module on
     # the runtime end to end, host-fed batches through the dispatcher - each with the bound it runs against, measured in this run
-    if not args.no_extras and rank == 0 and n_gpus == 1:
+    if args.full and not args.no_extras and rank == 0 and n_gpus == 1:
         import contextlib
         import module_harness as MH
         try:
@@ -322,7 +376,7 @@ def main():
 
     # N > 1: the host-fed leg on every rank at once (its own GPU, feeders on that GPU's NUMA node) - where scaling would bend first.
     # `value` stays the resident-batch number.
-    if not args.no_extras and n_gpus > 1:
+    if args.full and not args.no_extras and n_gpus > 1:
         try:
             chain = dict(color_mode=_vp.BGR2LAB, lo=(0, 150, 0), hi=(255, 255, 255), morph=morph, ccl=1, max_labels=args.max_labels, want=("stats",))
             import contextlib
@@ -340,7 +394,7 @@ def main():
     # instantiation of the kernel that was timed - otherwise the field is null rather than a number of unknown provenance.
     traffic_tab, traffic_src = {}, None
     tpath = args.traffic_file if os.path.isabs(args.traffic_file) else os.path.join(ROOT, args.traffic_file)
-    if args.batch == 128 and os.path.exists(tpath):
+    if args.full and args.batch == 128 and os.path.exists(tpath):
         try:
             import importlib.util
             spec = importlib.util.spec_from_file_location("vp_build", os.path.join(ROOT, "cuauv-vision-pipeline_amd", "build.py"))
@@ -387,7 +441,7 @@ def main():
 
     cpu = None
     real_cv2 = None
-    if rank == 0 and n_gpus == 1 and not args.no_cpu_baseline:
+    if args.full and rank == 0 and n_gpus == 1 and not args.no_cpu_baseline:
         try:   # a real OpenCV (third-party, not reference code) gives the reference's own CPU path; never the facade of this repo
             import cv2 as _cv2
             if "vision" not in (getattr(_cv2, "__file__", "") or "") and hasattr(_cv2, "connectedComponentsWithStats"):
@@ -413,7 +467,7 @@ def main():
         cpu = {"value": round(done / dt, 2), "unit": "frames/s", "cores": 1, "kind": "reference",
                "sample": f"{done} S1 1080p frames through cv2 {cv2.__version__} (cvtColor, split, inRange, morphologyEx x2, "
                          f"connectedComponentsWithStats; setNumThreads(1), {dt:.1f} s); host has {os.cpu_count()} cores"}
-    elif rank == 0 and n_gpus == 1 and not args.no_cpu_baseline:
+    elif args.full and rank == 0 and n_gpus == 1 and not args.no_cpu_baseline:
         from oracle import oracle as orc
         orc.lib()
         done, t_start = 0, time.perf_counter()
@@ -447,7 +501,7 @@ def main():
         out = {
             "metric": "frames/sec for color->threshold->morph->CCL at 1080p",
             "value": round(fps, 1), "unit": "frames/s", "n_gpus": n_gpus, "steps": args.steps, "warmup": args.warmup,
-            "regions": len(region_s), "region_ms_per_step": [round(1e3 * r / args.steps, 4) for r in region_s], "value_from": "median region",
+            "regions": len(region_s), "region_ms_per_step": [round(1e3 * r / args.steps, 4) for r in region_s], "value_from": "median region" if len(region_s) > 1 else "one region",
             "ms_per_step": round(ms_per_step, 4), "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
             "dtype": "u8", "data": "synthetic",
             "config": {"workload": "configs[1]: preprocessor+red_buoy fused chain, S1 synthetic 1080p frames resident in HBM: "

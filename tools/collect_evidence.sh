@@ -8,17 +8,17 @@ root=${GRAFT_REPO_ROOT:-$(pwd)}
 out=$root/gpurun_out/evidence
 mkdir -p $out/$(dirname $tag)
 cd $root
-python3 bench.py --steps 30 --warmup 5 > $out/${tag}_bench.json 2> $out/${tag}_bench.err
+python3 bench.py --full --steps 30 --warmup 5 > $out/${tag}_bench.json 2> $out/${tag}_bench.err
 cd /tmp && export TMPDIR=/tmp
 # the headline kernel table comes from the timed chain ALONE (--no-extras --no-cpu-baseline): the extras launch the same kernels from
 # the contour code, on two streams and on other inputs, and their durations must not be averaged into the chain's
-rocprofv3 --kernel-trace --stats --output-format csv -d $out/ks -o ks -- python3 $root/bench.py --steps 30 --warmup 5 --no-cpu-baseline --no-extras > /dev/null 2>&1
+rocprofv3 --kernel-trace --stats --output-format csv -d $out/ks -o ks -- python3 $root/bench.py --full --steps 30 --warmup 5 --no-cpu-baseline --no-extras > /dev/null 2>&1
 cp $(find $out/ks -name '*kernel_stats.csv' | head -1) $out/${tag}_kernel_stats.csv
 # (and the same with the extras, under its own name: the kernels of the module bodies, the contour code and the crowded-frame path)
-rocprofv3 --kernel-trace --stats --output-format csv -d $out/kx -o kx -- python3 $root/bench.py --steps 10 --warmup 2 --no-cpu-baseline > /dev/null 2>&1
+rocprofv3 --kernel-trace --stats --output-format csv -d $out/kx -o kx -- python3 $root/bench.py --full --steps 10 --warmup 2 --no-cpu-baseline > /dev/null 2>&1
 cp $(find $out/kx -name '*kernel_stats.csv' | head -1) $out/${tag}_kernel_stats_with_extras.csv
 # counter passes see the timed chain only (--no-extras: no second instantiation of any kernel, no contour code reusing the labelling kernels)
-pmc_cmd="bench.py --steps 3 --warmup 1 --regions 1 --no-cpu-baseline --no-extras"
+pmc_cmd="bench.py --full --steps 3 --warmup 1 --regions 1 --no-cpu-baseline --no-extras"
 rocprofv3 --pmc FETCH_SIZE --output-format csv -d $out/pf -o pf -- python3 $root/$pmc_cmd > /dev/null 2>&1
 rocprofv3 --pmc WRITE_SIZE --output-format csv -d $out/pw -o pw -- python3 $root/$pmc_cmd > /dev/null 2>&1
 cd $root

@@ -30,6 +30,6 @@ python3 tools/exp_latency.py > $out/${tag}_latency.txt 2>&1
 python3 -m pytest tests/test_gpu_yolo_module.py -q -s -k rate > $out/${tag}_yolo.txt 2>&1
 # the N-rank code path of bench.py on one GPU (two ranks on cuda:0, gloo for the barrier and the MAX), with the host-fed leg every rank
 # runs for N > 1: not a scaling number
-python3 -m torch.distributed.run --nnodes=1 --nproc-per-node 2 --master-addr 127.0.0.1 --master-port 29517 bench.py --gpus 2 --rehearse-on-one-gpu \
+python3 -m torch.distributed.run --nnodes=1 --nproc-per-node 2 --master-addr 127.0.0.1 --master-port 29517 bench.py --full --gpus 2 --rehearse-on-one-gpu \
     --no-cpu-baseline --steps 20 2> $out/${tag}_rehearse.err | grep '^{"metric"' > $out/${tag}_rehearse_2ranks_one_gpu.json
 tail -3 $out/${tag}_runtime.txt
