@@ -163,6 +163,7 @@ int vp_set_option(vp_ctx* ctx, int option, int value)
     if (option == VP_OPT_CCL_LEVELS && (value == 1 || value == 2)) { ctx->ccl_levels = value; return VP_OK; }
     if (option == VP_OPT_CCL_MERGE_CAP && value >= -1) { ctx->ccl_mcap = value; return VP_OK; }
     if (option == VP_OPT_FLAT_OPS && (value == 0 || value == 1)) { ctx->flat_ops = value; return VP_OK; }
+    if (option == VP_OPT_HOUGH_LDS && (value == 0 || value == 1)) { ctx->hough_global = !value; return VP_OK; }
     return vp_fail(ctx, VP_ERR_INVALID, "vp_set_option");
 }
 
@@ -1805,6 +1806,61 @@ int vp_canny_u8(vp_ctx* ctx, const uint8_t* src, int w, int h, int cn, double t1
     VP_TRY(vpk_canny_u8(ctx, d_src, w, h, cn, low, high, d_dst));
     VP_TRY(d2h(ctx, dst, d_dst, npx));
     return vp_synchronize(ctx);
+}
+
+// canny -> find_lines without leaving HBM: the same kernels as vp_canny_u8 on a device image; enqueued, not synchronised
+int vp_canny_u8_dev(vp_ctx* ctx, const uint8_t* d_src, size_t src_stride, int w, int h, int cn, double t1, double t2, uint8_t* d_dst)
+{
+    VP_TRY(check_ctx(ctx));
+    if (!d_src || !d_dst || w <= 0 || h <= 0 || h > 65535 || (size_t)w * h > ((size_t)1 << 30) || cn < 1 || cn > 4 || src_stride < (size_t)w * cn ||
+        !std::isfinite(t1) || !std::isfinite(t2))
+        return vp_fail(ctx, VP_ERR_INVALID, "vp_canny_u8_dev arguments");
+    if (t1 > t2) std::swap(t1, t2);
+    const int low = (int)std::floor(std::min(std::max(t1, -1.0), 1e9)), high = (int)std::floor(std::min(std::max(t2, -1.0), 1e9));
+    const size_t npx = (size_t)w * h;
+    const bool packed = src_stride == (size_t)w * cn;
+    VP_TRY(vp_ws_reserve(ctx, (packed ? 0 : vp_align(npx * cn)) + vp_canny_ws_bytes(w, h) + 1024));
+    const uint8_t* src = d_src;
+    if (!packed) {
+        TAKE(d_pk, uint8_t*, npx * cn);
+        VP_HIP(ctx, hipMemcpy2DAsync(d_pk, (size_t)w * cn, d_src, src_stride, (size_t)w * cn, h, hipMemcpyDeviceToDevice, ctx->stream));
+        src = d_pk;
+    }
+    return vpk_canny_u8(ctx, src, w, h, cn, low, high, d_dst);
+}
+
+static int hough_args(vp_ctx* ctx, const void* src, int w, int h, float* lines, int max_lines, int* n_lines)
+{
+    if (!src || !n_lines || w <= 0 || h <= 0 || w > 65535 || h > 65535 || max_lines < 0 || (max_lines > 0 && !lines))
+        return vp_fail(ctx, VP_ERR_INVALID, "hough lines arguments");
+    return VP_OK;
+}
+
+int vp_hough_lines_u8(vp_ctx* ctx, const uint8_t* src, int w, int h, double rho, double theta, int threshold, double min_theta, double max_theta,
+                      float* lines, int max_lines, int* n_lines)
+{
+    VP_TRY(check_ctx(ctx));
+    VP_TRY(hough_args(ctx, src, w, h, lines, max_lines, n_lines));
+    return vp_hough_run(ctx, nullptr, src, w, (size_t)w * h, 1, w, h, rho, theta, threshold, min_theta, max_theta, lines, max_lines, n_lines);
+}
+
+int vp_hough_lines_dev(vp_ctx* ctx, const uint8_t* d_src, size_t src_stride, int w, int h, double rho, double theta, int threshold,
+                       double min_theta, double max_theta, float* lines, int max_lines, int* n_lines)
+{
+    VP_TRY(check_ctx(ctx));
+    VP_TRY(hough_args(ctx, d_src, w, h, lines, max_lines, n_lines));
+    if (src_stride < (size_t)w) return vp_fail(ctx, VP_ERR_INVALID, "src_stride");
+    return vp_hough_run(ctx, d_src, nullptr, src_stride, src_stride * h, 1, w, h, rho, theta, threshold, min_theta, max_theta, lines, max_lines, n_lines);
+}
+
+int vp_hough_lines_batch_dev(vp_ctx* ctx, const uint8_t* d_src, size_t src_stride, size_t frame_stride, int n, int w, int h, double rho,
+                             double theta, int threshold, double min_theta, double max_theta, float* lines, int max_lines, int* n_lines)
+{
+    VP_TRY(check_ctx(ctx));
+    VP_TRY(hough_args(ctx, d_src, w, h, lines, max_lines, n_lines));
+    if (n <= 0 || n > 65535 || src_stride < (size_t)w || (n > 1 && frame_stride < src_stride * (h - 1) + w))
+        return vp_fail(ctx, VP_ERR_INVALID, "vp_hough_lines_batch_dev strides / frame count");
+    return vp_hough_run(ctx, d_src, nullptr, src_stride, frame_stride, n, w, h, rho, theta, threshold, min_theta, max_theta, lines, max_lines, n_lines);
 }
 
 int vp_warp_affine_u8(vp_ctx* ctx, const uint8_t* src, int w, int h, int cn, const double* m23, int flags, int border_mode,

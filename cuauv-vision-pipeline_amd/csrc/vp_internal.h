@@ -67,6 +67,7 @@ struct vp_ctx {
     void* c3_acc;                 // crowded-frame labelling: accumulators of components that span strips, all empty between calls (vp_ccl.hip)
     size_t c3_acc_bytes;
     int c3_acc_dirty;             // a call was cut short after its labelling launch: reinitialise before the next use
+    int hough_global;             // 1: every Hough vote is a global atomic (VP_OPT_HOUGH_LDS 0); 0 (default): rows counted in LDS where they fit
     int flat_ops;                 // 1 (default): the per-operator kernels take their 16-px-per-lane forms when rows are packed and pointers aligned; 0: always the generic kernels (tests)
     int ccl_mcap;                 // components per frame the merge block accepts (-1: its LDS capacity); tests lower it to force the fallback
     vp_prof prof;
@@ -143,6 +144,11 @@ int vpk_hist_u8(vp_ctx* ctx, const uint8_t* d_src, size_t n, u32* d_hist);   // 
 int vpk_adaptive_threshold_mean(vp_ctx* ctx, const uint8_t* d_src, int w, int h, int imax, int idelta, int inv, int block, uint16_t* d_tmp, uint8_t* d_dst);
 size_t vp_canny_ws_bytes(int w, int h);
 int vpk_canny_u8(vp_ctx* ctx, const uint8_t* d_src, int w, int h, int cn, int low, int high, uint8_t* d_dst);
+// ---- Hough lines (vp_hough.hip) ----------------------------------------------------------------------
+// n frames of w x h u8 at d_src (row stride, frame stride; or one packed host image at h_src, staged in the workspace): lines of frame f
+// -> lines + f * max_lines * 2 (host), true counts -> n_lines; synchronises.  Checks beyond rho / theta / min_theta / max_theta are the caller's.
+int vp_hough_run(vp_ctx* ctx, const uint8_t* d_src, const uint8_t* h_src, size_t stride, size_t fstride, int n, int w, int h, double rho, double theta, int threshold,
+                 double min_theta, double max_theta, float* lines, int max_lines, int* n_lines);
 void vp_gaussian_taps(int n, double sigma, uint16_t* out);   // n odd, <= 511
 int vpk_gaussian_blur(vp_ctx* ctx, const uint8_t* d_src, int w, int h, int cn, const uint16_t* d_taps, int kw, int kh, uint16_t* d_tmp, uint8_t* d_dst);
 

@@ -26,6 +26,7 @@ OPT_CHAIN_STREAMS = 1
 OPT_CCL_LEVELS = 2
 OPT_CCL_MERGE_CAP = 3
 OPT_FLAT_OPS = 4
+OPT_HOUGH_LDS = 5
 PROF_KERNELS = 15
 
 
@@ -147,6 +148,13 @@ _SIGS = {
     "vp_memcpy_h2d_async": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t]),
     "vp_wait_uploads": (C.c_int, [C.c_void_p]),
     "vp_memcpy_d2h": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t]),
+    "vp_canny_u8_dev": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_int, C.c_int, C.c_int, C.c_double, C.c_double, C.c_void_p]),
+    "vp_hough_lines_u8": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_double, C.c_double, C.c_int, C.c_double, C.c_double,
+                                    C.c_void_p, C.c_int, C.POINTER(C.c_int)]),
+    "vp_hough_lines_dev": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_int, C.c_int, C.c_double, C.c_double, C.c_int, C.c_double,
+                                     C.c_double, C.c_void_p, C.c_int, C.POINTER(C.c_int)]),
+    "vp_hough_lines_batch_dev": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_size_t, C.c_int, C.c_int, C.c_int, C.c_double, C.c_double,
+                                           C.c_int, C.c_double, C.c_double, C.c_void_p, C.c_int, C.c_void_p]),
 }
 
 

@@ -27,6 +27,7 @@ CHAIN_APPROX_NONE, CHAIN_APPROX_SIMPLE = 1, 2
 CC_STAT_LEFT, CC_STAT_TOP, CC_STAT_WIDTH, CC_STAT_HEIGHT, CC_STAT_AREA = 0, 1, 2, 3, 4
 CV_8U = 0
 CV_32S = 4
+CV_PI = math.pi
 
 
 class UMat:   # only so that `from cv2 import UMat` and isinstance checks work
@@ -469,6 +470,18 @@ def Canny(image, threshold1, threshold2, apertureSize=3, L2gradient=False):
     _vp.check(_vp.lib().vp_canny_u8(ctx.handle, _vp.ptr(image), image.shape[1], image.shape[0], cn, float(threshold1), float(threshold2),
                                     _vp.ptr(out)), ctx.handle)
     return out
+
+
+def HoughLines(image, rho, theta, threshold, lines=None, srn=0, stn=0, min_theta=0, max_theta=CV_PI):
+    """cv2.HoughLines (utils/feature.py:209) in cv2's positional order: (N, 1, 2) float32 (rho, theta), or None when nothing is found.
+    The multi-scale variant (srn or stn non-zero) is outside the accelerated path."""
+    if srn or stn:
+        raise error("HoughLines: the multi-scale transform (srn / stn != 0) is outside the accelerated path")
+    if not (rho > 0 and theta > 0):
+        raise error("HoughLines: rho and theta must be positive")
+    if max_theta < min_theta:
+        raise error("HoughLines: max_theta must be greater than min_theta")
+    return _feature.hough_lines(image, rho, theta, threshold, min_theta, max_theta)
 
 
 def drawContours(image, contours, contourIdx, color, thickness=1):

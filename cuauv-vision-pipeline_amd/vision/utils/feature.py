@@ -158,7 +158,19 @@ min_enclosing_ellipse = _outside_path("min_enclosing_ellipse")
 
 
 def canny(mat: np.ndarray, lower: int, upper: int) -> np.ndarray:
-    """utils/feature.py:43-66 (cv2.Canny with the default 3x3 aperture and L1 gradient) on the GPU (libvp vp_canny_u8)."""
+    """utils/feature.py:43-66 (cv2.Canny with the default 3x3 aperture and L1 gradient) on the GPU (libvp vp_canny_u8).  A device image
+    gives a device image (vp_canny_u8_dev), so that canny -> find_lines never visits the host; a numpy image gives numpy."""
+    mat = as_mat(mat)
+    if isinstance(mat, DeviceMat):
+        ctx = _vp.default_context()
+        src = device_image(ctx, mat, 0)
+        h, w = src.shape[:2]
+        cn = 1 if src.ndim == 2 else src.shape[2]
+        if cn > 4:
+            raise ValueError("canny: at most 4 channels")
+        out = DeviceMat(ctx, (h, w), binary=True)
+        _vp.check(_vp.lib().vp_canny_u8_dev(ctx.handle, src.dev_ptr, w * cn, w, h, cn, float(lower), float(upper), out.dev_ptr), ctx.handle)
+        return out
     from vision import cv2_facade
     return cv2_facade.Canny(mat, lower, upper)
 
@@ -169,10 +181,68 @@ def simple_canny(mat: np.ndarray, sigma: float = 0.33, use_mean: bool = False) -
     lower = int(max(0, (1.0 - sigma) * mid))
     upper = int(min(255, (1.0 + sigma) * mid))
     return canny(mat, lower, upper)
+# Outside the path on purpose: cv2.HoughLinesP (find_line_segments) draws its points in the order of a seeded RNG and removes each
+# segment's votes before the next draw, a serial algorithm by definition; cv2.HoughCircles (find_circles) and cv2.goodFeaturesToTrack
+# (find_corners) go through OpenCV's SIMD float paths, which cannot be restated bit for bit.
 find_corners = _outside_path("find_corners")
 find_circles = _outside_path("find_circles")
-find_lines = _outside_path("find_lines")
 find_line_segments = _outside_path("find_line_segments")
+
+_lines_cap = threading.local()
+
+
+def hough_lines(mat, rho: float, theta: float, threshold: int, min_theta: float = 0.0, max_theta: float = np.pi):
+    """cv2.HoughLines(mat, rho, theta, threshold, min_theta=min_theta, max_theta=max_theta) on the GPU (libvp vp_hough_lines_*):
+    (N, 1, 2) float32 (rho, theta) in cv2's order, or None when no line is found.  A device image is read where it is."""
+    mat = as_mat(mat)
+    ctx = _vp.default_context()
+    if isinstance(mat, DeviceMat):
+        src = device_image(ctx, mat, 1)
+        h, w = src.shape
+    else:
+        if not isinstance(mat, np.ndarray) or mat.dtype != np.uint8:
+            raise TypeError("expected a uint8 single-channel image")
+        if mat.ndim == 3 and mat.shape[2] == 1:
+            mat = mat[:, :, 0]
+        if mat.ndim != 2 or mat.size == 0:
+            raise ValueError("expected a non-empty (h, w) image")
+        mat = np.ascontiguousarray(mat)
+        h, w = mat.shape
+        src = None
+    cap = getattr(_lines_cap, "n", 1024)
+    while True:
+        out = np.empty((max(cap, 1), 1, 2), np.float32)
+        n = _vp.C.c_int(0)
+        if src is not None:
+            _vp.check(_vp.lib().vp_hough_lines_dev(ctx.handle, src.dev_ptr, w, w, h, float(rho), float(theta), int(threshold), float(min_theta),
+                                                   float(max_theta), _vp.ptr(out), cap, _vp.C.byref(n)), ctx.handle)
+        else:
+            _vp.check(_vp.lib().vp_hough_lines_u8(ctx.handle, _vp.ptr(mat), w, h, float(rho), float(theta), int(threshold), float(min_theta),
+                                                  float(max_theta), _vp.ptr(out), cap, _vp.C.byref(n)), ctx.handle)
+        if n.value <= cap:
+            break
+        cap = _lines_cap.n = n.value                   # the true count came back: once more with room for all of them
+    return out[:n.value].copy() if n.value else None
+
+
+def line_polar_to_cartesian(rho: float, theta: float) -> Tuple[int, int, int, int]:
+    """utils/feature.py:158-180: two points 1000 px either side of the foot of the normal.  The arithmetic stays in the dtype of the
+    arguments (float32 for what find_lines returns), as in the reference, and int() truncates."""
+    c, s = np.cos(theta), np.sin(theta)
+    px, py = c * rho, s * rho
+    return int(px + 1000 * (-s)), int(py + 1000 * c), int(px - 1000 * (-s)), int(py - 1000 * c)
+
+
+def find_lines(mat: np.ndarray, rho: float, theta: float, threshold: int):
+    """utils/feature.py:183-213 (cv2.HoughLines): (list of (x1, y1, x2, y2), list of (rho, theta) np.float32 pairs), strongest first."""
+    lines = hough_lines(mat, rho, theta, threshold)
+    cartesian, polar = [], []
+    if lines is not None:
+        for line in lines:
+            r, t = line[0]
+            cartesian.append(line_polar_to_cartesian(r, t))
+            polar.append((r, t))
+    return cartesian, polar
 
 
 def find_contours(mat: np.ndarray, mode: int = _vp.RETR_EXTERNAL, method: int = _vp.CHAIN_APPROX_SIMPLE, with_holes: bool = False):

@@ -68,8 +68,10 @@ int vp_synchronize(vp_ctx* ctx);
  * VP_OPT_CCL_MERGE_CAP (-1 = capacity of the merge block, or a smaller count): strip components per frame above which a frame
  * is handed to the one-level kernels (test hook: 0 sends every non-empty frame there).
  * VP_OPT_FLAT_OPS (0 or 1, default 1): the per-operator kernels (vp_cvt_color_*, vp_inrange_u8_*) use their 16-pixels-per-lane forms
- * whenever rows are packed and pointers 16-B aligned; 0 forces the generic one-pixel-per-thread kernels (the tests run both). */
-enum { VP_OPT_CHAIN_STREAMS = 1, VP_OPT_CCL_LEVELS = 2, VP_OPT_CCL_MERGE_CAP = 3, VP_OPT_FLAT_OPS = 4 };
+ * whenever rows are packed and pointers 16-B aligned; 0 forces the generic one-pixel-per-thread kernels (the tests run both).
+ * VP_OPT_HOUGH_LDS (0 or 1, default 1): the Hough vote counts accumulator rows in LDS and flushes them with global atomics where a
+ * row fits the block's LDS budget; 0 makes every vote a global atomic.  Results are identical. */
+enum { VP_OPT_CHAIN_STREAMS = 1, VP_OPT_CCL_LEVELS = 2, VP_OPT_CCL_MERGE_CAP = 3, VP_OPT_FLAT_OPS = 4, VP_OPT_HOUGH_LDS = 5 };
 int vp_set_option(vp_ctx* ctx, int option, int value);
 /* HIP-event stopwatch on the context's stream (bench.py: roofline.achieved). */
 int vp_timer_start(vp_ctx* ctx);
@@ -332,6 +334,24 @@ int vp_adaptive_threshold_mean_u8(vp_ctx* ctx, const uint8_t* src_host, int w, i
  * (utils/feature.py:43-101 canny / simple_canny): Sobel derivatives, non-maximum suppression with OpenCV's integer direction test,
  * hysteresis as connected components of the surviving pixels that hold a pixel above the high threshold.  dst: (h, w) 0 / 255. */
 int vp_canny_u8(vp_ctx* ctx, const uint8_t* src_host, int w, int h, int cn, double threshold1, double threshold2, uint8_t* dst_host);
+/* vp_canny_u8 on a device image (row stride src_stride bytes) into a packed device image; enqueued on the context's stream, not
+ * synchronised, so that canny -> find_lines (utils/feature.py:43-66, :183-213) never leaves HBM. */
+int vp_canny_u8_dev(vp_ctx* ctx, const uint8_t* src_dev, size_t src_stride, int w, int h, int cn, double threshold1, double threshold2,
+                    uint8_t* dst_dev);
+/* utils/feature.py:183-213 `find_lines` (cv2.HoughLines(image, rho, theta, threshold, srn=0, stn=0, min_theta, max_theta)): the
+ * standard Hough transform of OpenCV 4.x HoughLinesStandard on a single-channel 8-bit image, non-zero = edge pixel.  Lines come back
+ * as (rho, theta) float pairs in cv2's order (votes descending, then accumulator cell ascending); at most max_lines are written,
+ * *n_lines is always the true count (a caller with too small a buffer learns the size it needs).  VP_ERR_INVALID for rho <= 0,
+ * theta <= 0 or max_theta < min_theta; VP_ERR_UNSUPPORTED for accumulators above 2^28 cells.  Synchronises. */
+int vp_hough_lines_u8(vp_ctx* ctx, const uint8_t* src_host, int w, int h, double rho, double theta, int threshold, double min_theta,
+                      double max_theta, float* lines_host, int max_lines, int* n_lines);
+int vp_hough_lines_dev(vp_ctx* ctx, const uint8_t* src_dev, size_t src_stride, int w, int h, double rho, double theta, int threshold,
+                       double min_theta, double max_theta, float* lines_host, int max_lines, int* n_lines);
+/* n equal-shape device frames (frame f at src_dev + f * frame_stride) in one launch sequence: frame f's lines at
+ * lines_host + 2 * f * max_lines, its true count in n_lines[f]. */
+int vp_hough_lines_batch_dev(vp_ctx* ctx, const uint8_t* src_dev, size_t src_stride, size_t frame_stride, int n, int w, int h, double rho,
+                             double theta, int threshold, double min_theta, double max_theta, float* lines_host, int max_lines,
+                             int* n_lines);
 /* cv2.warpAffine(src, M, (dst_w, dst_h), flags, borderMode, borderValue) with bilinear interpolation on 8-bit images, cn = 1..4
  * (modules/preprocessor.py:130-135 rotate with BORDER_REPLICATE, :145-149 translate; utils/transform.py:180-210).  m23: the 2x3
  * matrix, row-major doubles, mapping source to destination unless VP_WARP_INVERSE_MAP is set.  OpenCV's classical fixed-point path
