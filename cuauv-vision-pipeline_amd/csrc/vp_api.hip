@@ -44,6 +44,12 @@ int vp_get_tables(uint16_t* gamma, uint16_t* cbrt_tab, int32_t* sdiv, int32_t* h
     return VP_OK;
 }
 
+int vp_get_lab_inv_tables(uint16_t* yf, int32_t* ab_xz, uint16_t* inv_gamma, int32_t* coeffs)
+{
+    vp_host_lab_inv_tables(yf, ab_xz, inv_gamma, coeffs);
+    return VP_OK;
+}
+
 int vp_device_count(void)
 {
     int n = 0;
@@ -117,6 +123,23 @@ vp_ctx* vp_create(int device)
     ctx->tab.hdiv = (const int32_t*)(base + 512 + 4096 + 1024);
     ctx->cb_folds_own = (u32*)(base + bytes);       // a word of the context's own: workspace pointers do not survive a later call
     hipMemset(ctx->cb_folds_own, 0, 4);
+    // Lab -> BGR tables: abToXZ_b i32[VP_LAB_AB_TAB] | LabToYF_b u16[512] | inverse gamma as bytes [4096]
+    {
+        std::vector<int32_t> abxz(VP_LAB_AB_TAB);
+        std::vector<uint16_t> yf(512), invg16(4096);
+        std::vector<uint8_t> invg(4096);
+        vp_host_lab_inv_tables(yf.data(), abxz.data(), invg16.data(), nullptr);
+        for (int i = 0; i < 4096; i++) invg[i] = (uint8_t)invg16[i];
+        const size_t nab = (size_t)VP_LAB_AB_TAB * 4;
+        if ((e = hipMalloc(&ctx->d_labinv, nab + 1024 + 4096)) != hipSuccess) { vp_fail(nullptr, VP_ERR_NOMEM, "hipMalloc Lab -> BGR tables", e); vp_destroy(ctx); return nullptr; }
+        uint8_t* lb = (uint8_t*)ctx->d_labinv;
+        hipMemcpy(lb, abxz.data(), nab, hipMemcpyHostToDevice);
+        hipMemcpy(lb + nab, yf.data(), 1024, hipMemcpyHostToDevice);
+        if ((e = hipMemcpy(lb + nab + 1024, invg.data(), 4096, hipMemcpyHostToDevice)) != hipSuccess) { vp_fail(nullptr, VP_ERR_HIP, "Lab -> BGR table upload", e); vp_destroy(ctx); return nullptr; }
+        ctx->tab.abxz = (const int32_t*)lb;
+        ctx->tab.yf = (const uint16_t*)(lb + nab);
+        ctx->tab.invg = lb + nab + 1024;
+    }
     return ctx;
 }
 
@@ -135,6 +158,7 @@ int vp_destroy(vp_ctx* ctx)
     }
     if (ctx->hstage) hipHostFree(ctx->hstage);
     if (ctx->d_tables) hipFree(ctx->d_tables);
+    if (ctx->d_labinv) hipFree(ctx->d_labinv);
     hipEventDestroy(ctx->ev0);
     hipEventDestroy(ctx->ev1);
     for (int i = 0; i < 4; i++) { hipStreamDestroy(ctx->aux[i]); hipEventDestroy(ctx->ev_join[i]); }
@@ -529,7 +553,7 @@ int vp_cvt_color_u8(vp_ctx* ctx, int code, const uint8_t* src, size_t src_stride
 {
     VP_TRY(check_ctx(ctx));
     if (!src || w <= 0 || h <= 0 || h > 65535) return vp_fail(ctx, VP_ERR_INVALID, "vp_cvt_color_u8 arguments");
-    if (code < VP_BGR2LAB || code > VP_BGR2HLS) return vp_fail(ctx, VP_ERR_INVALID, "conversion code");
+    if (code < VP_BGR2LAB || code > VP_LAB2BGR) return vp_fail(ctx, VP_ERR_INVALID, "conversion code");
     const int scn = code == VP_GRAY2BGR ? 1 : 3, dcn = code == VP_BGR2GRAY ? 1 : 3;
     if (src_stride < (size_t)w * scn) return vp_fail(ctx, VP_ERR_INVALID, "src_stride");
     const size_t npx = (size_t)w * h;
@@ -1077,7 +1101,7 @@ int vp_cvt_color_dev(vp_ctx* ctx, int code, const uint8_t* d_src, size_t src_str
 {
     VP_TRY(check_ctx(ctx));
     if (!d_src || w <= 0 || h <= 0 || h > 65535) return vp_fail(ctx, VP_ERR_INVALID, "vp_cvt_color_dev arguments");
-    if (code < VP_BGR2LAB || code > VP_BGR2HLS) return vp_fail(ctx, VP_ERR_INVALID, "conversion code");
+    if (code < VP_BGR2LAB || code > VP_LAB2BGR) return vp_fail(ctx, VP_ERR_INVALID, "conversion code");
     const int scn = code == VP_GRAY2BGR ? 1 : 3, dcn = code == VP_BGR2GRAY ? 1 : 3;
     if (src_stride < (size_t)w * scn) return vp_fail(ctx, VP_ERR_INVALID, "src_stride");
     uint8_t* dp[3] = {nullptr, nullptr, nullptr};
@@ -1861,6 +1885,48 @@ int vp_hough_lines_batch_dev(vp_ctx* ctx, const uint8_t* d_src, size_t src_strid
     if (n <= 0 || n > 65535 || src_stride < (size_t)w || (n > 1 && frame_stride < src_stride * (h - 1) + w))
         return vp_fail(ctx, VP_ERR_INVALID, "vp_hough_lines_batch_dev strides / frame count");
     return vp_hough_run(ctx, d_src, nullptr, src_stride, frame_stride, n, w, h, rho, theta, threshold, min_theta, max_theta, lines, max_lines, n_lines);
+}
+
+static int wb_args(vp_ctx* ctx, const void* src, size_t src_stride, int w, int h, int kernel_size, const void* dst)
+{
+    if (!src || !dst || w <= 0 || h <= 0 || h > 65535 || src_stride < (size_t)w * 3) return vp_fail(ctx, VP_ERR_INVALID, "white balance arguments");
+    if (kernel_size != VP_WB_GLOBAL_MEAN && (kernel_size < 1 || kernel_size % 2 == 0)) return vp_fail(ctx, VP_ERR_INVALID, "white balance: kernel size must be odd");
+    if (kernel_size > VP_WB_MAX_KERNEL) return vp_fail(ctx, VP_ERR_UNSUPPORTED, "white balance: kernel size above VP_WB_MAX_KERNEL");
+    return VP_OK;
+}
+
+// the means go through the workspace and come back only when asked for; the device forms stay asynchronous otherwise
+static int wb_run(vp_ctx* ctx, const uint8_t* d_src, size_t stride, int w, int h, int kernel_size, uint8_t* d_dst, float* ab_mean_out)
+{
+    TAKE(d_mean, float*, 8);
+    VP_TRY(vpk_white_balance(ctx, d_src, stride, w, h, kernel_size, d_dst, d_mean));
+    if (ab_mean_out && kernel_size == VP_WB_GLOBAL_MEAN) {
+        VP_TRY(d2h(ctx, ab_mean_out, d_mean, 8));
+        return vp_synchronize(ctx);
+    }
+    return VP_OK;
+}
+
+int vp_white_balance_u8(vp_ctx* ctx, const uint8_t* src, size_t src_stride, int w, int h, int kernel_size, uint8_t* dst, float* ab_mean_out)
+{
+    VP_TRY(check_ctx(ctx));
+    VP_TRY(wb_args(ctx, src, src_stride, w, h, kernel_size, dst));
+    const size_t npx = (size_t)w * h;
+    VP_TRY(vp_ws_reserve(ctx, 2 * vp_align(npx * 3) + vp_align(8) + vp_white_balance_ws_bytes(w, h, kernel_size) + 4096));
+    TAKE(d_src, uint8_t*, npx * 3);
+    TAKE(d_dst, uint8_t*, npx * 3);
+    VP_TRY(h2d_rows(ctx, d_src, (size_t)w * 3, src, src_stride, (size_t)w * 3, h));
+    VP_TRY(wb_run(ctx, d_src, (size_t)w * 3, w, h, kernel_size, d_dst, ab_mean_out));
+    VP_TRY(d2h(ctx, dst, d_dst, npx * 3));
+    return vp_synchronize(ctx);
+}
+
+int vp_white_balance_dev(vp_ctx* ctx, const uint8_t* d_src, size_t src_stride, int w, int h, int kernel_size, uint8_t* d_dst, float* ab_mean_out)
+{
+    VP_TRY(check_ctx(ctx));
+    VP_TRY(wb_args(ctx, d_src, src_stride, w, h, kernel_size, d_dst));
+    VP_TRY(vp_ws_reserve(ctx, vp_align(8) + vp_white_balance_ws_bytes(w, h, kernel_size) + 4096));
+    return wb_run(ctx, d_src, src_stride, w, h, kernel_size, d_dst, ab_mean_out);
 }
 
 int vp_warp_affine_u8(vp_ctx* ctx, const uint8_t* src, int w, int h, int cn, const double* m23, int flags, int border_mode,

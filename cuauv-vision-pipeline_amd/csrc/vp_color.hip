@@ -8,42 +8,12 @@
 // writes the 0/255 mask (1 B/px) plus a bit-packed copy (1/8 B/px) that the morphology and CCL
 // kernels consume.  The arithmetic is OpenCV's 8-bit fixed point; the
 // LUTs live in LDS.  HBM-bound: 4.125 B/px.
-#include "vp_internal.h"
+#include "vp_lab.h"
 #include <algorithm>
 #include <cstdlib>
 #include <cstring>
 
-#define LAB_LSHIFT (-1336934)  // -((16*255*32768 + 50)/100)
-
-struct LabLds { uint16_t gamma[256]; uint16_t cbrt[2048]; };
 struct HsvLds { int32_t sdiv[256]; int32_t hdiv[256]; };
-
-__device__ __forceinline__ int clamp255(int v) { return v < 0 ? 0 : (v > 255 ? 255 : v); }
-// signed 24-bit multiply, low 32 bits of the product (full rate; v_mul_lo_u32 runs at a quarter of it).  Spelled as the instruction:
-// __mul24 becomes it only where the compiler can bound both operands itself.
-__device__ __forceinline__ int mul_i24(int a, int b)
-{
-    int r;
-    asm("v_mul_i32_i24 %0, %1, %2" : "=v"(r) : "v"(a), "v"(b));
-    return r;
-}
-
-// NEED bit0 = L, bit1 = a, bit2 = b
-template <int NEED>
-__device__ __forceinline__ void lab_px(const LabLds& t, int b, int g, int r, int& L, int& A, int& Bc)
-{
-    const int R = t.gamma[r], G = t.gamma[g], B = t.gamma[b];
-    const int fY = t.cbrt[(R * 871 + G * 2929 + B * 296 + 2048) >> 12];
-    if (NEED & 1) L = clamp255((296 * fY + LAB_LSHIFT + 16384) >> 15);
-    if (NEED & 2) {
-        const int fX = t.cbrt[(R * 1777 + G * 1541 + B * 778 + 2048) >> 12];
-        A = clamp255((500 * (fX - fY) + (128 << 15) + 16384) >> 15);
-    }
-    if (NEED & 4) {
-        const int fZ = t.cbrt[(R * 73 + G * 448 + B * 3575 + 2048) >> 12];
-        Bc = clamp255((200 * (fY - fZ) + (128 << 15) + 16384) >> 15);
-    }
-}
 
 __device__ __forceinline__ void hsv_px(const HsvLds& t, int b, int g, int r, int& H, int& S, int& V)
 {
@@ -135,13 +105,16 @@ template <>
 struct ModeLds<VP_BGR2YCRCB> { typedef int type; };
 template <>
 struct ModeLds<VP_BGR2HLS> { typedef int type; };
+template <>
+struct ModeLds<VP_LAB2BGR> { typedef LabInvLds type; };
 
 template <int MODE>
 __device__ __forceinline__ void load_lds(typename ModeLds<MODE>::type& s, const vp_tables& tab)
 {
     if constexpr (MODE == VP_BGR2LAB) {
-        for (int i = threadIdx.x; i < 256; i += blockDim.x) s.gamma[i] = tab.gamma[i];
-        for (int i = threadIdx.x; i < 2048; i += blockDim.x) s.cbrt[i] = tab.cbrt[i];
+        load_lab_lds(s, tab);
+    } else if constexpr (MODE == VP_LAB2BGR) {
+        load_labinv_lds(s, tab);
     } else if constexpr (MODE == VP_BGR2HSV) {
         for (int i = threadIdx.x; i < 256; i += blockDim.x) { s.sdiv[i] = tab.sdiv[i]; s.hdiv[i] = tab.hdiv[i]; }
     }
@@ -437,6 +410,7 @@ __global__ __launch_bounds__(256) void k_cvt_color(const uint8_t* __restrict__ s
         if constexpr (CODE == VP_BGR2LAB) lab_px<7>(s, b, g, r, c0, c1, c2);
         else if constexpr (CODE == VP_BGR2YCRCB) ycrcb_px(b, g, r, c0, c1, c2);
         else if constexpr (CODE == VP_BGR2HLS) hls_px(b, g, r, c0, c1, c2);
+        else if constexpr (CODE == VP_LAB2BGR) lab2bgr_px(s, tab.abxz, b, g, r, c0, c1, c2);   // (b, g, r) hold (L, a, b) here
         else hsv_px(s, b, g, r, c0, c1, c2);
         if (dst) { dst[3 * o] = (uint8_t)c0; dst[3 * o + 1] = (uint8_t)c1; dst[3 * o + 2] = (uint8_t)c2; }
         if (p0) p0[o] = (uint8_t)c0;
@@ -483,6 +457,7 @@ __global__ __launch_bounds__(256) void k_cvt_color_flat(const uint8_t* __restric
             else if constexpr (CODE == VP_BGR2LAB) lab_px<NEED>(s, bb, gg, rr, c0, c1, c2);
             else if constexpr (CODE == VP_BGR2YCRCB) ycrcb_px(bb, gg, rr, c0, c1, c2);
             else if constexpr (CODE == VP_BGR2HLS) hls_px(bb, gg, rr, c0, c1, c2);
+            else if constexpr (CODE == VP_LAB2BGR) lab2bgr_px(s, tab.abxz, bb, gg, rr, c0, c1, c2);
             else hsv_px(s, bb, gg, rr, c0, c1, c2);
             a[k >> 2] |= (u32)c0 << (8 * (k & 3));
             b[k >> 2] |= (u32)c1 << (8 * (k & 3));
@@ -580,6 +555,7 @@ int vpk_cvt_color(vp_ctx* ctx, int code, const uint8_t* d_src, size_t stride, in
         case VP_BGR2GRAY: launch_cvt<VP_BGR2GRAY>(ctx, d_src, stride, w, h, d_dst, d_p0, d_p1, d_p2); break;
         case VP_BGR2YCRCB: launch_cvt<VP_BGR2YCRCB>(ctx, d_src, stride, w, h, d_dst, d_p0, d_p1, d_p2); break;
         case VP_BGR2HLS: launch_cvt<VP_BGR2HLS>(ctx, d_src, stride, w, h, d_dst, d_p0, d_p1, d_p2); break;
+        case VP_LAB2BGR: launch_cvt<VP_LAB2BGR>(ctx, d_src, stride, w, h, d_dst, d_p0, d_p1, d_p2); break;
         case VP_GRAY2BGR: {
             const size_t npx = (size_t)w * h, ngroups = npx / 16;
             const bool flat = ctx->flat_ops && (stride == (size_t)w || h == 1) && ngroups > 0 && aligned16(d_src) && aligned16(d_dst) && aligned16(d_p0) &&

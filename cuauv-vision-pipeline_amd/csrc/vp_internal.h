@@ -13,6 +13,9 @@ struct vp_tables {          // device copies of the OpenCV integer tables
     const uint16_t* cbrt;   // [2048] LabCbrtTab_b (indices 0..2040 are reachable)
     const int32_t* sdiv;    // [256]
     const int32_t* hdiv;    // [256]  hdiv_table180
+    const uint16_t* yf;     // [512]  LabToYF_b (Lab -> BGR)
+    const int32_t* abxz;    // [VP_LAB_AB_TAB] abToXZ_b
+    const uint8_t* invg;    // [4096] sRGBInvGammaTab_b (values <= 255, stored as bytes)
 };
 
 enum { VPK_COLOR = 0, VPK_MORPH, VPK_CCL_LOCAL, VPK_CCL_BOUNDARY, VPK_CCL_FLATTEN, VPK_CCL_RANK, VPK_CCL_BG, VPK_CCL_STATS,
@@ -31,6 +34,7 @@ struct vp_ctx {
     hipStream_t own_stream;
     hipEvent_t ev0, ev1;
     void* d_tables;
+    void* d_labinv;   // Lab -> BGR tables (tab.abxz / yf / invg)
     vp_tables tab;
     uint8_t* ws;      // grow-only device workspace, carved per call
     size_t ws_cap;
@@ -108,6 +112,7 @@ int vp_fail(vp_ctx* ctx, int code, const char* what, hipError_t e = hipSuccess);
 
 // ---- host-side table generation (vp_tables.cpp) ------------------------------------------
 void vp_host_tables(uint16_t* gamma, uint16_t* cbrt_tab, int32_t* sdiv, int32_t* hdiv180, int32_t* labC);
+void vp_host_lab_inv_tables(uint16_t* yf, int32_t* abxz, uint16_t* inv_gamma, int32_t* coeffs);
 
 // ---- colour kernels (vp_color.hip) ---------------------------------------------------------
 struct vp_range3 { int lo[3], hi[3]; int lo2, hi2; };   // lo2 / hi2: second interval of the hue test inside the HSV threshold kernels (vpk_color_thresh)
@@ -121,6 +126,9 @@ int vpk_inrange_u8(vp_ctx* ctx, const uint8_t* d_src, size_t stride, int w, int 
 int vpk_inrange_f32(vp_ctx* ctx, const float* d_src, size_t stride_bytes, int w, int h, float lo, float hi,
                     uint8_t* d_dst);
 int vpk_kth_f32(vp_ctx* ctx, const float* d_src, size_t n, size_t k, u32* d_hist, float* out);
+// white balance (vp_whitebal.hip): kernel_size VP_WB_GLOBAL_MEAN or an odd k; d_mean (nullable) receives the two global means
+int vpk_white_balance(vp_ctx* ctx, const uint8_t* d_src, size_t stride, int w, int h, int kernel_size, uint8_t* d_dst, float* d_mean);
+size_t vp_white_balance_ws_bytes(int w, int h, int kernel_size);
 int vpk_bgr2lab_f32(vp_ctx* ctx, const float* d_src, size_t npx, float* d_dst);
 int vpk_color_distance(vp_ctx* ctx, const uint8_t* p0, const uint8_t* p1, const uint8_t* p2, size_t npx,
                        const float* color, const float* wts, int skipmask, float* d2, uint8_t* sq);

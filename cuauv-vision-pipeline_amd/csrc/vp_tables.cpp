@@ -7,6 +7,8 @@
 #include <cmath>
 #include <cstdint>
 #include <cstring>
+#include "../../include/vp.h"
+#include "vp_lab_coeffs.h"
 
 static int round_even(double v) { return (int)std::nearbyint(v); }
 static int round_even(float v) { return (int)std::nearbyintf(v); }
@@ -69,4 +71,47 @@ void vp_host_tables(uint16_t* gamma, uint16_t* cbrt_tab, int32_t* sdiv, int32_t*
         const double white[3] = {0.950456, 1.0, 1.088754};
         for (int k = 0; k < 9; k++) labC[k] = round_even(4096.0 * m[k] / white[k / 3]);
     }
+}
+
+// Tables of the 8-bit Lab -> BGR conversion (color_lab.cpp initLabTabs + Lab2RGBinteger ctor).  Same evaluation rules as above:
+// LabToYF_b in binary32 statement by statement, the inverse gamma in binary64 (softdouble) rounded once to binary32 before the
+// scale by 255, abToXZ_b in C integer arithmetic (division truncates toward zero), the matrix in binary64 at compile time (vp_lab_coeffs.h).
+//   yf[2 L], yf[2 L + 1]   = y (Q14, 0..16384) and ify = f(y) (Q14, 2260..16384) of the 8-bit L
+//   abxz[i - VP_LAB_MIN_AB] = x or z (Q14) of the Q14 value i of f(x) / f(z), i in [VP_LAB_MIN_AB, VP_LAB_MIN_AB + VP_LAB_AB_TAB)
+//   inv_gamma[i]           = cvRound(255 * sRGB(i / 4096)), i < 4096
+//   coeffs[3 c + j]        = Q12 coefficient of x, y, z (j) in output channel c, c = 0 blue, 1 green, 2 red; white point folded in
+void vp_host_lab_inv_tables(uint16_t* yf, int32_t* abxz, uint16_t* inv_gamma, int32_t* coeffs)
+{
+    const int BASE = 1 << 14;
+    if (yf)
+        for (int i = 0; i < 256; i++) {
+            int y, ify;
+            if (i <= 20) {             // L <= 8: the linear segment, y = L / 903.3 = (i * 100 / 255) * 27 / 24389
+                y = round_even((float)(i * BASE * 20 * 9) / (float)(17 * 29 * 29 * 29));
+                ify = round_even((float)BASE * (16.0f / 116.0f + (float)(i * 5) / (float)(3 * 17 * 29)));
+            } else {                   // fy = (L + 16) / 116, y = fy^3
+                const float fy = (float)(i * 100 * BASE) / (float)(255 * 116) + (float)(16 * BASE) / 116.0f;
+                ify = round_even(fy);
+                y = round_even(fy * fy * fy / (float)(BASE * BASE));
+            }
+            yf[2 * i] = (uint16_t)y;
+            yf[2 * i + 1] = (uint16_t)ify;
+        }
+    if (abxz)
+        for (int i = VP_LAB_MIN_AB; i < VP_LAB_MIN_AB + VP_LAB_AB_TAB; i++) {
+            int v;
+            if (i <= 3390) v = i * 108 / 841 - BASE * 16 / 116 * 108 / 841;   // (f - 16/116) / 7.787; 6/29 * BASE = 3389.73
+            else v = i * i / BASE * i / BASE;                                  // f^3
+            abxz[i - VP_LAB_MIN_AB] = v;
+        }
+    if (inv_gamma) {
+        const double thr = 7827.0 / 2500000.0, low = 323.0 / 25.0, power = 12.0 / 5.0, xshift = 11.0 / 200.0;
+        for (int i = 0; i < 4096; i++) {
+            const double x = (double)((float)i * (1.0f / 4096.0f));
+            const float g = (float)(x <= thr ? x * low : std::pow(x, 1.0 / power) * (1.0 + xshift) - xshift);
+            inv_gamma[i] = (uint16_t)round_even(255.0f * g);
+        }
+    }
+    if (coeffs)
+        for (int k = 0; k < 9; k++) coeffs[k] = VP_LABINV_C[k];
 }

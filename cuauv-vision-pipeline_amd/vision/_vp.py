@@ -13,7 +13,9 @@ import numpy as np
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("VP_LIB") or os.path.join(os.path.dirname(_HERE), "lib", "libvp.so")   # VP_LIB: measurement builds (tools/build_probe.sh)
 
-BGR2LAB, BGR2HSV, BGR2GRAY, GRAY2BGR, HSV2BGR, BGR2YCRCB, BGR2HLS = 0, 1, 2, 3, 4, 5, 6
+BGR2LAB, BGR2HSV, BGR2GRAY, GRAY2BGR, HSV2BGR, BGR2YCRCB, BGR2HLS, LAB2BGR = 0, 1, 2, 3, 4, 5, 6, 7
+LAB_MIN_AB, LAB_AB_TAB = -8145, 36864
+WB_GLOBAL_MEAN, WB_MAX_KERNEL = 0, 4095
 CB_EQUALIZE_RGB, CB_RGB_CONTRAST, CB_HSV_CONTRAST, CB_HSI_CONTRAST, CB_EXTREMA_CLIPPING, CB_ADAPTIVE_CAST = 1, 2, 4, 8, 16, 32
 CB_DEFAULT = CB_EQUALIZE_RGB | CB_HSV_CONTRAST | CB_EXTREMA_CLIPPING
 MORPH_ERODE, MORPH_DILATE, MORPH_OPEN, MORPH_CLOSE, MORPH_GRADIENT = 0, 1, 2, 3, 4
@@ -75,6 +77,9 @@ _SIGS = {
     "vp_timer_start": (C.c_int, [C.c_void_p]),
     "vp_timer_stop": (C.c_int, [C.c_void_p, C.POINTER(C.c_float)]),
     "vp_get_tables": (C.c_int, [C.c_void_p] * 5),
+    "vp_get_lab_inv_tables": (C.c_int, [C.c_void_p] * 4),
+    "vp_white_balance_u8": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
+    "vp_white_balance_dev": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
     "vp_profile_begin": (C.c_int, [C.c_void_p, C.c_int]),
     "vp_profile_end": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
     "vp_profile_kernel_name": (C.c_char_p, [C.c_int]),
@@ -320,6 +325,16 @@ def get_tables():
     labc = np.zeros(9, np.int32)
     check(lib().vp_get_tables(ptr(gamma), ptr(cbrt), ptr(sdiv), ptr(hdiv), ptr(labc)))
     return gamma, cbrt, sdiv, hdiv, labc
+
+
+def get_lab_inv_tables():
+    """(yf (256, 2) u16, ab_xz i32[LAB_AB_TAB], inv_gamma u16[4096], coeffs (3, 3) i32 rows blue, green, red) - include/vp.h."""
+    yf = np.zeros(512, np.uint16)
+    abxz = np.zeros(LAB_AB_TAB, np.int32)
+    invg = np.zeros(4096, np.uint16)
+    coeffs = np.zeros(9, np.int32)
+    check(lib().vp_get_lab_inv_tables(ptr(yf), ptr(abxz), ptr(invg), ptr(coeffs)))
+    return yf.reshape(256, 2), abxz, invg, coeffs.reshape(3, 3)
 
 
 def make_chain_desc(width, height, color_mode, lo, hi, morph=(), ccl=1, numbering=CCL_BLOCK2X2, max_labels=256):

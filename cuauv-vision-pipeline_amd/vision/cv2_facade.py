@@ -19,6 +19,7 @@ from vision.utils import transform as _transform
 
 COLOR_BGR2LAB, COLOR_BGR2HSV, COLOR_BGR2GRAY, COLOR_GRAY2BGR, COLOR_HSV2BGR = 44, 40, 6, 8, 54     # cv2's own enum values
 COLOR_BGR2YCrCb, COLOR_BGR2YCR_CB, COLOR_BGR2HLS = 36, 36, 52
+COLOR_LAB2BGR = COLOR_Lab2BGR = 56
 COLOR_BGR2Luv, COLOR_BGR2LUV = 50, 50     # named by modules/preprocessor.py:76; see DESIGN.md section 7 for what the stand-in does with it
 MORPH_RECT, MORPH_CROSS, MORPH_ELLIPSE = 0, 1, 2
 MORPH_ERODE, MORPH_DILATE, MORPH_OPEN, MORPH_CLOSE, MORPH_GRADIENT = 0, 1, 2, 3, 4
@@ -44,7 +45,7 @@ class error(Exception):
 
 _CVT = {COLOR_BGR2LAB: _color.bgr_to_lab, COLOR_BGR2HSV: _color.bgr_to_hsv, COLOR_BGR2GRAY: _color.bgr_to_gray,
         COLOR_GRAY2BGR: _color.gray_to_bgr, COLOR_HSV2BGR: _color.hsv_to_bgr, COLOR_BGR2YCrCb: _color.bgr_to_ycrcb,
-        COLOR_BGR2HLS: _color.bgr_to_hls}
+        COLOR_BGR2HLS: _color.bgr_to_hls, COLOR_LAB2BGR: _color.lab_to_bgr}
 
 
 def cvtColor(src, code):

@@ -94,7 +94,7 @@ gray_to_bgr = _convert_colorspace(_vp.GRAY2BGR)
 bgr_to_hls = _convert_colorspace(_vp.BGR2HLS)
 bgr_to_ycrcb = _convert_colorspace(_vp.BGR2YCRCB)
 bgr_to_luv = _unsupported("bgr_to_luv")
-lab_to_bgr = _unsupported("lab_to_bgr")
+lab_to_bgr = _convert_colorspace(_vp.LAB2BGR)
 hsv_to_bgr = _convert_colorspace(_vp.HSV2BGR)
 
 
@@ -338,5 +338,45 @@ def mask_from_labels(labels: np.ndarray, centers: np.ndarray) -> List[np.ndarray
 
 
 mask_from_labels_target_color = _outside_path("mask_from_labels_target_color")
-white_balance_bgr = _outside_path("white_balance_bgr")
-white_balance_bgr_blur = _outside_path("white_balance_bgr_blur")
+
+
+def _white_balance(bgr_img, kernel_size, ab_mean_out=None):
+    """libvp vp_white_balance_u8 / _dev: numpy in -> numpy out; a DeviceMat (or the lazy mode) -> a DeviceMat that stays in HBM."""
+    mat = as_mat(bgr_img)
+    out_mean = np.zeros(2, np.float32) if ab_mean_out is not None else None
+    ctx = _vp.default_context()
+    if lazy_enabled() or isinstance(mat, DeviceMat):
+        up = []
+        src = device_image(ctx, mat, 3, pending=up)
+        try:
+            h, w = src.shape[:2]
+            dst = DeviceMat(ctx, (h, w, 3))
+            _vp.check(_vp.lib().vp_white_balance_dev(ctx.handle, src.dev_ptr, w * 3, w, h, int(kernel_size), dst.dev_ptr, _vp.ptr(out_mean)),
+                      ctx.handle)
+        finally:
+            finish_uploads(ctx, up)
+    else:
+        mat = _u8_image(mat, 3)
+        h, w = mat.shape[:2]
+        dst = np.empty((h, w, 3), np.uint8)
+        _vp.check(_vp.lib().vp_white_balance_u8(ctx.handle, _vp.ptr(mat), mat.strides[0], w, h, int(kernel_size), _vp.ptr(dst),
+                                                _vp.ptr(out_mean)), ctx.handle)
+    if ab_mean_out is not None:
+        ab_mean_out[:] = out_mean
+    return dst
+
+
+def white_balance_bgr(bgr_img, ab_mean_out=None):
+    """utils/color.py:370-378: a and b of the 8-bit Lab image moved so that their means (np.mean of the float32 planes) become 128,
+    cast back with numpy's astype(np.uint8) (truncation, low 8 bits), LAB2BGR.  ab_mean_out (optional float32[2]) receives the means."""
+    return _white_balance(bgr_img, _vp.WB_GLOBAL_MEAN, ab_mean_out)
+
+
+def white_balance_bgr_blur(bgr_img, kernel_size):
+    """utils/color.py:381-392: as white_balance_bgr with the k x k box mean (cv2.blur, BORDER_REPLICATE) in place of the global mean,
+    k = 2 * (kernel_size // 2) + 1; a negative kernel_size raises the facade's cv2.error (vision.cv2_facade.error), as cv2.blur does."""
+    k = 2 * (int(kernel_size) // 2) + 1
+    if k <= 0:                                    # the reference fails inside cv2.blur with cv2.error
+        from vision.cv2_facade import error
+        raise error(f"white_balance_bgr_blur: kernel size {k} is not positive")
+    return _white_balance(bgr_img, k)

@@ -33,7 +33,7 @@ extern "C" {
 typedef struct vp_ctx vp_ctx;
 
 /* colour conversion codes (values are libvp's own, not cv2's) */
-enum { VP_BGR2LAB = 0, VP_BGR2HSV = 1, VP_BGR2GRAY = 2, VP_GRAY2BGR = 3, VP_HSV2BGR = 4, VP_BGR2YCRCB = 5, VP_BGR2HLS = 6 };
+enum { VP_BGR2LAB = 0, VP_BGR2HSV = 1, VP_BGR2GRAY = 2, VP_GRAY2BGR = 3, VP_HSV2BGR = 4, VP_BGR2YCRCB = 5, VP_BGR2HLS = 6, VP_LAB2BGR = 7 };
 /* morphology ops — utils/transform.py:80-164 */
 enum { VP_MORPH_ERODE = 0, VP_MORPH_DILATE = 1, VP_MORPH_OPEN = 2, VP_MORPH_CLOSE = 3, VP_MORPH_GRADIENT = 4 };
 /* structuring element shapes — cv2.MORPH_RECT / MORPH_CROSS / MORPH_ELLIPSE */
@@ -86,6 +86,13 @@ const char* vp_profile_kernel_name(int id);
 /* Copies of the integer tables the kernels use (for parity tests against the oracle):
  * gamma[256] u16, cbrt[3072] u16, sdiv[256] i32, hdiv180[256] i32, lab_coeffs[9] i32. */
 int vp_get_tables(uint16_t* gamma, uint16_t* cbrt_tab, int32_t* sdiv, int32_t* hdiv180, int32_t* lab_coeffs);
+/* Copies of the tables of the 8-bit Lab -> BGR conversion (VP_LAB2BGR and the white balance; OpenCV 4.x Lab2RGBinteger, each may be
+ * NULL): yf[512] u16 = (y, f(y)) in Q14 per 8-bit L; ab_xz[VP_LAB_AB_TAB] i32 = x (or z) in Q14 of the Q14 value
+ * VP_LAB_MIN_AB + i of f(x) (or f(z)); inv_gamma[4096] u16 = round(255 * sRGB(i / 4096)); coeffs[9] i32 = Q12 coefficients of
+ * (x, y, z), white point folded in, rows blue, green, red. */
+#define VP_LAB_MIN_AB (-8145)
+#define VP_LAB_AB_TAB 36864
+int vp_get_lab_inv_tables(uint16_t* yf, int32_t* ab_xz, uint16_t* inv_gamma, int32_t* coeffs);
 
 /* ---- per-operator API, host pointers --------------------------------------------------- */
 
@@ -96,6 +103,19 @@ int vp_get_tables(uint16_t* gamma, uint16_t* cbrt_tab, int32_t* sdiv, int32_t* h
  * (each (h,w) tightly packed, each may be NULL, array may be NULL) receive the split channels. */
 int vp_cvt_color_u8(vp_ctx* ctx, int code, const uint8_t* src_host, size_t src_stride, int w, int h,
                     uint8_t* dst_interleaved_host, uint8_t* const* dst_planes_host);
+/* VP_LAB2BGR (utils/color.py:26-32 `lab_to_bgr`, cv2.COLOR_LAB2BGR on 8-bit images) is OpenCV's integer path Lab2RGBinteger:
+ * table look-ups, Q14 divisions of a and b by 500 and 200, the XYZ -> sRGB matrix in Q12 fixed point, the 4096-entry inverse gamma. */
+
+/* utils/color.py:370-392 `white_balance_bgr` / `white_balance_bgr_blur` on an 8-bit BGR image (row stride src_stride) into a packed
+ * BGR image dst: Lab (as VP_BGR2LAB), a and b each shifted by (mean - 128) in float32 and cast back to uint8 the way numpy's
+ * astype does (truncation, low 8 bits), then VP_LAB2BGR.  kernel_size = VP_WB_GLOBAL_MEAN: the mean is np.mean of the plane
+ * (float32 sum of exact per-8192-pixel sums, in order); an odd kernel_size k >= 1 (k <= VP_WB_MAX_KERNEL): the k x k box mean of
+ * cv2.blur with BORDER_REPLICATE, float32(sum * (1.0 / (k k))).  ab_mean_out (host, may be NULL): the two global means (a, b)
+ * (global form only; the call then synchronises).  dst must not overlap src.  The _u8 form synchronises. */
+#define VP_WB_GLOBAL_MEAN 0
+#define VP_WB_MAX_KERNEL 4095
+int vp_white_balance_u8(vp_ctx* ctx, const uint8_t* src_host, size_t src_stride, int w, int h, int kernel_size, uint8_t* dst_host,
+                        float* ab_mean_out);
 
 /* Extension (BASELINE north star "LAB floats within 1e-4"; no reference call site converts float images): BGR float32 in
  * [0,1] (h,w,3 tightly packed) -> CIE L*a*b* float32 (L 0..100, a/b about -127..127), analytic sRGB / D65. */
@@ -195,6 +215,9 @@ int vp_draw_polylines_u8(uint8_t* img_host, size_t stride, int w, int h, int cn,
  * vp_find_contours_dev returns the lists in host memory and synchronises, like its host form. */
 int vp_cvt_color_dev(vp_ctx* ctx, int code, const uint8_t* src_dev, size_t src_stride, int w, int h, uint8_t* dst_interleaved_dev,
                      uint8_t* const* dst_planes_dev);
+/* vp_white_balance_u8 on device images, enqueued on the context's stream (synchronises only to fill ab_mean_out). */
+int vp_white_balance_dev(vp_ctx* ctx, const uint8_t* src_dev, size_t src_stride, int w, int h, int kernel_size, uint8_t* dst_dev,
+                         float* ab_mean_out);
 int vp_inrange_u8_dev(vp_ctx* ctx, const uint8_t* src_dev, size_t src_stride, int w, int h, int cn, const int32_t* lo, const int32_t* hi,
                       uint8_t* dst_dev);
 /* vp_inrange_u8_dev that can also leave the mask's BIT-PACKED form ((h, ceil(w / 64)) u64, bit i of word j = pixel 64 j + i) in bits_dev
