@@ -159,6 +159,7 @@ int vp_destroy(vp_ctx* ctx)
     if (ctx->hstage) hipHostFree(ctx->hstage);
     if (ctx->d_tables) hipFree(ctx->d_tables);
     if (ctx->d_labinv) hipFree(ctx->d_labinv);
+    if (ctx->agauss_taps) hipFree(ctx->agauss_taps);
     hipEventDestroy(ctx->ev0);
     hipEventDestroy(ctx->ev1);
     for (int i = 0; i < 4; i++) { hipStreamDestroy(ctx->aux[i]); hipEventDestroy(ctx->ev_join[i]); }
@@ -1813,6 +1814,66 @@ int vp_adaptive_threshold_mean_u8(vp_ctx* ctx, const uint8_t* src, int w, int h,
     VP_TRY(vpk_adaptive_threshold_mean(ctx, d_src, w, h, imax, idelta, type == VP_THRESH_BINARY_INV, block, d_tmp, d_dst));
     VP_TRY(d2h(ctx, dst, d_dst, npx));
     return vp_synchronize(ctx);
+}
+
+static int agauss_args(vp_ctx* ctx, const void* src, const void* dst, int w, int h, double max_value, int type, int block, double c)
+{
+    if (!src || !dst || w <= 0 || h <= 0 || h > 65535 || (type != VP_THRESH_BINARY && type != VP_THRESH_BINARY_INV) || !std::isfinite(max_value) ||
+        !std::isfinite(c) || std::fabs(c) > 1e6)
+        return vp_fail(ctx, VP_ERR_INVALID, "vp_adaptive_threshold_gaussian arguments");
+    if (block < 3 || (block & 1) == 0) return vp_fail(ctx, VP_ERR_INVALID, "adaptive threshold: block size must be odd and > 1");
+    if (block > VP_AGAUSS_MAX_BLOCK) return vp_fail(ctx, VP_ERR_UNSUPPORTED, "adaptive threshold: Gaussian block size above 511");
+    return VP_OK;
+}
+
+// n frames in HBM -> packed (n, h, w) dst in HBM, enqueued on the context's stream; max_value < 0 gives zeros, as cv2 does
+static int agauss_run(vp_ctx* ctx, const uint8_t* d_src, size_t stride, size_t fstride, int n, int w, int h, double max_value, int type, int block,
+                      double c, uint8_t* d_dst)
+{
+    if (max_value < 0) {
+        VP_HIP(ctx, hipMemsetAsync(d_dst, 0, (size_t)n * w * h, ctx->stream));
+        return VP_OK;
+    }
+    const int imax = (int)std::min(255.0, std::max(0.0, std::nearbyint(max_value)));
+    const int idelta = type == VP_THRESH_BINARY ? (int)std::ceil(c) : (int)std::floor(c);
+    TAKE(d_tmp, uint64_t*, vp_agauss_ws_bytes(w, h, n));
+    return vpk_adaptive_threshold_gaussian(ctx, d_src, stride, fstride, n, w, h, imax, idelta, type == VP_THRESH_BINARY_INV, block, d_tmp, d_dst);
+}
+
+int vp_adaptive_threshold_gaussian_u8(vp_ctx* ctx, const uint8_t* src, int w, int h, double max_value, int type, int block, double c, uint8_t* dst)
+{
+    VP_TRY(check_ctx(ctx));
+    VP_TRY(agauss_args(ctx, src, dst, w, h, max_value, type, block, c));
+    const size_t npx = (size_t)w * h;
+    if (max_value < 0) { memset(dst, 0, npx); return VP_OK; }
+    VP_TRY(vp_ws_reserve(ctx, 2 * vp_align(npx) + vp_agauss_ws_bytes(w, h, 1) + 1024));
+    TAKE(d_src, uint8_t*, npx);
+    TAKE(d_dst, uint8_t*, npx);
+    VP_TRY(h2d(ctx, d_src, src, npx));
+    VP_TRY(agauss_run(ctx, d_src, (size_t)w, npx, 1, w, h, max_value, type, block, c, d_dst));
+    VP_TRY(d2h(ctx, dst, d_dst, npx));
+    return vp_synchronize(ctx);
+}
+
+int vp_adaptive_threshold_gaussian_dev(vp_ctx* ctx, const uint8_t* d_src, size_t src_stride, int w, int h, double max_value, int type, int block,
+                                       double c, uint8_t* d_dst)
+{
+    VP_TRY(check_ctx(ctx));
+    VP_TRY(agauss_args(ctx, d_src, d_dst, w, h, max_value, type, block, c));
+    if (src_stride < (size_t)w) return vp_fail(ctx, VP_ERR_INVALID, "vp_adaptive_threshold_gaussian_dev src_stride");
+    VP_TRY(vp_ws_reserve(ctx, vp_agauss_ws_bytes(w, h, 1) + 1024));
+    return agauss_run(ctx, d_src, src_stride, src_stride * h, 1, w, h, max_value, type, block, c, d_dst);
+}
+
+int vp_adaptive_threshold_gaussian_batch_dev(vp_ctx* ctx, const uint8_t* d_src, size_t src_stride, size_t frame_stride, int n, int w, int h,
+                                             double max_value, int type, int block, double c, uint8_t* d_dst)
+{
+    VP_TRY(check_ctx(ctx));
+    VP_TRY(agauss_args(ctx, d_src, d_dst, w, h, max_value, type, block, c));
+    if (n <= 0 || n > 65535 || src_stride < (size_t)w || (n > 1 && frame_stride < src_stride * h))
+        return vp_fail(ctx, VP_ERR_INVALID, "vp_adaptive_threshold_gaussian_batch_dev strides / frame count");
+    VP_TRY(vp_ws_reserve(ctx, vp_agauss_ws_bytes(w, h, n) + 1024));
+    return agauss_run(ctx, d_src, src_stride, frame_stride, n, w, h, max_value, type, block, c, d_dst);
 }
 
 int vp_canny_u8(vp_ctx* ctx, const uint8_t* src, int w, int h, int cn, double t1, double t2, uint8_t* dst)

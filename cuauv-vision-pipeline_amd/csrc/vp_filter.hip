@@ -66,14 +66,12 @@ __global__ __launch_bounds__(256) void k_gauss_v(const uint16_t* __restrict__ tm
     dst[(size_t)y * rowbytes + b] = (uint8_t)(v > 255u ? 255u : v);
 }
 
-// getGaussianKernelBitExact + getGaussianKernelFixedPoint_ED (8 fraction bits): n odd, 1 <= n <= GB_MAX_TAPS
-void vp_gaussian_taps(int n, double sigma, uint16_t* out)
+// getGaussianKernelBitExact in double precision: n odd, 3 <= n <= GB_MAX_TAPS (n = 1 is the single tap 1.0)
+void vp_gaussian_kernel_f64(int n, double sigma, double* k)
 {
     static const double t3[] = {0.25, 0.5, 0.25}, t5[] = {0.0625, 0.25, 0.375, 0.25, 0.0625},
                         t7[] = {0.03125, 0.109375, 0.21875, 0.28125, 0.21875, 0.109375, 0.03125},
                         t9[] = {4 / 256., 13 / 256., 30 / 256., 51 / 256., 60 / 256., 51 / 256., 30 / 256., 13 / 256., 4 / 256.};
-    if (n == 1) { out[0] = 256; return; }
-    double k[GB_MAX_TAPS + 1];
     const double* tab = nullptr;
     if (sigma <= 0) tab = n == 3 ? t3 : n == 5 ? t5 : n == 7 ? t7 : n == 9 ? t9 : nullptr;
     if (tab) {
@@ -89,6 +87,14 @@ void vp_gaussian_taps(int n, double sigma, uint16_t* out)
         for (int i = 0; i < n2; i++) { k[i] *= mul1; k[n - 1 - i] = k[i]; }
         k[n2] = mul1;
     }
+}
+
+// getGaussianKernelBitExact + getGaussianKernelFixedPoint_ED (8 fraction bits): n odd, 1 <= n <= GB_MAX_TAPS
+void vp_gaussian_taps(int n, double sigma, uint16_t* out)
+{
+    if (n == 1) { out[0] = 256; return; }
+    double k[GB_MAX_TAPS + 1];
+    vp_gaussian_kernel_f64(n, sigma, k);
     const int n2 = n / 2;
     double err = 0;
     long long sum = 0;

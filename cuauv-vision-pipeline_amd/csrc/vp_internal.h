@@ -74,6 +74,11 @@ struct vp_ctx {
     int hough_global;             // 1: every Hough vote is a global atomic (VP_OPT_HOUGH_LDS 0); 0 (default): rows counted in LDS where they fit
     int flat_ops;                 // 1 (default): the per-operator kernels take their 16-px-per-lane forms when rows are packed and pointers aligned; 0: always the generic kernels (tests)
     int ccl_mcap;                 // components per frame the merge block accepts (-1: its LDS capacity); tests lower it to force the fallback
+    u32* agauss_taps;             // Gaussian adaptive threshold: 8 slots of 256 integer taps (half kernels), made on first use
+    int agauss_n[8];              // block size held by each slot (0: empty)
+    int agauss_e[8];              // its scale: tap i = agauss_taps[slot][i] * 2^-agauss_e
+    u32 agauss_host[8][256];      // host copy of each slot
+    int agauss_next;              // slot replaced next
     vp_prof prof;
     char err[256];
 };
@@ -158,6 +163,12 @@ int vpk_canny_u8(vp_ctx* ctx, const uint8_t* d_src, int w, int h, int cn, int lo
 int vp_hough_run(vp_ctx* ctx, const uint8_t* d_src, const uint8_t* h_src, size_t stride, size_t fstride, int n, int w, int h, double rho, double theta, int threshold,
                  double min_theta, double max_theta, float* lines, int max_lines, int* n_lines);
 void vp_gaussian_taps(int n, double sigma, uint16_t* out);   // n odd, <= 511
+void vp_gaussian_kernel_f64(int n, double sigma, double* k);  // the double kernel vp_gaussian_taps rounds: n odd, 3..511
+// Gaussian adaptive threshold (vp_adaptive.hip): n frames (src row stride, frame stride) -> packed (n, h, w) dst; d_tmp: n * w * h u64
+#define VP_AGAUSS_MAX_BLOCK 511
+size_t vp_agauss_ws_bytes(int w, int h, int n);
+int vpk_adaptive_threshold_gaussian(vp_ctx* ctx, const uint8_t* d_src, size_t stride, size_t fstride, int n, int w, int h, int imax, int idelta,
+                                    int inv, int block, uint64_t* d_tmp, uint8_t* d_dst);
 int vpk_gaussian_blur(vp_ctx* ctx, const uint8_t* d_src, int w, int h, int cn, const uint16_t* d_taps, int kw, int kh, uint16_t* d_tmp, uint8_t* d_dst);
 
 // ---- morphology (vp_morph.hip) ---------------------------------------------------------------

@@ -27,6 +27,8 @@ RETR_EXTERNAL, RETR_LIST = 0, 1
 CHAIN_APPROX_NONE, CHAIN_APPROX_SIMPLE = 1, 2
 CC_STAT_LEFT, CC_STAT_TOP, CC_STAT_WIDTH, CC_STAT_HEIGHT, CC_STAT_AREA = 0, 1, 2, 3, 4
 CV_8U = 0
+ADAPTIVE_THRESH_MEAN_C, ADAPTIVE_THRESH_GAUSSIAN_C = 0, 1
+THRESH_BINARY, THRESH_BINARY_INV = 0, 1
 CV_32S = 4
 CV_PI = math.pi
 
@@ -483,6 +485,37 @@ def HoughLines(image, rho, theta, threshold, lines=None, srn=0, stn=0, min_theta
     if max_theta < min_theta:
         raise error("HoughLines: max_theta must be greater than min_theta")
     return _feature.hough_lines(image, rho, theta, threshold, min_theta, max_theta)
+
+
+def adaptiveThreshold(src, maxValue, adaptiveMethod, thresholdType, blockSize, C, dst=None):
+    """cv2.adaptiveThreshold (utils/color.py:220-292) in cv2's positional order on CV_8UC1 images.  ADAPTIVE_THRESH_MEAN_C: the mean
+    path (libvp vp_adaptive_threshold_mean_u8, block sizes 3..151); ADAPTIVE_THRESH_GAUSSIAN_C: the exact Gaussian-weighted mean
+    (vp_adaptive_threshold_gaussian_*, block sizes 3..511; a DeviceMat in gives a DeviceMat out)."""
+    from vision import _vp
+    from vision.devmat import DeviceMat, to_host
+    from vision.utils.helpers import as_mat
+    src = as_mat(src)
+    shape = tuple(src.shape) if isinstance(src, (np.ndarray, DeviceMat)) else ()
+    if (not isinstance(src, (np.ndarray, DeviceMat)) or src.dtype != np.uint8 or len(shape) not in (2, 3) or (len(shape) == 3 and shape[2] != 1)
+            or shape[0] == 0 or shape[1] == 0):
+        raise error("adaptiveThreshold: the source must be a non-empty CV_8UC1 image")
+    blockSize = int(blockSize)
+    if blockSize % 2 != 1 or blockSize <= 1:
+        raise error("adaptiveThreshold: blockSize must be odd and greater than 1")
+    if maxValue < 0:                               # thresh.cpp: an all-zero result before the method and the type are looked at
+        return _into(dst, np.zeros(shape[:2], np.uint8))
+    if adaptiveMethod not in (ADAPTIVE_THRESH_MEAN_C, ADAPTIVE_THRESH_GAUSSIAN_C):
+        raise error("adaptiveThreshold: unknown or unsupported adaptive threshold method")
+    if thresholdType not in (THRESH_BINARY, THRESH_BINARY_INV):
+        raise error("adaptiveThreshold: unknown or unsupported threshold type")
+    if adaptiveMethod == ADAPTIVE_THRESH_GAUSSIAN_C:
+        return _into(dst, _color._adaptive_gaussian(src, blockSize, float(C), int(thresholdType), float(maxValue)))
+    img = np.ascontiguousarray(np.asarray(to_host(src)).reshape(shape[:2]))
+    out = np.empty_like(img)
+    ctx = _vp.default_context()
+    _vp.check(_vp.lib().vp_adaptive_threshold_mean_u8(ctx.handle, _vp.ptr(img), img.shape[1], img.shape[0], float(maxValue), int(thresholdType),
+                                                      blockSize, float(C), _vp.ptr(out)), ctx.handle)
+    return _into(dst, out)
 
 
 def drawContours(image, contours, contourIdx, color, thickness=1):

@@ -322,8 +322,40 @@ def adaptive_threshold_mean_inv(mat: np.ndarray, neighborhood_size: int, bias: f
     return _adaptive_mean(mat, neighborhood_size, bias, 1)
 
 
-adaptive_threshold_gaussian = _outside_path("adaptive_threshold_gaussian")
-adaptive_threshold_gaussian_inv = _outside_path("adaptive_threshold_gaussian_inv")
+def _adaptive_gaussian(mat, neighborhood_size: int, bias: float, kind: int, max_value: float = 255.0):
+    """libvp vp_adaptive_threshold_gaussian_u8 / _dev: numpy in -> numpy out; a DeviceMat (or the lazy mode) -> a DeviceMat that stays in
+    HBM."""
+    mat = as_mat(mat)
+    ctx = _vp.default_context()
+    if lazy_enabled() or isinstance(mat, DeviceMat):
+        up = []
+        src = device_image(ctx, mat, 1, pending=up)
+        try:
+            h, w = src.shape
+            dst = DeviceMat(ctx, (h, w), binary=float(max_value) == 255.0)
+            _vp.check(_vp.lib().vp_adaptive_threshold_gaussian_dev(ctx.handle, src.dev_ptr, w, w, h, float(max_value), kind, int(neighborhood_size),
+                                                                   float(bias), dst.dev_ptr), ctx.handle)
+        finally:
+            finish_uploads(ctx, up)
+        return dst
+    mat = np.ascontiguousarray(_u8_image(mat, 1))
+    out = np.empty_like(mat)
+    _vp.check(_vp.lib().vp_adaptive_threshold_gaussian_u8(ctx.handle, _vp.ptr(mat), mat.shape[1], mat.shape[0], float(max_value), kind,
+                                                          int(neighborhood_size), float(bias), _vp.ptr(out)), ctx.handle)
+    return out
+
+
+def adaptive_threshold_gaussian(mat: np.ndarray, neighborhood_size: int, bias: float = 0) -> np.ndarray:
+    """utils/color.py:257-273 (cv2.adaptiveThreshold, ADAPTIVE_THRESH_GAUSSIAN_C, THRESH_BINARY): 255 where the pixel exceeds the
+    Gaussian-weighted mean of its neighbourhood minus the bias (the exact mean of OpenCV's float32 taps, rounded half to even)."""
+    return _adaptive_gaussian(mat, neighborhood_size, bias, 0)
+
+
+def adaptive_threshold_gaussian_inv(mat: np.ndarray, neighborhood_size: int, bias: float = 0) -> np.ndarray:
+    """utils/color.py:276-292 (THRESH_BINARY_INV): 255 where the pixel does not exceed the Gaussian-weighted mean minus the bias."""
+    return _adaptive_gaussian(mat, neighborhood_size, bias, 1)
+
+
 kmeans = _outside_path("kmeans")
 
 

@@ -353,6 +353,22 @@ int vp_resize_u8(vp_ctx* ctx, const uint8_t* src_host, int w, int h, int cn, int
  * block_size odd, 3..151 (the range in which OpenCV's three roundings of the box mean provably coincide).  dst may equal src. */
 int vp_adaptive_threshold_mean_u8(vp_ctx* ctx, const uint8_t* src_host, int w, int h, double max_value, int type, int block_size, double c,
                                   uint8_t* dst_host);
+/* cv2.adaptiveThreshold(src, max_value, ADAPTIVE_THRESH_GAUSSIAN_C, type, block_size, c) on a single-channel 8-bit image
+ * (utils/color.py:257-292 adaptive_threshold_gaussian / adaptive_threshold_gaussian_inv): mean = the exact weighted mean of
+ * OpenCV's float32 taps getGaussianKernel(block_size, 0, CV_32F), separable, BORDER_REPLICATE, rounded half to even (a side of one
+ * pixel takes the single tap 1.0, as BORDER_ISOLATED does); then the compare of the mean method.  block_size odd, 3..511 (larger:
+ * VP_ERR_UNSUPPORTED); argument checks and error codes as vp_adaptive_threshold_mean_u8.  dst may equal src. */
+int vp_adaptive_threshold_gaussian_u8(vp_ctx* ctx, const uint8_t* src_host, int w, int h, double max_value, int type, int block_size,
+                                      double c, uint8_t* dst_host);
+/* the same on a device image (row stride src_stride bytes) into a packed (h, w) device image; enqueued on the context's stream.
+ * dst must not overlap src.  Exception: the first call with a block size the context has not cached (8 sizes are kept, counting the
+ * single tap of a one-pixel side) waits for the context's stream and uploads the taps synchronously; later calls do not wait. */
+int vp_adaptive_threshold_gaussian_dev(vp_ctx* ctx, const uint8_t* src_dev, size_t src_stride, int w, int h, double max_value, int type,
+                                       int block_size, double c, uint8_t* dst_dev);
+/* n equal-shape device frames (frame f at src_dev + f * frame_stride) in one launch sequence into packed (n, h, w) dst_dev; waits on
+ * a block size's first use as vp_adaptive_threshold_gaussian_dev does. */
+int vp_adaptive_threshold_gaussian_batch_dev(vp_ctx* ctx, const uint8_t* src_dev, size_t src_stride, size_t frame_stride, int n, int w,
+                                             int h, double max_value, int type, int block_size, double c, uint8_t* dst_dev);
 /* cv2.Canny(image, threshold1, threshold2) with the default 3x3 aperture and L1 gradient on 8-bit images, cn = 1..4
  * (utils/feature.py:43-101 canny / simple_canny): Sobel derivatives, non-maximum suppression with OpenCV's integer direction test,
  * hysteresis as connected components of the surviving pixels that hold a pixel above the high threshold.  dst: (h, w) 0 / 255. */
