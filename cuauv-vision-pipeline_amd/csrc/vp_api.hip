@@ -1780,18 +1780,26 @@ int vp_gaussian_blur_u8(vp_ctx* ctx, const uint8_t* src, int w, int h, int cn, i
     return vp_synchronize(ctx);
 }
 
-int vp_resize_u8(vp_ctx* ctx, const uint8_t* src, int w, int h, int cn, int dw, int dh, uint8_t* dst)
+int vp_resize_u8_scaled(vp_ctx* ctx, const uint8_t* src, int w, int h, int cn, int dw, int dh, double inv_sx, double inv_sy, uint8_t* dst)
 {
     VP_TRY(check_ctx(ctx));
-    if (!src || !dst || w <= 0 || h <= 0 || dw <= 0 || dh <= 0 || dh > 65535 || cn < 1 || cn > 4) return vp_fail(ctx, VP_ERR_INVALID, "vp_resize_u8 arguments");
+    if (!src || !dst || w <= 0 || h <= 0 || dw <= 0 || dh <= 0 || dh > 65535 || cn < 1 || cn > 4 || !std::isfinite(inv_sx) || !std::isfinite(inv_sy) ||
+        !(inv_sx > 0) || !(inv_sy > 0))
+        return vp_fail(ctx, VP_ERR_INVALID, "vp_resize_u8 arguments");
     const size_t sbytes = (size_t)w * h * cn, dbytes = (size_t)dw * dh * cn;
     VP_TRY(vp_ws_reserve(ctx, vp_align(sbytes) + vp_align(dbytes) + 1024));
     TAKE(d_src, uint8_t*, sbytes);
     TAKE(d_dst, uint8_t*, dbytes);
     VP_TRY(h2d(ctx, d_src, src, sbytes));
-    VP_TRY(vpk_resize_u8(ctx, d_src, w, h, cn, dw, dh, d_dst));
+    VP_TRY(vpk_resize_u8(ctx, d_src, w, h, cn, dw, dh, inv_sx, inv_sy, d_dst));
     VP_TRY(d2h(ctx, dst, d_dst, dbytes));
     return vp_synchronize(ctx);
+}
+
+int vp_resize_u8(vp_ctx* ctx, const uint8_t* src, int w, int h, int cn, int dw, int dh, uint8_t* dst)
+{
+    // cv::resize with a dsize: inv_scale = (double)dsize / ssize (an empty source is rejected by the scaled entry)
+    return vp_resize_u8_scaled(ctx, src, w, h, cn, dw, dh, w > 0 ? (double)dw / w : 0.0, h > 0 ? (double)dh / h : 0.0, dst);
 }
 
 int vp_adaptive_threshold_mean_u8(vp_ctx* ctx, const uint8_t* src, int w, int h, double max_value, int type, int block, double c, uint8_t* dst)

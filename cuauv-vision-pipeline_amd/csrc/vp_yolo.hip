@@ -8,28 +8,57 @@
 // tests/test_gpu_yolo.py - parity unpinned, like the rest of that row.
 #include "vp_internal.h"
 
-// cv2.resize(INTER_LINEAR) on 8-bit data as OpenCV's generic path computes it (imgproc/src/resize.cpp): 11-bit horizontal and
-// vertical coefficients (cvRound(f * 2048)), half-pixel centres, edge replication, and the two-stage rounding
-// (((b0 * (S0 >> 4)) >> 16) + ((b1 * (S1 >> 4)) >> 16) + 2) >> 2.
+#include <cfloat>
+#include <cmath>
+
+// cv2.resize(INTER_LINEAR) on 8-bit data as OpenCV's generic path computes it (imgproc/src/resize.cpp): scale = 1. / inv_scale in
+// double (inv_scale = dsize / ssize, or fx / fy as given), f = (float)((d + 0.5) * scale - 0.5), 11-bit weights cvRound((1 - f) * 2048)
+// and cvRound(f * 2048), and the two-stage rounding (((b0 * (S0 >> 4)) >> 16) + ((b1 * (S1 >> 4)) >> 16) + 2) >> 2.  The column table
+// is clamped at both edges (sx < 0 or sx >= sw - 1: weight pair (2048, 0)); the row table is not: at the top and bottom of an upscale
+// both rows clip to the edge row and keep their weights (1 - fy, fy).  Each thread derives its table entries itself (two double
+// products per pixel) instead of reading tables built on the host, so the device entries stay asynchronous.
 struct lb_params {
     int sw, sh;          // source size
     int dw, dh;          // destination (network input) size
     int nw, nh;          // resized content size
     int left, top;       // content offset inside the destination
-    float scale_x, scale_y;   // source pixels per content pixel
+    double scale_x, scale_y;   // source pixels per content pixel: 1. / ((double)n / s)
     int pad;
 };
 
-__device__ __forceinline__ void lb_coef(int d, float scale, int ssize, int& s0, int& a0, int& a1)
+// table entry of destination index d: source index s and fraction f of OpenCV's xofs / yofs and alpha / beta.  The double product
+// and difference are rounded separately, never contracted into a fused multiply-add (a fused one moves f across roundings).
+__device__ __forceinline__ void rs_coef(int d, double scale, int& s, float& f)
 {
-    float f = (float)(((double)d + 0.5) * (double)scale - 0.5);
-    int s = (int)floorf(f);
-    f -= (float)s;
-    if (s < 0) { s = 0; f = 0.f; }
-    if (s >= ssize - 1) { s = ssize - 1; f = 0.f; }
-    s0 = s;
-    a1 = (int)rintf(f * 2048.f);
-    a0 = (int)rintf((1.f - f) * 2048.f);
+#pragma clang fp contract(off)
+    const float fd = (float)(((double)d + 0.5) * scale - 0.5);
+    s = (int)floorf(fd);
+    f = fd - (float)s;
+}
+__device__ __forceinline__ void rs_weights(float f, int& w0, int& w1)
+{
+    w1 = (int)rintf(f * 2048.f);
+    w0 = (int)rintf((1.f - f) * 2048.f);
+}
+// column: clamped to the edge pixel with weights (2048, 0); sx1 = the right neighbour (its weight is 0 wherever it would leave the row)
+__device__ __forceinline__ void rs_col(int d, double scale, int ssize, int& sx, int& sx1, int& a0, int& a1)
+{
+    float f;
+    rs_coef(d, scale, sx, f);
+    if (sx < 0) { sx = 0; f = 0.f; }
+    if (sx >= ssize - 1) { sx = ssize - 1; f = 0.f; }
+    sx1 = min(sx + 1, ssize - 1);
+    rs_weights(f, a0, a1);
+}
+// row: the weights keep the unclamped fraction, only the two row indices are clipped into [0, ssize - 1]
+__device__ __forceinline__ void rs_row(int d, double scale, int ssize, int& sy0, int& sy1, int& b0, int& b1)
+{
+    int sy;
+    float f;
+    rs_coef(d, scale, sy, f);
+    sy0 = min(max(sy, 0), ssize - 1);
+    sy1 = min(max(sy + 1, 0), ssize - 1);
+    rs_weights(f, b0, b1);
 }
 
 // grid (ceil(dw/64), dh), 64 threads: thread = one destination pixel, three planes written (R, G, B order)
@@ -56,10 +85,9 @@ __global__ __launch_bounds__(64) void k_letterbox(const uint8_t* __restrict__ sr
 #pragma unroll
         for (int c = 0; c < 3; c++) bgr[c] = (r0[c] + r0[3 + c] + r1[c] + r1[3 + c] + 2) >> 2;
     } else {
-        int sx, ax0, ax1, sy, ay0, ay1;
-        lb_coef(cx, P.scale_x, P.sw, sx, ax0, ax1);
-        lb_coef(cy, P.scale_y, P.sh, sy, ay0, ay1);
-        const int sx1 = min(sx + 1, P.sw - 1), sy1 = min(sy + 1, P.sh - 1);
+        int sx, sx1, ax0, ax1, sy, sy1, ay0, ay1;
+        rs_col(cx, P.scale_x, P.sw, sx, sx1, ax0, ax1);
+        rs_row(cy, P.scale_y, P.sh, sy, sy1, ay0, ay1);
         const uint8_t* r0 = src + (size_t)sy * P.sw * 3;
         const uint8_t* r1 = src + (size_t)sy1 * P.sw * 3;
 #pragma unroll
@@ -75,42 +103,59 @@ __global__ __launch_bounds__(64) void k_letterbox(const uint8_t* __restrict__ sr
     o[2 * plane] = (float)bgr[0] / 255.f;
 }
 
-// cv2.resize(src, (dw, dh), interpolation=INTER_LINEAR) for 8-bit images with cn interleaved channels: thread = one destination byte
-__global__ __launch_bounds__(256) void k_resize_u8(const uint8_t* __restrict__ src, int sw, int sh, int cn, int dw, int dh, float scale_x, float scale_y,
+// cv2.resize(src, (dw, dh), interpolation=INTER_LINEAR) for 8-bit images with CN interleaved channels: thread = one destination pixel,
+// so the table entries are derived once for all of its channels.  grid (ceil(dw/256), dh).
+// area2: hal::resize's switch to the area-fast path (both scales exactly 2), taken only when the source is exactly twice the destination
+template <int CN>
+__global__ __launch_bounds__(256) void k_resize_u8(const uint8_t* __restrict__ src, int sw, int sh, int dw, double scale_x, double scale_y, int area2,
                                                    uint8_t* __restrict__ dst)
 {
-    const int xc = blockIdx.x * 256 + threadIdx.x, y = blockIdx.y;
-    if (xc >= dw * cn) return;
-    const int x = xc / cn, c = xc - x * cn;
-    int v;
-    if (sw == 2 * dw && sh == 2 * dh) {
-        const uint8_t* r0 = src + ((size_t)(2 * y) * sw + 2 * x) * cn + c;
-        const uint8_t* r1 = r0 + (size_t)sw * cn;
-        v = (r0[0] + r0[cn] + r1[0] + r1[cn] + 2) >> 2;
-    } else {
-        int sx, ax0, ax1, sy, ay0, ay1;
-        lb_coef(x, scale_x, sw, sx, ax0, ax1);
-        lb_coef(y, scale_y, sh, sy, ay0, ay1);
-        const int sx1 = min(sx + 1, sw - 1), sy1 = min(sy + 1, sh - 1);
-        const uint8_t* r0 = src + (size_t)sy * sw * cn + c;
-        const uint8_t* r1 = src + (size_t)sy1 * sw * cn + c;
-        const int S0 = r0[sx * cn] * ax0 + r0[sx1 * cn] * ax1;
-        const int S1 = r1[sx * cn] * ax0 + r1[sx1 * cn] * ax1;
-        v = (((ay0 * (S0 >> 4)) >> 16) + ((ay1 * (S1 >> 4)) >> 16) + 2) >> 2;
-        v = min(max(v, 0), 255);
+    const int x = blockIdx.x * 256 + threadIdx.x, y = blockIdx.y;
+    if (x >= dw) return;
+    uint8_t* d = dst + ((size_t)y * dw + x) * CN;
+    if (area2) {
+        const uint8_t* r0 = src + ((size_t)(2 * y) * sw + 2 * x) * CN;
+        const uint8_t* r1 = r0 + (size_t)sw * CN;
+#pragma unroll
+        for (int c = 0; c < CN; c++) d[c] = (uint8_t)((r0[c] + r0[CN + c] + r1[c] + r1[CN + c] + 2) >> 2);
+        return;
     }
-    dst[((size_t)y * dw + x) * cn + c] = (uint8_t)v;
+    int sx, sx1, ax0, ax1, sy, sy1, ay0, ay1;
+    rs_col(x, scale_x, sw, sx, sx1, ax0, ax1);
+    rs_row(y, scale_y, sh, sy, sy1, ay0, ay1);
+    const uint8_t* r0 = src + (size_t)sy * sw * CN;
+    const uint8_t* r1 = src + (size_t)sy1 * sw * CN;
+#pragma unroll
+    for (int c = 0; c < CN; c++) {
+        const int S0 = r0[sx * CN + c] * ax0 + r0[sx1 * CN + c] * ax1;
+        const int S1 = r1[sx * CN + c] * ax0 + r1[sx1 * CN + c] * ax1;
+        const int v = (((ay0 * (S0 >> 4)) >> 16) + ((ay1 * (S1 >> 4)) >> 16) + 2) >> 2;
+        d[c] = (uint8_t)min(max(v, 0), 255);
+    }
 }
 
-int vpk_resize_u8(vp_ctx* ctx, const uint8_t* d_src, int sw, int sh, int cn, int dw, int dh, uint8_t* d_dst)
+// inv_sx, inv_sy: cv::resize's inverse scales (dsize / ssize, or fx / fy of the size-less form)
+int vpk_resize_u8(vp_ctx* ctx, const uint8_t* d_src, int sw, int sh, int cn, int dw, int dh, double inv_sx, double inv_sy, uint8_t* d_dst)
 {
     vp_prof_scope ps(ctx, VPK_OTHER);
     if (sw == dw && sh == dh) {
         VP_HIP(ctx, hipMemcpyAsync(d_dst, d_src, (size_t)sw * sh * cn, hipMemcpyDeviceToDevice, ctx->stream));
         return VP_OK;
     }
-    hipLaunchKernelGGL(k_resize_u8, dim3((unsigned)((dw * cn + 255) / 256), (unsigned)dh), dim3(256), 0, ctx->stream, d_src, sw, sh, cn, dw, dh,
-                       (float)((double)sw / dw), (float)((double)sh / dh), d_dst);
+    const double scale_x = 1. / inv_sx, scale_y = 1. / inv_sy;
+    // is_area_fast with iscale_x == iscale_y == 2: |scale - saturate_cast<int>(scale)| < DBL_EPSILON
+    const bool area2 = std::fabs(scale_x - 2.0) < DBL_EPSILON && std::fabs(scale_y - 2.0) < DBL_EPSILON;
+    if (area2 && (sw != 2 * dw || sh != 2 * dh))
+        return vp_fail(ctx, VP_ERR_UNSUPPORTED, "resize: scale 2 with a partial edge cell (OpenCV's area-fast edge handling)");
+    const dim3 grid((unsigned)((dw + 255) / 256), (unsigned)dh);
+    const int a2 = area2 ? 1 : 0;
+    switch (cn) {
+    case 1: hipLaunchKernelGGL(k_resize_u8<1>, grid, dim3(256), 0, ctx->stream, d_src, sw, sh, dw, scale_x, scale_y, a2, d_dst); break;
+    case 2: hipLaunchKernelGGL(k_resize_u8<2>, grid, dim3(256), 0, ctx->stream, d_src, sw, sh, dw, scale_x, scale_y, a2, d_dst); break;
+    case 3: hipLaunchKernelGGL(k_resize_u8<3>, grid, dim3(256), 0, ctx->stream, d_src, sw, sh, dw, scale_x, scale_y, a2, d_dst); break;
+    case 4: hipLaunchKernelGGL(k_resize_u8<4>, grid, dim3(256), 0, ctx->stream, d_src, sw, sh, dw, scale_x, scale_y, a2, d_dst); break;
+    default: return vp_fail(ctx, VP_ERR_INVALID, "resize: cn must be 1..4");
+    }
     VP_HIP(ctx, hipGetLastError());
     return VP_OK;
 }
@@ -203,8 +248,8 @@ int vpk_letterbox(vp_ctx* ctx, const uint8_t* d_src, int sw, int sh, int dw, int
     const double px = (dw - P.nw) / 2.0, py = (dh - P.nh) / 2.0;
     P.left = (int)nearbyint(px - 0.1);
     P.top = (int)nearbyint(py - 0.1);
-    P.scale_x = (float)((double)sw / P.nw);
-    P.scale_y = (float)((double)sh / P.nh);
+    P.scale_x = 1. / ((double)P.nw / sw);
+    P.scale_y = 1. / ((double)P.nh / sh);
     if (geom_out) { geom_out[0] = (float)r; geom_out[1] = (float)P.left; geom_out[2] = (float)P.top; }
     vp_prof_scope ps(ctx, VPK_OTHER);
     hipLaunchKernelGGL(k_letterbox, dim3((unsigned)((dw + 63) / 64), (unsigned)dh), dim3(64), 0, ctx->stream, d_src, P, d_dst);

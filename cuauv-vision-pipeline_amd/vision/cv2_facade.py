@@ -439,12 +439,13 @@ def resize(src, dsize, dst=None, fx=None, fy=None, interpolation=INTER_LINEAR):
     if interpolation != INTER_LINEAR:
         raise error("resize: only INTER_LINEAR is on the accelerated path")
     src = np.ascontiguousarray(src)
-    if dsize is None or tuple(dsize) == (0, 0):
-        if not fx or not fy:
-            raise error("resize: dsize or both fx and fy are needed")
+    scaled = dsize is None or tuple(dsize) == (0, 0)
+    if scaled:
+        if not fx or not fy or not (fx > 0 and fy > 0):
+            raise error("resize: dsize or both fx and fy (positive) are needed")
+        fx, fy = float(fx), float(fy)                # cv2 keeps them as the inverse scales: the tables use 1 / fx, not size / dsize
         dsize = (int(round(src.shape[1] * fx)), int(round(src.shape[0] * fy)))   # cv2: saturate_cast<int>(cols * fx): round half to even
-    elif fx or fy:
-        pass                                       # cv2 ignores fx / fy when dsize is given
+    # (cv2 ignores fx / fy when dsize is given)
     if src.dtype != np.uint8 or src.ndim not in (2, 3) or src.size == 0:
         raise error("resize: expected a non-empty uint8 image")
     cn = 1 if src.ndim == 2 else src.shape[2]
@@ -453,7 +454,14 @@ def resize(src, dsize, dst=None, fx=None, fy=None, interpolation=INTER_LINEAR):
         raise error("resize: bad size")
     out = np.empty((dh, dw) if src.ndim == 2 else (dh, dw, cn), np.uint8)
     ctx = _vp.default_context()
-    _vp.check(_vp.lib().vp_resize_u8(ctx.handle, _vp.ptr(src), src.shape[1], src.shape[0], cn, dw, dh, _vp.ptr(out)), ctx.handle)
+    lib = _vp.lib()
+    try:
+        if scaled:
+            _vp.check(lib.vp_resize_u8_scaled(ctx.handle, _vp.ptr(src), src.shape[1], src.shape[0], cn, dw, dh, fx, fy, _vp.ptr(out)), ctx.handle)
+        else:
+            _vp.check(lib.vp_resize_u8(ctx.handle, _vp.ptr(src), src.shape[1], src.shape[0], cn, dw, dh, _vp.ptr(out)), ctx.handle)
+    except _vp.VpError as e:                         # scale 2 with a partial edge cell: not reproduced
+        raise error(f"resize: {e}") from e
     return _into(dst, out)
 
 

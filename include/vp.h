@@ -345,9 +345,15 @@ int vp_otsu_threshold_u8(vp_ctx* ctx, const uint8_t* src_host, size_t n_bytes, d
 int vp_gaussian_blur_u8(vp_ctx* ctx, const uint8_t* src_host, int w, int h, int cn, int kw, int kh, double sigma1, double sigma2,
                         uint8_t* dst_host);
 /* cv2.resize(src, (dst_w, dst_h)) with the default INTER_LINEAR on 8-bit images, cn = 1..4 interleaved channels
- * (modules/preprocessor.py:136-144): OpenCV's generic fixed-point path, including the 2x2 box average it substitutes at an
- * exact halving.  (IPP-enabled OpenCV builds may round differently.) */
+ * (modules/preprocessor.py:136-144): OpenCV's generic fixed-point path (scale = 1. / (dst / src) in double, the column table
+ * clamped at the edges, the row weights not), including the 2x2 box average it substitutes at an exact halving.  (IPP-enabled
+ * OpenCV builds may round differently.) */
 int vp_resize_u8(vp_ctx* ctx, const uint8_t* src_host, int w, int h, int cn, int dst_w, int dst_h, uint8_t* dst_host);
+/* the same with cv::resize's inverse scales given, as cv2.resize(src, None, fx=inv_sx, fy=inv_sy) keeps them (the caller passes
+ * dst_w = saturate_cast<int>(w * inv_sx), dst_h likewise).  Scale exactly 2 on both axes is OpenCV's area-fast path: supported when
+ * w == 2 * dst_w and h == 2 * dst_h, VP_ERR_UNSUPPORTED otherwise (its partial edge cells are not reproduced). */
+int vp_resize_u8_scaled(vp_ctx* ctx, const uint8_t* src_host, int w, int h, int cn, int dst_w, int dst_h, double inv_sx, double inv_sy,
+                        uint8_t* dst_host);
 /* cv2.adaptiveThreshold(src, max_value, ADAPTIVE_THRESH_MEAN_C, type, block_size, c) on a single-channel 8-bit image
  * (utils/color.py:220-254 adaptive_threshold_mean / adaptive_threshold_mean_inv).  type: VP_THRESH_BINARY or VP_THRESH_BINARY_INV;
  * block_size odd, 3..151 (the range in which OpenCV's three roundings of the box mean provably coincide).  dst may equal src. */

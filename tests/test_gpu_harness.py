@@ -160,8 +160,8 @@ def test_gate_module_echoes_two_directions(vp, oracle, capsys):
 
 
 def _resize_ref(img, nw, nh):
-    from test_gpu_yolo import _resize_linear_u8
-    return _resize_linear_u8(img, nw, nh)
+    import resize_restate as RR
+    return RR.resize(img, (nw, nh))
 
 
 @pytest.mark.parametrize("setting", ["defaults", "morph", "geometry", "balance_and_posts"])

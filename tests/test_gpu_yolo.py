@@ -6,36 +6,14 @@ import pytest
 import torch
 
 import frames as F
+import resize_restate as RR
 
 pytestmark = pytest.mark.gpu
 
 
 def _resize_linear_u8(src, nw, nh):
-    """cv2.resize(src, (nw, nh), interpolation=INTER_LINEAR) for uint8, OpenCV's 11-bit fixed-point generic path."""
-    h, w = src.shape[:2]
-    if w == 2 * nw and h == 2 * nh:          # OpenCV substitutes the 2x2 box average at an exact halving
-        s = src.astype(np.int64)
-        return ((s[0::2, 0::2] + s[0::2, 1::2] + s[1::2, 0::2] + s[1::2, 1::2] + 2) >> 2).astype(np.uint8)
-
-    def coef(n, ssize, scale):
-        d = np.arange(n)
-        f = ((d + 0.5) * np.float64(np.float32(scale)) - 0.5).astype(np.float32)
-        s = np.floor(f).astype(np.int64)
-        f = f - s.astype(np.float32)
-        lo = s < 0
-        s[lo], f[lo] = 0, 0
-        hi = s >= ssize - 1
-        s[hi], f[hi] = ssize - 1, 0
-        a1 = np.rint(f * np.float32(2048)).astype(np.int64)
-        a0 = np.rint((np.float32(1) - f) * np.float32(2048)).astype(np.int64)
-        return s, np.minimum(s + 1, ssize - 1), a0, a1
-    sx, sx1, ax0, ax1 = coef(nw, w, w / nw)
-    sy, sy1, ay0, ay1 = coef(nh, h, h / nh)
-    s = src.astype(np.int64)
-    rows0 = s[sy][:, sx] * ax0[None, :, None] + s[sy][:, sx1] * ax1[None, :, None]
-    rows1 = s[sy1][:, sx] * ax0[None, :, None] + s[sy1][:, sx1] * ax1[None, :, None]
-    out = (((ay0[:, None, None] * (rows0 >> 4)) >> 16) + ((ay1[:, None, None] * (rows1 >> 4)) >> 16) + 2) >> 2
-    return np.clip(out, 0, 255).astype(np.uint8)
+    """cv2.resize(src, (nw, nh), interpolation=INTER_LINEAR) for uint8: the statement of OpenCV's resize.cpp (resize_restate.py)."""
+    return RR.resize(src, (nw, nh))
 
 
 def _letterbox_ref(img, H, W, pad=114):
@@ -50,9 +28,23 @@ def _letterbox_ref(img, H, W, pad=114):
     return chw, (r, left, top), (nw, nh)
 
 
-@pytest.mark.parametrize("shape,new", [((1080, 1920), (640, 640)), ((360, 640), (640, 640)), ((480, 480), (640, 640)), ((97, 333), (320, 256)),
-                                       ((640, 640), (640, 640)), ((700, 300), (64, 96)), ((720, 1280), (640, 640))])
+# The ids are those these shapes had before 480x480 and 97x333 moved to test_letterbox_double_scale_rows below.
+@pytest.mark.parametrize("shape,new", [((1080, 1920), (640, 640)), ((360, 640), (640, 640)), ((640, 640), (640, 640)), ((700, 300), (64, 96)),
+                                       ((720, 1280), (640, 640))],
+                         ids=["shape0-new0", "shape1-new1", "shape4-new4", "shape5-new5", "shape6-new6"])
 def test_letterbox(vp, shape, new):
+    _check_letterbox(shape, new)
+
+
+# The two shapes whose expected values changed when the kernels took resize.cpp's double scale and unclamped row weights:
+# 480x480 -> 640x640 is an upscale (the first and last rows keep their weight pair on one clipped row), and 97x333 (h x w) fits into
+# 75x256, a row scale 97 / 75 that float32 does not hold exactly.
+@pytest.mark.parametrize("shape,new", [((480, 480), (640, 640)), ((97, 333), (320, 256))], ids=["480x480-640x640", "97x333-320x256"])
+def test_letterbox_double_scale_rows(vp, shape, new):
+    _check_letterbox(shape, new)
+
+
+def _check_letterbox(shape, new):
     from vision.yolo import letterbox
     img = F.s1_buoy(1, shape[1], shape[0])
     got, geom = letterbox(img, new)
@@ -173,8 +165,9 @@ def test_detection_records_and_corner_order(vp):
 
 
 @pytest.mark.parametrize("cn", [1, 3, 4])
-def test_resize_linear_u8(vp, cn):
-    """cv2.resize (facade) == the fixed-point restatement, and within one count of float bilinear interpolation."""
+def test_resize_linear_u8_statement(vp, cn):
+    """cv2.resize (facade) == the statement of resize.cpp (double scale, unclamped row weights), and within one count of float
+    bilinear interpolation."""
     from vision import cv2_facade as cv2
     rng = np.random.default_rng(cn)
     for (h, w), (dh, dw) in [((90, 160), (45, 80)), ((90, 160), (512, 512)), ((33, 65), (7, 200)), ((64, 64), (64, 64)), ((100, 50), (99, 51))]:
