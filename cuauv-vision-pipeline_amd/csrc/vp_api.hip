@@ -1266,7 +1266,7 @@ int vp_ccl_u8(vp_ctx* ctx, const uint8_t* src, size_t src_stride, int w, int h, 
 // src: host image (uploaded) or, with src_on_device, a device image read in place; or (bits_in) its bit-packed form, already on the device
 static int find_contours_impl(vp_ctx* ctx, const uint8_t* src, bool src_on_device, size_t src_stride, int w, int h, int mode, int method,
                               int32_t* points, int64_t max_points, int32_t* counts, uint8_t* is_hole, int max_contours, int32_t* n_contours,
-                              int64_t* n_points, const u64* bits_in = nullptr)
+                              int64_t* n_points, const u64* bits_in = nullptr, int32_t* hierarchy = nullptr, bool tree_entry = false)
 {
     VP_TRY(check_ctx(ctx));
     if ((!src && !bits_in) || w <= 0 || h <= 0 || (!bits_in && src_stride < (size_t)w) || !n_contours || !n_points || max_contours < 0 || max_points < 0)
@@ -1275,20 +1275,24 @@ static int find_contours_impl(vp_ctx* ctx, const uint8_t* src, bool src_on_devic
     const size_t bitbytes = (size_t)h * vp_ww(w) * 8;
     const int mc = max_contours > 0 ? max_contours : 1;
     const long long mp = max_points > 0 ? max_points : 1;
-    VP_TRY(vp_ws_reserve(ctx, vp_align(npx) + vp_align(bitbytes) + vp_contours_ws_bytes(w, h, 1, mc) + vp_align(16 + (size_t)mc * 9) +
-                                  vp_align((size_t)mp * 8) + 8192));
+    // RETR_CCOMP / RETR_TREE (the tree entries only): the header carries the hierarchy rows [mc][4] between the offsets and the hole flags
+    const bool tree = tree_entry && (mode == VP_RETR_CCOMP || mode == VP_RETR_TREE);
+    const size_t hier_bytes = tree ? (size_t)mc * 16 : 0;
+    VP_TRY(vp_ws_reserve(ctx, vp_align(npx) + vp_align(bitbytes) + vp_contours_ws_bytes(w, h, 1, mc) + vp_align(16 + (size_t)mc * 9 + hier_bytes) +
+                                  vp_align((size_t)mp * 8) + (tree ? vp_contour_tree_ws_bytes(mc) : 0) + 8192));
     TAKE(d_stage, uint8_t*, npx);
     const uint8_t* d_src = d_stage;
     size_t d_stride = (size_t)w;
     TAKE(d_bits, u64*, bitbytes);
-    // result header, one block so that one copy brings it back: info[2] (16 B) | counts[mc] | offsets[mc] | is_hole[mc]
-    const size_t hdr_bytes = 16 + (size_t)mc * 9;
+    // result header, one block so that one copy brings it back: info[2] (16 B) | counts[mc] | offsets[mc] | (tree: hierarchy[mc][4]) | is_hole[mc]
+    const size_t hdr_bytes = 16 + (size_t)mc * 9 + hier_bytes;
     TAKE(d_hdr, uint8_t*, hdr_bytes);
     TAKE(d_points, int32_t*, (size_t)mp * 8);
     int32_t* d_info = reinterpret_cast<int32_t*>(d_hdr);
     int32_t* d_counts = reinterpret_cast<int32_t*>(d_hdr + 16);
     int32_t* d_offsets = d_counts + mc;
-    uint8_t* d_hole = reinterpret_cast<uint8_t*>(d_offsets + mc);
+    int32_t* d_hier = tree ? d_offsets + mc : nullptr;
+    uint8_t* d_hole = reinterpret_cast<uint8_t*>(d_offsets + mc + (tree ? 4 * (size_t)mc : 0));
     const u64* bits_use = d_bits;
     if (bits_in) {
         bits_use = bits_in;                               // the caller made the bit plane with the mask (vp_inrange_u8_bits_dev): no packing launch
@@ -1313,7 +1317,8 @@ static int find_contours_impl(vp_ctx* ctx, const uint8_t* src, bool src_on_devic
     hm.info = reinterpret_cast<int32_t*>(hs);
     hm.counts = reinterpret_cast<int32_t*>(hs + 16);
     hm.offsets = hm.counts + mc;
-    hm.is_hole = reinterpret_cast<uint8_t*>(hm.offsets + mc);
+    hm.hier = tree ? hm.offsets + mc : nullptr;
+    hm.is_hole = reinterpret_cast<uint8_t*>(hm.offsets + mc + (tree ? 4 * (size_t)mc : 0));
     hm.points = spec_pts ? reinterpret_cast<int32_t*>(hs + hdr_pad) : nullptr;
     hm.points_cap = (long long)spec_pts;
     // One block only up to what its LDS tables hold: a mask that turns out to have more heads than that while none was expected says so
@@ -1326,7 +1331,7 @@ static int find_contours_impl(vp_ctx* ctx, const uint8_t* src, bool src_on_devic
         const bool defer = !many_now && many_env < 0;
         ctx->ws_off = ws_mark;
         VP_TRY(vpk_find_contours(ctx, bits_use, w, h, 1, mode, method, d_counts, d_hole, d_offsets, d_points, mc, mp, d_info, many_now,
-                                 reinterpret_cast<uint32_t*>(d_info + 2), mirror_off ? nullptr : &hm, defer));
+                                 reinterpret_cast<uint32_t*>(d_info + 2), mirror_off ? nullptr : &hm, defer, d_hier));
         if (mirror_off) {
             if (spec_pts && reinterpret_cast<uint8_t*>(d_points) == d_hdr + hdr_pad) {
                 VP_TRY(d2h(ctx, hs, d_hdr, hdr_pad + spec_pts * 8));           // header and points lie back to back in the workspace: one copy
@@ -1355,7 +1360,18 @@ static int find_contours_impl(vp_ctx* ctx, const uint8_t* src, bool src_on_devic
     std::vector<uint8_t> hh(K);
     memcpy(hc.data(), hs + 16, (size_t)K * 4);
     memcpy(ho.data(), hs + 16 + (size_t)mc * 4, (size_t)K * 4);
-    memcpy(hh.data(), hs + 16 + (size_t)mc * 8, (size_t)K);
+    memcpy(hh.data(), hs + 16 + (size_t)mc * 8 + hier_bytes, (size_t)K);
+    if (hierarchy) {
+        // RETR_CCOMP / RETR_TREE: the rows came in cv2's order; the flat modes: each contour the next one's newer sibling
+        if (tree) memcpy(hierarchy, hs + 16 + (size_t)mc * 8, (size_t)K * 16);
+        else
+            for (int j = 0; j < K; j++) {
+                hierarchy[4 * j] = j + 1 < K ? j + 1 : -1;
+                hierarchy[4 * j + 1] = j - 1;
+                hierarchy[4 * j + 2] = -1;
+                hierarchy[4 * j + 3] = -1;
+            }
+    }
     const int32_t* hp = reinterpret_cast<const int32_t*>(hs + hdr_pad);
     if (points && (size_t)P > spec_pts) {
         hs = (uint8_t*)vp_hstage(ctx, (size_t)P * 8 + 256);
@@ -1386,6 +1402,31 @@ int vp_find_contours_dev(vp_ctx* ctx, const uint8_t* d_src, size_t src_stride, i
                          int64_t max_points, int32_t* counts, uint8_t* is_hole, int max_contours, int32_t* n_contours, int64_t* n_points)
 {
     return find_contours_impl(ctx, d_src, true, src_stride, w, h, mode, method, points, max_points, counts, is_hole, max_contours, n_contours, n_points);
+}
+
+// the same with the hierarchy: modes VP_RETR_CCOMP / VP_RETR_TREE as well (vp.h)
+int vp_find_contours_tree_u8(vp_ctx* ctx, const uint8_t* src, size_t src_stride, int w, int h, int mode, int method, int32_t* points,
+                             int64_t max_points, int32_t* counts, uint8_t* is_hole, int max_contours, int32_t* n_contours, int64_t* n_points,
+                             int32_t* hierarchy)
+{
+    return find_contours_impl(ctx, src, false, src_stride, w, h, mode, method, points, max_points, counts, is_hole, max_contours, n_contours, n_points,
+                              nullptr, hierarchy, true);
+}
+
+int vp_find_contours_tree_dev(vp_ctx* ctx, const uint8_t* d_src, size_t src_stride, int w, int h, int mode, int method, int32_t* points,
+                              int64_t max_points, int32_t* counts, uint8_t* is_hole, int max_contours, int32_t* n_contours, int64_t* n_points,
+                              int32_t* hierarchy)
+{
+    return find_contours_impl(ctx, d_src, true, src_stride, w, h, mode, method, points, max_points, counts, is_hole, max_contours, n_contours, n_points,
+                              nullptr, hierarchy, true);
+}
+
+int vp_find_contours_tree_bits_dev(vp_ctx* ctx, const unsigned long long* d_bits, int w, int h, int mode, int method, int32_t* points,
+                                   int64_t max_points, int32_t* counts, uint8_t* is_hole, int max_contours, int32_t* n_contours, int64_t* n_points,
+                                   int32_t* hierarchy)
+{
+    return find_contours_impl(ctx, nullptr, true, 0, w, h, mode, method, points, max_points, counts, is_hole, max_contours, n_contours, n_points,
+                              reinterpret_cast<const u64*>(d_bits), hierarchy, true);
 }
 
 unsigned int vp_contours_last_heads(vp_ctx* ctx)

@@ -38,6 +38,7 @@
 #include <cstdlib>
 #include <algorithm>
 #include <vector>
+#include <hipcub/device/device_radix_sort.hpp>     // (vp_contours.inl: the children of each border in scan order, RETR_CCOMP / RETR_TREE)
 
 struct ccl_acc {   // 48 B
     u32 area;

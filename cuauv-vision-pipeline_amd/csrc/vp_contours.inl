@@ -293,23 +293,16 @@ __device__ __forceinline__ int ct_head_type(int s, int t, int x, int y, u32 R)
 __device__ __forceinline__ u32 ct_key_w(const ccl_geom& G, int y, int x) { return ((u32)y * (u32)(G.w + 1) + (u32)x) << 1; }
 __device__ __forceinline__ u32 ct_key_e(const ccl_geom& G, int y, int x) { return (((u32)y * (u32)(G.w + 1) + (u32)x + 1u) << 1) | 1u; }
 
-// RETR_EXTERNAL: what lies left of a possible first pixel (y, x) in its row: CT_FRAME, or a head of the border that owns the E crack
-// of the first foreground pixel met (the first head at or after the state that sweeps that crack)
+// the first head at or after the state of foreground pixel (y, x) that sweeps its crack in direction d (0: E, 4: W)
 template <bool SPARSE>
-__device__ __forceinline__ u32 ct_left_of(const ccl_geom& G, const u64* __restrict__ fb, const u64* __restrict__ hm, const u32* __restrict__ hb,
-                                          int y, int x)
+__device__ __forceinline__ u32 ct_walk_to_head(const ccl_geom& G, const u64* __restrict__ fb, const u64* __restrict__ hm, const u32* __restrict__ hb,
+                                               int y, int x, int d)
 {
-    const u64* row = fb + (size_t)y * G.ww;
-    int j = x >> 6;
-    u64 m = row[j] & ((1ull << (x & 63)) - 1ull);
-    while (!m && j > 0) m = row[--j];
-    if (!m) return CT_FRAME;
-    x = 64 * j + 63 - __clzll((long long)m);
     ct_tile T;
     ct_tile_load(G, fb, y - 3, x - 3, T);
     u32 R = ct_ring(T, y, x);
     if (!R) return ct_head_index(hm, hb, y * G.ww + (x >> 6), x & 63, 0);      // a pixel on its own: its one head is listed with the W heads
-    int s = ct_first_cw(R, 0);
+    int s = ct_first_cw(R, d);
     for (long long guard = 8ll * G.w * G.h + 16; guard > 0; guard--) {
         const int t = __ffs((int)((R | (R << 8)) >> (s + 1))) - 1;
         const int ht = ct_head_type<SPARSE>(s, t, x, y, R);
@@ -324,6 +317,34 @@ __device__ __forceinline__ u32 ct_left_of(const ccl_geom& G, const u64* __restri
         R = ct_ring(T, y, x);
     }
     return CT_FRAME;       // (not reached: every border has a head)
+}
+
+// RETR_EXTERNAL: what lies left of a possible first pixel (y, x) in its row: CT_FRAME, or a head of the border that owns the E crack
+// of the first foreground pixel met (the first head at or after the state that sweeps that crack)
+template <bool SPARSE>
+__device__ __forceinline__ u32 ct_left_of(const ccl_geom& G, const u64* __restrict__ fb, const u64* __restrict__ hm, const u32* __restrict__ hb,
+                                          int y, int x)
+{
+    const u64* row = fb + (size_t)y * G.ww;
+    int j = x >> 6;
+    u64 m = row[j] & ((1ull << (x & 63)) - 1ull);
+    while (!m && j > 0) m = row[--j];
+    if (!m) return CT_FRAME;
+    return ct_walk_to_head<SPARSE>(G, fb, hm, hb, y, 64 * j + 63 - __clzll((long long)m), 0);
+}
+
+// RETR_CCOMP / RETR_TREE, a hole border starting at foreground pixel (y, x): walk left along the row to the first background pixel;
+// the W crack right of it (or the frame's, at x = 0) belongs to another border of the same component - a head of that border
+template <bool SPARSE>
+__device__ __forceinline__ u32 ct_hole_left_of(const ccl_geom& G, const u64* __restrict__ fb, const u64* __restrict__ hm, const u32* __restrict__ hb,
+                                               int y, int x)
+{
+    const u64* row = fb + (size_t)y * G.ww;
+    int j = x >> 6;
+    u64 m = ~row[j] & ((2ull << (x & 63)) - 1ull);       // background at or left of x (x itself is foreground)
+    while (!m && j > 0) m = ~row[--j];
+    const int x0 = m ? 64 * j + 64 - __clzll((long long)m) : 0;
+    return ct_walk_to_head<SPARSE>(G, fb, hm, hb, y, x0, 4);
 }
 
 // one thread per head: follow the border from the head's state to the next head.
@@ -1126,6 +1147,169 @@ __global__ __launch_bounds__(1024) void k_ctm_scan(ctj_args A)
         __syncthreads();
     }
 }
+
+// ---- RETR_CCOMP / RETR_TREE: the hierarchy (one image) ----------------------------------------------------------------------
+// Runs between the bookkeeping (which treats the mode as RETR_LIST: every border returned, ranked in scan order, its counts and offsets
+// in workspace arrays) and k_ct_seg<true>, which writes every point where those offsets say - the caller finds each contour through
+// its offset, so the points stay where they are and only the per-contour rows are permuted.  Borders i < N in scan order:
+//   k_ctt_parent  the look to the left from the border's start (ct_left_of / ct_hole_left_of) -> the head owning the crack met -> its
+//                 leader (node[] after step (4)) -> its scan rank o (hrank[]).  Outer start: o a hole -> parent o; o outer -> o's
+//                 parent.  Hole start: o outer -> parent o; o a hole -> o's parent.  RETR_CCOMP: an outer border has none.
+//   k_ctt_jump_par  "o's parent" by pointer jumping; the chains strictly decrease in scan order (a parent starts before its children)
+//   k_ctt_keys    sort key = parent + 1 (0: top level) for a stable radix sort by key: the children of each border in scan order
+//   k_ctt_links   newest child, next older and next newer sibling
+//   k_ctt_tour    the Euler tour of the tree (a root above the top level), newest child first; an enter edge weighs 1
+//   k_ctt_jump_tour list ranking on (next, enter edges from here to the end) - pre-order index and subtree size of every border
+//   k_ctt_out     rows in the caller's order (pre-order), the per-contour arrays in device order (reversed pre-order)
+// Rounds of pointer jumping, not levels of the tree: concentric rings 500 deep cost what two do.
+#define CTT_FIN 0x80000000u      // par[]: the value is the parent (or CTT_NOPAR), not a border whose parent is the answer
+#define CTT_NOPAR 0xffffffffu
+struct ctt_args {
+    ccl_geom G;
+    const u64 *bits, *hmaps;
+    const u32 *hbase, *hrank, *starts;
+    const unsigned long long* node;
+    const ct_frame_out* out;
+    int max_contours, mode;
+    u32 *par, *key, *val, *skey, *sval, *fc, *ns, *nw;
+    unsigned long long* tour;
+    const int32_t *tcounts, *toffsets;
+    const uint8_t* thole;
+    int32_t *counts, *offsets, *hier;
+    uint8_t* hole;
+    ct_mirror M;                 // counts / offsets / is_hole of the caller's pinned buffer (NULL: none)
+    int32_t* mhier;              // the rows, likewise
+    int hops;
+};
+__device__ __forceinline__ int ctt_n(const ctt_args& A)           // borders of the image; -1: nothing to do (deferred, or beyond capacity)
+{
+    const int N = A.out->n_contours;
+    return (N < 0 || N > A.max_contours) ? -1 : N;
+}
+
+template <bool SPARSE>
+__global__ __launch_bounds__(256) void k_ctt_parent(ctt_args A)
+{
+    const int N = ctt_n(A);
+    const int i = blockIdx.x * 256 + threadIdx.x;
+    if (N < 0 || i > N) return;
+    A.fc[i] = CT_NONE;                                    // (i == N: the root above the top level)
+    if (i == N) return;
+    const u32 st = A.starts[i];
+    const bool hole = st >> 31;
+    u32 p = CTT_NOPAR;
+    if (hole || A.mode == 3) {
+        const int pix = (int)(st & 0x7fffffffu);
+        const int y = pix / A.G.w, x = pix - y * A.G.w;
+        const u32 e = hole ? ct_hole_left_of<SPARSE>(A.G, A.bits, A.hmaps, A.hbase, y, x) : ct_left_of<SPARSE>(A.G, A.bits, A.hmaps, A.hbase, y, x);
+        if (e != CT_FRAME) {
+            const u32 lead = (u32)(A.node[e] >> 32) & ~CT_TERM;
+            const u32 o = A.hrank[lead];
+            if (o < (u32)N && o != (u32)i) {
+                const bool ohole = A.starts[o] >> 31;
+                p = (hole != ohole) ? (o | CTT_FIN) : o;  // a border of the other kind is the parent; one of the same kind shares it
+            }
+        }
+    }
+    A.par[i] = p;
+}
+
+// in place: a value read is always a true statement (the parent, or a border whose parent is the same), older or newer
+__global__ __launch_bounds__(256) void k_ctt_jump_par(ctt_args A)
+{
+    const int N = ctt_n(A);
+    for (int i = blockIdx.x * 256 + threadIdx.x; i < N; i += gridDim.x * 256) {
+        u32 v = ctj_gld(A.par + i);
+        if (v & CTT_FIN) continue;
+        for (int h = 0; h < A.hops && !(v & CTT_FIN); h++) v = ctj_gld(A.par + v);
+        ctj_gst(A.par + i, v);
+    }
+}
+
+__global__ __launch_bounds__(256) void k_ctt_keys(ctt_args A)
+{
+    const int N = ctt_n(A);
+    const int i = blockIdx.x * 256 + threadIdx.x;
+    if (i >= A.max_contours) return;
+    u32 k = (u32)A.max_contours + 1u;                    // (past the borders: sorted behind them)
+    if (N >= 0 && i < N) {
+        const u32 p = A.par[i];
+        k = p == CTT_NOPAR ? 0u : (p & ~CTT_FIN) + 1u;
+    }
+    A.key[i] = k;
+    A.val[i] = (u32)i;
+}
+
+__global__ __launch_bounds__(256) void k_ctt_links(ctt_args A)
+{
+    const int N = ctt_n(A);
+    const int i = blockIdx.x * 256 + threadIdx.x;
+    if (i >= N) return;
+    const u32 g = A.skey[i], v = A.sval[i];
+    const bool newest = i + 1 == N || A.skey[i + 1] != g;
+    if (newest) A.fc[g == 0 ? (u32)N : g - 1u] = v;
+    A.ns[v] = (i > 0 && A.skey[i - 1] == g) ? A.sval[i - 1] : CT_NONE;
+    A.nw[v] = newest ? CT_NONE : A.sval[i + 1];
+}
+
+// tour[v] = enter v, tour[N + 1 + v] = leave v (v = N: the root); (next | CT_TERM at the end) << 32 | weight
+__global__ __launch_bounds__(256) void k_ctt_tour(ctt_args A)
+{
+    const int N = ctt_n(A);
+    const int e = blockIdx.x * 256 + threadIdx.x;
+    if (N < 0 || e >= 2 * N + 2) return;
+    unsigned long long t;
+    if (e <= N) {
+        const u32 c = A.fc[e];
+        t = ((unsigned long long)(c != CT_NONE ? c : (u32)(N + 1 + e)) << 32) | 1u;
+    } else if (e == 2 * N + 1) {
+        t = (unsigned long long)CT_TERM << 32;
+    } else {
+        const u32 v = (u32)(e - N - 1);
+        const u32 s = A.ns[v], p = A.par[v];
+        const u32 up = p == CTT_NOPAR ? (u32)N : (p & ~CTT_FIN);
+        t = (unsigned long long)(s != CT_NONE ? s : (u32)N + 1u + up) << 32;
+    }
+    A.tour[e] = t;
+}
+
+__global__ __launch_bounds__(256) void k_ctt_jump_tour(ctt_args A)
+{
+    const int N = ctt_n(A);
+    for (int e = blockIdx.x * 256 + threadIdx.x; e < 2 * N + 2; e += gridDim.x * 256)
+        for (int h = 0; h < A.hops; h++)
+            if (!ctj_dist_step<false>(A.tour, (u32)e)) break;
+}
+
+__global__ __launch_bounds__(256) void k_ctt_out(ctt_args A)
+{
+    const int N = ctt_n(A);
+    const int i = blockIdx.x * 256 + threadIdx.x;
+    if (i >= N) return;
+    // pre-order index = enter edges before this one (the root's is -1); subtree size = enter edges between entering and leaving
+    const u32 din = (u32)A.tour[i], dout = (u32)A.tour[N + 1 + i];
+    const int pre = N - (int)din;
+    if (pre < 0 || pre >= N) return;                      // (tables that do not add up must not turn into a write outside the rows)
+    const int slot = N - 1 - pre;
+    A.counts[slot] = A.tcounts[i];
+    A.offsets[slot] = A.toffsets[i];
+    A.hole[slot] = A.thole[i];
+    const u32 s = A.ns[i], w = A.nw[i], p = A.par[i];
+    int32_t row[4];
+    row[0] = s != CT_NONE ? N - (int)(u32)A.tour[s] : -1;
+    row[1] = w != CT_NONE ? N - (int)(u32)A.tour[w] : -1;
+    row[2] = din - dout > 1u ? pre + 1 : -1;
+    row[3] = p != CTT_NOPAR ? N - (int)(u32)A.tour[p & ~CTT_FIN] : -1;
+    for (int c = 0; c < 4; c++) A.hier[4 * pre + c] = row[c];
+    if (A.M.counts) {
+        A.M.counts[slot] = A.tcounts[i];
+        A.M.offsets[slot] = A.toffsets[i];
+        A.M.hole[slot] = A.thole[i];
+    }
+    if (A.mhier)
+        for (int c = 0; c < 4; c++) A.mhier[4 * pre + c] = row[c];
+}
+
 #undef dx8
 #undef dy8
 
@@ -1187,6 +1371,27 @@ int vpk_contour_features(vp_ctx* ctx, const int32_t* d_info, const int32_t* d_co
     return VP_OK;
 }
 
+// sort key = parent + 1 in [0, max_contours], max_contours + 1 past the borders
+static int ctt_key_bits(int max_contours)
+{
+    int b = 1;
+    while (b < 31 && ((u32)max_contours + 1u) >> b) b++;
+    return b;
+}
+
+size_t vp_contour_tree_ws_bytes(int max_contours)
+{
+    const size_t mc = (size_t)max_contours;
+    size_t sort_bytes = 0;
+    u32* p = nullptr;
+    if (hipcub::DeviceRadixSort::SortPairs(nullptr, sort_bytes, p, p, p, p, max_contours, 0, ctt_key_bits(max_contours)) != hipSuccess) {
+        (void)hipGetLastError();
+        sort_bytes = mc * 16 + (1 << 20);
+    }
+    return 2 * vp_align(mc * 4) + vp_align(mc) + 8 * vp_align(mc * 4) + vp_align((mc + 1) * 4) + vp_align((2 * mc + 2) * 8) + vp_align(sort_bytes) +
+           4096;
+}
+
 size_t vp_contours_ws_bytes(int w, int h, int n, int max_contours)
 {
     const size_t words = (size_t)n * h * vp_ww(w);
@@ -1226,9 +1431,10 @@ uint32_t vp_ct_batch_hint(vp_ctx* ctx)
 // d_nheads_out (nullable, [n]): the frames' head counts.
 int vpk_find_contours(vp_ctx* ctx, const u64* d_bits, int w, int h, int n, int mode, int method, int32_t* d_counts, uint8_t* d_is_hole,
                       int32_t* d_offsets, int32_t* d_points, int max_contours, long long max_points, int32_t* d_info, bool many_heads,
-                      uint32_t* d_nheads_out, const vp_contour_mirror* host, bool defer_big)
+                      uint32_t* d_nheads_out, const vp_contour_mirror* host, bool defer_big, int32_t* d_hier)
 {
-    if (mode != 0 && mode != 1) return vp_fail(ctx, VP_ERR_INVALID, "contour mode");
+    const bool tree = (mode == 2 || mode == 3) && d_hier && n == 1;
+    if (mode != 0 && mode != 1 && !tree) return vp_fail(ctx, VP_ERR_INVALID, "contour mode");
     if (method != 1 && method != 2) return vp_fail(ctx, VP_ERR_INVALID, "contour approximation");
     if ((size_t)w * h >= (1u << 29)) return vp_fail(ctx, VP_ERR_INVALID, "contours: image too large");
     ctj_args A;
@@ -1256,19 +1462,55 @@ int vpk_find_contours(vp_ctx* ctx, const u64* d_bits, int w, int h, int n, int m
     if (!hmaps || !hbase || !cnt8 || !head_pix || !A.hrank || !hkey || !A.hext || !A.node || !A.node2 || !A.starts || !A.shead || !A.aux || !partsum ||
         !A.flags || !A.csum)
         return vp_fail(ctx, VP_ERR_NOMEM, "contour workspace");
+    // RETR_CCOMP / RETR_TREE: the bookkeeping runs as for RETR_LIST into workspace arrays, the hierarchy pass permutes them into the caller's
+    ctt_args T;
+    size_t sort_bytes = 0;
+    void* sort_tmp = nullptr;
+    if (tree) {
+        const size_t mc = (size_t)max_contours;
+        T.tcounts = (int32_t*)vp_ws_take(ctx, mc * 4);
+        T.toffsets = (int32_t*)vp_ws_take(ctx, mc * 4);
+        T.thole = (uint8_t*)vp_ws_take(ctx, mc);
+        T.par = (u32*)vp_ws_take(ctx, mc * 4);
+        T.key = (u32*)vp_ws_take(ctx, mc * 4);
+        T.val = (u32*)vp_ws_take(ctx, mc * 4);
+        T.skey = (u32*)vp_ws_take(ctx, mc * 4);
+        T.sval = (u32*)vp_ws_take(ctx, mc * 4);
+        T.fc = (u32*)vp_ws_take(ctx, (mc + 1) * 4);
+        T.ns = (u32*)vp_ws_take(ctx, mc * 4);
+        T.nw = (u32*)vp_ws_take(ctx, mc * 4);
+        T.tour = (unsigned long long*)vp_ws_take(ctx, (2 * mc + 2) * 8);
+        VP_HIP(ctx, hipcub::DeviceRadixSort::SortPairs(nullptr, sort_bytes, T.key, T.skey, T.val, T.sval, max_contours, 0, ctt_key_bits(max_contours),
+                                                       ctx->stream));
+        sort_tmp = vp_ws_take(ctx, sort_bytes);
+        if (!T.tcounts || !T.toffsets || !T.thole || !T.par || !T.key || !T.val || !T.skey || !T.sval || !T.fc || !T.ns || !T.nw || !T.tour || !sort_tmp)
+            return vp_fail(ctx, VP_ERR_NOMEM, "contour hierarchy workspace");
+    }
     const size_t jump_lds = (size_t)CTJ_LDS_HEADS * 16;
     if (!ctx->ct_lds_set) {                               // (per context = per device: the attribute belongs to the device's copy of the kernel)
         VP_HIP(ctx, hipFuncSetAttribute(reinterpret_cast<const void*>(k_ct_jump), hipFuncAttributeMaxDynamicSharedMemorySize, (int)jump_lds));
         ctx->ct_lds_set = 1;
     }
     A.hkey = hkey; A.hbase = hbase; A.cnt8 = cnt8; A.head_pix = head_pix; A.hcap = hcap;
-    A.counts = d_counts; A.is_hole = d_is_hole; A.offsets = d_offsets; A.points = d_points;
+    A.counts = tree ? const_cast<int32_t*>(T.tcounts) : d_counts;
+    A.is_hole = tree ? const_cast<uint8_t*>(T.thole) : d_is_hole;
+    A.offsets = tree ? const_cast<int32_t*>(T.toffsets) : d_offsets;
+    A.points = d_points;
     A.out = reinterpret_cast<ct_frame_out*>(d_info);
-    A.max_contours = max_contours; A.max_points = max_points; A.mode = mode; A.lds_heads = CTJ_LDS_HEADS; A.nheads_out = d_nheads_out;
+    A.max_contours = max_contours; A.max_points = max_points; A.mode = mode == 0 ? 0 : 1; A.lds_heads = CTJ_LDS_HEADS; A.nheads_out = d_nheads_out;
     A.hops = 3;
     A.defer_big = (defer_big && n == 1 && !many_heads) ? 1 : 0;
     A.mirror = ct_mirror{nullptr, nullptr, nullptr, nullptr, nullptr, 0};
     if (host && n == 1) A.mirror = ct_mirror{host->info, host->counts, host->offsets, host->is_hole, host->points, host->points_cap};
+    if (tree) {
+        T.M = A.mirror;
+        T.mhier = host ? host->hier : nullptr;
+        A.mirror.counts = nullptr; A.mirror.offsets = nullptr; A.mirror.hole = nullptr;     // (the rows the bookkeeping writes are not the caller's order)
+        T.G = A.G; T.bits = d_bits; T.hmaps = hmaps; T.hbase = hbase; T.hrank = A.hrank; T.starts = A.starts; T.node = A.node; T.out = A.out;
+        T.max_contours = max_contours; T.mode = mode; T.counts = d_counts; T.offsets = d_offsets; T.hole = d_is_hole; T.hier = d_hier; T.hops = 3;
+    }
+    const int seg_mode = A.mode;
+    int32_t* seg_offsets = A.offsets;
     hipStream_t s = ctx->stream;
     vp_prof_scope ps(ctx, VPK_OTHER);
     const dim3 wgrid((unsigned)((nwords + 255) / 256), (unsigned)n);
@@ -1283,7 +1525,7 @@ int vpk_find_contours(vp_ctx* ctx, const u64* d_bits, int w, int h, int n, int m
     else hipLaunchKernelGGL(k_ct_headmaps<false>, wgrid, dim3(256), 0, s, d_bits, G, hmaps, partsum, cnt8);
     hipLaunchKernelGGL(k_ct_prefix, wgrid, dim3(256), 0, s, hmaps, 4, nwords, partsum, hbase, &A.aux->nheads, 2, w, G.ww, head_pix, hcap, cnt8,
                        (n > 1 || !host) ? vp_ct_hint_slots(ctx, n) : nullptr);
-#define CT_SEG_ARGS d_bits, G, hmaps, hbase, head_pix, A.hrank, hcap, A.aux, A.node, hkey, A.hext, mode, method, d_offsets, d_points, max_contours, max_points
+#define CT_SEG_ARGS d_bits, G, hmaps, hbase, head_pix, A.hrank, hcap, A.aux, A.node, hkey, A.hext, seg_mode, method, seg_offsets, d_points, max_contours, max_points
     const u32 skip_above = A.defer_big ? (u32)CTJ_LDS_HEADS : 0u;
     if (many_heads) hipLaunchKernelGGL((k_ct_seg<false, true>), hgrid, dim3(256), 0, s, CT_SEG_ARGS, (int32_t*)nullptr, 0ll, skip_above);
     else hipLaunchKernelGGL((k_ct_seg<false, false>), hgrid, dim3(256), 0, s, CT_SEG_ARGS, (int32_t*)nullptr, 0ll, skip_above);
@@ -1297,7 +1539,7 @@ int vpk_find_contours(vp_ctx* ctx, const u64* d_bits, int w, int h, int n, int m
         const dim3 mg((unsigned)std::max(32, std::min(1024, 8192 / n)), (unsigned)n), sg((unsigned)std::max(8, std::min(256, 2048 / n)), (unsigned)n);
         hipLaunchKernelGGL((k_ctm<CTM_LEAD_INIT>), mg, dim3(256), 0, s, A, 0);
         for (int i = 1; i <= rounds; i++) hipLaunchKernelGGL((k_ctm<CTM_LEAD>), mg, dim3(256), 0, s, A, i);
-        if (mode == 0) {
+        if (A.mode == 0) {
             hipLaunchKernelGGL((k_ctm<CTM_EXT_INIT>), mg, dim3(256), 0, s, A, 0);
             for (int i = 1; i <= rounds; i++) hipLaunchKernelGGL((k_ctm<CTM_EXT>), mg, dim3(256), 0, s, A, CTM_SEQ + i);
         }
@@ -1309,6 +1551,21 @@ int vpk_find_contours(vp_ctx* ctx, const u64* d_bits, int w, int h, int n, int m
         for (int i = 1; i <= rounds; i++) hipLaunchKernelGGL((k_ctm<CTM_DIST>), mg, dim3(256), 0, s, A, 2 * CTM_SEQ + i);
         hipLaunchKernelGGL((k_ctm_sums<1>), sg, dim3(1024), 0, s, A);
         hipLaunchKernelGGL((k_ctm_scan<1>), sg, dim3(1024), 0, s, A);
+    }
+    if (tree) {
+        int rounds = 2;
+        for (size_t reach = 1; reach < 2 * (size_t)max_contours + 2; reach *= (size_t)(T.hops + 1)) rounds++;
+        const unsigned nb = (unsigned)((max_contours + 256) / 256), tb = (unsigned)((2 * (size_t)max_contours + 2 + 255) / 256);
+        const unsigned jb = std::min(nb, 1024u), jtb = std::min(tb, 1024u);
+        if (many_heads) hipLaunchKernelGGL(k_ctt_parent<true>, dim3(nb), dim3(256), 0, s, T);
+        else hipLaunchKernelGGL(k_ctt_parent<false>, dim3(nb), dim3(256), 0, s, T);
+        for (int i = 0; i < rounds; i++) hipLaunchKernelGGL(k_ctt_jump_par, dim3(jb), dim3(256), 0, s, T);
+        hipLaunchKernelGGL(k_ctt_keys, dim3(nb), dim3(256), 0, s, T);
+        VP_HIP(ctx, hipcub::DeviceRadixSort::SortPairs(sort_tmp, sort_bytes, T.key, T.skey, T.val, T.sval, max_contours, 0, ctt_key_bits(max_contours), s));
+        hipLaunchKernelGGL(k_ctt_links, dim3(nb), dim3(256), 0, s, T);
+        hipLaunchKernelGGL(k_ctt_tour, dim3(tb), dim3(256), 0, s, T);
+        for (int i = 0; i < rounds; i++) hipLaunchKernelGGL(k_ctt_jump_tour, dim3(jtb), dim3(256), 0, s, T);
+        hipLaunchKernelGGL(k_ctt_out, dim3(nb), dim3(256), 0, s, T);
     }
     if (many_heads) hipLaunchKernelGGL((k_ct_seg<true, true>), hgrid, dim3(256), 0, s, CT_SEG_ARGS, A.mirror.points, A.mirror.cap, skip_above);
     else hipLaunchKernelGGL((k_ct_seg<true, false>), hgrid, dim3(256), 0, s, CT_SEG_ARGS, A.mirror.points, A.mirror.cap, skip_above);

@@ -235,10 +235,13 @@ int vpk_contour_features(vp_ctx* ctx, const int32_t* d_info, const int32_t* d_co
 // defer_big (n == 1, not many_heads): a frame with more heads than the one block's LDS tables hold reports n_contours = -1 and nothing
 // else; the caller repeats the pass with many_heads.
 uint32_t vp_ct_batch_hint(vp_ctx* ctx);      // largest head count the last batched pass reported (a guess; no synchronisation)
-struct vp_contour_mirror { int32_t* info; int32_t* counts; int32_t* offsets; uint8_t* is_hole; int32_t* points; long long points_cap; };
+// d_hier (n == 1 only, [max_contours][4]): RETR_CCOMP / RETR_TREE, which need it - the hierarchy rows in cv2's order (the contour arrays
+// stay in device order, reversed by the caller); the modes 0 / 1 take it as NULL.  host->hier: the same rows in the pinned buffer.
+struct vp_contour_mirror { int32_t* info; int32_t* counts; int32_t* offsets; uint8_t* is_hole; int32_t* points; long long points_cap; int32_t* hier; };
+size_t vp_contour_tree_ws_bytes(int max_contours);
 int vpk_find_contours(vp_ctx* ctx, const u64* d_bits, int w, int h, int n, int mode, int method, int32_t* d_counts, uint8_t* d_is_hole,
                       int32_t* d_offsets, int32_t* d_points, int max_contours, long long max_points, int32_t* d_info, bool many_heads = false,
-                      uint32_t* d_nheads_out = nullptr, const vp_contour_mirror* host = nullptr, bool defer_big = false);
+                      uint32_t* d_nheads_out = nullptr, const vp_contour_mirror* host = nullptr, bool defer_big = false, int32_t* d_hier = nullptr);
 int vpk_ccl(vp_ctx* ctx, const u64* d_bits, int w, int h, int n, int numbering, const vp_ccl_ws& ws, int32_t* d_labels,
             int32_t* d_stats, double* d_centroids, int max_labels, int32_t* d_nlabels);
 

@@ -21,7 +21,7 @@ CB_DEFAULT = CB_EQUALIZE_RGB | CB_HSV_CONTRAST | CB_EXTREMA_CLIPPING
 MORPH_ERODE, MORPH_DILATE, MORPH_OPEN, MORPH_CLOSE, MORPH_GRADIENT = 0, 1, 2, 3, 4
 SHAPE_RECT, SHAPE_CROSS, SHAPE_ELLIPSE = 0, 1, 2
 CCL_PIXEL, CCL_BLOCK2X2 = 1, 2
-RETR_EXTERNAL, RETR_LIST = 0, 1
+RETR_EXTERNAL, RETR_LIST, RETR_CCOMP, RETR_TREE = 0, 1, 2, 3
 CHAIN_APPROX_NONE, CHAIN_APPROX_SIMPLE = 1, 2
 CHAIN_MAX_MORPH = 8
 OPT_CHAIN_STREAMS = 1
@@ -152,6 +152,12 @@ _SIGS = {
     "vp_contours_last_heads": (C.c_uint, [C.c_void_p]),
     "vp_find_contours_bits_dev": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_int,
                                            C.POINTER(C.c_int32), C.POINTER(C.c_int64)]),
+    "vp_find_contours_tree_u8": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int64,
+                                           C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "vp_find_contours_tree_dev": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int64,
+                                            C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "vp_find_contours_tree_bits_dev": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int64, C.c_void_p,
+                                                 C.c_void_p, C.c_int, C.POINTER(C.c_int32), C.POINTER(C.c_int64), C.c_void_p]),
     "vp_memcpy_d2d_async": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t]),
     "vp_memcpy_h2d": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t]),
     "vp_draw_polylines_dev": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int]),

@@ -23,7 +23,7 @@ COLOR_LAB2BGR = COLOR_Lab2BGR = 56
 COLOR_BGR2Luv, COLOR_BGR2LUV = 50, 50     # named by modules/preprocessor.py:76; see DESIGN.md section 7 for what the stand-in does with it
 MORPH_RECT, MORPH_CROSS, MORPH_ELLIPSE = 0, 1, 2
 MORPH_ERODE, MORPH_DILATE, MORPH_OPEN, MORPH_CLOSE, MORPH_GRADIENT = 0, 1, 2, 3, 4
-RETR_EXTERNAL, RETR_LIST = 0, 1
+RETR_EXTERNAL, RETR_LIST, RETR_CCOMP, RETR_TREE = 0, 1, 2, 3
 CHAIN_APPROX_NONE, CHAIN_APPROX_SIMPLE = 1, 2
 CC_STAT_LEFT, CC_STAT_TOP, CC_STAT_WIDTH, CC_STAT_HEIGHT, CC_STAT_AREA = 0, 1, 2, 3, 4
 CV_8U = 0
@@ -116,8 +116,15 @@ def morphologyEx(src, op, kernel, dst=None, anchor=None, iterations=1, borderTyp
 
 
 def findContours(image, mode, method):
-    """-> (contours, hierarchy); hierarchy is None (RETR_EXTERNAL / RETR_LIST are flat)."""
-    return _feature.find_contours(image, int(mode), int(method)), None
+    """-> (contours, hierarchy).  RETR_CCOMP / RETR_TREE: cv2's hierarchy, int32 (1, N, 4) [next, prev, first_child, parent], and
+    ((), None) without contours; RETR_EXTERNAL / RETR_LIST: the hierarchy is None (they are flat)."""
+    mode, method = int(mode), int(method)
+    if mode not in (RETR_EXTERNAL, RETR_LIST, RETR_CCOMP, RETR_TREE):
+        raise error(f"findContours: retrieval mode {mode} is not implemented (RETR_FLOODFILL is out of scope)")
+    if mode in (RETR_CCOMP, RETR_TREE):
+        contours, hierarchy = _feature.find_contours(image, mode, method, with_hierarchy=True)
+        return (contours if len(contours) else ()), hierarchy
+    return _feature.find_contours(image, mode, method), None
 
 
 def connectedComponentsWithStats(image, connectivity=8, ltype=CV_32S):

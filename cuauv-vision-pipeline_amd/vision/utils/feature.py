@@ -245,9 +245,12 @@ def find_lines(mat: np.ndarray, rho: float, theta: float, threshold: int):
     return cartesian, polar
 
 
-def find_contours(mat: np.ndarray, mode: int = _vp.RETR_EXTERNAL, method: int = _vp.CHAIN_APPROX_SIMPLE, with_holes: bool = False):
+def find_contours(mat: np.ndarray, mode: int = _vp.RETR_EXTERNAL, method: int = _vp.CHAIN_APPROX_SIMPLE, with_holes: bool = False,
+                  with_hierarchy: bool = False):
     """cv2.findContours(mat, mode, method)[0] on the GPU (libvp vp_find_contours_u8): tuple of (N,1,2) int32 arrays of
-    (x, y) points, newest contour first like cv2."""
+    (x, y) points, newest contour first like cv2.  with_hierarchy: also cv2's hierarchy, int32 (1, N, 4) rows [next, prev,
+    first_child, parent] (None when there is no contour), through the vp_find_contours_tree_* entries, which take every mode
+    (RETR_EXTERNAL, RETR_LIST, RETR_CCOMP, RETR_TREE); returned last: (contours, hierarchy) or (contours, holes, hierarchy)."""
     mat = as_mat(mat)
     ctx = _vp.default_context()
     dev = None
@@ -280,7 +283,23 @@ def find_contours(mat: np.ndarray, mode: int = _vp.RETR_EXTERNAL, method: int = 
         _, pts, counts, holes = sc
         nc, npts = _vp.C.c_int32(0), _vp.C.c_int64(0)
         bits = getattr(dev, "_bits", None) if dev is not None else None
-        if bits is not None and dev._dev_ok and dev._ctx is ctx:
+        if with_hierarchy:
+            hier = getattr(_scratch, "hier", None)
+            if hier is None or len(hier) != max_c:
+                hier = _scratch.hier = np.empty((max_c, 4), np.int32)
+            if bits is not None and dev._dev_ok and dev._ctx is ctx:
+                _vp.check(_vp.lib().vp_find_contours_tree_bits_dev(ctx.handle, bits.ptr, w, h, int(mode), int(method), _vp.ptr(pts), max_p,
+                                                                   _vp.ptr(counts), _vp.ptr(holes), max_c, _vp.C.byref(nc), _vp.C.byref(npts),
+                                                                   _vp.ptr(hier)), ctx.handle)
+            elif dev is not None:
+                _vp.check(_vp.lib().vp_find_contours_tree_dev(ctx.handle, dev.dev_ptr, w, w, h, int(mode), int(method), _vp.ptr(pts), max_p,
+                                                              _vp.ptr(counts), _vp.ptr(holes), max_c, _vp.C.byref(nc), _vp.C.byref(npts),
+                                                              _vp.ptr(hier)), ctx.handle)
+            else:
+                _vp.check(_vp.lib().vp_find_contours_tree_u8(ctx.handle, _vp.ptr(mat), mat.strides[0], w, h, int(mode), int(method), _vp.ptr(pts),
+                                                             max_p, _vp.ptr(counts), _vp.ptr(holes), max_c, _vp.C.byref(nc), _vp.C.byref(npts),
+                                                             _vp.ptr(hier)), ctx.handle)
+        elif bits is not None and dev._dev_ok and dev._ctx is ctx:
             # the mask came with its bit plane (range_threshold) and has not been written to since: no packing launch
             _vp.check(_vp.lib().vp_find_contours_bits_dev(ctx.handle, bits.ptr, w, h, int(mode), int(method), _vp.ptr(pts), max_p,
                                                           _vp.ptr(counts), _vp.ptr(holes), max_c, _vp.C.byref(nc), _vp.C.byref(npts)), ctx.handle)
@@ -313,6 +332,9 @@ def find_contours(mat: np.ndarray, mode: int = _vp.RETR_EXTERNAL, method: int = 
             o += c
         out = ContourList(out)
         out._flat, out._counts = flat, counts[:k].copy()
+    if with_hierarchy:
+        hierarchy = hier[:k].reshape(1, k, 4).copy() if k else None
+        return (out, holes[:k].copy(), hierarchy) if with_holes else (out, hierarchy)
     return (out, holes[:k].copy()) if with_holes else out
 
 

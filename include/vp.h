@@ -178,7 +178,7 @@ int vp_ccl_u8(vp_ctx* ctx, const uint8_t* src_host, size_t src_stride, int w, in
  * cv2's order (last found first): counts[k] points of contour k, is_hole[k] (may be NULL), points = (x, y) int32 pairs
  * of all contours back to back.  *n_contours / *n_points are always the true totals; when either exceeds its capacity
  * nothing is copied out and the caller retries with larger buffers. */
-enum { VP_RETR_EXTERNAL = 0, VP_RETR_LIST = 1 };
+enum { VP_RETR_EXTERNAL = 0, VP_RETR_LIST = 1, VP_RETR_CCOMP = 2, VP_RETR_TREE = 3 };
 enum { VP_CHAIN_APPROX_NONE = 1, VP_CHAIN_APPROX_SIMPLE = 2 };
 int vp_find_contours_u8(vp_ctx* ctx, const uint8_t* src_host, size_t src_stride, int w, int h, int mode, int method,
                         int32_t* points_host, int64_t max_points, int32_t* counts_host, uint8_t* is_hole_host, int max_contours,
@@ -244,6 +244,23 @@ int vp_find_contours_bits_dev(vp_ctx* ctx, const unsigned long long* bits_dev, i
  * late).  It is what the next pass chooses the form of its bookkeeping by (one block per frame / launches over the chip) - a choice
  * the results do not depend on. */
 unsigned int vp_contours_last_heads(vp_ctx* ctx);
+/* cv2.findContours with its hierarchy: the three entries above with one more argument, hierarchy_host (4 int32 per contour, may be
+ * NULL), and all four modes.  VP_RETR_CCOMP / VP_RETR_TREE return the borders of VP_RETR_LIST (same points, start points, hole
+ * flags) in the pre-order of the Suzuki-Abe tree - top level first, siblings newest first - and the rows [next, prev, first_child,
+ * parent] (indices into the returned list, -1 for none) that cv2 returns as hierarchy[0].  TREE: the parent of an outer border is
+ * the hole border of the background region around it (none if that region reaches the frame), the parent of a hole border is the
+ * outer border of its component; CCOMP: every outer border is at the top level.  VP_RETR_EXTERNAL / VP_RETR_LIST give what the
+ * entries above give, with the flat rows [next, prev, -1, -1].  Totals and retries as above: the rows are filled when the contours
+ * are.  The entries above (and vp_chain_run_contours) keep rejecting modes 2 and 3. */
+int vp_find_contours_tree_u8(vp_ctx* ctx, const uint8_t* src_host, size_t src_stride, int w, int h, int mode, int method,
+                             int32_t* points_host, int64_t max_points, int32_t* counts_host, uint8_t* is_hole_host, int max_contours,
+                             int32_t* n_contours, int64_t* n_points, int32_t* hierarchy_host);
+int vp_find_contours_tree_dev(vp_ctx* ctx, const uint8_t* src_dev, size_t src_stride, int w, int h, int mode, int method,
+                              int32_t* points_host, int64_t max_points, int32_t* counts_host, uint8_t* is_hole_host, int max_contours,
+                              int32_t* n_contours, int64_t* n_points, int32_t* hierarchy_host);
+int vp_find_contours_tree_bits_dev(vp_ctx* ctx, const unsigned long long* bits_dev, int w, int h, int mode, int method,
+                                   int32_t* points_host, int64_t max_points, int32_t* counts_host, uint8_t* is_hole_host, int max_contours,
+                                   int32_t* n_contours, int64_t* n_points, int32_t* hierarchy_host);
 int vp_find_contours_dev(vp_ctx* ctx, const uint8_t* src_dev, size_t src_stride, int w, int h, int mode, int method,
                          int32_t* points_host, int64_t max_points, int32_t* counts_host, uint8_t* is_hole_host, int max_contours,
                          int32_t* n_contours, int64_t* n_points);
