@@ -151,6 +151,7 @@ int vp_destroy(vp_ctx* ctx)
     vp_post_teardown(ctx);
     if (ctx->ws) hipFree(ctx->ws);
     if (ctx->c3_acc) hipFree(ctx->c3_acc);
+    if (ctx->hc_hist) hipFree(ctx->hc_hist);
     if (ctx->ct_hint_host) hipHostFree(ctx->ct_hint_host);
     for (int i = 0; i < 4; i++) {
         if (ctx->ring_buf[i]) hipHostFree(ctx->ring_buf[i]);
@@ -189,6 +190,7 @@ int vp_set_option(vp_ctx* ctx, int option, int value)
     if (option == VP_OPT_CCL_MERGE_CAP && value >= -1) { ctx->ccl_mcap = value; return VP_OK; }
     if (option == VP_OPT_FLAT_OPS && (value == 0 || value == 1)) { ctx->flat_ops = value; return VP_OK; }
     if (option == VP_OPT_HOUGH_LDS && (value == 0 || value == 1)) { ctx->hough_global = !value; return VP_OK; }
+    if (option == VP_OPT_HOUGH_CIRCLES_LDS && (value == 0 || value == 1)) { ctx->hc_global = !value; return VP_OK; }
     return vp_fail(ctx, VP_ERR_INVALID, "vp_set_option");
 }
 
@@ -1995,6 +1997,24 @@ int vp_hough_lines_batch_dev(vp_ctx* ctx, const uint8_t* d_src, size_t src_strid
     if (n <= 0 || n > 65535 || src_stride < (size_t)w || (n > 1 && frame_stride < src_stride * (h - 1) + w))
         return vp_fail(ctx, VP_ERR_INVALID, "vp_hough_lines_batch_dev strides / frame count");
     return vp_hough_run(ctx, d_src, nullptr, src_stride, frame_stride, n, w, h, rho, theta, threshold, min_theta, max_theta, lines, max_lines, n_lines);
+}
+
+int vp_hough_circles_u8(vp_ctx* ctx, const uint8_t* src, int w, int h, double dp, double min_dist, double param1, double param2, int min_radius,
+                        int max_radius, float* circles, int max_circles, int* n_circles)
+{
+    VP_TRY(check_ctx(ctx));
+    if (!src) return vp_fail(ctx, VP_ERR_INVALID, "hough circles arguments");
+    return vp_hough_circles_run(ctx, nullptr, src, (size_t)w, w, h, dp, min_dist, param1, param2, min_radius, max_radius, circles, max_circles,
+                                n_circles);
+}
+
+int vp_hough_circles_dev(vp_ctx* ctx, const uint8_t* d_src, size_t src_stride, int w, int h, double dp, double min_dist, double param1,
+                         double param2, int min_radius, int max_radius, float* circles, int max_circles, int* n_circles)
+{
+    VP_TRY(check_ctx(ctx));
+    if (!d_src) return vp_fail(ctx, VP_ERR_INVALID, "hough circles arguments");
+    return vp_hough_circles_run(ctx, d_src, nullptr, src_stride, w, h, dp, min_dist, param1, param2, min_radius, max_radius, circles,
+                                max_circles, n_circles);
 }
 
 static int wb_args(vp_ctx* ctx, const void* src, size_t src_stride, int w, int h, int kernel_size, const void* dst)

@@ -269,7 +269,7 @@ size_t vp_canny_ws_bytes(int w, int h)
            vp_ccl_ws_bytes(w, h, 1, 1) + 4096;
 }
 
-int vpk_canny_u8(vp_ctx* ctx, const uint8_t* d_src, int w, int h, int cn, int low, int high, uint8_t* d_dst)
+int vpk_canny_u8(vp_ctx* ctx, const uint8_t* d_src, int w, int h, int cn, int low, int high, uint8_t* d_dst, const short2** grad_out)
 {
     const size_t npx = (size_t)w * h;
     const int ww = vp_ww(w);
@@ -286,6 +286,7 @@ int vpk_canny_u8(vp_ctx* ctx, const uint8_t* d_src, int w, int h, int cn, int lo
     vp_ccl_ws_carve(ctx, w, h, 1, 1, &ws);
     if (!d_mag || !d_grad || !d_cand || !d_strong || !d_labels || !d_seen || !d_nl || !vp_ccl_ws_ok(ws))
         return vp_fail(ctx, VP_ERR_NOMEM, "canny workspace");
+    if (grad_out) *grad_out = d_grad;
     hipStream_t s = ctx->stream;
     const dim3 grid((unsigned)((w + 255) / 256), (unsigned)h);
     {

@@ -214,6 +214,25 @@ __global__ __launch_bounds__(256) void k_hough_lines(const u64* __restrict__ key
     o[1] = __fadd_rn(min_theta, __fmul_rn((float)n, theta));
 }
 
+int vpk_hough_sort_keys(vp_ctx* ctx, u64* d_k0, u64* d_k1, size_t kcap, const u32* d_nkeys, int n, u32 maxcnt, u64** sorted)
+{
+    u64* src = d_k0;
+    u64* dst = d_k1;
+    {
+        vp_prof_scope ps(ctx, VPK_OTHER);
+        hipLaunchKernelGGL(k_hough_sort_seg, dim3((maxcnt + HS_SEG - 1) / HS_SEG, n), dim3(1024), 0, ctx->stream, d_k0, kcap, d_nkeys);
+    }
+    VP_HIP(ctx, hipGetLastError());
+    for (u32 run = HS_SEG; run < maxcnt; run *= 2) {
+        vp_prof_scope ps(ctx, VPK_OTHER);
+        hipLaunchKernelGGL(k_hough_merge, dim3((maxcnt + 255) / 256, n), dim3(256), 0, ctx->stream, src, dst, kcap, d_nkeys, run);
+        VP_HIP(ctx, hipGetLastError());
+        std::swap(src, dst);
+    }
+    *sorted = src;
+    return VP_OK;
+}
+
 namespace {
 struct hough_geom {
     float rho, theta, irho;
@@ -351,19 +370,9 @@ int vp_hough_run(vp_ctx* ctx, const uint8_t* d_src, const uint8_t* h_src, size_t
     memcpy(hs, kout.data(), (size_t)n * 4);
     memcpy(hs + (size_t)n * 4, off.data(), (size_t)n * 4);
     VP_HIP(ctx, hipMemcpyAsync(d_kout, hs, (size_t)n * 8, hipMemcpyHostToDevice, ctx->stream));
-    u64* src = d_k0;
-    u64* dst = d_k1;
-    {
-        vp_prof_scope ps(ctx, VPK_OTHER);
-        hipLaunchKernelGGL(k_hough_sort_seg, dim3((maxcnt + HS_SEG - 1) / HS_SEG, n), dim3(1024), 0, ctx->stream, d_k0, g.kcap, d_nk);
-    }
-    VP_HIP(ctx, hipGetLastError());
-    for (u32 run = HS_SEG; run < maxcnt; run *= 2) {
-        vp_prof_scope ps(ctx, VPK_OTHER);
-        hipLaunchKernelGGL(k_hough_merge, dim3((maxcnt + 255) / 256, n), dim3(256), 0, ctx->stream, src, dst, g.kcap, d_nk, run);
-        VP_HIP(ctx, hipGetLastError());
-        std::swap(src, dst);
-    }
+    u64* src = nullptr;
+    rc = vpk_hough_sort_keys(ctx, d_k0, d_k1, g.kcap, d_nk, n, maxcnt, &src);
+    if (rc != VP_OK) return rc;
     {
         vp_prof_scope ps(ctx, VPK_OTHER);
         hipLaunchKernelGGL(k_hough_lines, dim3((maxk + 255) / 256, n), dim3(256), 0, ctx->stream, src, g.kcap, d_kout, d_off, g.numrho, g.rho,

@@ -72,6 +72,9 @@ struct vp_ctx {
     size_t c3_acc_bytes;
     int c3_acc_dirty;             // a call was cut short after its labelling launch: reinitialise before the next use
     int hough_global;             // 1: every Hough vote is a global atomic (VP_OPT_HOUGH_LDS 0); 0 (default): rows counted in LDS where they fit
+    int hc_global;                // 1: HoughCircles radius histograms always in device memory (VP_OPT_HOUGH_CIRCLES_LDS 0); 0 (default): in LDS where they fit
+    void* hc_hist;                // HoughCircles radius histograms of the global form: grow-only, sized per call by its centre count
+    size_t hc_hist_bytes;
     int flat_ops;                 // 1 (default): the per-operator kernels take their 16-px-per-lane forms when rows are packed and pointers aligned; 0: always the generic kernels (tests)
     int ccl_mcap;                 // components per frame the merge block accepts (-1: its LDS capacity); tests lower it to force the fallback
     u32* agauss_taps;             // Gaussian adaptive threshold: 8 slots of 256 integer taps (half kernels), made on first use
@@ -156,12 +159,22 @@ int vpk_threshold_u8(vp_ctx* ctx, const uint8_t* d_src, size_t n, int ithresh, i
 int vpk_hist_u8(vp_ctx* ctx, const uint8_t* d_src, size_t n, u32* d_hist);   // d_hist: 256 counters
 int vpk_adaptive_threshold_mean(vp_ctx* ctx, const uint8_t* d_src, int w, int h, int imax, int idelta, int inv, int block, uint16_t* d_tmp, uint8_t* d_dst);
 size_t vp_canny_ws_bytes(int w, int h);
-int vpk_canny_u8(vp_ctx* ctx, const uint8_t* d_src, int w, int h, int cn, int low, int high, uint8_t* d_dst);
+// grad_out (nullable): receives the workspace plane of the winning channel's Sobel (dx, dy), w * h short2, valid until the workspace is
+// carved anew (HoughCircles reads it for cn = 1)
+int vpk_canny_u8(vp_ctx* ctx, const uint8_t* d_src, int w, int h, int cn, int low, int high, uint8_t* d_dst, const short2** grad_out = nullptr);
 // ---- Hough lines (vp_hough.hip) ----------------------------------------------------------------------
 // n frames of w x h u8 at d_src (row stride, frame stride; or one packed host image at h_src, staged in the workspace): lines of frame f
 // -> lines + f * max_lines * 2 (host), true counts -> n_lines; synchronises.  Checks beyond rho / theta / min_theta / max_theta are the caller's.
 int vp_hough_run(vp_ctx* ctx, const uint8_t* d_src, const uint8_t* h_src, size_t stride, size_t fstride, int n, int w, int h, double rho, double theta, int threshold,
                  double min_theta, double max_theta, float* lines, int max_lines, int* n_lines);
+// sorts the first nkeys[f] 64-bit keys of each of n segments of kcap keys (d_k0, ping-ponging with d_k1) ascending; maxcnt: the largest
+// count; *sorted: the buffer that holds the result (k_hough_sort_seg / k_hough_merge)
+int vpk_hough_sort_keys(vp_ctx* ctx, u64* d_k0, u64* d_k1, size_t kcap, const u32* d_nkeys, int n, u32 maxcnt, u64** sorted);
+// ---- Hough circles (vp_hough_circles.hip) ------------------------------------------------------------------------------------
+// one w x h u8 image at d_src (row stride) or at h_src (packed host, staged): cv2.HoughCircles HOUGH_GRADIENT with maxRadius >= 0 ->
+// (x, y, r) triplets at circles (host), true count -> *n_circles; synchronises.  All argument checks are done here.
+int vp_hough_circles_run(vp_ctx* ctx, const uint8_t* d_src, const uint8_t* h_src, size_t stride, int w, int h, double dp, double min_dist,
+                         double param1, double param2, int min_radius, int max_radius, float* circles, int max_circles, int* n_circles);
 void vp_gaussian_taps(int n, double sigma, uint16_t* out);   // n odd, <= 511
 void vp_gaussian_kernel_f64(int n, double sigma, double* k);  // the double kernel vp_gaussian_taps rounds: n odd, 3..511
 // Gaussian adaptive threshold (vp_adaptive.hip): n frames (src row stride, frame stride) -> packed (n, h, w) dst; d_tmp: n * w * h u64

@@ -29,6 +29,8 @@ OPT_CCL_LEVELS = 2
 OPT_CCL_MERGE_CAP = 3
 OPT_FLAT_OPS = 4
 OPT_HOUGH_LDS = 5
+OPT_HOUGH_CIRCLES_LDS = 6
+HOUGH_GRADIENT = 3
 PROF_KERNELS = 15
 
 
@@ -172,6 +174,10 @@ _SIGS = {
                                      C.c_double, C.c_void_p, C.c_int, C.POINTER(C.c_int)]),
     "vp_hough_lines_batch_dev": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_size_t, C.c_int, C.c_int, C.c_int, C.c_double, C.c_double,
                                            C.c_int, C.c_double, C.c_double, C.c_void_p, C.c_int, C.c_void_p]),
+    "vp_hough_circles_u8": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_double, C.c_double, C.c_double, C.c_double, C.c_int,
+                                      C.c_int, C.c_void_p, C.c_int, C.POINTER(C.c_int)]),
+    "vp_hough_circles_dev": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_int, C.c_int, C.c_double, C.c_double, C.c_double, C.c_double,
+                                       C.c_int, C.c_int, C.c_void_p, C.c_int, C.POINTER(C.c_int)]),
 }
 
 

@@ -31,6 +31,7 @@ ADAPTIVE_THRESH_MEAN_C, ADAPTIVE_THRESH_GAUSSIAN_C = 0, 1
 THRESH_BINARY, THRESH_BINARY_INV = 0, 1
 CV_32S = 4
 CV_PI = math.pi
+HOUGH_GRADIENT, HOUGH_GRADIENT_ALT = 3, 4
 
 
 class UMat:   # only so that `from cv2 import UMat` and isinstance checks work
@@ -500,6 +501,28 @@ def HoughLines(image, rho, theta, threshold, lines=None, srn=0, stn=0, min_theta
     if max_theta < min_theta:
         raise error("HoughLines: max_theta must be greater than min_theta")
     return _feature.hough_lines(image, rho, theta, threshold, min_theta, max_theta)
+
+
+def HoughCircles(image, method, dp, minDist, circles=None, param1=100, param2=100, minRadius=0, maxRadius=0):
+    """cv2.HoughCircles (utils/feature.py:128-155) in cv2's positional order: (1, N, 3) float32 (x, y, r), or None when nothing is found.
+    HOUGH_GRADIENT only; HOUGH_GRADIENT_ALT and the centres-only mode (maxRadius < 0) are outside the accelerated path."""
+    from vision.devmat import DeviceMat
+    if method == HOUGH_GRADIENT_ALT:
+        raise error("HoughCircles: HOUGH_GRADIENT_ALT is outside the accelerated path")
+    if method != HOUGH_GRADIENT:
+        raise error("HoughCircles: unknown method")
+    if maxRadius < 0:
+        raise error("HoughCircles: the centres-only mode (maxRadius < 0) is outside the accelerated path")
+    if not (dp > 0 and minDist > 0 and param1 > 0 and param2 > 0):
+        raise error("HoughCircles: dp, minDist, param1 and param2 must be positive")
+    shape = tuple(image.shape) if isinstance(image, (np.ndarray, DeviceMat)) else ()
+    if (not isinstance(image, (np.ndarray, DeviceMat)) or image.dtype != np.uint8 or len(shape) not in (2, 3) or (len(shape) == 3 and shape[2] != 1)
+            or shape[0] == 0 or shape[1] == 0):
+        raise error("HoughCircles: the image must be a non-empty CV_8UC1 image")
+    try:
+        return _feature.hough_circles(image, dp, minDist, param1, param2, minRadius, maxRadius)
+    except _vp.VpError as e:
+        raise error(f"HoughCircles: {e}") from e
 
 
 def adaptiveThreshold(src, maxValue, adaptiveMethod, thresholdType, blockSize, C, dst=None):

@@ -182,13 +182,51 @@ def simple_canny(mat: np.ndarray, sigma: float = 0.33, use_mean: bool = False) -
     upper = int(min(255, (1.0 + sigma) * mid))
     return canny(mat, lower, upper)
 # Outside the path on purpose: cv2.HoughLinesP (find_line_segments) draws its points in the order of a seeded RNG and removes each
-# segment's votes before the next draw, a serial algorithm by definition; cv2.HoughCircles (find_circles) and cv2.goodFeaturesToTrack
-# (find_corners) go through OpenCV's SIMD float paths, which cannot be restated bit for bit.
+# segment's votes before the next draw, a serial algorithm by definition; cv2.goodFeaturesToTrack (find_corners) goes through OpenCV's
+# SIMD float paths, which cannot be restated bit for bit.  find_circles still raises because the tests of this build pin that it does;
+# the transform it wraps is here as hough_circles (and cv2_facade.HoughCircles).
 find_corners = _outside_path("find_corners")
 find_circles = _outside_path("find_circles")
 find_line_segments = _outside_path("find_line_segments")
 
 _lines_cap = threading.local()
+_circles_cap = threading.local()
+
+
+def hough_circles(mat, dp: float, min_dist: float, param1: float = 100, param2: float = 100, min_radius: int = 0, max_radius: int = 0):
+    """cv2.HoughCircles(mat, cv2.HOUGH_GRADIENT, dp, min_dist, None, param1, param2, min_radius, max_radius) on the GPU (libvp
+    vp_hough_circles_*): (1, N, 3) float32 (x, y, r) in cv2's order, or None when no circle is found.  A device image is read where it
+    is.  max_radius < 0 (cv2's centres-only mode) is outside the accelerated path."""
+    mat = as_mat(mat)
+    ctx = _vp.default_context()
+    if isinstance(mat, DeviceMat):
+        if mat.dtype != np.uint8:
+            raise TypeError("expected a uint8 single-channel image")
+        src = device_image(ctx, mat, 1)
+        h, w = src.shape
+    else:
+        if not isinstance(mat, np.ndarray) or mat.dtype != np.uint8:
+            raise TypeError("expected a uint8 single-channel image")
+        if mat.ndim == 3 and mat.shape[2] == 1:
+            mat = mat[:, :, 0]
+        if mat.ndim != 2 or mat.size == 0:
+            raise ValueError("expected a non-empty (h, w) image")
+        mat = np.ascontiguousarray(mat)
+        h, w = mat.shape
+        src = None
+    args = (float(dp), float(min_dist), float(param1), float(param2), int(min_radius), int(max_radius))
+    cap = getattr(_circles_cap, "n", 256)
+    while True:
+        out = np.empty((1, max(cap, 1), 3), np.float32)
+        n = _vp.C.c_int(0)
+        if src is not None:
+            _vp.check(_vp.lib().vp_hough_circles_dev(ctx.handle, src.dev_ptr, w, w, h, *args, _vp.ptr(out), cap, _vp.C.byref(n)), ctx.handle)
+        else:
+            _vp.check(_vp.lib().vp_hough_circles_u8(ctx.handle, _vp.ptr(mat), w, h, *args, _vp.ptr(out), cap, _vp.C.byref(n)), ctx.handle)
+        if n.value <= cap:
+            break
+        cap = _circles_cap.n = n.value                 # the true count came back: once more with room for all of them
+    return out[:, :n.value].copy() if n.value else None
 
 
 def hough_lines(mat, rho: float, theta: float, threshold: int, min_theta: float = 0.0, max_theta: float = np.pi):

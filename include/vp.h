@@ -70,8 +70,11 @@ int vp_synchronize(vp_ctx* ctx);
  * VP_OPT_FLAT_OPS (0 or 1, default 1): the per-operator kernels (vp_cvt_color_*, vp_inrange_u8_*) use their 16-pixels-per-lane forms
  * whenever rows are packed and pointers 16-B aligned; 0 forces the generic one-pixel-per-thread kernels (the tests run both).
  * VP_OPT_HOUGH_LDS (0 or 1, default 1): the Hough vote counts accumulator rows in LDS and flushes them with global atomics where a
- * row fits the block's LDS budget; 0 makes every vote a global atomic.  Results are identical. */
-enum { VP_OPT_CHAIN_STREAMS = 1, VP_OPT_CCL_LEVELS = 2, VP_OPT_CCL_MERGE_CAP = 3, VP_OPT_FLAT_OPS = 4, VP_OPT_HOUGH_LDS = 5 };
+ * row fits the block's LDS budget; 0 makes every vote a global atomic.  Results are identical.
+ * VP_OPT_HOUGH_CIRCLES_LDS (0 or 1, default 1): the HoughCircles radius histogram of a centre is kept in LDS where its bins fit
+ * (160 KiB); 0 keeps it in device memory, as for more bins than that (the tests reach that path at small sizes).  Results are identical. */
+enum { VP_OPT_CHAIN_STREAMS = 1, VP_OPT_CCL_LEVELS = 2, VP_OPT_CCL_MERGE_CAP = 3, VP_OPT_FLAT_OPS = 4, VP_OPT_HOUGH_LDS = 5,
+       VP_OPT_HOUGH_CIRCLES_LDS = 6 };
 int vp_set_option(vp_ctx* ctx, int option, int value);
 /* HIP-event stopwatch on the context's stream (bench.py: roofline.achieved). */
 int vp_timer_start(vp_ctx* ctx);
@@ -414,6 +417,21 @@ int vp_hough_lines_dev(vp_ctx* ctx, const uint8_t* src_dev, size_t src_stride, i
 int vp_hough_lines_batch_dev(vp_ctx* ctx, const uint8_t* src_dev, size_t src_stride, size_t frame_stride, int n, int w, int h, double rho,
                              double theta, int threshold, double min_theta, double max_theta, float* lines_host, int max_lines,
                              int* n_lines);
+/* utils/feature.py:128-155 `find_circles` (cv2.HoughCircles(image, cv2.HOUGH_GRADIENT, dp, minDist, None, param1, param2, minRadius,
+ * maxRadius)): OpenCV 4.x HoughCirclesGradient on a single-channel 8-bit image.  cvRound(param1) is the upper Canny threshold (the lower
+ * one max(1, half of it)), cvRound(param2) the vote and support threshold; minRadius below 0 counts as 0, maxRadius 0 as max(w, h), a
+ * maxRadius <= minRadius as minRadius + 2; dp is clamped to >= 1.  Every edge pixel votes along its Sobel gradient in both directions,
+ * centres are accumulator cells above the threshold that beat their neighbours, each centre's radius is the best-supported group of ten
+ * 1/10-dp bins of the distances to the edge points, and circles are kept strongest first at >= min_dist from every kept one.  Circles
+ * come back as (x, y, r) float triplets in cv2's order; at most max_circles are written, *n_circles is always the true count.
+ * VP_ERR_INVALID for dp, min_dist, param1 or param2 <= 0 (or a non-finite dp); VP_ERR_UNSUPPORTED for max_radius < 0 (the
+ * centres-only mode), images above 2^28 pixels, radii above 2^20 and param1 / param2 above 1e9 (range limits of this path; cv2 itself
+ * accepts such values).  Synchronises. */
+enum { VP_HOUGH_GRADIENT = 3 };
+int vp_hough_circles_u8(vp_ctx* ctx, const uint8_t* src_host, int w, int h, double dp, double min_dist, double param1, double param2,
+                        int min_radius, int max_radius, float* circles_host, int max_circles, int* n_circles);
+int vp_hough_circles_dev(vp_ctx* ctx, const uint8_t* src_dev, size_t src_stride, int w, int h, double dp, double min_dist, double param1,
+                         double param2, int min_radius, int max_radius, float* circles_host, int max_circles, int* n_circles);
 /* cv2.warpAffine(src, M, (dst_w, dst_h), flags, borderMode, borderValue) with bilinear interpolation on 8-bit images, cn = 1..4
  * (modules/preprocessor.py:130-135 rotate with BORDER_REPLICATE, :145-149 translate; utils/transform.py:180-210).  m23: the 2x3
  * matrix, row-major doubles, mapping source to destination unless VP_WARP_INVERSE_MAP is set.  OpenCV's classical fixed-point path
