@@ -100,6 +100,7 @@ vp_ctx* vp_create(int device)
     ctx->ccl_levels = 2;
     ctx->ccl_mcap = -1;
     ctx->flat_ops = 1;
+    ctx->blur_onepass = -1;
     for (size_t& v : ctx->c3_lds_set) v = 0;
     if (const char* env = getenv("VP_CCL_LEVELS")) { const int v = atoi(env); if (v == 1 || v == 2) ctx->ccl_levels = v; }
     // tables: gamma u16[256] | cbrt u16[2048] | sdiv i32[256] | hdiv i32[256]
@@ -191,6 +192,7 @@ int vp_set_option(vp_ctx* ctx, int option, int value)
     if (option == VP_OPT_FLAT_OPS && (value == 0 || value == 1)) { ctx->flat_ops = value; return VP_OK; }
     if (option == VP_OPT_HOUGH_LDS && (value == 0 || value == 1)) { ctx->hough_global = !value; return VP_OK; }
     if (option == VP_OPT_HOUGH_CIRCLES_LDS && (value == 0 || value == 1)) { ctx->hc_global = !value; return VP_OK; }
+    if (option == VP_OPT_BLUR_ONEPASS && value >= -1 && value <= 1) { ctx->blur_onepass = value; return VP_OK; }
     return vp_fail(ctx, VP_ERR_INVALID, "vp_set_option");
 }
 
@@ -2129,6 +2131,200 @@ int vp_nms_dev(vp_ctx* ctx, const float* boxes, const float* scores, int n, floa
     if (n < 0 || max_keep <= 0 || !n_keep || !keep_out || (n > 0 && (!boxes || !scores))) return vp_fail(ctx, VP_ERR_INVALID, "vp_nms_dev arguments");
     VP_TRY(vp_ws_reserve(ctx, vp_nms_ws_bytes(n > 0 ? n : 1) + 2048));
     return vpk_nms(ctx, boxes, scores, n, thr, rotated ? 1 : 0, max_keep, keep_out, n_keep);
+}
+
+// ---- the rest of the per-operator family on device images ---------------------------------------------------------------------------
+// blur, resize, warp, the thresholds and the labelling with the image where the operator before them left it: same checks and kernels
+// as the host forms above, nothing copied, enqueued on the context's stream (the labelling and the histogram bring numbers back and
+// synchronise for them).
+
+// [a, a + an) and [b, b + bn) share a byte
+static bool dev_overlap(const void* a, size_t an, const void* b, size_t bn)
+{
+    const uintptr_t pa = (uintptr_t)a, pb = (uintptr_t)b;
+    return pa < pb + bn && pb < pa + an;
+}
+static size_t strided_bytes(size_t stride, size_t rowbytes, int h) { return (size_t)(h - 1) * stride + rowbytes; }
+
+// VP_OPT_BLUR_ONEPASS left at its default: the one-pass kernel serves the classes in which it measured faster than the two passes
+// on the MI355X by more than the box-to-box spread (tools/exp_dev_ops.py --part blur): three channels, kernels
+// up to 21 (1080p: 27 % faster at 3, 9 % at 15, 5 % at 21; 12 % slower at 31).  One channel gains 4 % at 3 and loses from 7 on, and
+// two and four channels were not measured: they stay on the two passes.
+#define BLUR_ONEPASS_MAX_K 21
+static bool blur_onepass_measured_faster(int cn, int kw, int kh) { return cn == 3 && kw <= BLUR_ONEPASS_MAX_K && kh <= BLUR_ONEPASS_MAX_K; }
+
+int vp_gaussian_blur_dev(vp_ctx* ctx, const uint8_t* d_src, size_t src_stride, int w, int h, int cn, int kw, int kh, double sigma1, double sigma2,
+                         uint8_t* d_dst)
+{
+    VP_TRY(check_ctx(ctx));
+    if (!d_src || !d_dst || w <= 0 || h <= 0 || h > 65535 || cn < 1 || cn > 4 || kw <= 0 || kh <= 0 || !(kw & 1) || !(kh & 1) || kw > 511 || kh > 511)
+        return vp_fail(ctx, VP_ERR_INVALID, "vp_gaussian_blur_dev arguments");
+    const size_t rowbytes = (size_t)w * cn, nbytes = rowbytes * h;
+    if (src_stride < rowbytes || dev_overlap(d_src, strided_bytes(src_stride, rowbytes, h), d_dst, nbytes))
+        return vp_fail(ctx, VP_ERR_INVALID, "vp_gaussian_blur_dev: src_stride, or dst overlaps src");
+    if (sigma1 < 0) sigma1 = 0;
+    if (sigma2 <= 0) sigma2 = sigma1;
+    if (kw == 1 && kh == 1) {
+        VP_HIP(ctx, hipMemcpy2DAsync(d_dst, rowbytes, d_src, src_stride, rowbytes, h, hipMemcpyDeviceToDevice, ctx->stream));
+        return VP_OK;
+    }
+    const bool one = vp_gaussian_onepass_fits(kw, kh) && (ctx->blur_onepass == 1 || (ctx->blur_onepass < 0 && blur_onepass_measured_faster(cn, kw, kh)));
+    VP_TRY(vp_ws_reserve(ctx, (one ? 0 : vp_align(nbytes * 2)) + 4096));
+    TAKE(d_taps, uint16_t*, 2048);
+    // the taps go over in a pinned chunk of the context's ring: the copy is enqueued, nothing waits for it
+    int slot = -1;
+    uint16_t* taps = reinterpret_cast<uint16_t*>(ring_take(ctx, 2048, &slot));
+    if (!taps) return vp_fail(ctx, VP_ERR_NOMEM, "pinned staging");
+    vp_gaussian_taps(kw, sigma1, taps);
+    vp_gaussian_taps(kh, sigma2, taps + kw);
+    int rc = h2d(ctx, d_taps, taps, (size_t)(kw + kh) * 2);
+    if (rc == VP_OK) {
+        if (one) rc = vpk_gaussian_blur_onepass(ctx, d_src, src_stride, w, h, cn, d_taps, kw, kh, d_dst);
+        else {
+            uint16_t* d_tmp = (uint16_t*)vp_ws_take(ctx, nbytes * 2);
+            rc = d_tmp ? vpk_gaussian_blur(ctx, d_src, w, h, cn, d_taps, kw, kh, d_tmp, d_dst, src_stride) : vp_fail(ctx, VP_ERR_NOMEM, "workspace exhausted: d_tmp");
+        }
+    }
+    ring_done(ctx, slot);
+    return rc;
+}
+
+int vp_resize_dev(vp_ctx* ctx, const uint8_t* d_src, size_t src_stride, int w, int h, int cn, int dw, int dh, double inv_sx, double inv_sy, uint8_t* d_dst)
+{
+    VP_TRY(check_ctx(ctx));
+    if (inv_sx <= 0 && inv_sy <= 0) {                    // cv::resize with a dsize: inv_scale = (double)dsize / ssize
+        inv_sx = w > 0 ? (double)dw / w : 0.0;
+        inv_sy = h > 0 ? (double)dh / h : 0.0;
+    }
+    if (!d_src || !d_dst || w <= 0 || h <= 0 || dw <= 0 || dh <= 0 || dh > 65535 || cn < 1 || cn > 4 || !std::isfinite(inv_sx) || !std::isfinite(inv_sy) ||
+        !(inv_sx > 0) || !(inv_sy > 0))
+        return vp_fail(ctx, VP_ERR_INVALID, "vp_resize_dev arguments");
+    const size_t rowbytes = (size_t)w * cn;
+    if (src_stride < rowbytes || dev_overlap(d_src, strided_bytes(src_stride, rowbytes, h), d_dst, (size_t)dw * dh * cn))
+        return vp_fail(ctx, VP_ERR_INVALID, "vp_resize_dev: src_stride, or dst overlaps src");
+    return vpk_resize_u8(ctx, d_src, w, h, cn, dw, dh, inv_sx, inv_sy, d_dst, src_stride);
+}
+
+int vp_warp_affine_dev(vp_ctx* ctx, const uint8_t* d_src, size_t src_stride, int w, int h, int cn, const double* m23, int flags, int border_mode,
+                       const uint8_t* border_value, uint8_t* d_dst, int dw, int dh)
+{
+    VP_TRY(check_ctx(ctx));
+    if (!d_src || !d_dst || !m23 || w <= 0 || h <= 0 || dw <= 0 || dh <= 0 || dh > 65535 || cn < 1 || cn > 4 || (flags & ~VP_WARP_INVERSE_MAP) ||
+        (border_mode != VP_BORDER_CONSTANT && border_mode != VP_BORDER_REPLICATE))
+        return vp_fail(ctx, VP_ERR_INVALID, "vp_warp_affine_dev arguments");
+    for (int i = 0; i < 6; i++)
+        if (!std::isfinite(m23[i])) return vp_fail(ctx, VP_ERR_INVALID, "vp_warp_affine_dev: matrix is not finite");
+    const size_t rowbytes = (size_t)w * cn;
+    if (src_stride < rowbytes || dev_overlap(d_src, strided_bytes(src_stride, rowbytes, h), d_dst, (size_t)dw * dh * cn))
+        return vp_fail(ctx, VP_ERR_INVALID, "vp_warp_affine_dev: src_stride, or dst overlaps src");
+    // the matrix and the border value travel as kernel arguments
+    return vpk_warp_affine_u8(ctx, d_src, w, h, cn, m23, (flags & VP_WARP_INVERSE_MAP) != 0, border_mode, border_value, d_dst, dw, dh, src_stride);
+}
+
+int vp_threshold_u8_dev(vp_ctx* ctx, const uint8_t* d_src, size_t n, double thresh, double maxval, int type, uint8_t* d_dst)
+{
+    VP_TRY(check_ctx(ctx));
+    if (!d_src || !d_dst || n == 0 || type < VP_THRESH_BINARY || type > VP_THRESH_TOZERO_INV || thresh != thresh || maxval != maxval ||
+        dev_overlap(d_src, n, d_dst, n))
+        return vp_fail(ctx, VP_ERR_INVALID, "vp_threshold_u8_dev arguments");
+    const double ft = floor(thresh);
+    const int ithresh = ft < -1 ? -1 : (ft > 256 ? 256 : (int)ft);
+    const double rm = nearbyint(maxval);
+    const int imaxval = rm < 0 ? 0 : (rm > 255 ? 255 : (int)rm);
+    return vpk_threshold_u8(ctx, d_src, n, ithresh, imaxval, type, d_dst);
+}
+
+// histogram -> Otsu's scan by one wave -> threshold from the word the scan wrote: three launches, nothing comes back
+int vp_otsu_threshold_dev(vp_ctx* ctx, const uint8_t* d_src, size_t n, double maxval, int type, double* d_thresh, uint8_t* d_dst)
+{
+    VP_TRY(check_ctx(ctx));
+    if (!d_src || !d_dst || n == 0 || n > 0xffffffffull || type < VP_THRESH_BINARY || type > VP_THRESH_TOZERO_INV || maxval != maxval ||
+        dev_overlap(d_src, n, d_dst, n))
+        return vp_fail(ctx, VP_ERR_INVALID, "vp_otsu_threshold_dev arguments");
+    VP_TRY(vp_ws_reserve(ctx, 4096));
+    TAKE(d_hist, u32*, 1024);
+    TAKE(d_it, int32_t*, 4);
+    VP_TRY(vpk_hist_u8(ctx, d_src, n, d_hist));
+    VP_TRY(vpk_otsu_scan(ctx, d_hist, n, d_thresh, d_it));
+    const double rm = nearbyint(maxval);
+    return vpk_threshold_u8(ctx, d_src, n, 0, rm < 0 ? 0 : (rm > 255 ? 255 : (int)rm), type, d_dst, d_it);
+}
+
+int vp_adaptive_threshold_mean_dev(vp_ctx* ctx, const uint8_t* d_src, size_t src_stride, int w, int h, double max_value, int type, int block, double c,
+                                   uint8_t* d_dst)
+{
+    VP_TRY(check_ctx(ctx));
+    if (!d_src || !d_dst || w <= 0 || h <= 0 || h > 65535 || (type != VP_THRESH_BINARY && type != VP_THRESH_BINARY_INV) || !std::isfinite(max_value) ||
+        !std::isfinite(c) || std::fabs(c) > 1e6)
+        return vp_fail(ctx, VP_ERR_INVALID, "vp_adaptive_threshold_mean_dev arguments");
+    if (block < 3 || (block & 1) == 0) return vp_fail(ctx, VP_ERR_INVALID, "adaptive threshold: block size must be odd and > 1");
+    if (block > 151) return vp_fail(ctx, VP_ERR_UNSUPPORTED, "adaptive threshold: block size above 151");
+    const size_t npx = (size_t)w * h;
+    if (src_stride < (size_t)w || dev_overlap(d_src, strided_bytes(src_stride, (size_t)w, h), d_dst, npx))
+        return vp_fail(ctx, VP_ERR_INVALID, "vp_adaptive_threshold_mean_dev: src_stride, or dst overlaps src");
+    if (max_value < 0) {
+        VP_HIP(ctx, hipMemsetAsync(d_dst, 0, npx, ctx->stream));
+        return VP_OK;
+    }
+    const int imax = (int)std::min(255.0, std::max(0.0, std::nearbyint(max_value)));
+    const int idelta = type == VP_THRESH_BINARY ? (int)std::ceil(c) : (int)std::floor(c);
+    VP_TRY(vp_ws_reserve(ctx, vp_align(npx * 2) + 1024));
+    TAKE(d_tmp, uint16_t*, npx * 2);
+    return vpk_adaptive_threshold_mean(ctx, d_src, w, h, imax, idelta, type == VP_THRESH_BINARY_INV, block, d_tmp, d_dst, src_stride);
+}
+
+int vp_hist_u8_dev(vp_ctx* ctx, const uint8_t* d_src, size_t n, uint32_t* hist)
+{
+    VP_TRY(check_ctx(ctx));
+    if (!d_src || !hist || n == 0 || n > 0xffffffffull) return vp_fail(ctx, VP_ERR_INVALID, "vp_hist_u8_dev arguments");
+    VP_TRY(vp_ws_reserve(ctx, 4096));
+    TAKE(d_hist, u32*, 1024);
+    VP_TRY(vpk_hist_u8(ctx, d_src, n, d_hist));
+    VP_TRY(d2h(ctx, hist, d_hist, 1024));
+    return vp_synchronize(ctx);
+}
+
+// vp_ccl_u8 with the mask (or its bit plane) already in HBM; labels (nullable) stay there, the statistics come back
+static int ccl_dev_impl(vp_ctx* ctx, const char* who, const uint8_t* d_src, size_t src_stride, const u64* bits_in, int w, int h, int numbering,
+                        int32_t* d_labels, int32_t* stats, double* centroids, int max_labels, int32_t* nlabels)
+{
+    VP_TRY(check_ctx(ctx));
+    if ((!d_src && !bits_in) || w <= 0 || h <= 0 || (!bits_in && src_stride < (size_t)w) || max_labels < 1 || !nlabels) return vp_fail(ctx, VP_ERR_INVALID, who);
+    if (numbering != VP_CCL_BLOCK2X2 && numbering != VP_CCL_PIXEL) return vp_fail(ctx, VP_ERR_INVALID, "numbering");
+    const size_t bitbytes = (size_t)h * vp_ww(w) * 8;
+    VP_TRY(vp_ws_reserve(ctx, vp_align(bitbytes) + vp_align((size_t)max_labels * 20) + vp_align((size_t)max_labels * 16) + vp_ccl_ws_bytes(w, h, 1, max_labels) + 8192));
+    TAKE(d_bits, u64*, bitbytes);
+    TAKE(d_stats, int32_t*, (size_t)max_labels * 20);
+    TAKE(d_cent, double*, (size_t)max_labels * 16);
+    TAKE(d_nl, int32_t*, 4);
+    vp_ccl_ws ws;
+    vp_ccl_ws_carve(ctx, w, h, 1, max_labels, &ws);
+    if (!vp_ccl_ws_ok(ws)) return vp_fail(ctx, VP_ERR_NOMEM, "ccl workspace");
+    const u64* bits = bits_in;
+    if (!bits) {
+        VP_TRY(vpk_pack_bits(ctx, d_src, src_stride, w, h, 1, d_bits, nullptr));
+        bits = d_bits;
+    }
+    VP_TRY(vpk_ccl(ctx, bits, w, h, 1, numbering, ws, d_labels, d_stats, d_cent, max_labels, d_nl));
+    VP_TRY(d2h(ctx, nlabels, d_nl, 4));
+    if (stats) VP_TRY(d2h(ctx, stats, d_stats, (size_t)max_labels * 20));
+    if (centroids) VP_TRY(d2h(ctx, centroids, d_cent, (size_t)max_labels * 16));
+    return vp_synchronize(ctx);
+}
+
+int vp_ccl_dev(vp_ctx* ctx, const uint8_t* d_src, size_t src_stride, int w, int h, int numbering, int32_t* d_labels, int32_t* stats, double* centroids,
+               int max_labels, int32_t* nlabels)
+{
+    if (!d_src) return vp_fail(ctx, VP_ERR_INVALID, "vp_ccl_dev arguments");
+    return ccl_dev_impl(ctx, "vp_ccl_dev arguments", d_src, src_stride, nullptr, w, h, numbering, d_labels, stats, centroids, max_labels, nlabels);
+}
+
+int vp_ccl_bits_dev(vp_ctx* ctx, const unsigned long long* d_bits, int w, int h, int numbering, int32_t* d_labels, int32_t* stats, double* centroids,
+                    int max_labels, int32_t* nlabels)
+{
+    if (!d_bits) return vp_fail(ctx, VP_ERR_INVALID, "vp_ccl_bits_dev arguments");
+    return ccl_dev_impl(ctx, "vp_ccl_bits_dev arguments", nullptr, 0, reinterpret_cast<const u64*>(d_bits), w, h, numbering, d_labels, stats, centroids,
+                        max_labels, nlabels);
 }
 
 uint64_t vp_chain_algorithmic_bytes(const vp_chain_desc* desc, const vp_chain_buffers* bufs, int n)

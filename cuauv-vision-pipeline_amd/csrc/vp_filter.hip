@@ -19,8 +19,8 @@ __device__ __forceinline__ int gb_reflect101(int p, int len)
 }
 
 // grid (ceil(w*cn / GB_TILE), h), 256 threads.  A block stages its piece of the row (+ halo, already reflected) in LDS.
-__global__ __launch_bounds__(256) void k_gauss_h(const uint8_t* __restrict__ src, int w, int cn, const uint16_t* __restrict__ taps, int kw,
-                                                 uint16_t* __restrict__ tmp)
+__global__ __launch_bounds__(256) void k_gauss_h(const uint8_t* __restrict__ src, size_t sstride, int w, int cn, const uint16_t* __restrict__ taps,
+                                                 int kw, uint16_t* __restrict__ tmp)
 {
     extern __shared__ uint8_t gb_lds[];
     __shared__ uint16_t tp[GB_MAX_TAPS + 1];
@@ -30,7 +30,7 @@ __global__ __launch_bounds__(256) void k_gauss_h(const uint8_t* __restrict__ src
     const int x0 = b0 / cn;                                 // first pixel touched
     const int x1 = (b0 + nb - 1) / cn;                      // last pixel touched
     const int npx = x1 - x0 + 1 + 2 * r;                    // staged pixels
-    const uint8_t* row = src + (size_t)y * rowbytes;
+    const uint8_t* row = src + (size_t)y * sstride;
     for (int i = threadIdx.x; i < kw; i += 256) tp[i] = taps[i];
     for (int i = threadIdx.x; i < npx * cn; i += 256) {
         const int px = i / cn, c = i - px * cn;
@@ -108,14 +108,86 @@ void vp_gaussian_taps(int n, double sigma, uint16_t* out)
     out[n2] = (uint16_t)(256 - sum);
 }
 
-// d_taps: kw + kh uint16 (x taps then y taps); d_tmp: w*h*cn uint16
-int vpk_gaussian_blur(vp_ctx* ctx, const uint8_t* d_src, int w, int h, int cn, const uint16_t* d_taps, int kw, int kh, uint16_t* d_tmp, uint8_t* d_dst)
+// d_taps: kw + kh uint16 (x taps then y taps); d_tmp: w*h*cn uint16; sstride: bytes between source rows (0: packed)
+int vpk_gaussian_blur(vp_ctx* ctx, const uint8_t* d_src, int w, int h, int cn, const uint16_t* d_taps, int kw, int kh, uint16_t* d_tmp, uint8_t* d_dst,
+                      size_t sstride)
 {
     const int rowbytes = w * cn;
+    if (!sstride) sstride = (size_t)rowbytes;
     vp_prof_scope ps(ctx, VPK_OTHER);
     const size_t lds = (size_t)(GB_TILE / cn + 2 + 2 * (kw / 2)) * cn + 16;
-    hipLaunchKernelGGL(k_gauss_h, dim3((unsigned)((rowbytes + GB_TILE - 1) / GB_TILE), (unsigned)h), dim3(256), lds, ctx->stream, d_src, w, cn, d_taps, kw, d_tmp);
+    hipLaunchKernelGGL(k_gauss_h, dim3((unsigned)((rowbytes + GB_TILE - 1) / GB_TILE), (unsigned)h), dim3(256), lds, ctx->stream, d_src, sstride, w, cn, d_taps, kw, d_tmp);
     hipLaunchKernelGGL(k_gauss_v, dim3((unsigned)((rowbytes + 255) / 256), (unsigned)h), dim3(256), 0, ctx->stream, d_tmp, rowbytes, h, d_taps + kw, kh, d_dst);
+    VP_HIP(ctx, hipGetLastError());
+    return VP_OK;
+}
+
+// ---- the same blur in one launch ---------------------------------------------------------------------------------------------------
+// A block stages GB1_TH rows of GB1_TB bytes plus the halo of both passes in LDS (borders already reflected), keeps the 8.8 horizontal
+// sums of all staged rows there and writes the rounded vertical result once: the 16-bit intermediate never reaches device memory.  The
+// same integer sums as k_gauss_h / k_gauss_v, so the result is bit-equal by construction.  Kernels up to 2 * GB1_MAXR + 1 on either axis.
+#define GB1_TB 128                                        // output bytes per block row
+#define GB1_TH 32                                         // output rows per block
+#define GB1_MAXR 15
+#define GB1_SW (GB1_TB + 2 * 4 + 2 * GB1_MAXR * 4)        // staged bytes per row at cn = 4: (TB / cn + 2 + 2 r) pixels
+#define GB1_SH (GB1_TH + 2 * GB1_MAXR)                    // staged rows
+#define GB1_TAPS (2 * GB1_MAXR + 1)
+static_assert(GB1_SW == 256 && GB1_TB * 2 == 256, "k_gauss_onepass: one staged byte and two result columns per thread");
+static_assert(GB1_SH * GB1_SW + GB1_SH * GB1_TB * 2 + 2 * (GB1_TAPS + 1) * 2 <= 64 * 1024, "k_gauss_onepass: static LDS above 64 KiB");
+
+// grid (ceil(w*cn / GB1_TB), ceil(h / GB1_TH)), 256 threads
+__global__ __launch_bounds__(256) void k_gauss_onepass(const uint8_t* __restrict__ src, size_t sstride, int w, int h, int cn,
+                                                       const uint16_t* __restrict__ taps, int kw, int kh, uint8_t* __restrict__ dst)
+{
+    __shared__ uint8_t st[GB1_SH * GB1_SW];
+    __shared__ uint16_t hs[GB1_SH * GB1_TB];
+    __shared__ uint16_t tpx[GB1_TAPS + 1], tpy[GB1_TAPS + 1];
+    const int rowbytes = w * cn, rx = kw / 2, ry = kh / 2;
+    const int b0 = blockIdx.x * GB1_TB, y0 = blockIdx.y * GB1_TH;
+    const int nb = min(GB1_TB, rowbytes - b0), nrows = min(GB1_TH, h - y0);
+    const int x0 = b0 / cn, x1 = (b0 + nb - 1) / cn;
+    const int nbs = (x1 - x0 + 1 + 2 * rx) * cn;            // staged bytes per row <= GB1_SW
+    const int sh = nrows + 2 * ry;                          // staged rows <= GB1_SH
+    const int t = threadIdx.x;
+    if (t < kw) tpx[t] = taps[t];
+    if (t < kh) tpy[t] = taps[kw + t];
+    if (t < nbs) {                                          // thread = one staged column, all rows
+        const int px = t / cn, c = t - px * cn;
+        const size_t xoff = (size_t)gb_reflect101(x0 - rx + px, w) * cn + c;
+        for (int j = 0; j < sh; j++) st[j * GB1_SW + t] = src[(size_t)gb_reflect101(y0 - ry + j, h) * sstride + xoff];
+    }
+    __syncthreads();
+    const int o = t & (GB1_TB - 1), half = t >> 7;          // thread = one result column, every second row
+    if (o < nb) {
+        const uint8_t* p0 = st + o + (b0 - x0 * cn);        // tap 0 of result byte b0 + o
+        for (int j = half; j < sh; j += 2) {
+            const uint8_t* p = p0 + j * GB1_SW;
+            u32 s = 0;
+            for (int k = 0; k < kw; k++) s += (u32)tpx[k] * p[k * cn];
+            hs[j * GB1_TB + o] = (uint16_t)s;
+        }
+    }
+    __syncthreads();
+    if (o < nb) {
+        for (int r = half; r < nrows; r += 2) {
+            const uint16_t* p = hs + r * GB1_TB + o;
+            u32 s = 0;
+            for (int k = 0; k < kh; k++) s += (u32)tpy[k] * p[k * GB1_TB];
+            const u32 v = (s + (1u << 15)) >> 16;
+            dst[(size_t)(y0 + r) * rowbytes + b0 + o] = (uint8_t)(v > 255u ? 255u : v);
+        }
+    }
+}
+
+bool vp_gaussian_onepass_fits(int kw, int kh) { return kw <= GB1_TAPS && kh <= GB1_TAPS; }
+
+int vpk_gaussian_blur_onepass(vp_ctx* ctx, const uint8_t* d_src, size_t sstride, int w, int h, int cn, const uint16_t* d_taps, int kw, int kh, uint8_t* d_dst)
+{
+    if (!vp_gaussian_onepass_fits(kw, kh)) return vp_fail(ctx, VP_ERR_UNSUPPORTED, "one-pass blur: kernel above its tile");
+    const int rowbytes = w * cn;
+    vp_prof_scope ps(ctx, VPK_OTHER);
+    hipLaunchKernelGGL(k_gauss_onepass, dim3((unsigned)((rowbytes + GB1_TB - 1) / GB1_TB), (unsigned)((h + GB1_TH - 1) / GB1_TH)), dim3(256), 0, ctx->stream,
+                       d_src, sstride ? sstride : (size_t)rowbytes, w, h, cn, d_taps, kw, kh, d_dst);
     VP_HIP(ctx, hipGetLastError());
     return VP_OK;
 }
@@ -123,8 +195,11 @@ int vpk_gaussian_blur(vp_ctx* ctx, const uint8_t* d_src, int w, int h, int cn, c
 // cv2.threshold on 8-bit data (utils/color.py:124-199 binary_threshold / binary_threshold_inv / max_threshold / above_threshold /
 // below_threshold): imgproc/src/thresh.cpp compares against ithresh = floor(thresh); imaxval = saturate(round(maxval)).
 // type: 0 BINARY, 1 BINARY_INV, 2 TRUNC, 3 TOZERO, 4 TOZERO_INV
-__global__ __launch_bounds__(256) void k_threshold_u8(const uint8_t* __restrict__ src, size_t n, int ithresh, int imaxval, int type, uint8_t* __restrict__ dst)
+// ithresh_dev (nullable): the threshold is read from that device word instead (Otsu's, chosen by k_otsu_scan earlier on the stream)
+__global__ __launch_bounds__(256) void k_threshold_u8(const uint8_t* __restrict__ src, size_t n, int ithresh, const int32_t* __restrict__ ithresh_dev,
+                                                      int imaxval, int type, uint8_t* __restrict__ dst)
 {
+    if (ithresh_dev) ithresh = *ithresh_dev;
     const int tr = ithresh < 0 ? 0 : (ithresh > 255 ? 255 : ithresh);
     for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (size_t)gridDim.x * 256) {
         const int v = src[i];
@@ -141,11 +216,11 @@ __global__ __launch_bounds__(256) void k_threshold_u8(const uint8_t* __restrict_
     }
 }
 
-int vpk_threshold_u8(vp_ctx* ctx, const uint8_t* d_src, size_t n, int ithresh, int imaxval, int type, uint8_t* d_dst)
+int vpk_threshold_u8(vp_ctx* ctx, const uint8_t* d_src, size_t n, int ithresh, int imaxval, int type, uint8_t* d_dst, const int32_t* d_ithresh)
 {
     vp_prof_scope ps(ctx, VPK_OTHER);
     const unsigned blocks = (unsigned)std::max<size_t>(1, std::min<size_t>((n + 255) / 256, (size_t)ctx->num_cu * 16));
-    hipLaunchKernelGGL(k_threshold_u8, dim3(blocks), dim3(256), 0, ctx->stream, d_src, n, ithresh, imaxval, type, d_dst);
+    hipLaunchKernelGGL(k_threshold_u8, dim3(blocks), dim3(256), 0, ctx->stream, d_src, n, ithresh, d_ithresh, imaxval, type, d_dst);
     VP_HIP(ctx, hipGetLastError());
     return VP_OK;
 }
@@ -171,6 +246,40 @@ int vpk_hist_u8(vp_ctx* ctx, const uint8_t* d_src, size_t n, u32* d_hist)
     VP_HIP(ctx, hipMemsetAsync(d_hist, 0, 1024, ctx->stream));
     const unsigned blocks = (unsigned)std::max<size_t>(1, std::min<size_t>((n + 255) / 256, (size_t)ctx->num_cu * 8));
     hipLaunchKernelGGL(k_hist_u8, dim3(blocks), dim3(256), 0, ctx->stream, d_src, n, d_hist);
+    VP_HIP(ctx, hipGetLastError());
+    return VP_OK;
+}
+
+// imgproc/src/thresh.cpp getThreshVal_Otsu_8u on the device histogram, statement by statement as vp_otsu_threshold_u8 runs it on the
+// host: one lane, the same doubles in the same order (no contraction: the build uses -ffp-contract=off).  One wave; the threshold goes
+// to *ithresh (what k_threshold_u8 compares against) and, as a double, to *thresh_out (nullable).
+__global__ __launch_bounds__(64) void k_otsu_scan(const u32* __restrict__ h, double n, double* __restrict__ thresh_out, int32_t* __restrict__ ithresh)
+{
+    if (threadIdx.x != 0) return;
+    const double scale = 1. / n;
+    double mu = 0;
+    for (int i = 0; i < 256; i++) mu += i * (double)h[i];
+    mu *= scale;
+    double mu1 = 0, q1 = 0, max_sigma = 0, max_val = 0;
+    for (int i = 0; i < 256; i++) {
+        const double p_i = h[i] * scale;
+        mu1 *= q1;
+        q1 += p_i;
+        const double q2 = 1. - q1;
+        if (fmin(q1, q2) < 1.1920929e-07 || fmax(q1, q2) > 1. - 1.1920929e-07) continue;
+        mu1 = (mu1 + i * p_i) / q1;
+        const double mu2 = (mu - q1 * mu1) / q2;
+        const double sigma = q1 * q2 * (mu1 - mu2) * (mu1 - mu2);
+        if (sigma > max_sigma) { max_sigma = sigma; max_val = i; }
+    }
+    *ithresh = (int32_t)max_val;
+    if (thresh_out) *thresh_out = max_val;
+}
+
+int vpk_otsu_scan(vp_ctx* ctx, const u32* d_hist, size_t n, double* d_thresh, int32_t* d_ithresh)
+{
+    vp_prof_scope ps(ctx, VPK_OTHER);
+    hipLaunchKernelGGL(k_otsu_scan, dim3(1), dim3(64), 0, ctx->stream, d_hist, (double)n, d_thresh, d_ithresh);
     VP_HIP(ctx, hipGetLastError());
     return VP_OK;
 }
@@ -310,12 +419,12 @@ int vpk_canny_u8(vp_ctx* ctx, const uint8_t* d_src, int w, int h, int cn, int lo
 // mean = exact nearest integer of the block sum / blockSize^2 over a window with replicated borders (what all of OpenCV's box-filter
 // roundings give for odd block sizes up to 151), then src - mean > -ceil(C) (BINARY) or src - mean <= -floor(C) (BINARY_INV).
 #define AT_TILE 1024
-__global__ __launch_bounds__(256) void k_box_h(const uint8_t* __restrict__ src, int w, int r, uint16_t* __restrict__ tmp)
+__global__ __launch_bounds__(256) void k_box_h(const uint8_t* __restrict__ src, size_t sstride, int w, int r, uint16_t* __restrict__ tmp)
 {
     extern __shared__ uint8_t at_lds[];
     const int y = blockIdx.y, x0 = blockIdx.x * AT_TILE;
     const int nx = min(AT_TILE, w - x0);
-    const uint8_t* row = src + (size_t)y * w;
+    const uint8_t* row = src + (size_t)y * sstride;
     for (int i = threadIdx.x; i < nx + 2 * r; i += 256) at_lds[i] = row[min(max(x0 - r + i, 0), w - 1)];
     __syncthreads();
     for (int o = threadIdx.x; o < nx; o += 256) {
@@ -324,8 +433,8 @@ __global__ __launch_bounds__(256) void k_box_h(const uint8_t* __restrict__ src, 
         tmp[(size_t)y * w + x0 + o] = (uint16_t)s;
     }
 }
-__global__ __launch_bounds__(256) void k_box_v_adaptive(const uint8_t* __restrict__ src, const uint16_t* __restrict__ tmp, int w, int h, int r, int imax,
-                                                        int idelta, int inv, uint8_t* __restrict__ dst)
+__global__ __launch_bounds__(256) void k_box_v_adaptive(const uint8_t* __restrict__ src, size_t sstride, const uint16_t* __restrict__ tmp, int w, int h, int r,
+                                                        int imax, int idelta, int inv, uint8_t* __restrict__ dst)
 {
     const int x = blockIdx.x * 256 + threadIdx.x, y = blockIdx.y;
     if (x >= w) return;
@@ -333,18 +442,20 @@ __global__ __launch_bounds__(256) void k_box_v_adaptive(const uint8_t* __restric
     for (int k = -r; k <= r; k++) s += tmp[(size_t)min(max(y + k, 0), h - 1) * w + x];
     const u32 d = (u32)(2 * r + 1) * (u32)(2 * r + 1);
     const int mean = (int)((2ull * s + d) / (2ull * d));
-    const int diff = (int)src[(size_t)y * w + x] - mean;
+    const int diff = (int)src[(size_t)y * sstride + x] - mean;
     const bool on = inv ? diff <= -idelta : diff > -idelta;
     dst[(size_t)y * w + x] = (uint8_t)(on ? imax : 0);
 }
 
-// d_tmp: w*h uint16
-int vpk_adaptive_threshold_mean(vp_ctx* ctx, const uint8_t* d_src, int w, int h, int imax, int idelta, int inv, int block, uint16_t* d_tmp, uint8_t* d_dst)
+// d_tmp: w*h uint16; sstride: bytes between source rows (0: packed)
+int vpk_adaptive_threshold_mean(vp_ctx* ctx, const uint8_t* d_src, int w, int h, int imax, int idelta, int inv, int block, uint16_t* d_tmp, uint8_t* d_dst,
+                                size_t sstride)
 {
     const int r = block / 2;
+    if (!sstride) sstride = (size_t)w;
     vp_prof_scope ps(ctx, VPK_OTHER);
-    hipLaunchKernelGGL(k_box_h, dim3((unsigned)((w + AT_TILE - 1) / AT_TILE), (unsigned)h), dim3(256), (size_t)AT_TILE + 2 * r + 16, ctx->stream, d_src, w, r, d_tmp);
-    hipLaunchKernelGGL(k_box_v_adaptive, dim3((unsigned)((w + 255) / 256), (unsigned)h), dim3(256), 0, ctx->stream, d_src, d_tmp, w, h, r, imax, idelta, inv, d_dst);
+    hipLaunchKernelGGL(k_box_h, dim3((unsigned)((w + AT_TILE - 1) / AT_TILE), (unsigned)h), dim3(256), (size_t)AT_TILE + 2 * r + 16, ctx->stream, d_src, sstride, w, r, d_tmp);
+    hipLaunchKernelGGL(k_box_v_adaptive, dim3((unsigned)((w + 255) / 256), (unsigned)h), dim3(256), 0, ctx->stream, d_src, sstride, d_tmp, w, h, r, imax, idelta, inv, d_dst);
     VP_HIP(ctx, hipGetLastError());
     return VP_OK;
 }

@@ -72,6 +72,7 @@ struct vp_ctx {
     size_t c3_acc_bytes;
     int c3_acc_dirty;             // a call was cut short after its labelling launch: reinitialise before the next use
     int hough_global;             // 1: every Hough vote is a global atomic (VP_OPT_HOUGH_LDS 0); 0 (default): rows counted in LDS where they fit
+    int blur_onepass;             // VP_OPT_BLUR_ONEPASS: -1 (default) the measured choice, 1 the one-pass kernel wherever its tile fits, 0 always two passes
     int hc_global;                // 1: HoughCircles radius histograms always in device memory (VP_OPT_HOUGH_CIRCLES_LDS 0); 0 (default): in LDS where they fit
     void* hc_hist;                // HoughCircles radius histograms of the global form: grow-only, sized per call by its centre count
     size_t hc_hist_bytes;
@@ -148,16 +149,21 @@ int vpk_color_balance(vp_ctx* ctx, const uint8_t* d_src, uint8_t* d_dst, int w, 
 
 // ---- detector pre / post-processing (vp_yolo.hip) ------------------------------------------------
 int vpk_letterbox(vp_ctx* ctx, const uint8_t* d_src, int sw, int sh, int dw, int dh, int pad, float* d_dst, float* geom_out);
-int vpk_resize_u8(vp_ctx* ctx, const uint8_t* d_src, int sw, int sh, int cn, int dw, int dh, double inv_sx, double inv_sy, uint8_t* d_dst);
+// sstride: bytes between source rows (0: packed)
+int vpk_resize_u8(vp_ctx* ctx, const uint8_t* d_src, int sw, int sh, int cn, int dw, int dh, double inv_sx, double inv_sy, uint8_t* d_dst, size_t sstride = 0);
 int vpk_warp_affine_u8(vp_ctx* ctx, const uint8_t* d_src, int sw, int sh, int cn, const double* M23, int inverse_map, int border,
-                       const uint8_t* cval, uint8_t* d_dst, int dw, int dh);
+                       const uint8_t* cval, uint8_t* d_dst, int dw, int dh, size_t sstride = 0);
 size_t vp_nms_ws_bytes(int n);
 int vpk_nms(vp_ctx* ctx, const float* d_boxes, const float* d_scores, int n, float thr, int rotated, int max_keep, int* d_keep, int* d_nkeep);
 
 // ---- filters (vp_filter.hip) -----------------------------------------------------------------------
-int vpk_threshold_u8(vp_ctx* ctx, const uint8_t* d_src, size_t n, int ithresh, int imaxval, int type, uint8_t* d_dst);
+// d_ithresh (nullable): the threshold comes from that device word (vpk_otsu_scan) instead of ithresh
+int vpk_threshold_u8(vp_ctx* ctx, const uint8_t* d_src, size_t n, int ithresh, int imaxval, int type, uint8_t* d_dst, const int32_t* d_ithresh = nullptr);
+// Otsu's threshold of a 256-bin device histogram of n bytes -> *d_ithresh (and *d_thresh, a double, nullable); one wave, enqueued
+int vpk_otsu_scan(vp_ctx* ctx, const u32* d_hist, size_t n, double* d_thresh, int32_t* d_ithresh);
 int vpk_hist_u8(vp_ctx* ctx, const uint8_t* d_src, size_t n, u32* d_hist);   // d_hist: 256 counters
-int vpk_adaptive_threshold_mean(vp_ctx* ctx, const uint8_t* d_src, int w, int h, int imax, int idelta, int inv, int block, uint16_t* d_tmp, uint8_t* d_dst);
+int vpk_adaptive_threshold_mean(vp_ctx* ctx, const uint8_t* d_src, int w, int h, int imax, int idelta, int inv, int block, uint16_t* d_tmp, uint8_t* d_dst,
+                                size_t sstride = 0);   // sstride: bytes between source rows (0: packed)
 size_t vp_canny_ws_bytes(int w, int h);
 // grad_out (nullable): receives the workspace plane of the winning channel's Sobel (dx, dy), w * h short2, valid until the workspace is
 // carved anew (HoughCircles reads it for cn = 1)
@@ -182,7 +188,11 @@ void vp_gaussian_kernel_f64(int n, double sigma, double* k);  // the double kern
 size_t vp_agauss_ws_bytes(int w, int h, int n);
 int vpk_adaptive_threshold_gaussian(vp_ctx* ctx, const uint8_t* d_src, size_t stride, size_t fstride, int n, int w, int h, int imax, int idelta,
                                     int inv, int block, uint64_t* d_tmp, uint8_t* d_dst);
-int vpk_gaussian_blur(vp_ctx* ctx, const uint8_t* d_src, int w, int h, int cn, const uint16_t* d_taps, int kw, int kh, uint16_t* d_tmp, uint8_t* d_dst);
+int vpk_gaussian_blur(vp_ctx* ctx, const uint8_t* d_src, int w, int h, int cn, const uint16_t* d_taps, int kw, int kh, uint16_t* d_tmp, uint8_t* d_dst,
+                      size_t sstride = 0);             // sstride: bytes between source rows (0: packed)
+// the blur in one launch, the 8.8 intermediate kept in LDS (k_gauss_onepass); kernels for which vp_gaussian_onepass_fits only
+bool vp_gaussian_onepass_fits(int kw, int kh);
+int vpk_gaussian_blur_onepass(vp_ctx* ctx, const uint8_t* d_src, size_t sstride, int w, int h, int cn, const uint16_t* d_taps, int kw, int kh, uint8_t* d_dst);
 
 // ---- morphology (vp_morph.hip) ---------------------------------------------------------------
 struct vp_bitstage { int dilate; int l, r, u, d; };  // window [-l, r] x [-u, d]

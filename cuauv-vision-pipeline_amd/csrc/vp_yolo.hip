@@ -107,15 +107,15 @@ __global__ __launch_bounds__(64) void k_letterbox(const uint8_t* __restrict__ sr
 // so the table entries are derived once for all of its channels.  grid (ceil(dw/256), dh).
 // area2: hal::resize's switch to the area-fast path (both scales exactly 2), taken only when the source is exactly twice the destination
 template <int CN>
-__global__ __launch_bounds__(256) void k_resize_u8(const uint8_t* __restrict__ src, int sw, int sh, int dw, double scale_x, double scale_y, int area2,
-                                                   uint8_t* __restrict__ dst)
+__global__ __launch_bounds__(256) void k_resize_u8(const uint8_t* __restrict__ src, size_t sstride, int sw, int sh, int dw, double scale_x, double scale_y,
+                                                   int area2, uint8_t* __restrict__ dst)
 {
     const int x = blockIdx.x * 256 + threadIdx.x, y = blockIdx.y;
     if (x >= dw) return;
     uint8_t* d = dst + ((size_t)y * dw + x) * CN;
     if (area2) {
-        const uint8_t* r0 = src + ((size_t)(2 * y) * sw + 2 * x) * CN;
-        const uint8_t* r1 = r0 + (size_t)sw * CN;
+        const uint8_t* r0 = src + (size_t)(2 * y) * sstride + (size_t)(2 * x) * CN;
+        const uint8_t* r1 = r0 + sstride;
 #pragma unroll
         for (int c = 0; c < CN; c++) d[c] = (uint8_t)((r0[c] + r0[CN + c] + r1[c] + r1[CN + c] + 2) >> 2);
         return;
@@ -123,8 +123,8 @@ __global__ __launch_bounds__(256) void k_resize_u8(const uint8_t* __restrict__ s
     int sx, sx1, ax0, ax1, sy, sy1, ay0, ay1;
     rs_col(x, scale_x, sw, sx, sx1, ax0, ax1);
     rs_row(y, scale_y, sh, sy, sy1, ay0, ay1);
-    const uint8_t* r0 = src + (size_t)sy * sw * CN;
-    const uint8_t* r1 = src + (size_t)sy1 * sw * CN;
+    const uint8_t* r0 = src + (size_t)sy * sstride;
+    const uint8_t* r1 = src + (size_t)sy1 * sstride;
 #pragma unroll
     for (int c = 0; c < CN; c++) {
         const int S0 = r0[sx * CN + c] * ax0 + r0[sx1 * CN + c] * ax1;
@@ -135,11 +135,13 @@ __global__ __launch_bounds__(256) void k_resize_u8(const uint8_t* __restrict__ s
 }
 
 // inv_sx, inv_sy: cv::resize's inverse scales (dsize / ssize, or fx / fy of the size-less form)
-int vpk_resize_u8(vp_ctx* ctx, const uint8_t* d_src, int sw, int sh, int cn, int dw, int dh, double inv_sx, double inv_sy, uint8_t* d_dst)
+int vpk_resize_u8(vp_ctx* ctx, const uint8_t* d_src, int sw, int sh, int cn, int dw, int dh, double inv_sx, double inv_sy, uint8_t* d_dst, size_t sstride)
 {
     vp_prof_scope ps(ctx, VPK_OTHER);
+    if (!sstride) sstride = (size_t)sw * cn;
     if (sw == dw && sh == dh) {
-        VP_HIP(ctx, hipMemcpyAsync(d_dst, d_src, (size_t)sw * sh * cn, hipMemcpyDeviceToDevice, ctx->stream));
+        if (sstride == (size_t)sw * cn) VP_HIP(ctx, hipMemcpyAsync(d_dst, d_src, (size_t)sw * sh * cn, hipMemcpyDeviceToDevice, ctx->stream));
+        else VP_HIP(ctx, hipMemcpy2DAsync(d_dst, (size_t)sw * cn, d_src, sstride, (size_t)sw * cn, sh, hipMemcpyDeviceToDevice, ctx->stream));
         return VP_OK;
     }
     const double scale_x = 1. / inv_sx, scale_y = 1. / inv_sy;
@@ -150,10 +152,10 @@ int vpk_resize_u8(vp_ctx* ctx, const uint8_t* d_src, int sw, int sh, int cn, int
     const dim3 grid((unsigned)((dw + 255) / 256), (unsigned)dh);
     const int a2 = area2 ? 1 : 0;
     switch (cn) {
-    case 1: hipLaunchKernelGGL(k_resize_u8<1>, grid, dim3(256), 0, ctx->stream, d_src, sw, sh, dw, scale_x, scale_y, a2, d_dst); break;
-    case 2: hipLaunchKernelGGL(k_resize_u8<2>, grid, dim3(256), 0, ctx->stream, d_src, sw, sh, dw, scale_x, scale_y, a2, d_dst); break;
-    case 3: hipLaunchKernelGGL(k_resize_u8<3>, grid, dim3(256), 0, ctx->stream, d_src, sw, sh, dw, scale_x, scale_y, a2, d_dst); break;
-    case 4: hipLaunchKernelGGL(k_resize_u8<4>, grid, dim3(256), 0, ctx->stream, d_src, sw, sh, dw, scale_x, scale_y, a2, d_dst); break;
+    case 1: hipLaunchKernelGGL(k_resize_u8<1>, grid, dim3(256), 0, ctx->stream, d_src, sstride, sw, sh, dw, scale_x, scale_y, a2, d_dst); break;
+    case 2: hipLaunchKernelGGL(k_resize_u8<2>, grid, dim3(256), 0, ctx->stream, d_src, sstride, sw, sh, dw, scale_x, scale_y, a2, d_dst); break;
+    case 3: hipLaunchKernelGGL(k_resize_u8<3>, grid, dim3(256), 0, ctx->stream, d_src, sstride, sw, sh, dw, scale_x, scale_y, a2, d_dst); break;
+    case 4: hipLaunchKernelGGL(k_resize_u8<4>, grid, dim3(256), 0, ctx->stream, d_src, sstride, sw, sh, dw, scale_x, scale_y, a2, d_dst); break;
     default: return vp_fail(ctx, VP_ERR_INVALID, "resize: cn must be 1..4");
     }
     VP_HIP(ctx, hipGetLastError());
@@ -163,7 +165,7 @@ int vpk_resize_u8(vp_ctx* ctx, const uint8_t* d_src, int sw, int sh, int cn, int
 // cv2.warpAffine(src, M, (dw, dh), INTER_LINEAR, borderMode) on 8-bit images, OpenCV's classical fixed-point path: source coordinates in
 // 22.10 fixed point from round-half-even products (no fused multiply-add: the reference arithmetic is plain IEEE double), 5 fractional
 // bits kept, 15-bit bilinear weights, (sum + 2^14) >> 15.  M maps destination to source here (the host inverts).  thread = one pixel.
-struct wa_params { double m[6]; int sw, sh, cn, dw, dh, border; uint8_t cval[4]; };
+struct wa_params { double m[6]; size_t sstride; int sw, sh, cn, dw, dh, border; uint8_t cval[4]; };
 __device__ __forceinline__ int wa_round(double v)
 {
     if (!(v > -2147483648.0)) return INT_MIN;
@@ -197,10 +199,10 @@ __global__ __launch_bounds__(256) void k_warp_affine_u8(const uint8_t* __restric
         y0 = (sy >= 0 && sy < sh) ? sy : -1; y1 = (sy + 1 >= 0 && sy + 1 < sh) ? sy + 1 : -1;
     }
     const bool i00 = x0 >= 0 && y0 >= 0, i01 = x1 >= 0 && y0 >= 0, i10 = x0 >= 0 && y1 >= 0, i11 = x1 >= 0 && y1 >= 0;
-    const uint8_t* p00 = src + ((size_t)max(y0, 0) * sw + max(x0, 0)) * cn;
-    const uint8_t* p01 = src + ((size_t)max(y0, 0) * sw + max(x1, 0)) * cn;
-    const uint8_t* p10 = src + ((size_t)max(y1, 0) * sw + max(x0, 0)) * cn;
-    const uint8_t* p11 = src + ((size_t)max(y1, 0) * sw + max(x1, 0)) * cn;
+    const uint8_t* p00 = src + (size_t)max(y0, 0) * P.sstride + (size_t)max(x0, 0) * cn;
+    const uint8_t* p01 = src + (size_t)max(y0, 0) * P.sstride + (size_t)max(x1, 0) * cn;
+    const uint8_t* p10 = src + (size_t)max(y1, 0) * P.sstride + (size_t)max(x0, 0) * cn;
+    const uint8_t* p11 = src + (size_t)max(y1, 0) * P.sstride + (size_t)max(x1, 0) * cn;
     for (int c = 0; c < cn; c++) {
         const int cv = P.cval[c];
         const int v00 = i00 ? p00[c] : cv, v01 = i01 ? p01[c] : cv, v10 = i10 ? p10[c] : cv, v11 = i11 ? p11[c] : cv;
@@ -210,7 +212,7 @@ __global__ __launch_bounds__(256) void k_warp_affine_u8(const uint8_t* __restric
 }
 
 int vpk_warp_affine_u8(vp_ctx* ctx, const uint8_t* d_src, int sw, int sh, int cn, const double* M23, int inverse_map, int border,
-                       const uint8_t* cval, uint8_t* d_dst, int dw, int dh)
+                       const uint8_t* cval, uint8_t* d_dst, int dw, int dh, size_t sstride)
 {
 #pragma clang fp contract(off)   // the inversion is plain IEEE double in the reference arithmetic
     wa_params P;
@@ -227,6 +229,7 @@ int vpk_warp_affine_u8(vp_ctx* ctx, const uint8_t* d_src, int sw, int sh, int cn
         M[2] = b1; M[5] = b2;
     }
     for (int i = 0; i < 6; i++) P.m[i] = M[i];
+    P.sstride = sstride ? sstride : (size_t)sw * cn;
     P.sw = sw; P.sh = sh; P.cn = cn; P.dw = dw; P.dh = dh; P.border = border;
     for (int c = 0; c < 4; c++) P.cval[c] = cval ? cval[c] : 0;
     vp_prof_scope ps(ctx, VPK_OTHER);

@@ -28,7 +28,8 @@ CHAIN_APPROX_NONE, CHAIN_APPROX_SIMPLE = 1, 2
 CC_STAT_LEFT, CC_STAT_TOP, CC_STAT_WIDTH, CC_STAT_HEIGHT, CC_STAT_AREA = 0, 1, 2, 3, 4
 CV_8U = 0
 ADAPTIVE_THRESH_MEAN_C, ADAPTIVE_THRESH_GAUSSIAN_C = 0, 1
-THRESH_BINARY, THRESH_BINARY_INV = 0, 1
+THRESH_BINARY, THRESH_BINARY_INV, THRESH_TRUNC, THRESH_TOZERO, THRESH_TOZERO_INV = 0, 1, 2, 3, 4
+THRESH_MASK, THRESH_OTSU, THRESH_TRIANGLE = 7, 8, 16
 CV_32S = 4
 CV_PI = math.pi
 HOUGH_GRADIENT, HOUGH_GRADIENT_ALT = 3, 4
@@ -389,15 +390,22 @@ def _gaussian_blur(src, ksize, sigmaX, sigmaY, borderType):
     from vision import _vp
     if borderType not in (None, BORDER_DEFAULT):
         raise error("GaussianBlur: only BORDER_DEFAULT (reflect 101) is on the accelerated path")
-    src = np.ascontiguousarray(src)
+    src, on_dev = _device_source(src)
     if src.dtype != np.uint8 or src.ndim not in (2, 3) or src.size == 0:
         raise error("GaussianBlur: only non-empty uint8 images are on the accelerated path")
     cn = 1 if src.ndim == 2 else src.shape[2]
     kw, kh = int(ksize[0]), int(ksize[1])
     if kw <= 0 or kh <= 0 or kw % 2 == 0 or kh % 2 == 0 or kw > 511 or kh > 511 or cn > 4:
         raise error("GaussianBlur: kernel sizes must be odd, 1..511")
-    out = np.empty_like(src)
     ctx = _vp.default_context()
+    if on_dev:                                       # the image stays in HBM (libvp vp_gaussian_blur_dev)
+        from vision.devmat import DeviceMat
+        src.refresh_device(ctx)
+        out = DeviceMat(ctx, src.shape)
+        _vp.check(_vp.lib().vp_gaussian_blur_dev(ctx.handle, src.dev_ptr, src.shape[1] * cn, src.shape[1], src.shape[0], cn, kw, kh, float(sigmaX),
+                                                 float(sigmaY), out.dev_ptr), ctx.handle)
+        return out
+    out = np.empty_like(src)
     _vp.check(_vp.lib().vp_gaussian_blur_u8(ctx.handle, _vp.ptr(src), src.shape[1], src.shape[0], cn, kw, kh, float(sigmaX), float(sigmaY),
                                             _vp.ptr(out)), ctx.handle)
     return out
@@ -405,6 +413,16 @@ def _gaussian_blur(src, ksize, sigmaX, sigmaY, borderType):
 
 INTER_LINEAR = 1
 WARP_INVERSE_MAP = 16
+
+
+def _device_source(src):
+    """(image, True) for a DeviceMat, which the operator reads where it is; (packed numpy array, False) for everything else."""
+    from vision.devmat import DeviceMat
+    from vision.utils.helpers import as_mat
+    src = as_mat(src)
+    if isinstance(src, DeviceMat):
+        return src, True
+    return np.ascontiguousarray(src), False
 
 
 def warpAffine(src, M, dsize, dst=None, flags=INTER_LINEAR, borderMode=BORDER_CONSTANT, borderValue=0):
@@ -422,7 +440,7 @@ def _warp_affine(src, M, dsize, flags, borderMode, borderValue):
         raise error("warpAffine: only INTER_LINEAR is on the accelerated path")
     if borderMode not in (BORDER_CONSTANT, BORDER_REPLICATE):
         raise error("warpAffine: only BORDER_CONSTANT and BORDER_REPLICATE are on the accelerated path")
-    src = np.ascontiguousarray(src)
+    src, on_dev = _device_source(src)
     if src.dtype != np.uint8 or src.ndim not in (2, 3) or src.size == 0:
         raise error("warpAffine: expected a non-empty uint8 image")
     cn = 1 if src.ndim == 2 else src.shape[2]
@@ -433,8 +451,15 @@ def _warp_affine(src, M, dsize, flags, borderMode, borderValue):
     bv = np.zeros(4, np.uint8)
     vals = np.atleast_1d(np.asarray(borderValue, dtype=np.float64))[:4]
     bv[:len(vals)] = np.clip(np.rint(vals), 0, 255).astype(np.uint8)
-    out = np.empty((dh, dw) if src.ndim == 2 else (dh, dw, cn), np.uint8)
     ctx = _vp.default_context()
+    if on_dev:                                       # the image stays in HBM (libvp vp_warp_affine_dev)
+        from vision.devmat import DeviceMat
+        src.refresh_device(ctx)
+        out = DeviceMat(ctx, (dh, dw) if src.ndim == 2 else (dh, dw, cn))
+        _vp.check(_vp.lib().vp_warp_affine_dev(ctx.handle, src.dev_ptr, src.shape[1] * cn, src.shape[1], src.shape[0], cn, _vp.ptr(m),
+                                               int(flags & WARP_INVERSE_MAP), int(borderMode), _vp.ptr(bv), out.dev_ptr, dw, dh), ctx.handle)
+        return out
+    out = np.empty((dh, dw) if src.ndim == 2 else (dh, dw, cn), np.uint8)
     _vp.check(_vp.lib().vp_warp_affine_u8(ctx.handle, _vp.ptr(src), src.shape[1], src.shape[0], cn, _vp.ptr(m), int(flags & WARP_INVERSE_MAP),
                                           int(borderMode), _vp.ptr(bv), _vp.ptr(out), dw, dh), ctx.handle)
     return out
@@ -446,7 +471,7 @@ def resize(src, dsize, dst=None, fx=None, fy=None, interpolation=INTER_LINEAR):
     from vision import _vp
     if interpolation != INTER_LINEAR:
         raise error("resize: only INTER_LINEAR is on the accelerated path")
-    src = np.ascontiguousarray(src)
+    src, on_dev = _device_source(src)
     scaled = dsize is None or tuple(dsize) == (0, 0)
     if scaled:
         if not fx or not fy or not (fx > 0 and fy > 0):
@@ -460,11 +485,19 @@ def resize(src, dsize, dst=None, fx=None, fy=None, interpolation=INTER_LINEAR):
     dw, dh = int(dsize[0]), int(dsize[1])
     if dw <= 0 or dh <= 0 or cn > 4:
         raise error("resize: bad size")
-    out = np.empty((dh, dw) if src.ndim == 2 else (dh, dw, cn), np.uint8)
     ctx = _vp.default_context()
     lib = _vp.lib()
+    if on_dev:
+        from vision.devmat import DeviceMat
+        out = DeviceMat(ctx, (dh, dw) if src.ndim == 2 else (dh, dw, cn))
+    else:
+        out = np.empty((dh, dw) if src.ndim == 2 else (dh, dw, cn), np.uint8)
     try:
-        if scaled:
+        if on_dev:                                   # the image stays in HBM (libvp vp_resize_dev; scales <= 0: dsize / ssize)
+            src.refresh_device(ctx)
+            _vp.check(lib.vp_resize_dev(ctx.handle, src.dev_ptr, src.shape[1] * cn, src.shape[1], src.shape[0], cn, dw, dh, fx if scaled else 0.0,
+                                        fy if scaled else 0.0, out.dev_ptr), ctx.handle)
+        elif scaled:
             _vp.check(lib.vp_resize_u8_scaled(ctx.handle, _vp.ptr(src), src.shape[1], src.shape[0], cn, dw, dh, fx, fy, _vp.ptr(out)), ctx.handle)
         else:
             _vp.check(lib.vp_resize_u8(ctx.handle, _vp.ptr(src), src.shape[1], src.shape[0], cn, dw, dh, _vp.ptr(out)), ctx.handle)
@@ -527,8 +560,8 @@ def HoughCircles(image, method, dp, minDist, circles=None, param1=100, param2=10
 
 def adaptiveThreshold(src, maxValue, adaptiveMethod, thresholdType, blockSize, C, dst=None):
     """cv2.adaptiveThreshold (utils/color.py:220-292) in cv2's positional order on CV_8UC1 images.  ADAPTIVE_THRESH_MEAN_C: the mean
-    path (libvp vp_adaptive_threshold_mean_u8, block sizes 3..151); ADAPTIVE_THRESH_GAUSSIAN_C: the exact Gaussian-weighted mean
-    (vp_adaptive_threshold_gaussian_*, block sizes 3..511; a DeviceMat in gives a DeviceMat out)."""
+    path (libvp vp_adaptive_threshold_mean_*, block sizes 3..151); ADAPTIVE_THRESH_GAUSSIAN_C: the exact Gaussian-weighted mean
+    (vp_adaptive_threshold_gaussian_*, block sizes 3..511).  A DeviceMat in gives a DeviceMat out."""
     from vision import _vp
     from vision.devmat import DeviceMat, to_host
     from vision.utils.helpers import as_mat
@@ -548,12 +581,43 @@ def adaptiveThreshold(src, maxValue, adaptiveMethod, thresholdType, blockSize, C
         raise error("adaptiveThreshold: unknown or unsupported threshold type")
     if adaptiveMethod == ADAPTIVE_THRESH_GAUSSIAN_C:
         return _into(dst, _color._adaptive_gaussian(src, blockSize, float(C), int(thresholdType), float(maxValue)))
+    if isinstance(src, DeviceMat):                 # the image stays in HBM (libvp vp_adaptive_threshold_mean_dev)
+        return _into(dst, _color._adaptive_mean(src, blockSize, float(C), int(thresholdType), float(maxValue)))
     img = np.ascontiguousarray(np.asarray(to_host(src)).reshape(shape[:2]))
     out = np.empty_like(img)
     ctx = _vp.default_context()
     _vp.check(_vp.lib().vp_adaptive_threshold_mean_u8(ctx.handle, _vp.ptr(img), img.shape[1], img.shape[0], float(maxValue), int(thresholdType),
                                                       blockSize, float(C), _vp.ptr(out)), ctx.handle)
     return _into(dst, out)
+
+
+def threshold(src, thresh, maxval, type, dst=None):
+    """cv2.threshold on uint8 images in cv2's positional order -> (retval, dst): THRESH_BINARY, BINARY_INV, TRUNC, TOZERO and
+    TOZERO_INV on any channel count (libvp vp_threshold_u8 / _dev; retval is thresh), each optionally with THRESH_OTSU on a single
+    channel (vp_otsu_threshold_u8 / _dev; retval is the threshold Otsu's method chose).  A DeviceMat in gives a DeviceMat out."""
+    from vision.devmat import DeviceMat
+    from vision.utils.helpers import as_mat
+    src = as_mat(src)
+    try:
+        kind = int(type)
+    except (TypeError, ValueError):
+        raise error("threshold: the threshold type must be an integer") from None
+    if kind & THRESH_TRIANGLE:
+        raise error("threshold: THRESH_TRIANGLE is outside the accelerated path")
+    if (kind & ~(THRESH_MASK | THRESH_OTSU)) or (kind & THRESH_MASK) > THRESH_TOZERO_INV:
+        raise error("threshold: unknown threshold type")
+    shape = tuple(src.shape) if isinstance(src, (np.ndarray, DeviceMat)) else ()
+    if not isinstance(src, (np.ndarray, DeviceMat)) or src.dtype != np.uint8 or len(shape) not in (2, 3) or 0 in shape:
+        raise error("threshold: expected a non-empty uint8 image")
+    thresh, maxval = float(thresh), float(maxval)
+    if thresh != thresh or maxval != maxval:
+        raise error("threshold: thresh and maxval must be numbers")
+    if kind & THRESH_OTSU:
+        if len(shape) == 3 and shape[2] != 1:
+            raise error("threshold: THRESH_OTSU takes a CV_8UC1 image")
+        t, out = _color._otsu(src, maxval, kind & THRESH_MASK)
+        return t, _into(dst, out)
+    return thresh, _into(dst, _color._threshold(src, thresh, maxval, kind & THRESH_MASK))
 
 
 def drawContours(image, contours, contourIdx, color, thickness=1):

@@ -263,8 +263,20 @@ def _outside_path(name):
 
 
 def _threshold(mat: np.ndarray, thresh: float, maxval: float, kind: int) -> np.ndarray:
-    """cv2.threshold(mat, thresh, maxval, kind)[1] on uint8 images (libvp vp_threshold_u8)."""
-    mat = to_host(as_mat(mat))
+    """cv2.threshold(mat, thresh, maxval, kind)[1] on uint8 images (libvp vp_threshold_u8; a DeviceMat gives a DeviceMat that stays in
+    HBM, vp_threshold_u8_dev)."""
+    mat = as_mat(mat)
+    if isinstance(mat, DeviceMat):
+        if mat.dtype != np.uint8 or mat.size == 0:
+            raise TypeError("expected a non-empty uint8 numpy image")
+        ctx = _vp.default_context()
+        mat.refresh_device(ctx)
+        # a BINARY / BINARY_INV result with maxval 255 is a 0 / 255 mask: morphology and contours take their bit paths on it
+        mask = int(kind) in (_vp.THRESH_BINARY, _vp.THRESH_BINARY_INV) and mat.ndim == 2 and maxval == maxval and round(float(maxval)) == 255
+        out = DeviceMat(ctx, mat.shape, binary=mask)
+        _vp.check(_vp.lib().vp_threshold_u8_dev(ctx.handle, mat.dev_ptr, mat.size, float(thresh), float(maxval), int(kind), out.dev_ptr), ctx.handle)
+        return out
+    mat = to_host(mat)
     if not isinstance(mat, np.ndarray) or mat.dtype != np.uint8 or mat.size == 0:
         raise TypeError("expected a non-empty uint8 numpy image")
     mat = np.ascontiguousarray(mat)
@@ -291,22 +303,54 @@ def below_threshold(mat: np.ndarray, threshold: float) -> np.ndarray:
 
 
 def otsu_threshold(mat: np.ndarray):
-    """utils/color.py:204-217 (cv2.threshold(mat, 0, 255, THRESH_OTSU)): (threshold chosen by Otsu's method, thresholded image)."""
+    """utils/color.py:204-217 (cv2.threshold(mat, 0, 255, THRESH_OTSU)): (threshold chosen by Otsu's method, thresholded image).  A
+    DeviceMat gives a DeviceMat: histogram, scan and threshold run on the device (vp_otsu_threshold_dev) and only the 8 bytes of the
+    chosen threshold come back."""
+    return _otsu(mat, 255.0, 0)
+
+
+def _otsu(mat, maxval: float, kind: int):
+    mat = as_mat(mat)
+    if isinstance(mat, DeviceMat):
+        if mat.dtype != np.uint8:
+            raise TypeError("expected a uint8 numpy image")
+        from vision.devmat import _DevBuf
+        ctx = _vp.default_context()
+        src = device_image(ctx, mat, 1)
+        h, w = src.shape
+        mask = int(kind) in (_vp.THRESH_BINARY, _vp.THRESH_BINARY_INV) and round(float(maxval)) == 255
+        out = DeviceMat(ctx, (h, w), binary=mask)
+        word = _DevBuf(ctx, 8)
+        _vp.check(_vp.lib().vp_otsu_threshold_dev(ctx.handle, src.dev_ptr, h * w, float(maxval), int(kind), word.ptr, out.dev_ptr), ctx.handle)
+        t = _vp.C.c_double(0)
+        _vp.check(_vp.lib().vp_memcpy_d2h(ctx.handle, _vp.C.addressof(t), word.ptr, 8), ctx.handle)
+        return t.value, out
     mat = _u8_image(mat, 1)
     mat = np.ascontiguousarray(mat)
     out = np.empty_like(mat)
     t = _vp.C.c_double(0)
     ctx = _vp.default_context()
-    _vp.check(_vp.lib().vp_otsu_threshold_u8(ctx.handle, _vp.ptr(mat), mat.size, 255.0, 0, _vp.C.byref(t), _vp.ptr(out)), ctx.handle)
+    _vp.check(_vp.lib().vp_otsu_threshold_u8(ctx.handle, _vp.ptr(mat), mat.size, float(maxval), int(kind), _vp.C.byref(t), _vp.ptr(out)), ctx.handle)
     return t.value, out
 
 
 
-def _adaptive_mean(mat: np.ndarray, neighborhood_size: int, bias: float, kind: int) -> np.ndarray:
+def _adaptive_mean(mat: np.ndarray, neighborhood_size: int, bias: float, kind: int, max_value: float = 255.0) -> np.ndarray:
+    """libvp vp_adaptive_threshold_mean_u8: numpy in -> numpy out; a DeviceMat -> a DeviceMat that stays in HBM (_dev)."""
+    mat = as_mat(mat)
+    ctx = _vp.default_context()
+    if isinstance(mat, DeviceMat):
+        if mat.dtype != np.uint8:
+            raise TypeError("expected a uint8 numpy image")
+        src = device_image(ctx, mat, 1)
+        h, w = src.shape
+        dst = DeviceMat(ctx, (h, w), binary=float(max_value) == 255.0)
+        _vp.check(_vp.lib().vp_adaptive_threshold_mean_dev(ctx.handle, src.dev_ptr, w, w, h, float(max_value), kind, int(neighborhood_size),
+                                                           float(bias), dst.dev_ptr), ctx.handle)
+        return dst
     mat = np.ascontiguousarray(_u8_image(mat, 1))
     out = np.empty_like(mat)
-    ctx = _vp.default_context()
-    _vp.check(_vp.lib().vp_adaptive_threshold_mean_u8(ctx.handle, _vp.ptr(mat), mat.shape[1], mat.shape[0], 255.0, kind, int(neighborhood_size),
+    _vp.check(_vp.lib().vp_adaptive_threshold_mean_u8(ctx.handle, _vp.ptr(mat), mat.shape[1], mat.shape[0], float(max_value), kind, int(neighborhood_size),
                                                       float(bias), _vp.ptr(out)), ctx.handle)
     return out
 

@@ -20,8 +20,12 @@ from vision.utils.helpers import as_mat, device_image
 def connected_components(mat: np.ndarray, numbering: int = _vp.CCL_BLOCK2X2, max_labels: int = 4096,
                          want_labels: bool = True):
     """Returns (nlabels, labels int32 (h,w) or None, stats int32 (k,5), centroids float64 (k,2)),
-    k = min(nlabels, max_labels); row 0 is the background, like cv2."""
-    mat = to_host_readonly(as_mat(mat))
+    k = min(nlabels, max_labels); row 0 is the background, like cv2.  A DeviceMat mask is labelled where it is (libvp vp_ccl_dev, or
+    vp_ccl_bits_dev on the bit plane range_threshold left with it): the labels are a DeviceMat too, only the statistics come back."""
+    mat = as_mat(mat)
+    if isinstance(mat, DeviceMat):
+        return _connected_components_dev(mat, numbering, max_labels, want_labels)
+    mat = to_host_readonly(mat)
     if not isinstance(mat, np.ndarray) or mat.dtype != np.uint8:
         raise TypeError("expected a uint8 mask")
     if mat.ndim == 3 and mat.shape[2] == 1:
@@ -40,6 +44,69 @@ def connected_components(mat: np.ndarray, numbering: int = _vp.CCL_BLOCK2X2, max
                                   _vp.ptr(cent), int(max_labels), _vp.C.byref(n)), ctx.handle)
     k = min(n.value, max_labels)
     return n.value, labels, stats[:k].copy(), cent[:k].copy()
+
+
+def _connected_components_dev(mat, numbering, max_labels, want_labels):
+    if mat.dtype != np.uint8:
+        raise TypeError("expected a uint8 mask")
+    if mat.ndim == 3 and mat.shape[2] == 1:
+        mat = mat.reshaped(mat.shape[:2])
+    if mat.ndim != 2 or mat.size == 0:
+        raise ValueError("expected a non-empty (h, w) mask")
+    ctx = _vp.default_context()
+    mat.refresh_device(ctx)
+    h, w = mat.shape
+    labels = DeviceMat(ctx, (h, w), np.int32) if want_labels else None
+    stats = np.empty((max_labels, 5), np.int32)
+    cent = np.empty((max_labels, 2), np.float64)
+    n = _vp.C.c_int32(0)
+    lp = labels.dev_ptr if want_labels else None
+    bits = mat._bits
+    if bits is not None and mat._dev_ok and mat._ctx is ctx:       # the same test find_contours uses: the plane still describes the mask
+        _vp.check(_vp.lib().vp_ccl_bits_dev(ctx.handle, bits.ptr, w, h, int(numbering), lp, _vp.ptr(stats), _vp.ptr(cent), int(max_labels),
+                                            _vp.C.byref(n)), ctx.handle)
+    else:
+        _vp.check(_vp.lib().vp_ccl_dev(ctx.handle, mat.dev_ptr, w, w, h, int(numbering), lp, _vp.ptr(stats), _vp.ptr(cent), int(max_labels),
+                                       _vp.C.byref(n)), ctx.handle)
+    k = min(n.value, max_labels)
+    return n.value, labels, stats[:k].copy(), cent[:k].copy()
+
+
+def hist_median(counts) -> np.float64:
+    """np.median of the uint8 values whose 256 counters are `counts`: the middle value, or the exact half-sum of the two middle ones."""
+    counts = [int(c) for c in counts]
+    n = sum(counts)
+    if n == 0:
+        raise ValueError("median of an empty histogram")
+    lo_rank, hi_rank = (n - 1) // 2, n // 2              # ranks (from 0) of the two middle values; equal for odd n
+    lo = hi = None
+    seen = 0
+    for v, c in enumerate(counts):
+        seen += c
+        if lo is None and seen > lo_rank:
+            lo = v
+        if seen > hi_rank:
+            hi = v
+            break
+    return np.float64((lo + hi) / 2.0)
+
+
+def hist_mean(counts) -> np.float64:
+    """np.mean of the uint8 values whose 256 counters are `counts`: the exact integer sum divided by the count in float64."""
+    counts = [int(c) for c in counts]
+    n = sum(counts)
+    if n == 0:
+        raise ValueError("mean of an empty histogram")
+    return np.float64(float(sum(v * c for v, c in enumerate(counts))) / float(n))
+
+
+def device_histogram(mat) -> np.ndarray:
+    """256 counters over all bytes of a uint8 DeviceMat (libvp vp_hist_u8_dev): 1 KB comes back, the image stays in HBM."""
+    ctx = _vp.default_context()
+    src = device_image(ctx, mat, 0)
+    hist = np.zeros(256, np.uint32)
+    _vp.check(_vp.lib().vp_hist_u8_dev(ctx.handle, src.dev_ptr, src.size, _vp.ptr(hist)), ctx.handle)
+    return hist
 
 
 _sums_tls = threading.local()
@@ -176,8 +243,14 @@ def canny(mat: np.ndarray, lower: int, upper: int) -> np.ndarray:
 
 
 def simple_canny(mat: np.ndarray, sigma: float = 0.33, use_mean: bool = False) -> np.ndarray:
-    """utils/feature.py:69-101: thresholds (1 -/+ sigma) x median (or mean) of the image, truncated to int and clamped to [0, 255]."""
-    mid = np.mean(mat) if use_mean else np.median(mat)
+    """utils/feature.py:69-101: thresholds (1 -/+ sigma) x median (or mean) of the image, truncated to int and clamped to [0, 255].  For a
+    DeviceMat the statistic comes from the device histogram (all bytes, as numpy's over a multi-channel image)."""
+    mat = as_mat(mat)
+    if isinstance(mat, DeviceMat) and mat.dtype == np.uint8:
+        hist = device_histogram(mat)
+        mid = hist_mean(hist) if use_mean else hist_median(hist)
+    else:
+        mid = np.mean(mat) if use_mean else np.median(mat)
     lower = int(max(0, (1.0 - sigma) * mid))
     upper = int(min(255, (1.0 + sigma) * mid))
     return canny(mat, lower, upper)

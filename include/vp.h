@@ -72,9 +72,12 @@ int vp_synchronize(vp_ctx* ctx);
  * VP_OPT_HOUGH_LDS (0 or 1, default 1): the Hough vote counts accumulator rows in LDS and flushes them with global atomics where a
  * row fits the block's LDS budget; 0 makes every vote a global atomic.  Results are identical.
  * VP_OPT_HOUGH_CIRCLES_LDS (0 or 1, default 1): the HoughCircles radius histogram of a centre is kept in LDS where its bins fit
- * (160 KiB); 0 keeps it in device memory, as for more bins than that (the tests reach that path at small sizes).  Results are identical. */
+ * (160 KiB); 0 keeps it in device memory, as for more bins than that (the tests reach that path at small sizes).  Results are identical.
+ * VP_OPT_BLUR_ONEPASS (1, 0 or -1, default -1): which kernels vp_gaussian_blur_dev runs.  1 = the one-pass kernel (rows and halo staged
+ * in LDS, the 16-bit intermediate never written to device memory) wherever its tile fits, i.e. kernels up to 31 on both axes; 0 = always
+ * the two passes of vp_gaussian_blur_u8; -1 = the measured choice.  Results are identical. */
 enum { VP_OPT_CHAIN_STREAMS = 1, VP_OPT_CCL_LEVELS = 2, VP_OPT_CCL_MERGE_CAP = 3, VP_OPT_FLAT_OPS = 4, VP_OPT_HOUGH_LDS = 5,
-       VP_OPT_HOUGH_CIRCLES_LDS = 6 };
+       VP_OPT_HOUGH_CIRCLES_LDS = 6, VP_OPT_BLUR_ONEPASS = 7 };
 int vp_set_option(vp_ctx* ctx, int option, int value);
 /* HIP-event stopwatch on the context's stream (bench.py: roofline.achieved). */
 int vp_timer_start(vp_ctx* ctx);
@@ -448,6 +451,40 @@ int vp_nms_f32(vp_ctx* ctx, const float* boxes_host, const float* scores_host, i
                int32_t* keep_out_host, int32_t* n_keep_out);
 int vp_nms_dev(vp_ctx* ctx, const float* boxes_dev, const float* scores_dev, int n, float thr, int rotated, int max_keep,
                int32_t* keep_out_dev, int32_t* n_keep_dev);
+
+/* ---- blur, resize, warp, thresholds, histogram and labelling on device images ------------------------------------------------ *
+ * The device-resident forms of vp_gaussian_blur_u8, vp_resize_u8(_scaled), vp_warp_affine_u8, vp_threshold_u8, vp_otsu_threshold_u8,
+ * vp_adaptive_threshold_mean_u8 and vp_ccl_u8: the same arithmetic, argument checks, limits and error codes (h <= 65535, odd kernels
+ * up to 511, block sizes up to 151, ...), images are device pointers.  A source with a stride is read in place (row stride in bytes,
+ * at least w * cn); results are tightly packed; dst must not overlap src (VP_ERR_INVALID).  Nothing is copied and nothing waits:
+ * the kernels are enqueued on the context's stream and the call returns - except where a number has to come back, as said below.
+ * Small parameters reach the device without a wait as well: the Gaussian taps through the context's pinned staging, the warp matrix
+ * as kernel arguments.
+ * vp_gaussian_blur_dev: kernels up to 31 x 31 may run as one launch (see VP_OPT_BLUR_ONEPASS); the result is the same either way.
+ * vp_resize_dev: inv_sx, inv_sy as vp_resize_u8_scaled; both <= 0 means dst / src, as vp_resize_u8.
+ * vp_otsu_threshold_dev: the histogram, getThreshVal_Otsu_8u (one lane of one wave, the doubles of the host form in the same order)
+ * and the threshold are three launches with no synchronisation; the threshold chosen is left in *thresh_dev (a double in device
+ * memory, may be NULL), for the caller to fetch when it wants the number.
+ * vp_hist_u8_dev: the 256-bin histogram of n_bytes device bytes into hist_host (256 uint32); synchronises.
+ * vp_ccl_dev / vp_ccl_bits_dev: vp_ccl_u8 on a device mask, or on the bit plane vp_inrange_u8_bits_dev left of it.  labels_dev
+ * (nullable) is a packed (h, w) int32 device image and stays there; stats_host / centroids_host / n_labels are host memory as in
+ * vp_ccl_u8; synchronises. */
+int vp_gaussian_blur_dev(vp_ctx* ctx, const uint8_t* src_dev, size_t src_stride, int w, int h, int cn, int kw, int kh, double sigma1,
+                         double sigma2, uint8_t* dst_dev);
+int vp_resize_dev(vp_ctx* ctx, const uint8_t* src_dev, size_t src_stride, int w, int h, int cn, int dst_w, int dst_h, double inv_sx,
+                  double inv_sy, uint8_t* dst_dev);
+int vp_warp_affine_dev(vp_ctx* ctx, const uint8_t* src_dev, size_t src_stride, int w, int h, int cn, const double* m23, int flags,
+                       int border_mode, const uint8_t* border_value, uint8_t* dst_dev, int dst_w, int dst_h);
+int vp_threshold_u8_dev(vp_ctx* ctx, const uint8_t* src_dev, size_t n_bytes, double thresh, double maxval, int type, uint8_t* dst_dev);
+int vp_otsu_threshold_dev(vp_ctx* ctx, const uint8_t* src_dev, size_t n_bytes, double maxval, int type, double* thresh_dev,
+                          uint8_t* dst_dev);
+int vp_adaptive_threshold_mean_dev(vp_ctx* ctx, const uint8_t* src_dev, size_t src_stride, int w, int h, double max_value, int type,
+                                   int block_size, double c, uint8_t* dst_dev);
+int vp_hist_u8_dev(vp_ctx* ctx, const uint8_t* src_dev, size_t n_bytes, uint32_t* hist_host);
+int vp_ccl_dev(vp_ctx* ctx, const uint8_t* src_dev, size_t src_stride, int w, int h, int numbering, int32_t* labels_dev,
+               int32_t* stats_host, double* centroids_host, int max_labels, int32_t* n_labels);
+int vp_ccl_bits_dev(vp_ctx* ctx, const unsigned long long* bits_dev, int w, int h, int numbering, int32_t* labels_dev,
+                    int32_t* stats_host, double* centroids_host, int max_labels, int32_t* n_labels);
 
 /* ---- device memory helpers (so a host program needs no HIP binding of its own) --------- */
 int vp_dev_alloc(vp_ctx* ctx, size_t bytes, void** dev_ptr);
