@@ -2284,6 +2284,82 @@ int vp_hist_u8_dev(vp_ctx* ctx, const uint8_t* d_src, size_t n, uint32_t* hist)
     return vp_synchronize(ctx);
 }
 
+// ---- element-wise operators on device images (kernels: vp_elementwise.hip) ----------------------------------------------------------
+#define VP_EW_MAX ((size_t)1 << 40)
+// dst is a source itself or apart from it
+static bool ew_dst_ok(const void* src, const void* dst, size_t n) { return !src || src == dst || !dev_overlap(src, n, dst, n); }
+
+int vp_bitwise_u8_dev(vp_ctx* ctx, int op, const uint8_t* d_a, const uint8_t* d_b, int scalar, const uint8_t* d_mask, int cn, size_t n, uint8_t* d_dst, int bits_w,
+                      unsigned long long* d_bits, int* made_bits)
+{
+    VP_TRY(check_ctx(ctx));
+    if (made_bits) *made_bits = 0;
+    if (op < VP_BITWISE_AND || op > VP_BITWISE_NOT || !d_a || !d_dst || n == 0 || n > VP_EW_MAX || cn < 1 || cn > 4 || n % (size_t)cn != 0 ||
+        (op != VP_BITWISE_NOT && !d_b && (scalar < 0 || scalar > 255)) || bits_w < 0 || (d_bits && bits_w > 0 && (cn != 1 || n % (size_t)bits_w != 0)))
+        return vp_fail(ctx, VP_ERR_INVALID, "vp_bitwise_u8_dev arguments");
+    if (op == VP_BITWISE_NOT) d_b = nullptr;
+    if (!ew_dst_ok(d_a, d_dst, n) || !ew_dst_ok(d_b, d_dst, n) || (d_mask && dev_overlap(d_mask, n / cn, d_dst, n)) ||
+        (d_bits && bits_w > 0 && (dev_overlap(d_bits, (n + 7) / 8, d_dst, n) || dev_overlap(d_bits, (n + 7) / 8, d_a, n) || (d_b && dev_overlap(d_bits, (n + 7) / 8, d_b, n)))))
+        return vp_fail(ctx, VP_ERR_INVALID, "vp_bitwise_u8_dev: dst overlaps a source partly, or the mask or the bit plane overlaps an image");
+    return vpk_bitwise_u8(ctx, op, d_a, d_b, scalar, d_mask, cn, n, d_dst, bits_w, reinterpret_cast<u64*>(d_bits), made_bits);
+}
+
+int vp_arith_u8_dev(vp_ctx* ctx, int op, const uint8_t* d_a, const uint8_t* d_b, size_t n, uint8_t* d_dst)
+{
+    VP_TRY(check_ctx(ctx));
+    if (op < VP_ARITH_ADD || op > VP_ARITH_ABSDIFF || !d_a || !d_b || !d_dst || n == 0 || n > VP_EW_MAX || !ew_dst_ok(d_a, d_dst, n) || !ew_dst_ok(d_b, d_dst, n))
+        return vp_fail(ctx, VP_ERR_INVALID, "vp_arith_u8_dev arguments");
+    return vpk_arith_u8(ctx, op, d_a, d_b, n, d_dst);
+}
+
+int vp_lut_u8_dev(vp_ctx* ctx, const uint8_t* d_src, size_t n, int cn, const uint8_t* lut, uint8_t* d_dst)
+{
+    VP_TRY(check_ctx(ctx));
+    if (!d_src || !d_dst || !lut || n == 0 || n > VP_EW_MAX || cn < 1 || cn > 4 || n % (size_t)cn != 0 || !ew_dst_ok(d_src, d_dst, n))
+        return vp_fail(ctx, VP_ERR_INVALID, "vp_lut_u8_dev arguments");
+    return vpk_lut_u8(ctx, d_src, n, cn, lut, d_dst);
+}
+
+int vp_split_u8_dev(vp_ctx* ctx, const uint8_t* d_src, size_t npx, int cn, uint8_t* d_p0, uint8_t* d_p1, uint8_t* d_p2, uint8_t* d_p3)
+{
+    VP_TRY(check_ctx(ctx));
+    if (!d_src || npx == 0 || npx > VP_EW_MAX || cn < 2 || cn > 4) return vp_fail(ctx, VP_ERR_INVALID, "vp_split_u8_dev arguments");
+    uint8_t* pl[4] = {d_p0, cn > 1 ? d_p1 : nullptr, cn > 2 ? d_p2 : nullptr, cn > 3 ? d_p3 : nullptr};
+    bool any = false;
+    for (int c = 0; c < cn; c++) {
+        if (!pl[c]) continue;
+        any = true;
+        if (dev_overlap(d_src, npx * cn, pl[c], npx)) return vp_fail(ctx, VP_ERR_INVALID, "vp_split_u8_dev: a plane overlaps the source");
+        for (int e = 0; e < c; e++)
+            if (pl[e] && dev_overlap(pl[e], npx, pl[c], npx)) return vp_fail(ctx, VP_ERR_INVALID, "vp_split_u8_dev: planes overlap");
+    }
+    if (!any) return vp_fail(ctx, VP_ERR_INVALID, "vp_split_u8_dev: no destination plane");
+    return vpk_split_u8(ctx, d_src, npx, cn, pl[0], pl[1], pl[2], pl[3]);
+}
+
+int vp_merge_u8_dev(vp_ctx* ctx, const uint8_t* d_p0, const uint8_t* d_p1, const uint8_t* d_p2, const uint8_t* d_p3, size_t npx, int cn, uint8_t* d_dst)
+{
+    VP_TRY(check_ctx(ctx));
+    if (!d_dst || npx == 0 || npx > VP_EW_MAX || cn < 2 || cn > 4) return vp_fail(ctx, VP_ERR_INVALID, "vp_merge_u8_dev arguments");
+    const uint8_t* pl[4] = {d_p0, d_p1, cn > 2 ? d_p2 : nullptr, cn > 3 ? d_p3 : nullptr};
+    for (int c = 0; c < cn; c++)
+        if (!pl[c] || dev_overlap(pl[c], npx, d_dst, npx * cn)) return vp_fail(ctx, VP_ERR_INVALID, "vp_merge_u8_dev: a plane is missing or overlaps the destination");
+    return vpk_merge_u8(ctx, pl[0], pl[1], pl[2], pl[3], npx, cn, d_dst);
+}
+
+// the counter lives in the context's workspace: carved, zeroed, counted into and read back in stream order, and the call returns only
+// after the read - a second call finds nothing of the first
+int vp_count_nonzero_u8_dev(vp_ctx* ctx, const uint8_t* d_src, size_t n, uint64_t* count)
+{
+    VP_TRY(check_ctx(ctx));
+    if (!d_src || !count || n == 0 || n > VP_EW_MAX) return vp_fail(ctx, VP_ERR_INVALID, "vp_count_nonzero_u8_dev arguments");
+    VP_TRY(vp_ws_reserve(ctx, 4096));
+    TAKE(d_total, u64*, 8);
+    VP_TRY(vpk_count_nonzero_u8(ctx, d_src, n, d_total));
+    VP_TRY(d2h(ctx, count, d_total, 8));
+    return vp_synchronize(ctx);
+}
+
 // vp_ccl_u8 with the mask (or its bit plane) already in HBM; labels (nullable) stay there, the statistics come back
 static int ccl_dev_impl(vp_ctx* ctx, const char* who, const uint8_t* d_src, size_t src_stride, const u64* bits_in, int w, int h, int numbering,
                         int32_t* d_labels, int32_t* stats, double* centroids, int max_labels, int32_t* nlabels)

@@ -219,6 +219,18 @@ int vpk_draw_segments(vp_ctx* ctx, uint8_t* d_img, int w, int h, int cn, const i
 int vpk_add_weighted_u8(vp_ctx* ctx, const uint8_t* a, const uint8_t* b, size_t n, double alpha, double beta, double gamma, uint8_t* dst);
 int vpk_absdiff_sub_u8(vp_ctx* ctx, const uint8_t* a, const uint8_t* b, size_t n, uint8_t* dst);  // a - b saturating
 
+// ---- element-wise operators (vp_elementwise.hip) ------------------------------------------------
+// packed uint8 images of n bytes; dst may be one of the sources of the first three.  b == nullptr: the second operand is `scalar`;
+// mask (nullable): one byte per pixel of cn channels; d_bits (nullable): the result's bit plane as vpk_inrange_u8 leaves it, for a
+// single-channel 0/255 result of rows of bits_w pixels - *made_bits says whether it was written
+int vpk_bitwise_u8(vp_ctx* ctx, int op, const uint8_t* a, const uint8_t* b, int scalar, const uint8_t* mask, int cn, size_t n, uint8_t* dst, int bits_w = 0,
+                   u64* d_bits = nullptr, int* made_bits = nullptr);
+int vpk_arith_u8(vp_ctx* ctx, int op, const uint8_t* a, const uint8_t* b, size_t n, uint8_t* dst);
+int vpk_lut_u8(vp_ctx* ctx, const uint8_t* src, size_t n, int cn, const uint8_t* lut_host, uint8_t* dst);   // lut_host: cn tables of 256 bytes
+int vpk_split_u8(vp_ctx* ctx, const uint8_t* src, size_t npx, int cn, uint8_t* p0, uint8_t* p1, uint8_t* p2, uint8_t* p3);   // null plane: not written
+int vpk_merge_u8(vp_ctx* ctx, const uint8_t* p0, const uint8_t* p1, const uint8_t* p2, const uint8_t* p3, size_t npx, int cn, uint8_t* dst);
+int vpk_count_nonzero_u8(vp_ctx* ctx, const uint8_t* src, size_t n, u64* d_total);   // zeroes *d_total and counts into it, enqueued
+
 // ---- CCL (vp_ccl.hip) ----------------------------------------------------------------------------
 struct vp_ccl_ws {           // per-batch scratch, all device pointers
     u32* parent;             // [n][nids]

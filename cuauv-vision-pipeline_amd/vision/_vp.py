@@ -33,6 +33,8 @@ OPT_HOUGH_CIRCLES_LDS = 6
 OPT_BLUR_ONEPASS = 7
 THRESH_BINARY, THRESH_BINARY_INV, THRESH_TRUNC, THRESH_TOZERO, THRESH_TOZERO_INV = 0, 1, 2, 3, 4
 HOUGH_GRADIENT = 3
+BITWISE_AND, BITWISE_OR, BITWISE_XOR, BITWISE_NOT = 0, 1, 2, 3
+ARITH_ADD, ARITH_SUB, ARITH_ABSDIFF = 0, 1, 2
 PROF_KERNELS = 15
 
 
@@ -191,6 +193,13 @@ _SIGS = {
     "vp_hist_u8_dev": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
     "vp_ccl_dev": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]),
     "vp_ccl_bits_dev": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]),
+    "vp_bitwise_u8_dev": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_size_t, C.c_void_p, C.c_int, C.c_void_p,
+                                    C.POINTER(C.c_int)]),
+    "vp_arith_u8_dev": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
+    "vp_lut_u8_dev": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_int, C.c_void_p, C.c_void_p]),
+    "vp_split_u8_dev": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "vp_merge_u8_dev": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_int, C.c_void_p]),
+    "vp_count_nonzero_u8_dev": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.POINTER(C.c_uint64)]),
 }
 
 

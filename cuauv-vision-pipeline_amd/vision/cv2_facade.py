@@ -3,8 +3,9 @@ morphology lines of modules/preprocessor.py:52-129), so they run where no OpenCV
 
 `install()` registers this module as `cv2` ONLY when a real cv2 cannot be imported — a real OpenCV is never shadowed.
 Image arithmetic (cvtColor, inRange, erode/dilate/morphologyEx, findContours, connectedComponentsWithStats) goes to
-libvp (HIP); small polygon maths (moments, contourArea, arcLength, minAreaRect, boxPoints, approxPolyDP) and overlay
-helpers (addWeighted, drawContours, split/merge) are host numpy, as they are CPU code in OpenCV too.  Anything else
+libvp (HIP); small polygon maths (moments, contourArea, arcLength, minAreaRect, boxPoints, approxPolyDP) is host numpy, as it is
+CPU code in OpenCV too.  The element-wise operators (bitwise_*, add / subtract / absdiff, LUT, split / merge / extractChannel,
+countNonZero) are host numpy for numpy images and libvp kernels as soon as one image operand is a DeviceMat.  Anything else
 raises AttributeError like a missing cv2 symbol would."""
 import math
 import sys
@@ -59,12 +60,92 @@ def cvtColor(src, code):
 
 
 def split(m):
+    """cv2.split.  A uint8 DeviceMat of 2..4 channels gives DeviceMat planes (libvp vp_split_u8_dev) that share one allocation, each
+    starting at a multiple of 256 bytes; a single-channel one gives a one-element tuple with a device copy."""
+    from vision.devmat import DeviceMat, _DevBuf
+    from vision.utils.helpers import as_mat
+    m = as_mat(m)
+    if isinstance(m, DeviceMat) and m.dtype == np.uint8 and m.size and (m.ndim == 2 or (m.ndim == 3 and 1 <= m.shape[2] <= 4)):
+        ctx = _vp.default_context()
+        m.refresh_device(ctx)
+        h, w = m.shape[:2]
+        cn = 1 if m.ndim == 2 else m.shape[2]
+        if cn == 1:
+            out = DeviceMat(ctx, (h, w))
+            _vp.check(_vp.lib().vp_memcpy_d2d_async(ctx.handle, out.dev_ptr, m.dev_ptr, h * w), ctx.handle)
+            return (out,)
+        pitch = (h * w + 255) & ~255
+        buf = _DevBuf(ctx, pitch * cn)
+        planes = tuple(DeviceMat.over_buffer(ctx, buf, c * pitch, (h, w), np.uint8) for c in range(cn))
+        ptrs = [p.dev_ptr for p in planes] + [None] * (4 - cn)
+        _vp.check(_vp.lib().vp_split_u8_dev(ctx.handle, m.dev_ptr, h * w, cn, *ptrs), ctx.handle)
+        return planes
     m = np.asarray(m)
     return tuple(np.ascontiguousarray(m[:, :, c]) for c in range(m.shape[2])) if m.ndim == 3 else (m.copy(),)
 
 
 def merge(mv):
-    return np.ascontiguousarray(np.dstack(list(mv)))
+    """cv2.merge.  2..4 uint8 planes of one 2-D shape of which at least one is a DeviceMat give a DeviceMat (libvp vp_merge_u8_dev;
+    numpy planes are uploaded)."""
+    from vision.devmat import DeviceMat, finish_uploads
+    from vision.utils.helpers import as_mat
+    mv = [as_mat(p) for p in mv]
+    if any(isinstance(p, DeviceMat) for p in mv) and 2 <= len(mv) <= 4 and \
+            all(isinstance(p, (np.ndarray, DeviceMat)) and p.dtype == np.uint8 and p.ndim == 2 and p.size and tuple(p.shape) == tuple(mv[0].shape) for p in mv):
+        ctx = _vp.default_context()
+        up = []
+        try:
+            planes = [_on_device(ctx, p, up) for p in mv]
+            h, w = planes[0].shape
+            out = DeviceMat(ctx, (h, w, len(planes)))
+            ptrs = [p.dev_ptr for p in planes] + [None] * (4 - len(planes))
+            _vp.check(_vp.lib().vp_merge_u8_dev(ctx.handle, *ptrs, h * w, len(planes), out.dev_ptr), ctx.handle)
+        finally:
+            finish_uploads(ctx, up)
+        return out
+    return np.ascontiguousarray(np.dstack([np.asarray(p) for p in mv]))
+
+
+def extractChannel(src, coi):
+    """cv2.extractChannel: plane `coi` of an image; of a uint8 DeviceMat on the device (vp_split_u8_dev with one destination)."""
+    from vision.devmat import DeviceMat
+    from vision.utils.helpers import as_mat
+    src = as_mat(src)
+    if not isinstance(src, (np.ndarray, DeviceMat)) or src.ndim not in (2, 3) or src.size == 0:
+        raise error("extractChannel: expected a non-empty image")
+    cn = 1 if src.ndim == 2 else src.shape[2]
+    coi = int(coi)
+    if not 0 <= coi < cn:
+        raise error("extractChannel: the channel index is out of range")
+    if isinstance(src, DeviceMat) and src.dtype == np.uint8 and cn <= 4:
+        ctx = _vp.default_context()
+        src.refresh_device(ctx)
+        h, w = src.shape[:2]
+        out = DeviceMat(ctx, (h, w))
+        if cn == 1:
+            _vp.check(_vp.lib().vp_memcpy_d2d_async(ctx.handle, out.dev_ptr, src.dev_ptr, h * w), ctx.handle)
+        else:
+            ptrs = [out.dev_ptr if c == coi else None for c in range(4)]
+            _vp.check(_vp.lib().vp_split_u8_dev(ctx.handle, src.dev_ptr, h * w, cn, *ptrs), ctx.handle)
+        return out
+    src = np.asarray(src)
+    return src.copy() if src.ndim == 2 else np.ascontiguousarray(src[:, :, coi])
+
+
+def countNonZero(src):
+    """cv2.countNonZero (single channel only): of a uint8 DeviceMat on the device (vp_count_nonzero_u8_dev), numpy input by numpy."""
+    from vision.devmat import DeviceMat
+    from vision.utils.helpers import as_mat
+    src = as_mat(src)
+    if not isinstance(src, (np.ndarray, DeviceMat)) or src.ndim not in (1, 2, 3) or (src.ndim == 3 and src.shape[2] != 1):
+        raise error("countNonZero: expected a single-channel image")
+    if isinstance(src, DeviceMat) and src.dtype == np.uint8 and src.size:
+        ctx = _vp.default_context()
+        src.refresh_device(ctx)
+        n = _vp.C.c_uint64(0)
+        _vp.check(_vp.lib().vp_count_nonzero_u8_dev(ctx.handle, src.dev_ptr, src.size, _vp.C.byref(n)), ctx.handle)
+        return int(n.value)
+    return int(np.count_nonzero(np.asarray(src)))
 
 
 def inRange(src, lowerb, upperb):
@@ -360,16 +441,216 @@ def addWeighted(src1, alpha, src2, beta, gamma, dst=None, dtype=-1):
     return _into(dst, out)
 
 
-def add(src1, src2):
-    """cv2.add with saturation; one operand may be a scalar (modules/preprocessor.py:90-103 adds a bias to a channel)."""
-    a, b = (src1, src2) if isinstance(src1, np.ndarray) else (src2, src1)
-    a = np.asarray(a)
-    if a.dtype != np.uint8:
-        raise error("add: only uint8 arrays are on the accelerated path")
-    if np.isscalar(b):
-        acc = a.astype(np.float64) + float(b)          # cv2 adds the scalar as a double, then saturate_cast (round half even)
-        return np.clip(np.rint(acc), 0, 255).astype(np.uint8)
-    return np.clip(a.astype(np.int32) + np.asarray(b, np.int32), 0, 255).astype(np.uint8)
+# ---- element-wise operators (libvp vp_elementwise.hip) ------------------------------------------------------------------------------
+# numpy in gives numpy out through host numpy; one DeviceMat among the image operands keeps the work and the result on the device.
+
+def _on_device(ctx, m, pending):
+    """DeviceMat of a checked uint8 image on ctx (a numpy image is uploaded, shape kept)."""
+    from vision.devmat import DeviceMat
+    if isinstance(m, DeviceMat):
+        m.refresh_device(ctx)
+        return m
+    return DeviceMat.from_host(ctx, m, pending=pending)
+
+
+def _is_image(x):
+    from vision.devmat import DeviceMat
+    return isinstance(x, DeviceMat) or (isinstance(x, np.ndarray) and x.ndim >= 2)
+
+
+def _check_images(name, *mats):
+    """What cv2 rejects of the image operands of an element-wise operator, and what is outside this path."""
+    for m in mats:
+        if m.ndim not in (2, 3) or m.size == 0:
+            raise error(f"{name}: expected non-empty (h, w) or (h, w, c) images")
+        if m.dtype != np.uint8:
+            raise error(f"{name}: only uint8 images are on the accelerated path")
+        if tuple(m.shape) != tuple(mats[0].shape):
+            raise error(f"{name}: the images differ in size or in the number of channels")
+
+
+def _scalar_per_channel(name, s, cn):
+    """cv2's scalar operand as cn float64 values: one number (every channel, as `add` always did here) or up to four, one per channel."""
+    try:
+        v = np.asarray(s, dtype=np.float64).ravel()
+    except (TypeError, ValueError):
+        raise error(f"{name}: an operand is neither an image nor a scalar") from None
+    if np.ndim(s) == 0:
+        return np.full(cn, float(v[0]))
+    if not cn <= v.size <= 4:
+        raise error(f"{name}: the scalar needs one value per channel")
+    return v[:cn].copy()
+
+
+def _arith_statement(op, a, s, image_first):
+    """The float64 statement of image-with-scalar arithmetic: the scalar is a double, the result saturate_cast (round half even)."""
+    a = a.astype(np.float64)
+    if op == _vp.ARITH_ADD:
+        acc = a + s
+    elif op == _vp.ARITH_SUB:
+        acc = a - s if image_first else s - a
+    else:
+        acc = np.abs(a - s)
+    return np.clip(np.rint(acc), 0, 255).astype(np.uint8)
+
+
+def _launch(ctx, shape, inputs, run, binary=False):
+    """The result of an element-wise operator: computed when first needed (DeviceMat.deferred) under the rule addWeighted follows."""
+    from vision.devmat import DeviceMat, defer_enabled
+    if defer_enabled() and not any(x.host_escaped for x in inputs):
+        return DeviceMat.deferred(ctx, shape, np.uint8, binary, inputs, run)
+    out = DeviceMat(ctx, shape, binary=binary)
+    run(out)
+    return out
+
+
+def _lut_on_device(src, tables):
+    """tables: uint8 (cn, 256) for the cn interleaved channels of src, or (1, 256) for every byte."""
+    from vision.devmat import finish_uploads
+    ctx = _vp.default_context()
+    up = []
+    try:
+        d = _on_device(ctx, src, up)
+        tables = np.ascontiguousarray(tables, np.uint8)
+        n = int(d.size)
+
+        def run(out, d=d):
+            _vp.check(_vp.lib().vp_lut_u8_dev(ctx.handle, d.dev_ptr, n, len(tables), _vp.ptr(tables), out.dev_ptr), ctx.handle)
+        return _launch(ctx, d.shape, (d,), run)
+    finally:
+        finish_uploads(ctx, up)
+
+
+def _arith(name, op, src1, src2, dst):
+    from vision.devmat import DeviceMat, finish_uploads
+    from vision.utils.helpers import as_mat
+    a, b = as_mat(src1), as_mat(src2)
+    ia, ib = _is_image(a), _is_image(b)
+    if not (ia or ib):
+        raise error(f"{name}: at least one operand must be an image")
+    if ia and ib:
+        _check_images(name, a, b)
+        if not (isinstance(a, DeviceMat) or isinstance(b, DeviceMat)):
+            x, y = a.astype(np.int32), b.astype(np.int32)
+            r = x + y if op == _vp.ARITH_ADD else x - y if op == _vp.ARITH_SUB else np.abs(x - y)
+            return _into(dst, np.clip(r, 0, 255).astype(np.uint8))
+        ctx = _vp.default_context()
+        up = []
+        try:
+            da, db = _on_device(ctx, a, up), _on_device(ctx, b, up)
+            n = int(da.size)
+
+            def run(out, da=da, db=db):
+                _vp.check(_vp.lib().vp_arith_u8_dev(ctx.handle, op, da.dev_ptr, db.dev_ptr, n, out.dev_ptr), ctx.handle)
+            return _into(dst, _launch(ctx, da.shape, (da, db), run))
+        finally:
+            finish_uploads(ctx, up)
+    img, s = (a, b) if ia else (b, a)
+    _check_images(name, img)
+    cn = 1 if img.ndim == 2 else img.shape[2]
+    if cn > 4:
+        raise error(f"{name}: at most 4 channels with a scalar operand")
+    per_channel = np.ndim(s) != 0
+    s = _scalar_per_channel(name, s, cn)
+    if isinstance(img, np.ndarray):                      # host numpy, as ever: cv2 adds the scalar as a double, then saturate_cast
+        return _into(dst, _arith_statement(op, img, (s if img.ndim == 3 else s[0]) if per_channel else float(s[0]), ia))
+    # a device image: the same statement on the 256 values a byte can take, per channel, applied as a table (vp_lut_u8_dev)
+    tables = np.stack([_arith_statement(op, np.arange(256), float(v), ia) for v in (s if per_channel else s[:1])])
+    return _into(dst, _lut_on_device(img, tables))
+
+
+def add(src1, src2, dst=None):
+    """cv2.add with saturation; one operand may be a scalar or a per-channel tuple (modules/preprocessor.py:90-103 adds a bias to a
+    channel).  Two images, one of them a DeviceMat: libvp vp_arith_u8_dev; a DeviceMat and a scalar: a table (vp_lut_u8_dev)."""
+    return _arith("add", _vp.ARITH_ADD, src1, src2, dst)
+
+
+def subtract(src1, src2, dst=None):
+    """cv2.subtract (src1 - src2, saturated at 0); either operand may be the scalar."""
+    return _arith("subtract", _vp.ARITH_SUB, src1, src2, dst)
+
+
+def absdiff(src1, src2, dst=None):
+    """cv2.absdiff."""
+    return _arith("absdiff", _vp.ARITH_ABSDIFF, src1, src2, dst)
+
+
+def _bitwise(name, op, src1, src2, dst, mask):
+    from vision.devmat import DeviceMat, _byte_scalar, bitwise
+    from vision.utils.helpers import as_mat
+    if mask is not None and dst is not None:
+        raise error(f"{name}: mask together with dst (cv2 keeps dst's pixels where the mask is 0) is outside the accelerated path")
+    a = as_mat(src1)
+    b = None if op == _vp.BITWISE_NOT else as_mat(src2)
+    mask = None if mask is None else as_mat(mask)
+    scalar = 0
+    if b is not None and not _is_image(a):
+        a, b = b, a                                      # (and, or, xor commute)
+    if not _is_image(a):
+        raise error(f"{name}: expected an image")
+    if b is not None and not _is_image(b):
+        scalar, b = _byte_scalar(b), None
+        if scalar is None:
+            raise error(f"{name}: a scalar operand must be an integer in 0..255 on the accelerated path")
+    _check_images(name, *((a,) if b is None else (a, b)))
+    if mask is not None:
+        if not _is_image(mask) or mask.dtype != np.uint8:
+            raise error(f"{name}: the mask must be a uint8 image")
+        if mask.ndim == 3 and mask.shape[2] == 1:
+            mask = mask.reshaped(mask.shape[:2]) if isinstance(mask, DeviceMat) else mask[:, :, 0]
+        if tuple(mask.shape) != tuple(a.shape[:2]):
+            raise error(f"{name}: the mask must have the size of the image")
+        if a.ndim == 3 and a.shape[2] > 4:
+            raise error(f"{name}: at most 4 channels with a mask")
+    if any(isinstance(m, DeviceMat) for m in (a, b, mask)):
+        return _into(dst, bitwise(op, a, b, scalar, mask))
+    r = np.invert(a) if op == _vp.BITWISE_NOT else (np.bitwise_and, np.bitwise_or, np.bitwise_xor)[op](a, np.uint8(scalar) if b is None else b)
+    if mask is not None:
+        r = np.where((mask if a.ndim == 2 else mask[:, :, None]) != 0, r, np.uint8(0))
+    return _into(dst, np.ascontiguousarray(r))
+
+
+def bitwise_and(src1, src2, dst=None, mask=None):
+    """cv2.bitwise_and; where `mask` is 0 the result is 0 (vision_common.py:285 fill_ratio).  With a DeviceMat among the operands:
+    libvp vp_bitwise_u8_dev, and the result of two 0/255 masks is known to be one."""
+    return _bitwise("bitwise_and", _vp.BITWISE_AND, src1, src2, dst, mask)
+
+
+def bitwise_or(src1, src2, dst=None, mask=None):
+    return _bitwise("bitwise_or", _vp.BITWISE_OR, src1, src2, dst, mask)
+
+
+def bitwise_xor(src1, src2, dst=None, mask=None):
+    return _bitwise("bitwise_xor", _vp.BITWISE_XOR, src1, src2, dst, mask)
+
+
+def bitwise_not(src, dst=None, mask=None):
+    return _bitwise("bitwise_not", _vp.BITWISE_NOT, src, None, dst, mask)
+
+
+def LUT(src, lut, dst=None):
+    """cv2.LUT on uint8 images: one table of 256 uint8 entries for every channel, or one per channel as (256, cn) / (1, 256, cn)."""
+    from vision.devmat import DeviceMat
+    from vision.utils.helpers import as_mat
+    src = as_mat(src)
+    if not _is_image(src):
+        raise error("LUT: expected an image")
+    _check_images("LUT", src)
+    lut = np.asarray(as_mat(lut) if not isinstance(lut, DeviceMat) else lut.host(writable=False))
+    cn = 1 if src.ndim == 2 else src.shape[2]
+    if lut.dtype == np.uint8 and lut.size == 256 and (lut.ndim == 1 or lut.shape in ((256, 1), (1, 256), (1, 256, 1))):
+        tables = lut.reshape(1, 256)
+    elif lut.dtype == np.uint8 and cn > 1 and lut.shape in ((256, cn), (1, 256, cn)):
+        tables = np.ascontiguousarray(lut.reshape(256, cn).T)
+    else:
+        raise error("LUT: the table must be uint8 with 256 entries, or (256, cn) / (1, 256, cn) for an image of cn channels")
+    if isinstance(src, DeviceMat):
+        if cn > 4:
+            raise error("LUT: at most 4 channels on the accelerated path")
+        return _into(dst, _lut_on_device(src, tables))
+    if len(tables) == 1:
+        return _into(dst, tables[0][src])
+    return _into(dst, np.ascontiguousarray(np.stack([tables[c][src[:, :, c]] for c in range(cn)], axis=2)))
 
 
 def getRotationMatrix2D(center, angle, scale):

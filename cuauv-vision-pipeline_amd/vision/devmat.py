@@ -212,6 +212,13 @@ class DeviceMat:
         """A writable alias of the host copy has been handed out: writes through it are invisible to this object."""
         return self._escaped
 
+    def bit_plane(self, ctx):
+        """The mask's bit-packed form (a _DevBuf) when it was made with the mask and still describes it on `ctx`, else None.  A mask
+        that has not been launched yet is launched: its bit plane comes out of that launch (vision.devmat.bitwise)."""
+        if self._pending is not None and ctx is self._ctx:
+            self._force()
+        return self._bits if (self._dev_ok and self._ctx is ctx) else None
+
     def device_valid_for(self, ctx):
         return self._dev_ok and ctx is self._ctx and bool(ctx.handle)
 
@@ -315,6 +322,11 @@ class DeviceMat:
         return h.copy() if copy else h
 
     def __array_ufunc__(self, ufunc, method, *inputs, **kwargs):
+        if method == "__call__" and not kwargs and ufunc in _BITWISE:      # a & b, a | b, a ^ b, ~a (either side): stays on the device
+            r = _bitwise_operator(ufunc, inputs)
+            if r is not NotImplemented:
+                return r
+
         def conv(x, w):
             return x.host(writable=w) if isinstance(x, DeviceMat) else x
         ins = tuple(conv(x, False) for x in inputs)
@@ -394,6 +406,90 @@ DeviceMat.__neg__ = lambda self: np.negative(self)
 DeviceMat.__pos__ = lambda self: np.positive(self)
 DeviceMat.__abs__ = lambda self: np.absolute(self)
 DeviceMat.__invert__ = lambda self: np.invert(self)
+
+
+# ---- mask logic on the device ---------------------------------------------------------------------------------------------------
+_BITWISE = {np.bitwise_and: _vp.BITWISE_AND, np.bitwise_or: _vp.BITWISE_OR, np.bitwise_xor: _vp.BITWISE_XOR, np.invert: _vp.BITWISE_NOT}
+_U8_PROBE = np.zeros(1, np.uint8)
+
+
+def _byte_scalar(x):
+    """The value of a Python / numpy integer in 0..255 that numpy would combine with a uint8 image into a uint8 image; None for
+    everything else (booleans, floats, wider numpy integers, values outside a byte)."""
+    if isinstance(x, (bool, np.bool_)):
+        return None
+    if not (type(x) is int or (isinstance(x, np.integer) and np.result_type(_U8_PROBE, x) == np.uint8)):
+        return None
+    v = int(x)
+    return v if 0 <= v <= 255 else None
+
+
+def bitwise(op, a, b=None, scalar=0, mask=None):
+    """libvp vp_bitwise_u8_dev on uint8 images of one shape (DeviceMat or packed numpy, checked by the caller; at least one DeviceMat
+    or lazy mode on): op(a, b) - or op(a, scalar) when b is None, ~a for BITWISE_NOT - as a DeviceMat; `mask` (h, w): zero where it is
+    zero.  The result is a known 0/255 mask when the operands are, and then takes its bit plane from the same launch where the
+    kernel can make it; it is computed when first needed under the rule of DeviceMat.deferred."""
+    ctx = _vp.default_context()
+    up = []
+    try:
+        def dev(x):
+            if isinstance(x, DeviceMat):
+                x.refresh_device(ctx)
+                return x
+            return DeviceMat.from_host(ctx, x, pending=up)
+        da = dev(a)
+        db = dev(b) if (b is not None and op != _vp.BITWISE_NOT) else None
+        dm = dev(mask) if mask is not None else None
+        ins = tuple(x for x in (da, db, dm) if x is not None)
+        shape = da.shape
+        n = _prod(shape)
+        cn = 1 if dm is None else n // _prod(dm.shape)
+        if db is not None:
+            binary = da.binary and db.binary
+        else:
+            binary = da.binary and (op == _vp.BITWISE_NOT or scalar in (0, 255))
+        w = shape[1] if len(shape) == 2 else 0
+        want_bits = binary and w > 0 and w % 64 == 0 and (dm is None or cn == 1)
+        sc = int(scalar)
+
+        def run(out, da=da, db=db, dm=dm):
+            bits = _DevBuf(ctx, n // 8) if want_bits else None
+            made = C.c_int(0)
+            _vp.check(_vp.lib().vp_bitwise_u8_dev(ctx.handle, op, da.dev_ptr, None if db is None else db.dev_ptr, sc, None if dm is None else dm.dev_ptr,
+                                                  cn, n, out.dev_ptr, w if want_bits else 0, None if bits is None else bits.ptr, C.byref(made)), ctx.handle)
+            if made.value:
+                out._bits = bits
+        if defer_enabled() and not any(x.host_escaped for x in ins):
+            return DeviceMat.deferred(ctx, shape, np.uint8, binary, ins, run)
+        out = DeviceMat(ctx, shape, binary=binary)
+        run(out)
+        return out
+    finally:
+        finish_uploads(ctx, up)
+
+
+def _bitwise_operator(ufunc, inputs):
+    """The operators & | ^ ~ between uint8 images of one shape (DeviceMat or numpy, at least one DeviceMat) or an image and a byte:
+    a DeviceMat.  NotImplemented for everything else (other types, broadcasting, lazy mode off): the caller takes the host path."""
+    if not _lazy:
+        return NotImplemented
+    op = _BITWISE[ufunc]
+    if len(inputs) != (1 if op == _vp.BITWISE_NOT else 2):
+        return NotImplemented
+    imgs, scalar = [], None
+    for x in inputs:
+        if isinstance(x, (DeviceMat, np.ndarray)):
+            imgs.append(x)
+        else:
+            scalar = _byte_scalar(x)
+            if scalar is None:
+                return NotImplemented
+    shape = tuple(imgs[0].shape)
+    if not shape or 0 in shape or any(m.dtype != np.uint8 or tuple(m.shape) != shape for m in imgs):
+        return NotImplemented
+    if len(imgs) == 2:
+        return bitwise(op, imgs[0], imgs[1])
+    return bitwise(op, imgs[0], None, 0 if scalar is None else scalar)      # (the three binary operations commute)
 
 
 def finish_uploads(ctx, pending):

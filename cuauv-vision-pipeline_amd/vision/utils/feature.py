@@ -61,7 +61,7 @@ def _connected_components_dev(mat, numbering, max_labels, want_labels):
     cent = np.empty((max_labels, 2), np.float64)
     n = _vp.C.c_int32(0)
     lp = labels.dev_ptr if want_labels else None
-    bits = mat._bits
+    bits = mat.bit_plane(ctx)
     if bits is not None and mat._dev_ok and mat._ctx is ctx:       # the same test find_contours uses: the plane still describes the mask
         _vp.check(_vp.lib().vp_ccl_bits_dev(ctx.handle, bits.ptr, w, h, int(numbering), lp, _vp.ptr(stats), _vp.ptr(cent), int(max_labels),
                                             _vp.C.byref(n)), ctx.handle)
@@ -393,7 +393,7 @@ def find_contours(mat: np.ndarray, mode: int = _vp.RETR_EXTERNAL, method: int = 
             sc = _scratch.arrays = ((max_c, max_p), pts, counts, holes)
         _, pts, counts, holes = sc
         nc, npts = _vp.C.c_int32(0), _vp.C.c_int64(0)
-        bits = getattr(dev, "_bits", None) if dev is not None else None
+        bits = dev.bit_plane(ctx) if dev is not None else None
         if with_hierarchy:
             hier = getattr(_scratch, "hier", None)
             if hier is None or len(hier) != max_c:

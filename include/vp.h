@@ -486,6 +486,35 @@ int vp_ccl_dev(vp_ctx* ctx, const uint8_t* src_dev, size_t src_stride, int w, in
 int vp_ccl_bits_dev(vp_ctx* ctx, const unsigned long long* bits_dev, int w, int h, int numbering, int32_t* labels_dev,
                     int32_t* stats_host, double* centroids_host, int max_labels, int32_t* n_labels);
 
+/* ---- element-wise operators on device images ------------------------------------------------------------------------------------ *
+ * Packed uint8 device images; every entry enqueues on the context's stream and returns at once, except vp_count_nonzero_u8_dev.
+ * Pointers need no alignment (planes of one frame sit at byte offsets inside one allocation): 16-byte accesses are used where the
+ * pointers allow them, byte accesses elsewhere.  n_bytes / n_px at most 2^40.
+ * vp_bitwise_u8_dev: cv2.bitwise_and / _or / _xor / _not (op: VP_BITWISE_*) on n_bytes bytes.  The second operand is the image b_dev
+ *   or, when b_dev is NULL, the byte `scalar` (0..255); VP_BITWISE_NOT reads a_dev alone.  mask_dev (nullable): one byte per pixel of
+ *   an image of cn channels (1..4; n_bytes a multiple of cn) - where it is 0 the result is 0, as cv2 leaves a fresh dst.  dst_dev may
+ *   be a_dev or b_dev (not a partial overlap).  bits_dev (nullable) with bits_w > 0: the caller states that the result is a 0/255
+ *   mask of rows of bits_w pixels (cn == 1) and takes its bit-packed form from the same launch - layout and conditions of
+ *   vp_inrange_u8_bits_dev (bits_w % 64 == 0, dst_dev and bits_dev 16-B aligned); *made_bits (nullable) says whether it was written.
+ * vp_arith_u8_dev: cv2.add / subtract / absdiff (op: VP_ARITH_*) of two images, saturated to 0..255; dst_dev may be a source.
+ * vp_lut_u8_dev: dst[p, c] = lut_host[c * 256 + src[p, c]] for cn (1..4) interleaved channels; lut_host: cn * 256 bytes of host
+ *   memory, read before the call returns (the tables travel as kernel arguments).  Image-with-scalar arithmetic is a table.
+ * vp_split_u8_dev / vp_merge_u8_dev: n_px pixels of cn (2..4) interleaved channels to / from cn planes (plane c at pc_dev; the planes
+ *   beyond cn are ignored).  Source and destination must not overlap.  vp_split_u8_dev skips a plane whose pointer is NULL
+ *   (cv2.extractChannel: one plane), at least one must be given.
+ * vp_count_nonzero_u8_dev: cv2.countNonZero of n_bytes bytes into *count_host; synchronises. */
+enum { VP_BITWISE_AND = 0, VP_BITWISE_OR = 1, VP_BITWISE_XOR = 2, VP_BITWISE_NOT = 3 };
+enum { VP_ARITH_ADD = 0, VP_ARITH_SUB = 1, VP_ARITH_ABSDIFF = 2 };
+int vp_bitwise_u8_dev(vp_ctx* ctx, int op, const uint8_t* a_dev, const uint8_t* b_dev, int scalar, const uint8_t* mask_dev, int cn,
+                      size_t n_bytes, uint8_t* dst_dev, int bits_w, unsigned long long* bits_dev, int* made_bits);
+int vp_arith_u8_dev(vp_ctx* ctx, int op, const uint8_t* a_dev, const uint8_t* b_dev, size_t n_bytes, uint8_t* dst_dev);
+int vp_lut_u8_dev(vp_ctx* ctx, const uint8_t* src_dev, size_t n_bytes, int cn, const uint8_t* lut_host, uint8_t* dst_dev);
+int vp_split_u8_dev(vp_ctx* ctx, const uint8_t* src_dev, size_t n_px, int cn, uint8_t* p0_dev, uint8_t* p1_dev, uint8_t* p2_dev,
+                    uint8_t* p3_dev);
+int vp_merge_u8_dev(vp_ctx* ctx, const uint8_t* p0_dev, const uint8_t* p1_dev, const uint8_t* p2_dev, const uint8_t* p3_dev, size_t n_px,
+                    int cn, uint8_t* dst_dev);
+int vp_count_nonzero_u8_dev(vp_ctx* ctx, const uint8_t* src_dev, size_t n_bytes, uint64_t* count_host);
+
 /* ---- device memory helpers (so a host program needs no HIP binding of its own) --------- */
 int vp_dev_alloc(vp_ctx* ctx, size_t bytes, void** dev_ptr);
 int vp_dev_free(vp_ctx* ctx, void* dev_ptr);    /* ctx may be NULL (memory that outlived its context) */
