@@ -558,9 +558,10 @@ int vp_cvt_color_u8(vp_ctx* ctx, int code, const uint8_t* src, size_t src_stride
 {
     VP_TRY(check_ctx(ctx));
     if (!src || w <= 0 || h <= 0 || h > 65535) return vp_fail(ctx, VP_ERR_INVALID, "vp_cvt_color_u8 arguments");
-    if (code < VP_BGR2LAB || code > VP_LAB2BGR) return vp_fail(ctx, VP_ERR_INVALID, "conversion code");
-    const int scn = code == VP_GRAY2BGR ? 1 : 3, dcn = code == VP_BGR2GRAY ? 1 : 3;
+    int scn = 0, dcn = 0;
+    if (!vp_cvt_channels(code, &scn, &dcn)) return vp_fail(ctx, VP_ERR_INVALID, "conversion code");
     if (src_stride < (size_t)w * scn) return vp_fail(ctx, VP_ERR_INVALID, "src_stride");
+    if (planes && dcn != 3 && code != VP_BGR2GRAY) return vp_fail(ctx, VP_ERR_INVALID, "split planes of a 1- or 4-channel result");
     const size_t npx = (size_t)w * h;
     uint8_t* hp[3] = {nullptr, nullptr, nullptr};
     if (planes)
@@ -1106,9 +1107,10 @@ int vp_cvt_color_dev(vp_ctx* ctx, int code, const uint8_t* d_src, size_t src_str
 {
     VP_TRY(check_ctx(ctx));
     if (!d_src || w <= 0 || h <= 0 || h > 65535) return vp_fail(ctx, VP_ERR_INVALID, "vp_cvt_color_dev arguments");
-    if (code < VP_BGR2LAB || code > VP_LAB2BGR) return vp_fail(ctx, VP_ERR_INVALID, "conversion code");
-    const int scn = code == VP_GRAY2BGR ? 1 : 3, dcn = code == VP_BGR2GRAY ? 1 : 3;
+    int scn = 0, dcn = 0;
+    if (!vp_cvt_channels(code, &scn, &dcn)) return vp_fail(ctx, VP_ERR_INVALID, "conversion code");
     if (src_stride < (size_t)w * scn) return vp_fail(ctx, VP_ERR_INVALID, "src_stride");
+    if (d_planes && dcn != 3 && code != VP_BGR2GRAY) return vp_fail(ctx, VP_ERR_INVALID, "split planes of a 1- or 4-channel result");
     uint8_t* dp[3] = {nullptr, nullptr, nullptr};
     if (d_planes)
         for (int c = 0; c < dcn; c++) dp[c] = d_planes[c];

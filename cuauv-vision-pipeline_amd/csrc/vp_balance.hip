@@ -20,6 +20,7 @@
 // one of them could differ (a comparison within e of its boundary, a product gain * v within e of an integer: about one frame in
 // 10^5) three threads run the fold itself, in the reference's order, and the tables are built from its result.
 #include "vp_internal.h"
+#include "vp_hsv.h"
 #include <mutex>
 #include <cmath>
 #include <cstdlib>
@@ -45,41 +46,6 @@ __device__ __forceinline__ void cb_bgr2hsv(const HsvTab& t, int b, int g, int r,
     hh += hh < 0 ? 180 : 0;
     H = hh < 0 ? 0 : (hh > 255 ? 255 : hh);
     V = v;
-}
-
-__device__ __forceinline__ int cb_sat_round(float x)   // cv::saturate_cast<uchar>(float): round half to even, clamp
-{
-    const int v = (int)rintf(x);
-    return v < 0 ? 0 : (v > 255 ? 255 : v);
-}
-
-// OpenCV color_hsv.simd.hpp HSV2RGB_b -> HSV2RGB_f, vector arithmetic form (v - v*s, v - (v*s)*h, (v - v*s) + (v*s)*h), hrange 180.
-// Built with -ffp-contract=off: every product and sum rounds separately, as the universal intrinsics do.
-__device__ __forceinline__ void cb_hsv2bgr(int H, int S, int V, int& b, int& g, int& r)
-{
-    float h = (float)H * (6.f / 180.f);
-    const float s = (float)S * (1.f / 255.f), v = (float)V * (1.f / 255.f);
-    const float pre = truncf(h);
-    h = h - pre;
-    const float vs = v * s;
-    const float vsh = vs * h;
-    const float t1 = v - vs, t2 = v - vsh, t3 = (v - vs) + vsh;
-    float sec = truncf(pre * (1.0f / 6.0f));
-    sec = pre - sec * 6.0f;
-    const int sector = (int)sec;
-    // (b, g, r) = tab[{1,3,0}, {1,0,2}, {3,0,1}, {0,2,1}, {0,1,3}, {2,1,0}][sector], tab = {v, t1, t2, t3}
-    float fb, fg, fr;
-    switch (sector) {
-    case 0: fb = t1; fg = t3; fr = v; break;
-    case 1: fb = t1; fg = v; fr = t2; break;
-    case 2: fb = t3; fg = v; fr = t1; break;
-    case 3: fb = v; fg = t2; fr = t1; break;
-    case 4: fb = v; fg = t1; fr = t3; break;
-    default: fb = t2; fg = t1; fr = v; break;
-    }
-    b = cb_sat_round(fb * 255.f);
-    g = cb_sat_round(fg * 255.f);
-    r = cb_sat_round(fr * 255.f);
 }
 
 __device__ __forceinline__ int cb_tile_of(const cb_params& P, size_t pix_in_frame)

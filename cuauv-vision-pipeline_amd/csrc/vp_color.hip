@@ -9,6 +9,7 @@
 // kernels consume.  The arithmetic is OpenCV's 8-bit fixed point; the
 // LUTs live in LDS.  HBM-bound: 4.125 B/px.
 #include "vp_lab.h"
+#include "vp_hsv.h"
 #include <algorithm>
 #include <cstdlib>
 #include <cstring>
@@ -94,17 +95,11 @@ __device__ __forceinline__ bool in3(const vp_range3& q, int c0, int c1, int c2)
 }
 
 template <int MODE>
-struct ModeLds;
+struct ModeLds { typedef int type; };   // no tables: gray, YCrCb / YUV, XYZ, HLS, HSV -> BGR, the reorders
 template <>
 struct ModeLds<VP_BGR2LAB> { typedef LabLds type; };
 template <>
 struct ModeLds<VP_BGR2HSV> { typedef HsvLds type; };
-template <>
-struct ModeLds<VP_BGR2GRAY> { typedef int type; };
-template <>
-struct ModeLds<VP_BGR2YCRCB> { typedef int type; };
-template <>
-struct ModeLds<VP_BGR2HLS> { typedef int type; };
 template <>
 struct ModeLds<VP_LAB2BGR> { typedef LabInvLds type; };
 
@@ -356,13 +351,39 @@ int vpk_color_thresh(vp_ctx* ctx, int mode, const uint8_t* d_bgr, size_t stride,
 
 // ---- standalone conversions (operator API) ----------------------------------------------------
 
-// RGB2YCrCb_i<uchar>: Q14 integers, Y as in BGR2GRAY; stored Y, Cr, Cb
-__device__ __forceinline__ void ycrcb_px(int b, int g, int r, int& c0, int& c1, int& c2)
+// RGB2YCrCb_i<uchar>: Q14 integers, Y as in BGR2GRAY; cr / cb = the red and the blue difference with coefficients KR / KB
+template <int KR, int KB>
+__device__ __forceinline__ void ycc_px(int b, int g, int r, int& Y, int& cr, int& cb)
 {
-    const int Y = (b * 1868 + g * 9617 + r * 4899 + (1 << 13)) >> 14;
-    c0 = Y;
-    c1 = min(max(((r - Y) * 11682 + (128 << 14) + (1 << 13)) >> 14, 0), 255);
-    c2 = min(max(((b - Y) * 9241 + (128 << 14) + (1 << 13)) >> 14, 0), 255);
+    Y = (b * 1868 + g * 9617 + r * 4899 + (1 << 13)) >> 14;
+    cr = min(max(((r - Y) * KR + (128 << 14) + (1 << 13)) >> 14, 0), 255);
+    cb = min(max(((b - Y) * KB + (128 << 14) + (1 << 13)) >> 14, 0), 255);
+}
+// stored Y, Cr, Cb
+__device__ __forceinline__ void ycrcb_px(int b, int g, int r, int& c0, int& c1, int& c2) { ycc_px<11682, 9241>(b, g, r, c0, c1, c2); }
+// the YUV coefficients; stored Y, U (blue difference), V (red difference)
+__device__ __forceinline__ void yuv_px(int b, int g, int r, int& c0, int& c1, int& c2) { ycc_px<14369, 8061>(b, g, r, c0, c2, c1); }
+// YCrCb2RGB_i<uchar>: Q14, (C0..C3) = the coefficients of r from cr, g from cr, g from cb, b from cb
+template <int C0, int C1, int C2, int C3>
+__device__ __forceinline__ void ycc_inv_px(int Y, int cr, int cb, int& b, int& g, int& r)
+{
+    cr -= 128; cb -= 128;
+    b = clamp255(Y + ((cb * C3 + (1 << 13)) >> 14));
+    g = clamp255(Y + ((cb * C2 + cr * C1 + (1 << 13)) >> 14));
+    r = clamp255(Y + ((cr * C0 + (1 << 13)) >> 14));
+}
+// RGB2XYZ_i / XYZ2RGB_i<uchar>: Q12 rows
+__device__ __forceinline__ void xyz_px(int b, int g, int r, int& X, int& Y, int& Z)
+{
+    X = clamp255((r * 1689 + g * 1465 + b * 739 + (1 << 11)) >> 12);
+    Y = clamp255((r * 871 + g * 2929 + b * 296 + (1 << 11)) >> 12);
+    Z = clamp255((r * 79 + g * 488 + b * 3892 + (1 << 11)) >> 12);
+}
+__device__ __forceinline__ void xyz_inv_px(int X, int Y, int Z, int& b, int& g, int& r)
+{
+    b = clamp255((X * 228 - Y * 836 + Z * 4331 + (1 << 11)) >> 12);
+    g = clamp255((-X * 3970 + Y * 7684 + Z * 170 + (1 << 11)) >> 12);
+    r = clamp255((X * 13273 - Y * 6296 - Z * 2042 + (1 << 11)) >> 12);
 }
 // RGB2HLS_b: float32 statement sequence of RGB2HLS_f (hrange 180) on src * (1/255); single correctly rounded operations, no contraction
 __device__ __forceinline__ int hls_sat(float v) { return min(max((int)rintf(v), 0), 255); }
@@ -388,7 +409,29 @@ __device__ __forceinline__ void hls_px(int bi, int gi, int ri, int& c0, int& c1,
     c2 = hls_sat(__fmul_rn(sat, 255.f));
 }
 
-template <int CODE>
+// one pixel of a conversion with a 3-channel source, BGR order on the BGR side (the RGB twins exchange on the load or the store).
+// NEED: which channels of a Lab result are wanted
+template <int CODE, int NEED>
+__device__ __forceinline__ void cvt_px(const typename ModeLds<CODE>::type& s, const vp_tables& tab, int b, int g, int r, int& c0, int& c1, int& c2)
+{
+    if constexpr (CODE == VP_BGR2GRAY) c0 = gray_px(b, g, r);
+    else if constexpr (CODE == VP_BGR2LAB) lab_px<NEED>(s, b, g, r, c0, c1, c2);
+    else if constexpr (CODE == VP_BGR2YCRCB) ycrcb_px(b, g, r, c0, c1, c2);
+    else if constexpr (CODE == VP_BGR2HLS) hls_px(b, g, r, c0, c1, c2);
+    else if constexpr (CODE == VP_LAB2BGR) lab2bgr_px(s, tab.abxz, b, g, r, c0, c1, c2);   // (b, g, r) hold (L, a, b) here, and the source channels below
+    else if constexpr (CODE == VP_BGR2YUV) yuv_px(b, g, r, c0, c1, c2);
+    else if constexpr (CODE == VP_YCRCB2BGR) ycc_inv_px<22987, -11698, -5636, 29049>(b, g, r, c0, c1, c2);
+    else if constexpr (CODE == VP_YUV2BGR) ycc_inv_px<18678, -9519, -6472, 33292>(b, r, g, c0, c1, c2);   // V stands in for Cr, U for Cb
+    else if constexpr (CODE == VP_BGR2XYZ) xyz_px(b, g, r, c0, c1, c2);
+    else if constexpr (CODE == VP_XYZ2BGR) xyz_inv_px(b, g, r, c0, c1, c2);
+    else if constexpr (CODE == VP_HLS2BGR) hls2bgr_px(b, g, r, c0, c1, c2);
+    else if constexpr (CODE == VP_HSV2BGR) cb_hsv2bgr(b, g, r, c0, c1, c2);
+    else if constexpr (CODE == VP_BGR2RGB) { c0 = b; c1 = g; c2 = r; }
+    else hsv_px(s, b, g, r, c0, c1, c2);
+}
+
+// SWIN / SWOUT: the source / the result is in RGB order (first and third channel exchanged on the load / on the store)
+template <int CODE, bool SWIN, bool SWOUT>
 __global__ __launch_bounds__(256) void k_cvt_color(const uint8_t* __restrict__ src, size_t stride, int w, int h, vp_tables tab,
                                                    uint8_t* __restrict__ dst, uint8_t* __restrict__ p0,
                                                    uint8_t* __restrict__ p1, uint8_t* __restrict__ p2)
@@ -399,19 +442,16 @@ __global__ __launch_bounds__(256) void k_cvt_color(const uint8_t* __restrict__ s
     const int y = blockIdx.y;
     if (x >= w) return;
     const uint8_t* p = src + (size_t)y * stride + 3 * (size_t)x;
-    const int b = p[0], g = p[1], r = p[2];
+    const int b = p[SWIN ? 2 : 0], g = p[1], r = p[SWIN ? 0 : 2];
     const size_t o = (size_t)y * w + x;
+    int c0 = 0, c1 = 0, c2 = 0;
+    cvt_px<CODE, 7>(s, tab, b, g, r, c0, c1, c2);
     if constexpr (CODE == VP_BGR2GRAY) {
-        const uint8_t v = (uint8_t)gray_px(b, g, r);
+        const uint8_t v = (uint8_t)c0;
         if (dst) dst[o] = v;
         if (p0) p0[o] = v;
     } else {
-        int c0 = 0, c1 = 0, c2 = 0;
-        if constexpr (CODE == VP_BGR2LAB) lab_px<7>(s, b, g, r, c0, c1, c2);
-        else if constexpr (CODE == VP_BGR2YCRCB) ycrcb_px(b, g, r, c0, c1, c2);
-        else if constexpr (CODE == VP_BGR2HLS) hls_px(b, g, r, c0, c1, c2);
-        else if constexpr (CODE == VP_LAB2BGR) lab2bgr_px(s, tab.abxz, b, g, r, c0, c1, c2);   // (b, g, r) hold (L, a, b) here
-        else hsv_px(s, b, g, r, c0, c1, c2);
+        if constexpr (SWOUT) { const int t = c0; c0 = c2; c2 = t; }
         if (dst) { dst[3 * o] = (uint8_t)c0; dst[3 * o + 1] = (uint8_t)c1; dst[3 * o + 2] = (uint8_t)c2; }
         if (p0) p0[o] = (uint8_t)c0;
         if (p1) p1[o] = (uint8_t)c1;
@@ -437,7 +477,7 @@ __global__ __launch_bounds__(256) void k_gray2bgr(const uint8_t* __restrict__ sr
 // of pixels), every pointer 16-B aligned; one lane = 16 px = three 16-B loads, and per requested output 16-B stores (interleaved
 // image: three of them; a plane: one).  Only what is asked for is computed (NEED: bit c = channel c of the converted pixel is stored
 // somewhere) and stored.  The one-pixel-per-thread kernels above stay for strided views, unaligned planes and the last npx % 16 px.
-template <int CODE, int NEED>
+template <int CODE, int NEED, bool SWIN, bool SWOUT>
 __global__ __launch_bounds__(256) void k_cvt_color_flat(const uint8_t* __restrict__ src, size_t ngroups, vp_tables tab, uint8_t* __restrict__ dst,
                                                         uint8_t* __restrict__ p0, uint8_t* __restrict__ p1, uint8_t* __restrict__ p2)
 {
@@ -451,14 +491,10 @@ __global__ __launch_bounds__(256) void k_cvt_color_flat(const uint8_t* __restric
         u32 a[4] = {0, 0, 0, 0}, b[4] = {0, 0, 0, 0}, c[4] = {0, 0, 0, 0};
 #pragma unroll
         for (int k = 0; k < 16; k++) {
-            const int bb = BYTE_OF(in, 3 * k), gg = BYTE_OF(in, 3 * k + 1), rr = BYTE_OF(in, 3 * k + 2);
+            const int bb = BYTE_OF(in, 3 * k + (SWIN ? 2 : 0)), gg = BYTE_OF(in, 3 * k + 1), rr = BYTE_OF(in, 3 * k + (SWIN ? 0 : 2));
             int c0 = 0, c1 = 0, c2 = 0;
-            if constexpr (CODE == VP_BGR2GRAY) c0 = gray_px(bb, gg, rr);
-            else if constexpr (CODE == VP_BGR2LAB) lab_px<NEED>(s, bb, gg, rr, c0, c1, c2);
-            else if constexpr (CODE == VP_BGR2YCRCB) ycrcb_px(bb, gg, rr, c0, c1, c2);
-            else if constexpr (CODE == VP_BGR2HLS) hls_px(bb, gg, rr, c0, c1, c2);
-            else if constexpr (CODE == VP_LAB2BGR) lab2bgr_px(s, tab.abxz, bb, gg, rr, c0, c1, c2);
-            else hsv_px(s, bb, gg, rr, c0, c1, c2);
+            cvt_px<CODE, NEED>(s, tab, bb, gg, rr, c0, c1, c2);
+            if constexpr (SWOUT) { const int t = c0; c0 = c2; c2 = t; }
             a[k >> 2] |= (u32)c0 << (8 * (k & 3));
             b[k >> 2] |= (u32)c1 << (8 * (k & 3));
             c[k >> 2] |= (u32)c2 << (8 * (k & 3));
@@ -512,44 +548,184 @@ __global__ __launch_bounds__(256) void k_gray2bgr_flat(const uint8_t* __restrict
 
 static inline bool aligned16(const void* p) { return ((uintptr_t)p & 15u) == 0; }
 
-template <int CODE>
+template <int CODE, bool SWIN, bool SWOUT>
 static void launch_cvt_generic(vp_ctx* ctx, const uint8_t* d_src, size_t stride, int w, int h, uint8_t* d_dst, uint8_t* d_p0, uint8_t* d_p1, uint8_t* d_p2)
 {
-    hipLaunchKernelGGL((k_cvt_color<CODE>), dim3((unsigned)((w + 255) / 256), (unsigned)h), dim3(256), 0, ctx->stream, d_src, stride, w, h, ctx->tab, d_dst,
+    hipLaunchKernelGGL((k_cvt_color<CODE, SWIN, SWOUT>), dim3((unsigned)((w + 255) / 256), (unsigned)h), dim3(256), 0, ctx->stream, d_src, stride, w, h, ctx->tab, d_dst,
                        d_p0, d_p1, d_p2);
 }
 
-template <int CODE>
+template <int CODE, bool SWIN = false, bool SWOUT = false>
 static void launch_cvt(vp_ctx* ctx, const uint8_t* d_src, size_t stride, int w, int h, uint8_t* d_dst, uint8_t* d_p0, uint8_t* d_p1, uint8_t* d_p2)
 {
     const size_t npx = (size_t)w * h, ngroups = npx / 16;
     const bool flat = ctx->flat_ops && (stride == (size_t)w * 3 || h == 1) && ngroups > 0 && aligned16(d_src) && aligned16(d_dst) && aligned16(d_p0) &&
                       aligned16(d_p1) && aligned16(d_p2);
-    if (!flat) { launch_cvt_generic<CODE>(ctx, d_src, stride, w, h, d_dst, d_p0, d_p1, d_p2); return; }
+    if (!flat) { launch_cvt_generic<CODE, SWIN, SWOUT>(ctx, d_src, stride, w, h, d_dst, d_p0, d_p1, d_p2); return; }
     const dim3 grid((unsigned)std::min<size_t>((ngroups + 255) / 256, (size_t)ctx->num_cu * 32));
     int need = d_dst ? 7 : ((d_p0 ? 1 : 0) | (d_p1 ? 2 : 0) | (d_p2 ? 4 : 0));
     if constexpr (CODE == VP_BGR2LAB) {
         switch (need) {       // every cube-root look-up that is not needed is a dependent LDS read less per pixel
-            case 1: hipLaunchKernelGGL((k_cvt_color_flat<CODE, 1>), grid, dim3(256), 0, ctx->stream, d_src, ngroups, ctx->tab, d_dst, d_p0, d_p1, d_p2); break;
-            case 2: hipLaunchKernelGGL((k_cvt_color_flat<CODE, 2>), grid, dim3(256), 0, ctx->stream, d_src, ngroups, ctx->tab, d_dst, d_p0, d_p1, d_p2); break;
-            case 4: hipLaunchKernelGGL((k_cvt_color_flat<CODE, 4>), grid, dim3(256), 0, ctx->stream, d_src, ngroups, ctx->tab, d_dst, d_p0, d_p1, d_p2); break;
-            default: hipLaunchKernelGGL((k_cvt_color_flat<CODE, 7>), grid, dim3(256), 0, ctx->stream, d_src, ngroups, ctx->tab, d_dst, d_p0, d_p1, d_p2); break;
+            case 1: hipLaunchKernelGGL((k_cvt_color_flat<CODE, 1, SWIN, SWOUT>), grid, dim3(256), 0, ctx->stream, d_src, ngroups, ctx->tab, d_dst, d_p0, d_p1, d_p2); break;
+            case 2: hipLaunchKernelGGL((k_cvt_color_flat<CODE, 2, SWIN, SWOUT>), grid, dim3(256), 0, ctx->stream, d_src, ngroups, ctx->tab, d_dst, d_p0, d_p1, d_p2); break;
+            case 4: hipLaunchKernelGGL((k_cvt_color_flat<CODE, 4, SWIN, SWOUT>), grid, dim3(256), 0, ctx->stream, d_src, ngroups, ctx->tab, d_dst, d_p0, d_p1, d_p2); break;
+            default: hipLaunchKernelGGL((k_cvt_color_flat<CODE, 7, SWIN, SWOUT>), grid, dim3(256), 0, ctx->stream, d_src, ngroups, ctx->tab, d_dst, d_p0, d_p1, d_p2); break;
         }
     } else {
-        hipLaunchKernelGGL((k_cvt_color_flat<CODE, 7>), grid, dim3(256), 0, ctx->stream, d_src, ngroups, ctx->tab, d_dst, d_p0, d_p1, d_p2);
+        hipLaunchKernelGGL((k_cvt_color_flat<CODE, 7, SWIN, SWOUT>), grid, dim3(256), 0, ctx->stream, d_src, ngroups, ctx->tab, d_dst, d_p0, d_p1, d_p2);
     }
     const size_t done = ngroups * 16;
     if (done < npx) {   // the last npx % 16 pixels, as a one-row image
         const int dcn = CODE == VP_BGR2GRAY ? 1 : 3;
-        launch_cvt_generic<CODE>(ctx, d_src + done * 3, 0, (int)(npx - done), 1, d_dst ? d_dst + done * dcn : nullptr, d_p0 ? d_p0 + done : nullptr,
+        launch_cvt_generic<CODE, SWIN, SWOUT>(ctx, d_src + done * 3, 0, (int)(npx - done), 1, d_dst ? d_dst + done * dcn : nullptr, d_p0 ? d_p0 + done : nullptr,
                                  d_p1 ? d_p1 + done : nullptr, d_p2 ? d_p2 + done : nullptr);
     }
+}
+
+// ---- alpha and reorders: BGRA / RGBA <-> BGR, BGRA <-> RGBA, GRAY -> BGRA, BGRA / RGBA -> GRAY -------------------------------------
+// One pixel: SCN source bytes -> (c0, c1, c2) in the source's order, SWAP exchanges the first and the third, then DCN bytes out:
+// 3 = the triple, 4 = the triple and alpha (the source's, or 255), 1 = the gray of the triple taken as (b, g, r).
+template <int SCN, int DCN, bool SWAP>
+__device__ __forceinline__ u32 reorder_px(u32 c0, u32 c1, u32 c2, u32 a)     // the DCN result bytes, first byte lowest
+{
+    if constexpr (SCN == 1) { c1 = c0; c2 = c0; }
+    if constexpr (SWAP) { const u32 t = c0; c0 = c2; c2 = t; }
+    if constexpr (DCN == 1) return (u32)gray_px((int)c0, (int)c1, (int)c2);
+    return c0 | (c1 << 8) | (c2 << 16) | (DCN == 4 ? (SCN == 4 ? a : 255u) << 24 : 0u);
+}
+
+template <int SCN, int DCN, bool SWAP>
+__global__ __launch_bounds__(256) void k_reorder(const uint8_t* __restrict__ src, size_t stride, int w, int h, uint8_t* __restrict__ dst,
+                                                 uint8_t* __restrict__ p0, uint8_t* __restrict__ p1, uint8_t* __restrict__ p2)   // planes: DCN == 3 only
+{
+    const int x = blockIdx.x * 256 + threadIdx.x;
+    const int y = blockIdx.y;
+    if (x >= w) return;
+    const uint8_t* p = src + (size_t)y * stride + (size_t)SCN * x;
+    const u32 v = reorder_px<SCN, DCN, SWAP>(p[0], SCN > 1 ? p[SCN > 1 ? 1 : 0] : 0u, SCN > 1 ? p[SCN > 1 ? 2 : 0] : 0u, SCN == 4 ? p[SCN == 4 ? 3 : 0] : 0u);
+    const size_t o = (size_t)y * w + x;
+    if (dst) {
+#pragma unroll
+        for (int c = 0; c < DCN; c++) dst[o * DCN + c] = (uint8_t)(v >> (8 * c));
+    }
+    if constexpr (DCN == 3) {
+        if (p0) p0[o] = (uint8_t)v;
+        if (p1) p1[o] = (uint8_t)(v >> 8);
+        if (p2) p2[o] = (uint8_t)(v >> 16);
+    }
+}
+
+// Flat form on the pattern of k_cvt_color_flat: lane = 16 px = SCN 16-B loads and DCN 16-B stores, whole dwords both ways; the byte
+// shuffles between a 3-byte and a 4-byte pixel stay in registers (compile-time positions), so neither side of the copy goes through LDS.
+// A 3-channel result may also (or only) go to split planes, one 16-B store each.
+template <int SCN, int DCN, bool SWAP>
+__global__ __launch_bounds__(256) void k_reorder_flat(const uint8_t* __restrict__ src, size_t ngroups, uint8_t* __restrict__ dst, uint8_t* __restrict__ p0,
+                                                      uint8_t* __restrict__ p1, uint8_t* __restrict__ p2)
+{
+    const size_t step = (size_t)gridDim.x * 256;
+    for (size_t g = (size_t)blockIdx.x * 256 + threadIdx.x; g < ngroups; g += step) {
+        u32 in[4 * SCN];
+#pragma unroll
+        for (int j = 0; j < SCN; j++) {
+            const uint4 v = reinterpret_cast<const uint4*>(src + g * 16 * SCN)[j];
+            in[4 * j] = v.x; in[4 * j + 1] = v.y; in[4 * j + 2] = v.z; in[4 * j + 3] = v.w;
+        }
+        u32 out[4 * DCN];
+        u32 pl[3][4] = {{0, 0, 0, 0}, {0, 0, 0, 0}, {0, 0, 0, 0}};
+#pragma unroll
+        for (int j = 0; j < 4 * DCN; j++) out[j] = 0;
+#pragma unroll
+        for (int k = 0; k < 16; k++) {
+            u32 v;
+            if constexpr (SCN == 4 && DCN == 4) {       // one dword in, one dword out
+                v = in[k];
+                if constexpr (SWAP) v = (v & 0xff00ff00u) | ((v >> 16) & 0xffu) | ((v & 0xffu) << 16);
+                out[k] = v;
+            } else {
+                v = reorder_px<SCN, DCN, SWAP>(BYTE_OF(in, SCN * k), SCN > 1 ? BYTE_OF(in, SCN * k + (SCN > 1 ? 1 : 0)) : 0u,
+                                               SCN > 1 ? BYTE_OF(in, SCN * k + (SCN > 1 ? 2 : 0)) : 0u, SCN == 4 ? in[k] >> 24 : 0u);
+                if constexpr (DCN == 4) out[k] = v;
+                else {
+#pragma unroll
+                    for (int c = 0; c < DCN; c++) out[(DCN * k + c) >> 2] |= ((v >> (8 * c)) & 0xffu) << (8 * ((DCN * k + c) & 3));
+                    if constexpr (DCN == 3) {
+#pragma unroll
+                        for (int c = 0; c < 3; c++) pl[c][k >> 2] |= ((v >> (8 * c)) & 0xffu) << (8 * (k & 3));
+                    }
+                }
+            }
+        }
+        if (dst) {
+#pragma unroll
+            for (int j = 0; j < DCN; j++) vp_store16(dst + g * 16 * DCN + 16 * j, out[4 * j], out[4 * j + 1], out[4 * j + 2], out[4 * j + 3]);
+        }
+        if constexpr (DCN == 3) {
+            if (p0) vp_store16(p0 + g * 16, pl[0][0], pl[0][1], pl[0][2], pl[0][3]);
+            if (p1) vp_store16(p1 + g * 16, pl[1][0], pl[1][1], pl[1][2], pl[1][3]);
+            if (p2) vp_store16(p2 + g * 16, pl[2][0], pl[2][1], pl[2][2], pl[2][3]);
+        }
+    }
+}
+
+template <int SCN, int DCN, bool SWAP>
+static void launch_reorder(vp_ctx* ctx, const uint8_t* d_src, size_t stride, int w, int h, uint8_t* d_dst, uint8_t* d_p0, uint8_t* d_p1, uint8_t* d_p2)
+{
+    const size_t npx = (size_t)w * h, ngroups = npx / 16;
+    const bool flat = ctx->flat_ops && (stride == (size_t)w * SCN || h == 1) && ngroups > 0 && aligned16(d_src) && aligned16(d_dst) && aligned16(d_p0) &&
+                      aligned16(d_p1) && aligned16(d_p2);
+    if (!flat) {
+        hipLaunchKernelGGL((k_reorder<SCN, DCN, SWAP>), dim3((unsigned)((w + 255) / 256), (unsigned)h), dim3(256), 0, ctx->stream, d_src, stride, w, h, d_dst,
+                           d_p0, d_p1, d_p2);
+        return;
+    }
+    const dim3 grid((unsigned)std::min<size_t>((ngroups + 255) / 256, (size_t)ctx->num_cu * 32));
+    hipLaunchKernelGGL((k_reorder_flat<SCN, DCN, SWAP>), grid, dim3(256), 0, ctx->stream, d_src, ngroups, d_dst, d_p0, d_p1, d_p2);
+    const size_t done = ngroups * 16;
+    if (done < npx)   // the last npx % 16 pixels, as a one-row image
+        hipLaunchKernelGGL((k_reorder<SCN, DCN, SWAP>), dim3(1, 1), dim3(256), 0, ctx->stream, d_src + done * SCN, (size_t)0, (int)(npx - done), 1,
+                           d_dst ? d_dst + done * DCN : nullptr, d_p0 ? d_p0 + done : nullptr, d_p1 ? d_p1 + done : nullptr, d_p2 ? d_p2 + done : nullptr);
+}
+
+// channels of the source and of the result of a conversion code; false: no such code
+bool vp_cvt_channels(int code, int* scn, int* dcn)
+{
+    if (code < 0 || code >= VP_CVT_CODES) return false;
+    *scn = 3; *dcn = 3;
+    switch (code) {
+        case VP_GRAY2BGR: *scn = 1; break;
+        case VP_BGR2GRAY: case VP_RGB2GRAY: *dcn = 1; break;
+        case VP_BGRA2BGR: case VP_RGBA2BGR: *scn = 4; break;
+        case VP_BGR2BGRA: case VP_BGR2RGBA: *dcn = 4; break;
+        case VP_BGRA2RGBA: *scn = 4; *dcn = 4; break;
+        case VP_GRAY2BGRA: *scn = 1; *dcn = 4; break;
+        case VP_BGRA2GRAY: case VP_RGBA2GRAY: *scn = 4; *dcn = 1; break;
+        default: break;
+    }
+    return true;
 }
 
 int vpk_cvt_color(vp_ctx* ctx, int code, const uint8_t* d_src, size_t stride, int w, int h, uint8_t* d_dst, uint8_t* d_p0,
                   uint8_t* d_p1, uint8_t* d_p2)
 {
+#define CVT3(code_, body_, swin_, swout_) \
+    case code_: launch_cvt<body_, swin_, swout_>(ctx, d_src, stride, w, h, d_dst, d_p0, d_p1, d_p2); break;
+#define REORDER(code_, scn_, dcn_, swap_) \
+    case code_: if (!d_dst && (dcn_ != 3 || (!d_p0 && !d_p1 && !d_p2))) return vp_fail(ctx, VP_ERR_INVALID, "conversion destination"); \
+                launch_reorder<scn_, dcn_, swap_>(ctx, d_src, stride, w, h, d_dst, dcn_ == 3 ? d_p0 : nullptr, dcn_ == 3 ? d_p1 : nullptr, \
+                                                  dcn_ == 3 ? d_p2 : nullptr); break;
     switch (code) {
+        CVT3(VP_BGR2YUV, VP_BGR2YUV, false, false)     CVT3(VP_RGB2YUV, VP_BGR2YUV, true, false)
+        CVT3(VP_YUV2BGR, VP_YUV2BGR, false, false)     CVT3(VP_YUV2RGB, VP_YUV2BGR, false, true)
+        CVT3(VP_YCRCB2BGR, VP_YCRCB2BGR, false, false) CVT3(VP_YCRCB2RGB, VP_YCRCB2BGR, false, true)
+        CVT3(VP_BGR2XYZ, VP_BGR2XYZ, false, false)     CVT3(VP_RGB2XYZ, VP_BGR2XYZ, true, false)
+        CVT3(VP_XYZ2BGR, VP_XYZ2BGR, false, false)     CVT3(VP_XYZ2RGB, VP_XYZ2BGR, false, true)
+        CVT3(VP_HLS2BGR, VP_HLS2BGR, false, false)     CVT3(VP_HLS2RGB, VP_HLS2BGR, false, true)
+        CVT3(VP_HSV2RGB, VP_HSV2BGR, false, true)      CVT3(VP_BGR2RGB, VP_BGR2RGB, false, true)
+        CVT3(VP_RGB2GRAY, VP_BGR2GRAY, true, false)    CVT3(VP_RGB2HSV, VP_BGR2HSV, true, false)
+        CVT3(VP_RGB2HLS, VP_BGR2HLS, true, false)      CVT3(VP_RGB2LAB, VP_BGR2LAB, true, false)
+        CVT3(VP_RGB2YCRCB, VP_BGR2YCRCB, true, false)  CVT3(VP_LAB2RGB, VP_LAB2BGR, false, true)
+        REORDER(VP_BGRA2BGR, 4, 3, false)  REORDER(VP_RGBA2BGR, 4, 3, true)  REORDER(VP_BGR2BGRA, 3, 4, false)  REORDER(VP_BGR2RGBA, 3, 4, true)
+        REORDER(VP_BGRA2RGBA, 4, 4, true)  REORDER(VP_GRAY2BGRA, 1, 4, false)  REORDER(VP_BGRA2GRAY, 4, 1, false)  REORDER(VP_RGBA2GRAY, 4, 1, true)
         case VP_BGR2LAB: launch_cvt<VP_BGR2LAB>(ctx, d_src, stride, w, h, d_dst, d_p0, d_p1, d_p2); break;
         case VP_BGR2HSV: launch_cvt<VP_BGR2HSV>(ctx, d_src, stride, w, h, d_dst, d_p0, d_p1, d_p2); break;
         case VP_BGR2GRAY: launch_cvt<VP_BGR2GRAY>(ctx, d_src, stride, w, h, d_dst, d_p0, d_p1, d_p2); break;
@@ -573,6 +749,8 @@ int vpk_cvt_color(vp_ctx* ctx, int code, const uint8_t* d_src, size_t stride, in
         }
         default: return vp_fail(ctx, VP_ERR_INVALID, "conversion code");
     }
+#undef CVT3
+#undef REORDER
     VP_HIP(ctx, hipGetLastError());
     return VP_OK;
 }

@@ -130,6 +130,7 @@ int vpk_color_thresh(vp_ctx* ctx, int mode, const uint8_t* d_bgr, size_t stride,
                      const vp_range3& r, uint8_t* d_mask /*nullable*/, u64* d_bits /*nullable*/);
 int vpk_cvt_color(vp_ctx* ctx, int code, const uint8_t* d_src, size_t stride, int w, int h, uint8_t* d_dst,
                   uint8_t* d_p0, uint8_t* d_p1, uint8_t* d_p2);
+bool vp_cvt_channels(int code, int* scn, int* dcn);     // channels of the source / result of a conversion code; false: no such code
 int vpk_inrange_u8(vp_ctx* ctx, const uint8_t* d_src, size_t stride, int w, int h, int cn, const vp_range3& r,
                    uint8_t* d_dst, u64* d_bits = nullptr, int* made_bits = nullptr);
 int vpk_inrange_f32(vp_ctx* ctx, const float* d_src, size_t stride_bytes, int w, int h, float lo, float hi,

@@ -14,6 +14,14 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("VP_LIB") or os.path.join(os.path.dirname(_HERE), "lib", "libvp.so")   # VP_LIB: measurement builds (tools/build_probe.sh)
 
 BGR2LAB, BGR2HSV, BGR2GRAY, GRAY2BGR, HSV2BGR, BGR2YCRCB, BGR2HLS, LAB2BGR = 0, 1, 2, 3, 4, 5, 6, 7
+BGR2YUV, YUV2BGR, YCRCB2BGR, BGR2XYZ, XYZ2BGR, HLS2BGR = 8, 9, 10, 11, 12, 13
+BGR2RGB, RGB2GRAY, RGB2HSV, HSV2RGB, RGB2HLS, HLS2RGB, RGB2LAB, LAB2RGB = 14, 15, 16, 17, 18, 19, 20, 21
+RGB2YCRCB, YCRCB2RGB, RGB2YUV, YUV2RGB, RGB2XYZ, XYZ2RGB = 22, 23, 24, 25, 26, 27
+BGRA2BGR, RGBA2BGR, BGR2BGRA, BGR2RGBA, BGRA2RGBA, GRAY2BGRA, BGRA2GRAY, RGBA2GRAY = 28, 29, 30, 31, 32, 33, 34, 35
+CVT_CODES = 36
+# (source channels, result channels) of the conversion codes that are not 3 -> 3 (vp_cvt_channels in csrc/vp_color.hip)
+CVT_CHANNELS = {GRAY2BGR: (1, 3), BGR2GRAY: (3, 1), RGB2GRAY: (3, 1), BGRA2BGR: (4, 3), RGBA2BGR: (4, 3), BGR2BGRA: (3, 4), BGR2RGBA: (3, 4),
+                BGRA2RGBA: (4, 4), GRAY2BGRA: (1, 4), BGRA2GRAY: (4, 1), RGBA2GRAY: (4, 1)}
 LAB_MIN_AB, LAB_AB_TAB = -8145, 36864
 WB_GLOBAL_MEAN, WB_MAX_KERNEL = 0, 4095
 CB_EQUALIZE_RGB, CB_RGB_CONTRAST, CB_HSV_CONTRAST, CB_HSI_CONTRAST, CB_EXTREMA_CLIPPING, CB_ADAPTIVE_CAST = 1, 2, 4, 8, 16, 32

@@ -21,6 +21,14 @@ from vision.utils import transform as _transform
 COLOR_BGR2LAB, COLOR_BGR2HSV, COLOR_BGR2GRAY, COLOR_GRAY2BGR, COLOR_HSV2BGR = 44, 40, 6, 8, 54     # cv2's own enum values
 COLOR_BGR2YCrCb, COLOR_BGR2YCR_CB, COLOR_BGR2HLS = 36, 36, 52
 COLOR_LAB2BGR = COLOR_Lab2BGR = 56
+COLOR_BGR2BGRA, COLOR_BGRA2BGR, COLOR_RGBA2RGB, COLOR_BGR2RGBA, COLOR_RGBA2BGR, COLOR_BGRA2RGB = 0, 1, 1, 2, 3, 3
+COLOR_BGR2RGB, COLOR_RGB2BGR, COLOR_BGRA2RGBA, COLOR_RGBA2BGRA = 4, 4, 5, 5
+COLOR_RGB2GRAY, COLOR_GRAY2BGRA, COLOR_BGRA2GRAY, COLOR_RGBA2GRAY = 7, 9, 10, 11
+COLOR_BGR2XYZ, COLOR_RGB2XYZ, COLOR_XYZ2BGR, COLOR_XYZ2RGB = 32, 33, 34, 35
+COLOR_RGB2YCrCb, COLOR_RGB2YCR_CB, COLOR_YCrCb2BGR, COLOR_YCR_CB2BGR, COLOR_YCrCb2RGB, COLOR_YCR_CB2RGB = 37, 37, 38, 38, 39, 39
+COLOR_RGB2HSV, COLOR_RGB2Lab, COLOR_RGB2LAB, COLOR_RGB2HLS, COLOR_HSV2RGB = 41, 45, 45, 53, 55
+COLOR_Lab2RGB, COLOR_LAB2RGB, COLOR_HLS2BGR, COLOR_HLS2RGB = 57, 57, 60, 61
+COLOR_BGR2YUV, COLOR_RGB2YUV, COLOR_YUV2BGR, COLOR_YUV2RGB = 82, 83, 84, 85
 COLOR_BGR2Luv, COLOR_BGR2LUV = 50, 50     # named by modules/preprocessor.py:76; see DESIGN.md section 7 for what the stand-in does with it
 MORPH_RECT, MORPH_CROSS, MORPH_ELLIPSE = 0, 1, 2
 MORPH_ERODE, MORPH_DILATE, MORPH_OPEN, MORPH_CLOSE, MORPH_GRADIENT = 0, 1, 2, 3, 4
@@ -50,7 +58,17 @@ class error(Exception):
 
 _CVT = {COLOR_BGR2LAB: _color.bgr_to_lab, COLOR_BGR2HSV: _color.bgr_to_hsv, COLOR_BGR2GRAY: _color.bgr_to_gray,
         COLOR_GRAY2BGR: _color.gray_to_bgr, COLOR_HSV2BGR: _color.hsv_to_bgr, COLOR_BGR2YCrCb: _color.bgr_to_ycrcb,
-        COLOR_BGR2HLS: _color.bgr_to_hls, COLOR_LAB2BGR: _color.lab_to_bgr}
+        COLOR_BGR2HLS: _color.bgr_to_hls, COLOR_LAB2BGR: _color.lab_to_bgr,
+        COLOR_BGR2YUV: _color.bgr_to_yuv, COLOR_YUV2BGR: _color.yuv_to_bgr, COLOR_BGR2XYZ: _color.bgr_to_xyz, COLOR_XYZ2BGR: _color.xyz_to_bgr,
+        COLOR_YCrCb2BGR: _color.ycrcb_to_bgr, COLOR_HLS2BGR: _color.hls_to_bgr}
+# the RGB-order, alpha and reorder codes have no name in utils/color.py: straight to their libvp codes
+_CVT.update({cv: _color._convert_colorspace(vp) for cv, vp in (
+    (COLOR_BGR2BGRA, _vp.BGR2BGRA), (COLOR_BGRA2BGR, _vp.BGRA2BGR), (COLOR_BGR2RGBA, _vp.BGR2RGBA), (COLOR_RGBA2BGR, _vp.RGBA2BGR),
+    (COLOR_BGR2RGB, _vp.BGR2RGB), (COLOR_BGRA2RGBA, _vp.BGRA2RGBA), (COLOR_RGB2GRAY, _vp.RGB2GRAY), (COLOR_GRAY2BGRA, _vp.GRAY2BGRA),
+    (COLOR_BGRA2GRAY, _vp.BGRA2GRAY), (COLOR_RGBA2GRAY, _vp.RGBA2GRAY), (COLOR_RGB2XYZ, _vp.RGB2XYZ), (COLOR_XYZ2RGB, _vp.XYZ2RGB),
+    (COLOR_RGB2YCrCb, _vp.RGB2YCRCB), (COLOR_YCrCb2RGB, _vp.YCRCB2RGB), (COLOR_RGB2HSV, _vp.RGB2HSV), (COLOR_HSV2RGB, _vp.HSV2RGB),
+    (COLOR_RGB2Lab, _vp.RGB2LAB), (COLOR_Lab2RGB, _vp.LAB2RGB), (COLOR_RGB2HLS, _vp.RGB2HLS), (COLOR_HLS2RGB, _vp.HLS2RGB),
+    (COLOR_RGB2YUV, _vp.RGB2YUV), (COLOR_YUV2RGB, _vp.YUV2RGB))})
 
 
 def cvtColor(src, code):

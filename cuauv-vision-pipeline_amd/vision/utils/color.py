@@ -19,8 +19,8 @@ def _u8_image(mat, channels):
     mat = to_host(as_mat(mat))
     if not isinstance(mat, np.ndarray) or mat.dtype != np.uint8:
         raise TypeError("expected a uint8 numpy image")
-    if channels == 3 and not (mat.ndim == 3 and mat.shape[2] == 3):
-        raise ValueError("expected an (h, w, 3) image")
+    if channels in (3, 4) and not (mat.ndim == 3 and mat.shape[2] == channels):
+        raise ValueError(f"expected an (h, w, {channels}) image")
     if channels == 1:
         if mat.ndim == 3 and mat.shape[2] == 1:
             mat = mat[:, :, 0]
@@ -36,18 +36,19 @@ def _u8_image(mat, channels):
 
 def _convert_colorspace(code: int) -> Callable[[np.ndarray], Tuple[np.ndarray, Tuple[np.ndarray, ...]]]:
     """utils/color.py:11-23: returns f(mat) -> (converted image, split channels)."""
-    scn = 1 if code == _vp.GRAY2BGR else 3
-    dcn = 1 if code == _vp.BGR2GRAY else 3
+    scn, dcn = _vp.CVT_CHANNELS.get(code, (3, 3))
     want_planes = code != _vp.HSV2BGR
 
     def _inner_device(mat):
         """The image stays in HBM: results are DeviceMat (vision/devmat.py), nothing is downloaded here."""
         ctx = _vp.default_context()
         up = []                                       # a host image is copied while the results are set up and the kernel is enqueued
-        src = device_image(ctx, mat, scn, pending=up)
+        src = device_image(ctx, mat, 0 if scn == 4 else scn, pending=up)
         try:
+            if scn == 4 and not (len(src.shape) == 3 and src.shape[2] == 4):
+                raise ValueError("expected an (h, w, 4) image")
             h, w = src.shape[:2]
-            conv = DeviceMat(ctx, (h, w) if dcn == 1 else (h, w, 3))
+            conv = DeviceMat(ctx, (h, w) if dcn == 1 else (h, w, dcn))
             planes = [DeviceMat(ctx, (h, w)) for _ in range(dcn)] if (dcn == 3 and want_planes) else []
             arr = (_vp.C.c_void_p * 3)(*[p.dev_ptr for p in planes], *([None] * (3 - len(planes))))
             _vp.check(_vp.lib().vp_cvt_color_dev(ctx.handle, code, src.dev_ptr, w * scn, w, h, conv.dev_ptr, arr if planes else None), ctx.handle)
@@ -56,6 +57,8 @@ def _convert_colorspace(code: int) -> Callable[[np.ndarray], Tuple[np.ndarray, T
                 return conv, tuple(np.ascontiguousarray(hc[:, :, c]) for c in range(3))
             if planes:
                 return conv, tuple(planes)
+            if dcn == 4:                                  # a 4-channel result comes without planes: cv2's split is a call of its own
+                return conv, ()
             second = DeviceMat(ctx, (h, w))               # cv2.split of a single-channel image: a 1-tuple holding a copy
             _vp.check(_vp.lib().vp_cvt_color_dev(ctx.handle, code, src.dev_ptr, w * scn, w, h, second.dev_ptr, None), ctx.handle)
             return conv, (second,)
@@ -68,7 +71,7 @@ def _convert_colorspace(code: int) -> Callable[[np.ndarray], Tuple[np.ndarray, T
             return _inner_device(mat)
         mat = _u8_image(mat, scn)
         h, w = mat.shape[:2]
-        conv = np.empty((h, w) if dcn == 1 else (h, w, 3), np.uint8)
+        conv = np.empty((h, w) if dcn == 1 else (h, w, dcn), np.uint8)
         planes = [np.empty((h, w), np.uint8) for _ in range(dcn)] if (dcn == 3 and want_planes) else []
         arr = (_vp.C.c_void_p * 3)(*[p.ctypes.data for p in planes], *([None] * (3 - len(planes))))
         ctx = _vp.default_context()
@@ -77,6 +80,8 @@ def _convert_colorspace(code: int) -> Callable[[np.ndarray], Tuple[np.ndarray, T
         # cv2.split of a single-channel image returns a 1-tuple holding a copy
         if not want_planes:
             return conv, tuple(np.ascontiguousarray(conv[:, :, c]) for c in range(3))
+        if dcn == 4:
+            return conv, ()
         return conv, (tuple(planes) if planes else (conv.copy(),))
     return _inner
 
@@ -96,6 +101,13 @@ bgr_to_ycrcb = _convert_colorspace(_vp.BGR2YCRCB)
 bgr_to_luv = _unsupported("bgr_to_luv")
 lab_to_bgr = _convert_colorspace(_vp.LAB2BGR)
 hsv_to_bgr = _convert_colorspace(_vp.HSV2BGR)
+# beyond the reference's name list (utils/color.py:26-28): the other conversions its modules ask cv2 for (vision_common.py:208-221)
+bgr_to_yuv = _convert_colorspace(_vp.BGR2YUV)
+yuv_to_bgr = _convert_colorspace(_vp.YUV2BGR)
+bgr_to_xyz = _convert_colorspace(_vp.BGR2XYZ)
+xyz_to_bgr = _convert_colorspace(_vp.XYZ2BGR)
+ycrcb_to_bgr = _convert_colorspace(_vp.YCRCB2BGR)
+hls_to_bgr = _convert_colorspace(_vp.HLS2BGR)
 
 
 def bgr_to_lab_f32(mat: np.ndarray):

@@ -33,7 +33,15 @@ extern "C" {
 typedef struct vp_ctx vp_ctx;
 
 /* colour conversion codes (values are libvp's own, not cv2's) */
-enum { VP_BGR2LAB = 0, VP_BGR2HSV = 1, VP_BGR2GRAY = 2, VP_GRAY2BGR = 3, VP_HSV2BGR = 4, VP_BGR2YCRCB = 5, VP_BGR2HLS = 6, VP_LAB2BGR = 7 };
+enum { VP_BGR2LAB = 0, VP_BGR2HSV = 1, VP_BGR2GRAY = 2, VP_GRAY2BGR = 3, VP_HSV2BGR = 4, VP_BGR2YCRCB = 5, VP_BGR2HLS = 6, VP_LAB2BGR = 7,
+       /* the rest of cv2.cvtColor's 8-bit table (vision_common.py:208-221, modules/color_balance.py:227-280, capture_sources/zed*.py) */
+       VP_BGR2YUV = 8, VP_YUV2BGR = 9, VP_YCRCB2BGR = 10, VP_BGR2XYZ = 11, VP_XYZ2BGR = 12, VP_HLS2BGR = 13,
+       /* RGB order: the same arithmetic with the first and third channel of the BGR side exchanged; VP_BGR2RGB is the plain exchange */
+       VP_BGR2RGB = 14, VP_RGB2GRAY = 15, VP_RGB2HSV = 16, VP_HSV2RGB = 17, VP_RGB2HLS = 18, VP_HLS2RGB = 19, VP_RGB2LAB = 20,
+       VP_LAB2RGB = 21, VP_RGB2YCRCB = 22, VP_YCRCB2RGB = 23, VP_RGB2YUV = 24, VP_YUV2RGB = 25, VP_RGB2XYZ = 26, VP_XYZ2RGB = 27,
+       /* alpha and reorders (4-channel images; a new alpha channel is 255) */
+       VP_BGRA2BGR = 28, VP_RGBA2BGR = 29, VP_BGR2BGRA = 30, VP_BGR2RGBA = 31, VP_BGRA2RGBA = 32, VP_GRAY2BGRA = 33, VP_BGRA2GRAY = 34,
+       VP_RGBA2GRAY = 35, VP_CVT_CODES = 36 };
 /* morphology ops — utils/transform.py:80-164 */
 enum { VP_MORPH_ERODE = 0, VP_MORPH_DILATE = 1, VP_MORPH_OPEN = 2, VP_MORPH_CLOSE = 3, VP_MORPH_GRADIENT = 4 };
 /* structuring element shapes — cv2.MORPH_RECT / MORPH_CROSS / MORPH_ELLIPSE */
@@ -106,7 +114,12 @@ int vp_get_lab_inv_tables(uint16_t* yf, int32_t* ab_xz, uint16_t* inv_gamma, int
  * bgr_to_gray, gray_to_bgr, bgr_to_ycrcb, bgr_to_hls (modules/preprocessor.py:66-75), plus HSV2BGR (color_balance.cpp:669).
  * YCrCb is OpenCV's Q14 integer form; HLS is the float32 statement sequence of RGB2HLS_f behind RGB2HLS_b.  src is (h,w,3) (or (h,w) for GRAY2BGR) with `src_stride` bytes per
  * row.  dst_interleaved (tightly packed, may be NULL) receives the converted image; dst_planes[k]
- * (each (h,w) tightly packed, each may be NULL, array may be NULL) receive the split channels. */
+ * (each (h,w) tightly packed, each may be NULL, array may be NULL) receive the split channels.
+ * The codes from VP_BGR2YUV on: the channel counts of src and dst_interleaved follow from the code (1, 3 or 4).  All arithmetic is
+ * OpenCV's 8-bit form, descale(x, n) = (x + (1 << (n - 1))) >> n, results saturated: YUV and YCrCb are RGB2YCrCb_i / YCrCb2RGB_i in
+ * Q14 (YUV stores Y, U, V), XYZ is RGB2XYZ_i / XYZ2RGB_i in Q12, HLS -> BGR the float32 statement sequence of HLS2RGB_f behind
+ * HLS2RGB_b (hue 0..180; DESIGN 4.16 holds every constant).  dst_planes of these codes: up to three planes for a 3-channel result;
+ * it must be NULL for a 1-channel or 4-channel result (VP_ERR_INVALID otherwise). */
 int vp_cvt_color_u8(vp_ctx* ctx, int code, const uint8_t* src_host, size_t src_stride, int w, int h,
                     uint8_t* dst_interleaved_host, uint8_t* const* dst_planes_host);
 /* VP_LAB2BGR (utils/color.py:26-32 `lab_to_bgr`, cv2.COLOR_LAB2BGR on 8-bit images) is OpenCV's integer path Lab2RGBinteger:
