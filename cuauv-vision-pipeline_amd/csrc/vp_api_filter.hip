@@ -1,0 +1,602 @@
+// C ABI of libvp.so, filters: thresholds, Otsu and histogram, blur, resize, warp, adaptive thresholds, Canny, Hough lines and
+// circles, letterbox, NMS and the element-wise operators (kernels: vp_filter / vp_adaptive / vp_hough* / vp_yolo / vp_elementwise).
+// Host forms stage their operands and synchronise; device forms take the image where the operator before them left it, copy nothing
+// and only enqueue (the histogram and the counters bring numbers back and synchronise for them).  Each host / device pair shares
+// one *_args check, which also normalises the parameters; what differs between the forms stays in the entry.
+#include "vp_api_util.h"
+
+extern "C" {
+
+// cv2.threshold on 8-bit images: the threshold floored into [-1, 256], maxval rounded into [0, 255]
+static int thresh_args(vp_ctx* ctx, const char* who, const void* src, const void* dst, size_t n, double thresh, double maxval, int type, int* ithresh,
+                       int* imaxval)
+{
+    if (!src || !dst || n == 0 || type < VP_THRESH_BINARY || type > VP_THRESH_TOZERO_INV || thresh != thresh || maxval != maxval)
+        return vp_fail(ctx, VP_ERR_INVALID, who);
+    const double ft = floor(thresh);
+    *ithresh = ft < -1 ? -1 : (ft > 256 ? 256 : (int)ft);
+    const double rm = nearbyint(maxval);
+    *imaxval = rm < 0 ? 0 : (rm > 255 ? 255 : (int)rm);
+    return VP_OK;
+}
+
+// Otsu: the same without a threshold of the caller's; the histogram counts in 32 bits
+static int otsu_args(vp_ctx* ctx, const char* who, const void* src, const void* dst, size_t n, double maxval, int type, int* imaxval)
+{
+    int ithresh;
+    if (n > 0xffffffffull) return vp_fail(ctx, VP_ERR_INVALID, who);
+    return thresh_args(ctx, who, src, dst, n, 0.0, maxval, type, &ithresh, imaxval);
+}
+
+int vp_threshold_u8(vp_ctx* ctx, const uint8_t* src, size_t n, double thresh, double maxval, int type, uint8_t* dst)
+{
+    VP_TRY(check_ctx(ctx));
+    int ithresh, imaxval;
+    VP_TRY(thresh_args(ctx, "vp_threshold_u8 arguments", src, dst, n, thresh, maxval, type, &ithresh, &imaxval));
+    VP_TRY(vp_ws_reserve(ctx, 2 * vp_align(n) + 1024));
+    TAKE(d_src, uint8_t*, n);
+    TAKE(d_dst, uint8_t*, n);
+    VP_TRY(h2d(ctx, d_src, src, n));
+    VP_TRY(vpk_threshold_u8(ctx, d_src, n, ithresh, imaxval, type, d_dst));
+    VP_TRY(d2h(ctx, dst, d_dst, n));
+    return vp_synchronize(ctx);
+}
+
+int vp_threshold_u8_dev(vp_ctx* ctx, const uint8_t* d_src, size_t n, double thresh, double maxval, int type, uint8_t* d_dst)
+{
+    VP_TRY(check_ctx(ctx));
+    int ithresh, imaxval;
+    VP_TRY(thresh_args(ctx, "vp_threshold_u8_dev arguments", d_src, d_dst, n, thresh, maxval, type, &ithresh, &imaxval));
+    if (dev_overlap(d_src, n, d_dst, n)) return vp_fail(ctx, VP_ERR_INVALID, "vp_threshold_u8_dev: dst overlaps src");
+    return vpk_threshold_u8(ctx, d_src, n, ithresh, imaxval, type, d_dst);
+}
+
+int vp_otsu_threshold_u8(vp_ctx* ctx, const uint8_t* src, size_t n, double maxval, int type, double* thresh_out, uint8_t* dst)
+{
+    VP_TRY(check_ctx(ctx));
+    int imaxval;
+    VP_TRY(otsu_args(ctx, "vp_otsu_threshold_u8 arguments", src, dst, n, maxval, type, &imaxval));
+    VP_TRY(vp_ws_reserve(ctx, 2 * vp_align(n) + 2048));
+    TAKE(d_src, uint8_t*, n);
+    TAKE(d_dst, uint8_t*, n);
+    TAKE(d_hist, u32*, 1024);
+    VP_TRY(h2d(ctx, d_src, src, n));
+    VP_TRY(vpk_hist_u8(ctx, d_src, n, d_hist));
+    u32 h[256];
+    VP_TRY(d2h(ctx, h, d_hist, 1024));
+    VP_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    // imgproc/src/thresh.cpp getThreshVal_Otsu_8u, statement by statement
+    const double scale = 1. / (double)n;
+    double mu = 0;
+    for (int i = 0; i < 256; i++) mu += i * (double)h[i];
+    mu *= scale;
+    double mu1 = 0, q1 = 0, max_sigma = 0, max_val = 0;
+    for (int i = 0; i < 256; i++) {
+        const double p_i = h[i] * scale;
+        mu1 *= q1;
+        q1 += p_i;
+        const double q2 = 1. - q1;
+        if (std::min(q1, q2) < 1.1920929e-07 || std::max(q1, q2) > 1. - 1.1920929e-07) continue;
+        mu1 = (mu1 + i * p_i) / q1;
+        const double mu2 = (mu - q1 * mu1) / q2;
+        const double sigma = q1 * q2 * (mu1 - mu2) * (mu1 - mu2);
+        if (sigma > max_sigma) { max_sigma = sigma; max_val = i; }
+    }
+    if (thresh_out) *thresh_out = max_val;
+    VP_TRY(vpk_threshold_u8(ctx, d_src, n, (int)max_val, imaxval, type, d_dst));
+    VP_TRY(d2h(ctx, dst, d_dst, n));
+    return vp_synchronize(ctx);
+}
+
+// histogram -> Otsu's scan by one wave -> threshold from the word the scan wrote: three launches, nothing comes back
+int vp_otsu_threshold_dev(vp_ctx* ctx, const uint8_t* d_src, size_t n, double maxval, int type, double* d_thresh, uint8_t* d_dst)
+{
+    VP_TRY(check_ctx(ctx));
+    int imaxval;
+    VP_TRY(otsu_args(ctx, "vp_otsu_threshold_dev arguments", d_src, d_dst, n, maxval, type, &imaxval));
+    if (dev_overlap(d_src, n, d_dst, n)) return vp_fail(ctx, VP_ERR_INVALID, "vp_otsu_threshold_dev: dst overlaps src");
+    VP_TRY(vp_ws_reserve(ctx, 4096));
+    TAKE(d_hist, u32*, 1024);
+    TAKE(d_it, int32_t*, 4);
+    VP_TRY(vpk_hist_u8(ctx, d_src, n, d_hist));
+    VP_TRY(vpk_otsu_scan(ctx, d_hist, n, d_thresh, d_it));
+    return vpk_threshold_u8(ctx, d_src, n, 0, imaxval, type, d_dst, d_it);
+}
+
+int vp_hist_u8_dev(vp_ctx* ctx, const uint8_t* d_src, size_t n, uint32_t* hist)
+{
+    VP_TRY(check_ctx(ctx));
+    if (!d_src || !hist || n == 0 || n > 0xffffffffull) return vp_fail(ctx, VP_ERR_INVALID, "vp_hist_u8_dev arguments");
+    VP_TRY(vp_ws_reserve(ctx, 4096));
+    TAKE(d_hist, u32*, 1024);
+    VP_TRY(vpk_hist_u8(ctx, d_src, n, d_hist));
+    VP_TRY(d2h(ctx, hist, d_hist, 1024));
+    return vp_synchronize(ctx);
+}
+
+// VP_OPT_BLUR_ONEPASS left at its default: the one-pass kernel serves the classes in which it measured faster than the two passes
+// on the MI355X by more than the box-to-box spread (tools/exp_dev_ops.py --part blur): three channels, kernels
+// up to 21 (1080p: 27 % faster at 3, 9 % at 15, 5 % at 21; 12 % slower at 31).  One channel gains 4 % at 3 and loses from 7 on, and
+// two and four channels were not measured: they stay on the two passes.
+#define BLUR_ONEPASS_MAX_K 21
+static bool blur_onepass_measured_faster(int cn, int kw, int kh) { return cn == 3 && kw <= BLUR_ONEPASS_MAX_K && kh <= BLUR_ONEPASS_MAX_K; }
+
+// cv2.GaussianBlur: odd kernels up to 511; a negative sigma counts as 0 (from the kernel size), sigma2 <= 0 takes sigma1
+static int blur_args(vp_ctx* ctx, const char* who, const void* src, const void* dst, int w, int h, int cn, int kw, int kh, double* sigma1, double* sigma2)
+{
+    if (!src || !dst || w <= 0 || h <= 0 || h > 65535 || cn < 1 || cn > 4 || kw <= 0 || kh <= 0 || !(kw & 1) || !(kh & 1) || kw > 511 || kh > 511)
+        return vp_fail(ctx, VP_ERR_INVALID, who);
+    if (*sigma1 < 0) *sigma1 = 0;
+    if (*sigma2 <= 0) *sigma2 = *sigma1;
+    return VP_OK;
+}
+
+int vp_gaussian_blur_u8(vp_ctx* ctx, const uint8_t* src, int w, int h, int cn, int kw, int kh, double sigma1, double sigma2, uint8_t* dst)
+{
+    VP_TRY(check_ctx(ctx));
+    VP_TRY(blur_args(ctx, "vp_gaussian_blur_u8 arguments", src, dst, w, h, cn, kw, kh, &sigma1, &sigma2));
+    const size_t nbytes = (size_t)w * h * cn;
+    uint16_t taps[1024];
+    vp_gaussian_taps(kw, sigma1, taps);
+    vp_gaussian_taps(kh, sigma2, taps + kw);
+    VP_TRY(vp_ws_reserve(ctx, 2 * vp_align(nbytes) + vp_align(nbytes * 2) + 4096));
+    TAKE(d_src, uint8_t*, nbytes);
+    TAKE(d_dst, uint8_t*, nbytes);
+    TAKE(d_tmp, uint16_t*, nbytes * 2);
+    TAKE(d_taps, uint16_t*, 2048);
+    VP_TRY(h2d(ctx, d_src, src, nbytes));
+    VP_TRY(h2d(ctx, d_taps, taps, (size_t)(kw + kh) * 2));
+    VP_HIP(ctx, hipStreamSynchronize(ctx->stream));   // taps is a local array
+    if (kw == 1 && kh == 1) { VP_TRY(d2h(ctx, dst, d_src, nbytes)); return vp_synchronize(ctx); }
+    VP_TRY(vpk_gaussian_blur(ctx, d_src, w, h, cn, d_taps, kw, kh, d_tmp, d_dst));
+    VP_TRY(d2h(ctx, dst, d_dst, nbytes));
+    return vp_synchronize(ctx);
+}
+
+int vp_gaussian_blur_dev(vp_ctx* ctx, const uint8_t* d_src, size_t src_stride, int w, int h, int cn, int kw, int kh, double sigma1, double sigma2,
+                         uint8_t* d_dst)
+{
+    VP_TRY(check_ctx(ctx));
+    VP_TRY(blur_args(ctx, "vp_gaussian_blur_dev arguments", d_src, d_dst, w, h, cn, kw, kh, &sigma1, &sigma2));
+    const size_t rowbytes = (size_t)w * cn, nbytes = rowbytes * h;
+    if (src_stride < rowbytes || dev_overlap(d_src, strided_bytes(src_stride, rowbytes, h), d_dst, nbytes))
+        return vp_fail(ctx, VP_ERR_INVALID, "vp_gaussian_blur_dev: src_stride, or dst overlaps src");
+    if (kw == 1 && kh == 1) {
+        VP_HIP(ctx, hipMemcpy2DAsync(d_dst, rowbytes, d_src, src_stride, rowbytes, h, hipMemcpyDeviceToDevice, ctx->stream));
+        return VP_OK;
+    }
+    const bool one = vp_gaussian_onepass_fits(kw, kh) && (ctx->blur_onepass == 1 || (ctx->blur_onepass < 0 && blur_onepass_measured_faster(cn, kw, kh)));
+    VP_TRY(vp_ws_reserve(ctx, (one ? 0 : vp_align(nbytes * 2)) + 4096));
+    TAKE(d_taps, uint16_t*, 2048);
+    // the taps go over in a pinned chunk of the context's ring: the copy is enqueued, nothing waits for it
+    int slot = -1;
+    uint16_t* taps = reinterpret_cast<uint16_t*>(vp_ring_take(ctx, 2048, &slot));
+    if (!taps) return vp_fail(ctx, VP_ERR_NOMEM, "pinned staging");
+    vp_gaussian_taps(kw, sigma1, taps);
+    vp_gaussian_taps(kh, sigma2, taps + kw);
+    int rc = h2d(ctx, d_taps, taps, (size_t)(kw + kh) * 2);
+    if (rc == VP_OK) {
+        if (one) rc = vpk_gaussian_blur_onepass(ctx, d_src, src_stride, w, h, cn, d_taps, kw, kh, d_dst);
+        else {
+            uint16_t* d_tmp = (uint16_t*)vp_ws_take(ctx, nbytes * 2);
+            rc = d_tmp ? vpk_gaussian_blur(ctx, d_src, w, h, cn, d_taps, kw, kh, d_tmp, d_dst, src_stride) : vp_fail(ctx, VP_ERR_NOMEM, "workspace exhausted: d_tmp");
+        }
+    }
+    vp_ring_done(ctx, slot);
+    return rc;
+}
+
+static int resize_args(vp_ctx* ctx, const char* who, const void* src, const void* dst, int w, int h, int cn, int dw, int dh, double inv_sx, double inv_sy)
+{
+    if (!src || !dst || w <= 0 || h <= 0 || dw <= 0 || dh <= 0 || dh > 65535 || cn < 1 || cn > 4 || !std::isfinite(inv_sx) || !std::isfinite(inv_sy) ||
+        !(inv_sx > 0) || !(inv_sy > 0))
+        return vp_fail(ctx, VP_ERR_INVALID, who);
+    return VP_OK;
+}
+
+int vp_resize_u8_scaled(vp_ctx* ctx, const uint8_t* src, int w, int h, int cn, int dw, int dh, double inv_sx, double inv_sy, uint8_t* dst)
+{
+    VP_TRY(check_ctx(ctx));
+    VP_TRY(resize_args(ctx, "vp_resize_u8 arguments", src, dst, w, h, cn, dw, dh, inv_sx, inv_sy));
+    const size_t sbytes = (size_t)w * h * cn, dbytes = (size_t)dw * dh * cn;
+    VP_TRY(vp_ws_reserve(ctx, vp_align(sbytes) + vp_align(dbytes) + 1024));
+    TAKE(d_src, uint8_t*, sbytes);
+    TAKE(d_dst, uint8_t*, dbytes);
+    VP_TRY(h2d(ctx, d_src, src, sbytes));
+    VP_TRY(vpk_resize_u8(ctx, d_src, w, h, cn, dw, dh, inv_sx, inv_sy, d_dst));
+    VP_TRY(d2h(ctx, dst, d_dst, dbytes));
+    return vp_synchronize(ctx);
+}
+
+int vp_resize_u8(vp_ctx* ctx, const uint8_t* src, int w, int h, int cn, int dw, int dh, uint8_t* dst)
+{
+    // cv::resize with a dsize: inv_scale = (double)dsize / ssize (an empty source is rejected by the scaled entry)
+    return vp_resize_u8_scaled(ctx, src, w, h, cn, dw, dh, w > 0 ? (double)dw / w : 0.0, h > 0 ? (double)dh / h : 0.0, dst);
+}
+
+int vp_resize_dev(vp_ctx* ctx, const uint8_t* d_src, size_t src_stride, int w, int h, int cn, int dw, int dh, double inv_sx, double inv_sy, uint8_t* d_dst)
+{
+    VP_TRY(check_ctx(ctx));
+    if (inv_sx <= 0 && inv_sy <= 0) {                    // cv::resize with a dsize: inv_scale = (double)dsize / ssize
+        inv_sx = w > 0 ? (double)dw / w : 0.0;
+        inv_sy = h > 0 ? (double)dh / h : 0.0;
+    }
+    VP_TRY(resize_args(ctx, "vp_resize_dev arguments", d_src, d_dst, w, h, cn, dw, dh, inv_sx, inv_sy));
+    const size_t rowbytes = (size_t)w * cn;
+    if (src_stride < rowbytes || dev_overlap(d_src, strided_bytes(src_stride, rowbytes, h), d_dst, (size_t)dw * dh * cn))
+        return vp_fail(ctx, VP_ERR_INVALID, "vp_resize_dev: src_stride, or dst overlaps src");
+    return vpk_resize_u8(ctx, d_src, w, h, cn, dw, dh, inv_sx, inv_sy, d_dst, src_stride);
+}
+
+static int warp_args(vp_ctx* ctx, const char* who, const void* src, const void* dst, int w, int h, int cn, const double* m23, int flags, int border_mode,
+                     int dw, int dh)
+{
+    if (!src || !dst || !m23 || w <= 0 || h <= 0 || dw <= 0 || dh <= 0 || dh > 65535 || cn < 1 || cn > 4 || (flags & ~VP_WARP_INVERSE_MAP) ||
+        (border_mode != VP_BORDER_CONSTANT && border_mode != VP_BORDER_REPLICATE))
+        return vp_fail(ctx, VP_ERR_INVALID, who);
+    for (int i = 0; i < 6; i++)
+        if (!std::isfinite(m23[i])) return vp_fail(ctx, VP_ERR_INVALID, "warp affine: matrix is not finite");
+    return VP_OK;
+}
+
+int vp_warp_affine_u8(vp_ctx* ctx, const uint8_t* src, int w, int h, int cn, const double* m23, int flags, int border_mode,
+                      const uint8_t* border_value, uint8_t* dst, int dw, int dh)
+{
+    VP_TRY(check_ctx(ctx));
+    VP_TRY(warp_args(ctx, "vp_warp_affine_u8 arguments", src, dst, w, h, cn, m23, flags, border_mode, dw, dh));
+    const size_t sbytes = (size_t)w * h * cn, dbytes = (size_t)dw * dh * cn;
+    VP_TRY(vp_ws_reserve(ctx, vp_align(sbytes) + vp_align(dbytes) + 1024));
+    TAKE(d_src, uint8_t*, sbytes);
+    TAKE(d_dst, uint8_t*, dbytes);
+    VP_TRY(h2d(ctx, d_src, src, sbytes));
+    VP_TRY(vpk_warp_affine_u8(ctx, d_src, w, h, cn, m23, (flags & VP_WARP_INVERSE_MAP) != 0, border_mode, border_value, d_dst, dw, dh));
+    VP_TRY(d2h(ctx, dst, d_dst, dbytes));
+    return vp_synchronize(ctx);
+}
+
+int vp_warp_affine_dev(vp_ctx* ctx, const uint8_t* d_src, size_t src_stride, int w, int h, int cn, const double* m23, int flags, int border_mode,
+                       const uint8_t* border_value, uint8_t* d_dst, int dw, int dh)
+{
+    VP_TRY(check_ctx(ctx));
+    VP_TRY(warp_args(ctx, "vp_warp_affine_dev arguments", d_src, d_dst, w, h, cn, m23, flags, border_mode, dw, dh));
+    const size_t rowbytes = (size_t)w * cn;
+    if (src_stride < rowbytes || dev_overlap(d_src, strided_bytes(src_stride, rowbytes, h), d_dst, (size_t)dw * dh * cn))
+        return vp_fail(ctx, VP_ERR_INVALID, "vp_warp_affine_dev: src_stride, or dst overlaps src");
+    // the matrix and the border value travel as kernel arguments
+    return vpk_warp_affine_u8(ctx, d_src, w, h, cn, m23, (flags & VP_WARP_INVERSE_MAP) != 0, border_mode, border_value, d_dst, dw, dh, src_stride);
+}
+
+// cv2.adaptiveThreshold, mean (blocks up to 151) and Gaussian (up to VP_AGAUSS_MAX_BLOCK): maxValue rounded into [0, 255], C rounded
+// away from the comparison (cv2's ceil for BINARY, floor for BINARY_INV)
+static int adaptive_args(vp_ctx* ctx, const char* who, const void* src, const void* dst, int w, int h, double max_value, int type, int block, int max_block,
+                         double c, int* imax, int* idelta)
+{
+    if (!src || !dst || w <= 0 || h <= 0 || h > 65535 || (type != VP_THRESH_BINARY && type != VP_THRESH_BINARY_INV) || !std::isfinite(max_value) ||
+        !std::isfinite(c) || std::fabs(c) > 1e6)
+        return vp_fail(ctx, VP_ERR_INVALID, who);
+    if (block < 3 || (block & 1) == 0) return vp_fail(ctx, VP_ERR_INVALID, "adaptive threshold: block size must be odd and > 1");
+    if (block > max_block) return vp_fail(ctx, VP_ERR_UNSUPPORTED, "adaptive threshold: block size above 151 (mean) / 511 (Gaussian)");
+    *imax = (int)std::min(255.0, std::max(0.0, std::nearbyint(max_value)));
+    *idelta = type == VP_THRESH_BINARY ? (int)std::ceil(c) : (int)std::floor(c);
+    return VP_OK;
+}
+
+int vp_adaptive_threshold_mean_u8(vp_ctx* ctx, const uint8_t* src, int w, int h, double max_value, int type, int block, double c, uint8_t* dst)
+{
+    VP_TRY(check_ctx(ctx));
+    int imax, idelta;
+    VP_TRY(adaptive_args(ctx, "vp_adaptive_threshold_mean_u8 arguments", src, dst, w, h, max_value, type, block, 151, c, &imax, &idelta));
+    const size_t npx = (size_t)w * h;
+    if (max_value < 0) { memset(dst, 0, npx); return VP_OK; }
+    VP_TRY(vp_ws_reserve(ctx, 2 * vp_align(npx) + vp_align(npx * 2) + 1024));
+    TAKE(d_src, uint8_t*, npx);
+    TAKE(d_dst, uint8_t*, npx);
+    TAKE(d_tmp, uint16_t*, npx * 2);
+    VP_TRY(h2d(ctx, d_src, src, npx));
+    VP_TRY(vpk_adaptive_threshold_mean(ctx, d_src, w, h, imax, idelta, type == VP_THRESH_BINARY_INV, block, d_tmp, d_dst));
+    VP_TRY(d2h(ctx, dst, d_dst, npx));
+    return vp_synchronize(ctx);
+}
+
+int vp_adaptive_threshold_mean_dev(vp_ctx* ctx, const uint8_t* d_src, size_t src_stride, int w, int h, double max_value, int type, int block, double c,
+                                   uint8_t* d_dst)
+{
+    VP_TRY(check_ctx(ctx));
+    int imax, idelta;
+    VP_TRY(adaptive_args(ctx, "vp_adaptive_threshold_mean_dev arguments", d_src, d_dst, w, h, max_value, type, block, 151, c, &imax, &idelta));
+    const size_t npx = (size_t)w * h;
+    if (src_stride < (size_t)w || dev_overlap(d_src, strided_bytes(src_stride, (size_t)w, h), d_dst, npx))
+        return vp_fail(ctx, VP_ERR_INVALID, "vp_adaptive_threshold_mean_dev: src_stride, or dst overlaps src");
+    if (max_value < 0) {
+        VP_HIP(ctx, hipMemsetAsync(d_dst, 0, npx, ctx->stream));
+        return VP_OK;
+    }
+    VP_TRY(vp_ws_reserve(ctx, vp_align(npx * 2) + 1024));
+    TAKE(d_tmp, uint16_t*, npx * 2);
+    return vpk_adaptive_threshold_mean(ctx, d_src, w, h, imax, idelta, type == VP_THRESH_BINARY_INV, block, d_tmp, d_dst, src_stride);
+}
+
+// n frames in HBM -> packed (n, h, w) dst in HBM, enqueued on the context's stream; max_value < 0 gives zeros, as cv2 does
+static int agauss_run(vp_ctx* ctx, const uint8_t* d_src, size_t stride, size_t fstride, int n, int w, int h, double max_value, int imax, int idelta, int inv,
+                      int block, uint8_t* d_dst)
+{
+    if (max_value < 0) {
+        VP_HIP(ctx, hipMemsetAsync(d_dst, 0, (size_t)n * w * h, ctx->stream));
+        return VP_OK;
+    }
+    TAKE(d_tmp, uint64_t*, vp_agauss_ws_bytes(w, h, n));
+    return vpk_adaptive_threshold_gaussian(ctx, d_src, stride, fstride, n, w, h, imax, idelta, inv, block, d_tmp, d_dst);
+}
+
+int vp_adaptive_threshold_gaussian_u8(vp_ctx* ctx, const uint8_t* src, int w, int h, double max_value, int type, int block, double c, uint8_t* dst)
+{
+    VP_TRY(check_ctx(ctx));
+    int imax, idelta;
+    VP_TRY(adaptive_args(ctx, "vp_adaptive_threshold_gaussian arguments", src, dst, w, h, max_value, type, block, VP_AGAUSS_MAX_BLOCK, c, &imax, &idelta));
+    const size_t npx = (size_t)w * h;
+    if (max_value < 0) { memset(dst, 0, npx); return VP_OK; }
+    VP_TRY(vp_ws_reserve(ctx, 2 * vp_align(npx) + vp_agauss_ws_bytes(w, h, 1) + 1024));
+    TAKE(d_src, uint8_t*, npx);
+    TAKE(d_dst, uint8_t*, npx);
+    VP_TRY(h2d(ctx, d_src, src, npx));
+    VP_TRY(agauss_run(ctx, d_src, (size_t)w, npx, 1, w, h, max_value, imax, idelta, type == VP_THRESH_BINARY_INV, block, d_dst));
+    VP_TRY(d2h(ctx, dst, d_dst, npx));
+    return vp_synchronize(ctx);
+}
+
+int vp_adaptive_threshold_gaussian_dev(vp_ctx* ctx, const uint8_t* d_src, size_t src_stride, int w, int h, double max_value, int type, int block,
+                                       double c, uint8_t* d_dst)
+{
+    VP_TRY(check_ctx(ctx));
+    int imax, idelta;
+    VP_TRY(adaptive_args(ctx, "vp_adaptive_threshold_gaussian arguments", d_src, d_dst, w, h, max_value, type, block, VP_AGAUSS_MAX_BLOCK, c, &imax, &idelta));
+    if (src_stride < (size_t)w) return vp_fail(ctx, VP_ERR_INVALID, "vp_adaptive_threshold_gaussian_dev src_stride");
+    VP_TRY(vp_ws_reserve(ctx, vp_agauss_ws_bytes(w, h, 1) + 1024));
+    return agauss_run(ctx, d_src, src_stride, src_stride * h, 1, w, h, max_value, imax, idelta, type == VP_THRESH_BINARY_INV, block, d_dst);
+}
+
+int vp_adaptive_threshold_gaussian_batch_dev(vp_ctx* ctx, const uint8_t* d_src, size_t src_stride, size_t frame_stride, int n, int w, int h,
+                                             double max_value, int type, int block, double c, uint8_t* d_dst)
+{
+    VP_TRY(check_ctx(ctx));
+    int imax, idelta;
+    VP_TRY(adaptive_args(ctx, "vp_adaptive_threshold_gaussian arguments", d_src, d_dst, w, h, max_value, type, block, VP_AGAUSS_MAX_BLOCK, c, &imax, &idelta));
+    if (n <= 0 || n > 65535 || src_stride < (size_t)w || (n > 1 && frame_stride < src_stride * h))
+        return vp_fail(ctx, VP_ERR_INVALID, "vp_adaptive_threshold_gaussian_batch_dev strides / frame count");
+    VP_TRY(vp_ws_reserve(ctx, vp_agauss_ws_bytes(w, h, n) + 1024));
+    return agauss_run(ctx, d_src, src_stride, frame_stride, n, w, h, max_value, imax, idelta, type == VP_THRESH_BINARY_INV, block, d_dst);
+}
+
+// cv2.Canny thresholds: ordered, floored, held inside what the integer gradient magnitude can reach
+static int canny_args(vp_ctx* ctx, const char* who, const void* src, const void* dst, int w, int h, int cn, double t1, double t2, int* low, int* high)
+{
+    if (!src || !dst || w <= 0 || h <= 0 || h > 65535 || (size_t)w * h > ((size_t)1 << 30) || cn < 1 || cn > 4 || !std::isfinite(t1) || !std::isfinite(t2))
+        return vp_fail(ctx, VP_ERR_INVALID, who);
+    if (t1 > t2) std::swap(t1, t2);
+    *low = (int)std::floor(std::min(std::max(t1, -1.0), 1e9));
+    *high = (int)std::floor(std::min(std::max(t2, -1.0), 1e9));
+    return VP_OK;
+}
+
+int vp_canny_u8(vp_ctx* ctx, const uint8_t* src, int w, int h, int cn, double t1, double t2, uint8_t* dst)
+{
+    VP_TRY(check_ctx(ctx));
+    int low, high;
+    VP_TRY(canny_args(ctx, "vp_canny_u8 arguments", src, dst, w, h, cn, t1, t2, &low, &high));
+    const size_t npx = (size_t)w * h;
+    VP_TRY(vp_ws_reserve(ctx, vp_align(npx * cn) + vp_align(npx) + vp_canny_ws_bytes(w, h) + 1024));
+    TAKE(d_src, uint8_t*, npx * cn);
+    TAKE(d_dst, uint8_t*, npx);
+    VP_TRY(h2d(ctx, d_src, src, npx * cn));
+    VP_TRY(vpk_canny_u8(ctx, d_src, w, h, cn, low, high, d_dst));
+    VP_TRY(d2h(ctx, dst, d_dst, npx));
+    return vp_synchronize(ctx);
+}
+
+// canny -> find_lines without leaving HBM: the same kernels as vp_canny_u8 on a device image; enqueued, not synchronised
+int vp_canny_u8_dev(vp_ctx* ctx, const uint8_t* d_src, size_t src_stride, int w, int h, int cn, double t1, double t2, uint8_t* d_dst)
+{
+    VP_TRY(check_ctx(ctx));
+    int low, high;
+    VP_TRY(canny_args(ctx, "vp_canny_u8_dev arguments", d_src, d_dst, w, h, cn, t1, t2, &low, &high));
+    if (src_stride < (size_t)w * cn) return vp_fail(ctx, VP_ERR_INVALID, "vp_canny_u8_dev src_stride");
+    const size_t npx = (size_t)w * h;
+    const bool packed = src_stride == (size_t)w * cn;
+    VP_TRY(vp_ws_reserve(ctx, (packed ? 0 : vp_align(npx * cn)) + vp_canny_ws_bytes(w, h) + 1024));
+    const uint8_t* src = d_src;
+    if (!packed) {
+        TAKE(d_pk, uint8_t*, npx * cn);
+        VP_HIP(ctx, hipMemcpy2DAsync(d_pk, (size_t)w * cn, d_src, src_stride, (size_t)w * cn, h, hipMemcpyDeviceToDevice, ctx->stream));
+        src = d_pk;
+    }
+    return vpk_canny_u8(ctx, src, w, h, cn, low, high, d_dst);
+}
+
+static int hough_args(vp_ctx* ctx, const void* src, int w, int h, float* lines, int max_lines, int* n_lines)
+{
+    if (!src || !n_lines || w <= 0 || h <= 0 || w > 65535 || h > 65535 || max_lines < 0 || (max_lines > 0 && !lines))
+        return vp_fail(ctx, VP_ERR_INVALID, "hough lines arguments");
+    return VP_OK;
+}
+
+int vp_hough_lines_u8(vp_ctx* ctx, const uint8_t* src, int w, int h, double rho, double theta, int threshold, double min_theta, double max_theta,
+                      float* lines, int max_lines, int* n_lines)
+{
+    VP_TRY(check_ctx(ctx));
+    VP_TRY(hough_args(ctx, src, w, h, lines, max_lines, n_lines));
+    return vp_hough_run(ctx, nullptr, src, w, (size_t)w * h, 1, w, h, rho, theta, threshold, min_theta, max_theta, lines, max_lines, n_lines);
+}
+
+int vp_hough_lines_dev(vp_ctx* ctx, const uint8_t* d_src, size_t src_stride, int w, int h, double rho, double theta, int threshold,
+                       double min_theta, double max_theta, float* lines, int max_lines, int* n_lines)
+{
+    VP_TRY(check_ctx(ctx));
+    VP_TRY(hough_args(ctx, d_src, w, h, lines, max_lines, n_lines));
+    if (src_stride < (size_t)w) return vp_fail(ctx, VP_ERR_INVALID, "src_stride");
+    return vp_hough_run(ctx, d_src, nullptr, src_stride, src_stride * h, 1, w, h, rho, theta, threshold, min_theta, max_theta, lines, max_lines, n_lines);
+}
+
+int vp_hough_lines_batch_dev(vp_ctx* ctx, const uint8_t* d_src, size_t src_stride, size_t frame_stride, int n, int w, int h, double rho,
+                             double theta, int threshold, double min_theta, double max_theta, float* lines, int max_lines, int* n_lines)
+{
+    VP_TRY(check_ctx(ctx));
+    VP_TRY(hough_args(ctx, d_src, w, h, lines, max_lines, n_lines));
+    if (n <= 0 || n > 65535 || src_stride < (size_t)w || (n > 1 && frame_stride < src_stride * (h - 1) + w))
+        return vp_fail(ctx, VP_ERR_INVALID, "vp_hough_lines_batch_dev strides / frame count");
+    return vp_hough_run(ctx, d_src, nullptr, src_stride, frame_stride, n, w, h, rho, theta, threshold, min_theta, max_theta, lines, max_lines, n_lines);
+}
+
+int vp_hough_circles_u8(vp_ctx* ctx, const uint8_t* src, int w, int h, double dp, double min_dist, double param1, double param2, int min_radius,
+                        int max_radius, float* circles, int max_circles, int* n_circles)
+{
+    VP_TRY(check_ctx(ctx));
+    if (!src) return vp_fail(ctx, VP_ERR_INVALID, "hough circles arguments");
+    return vp_hough_circles_run(ctx, nullptr, src, (size_t)w, w, h, dp, min_dist, param1, param2, min_radius, max_radius, circles, max_circles,
+                                n_circles);
+}
+
+int vp_hough_circles_dev(vp_ctx* ctx, const uint8_t* d_src, size_t src_stride, int w, int h, double dp, double min_dist, double param1,
+                         double param2, int min_radius, int max_radius, float* circles, int max_circles, int* n_circles)
+{
+    VP_TRY(check_ctx(ctx));
+    if (!d_src) return vp_fail(ctx, VP_ERR_INVALID, "hough circles arguments");
+    return vp_hough_circles_run(ctx, d_src, nullptr, src_stride, w, h, dp, min_dist, param1, param2, min_radius, max_radius, circles,
+                                max_circles, n_circles);
+}
+
+static int check_lb(vp_ctx* ctx, const void* src, const void* dst, int w, int h, int dw, int dh, int pad)
+{
+    if (!src || !dst || w <= 0 || h <= 0 || dw <= 0 || dh <= 0 || dh > 65535 || pad < 0 || pad > 255) return vp_fail(ctx, VP_ERR_INVALID, "letterbox arguments");
+    return VP_OK;
+}
+
+int vp_letterbox_u8_f32(vp_ctx* ctx, const uint8_t* src, int w, int h, int dw, int dh, int pad, float* dst, float* geom_out)
+{
+    VP_TRY(check_ctx(ctx));
+    VP_TRY(check_lb(ctx, src, dst, w, h, dw, dh, pad));
+    const size_t sbytes = (size_t)w * h * 3, dbytes = (size_t)dw * dh * 12;
+    VP_TRY(vp_ws_reserve(ctx, vp_align(sbytes) + vp_align(dbytes) + 1024));
+    TAKE(d_src, uint8_t*, sbytes);
+    TAKE(d_dst, float*, dbytes);
+    VP_TRY(h2d(ctx, d_src, src, sbytes));
+    VP_TRY(vpk_letterbox(ctx, d_src, w, h, dw, dh, pad, d_dst, geom_out));
+    VP_TRY(d2h(ctx, dst, d_dst, dbytes));
+    return vp_synchronize(ctx);
+}
+
+int vp_letterbox_dev(vp_ctx* ctx, const uint8_t* src, int w, int h, int dw, int dh, int pad, float* dst, float* geom_out)
+{
+    VP_TRY(check_ctx(ctx));
+    VP_TRY(check_lb(ctx, src, dst, w, h, dw, dh, pad));
+    return vpk_letterbox(ctx, src, w, h, dw, dh, pad, dst, geom_out);
+}
+
+int vp_nms_f32(vp_ctx* ctx, const float* boxes, const float* scores, int n, float thr, int rotated, int max_keep, int32_t* keep_out,
+               int32_t* n_keep_out)
+{
+    VP_TRY(check_ctx(ctx));
+    if (n < 0 || max_keep < 0 || !n_keep_out || (n > 0 && (!boxes || !scores)) || (max_keep > 0 && !keep_out))
+        return vp_fail(ctx, VP_ERR_INVALID, "vp_nms_f32 arguments");
+    *n_keep_out = 0;
+    if (n == 0 || max_keep == 0) return VP_OK;
+    const int bs = rotated ? 5 : 4;
+    VP_TRY(vp_ws_reserve(ctx, vp_align((size_t)n * bs * 4) + vp_align((size_t)n * 4) + vp_align((size_t)max_keep * 4) + vp_nms_ws_bytes(n) + 2048));
+    TAKE(d_boxes, float*, (size_t)n * bs * 4);
+    TAKE(d_scores, float*, (size_t)n * 4);
+    TAKE(d_keep, int*, (size_t)max_keep * 4);
+    TAKE(d_nk, int*, 4);
+    VP_TRY(h2d(ctx, d_boxes, boxes, (size_t)n * bs * 4));
+    VP_TRY(h2d(ctx, d_scores, scores, (size_t)n * 4));
+    VP_TRY(vpk_nms(ctx, d_boxes, d_scores, n, thr, rotated ? 1 : 0, max_keep, d_keep, d_nk));
+    VP_TRY(d2h(ctx, n_keep_out, d_nk, 4));
+    VP_TRY(vp_synchronize(ctx));
+    if (*n_keep_out > 0) { VP_TRY(d2h(ctx, keep_out, d_keep, (size_t)*n_keep_out * 4)); VP_TRY(vp_synchronize(ctx)); }
+    return VP_OK;
+}
+
+int vp_nms_dev(vp_ctx* ctx, const float* boxes, const float* scores, int n, float thr, int rotated, int max_keep, int32_t* keep_out,
+               int32_t* n_keep)
+{
+    VP_TRY(check_ctx(ctx));
+    if (n < 0 || max_keep <= 0 || !n_keep || !keep_out || (n > 0 && (!boxes || !scores))) return vp_fail(ctx, VP_ERR_INVALID, "vp_nms_dev arguments");
+    VP_TRY(vp_ws_reserve(ctx, vp_nms_ws_bytes(n > 0 ? n : 1) + 2048));
+    return vpk_nms(ctx, boxes, scores, n, thr, rotated ? 1 : 0, max_keep, keep_out, n_keep);
+}
+
+// ---- element-wise operators on device images (kernels: vp_elementwise.hip) ----------------------------------------------------------
+#define VP_EW_MAX ((size_t)1 << 40)
+// dst is a source itself or apart from it
+static bool ew_dst_ok(const void* src, const void* dst, size_t n) { return !src || src == dst || !dev_overlap(src, n, dst, n); }
+
+int vp_bitwise_u8_dev(vp_ctx* ctx, int op, const uint8_t* d_a, const uint8_t* d_b, int scalar, const uint8_t* d_mask, int cn, size_t n, uint8_t* d_dst, int bits_w,
+                      unsigned long long* d_bits, int* made_bits)
+{
+    VP_TRY(check_ctx(ctx));
+    if (made_bits) *made_bits = 0;
+    if (op < VP_BITWISE_AND || op > VP_BITWISE_NOT || !d_a || !d_dst || n == 0 || n > VP_EW_MAX || cn < 1 || cn > 4 || n % (size_t)cn != 0 ||
+        (op != VP_BITWISE_NOT && !d_b && (scalar < 0 || scalar > 255)) || bits_w < 0 || (d_bits && bits_w > 0 && (cn != 1 || n % (size_t)bits_w != 0)))
+        return vp_fail(ctx, VP_ERR_INVALID, "vp_bitwise_u8_dev arguments");
+    if (op == VP_BITWISE_NOT) d_b = nullptr;
+    if (!ew_dst_ok(d_a, d_dst, n) || !ew_dst_ok(d_b, d_dst, n) || (d_mask && dev_overlap(d_mask, n / cn, d_dst, n)) ||
+        (d_bits && bits_w > 0 && (dev_overlap(d_bits, (n + 7) / 8, d_dst, n) || dev_overlap(d_bits, (n + 7) / 8, d_a, n) || (d_b && dev_overlap(d_bits, (n + 7) / 8, d_b, n)))))
+        return vp_fail(ctx, VP_ERR_INVALID, "vp_bitwise_u8_dev: dst overlaps a source partly, or the mask or the bit plane overlaps an image");
+    return vpk_bitwise_u8(ctx, op, d_a, d_b, scalar, d_mask, cn, n, d_dst, bits_w, reinterpret_cast<u64*>(d_bits), made_bits);
+}
+
+int vp_arith_u8_dev(vp_ctx* ctx, int op, const uint8_t* d_a, const uint8_t* d_b, size_t n, uint8_t* d_dst)
+{
+    VP_TRY(check_ctx(ctx));
+    if (op < VP_ARITH_ADD || op > VP_ARITH_ABSDIFF || !d_a || !d_b || !d_dst || n == 0 || n > VP_EW_MAX || !ew_dst_ok(d_a, d_dst, n) || !ew_dst_ok(d_b, d_dst, n))
+        return vp_fail(ctx, VP_ERR_INVALID, "vp_arith_u8_dev arguments");
+    return vpk_arith_u8(ctx, op, d_a, d_b, n, d_dst);
+}
+
+int vp_lut_u8_dev(vp_ctx* ctx, const uint8_t* d_src, size_t n, int cn, const uint8_t* lut, uint8_t* d_dst)
+{
+    VP_TRY(check_ctx(ctx));
+    if (!d_src || !d_dst || !lut || n == 0 || n > VP_EW_MAX || cn < 1 || cn > 4 || n % (size_t)cn != 0 || !ew_dst_ok(d_src, d_dst, n))
+        return vp_fail(ctx, VP_ERR_INVALID, "vp_lut_u8_dev arguments");
+    return vpk_lut_u8(ctx, d_src, n, cn, lut, d_dst);
+}
+
+int vp_split_u8_dev(vp_ctx* ctx, const uint8_t* d_src, size_t npx, int cn, uint8_t* d_p0, uint8_t* d_p1, uint8_t* d_p2, uint8_t* d_p3)
+{
+    VP_TRY(check_ctx(ctx));
+    if (!d_src || npx == 0 || npx > VP_EW_MAX || cn < 2 || cn > 4) return vp_fail(ctx, VP_ERR_INVALID, "vp_split_u8_dev arguments");
+    uint8_t* pl[4] = {d_p0, cn > 1 ? d_p1 : nullptr, cn > 2 ? d_p2 : nullptr, cn > 3 ? d_p3 : nullptr};
+    bool any = false;
+    for (int c = 0; c < cn; c++) {
+        if (!pl[c]) continue;
+        any = true;
+        if (dev_overlap(d_src, npx * cn, pl[c], npx)) return vp_fail(ctx, VP_ERR_INVALID, "vp_split_u8_dev: a plane overlaps the source");
+        for (int e = 0; e < c; e++)
+            if (pl[e] && dev_overlap(pl[e], npx, pl[c], npx)) return vp_fail(ctx, VP_ERR_INVALID, "vp_split_u8_dev: planes overlap");
+    }
+    if (!any) return vp_fail(ctx, VP_ERR_INVALID, "vp_split_u8_dev: no destination plane");
+    return vpk_split_u8(ctx, d_src, npx, cn, pl[0], pl[1], pl[2], pl[3]);
+}
+
+int vp_merge_u8_dev(vp_ctx* ctx, const uint8_t* d_p0, const uint8_t* d_p1, const uint8_t* d_p2, const uint8_t* d_p3, size_t npx, int cn, uint8_t* d_dst)
+{
+    VP_TRY(check_ctx(ctx));
+    if (!d_dst || npx == 0 || npx > VP_EW_MAX || cn < 2 || cn > 4) return vp_fail(ctx, VP_ERR_INVALID, "vp_merge_u8_dev arguments");
+    const uint8_t* pl[4] = {d_p0, d_p1, cn > 2 ? d_p2 : nullptr, cn > 3 ? d_p3 : nullptr};
+    for (int c = 0; c < cn; c++)
+        if (!pl[c] || dev_overlap(pl[c], npx, d_dst, npx * cn)) return vp_fail(ctx, VP_ERR_INVALID, "vp_merge_u8_dev: a plane is missing or overlaps the destination");
+    return vpk_merge_u8(ctx, pl[0], pl[1], pl[2], pl[3], npx, cn, d_dst);
+}
+
+// the counter lives in the context's workspace: carved, zeroed, counted into and read back in stream order, and the call returns only
+// after the read - a second call finds nothing of the first
+int vp_count_nonzero_u8_dev(vp_ctx* ctx, const uint8_t* d_src, size_t n, uint64_t* count)
+{
+    VP_TRY(check_ctx(ctx));
+    if (!d_src || !count || n == 0 || n > VP_EW_MAX) return vp_fail(ctx, VP_ERR_INVALID, "vp_count_nonzero_u8_dev arguments");
+    VP_TRY(vp_ws_reserve(ctx, 4096));
+    TAKE(d_total, u64*, 8);
+    VP_TRY(vpk_count_nonzero_u8(ctx, d_src, n, d_total));
+    VP_TRY(d2h(ctx, count, d_total, 8));
+    return vp_synchronize(ctx);
+}
+
+}  // extern "C"

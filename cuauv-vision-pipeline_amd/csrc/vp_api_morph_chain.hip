@@ -1,0 +1,597 @@
+// C ABI of libvp.so, morphology and the batched device-resident chain: both plan their erode / dilate stages with the same
+// stage planner (kernels: vp_morph, and through the chain vp_color / vp_ccl + contours).
+#include "vp_api_util.h"
+
+// ---- morphology planning ---------------------------------------------------------------------------
+
+struct rect_se { int kw, kh, ax, ay; };
+
+// Adds one rect erode/dilate to a stage list, split so that every stage has extents <= 31 (the kernels' funnel shifts).
+static void push_rect_stage(std::vector<vp_bitstage>& v, int dilate, const rect_se& k)
+{
+    int l = k.ax, r = k.kw - 1 - k.ax, u = k.ay, d = k.kh - 1 - k.ay;
+    // merge with the previous stage of the same kind (erode∘erode / dilate∘dilate with cv2's border
+    // rule equal one pass with summed extents: the image is a box, clamping an intermediate sample
+    // into it never increases a coordinate distance)
+    if (!v.empty() && v.back().dilate == dilate) {
+        l += v.back().l; r += v.back().r; u += v.back().u; d += v.back().d;
+        v.pop_back();
+    }
+    do {
+        vp_bitstage s;
+        s.dilate = dilate;
+        s.l = l > 31 ? 31 : l; s.r = r > 31 ? 31 : r; s.u = u > 31 ? 31 : u; s.d = d > 31 ? 31 : d;
+        l -= s.l; r -= s.r; u -= s.u; d -= s.d;
+        v.push_back(s);
+    } while (l | r | u | d);
+}
+
+// Runs a stage list over bit images, grouping stages into launches whose halo fits LDS.
+// bits_a holds the input; bits_b is scratch of equal size.  The final launch writes out_bits /
+// out_mask (either may be NULL).  With an empty list the input is forwarded.
+static int run_bit_stages(vp_ctx* ctx, const std::vector<vp_bitstage>& st, u64* bits_a, u64* bits_b, int w, int h, int n,
+                          u64* out_bits, uint8_t* out_mask)
+{
+    const size_t words = (size_t)n * h * vp_ww(w);
+    if (st.empty()) {
+        if (out_bits && out_bits != bits_a) VP_HIP(ctx, hipMemcpyAsync(out_bits, bits_a, words * 8, hipMemcpyDeviceToDevice, ctx->stream));
+        if (out_mask) VP_TRY(vpk_unpack_bits(ctx, bits_a, w, h, n, out_mask));
+        return VP_OK;
+    }
+    const size_t lds_limit = 150 * 1024;
+    const int ww = vp_ww(w);
+    size_t i = 0;
+    u64* cur = bits_a;
+    u64* other = bits_b;
+    while (i < st.size()) {
+        vp_bitplan plan;
+        plan.n = 0;
+        int halo = 0;
+        while (i < st.size() && plan.n < VP_MAX_STAGES) {
+            const int nh = halo + st[i].u + st[i].d;
+            const size_t lds = (size_t)2 * (32 + nh) * ww * 8;
+            if (plan.n > 0 && lds > lds_limit) break;
+            if (plan.n == 0 && lds > lds_limit) return vp_fail(ctx, VP_ERR_UNSUPPORTED, "image too wide for the LDS bit-morphology strip");
+            plan.s[plan.n++] = st[i++];
+            halo = nh;
+        }
+        const bool last = i == st.size();
+        u64* dst_bits = last ? out_bits : other;
+        VP_TRY(vpk_morph_bits(ctx, plan, cur, w, h, n, dst_bits, last ? out_mask : nullptr));
+        if (!last) { u64* t = cur; cur = other; other = t; }
+    }
+    return VP_OK;
+}
+
+static int stages_for_op(std::vector<vp_bitstage>& v, int op, const rect_se& k)
+{
+    switch (op) {
+        case VP_MORPH_ERODE: push_rect_stage(v, 0, k); break;
+        case VP_MORPH_DILATE: push_rect_stage(v, 1, k); break;
+        case VP_MORPH_OPEN: push_rect_stage(v, 0, k); push_rect_stage(v, 1, k); break;
+        case VP_MORPH_CLOSE: push_rect_stage(v, 1, k); push_rect_stage(v, 0, k); break;
+        default: return VP_ERR_INVALID;
+    }
+    return VP_OK;
+}
+
+// cv2 morphOp() normalisation of (kernel, anchor, iterations).  Returns 1 when the op degenerates to a copy.
+struct norm_se { std::vector<uint8_t> k; int kw, kh, ax, ay, iterations; bool allones; };
+static int normalise_se(const uint8_t* kernel, int kw, int kh, int ax, int ay, int iterations, norm_se* o)
+{
+    if (iterations < 0) return VP_ERR_INVALID;
+    if (!kernel || kw * kh == 0) {
+        kw = kh = 1 + iterations * 2;
+        ax = ay = iterations;
+        iterations = 1;
+        o->k.assign((size_t)kw * kh, 1);
+    } else {
+        if (kw <= 0 || kh <= 0) return VP_ERR_INVALID;
+        o->k.assign(kernel, kernel + (size_t)kw * kh);
+    }
+    if (ax < 0) ax = kw / 2;
+    if (ay < 0) ay = kh / 2;
+    if (ax >= kw || ay >= kh) return VP_ERR_INVALID;
+    bool allones = true;
+    for (uint8_t b : o->k) allones = allones && b != 0;
+    if (iterations > 1 && allones) {
+        ax *= iterations;
+        ay *= iterations;
+        kw = kw + (iterations - 1) * (kw - 1);
+        kh = kh + (iterations - 1) * (kh - 1);
+        iterations = 1;
+        o->k.assign((size_t)kw * kh, 1);
+    }
+    o->kw = kw; o->kh = kh; o->ax = ax; o->ay = ay; o->iterations = iterations; o->allones = allones;
+    return VP_OK;
+}
+
+extern "C" {
+
+int vp_structuring_element(int shape, int kw, int kh, uint8_t* out)
+{
+    // imgproc getStructuringElement(): integer geometry, anchor at the centre
+    if (!out || kw <= 0 || kh <= 0 || shape < 0 || shape > 2) return VP_ERR_INVALID;
+    if (kw == 1 && kh == 1) shape = VP_SHAPE_RECT;
+    const int r = kh / 2, c = kw / 2;
+    const double inv_r2 = (shape == VP_SHAPE_ELLIPSE && r) ? 1.0 / ((double)r * r) : 0.0;
+    for (int i = 0; i < kh; i++) {
+        int j1 = 0, j2 = 0;
+        if (shape == VP_SHAPE_RECT || (shape == VP_SHAPE_CROSS && i == r)) j2 = kw;
+        else if (shape == VP_SHAPE_CROSS) { j1 = c; j2 = c + 1; }
+        else {
+            const int dy = i - r;
+            if (abs(dy) <= r) {
+                const int dx = (int)__builtin_nearbyint(c * __builtin_sqrt((r * r - dy * dy) * inv_r2));
+                j1 = c - dx > 0 ? c - dx : 0;
+                j2 = c + dx + 1 < kw ? c + dx + 1 : kw;
+            }
+        }
+        for (int j = 0; j < kw; j++) out[i * kw + j] = (j >= j1 && j < j2) ? 1 : 0;
+    }
+    return VP_OK;
+}
+
+// one erode or dilate (after cv2 normalisation) on a device image; result in d_out
+static int morph_basic_dev(vp_ctx* ctx, int dilate, const norm_se& se, const uint8_t* d_in, int w, int h, int cn, bool binary,
+                           uint8_t* d_out, uint8_t* d_tmp, u64* bits_a, u64* bits_b, int16_t* d_offs, uint8_t* d_tab = nullptr)
+{
+    const size_t nbytes = (size_t)w * h * cn;
+    if (se.iterations == 0 || se.kw * se.kh == 1) {
+        VP_HIP(ctx, hipMemcpyAsync(d_out, d_in, nbytes, hipMemcpyDeviceToDevice, ctx->stream));
+        return VP_OK;
+    }
+    if (se.allones && cn == 1 && binary) {
+        std::vector<vp_bitstage> st;
+        rect_se k = {se.kw, se.kh, se.ax, se.ay};
+        push_rect_stage(st, dilate, k);
+        VP_TRY(vpk_pack_bits(ctx, d_in, (size_t)w, w, h, 1, bits_a, nullptr));
+        return run_bit_stages(ctx, st, bits_a, bits_b, w, h, 1, nullptr, d_out);
+    }
+    // generic: offsets of the structuring element (all-ones kernels are applied separably)
+    std::vector<int16_t> offs;
+    int passes_first = 0;
+    if (se.allones) {
+        for (int j = 0; j < se.kw; j++) { offs.push_back((int16_t)(j - se.ax)); offs.push_back(0); }
+        passes_first = se.kw;
+        for (int i = 0; i < se.kh; i++) { offs.push_back(0); offs.push_back((int16_t)(i - se.ay)); }
+    } else {
+        for (int i = 0; i < se.kh; i++)
+            for (int j = 0; j < se.kw; j++)
+                if (se.k[(size_t)i * se.kw + j]) { offs.push_back((int16_t)(j - se.ax)); offs.push_back((int16_t)(i - se.ay)); }
+    }
+    VP_HIP(ctx, hipMemcpyAsync(d_offs, offs.data(), offs.size() * 2, hipMemcpyHostToDevice, ctx->stream));
+    VP_HIP(ctx, hipStreamSynchronize(ctx->stream));  // offs is a local vector
+    if (se.allones) {
+        VP_TRY(vpk_morph_generic(ctx, dilate, d_in, w, h, cn, d_offs, passes_first, d_tmp));
+        VP_TRY(vpk_morph_generic(ctx, dilate, d_tmp, w, h, cn, d_offs + 2 * passes_first, se.kh, d_out));
+        return VP_OK;
+    }
+    const int noffs = (int)(offs.size() / 2);
+    // span form when it saves reads: one (dy, x0, x1) triple per run of members in a row of the element
+    std::vector<int16_t> spans;
+    int max_len = 1;
+    for (int i = 0; i < se.kh; i++)
+        for (int j = 0; j < se.kw;) {
+            if (!se.k[(size_t)i * se.kw + j]) { j++; continue; }
+            int e = j;
+            while (e + 1 < se.kw && se.k[(size_t)i * se.kw + e + 1]) e++;
+            spans.push_back((int16_t)(i - se.ay)); spans.push_back((int16_t)(j - se.ax)); spans.push_back((int16_t)(e - se.ax));
+            max_len = std::max(max_len, e - j + 1);
+            j = e + 1;
+        }
+    const int nspans = (int)(spans.size() / 3);
+    const bool use_spans = d_tab && 2 * nspans < noffs && max_len <= 255 && nspans <= 2048 && (size_t)w * cn <= 16384;
+    if (use_spans) {
+        VP_HIP(ctx, hipMemcpyAsync(d_offs, spans.data(), spans.size() * 2, hipMemcpyHostToDevice, ctx->stream));
+        VP_HIP(ctx, hipStreamSynchronize(ctx->stream));  // spans is a local vector
+    }
+    const uint8_t* cur = d_in;
+    uint8_t* bufs[2] = {d_out, d_tmp};
+    // arrange so that the last pass lands in d_out
+    int which = (se.iterations % 2 == 1) ? 0 : 1;
+    for (int it = 0; it < se.iterations; it++) {
+        if (use_spans) VP_TRY(vpk_morph_spans(ctx, dilate, cur, w, h, cn, d_offs, nspans, max_len, d_tab, bufs[which]));
+        else VP_TRY(vpk_morph_generic(ctx, dilate, cur, w, h, cn, d_offs, noffs, bufs[which]));
+        cur = bufs[which];
+        which ^= 1;
+    }
+    return VP_OK;
+}
+
+// workspace a morphology call needs besides its source / result images
+static size_t morph_ws_bytes(const norm_se& se, int w, int h, int cn)
+{
+    const size_t nbytes = (size_t)w * h * cn;
+    const size_t bitbytes = (size_t)h * vp_ww(w) * 8;
+    const size_t offbytes = ((size_t)se.kw * se.kh + se.kw + se.kh) * 4 + 64;
+    const size_t tabbytes = se.allones ? 0 : 7 * nbytes;   // running min/max tables of the span form
+    return 4 * vp_align(nbytes) + 2 * vp_align(bitbytes) + vp_align(offbytes) + vp_align(tabbytes) + 4096;
+}
+
+// One morphology operation between device images (d_dst may equal neither d_src nor overlap it); temporaries are carved from the
+// workspace, which the caller has reserved (morph_ws_bytes).  binary_hint: 1 = the image is known to hold only 0 / 255 (a mask this
+// library produced), 0 = unknown: one flag comes back from the device to decide between the bit-plane and the grey-level path.
+static int morph_core(vp_ctx* ctx, int op, const norm_se& se, const uint8_t* d_src, int w, int h, int cn, int binary_hint, uint8_t* d_dst)
+{
+    const size_t nbytes = (size_t)w * h * cn;
+    const size_t bitbytes = (size_t)h * vp_ww(w) * 8;
+    const size_t offbytes = ((size_t)se.kw * se.kh + se.kw + se.kh) * 4 + 64;
+    const size_t tabbytes = se.allones ? 0 : 7 * nbytes;
+    uint8_t* d_tab = tabbytes ? (uint8_t*)vp_ws_take(ctx, tabbytes) : nullptr;
+    if (tabbytes && !d_tab) return vp_fail(ctx, VP_ERR_NOMEM, "workspace");
+    TAKE(d_b, uint8_t*, nbytes);
+    TAKE(d_c, uint8_t*, nbytes);
+    TAKE(d_tmp, uint8_t*, nbytes);
+    TAKE(bits_a, u64*, bitbytes);
+    TAKE(bits_b, u64*, bitbytes);
+    TAKE(d_offs, int16_t*, offbytes);
+    TAKE(d_flag, int*, 4);
+    bool binary = false;
+    if (cn == 1 && se.allones) {
+        // a 0/255 mask can take the bit-plane path; anything else is grey-level
+        if (binary_hint == 1) {
+            VP_TRY(vpk_pack_bits(ctx, d_src, (size_t)w, w, h, 1, bits_a, nullptr));
+            binary = true;
+        } else {
+            VP_HIP(ctx, hipMemsetAsync(d_flag, 0, 4, ctx->stream));
+            VP_TRY(vpk_pack_bits(ctx, d_src, (size_t)w, w, h, 1, bits_a, d_flag));
+            int flag = 1;
+            VP_TRY(d2h(ctx, &flag, d_flag, 4));
+            VP_HIP(ctx, hipStreamSynchronize(ctx->stream));
+            binary = flag == 0;
+        }
+    }
+    if (binary && op != VP_MORPH_GRADIENT) {
+        // whole op (incl. OPEN/CLOSE) as one fused bit-plane launch
+        std::vector<vp_bitstage> st;
+        rect_se k = {se.kw, se.kh, se.ax, se.ay};
+        if (!(se.iterations == 0 || se.kw * se.kh == 1)) stages_for_op(st, op, k);
+        VP_TRY(run_bit_stages(ctx, st, bits_a, bits_b, w, h, 1, nullptr, d_dst));
+    } else if (op == VP_MORPH_ERODE || op == VP_MORPH_DILATE) {
+        VP_TRY(morph_basic_dev(ctx, op == VP_MORPH_DILATE, se, d_src, w, h, cn, binary, d_dst, d_tmp, bits_a, bits_b, d_offs, d_tab));
+    } else if (op == VP_MORPH_OPEN || op == VP_MORPH_CLOSE) {
+        const int first = op == VP_MORPH_CLOSE;
+        VP_TRY(morph_basic_dev(ctx, first, se, d_src, w, h, cn, binary, d_b, d_tmp, bits_a, bits_b, d_offs, d_tab));
+        VP_TRY(morph_basic_dev(ctx, !first, se, d_b, w, h, cn, binary, d_dst, d_tmp, bits_a, bits_b, d_offs, d_tab));
+    } else {  // GRADIENT = dilate - erode
+        VP_TRY(morph_basic_dev(ctx, 1, se, d_src, w, h, cn, binary, d_b, d_tmp, bits_a, bits_b, d_offs, d_tab));
+        VP_TRY(morph_basic_dev(ctx, 0, se, d_src, w, h, cn, binary, d_c, d_tmp, bits_a, bits_b, d_offs, d_tab));
+        VP_TRY(vpk_absdiff_sub_u8(ctx, d_b, d_c, nbytes, d_dst));
+    }
+    return VP_OK;
+}
+
+int vp_morph_u8(vp_ctx* ctx, int op, const uint8_t* src, int w, int h, int cn, const uint8_t* kernel, int kw, int kh, int ax, int ay,
+                int iterations, uint8_t* dst)
+{
+    VP_TRY(check_ctx(ctx));
+    if (!src || !dst || w <= 0 || h <= 0 || h > 65535 || cn < 1 || cn > 4 || op < VP_MORPH_ERODE || op > VP_MORPH_GRADIENT)
+        return vp_fail(ctx, VP_ERR_INVALID, "vp_morph_u8 arguments");
+    norm_se se;
+    if (normalise_se(kernel, kw, kh, ax, ay, iterations, &se) != VP_OK) return vp_fail(ctx, VP_ERR_INVALID, "structuring element");
+    const size_t nbytes = (size_t)w * h * cn;
+    VP_TRY(vp_ws_reserve(ctx, 2 * vp_align(nbytes) + morph_ws_bytes(se, w, h, cn)));
+    TAKE(d_src, uint8_t*, nbytes);
+    TAKE(d_a, uint8_t*, nbytes);
+    VP_TRY(h2d(ctx, d_src, src, nbytes));
+    VP_TRY(morph_core(ctx, op, se, d_src, w, h, cn, 0, d_a));
+    VP_TRY(d2h(ctx, dst, d_a, nbytes));
+    return vp_synchronize(ctx);
+}
+
+int vp_morph_u8_dev(vp_ctx* ctx, int op, const uint8_t* d_src, int w, int h, int cn, const uint8_t* kernel, int kw, int kh, int ax, int ay,
+                    int iterations, int binary_hint, uint8_t* d_dst)
+{
+    VP_TRY(check_ctx(ctx));
+    if (!d_src || !d_dst || d_src == d_dst || w <= 0 || h <= 0 || h > 65535 || cn < 1 || cn > 4 || op < VP_MORPH_ERODE || op > VP_MORPH_GRADIENT)
+        return vp_fail(ctx, VP_ERR_INVALID, "vp_morph_u8_dev arguments");
+    norm_se se;
+    if (normalise_se(kernel, kw, kh, ax, ay, iterations, &se) != VP_OK) return vp_fail(ctx, VP_ERR_INVALID, "structuring element");
+    VP_TRY(vp_ws_reserve(ctx, morph_ws_bytes(se, w, h, cn)));
+    return morph_core(ctx, op, se, d_src, w, h, cn, binary_hint, d_dst);
+}
+
+// ---- chain -------------------------------------------------------------------------------------------
+
+static int check_desc(vp_ctx* ctx, const vp_chain_desc* d, int n)
+{
+    if (!d || n <= 0 || d->width <= 0 || d->height <= 0) return vp_fail(ctx, VP_ERR_INVALID, "chain: size");
+    // frames ride on gridDim.y; segment ids and pixel indices are 32-bit
+    if (n > 65535 || (unsigned long long)d->width * (unsigned long long)d->height > (1ull << 30)) return vp_fail(ctx, VP_ERR_UNSUPPORTED, "chain: batch or frame too large");
+    if (d->color_mode != VP_BGR2LAB && d->color_mode != VP_BGR2HSV && d->color_mode != VP_BGR2GRAY)
+        return vp_fail(ctx, VP_ERR_INVALID, "chain: color_mode");
+    if (d->n_morph < 0 || d->n_morph > VP_CHAIN_MAX_MORPH) return vp_fail(ctx, VP_ERR_INVALID, "chain: n_morph");
+    for (int i = 0; i < d->n_morph; i++)
+        if (d->morph_op[i] < VP_MORPH_ERODE || d->morph_op[i] > VP_MORPH_CLOSE || d->morph_kw[i] <= 0 || d->morph_kh[i] <= 0 ||
+            d->morph_iter[i] < 0)
+            return vp_fail(ctx, VP_ERR_INVALID, "chain: morph op");
+    if (d->ccl < 0 || d->ccl > 2) return vp_fail(ctx, VP_ERR_INVALID, "chain: ccl");
+    if (d->ccl && d->numbering != VP_CCL_BLOCK2X2 && d->numbering != VP_CCL_PIXEL) return vp_fail(ctx, VP_ERR_INVALID, "chain: numbering");
+    if (d->ccl && d->max_labels < 1) return vp_fail(ctx, VP_ERR_INVALID, "chain: max_labels");
+    return VP_OK;
+}
+
+static size_t chain_ws_bytes(const vp_chain_desc* d, int n)
+{
+    const size_t bitbytes = (size_t)n * d->height * vp_ww(d->width) * 8;
+    size_t need = 3 * vp_align(bitbytes) + vp_align((size_t)n * 4) + 8192 + 4 * 16384;
+    if (d->ccl) need += vp_ccl_ws_bytes(d->width, d->height, n, d->max_labels);
+    return need;
+}
+
+// core: all pointers device; workspace already reserved and not yet carved past `ctx->ws_off`
+// frames per contour pass: the contour scratch is about 41 B/px per frame (85 MB at 1080p: sized for the worst case of 1.25 heads per
+// pixel); a pass takes as many frames as fit a budget of 16 GiB (VP_CT_SCRATCH_MB overrides) - measured at 1080p, batch 128 (round 3): 16
+// frames per pass 2.26 ms, 64 1.57 ms, 128 1.40 ms
+static int ct_group_for(int w, int h, int max_contours)
+{
+    const char* e = getenv("VP_CT_SCRATCH_MB");
+    long long budget = (e ? atoll(e) : 16384ll) << 20;
+    if (budget < (1ll << 20)) budget = 1ll << 20;
+    const long long per = (long long)vp_contours_ws_bytes(w, h, 1, max_contours);
+    return (int)std::max<long long>(1, std::min<long long>(budget / per, 1 << 20));
+}
+static int chain_core(vp_ctx* ctx, const vp_chain_desc* d, const vp_chain_buffers* b, int n, const vp_contour_desc* cd = nullptr,
+                      const vp_contour_buffers* cb = nullptr)
+{
+    const int w = d->width, h = d->height;
+    const size_t bitbytes = (size_t)n * h * vp_ww(w) * 8;
+    TAKE(bits_t, u64*, bitbytes);   // threshold bits
+    TAKE(bits_a, u64*, bitbytes);
+    TAKE(bits_b, u64*, bitbytes);
+    TAKE(d_nl, int32_t*, (size_t)n * 4);
+    vp_range3 q;
+    norm_range(d->color_mode == VP_BGR2GRAY ? 1 : 3, d->lo, d->hi, &q);
+    VP_TRY(vpk_color_thresh(ctx, d->color_mode, b->bgr, (size_t)w * 3, w, h, n, q, b->threshed, bits_t));
+
+    std::vector<vp_bitstage> st;
+    for (int i = 0; i < d->n_morph; i++) {
+        norm_se se;
+        // rect kernel kw x kh, centre anchor, cv2 iteration collapse for all-ones kernels
+        std::vector<uint8_t> ones((size_t)d->morph_kw[i] * d->morph_kh[i], 1);
+        if (normalise_se(ones.data(), d->morph_kw[i], d->morph_kh[i], -1, -1, d->morph_iter[i], &se) != VP_OK)
+            return vp_fail(ctx, VP_ERR_INVALID, "chain: kernel");
+        if (se.iterations == 0 || se.kw * se.kh == 1) continue;
+        rect_se k = {se.kw, se.kh, se.ax, se.ay};
+        if (stages_for_op(st, d->morph_op[i], k) != VP_OK) return vp_fail(ctx, VP_ERR_INVALID, "chain: op");
+    }
+    const bool need_clean_bits = d->ccl == 1 || (cd && cd->source == 1);
+    const u64* ccl_bits = bits_t;
+    const u64* clean_bits = bits_t;   // no morphology: the cleaned mask is the threshold mask
+    vp_ccl_ws ws;
+    memset(&ws, 0, sizeof ws);
+    if (d->ccl) {
+        vp_ccl_ws_carve(ctx, w, h, n, d->max_labels, &ws);
+        if (!vp_ccl_ws_ok(ws)) return vp_fail(ctx, VP_ERR_NOMEM, "ccl workspace");
+    }
+    if ((!st.empty() && (need_clean_bits || b->cleaned)) || (st.empty() && b->cleaned)) {
+        if (st.empty()) {
+            VP_TRY(vpk_unpack_bits(ctx, bits_t, w, h, n, b->cleaned));
+        } else {
+            // bits_t must survive when CCL labels the threshold mask; run_bit_stages only reads its input
+            VP_TRY(run_bit_stages(ctx, st, bits_t, bits_b, w, h, n, need_clean_bits ? bits_a : nullptr, b->cleaned));
+            if (need_clean_bits) clean_bits = bits_a;
+            if (d->ccl == 1) ccl_bits = bits_a;
+        }
+    }
+    auto contours_of_batch = [&]() -> int {
+        const u64* src = cd->source == 1 ? clean_bits : bits_t;
+        const size_t fw = (size_t)h * vp_ww(w);
+        const size_t mc = (size_t)cd->max_contours;
+        const size_t mark = ctx->ws_off;
+        const int group = ct_group_for(w, h, cd->max_contours);
+        // speckled frames in the last batch (its prefix kernel left the head counts in pinned memory): the bookkeeping as launches over
+        // the chip instead of one block per frame (VP_CT_MANY=0 / 1: never / always)
+        const char* many_s = getenv("VP_CT_MANY");
+        const bool many = many_s ? atoi(many_s) != 0 : vp_ct_batch_hint(ctx) > 8192u;
+        for (int f0 = 0; f0 < n; f0 += group) {
+            const int g = std::min(group, n - f0);
+            ctx->ws_off = mark;   // every group reuses the same scratch (stream order keeps them apart)
+            VP_TRY(vpk_find_contours(ctx, src + (size_t)f0 * fw, w, h, g, cd->mode, cd->method, cb->counts + f0 * mc, cb->is_hole + f0 * mc,
+                                     cb->offsets + f0 * mc, cb->points + 2 * (size_t)f0 * (size_t)cd->max_points, cd->max_contours,
+                                     cd->max_points, cb->info + 2 * (size_t)f0, many));
+        }
+        if (cb->features) VP_TRY(vpk_contour_features(ctx, cb->info, cb->counts, cb->offsets, cb->points, n, cd->max_contours, cd->max_points, cb->features));
+        return VP_OK;
+    };
+    // The contour pass needs the mask only, not the labelling: when the chain does both it is queued on the context's side stream as
+    // soon as the mask exists and runs beside the labelling and its label write (latency-bound launches beside a bandwidth-bound one);
+    // the caller's stream joins it at the end.  One pass for the whole batch only (the scratch is carved once).  VP_CT_SIDE=0: in a row.
+    static const bool ct_side_off = getenv("VP_CT_SIDE") && atoi(getenv("VP_CT_SIDE")) == 0;
+    const bool ct_side = cd && d->ccl && !ct_side_off && ctx->chain_streams == 1 && ct_group_for(w, h, cd->max_contours) >= n;
+    int rc_ct = VP_OK;
+    bool joined = true;
+    hipStream_t s_main = ctx->stream;
+    if (ct_side) {
+        VP_HIP(ctx, hipEventRecord(ctx->ev_fb_fork, s_main));
+        VP_HIP(ctx, hipStreamWaitEvent(ctx->fb_stream, ctx->ev_fb_fork, 0));
+        ctx->stream = ctx->fb_stream;
+        rc_ct = contours_of_batch();
+        const hipError_t ej = hipEventRecord(ctx->ev_fb_join, ctx->fb_stream);
+        ctx->stream = s_main;
+        joined = false;
+        if (ej != hipSuccess) { (void)hipStreamSynchronize(ctx->fb_stream); joined = true; if (rc_ct == VP_OK) rc_ct = vp_fail(ctx, VP_ERR_HIP, "hipEventRecord", ej); }
+    }
+    int rc_ccl = VP_OK;
+    if (d->ccl) rc_ccl = vpk_ccl(ctx, ccl_bits, w, h, n, d->numbering, ws, b->labels, b->stats, b->centroids, d->max_labels, b->nlabels ? b->nlabels : d_nl);
+    if (!joined && hipStreamWaitEvent(s_main, ctx->ev_fb_join, 0) != hipSuccess) { (void)hipGetLastError(); (void)hipStreamSynchronize(ctx->fb_stream); }
+    if (rc_ccl != VP_OK) return rc_ccl;
+    if (rc_ct != VP_OK) return rc_ct;
+    if (cd && !ct_side) VP_TRY(contours_of_batch());
+    return VP_OK;
+}
+
+static int check_cdesc(vp_ctx* ctx, const vp_contour_desc* cd, const vp_contour_buffers* cb)
+{
+    if (!cd || !cb) return vp_fail(ctx, VP_ERR_INVALID, "contours: descriptor");
+    if (cd->source != 1 && cd->source != 2) return vp_fail(ctx, VP_ERR_INVALID, "contours: source");
+    if (cd->mode != VP_RETR_EXTERNAL && cd->mode != VP_RETR_LIST) return vp_fail(ctx, VP_ERR_INVALID, "contour mode");
+    if (cd->method != VP_CHAIN_APPROX_NONE && cd->method != VP_CHAIN_APPROX_SIMPLE) return vp_fail(ctx, VP_ERR_INVALID, "contour approximation");
+    if (cd->max_contours <= 0 || cd->max_points <= 0) return vp_fail(ctx, VP_ERR_INVALID, "contours: capacity");
+    if (!cb->info || !cb->counts || !cb->offsets || !cb->is_hole || !cb->points) return vp_fail(ctx, VP_ERR_INVALID, "contours: buffers");
+    return VP_OK;
+}
+
+// Runs the chain for n frames, split into sub-batches on the context's internal streams (fork/join around the
+// caller-visible stream).  Frames are independent, so the split changes scheduling only.
+static int chain_split(vp_ctx* ctx, const vp_chain_desc* d, const vp_chain_buffers* b, int n)
+{
+    int S = ctx->chain_streams;
+    if (S > n / 4) S = n / 4;      // keep sub-batches worth a launch
+    if (S <= 1) return chain_core(ctx, d, b, n);
+    const size_t npx = (size_t)d->width * d->height;
+    const size_t ml = (size_t)(d->ccl ? d->max_labels : 0);
+    hipStream_t user = ctx->stream;
+    VP_HIP(ctx, hipEventRecord(ctx->ev_fork, user));
+    int rc = VP_OK;
+    int f0 = 0;
+    for (int s = 0; s < S && rc == VP_OK; s++) {
+        const int cnt = n / S + (s < n % S ? 1 : 0);
+        vp_chain_buffers sb = *b;
+        sb.bgr = b->bgr + (size_t)f0 * npx * 3;
+        if (b->threshed) sb.threshed = b->threshed + (size_t)f0 * npx;
+        if (b->cleaned) sb.cleaned = b->cleaned + (size_t)f0 * npx;
+        if (b->labels) sb.labels = b->labels + (size_t)f0 * npx;
+        if (b->stats) sb.stats = b->stats + (size_t)f0 * ml * 5;
+        if (b->centroids) sb.centroids = b->centroids + (size_t)f0 * ml * 2;
+        if (b->nlabels) sb.nlabels = b->nlabels + f0;
+        hipError_t e = hipStreamWaitEvent(ctx->aux[s], ctx->ev_fork, 0);
+        if (e != hipSuccess) { rc = vp_fail(ctx, VP_ERR_HIP, "hipStreamWaitEvent", e); break; }
+        ctx->stream = ctx->aux[s];
+        rc = chain_core(ctx, d, &sb, cnt);
+        ctx->stream = user;
+        // join whatever was queued on the side stream, also after an error: it must not still run when the next call reuses the workspace
+        const hipError_t e1 = hipEventRecord(ctx->ev_join[s], ctx->aux[s]);
+        const hipError_t e2 = e1 == hipSuccess ? hipStreamWaitEvent(user, ctx->ev_join[s], 0) : e1;
+        if (rc != VP_OK) break;
+        if (e1 != hipSuccess) { rc = vp_fail(ctx, VP_ERR_HIP, "hipEventRecord", e1); break; }
+        if (e2 != hipSuccess) { rc = vp_fail(ctx, VP_ERR_HIP, "hipStreamWaitEvent", e2); break; }
+        f0 += cnt;
+    }
+    ctx->stream = user;
+    return rc;
+}
+
+int vp_chain_run(vp_ctx* ctx, const vp_chain_desc* desc, const vp_chain_buffers* dev, int n_frames)
+{
+    VP_TRY(check_ctx(ctx));
+    VP_TRY(check_desc(ctx, desc, n_frames));
+    if (!dev || !dev->bgr) return vp_fail(ctx, VP_ERR_INVALID, "chain: bgr");
+    VP_TRY(vp_ws_reserve(ctx, chain_ws_bytes(desc, n_frames) + 4 * 65536));
+    return chain_split(ctx, desc, dev, n_frames);
+}
+
+int vp_chain_run_host(vp_ctx* ctx, const vp_chain_desc* desc, const vp_chain_buffers* host, int n)
+{
+    VP_TRY(check_ctx(ctx));
+    VP_TRY(check_desc(ctx, desc, n));
+    if (!host || !host->bgr) return vp_fail(ctx, VP_ERR_INVALID, "chain: bgr");
+    const size_t npx = (size_t)n * desc->width * desc->height;
+    const size_t ml = (size_t)(desc->ccl ? desc->max_labels : 1);
+    VP_TRY(vp_ws_reserve(ctx, chain_ws_bytes(desc, n) + vp_align(npx * 3) + 2 * vp_align(npx) + vp_align(npx * 4) +
+                                  vp_align(n * ml * 20) + vp_align(n * ml * 16) + vp_align((size_t)n * 4) + 8192));
+    vp_chain_buffers d;
+    memset(&d, 0, sizeof d);
+    TAKE(d_bgr, uint8_t*, npx * 3);
+    d.bgr = d_bgr;
+    if (host->threshed) { d.threshed = (uint8_t*)vp_ws_take(ctx, npx); if (!d.threshed) return vp_fail(ctx, VP_ERR_NOMEM, "workspace"); }
+    if (host->cleaned) { d.cleaned = (uint8_t*)vp_ws_take(ctx, npx); if (!d.cleaned) return vp_fail(ctx, VP_ERR_NOMEM, "workspace"); }
+    if (desc->ccl) {
+        if (host->labels) { d.labels = (int32_t*)vp_ws_take(ctx, npx * 4); if (!d.labels) return vp_fail(ctx, VP_ERR_NOMEM, "workspace"); }
+        if (host->stats) { d.stats = (int32_t*)vp_ws_take(ctx, n * ml * 20); if (!d.stats) return vp_fail(ctx, VP_ERR_NOMEM, "workspace"); }
+        if (host->centroids) { d.centroids = (double*)vp_ws_take(ctx, n * ml * 16); if (!d.centroids) return vp_fail(ctx, VP_ERR_NOMEM, "workspace"); }
+        d.nlabels = (int32_t*)vp_ws_take(ctx, (size_t)n * 4);
+        if (!d.nlabels) return vp_fail(ctx, VP_ERR_NOMEM, "workspace");
+    }
+    VP_TRY(h2d(ctx, d_bgr, host->bgr, npx * 3));
+    VP_TRY(chain_split(ctx, desc, &d, n));
+    if (host->threshed) VP_TRY(d2h(ctx, host->threshed, d.threshed, npx));
+    if (host->cleaned) VP_TRY(d2h(ctx, host->cleaned, d.cleaned, npx));
+    if (desc->ccl) {
+        if (host->labels) VP_TRY(d2h(ctx, host->labels, d.labels, npx * 4));
+        if (host->stats) VP_TRY(d2h(ctx, host->stats, d.stats, n * ml * 20));
+        if (host->centroids) VP_TRY(d2h(ctx, host->centroids, d.centroids, n * ml * 16));
+        if (host->nlabels) VP_TRY(d2h(ctx, host->nlabels, d.nlabels, (size_t)n * 4));
+    }
+    return vp_synchronize(ctx);
+}
+
+int vp_chain_run_contours(vp_ctx* ctx, const vp_chain_desc* desc, const vp_chain_buffers* dev, const vp_contour_desc* cdesc,
+                          const vp_contour_buffers* cdev, int n_frames)
+{
+    VP_TRY(check_ctx(ctx));
+    VP_TRY(check_desc(ctx, desc, n_frames));
+    VP_TRY(check_cdesc(ctx, cdesc, cdev));
+    if (!dev || !dev->bgr) return vp_fail(ctx, VP_ERR_INVALID, "chain: bgr");
+    VP_TRY(vp_ws_reserve(ctx, chain_ws_bytes(desc, n_frames) + 4 * 65536 +
+                                  vp_contours_ws_bytes(desc->width, desc->height, std::min(n_frames, ct_group_for(desc->width, desc->height, cdesc->max_contours)), cdesc->max_contours)));
+    return chain_core(ctx, desc, dev, n_frames, cdesc, cdev);
+}
+
+int vp_chain_run_contours_host(vp_ctx* ctx, const vp_chain_desc* desc, const vp_chain_buffers* host, const vp_contour_desc* cdesc,
+                               const vp_contour_buffers* chost, int n)
+{
+    VP_TRY(check_ctx(ctx));
+    VP_TRY(check_desc(ctx, desc, n));
+    VP_TRY(check_cdesc(ctx, cdesc, chost));
+    if (!host || !host->bgr) return vp_fail(ctx, VP_ERR_INVALID, "chain: bgr");
+    const size_t npx = (size_t)n * desc->width * desc->height;
+    const size_t ml = (size_t)(desc->ccl ? desc->max_labels : 1);
+    const size_t mc = (size_t)cdesc->max_contours, mp = (size_t)cdesc->max_points;
+    VP_TRY(vp_ws_reserve(ctx, chain_ws_bytes(desc, n) + vp_align(npx * 3) + 2 * vp_align(npx) + vp_align(npx * 4) + vp_align(n * ml * 20) +
+                                  vp_align(n * ml * 16) + vp_align((size_t)n * 4) + vp_align((size_t)n * 8) + 2 * vp_align(n * mc * 4) +
+                                  vp_align(n * mc) + vp_align(n * mp * 8) + vp_align(n * mc * 64) + 16384 +
+                                  vp_contours_ws_bytes(desc->width, desc->height, std::min(n, ct_group_for(desc->width, desc->height, cdesc->max_contours)), cdesc->max_contours)));
+    vp_chain_buffers d;
+    memset(&d, 0, sizeof d);
+    TAKE(d_bgr, uint8_t*, npx * 3);
+    d.bgr = d_bgr;
+    if (host->threshed) { d.threshed = (uint8_t*)vp_ws_take(ctx, npx); if (!d.threshed) return vp_fail(ctx, VP_ERR_NOMEM, "workspace"); }
+    if (host->cleaned) { d.cleaned = (uint8_t*)vp_ws_take(ctx, npx); if (!d.cleaned) return vp_fail(ctx, VP_ERR_NOMEM, "workspace"); }
+    if (desc->ccl) {
+        if (host->labels) { d.labels = (int32_t*)vp_ws_take(ctx, npx * 4); if (!d.labels) return vp_fail(ctx, VP_ERR_NOMEM, "workspace"); }
+        if (host->stats) { d.stats = (int32_t*)vp_ws_take(ctx, n * ml * 20); if (!d.stats) return vp_fail(ctx, VP_ERR_NOMEM, "workspace"); }
+        if (host->centroids) { d.centroids = (double*)vp_ws_take(ctx, n * ml * 16); if (!d.centroids) return vp_fail(ctx, VP_ERR_NOMEM, "workspace"); }
+        d.nlabels = (int32_t*)vp_ws_take(ctx, (size_t)n * 4);
+        if (!d.nlabels) return vp_fail(ctx, VP_ERR_NOMEM, "workspace");
+    }
+    vp_contour_buffers c;
+    c.info = (int32_t*)vp_ws_take(ctx, (size_t)n * 8);
+    c.counts = (int32_t*)vp_ws_take(ctx, n * mc * 4);
+    c.offsets = (int32_t*)vp_ws_take(ctx, n * mc * 4);
+    c.is_hole = (uint8_t*)vp_ws_take(ctx, n * mc);
+    c.points = (int32_t*)vp_ws_take(ctx, n * mp * 8);
+    c.features = chost->features ? (double*)vp_ws_take(ctx, n * mc * 64) : nullptr;
+    if (!c.info || !c.counts || !c.offsets || !c.is_hole || !c.points || (chost->features && !c.features)) return vp_fail(ctx, VP_ERR_NOMEM, "workspace");
+    VP_TRY(h2d(ctx, d_bgr, host->bgr, npx * 3));
+    VP_TRY(chain_core(ctx, desc, &d, n, cdesc, &c));
+    if (host->threshed) VP_TRY(d2h(ctx, host->threshed, d.threshed, npx));
+    if (host->cleaned) VP_TRY(d2h(ctx, host->cleaned, d.cleaned, npx));
+    if (desc->ccl) {
+        if (host->labels) VP_TRY(d2h(ctx, host->labels, d.labels, npx * 4));
+        if (host->stats) VP_TRY(d2h(ctx, host->stats, d.stats, n * ml * 20));
+        if (host->centroids) VP_TRY(d2h(ctx, host->centroids, d.centroids, n * ml * 16));
+        if (host->nlabels) VP_TRY(d2h(ctx, host->nlabels, d.nlabels, (size_t)n * 4));
+    }
+    VP_TRY(d2h(ctx, chost->info, c.info, (size_t)n * 8));
+    VP_TRY(d2h(ctx, chost->counts, c.counts, n * mc * 4));
+    VP_TRY(d2h(ctx, chost->offsets, c.offsets, n * mc * 4));
+    VP_TRY(d2h(ctx, chost->is_hole, c.is_hole, n * mc));
+    VP_TRY(d2h(ctx, chost->points, c.points, n * mp * 8));
+    if (chost->features) VP_TRY(d2h(ctx, chost->features, c.features, n * mc * 64));
+    return vp_synchronize(ctx);
+}
+
+uint64_t vp_chain_algorithmic_bytes(const vp_chain_desc* desc, const vp_chain_buffers* bufs, int n)
+{
+    if (!desc || !bufs || n <= 0) return 0;
+    const uint64_t npx = (uint64_t)n * desc->width * desc->height;
+    uint64_t per = 3;
+    if (bufs->threshed) per += 1;
+    if (bufs->cleaned) per += 1;
+    if (desc->ccl && bufs->labels) per += 4;
+    return npx * per;
+}
+
+}  // extern "C"
