@@ -30,6 +30,7 @@ const char* vp_strerror(int code)
         case VP_ERR_HIP: return "HIP runtime error";
         case VP_ERR_NOMEM: return "out of memory";
         case VP_ERR_UNSUPPORTED: return "unsupported";
+        case VP_ERR_CAPACITY: return "capacity exceeded";
         default: return "unknown error";
     }
 }

@@ -1,5 +1,5 @@
 // C ABI of libvp.so, shapes: polygon sums, convex hull, minimum-area rectangle and the overlay rasteriser on the host, the
-// overlay and cv2.addWeighted on device images (kernels: vp_morph).
+// overlay, filled shapes and cv2.addWeighted on device images (kernels: vp_morph, vp_fill).
 #include "vp_api_util.h"
 
 extern "C" {
@@ -109,10 +109,10 @@ int vp_min_area_rect_i32(const int32_t* pts, int npts, float* out5)
 // counts[k] points per polyline, back to back in pts; one call draws them all (a frame's contours).
 // All stamps carry one colour, so the image is "colour wherever some stamp covers": the stamps are collected in a coverage bit plane
 // (one bit per pixel, 259 KB at 1080p, per thread, left zeroed) and the image is written once, row by row, run by run.
-int vp_draw_polylines_u8(uint8_t* img, size_t stride, int w, int h, int cn, const int32_t* pts, const int32_t* counts, int npolys, int closed,
-                         const uint8_t* color, int thickness)
+// filled (vp_fill_polys_u8; the caller has checked the coordinate bound): the even-odd spans of every polygon enter the plane first.
+static int raster_polys_u8(uint8_t* img, size_t stride, int w, int h, int cn, const int32_t* pts, const int32_t* counts, int npolys, int closed,
+                           const uint8_t* color, int thickness, bool filled)
 {
-    if (!img || !pts || !counts || !color || w <= 0 || h <= 0 || cn < 1 || cn > 4 || npolys < 0 || stride < (size_t)w * cn) return VP_ERR_INVALID;
     if (thickness < 1) thickness = 1;
     const int r0 = (thickness - 1) / 2, r1 = thickness / 2;
     const int ww = (w + 63) >> 6;
@@ -177,6 +177,36 @@ int vp_draw_polylines_u8(uint8_t* img, size_t stride, int w, int h, int cn, cons
             if (e2 <= dx) { err += dx; y0 += sy; }
         }
     };
+    // vision/utils/draw.py _fill: rows of the clipped bounding box; an edge counts on row y when min(ya, yb) <= y < max(ya, yb); the
+    // sorted crossings pair up into spans [ceil(a), floor(b)].  The edges are taken in the order of their first row and kept in a list
+    // while the sweep is inside them; the crossings are exact keys (vp_fill_cross_key), any number of them per row.
+    static thread_local std::vector<int> order, active;
+    static thread_local std::vector<u64> keys;
+    auto fill_poly = [&](const int32_t* p, int n) {
+        int ymin = p[1], ymax = p[1];
+        for (int i = 1; i < n; i++) { ymin = std::min(ymin, p[2 * i + 1]); ymax = std::max(ymax, p[2 * i + 1]); }
+        const int y0 = std::max(ymin, 0), y1 = std::min(ymax, h - 1);
+        if (y0 > y1 || ymin == ymax) return;
+        auto first_row = [&](int e) { int lo, hi; vp_fill_edge_rows(p[2 * e + 1], p[2 * (e + 1 == n ? 0 : e + 1) + 1], &lo, &hi); return lo; };
+        auto end_row = [&](int e) { int lo, hi; vp_fill_edge_rows(p[2 * e + 1], p[2 * (e + 1 == n ? 0 : e + 1) + 1], &lo, &hi); return hi; };
+        order.clear();
+        for (int e = 0; e < n; e++) { int lo, hi; if (vp_fill_edge_rows(p[2 * e + 1], p[2 * (e + 1 == n ? 0 : e + 1) + 1], &lo, &hi)) order.push_back(e); }
+        std::sort(order.begin(), order.end(), [&](int a, int b) { return first_row(a) < first_row(b); });
+        active.clear();
+        size_t next = 0;
+        for (int y = y0; y <= y1; y++) {
+            for (; next < order.size() && first_row(order[next]) <= y; next++) active.push_back(order[next]);
+            keys.clear();
+            for (size_t i = 0; i < active.size();) {
+                const int e = active[i], e1 = e + 1 == n ? 0 : e + 1;
+                if (end_row(e) <= y) { active[i] = active.back(); active.pop_back(); continue; }
+                keys.push_back(vp_fill_cross_key(p[2 * e], p[2 * e + 1], p[2 * e1], p[2 * e1 + 1], y));
+                i++;
+            }
+            std::sort(keys.begin(), keys.end());
+            for (size_t i = 0; i + 1 < keys.size(); i += 2) fill(vp_fill_key_ceil(keys[i]), vp_fill_key_floor(keys[i + 1]) + 1, y, y + 1);
+        }
+    };
     size_t o = 0;
     int rc = VP_OK;
     for (int k = 0; k < npolys; k++) {
@@ -186,6 +216,7 @@ int vp_draw_polylines_u8(uint8_t* img, size_t stride, int w, int h, int cn, cons
         o += (size_t)npts;
         have = false;
         if (npts == 0) continue;
+        if (filled) fill_poly(p, npts);
         if (npts == 1) { line(p[0], p[1], p[0], p[1]); continue; }
         const int last = closed ? npts : npts - 1;
         for (int i = 0; i < last; i++) {
@@ -237,6 +268,13 @@ int vp_draw_polylines_u8(uint8_t* img, size_t stride, int w, int h, int cn, cons
     return rc;
 }
 
+int vp_draw_polylines_u8(uint8_t* img, size_t stride, int w, int h, int cn, const int32_t* pts, const int32_t* counts, int npolys, int closed,
+                         const uint8_t* color, int thickness)
+{
+    if (!img || !pts || !counts || !color || w <= 0 || h <= 0 || cn < 1 || cn > 4 || npolys < 0 || stride < (size_t)w * cn) return VP_ERR_INVALID;
+    return raster_polys_u8(img, stride, w, h, cn, pts, counts, npolys, closed, color, thickness, false);
+}
+
 int vp_draw_polyline_u8(uint8_t* img, size_t stride, int w, int h, int cn, const int32_t* pts, int npts, int closed, const uint8_t* color,
                         int thickness)
 {
@@ -246,22 +284,16 @@ int vp_draw_polyline_u8(uint8_t* img, size_t stride, int w, int h, int cn, const
 
 // The polylines of vp_draw_polylines_u8 drawn into a packed device image (bins.py draws its rectangles into an overlay that only ever
 // leaves the device when it is posted).  Points and counts are host arrays; the same pixels as the host rasteriser.
-int vp_draw_polylines_dev(vp_ctx* ctx, uint8_t* d_img, int w, int h, int cn, const int32_t* pts, const int32_t* counts, int npolys, int closed,
-                          const uint8_t* color, int thickness)
+// fill (nullable; vp_fill_polys_dev): the polygons' rows, filled on the same stream before the outline - the descriptors travel with
+// the vertices.
+static int polylines_dev(vp_ctx* ctx, const char* who, uint8_t* d_img, int w, int h, int cn, const int32_t* pts, const int32_t* counts, int npolys, int closed,
+                         const uint8_t* color, int thickness, long long total, const std::vector<vp_fill_poly>* fill, int fill_rows)
 {
-    VP_TRY(check_ctx(ctx));
-    if (!d_img || !pts || !counts || !color || w <= 0 || h <= 0 || cn < 1 || cn > 4 || npolys < 0) return vp_fail(ctx, VP_ERR_INVALID, "vp_draw_polylines_dev arguments");
-    if (thickness < 1) thickness = 1;
-    if (thickness > 255) return vp_fail(ctx, VP_ERR_UNSUPPORTED, "vp_draw_polylines_dev: thickness");
     // the vertices and, per vertex, the vertex it is joined to go over in one pinned chunk; the device walks the lines (k_draw_segments)
-    long long total = 0;
-    for (int k = 0; k < npolys; k++) {
-        if (counts[k] < 0) return vp_fail(ctx, VP_ERR_INVALID, "vp_draw_polylines_dev: counts");
-        total += counts[k];
-    }
     if (total == 0) return VP_OK;
-    if (total > (1ll << 28)) return vp_fail(ctx, VP_ERR_INVALID, "vp_draw_polylines_dev: too many points");
+    if (total > (1ll << 28)) return vp_fail(ctx, VP_ERR_INVALID, who);
     const size_t N = (size_t)total;
+    const size_t nfill = fill ? fill->size() : 0;
     auto link = [&](int32_t* nx) {                       // per vertex, the vertex it is joined to (-1: the open end of a polyline)
         size_t o = 0;
         for (int k = 0; k < npolys; k++) {
@@ -271,24 +303,140 @@ int vp_draw_polylines_dev(vp_ctx* ctx, uint8_t* d_img, int w, int h, int cn, con
             o += npts;
         }
     };
-    if (N <= 48) {                                       // a few vertices travel as kernel arguments (vpk_draw_small)
+    if (N <= 48 && nfill <= VP_FILL_SMALL_POLYS) {       // a few vertices travel as kernel arguments (vpk_draw_small)
         int32_t nx[48];
         link(nx);
+        if (nfill) VP_TRY(vpk_fill_polys(ctx, d_img, w, h, cn, pts, (int)N, fill->data(), (int)nfill, fill_rows, color, true));
         return vpk_draw_small(ctx, d_img, w, h, cn, pts, nx, (int)N, thickness, color);
     }
+    const size_t fill_off = vp_align(N * 12, 16), bytes = fill_off + nfill * sizeof(vp_fill_poly);
     int slot = -1;
-    uint8_t* hp = vp_ring_take(ctx, N * 12, &slot);
+    uint8_t* hp = vp_ring_take(ctx, bytes, &slot);
     if (!hp) return vp_fail(ctx, VP_ERR_NOMEM, "pinned staging");
     memcpy(hp, pts, N * 8);
     link(reinterpret_cast<int32_t*>(hp + N * 8));
-    int rc = vp_ws_reserve(ctx, vp_align(N * 12) + 4096);
-    uint8_t* d_buf = rc == VP_OK ? (uint8_t*)vp_ws_take(ctx, N * 12) : nullptr;
+    if (nfill) memcpy(hp + fill_off, fill->data(), nfill * sizeof(vp_fill_poly));
+    int rc = vp_ws_reserve(ctx, vp_align(bytes) + 4096);
+    uint8_t* d_buf = rc == VP_OK ? (uint8_t*)vp_ws_take(ctx, bytes) : nullptr;
     if (rc == VP_OK && !d_buf) rc = vp_fail(ctx, VP_ERR_NOMEM, "workspace exhausted: overlay vertices");
-    if (rc == VP_OK) rc = h2d(ctx, d_buf, hp, N * 12);
+    if (rc == VP_OK) rc = h2d(ctx, d_buf, hp, bytes);
+    if (rc == VP_OK && nfill)
+        rc = vpk_fill_polys(ctx, d_img, w, h, cn, reinterpret_cast<const int32_t*>(d_buf), (int)N, reinterpret_cast<const vp_fill_poly*>(d_buf + fill_off), (int)nfill,
+                            fill_rows, color, false);
     if (rc == VP_OK)
         rc = vpk_draw_segments(ctx, d_img, w, h, cn, reinterpret_cast<const int32_t*>(d_buf), reinterpret_cast<const int32_t*>(d_buf + N * 8), (int)N, thickness, color);
     vp_ring_done(ctx, slot);
     return rc;
+}
+
+int vp_draw_polylines_dev(vp_ctx* ctx, uint8_t* d_img, int w, int h, int cn, const int32_t* pts, const int32_t* counts, int npolys, int closed,
+                          const uint8_t* color, int thickness)
+{
+    VP_TRY(check_ctx(ctx));
+    if (!d_img || !pts || !counts || !color || w <= 0 || h <= 0 || cn < 1 || cn > 4 || npolys < 0) return vp_fail(ctx, VP_ERR_INVALID, "vp_draw_polylines_dev arguments");
+    if (thickness < 1) thickness = 1;
+    if (thickness > 255) return vp_fail(ctx, VP_ERR_UNSUPPORTED, "vp_draw_polylines_dev: thickness");
+    long long total = 0;
+    for (int k = 0; k < npolys; k++) {
+        if (counts[k] < 0) return vp_fail(ctx, VP_ERR_INVALID, "vp_draw_polylines_dev: counts");
+        total += counts[k];
+    }
+    return polylines_dev(ctx, "vp_draw_polylines_dev: too many points", d_img, w, h, cn, pts, counts, npolys, closed, color, thickness, total, nullptr, 0);
+}
+
+// ---- filled polygons, rectangles and discs --------------------------------------------------------------------------------------
+// The checks vp_fill_polys_u8 and vp_fill_polys_dev share (ctx is NULL for the host form): the arguments of the outline entries, then
+// the coordinate bound under which the integer crossings are the float64 crossings of the Python statement.
+static int fill_polys_args(vp_ctx* ctx, const char* who, const void* img, int w, int h, int cn, const int32_t* pts, const int32_t* counts, int npolys,
+                           const uint8_t* color, long long* total)
+{
+    if (!img || !pts || !counts || !color || w <= 0 || h <= 0 || cn < 1 || cn > 4 || npolys < 0) return vp_fail(ctx, VP_ERR_INVALID, who);
+    long long n = 0;
+    for (int k = 0; k < npolys; k++) {
+        if (counts[k] < 0) return vp_fail(ctx, VP_ERR_INVALID, who);
+        n += counts[k];
+    }
+    if (n > (1ll << 28)) return vp_fail(ctx, VP_ERR_INVALID, who);
+    for (long long i = 0; i < 2 * n; i++)
+        if (pts[i] > VP_FILL_MAX_COORD || pts[i] < -VP_FILL_MAX_COORD) return vp_fail(ctx, VP_ERR_UNSUPPORTED, "filled polygon: a coordinate beyond VP_FILL_MAX_COORD");
+    *total = n;
+    return VP_OK;
+}
+
+int vp_fill_polys_u8(uint8_t* img, size_t stride, int w, int h, int cn, const int32_t* pts, const int32_t* counts, int npolys, const uint8_t* color)
+{
+    long long total = 0;
+    VP_TRY(fill_polys_args(nullptr, "vp_fill_polys_u8 arguments", img, w, h, cn, pts, counts, npolys, color, &total));
+    if (stride < (size_t)w * cn) return vp_fail(nullptr, VP_ERR_INVALID, "vp_fill_polys_u8 arguments");
+    return raster_polys_u8(img, stride, w, h, cn, pts, counts, npolys, 1, color, 1, true);
+}
+
+int vp_fill_polys_dev(vp_ctx* ctx, uint8_t* d_img, int w, int h, int cn, const int32_t* pts, const int32_t* counts, int npolys, const uint8_t* color)
+{
+    VP_TRY(check_ctx(ctx));
+    long long total = 0;
+    VP_TRY(fill_polys_args(ctx, "vp_fill_polys_dev arguments", d_img, w, h, cn, pts, counts, npolys, color, &total));
+    // per polygon its clipped rows, and the crossings of every one of them counted here (an edge adds one to each row from its upper end
+    // to just above its lower end: a difference array), so that a row the kernel could not sort is known before anything is enqueued
+    static thread_local std::vector<vp_fill_poly> polys;
+    static thread_local std::vector<int> diff;
+    polys.clear();
+    long long rows = 0;
+    size_t o = 0;
+    for (int k = 0; k < npolys; k++) {
+        const int n = counts[k];
+        const int32_t* p = pts + 2 * o;
+        const size_t first = o;
+        o += (size_t)n;
+        if (n < 2) continue;
+        int ymin = p[1], ymax = p[1];
+        for (int i = 1; i < n; i++) { ymin = std::min(ymin, p[2 * i + 1]); ymax = std::max(ymax, p[2 * i + 1]); }
+        const int y0 = std::max(ymin, 0), y1 = std::min(ymax, h - 1);
+        if (y0 > y1 || ymin == ymax) continue;
+        diff.assign((size_t)(y1 - y0 + 2), 0);
+        for (int i = 0; i < n; i++) {
+            int lo, hi;
+            if (!vp_fill_edge_rows(p[2 * i + 1], p[2 * (i + 1 == n ? 0 : i + 1) + 1], &lo, &hi)) continue;
+            lo = std::max(lo, y0); hi = std::min(hi, y1 + 1);
+            if (lo < hi) { diff[(size_t)(lo - y0)]++; diff[(size_t)(hi - y0)]--; }
+        }
+        int run = 0;
+        for (int y = y0; y <= y1; y++) {
+            run += diff[(size_t)(y - y0)];
+            if (run > VP_FILL_MAX_CROSS) return vp_fail(ctx, VP_ERR_CAPACITY, "vp_fill_polys_dev: a row with more than VP_FILL_MAX_CROSS crossings");
+        }
+        polys.push_back(vp_fill_poly{(int32_t)first, n, y0, y1 - y0 + 1, (int32_t)rows});
+        rows += y1 - y0 + 1;
+        if (rows > (1ll << 30)) return vp_fail(ctx, VP_ERR_UNSUPPORTED, "vp_fill_polys_dev: too many rows");
+    }
+    return polylines_dev(ctx, "vp_fill_polys_dev arguments", d_img, w, h, cn, pts, counts, npolys, 1, color, 1, total, &polys, (int)rows);
+}
+
+// draw_rect / draw_circle with a negative thickness (vision/utils/draw.py): the numpy slices, written by the device
+static int fill_shape_args(vp_ctx* ctx, const char* who, const void* img, int w, int h, int cn, const uint8_t* color, int a, int b, int c, int d)
+{
+    if (!img || !color || w <= 0 || h <= 0 || cn < 1 || cn > 4) return vp_fail(ctx, VP_ERR_INVALID, who);
+    const int lim = 1 << 20;
+    if (a > lim || a < -lim || b > lim || b < -lim || c > lim || c < -lim || d > lim || d < -lim) return vp_fail(ctx, VP_ERR_UNSUPPORTED, "filled shape: a coordinate beyond 2^20");
+    return VP_OK;
+}
+
+int vp_fill_rect_dev(vp_ctx* ctx, uint8_t* d_img, int w, int h, int cn, int x0, int y0, int x1, int y1, const uint8_t* color)
+{
+    VP_TRY(check_ctx(ctx));
+    VP_TRY(fill_shape_args(ctx, "vp_fill_rect_dev arguments", d_img, w, h, cn, color, x0, y0, x1, y1));
+    const int xa = std::max(std::min(x0, x1), 0), xb = std::min(std::max(x0, x1), w - 1);
+    const int ya = std::max(std::min(y0, y1), 0), yb = std::min(std::max(y0, y1), h - 1);
+    if (xa > xb || ya > yb) return VP_OK;
+    return vpk_fill_rect(ctx, d_img, w, h, cn, xa, xb, ya, yb, color);
+}
+
+int vp_fill_circle_dev(vp_ctx* ctx, uint8_t* d_img, int w, int h, int cn, int cx, int cy, int radius, const uint8_t* color)
+{
+    VP_TRY(check_ctx(ctx));
+    VP_TRY(fill_shape_args(ctx, "vp_fill_circle_dev arguments", d_img, w, h, cn, color, cx, cy, radius, 0));
+    if (radius < 0) return VP_OK;
+    return vpk_fill_disc(ctx, d_img, w, h, cn, cx, cy, radius, color);
 }
 
 // cv2.addWeighted on two device images of n bytes each (modules/bins.py:20: the mask overlay); d_dst may be one of the sources

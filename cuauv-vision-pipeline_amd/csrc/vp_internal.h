@@ -220,6 +220,51 @@ int vpk_draw_segments(vp_ctx* ctx, uint8_t* d_img, int w, int h, int cn, const i
 int vpk_add_weighted_u8(vp_ctx* ctx, const uint8_t* a, const uint8_t* b, size_t n, double alpha, double beta, double gamma, uint8_t* dst);
 int vpk_absdiff_sub_u8(vp_ctx* ctx, const uint8_t* a, const uint8_t* b, size_t n, uint8_t* dst);  // a - b saturating
 
+// ---- filled shapes (vp_fill.hip) ------------------------------------------------------------------
+// Even-odd scanline fill of vision/utils/draw.py _fill.  Where edge (a, b) meets row y (min(ya, yb) <= y < max(ya, yb)) the crossing
+// xa + (y - ya) (xb - xa) / (yb - ya) is kept as an exact 64-bit key: floor(crossing) + 32768 in the high word, floor(2^32 frac) in the
+// low one.  For coordinates within VP_FILL_MAX_COORD two different fractions differ by more than 2^-32, so the keys order exactly as
+// the rationals do, equal crossings have equal keys, and floor / ceil are read off the key (tests/fill_restate.py).
+#define VP_FILL_MAX_CROSS 256      // crossings per row the device kernel sorts (LDS); the host form has no limit
+__host__ __device__ static inline u64 vp_fill_cross_key(int xa, int ya, int xb, int yb, int y)
+{
+    int den = yb - ya;
+    long long num = (long long)(y - ya) * (xb - xa);
+    if (den < 0) { den = -den; num = -num; }
+    const u32 mag = (u32)(num < 0 ? -num : num), d = (u32)den;
+    u32 q = mag / d, r = mag - q * d;
+    int fl = (int)q;
+    if (num < 0) { fl = r ? -(int)q - 1 : -(int)q; r = r ? d - r : 0; }
+    return ((u64)(u32)(xa + fl + 32768) << 32) | (u32)(((u64)r << 32) / d);
+}
+// the rows edge (a, b) counts on, [*lo, *hi): from its upper end to just above its lower end; false for a horizontal edge.  The kernel's
+// edge test, the host form's sweep and the host count of crossings per row (vp_fill_polys_dev) all go through these two.
+static inline __host__ __device__ bool vp_fill_edge_rows(int ya, int yb, int* lo, int* hi)
+{
+    *lo = ya < yb ? ya : yb;
+    *hi = ya < yb ? yb : ya;
+    return ya != yb;
+}
+static inline __host__ __device__ bool vp_fill_edge_on_row(int ya, int yb, int y)
+{
+    int lo, hi;
+    return vp_fill_edge_rows(ya, yb, &lo, &hi) && lo <= y && y < hi;
+}
+static inline __host__ __device__ int vp_fill_key_floor(u64 key) { return (int)(key >> 32) - 32768; }
+static inline __host__ __device__ int vp_fill_key_ceil(u64 key) { return (int)(key >> 32) - 32768 + ((u32)key != 0); }
+// vertices [first, first + count) of the point list; image rows y0 .. y0 + rows - 1 (the bounding box, clipped, rows > 0); row_base: the
+// rows of the polygons before it in the list
+struct vp_fill_poly { int32_t first, count, y0, rows, row_base; };
+#define VP_FILL_SMALL_POLYS 8
+// one wave per (polygon, row).  on_host: pts (npts <= 48 points) and polys (<= VP_FILL_SMALL_POLYS) are host arrays and travel as kernel
+// arguments; otherwise both are device arrays.  The caller has made sure that no row has more than VP_FILL_MAX_CROSS crossings.
+int vpk_fill_polys(vp_ctx* ctx, uint8_t* d_img, int w, int h, int cn, const int32_t* pts, int npts, const vp_fill_poly* polys, int npolys, int total_rows,
+                   const uint8_t* color, bool on_host);
+// columns xa .. xb of rows ya .. yb, all inside the image
+int vpk_fill_rect(vp_ctx* ctx, uint8_t* d_img, int w, int h, int cn, int xa, int xb, int ya, int yb, const uint8_t* color);
+// row cy + dy gets columns cx - dx .. cx + dx, dx = floor(sqrt(r r - dy dy)) as an exact integer root, clipped; r >= 0
+int vpk_fill_disc(vp_ctx* ctx, uint8_t* d_img, int w, int h, int cn, int cx, int cy, int r, const uint8_t* color);
+
 // ---- element-wise operators (vp_elementwise.hip) ------------------------------------------------
 // packed uint8 images of n bytes; dst may be one of the sources of the first three.  b == nullptr: the second operand is `scalar`;
 // mask (nullable): one byte per pixel of cn channels; d_bits (nullable): the result's bit plane as vpk_inrange_u8 leaves it, for a

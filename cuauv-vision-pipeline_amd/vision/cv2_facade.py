@@ -919,10 +919,55 @@ def threshold(src, thresh, maxval, type, dst=None):
     return thresh, _into(dst, _color._threshold(src, thresh, maxval, kind & THRESH_MASK))
 
 
+FILLED = -1
+
+
 def drawContours(image, contours, contourIdx, color, thickness=1):
+    """cv2.drawContours: every contour (contourIdx < 0) or the one named; a negative thickness (FILLED) fills each contour by the
+    even-odd scanline of vision.utils.draw and outlines it."""
     sel = contours if contourIdx < 0 else [contours[contourIdx]]
     _draw.draw_contours(image, [np.asarray(c) for c in sel], color, thickness)
     return image
+
+
+def fillPoly(img, pts, color):
+    """cv2.fillPoly(img, pts, color) for a list of integer polygons.  Statement of this stand-in (tests/fill_restate.py fill_poly_restate):
+    every polygon is filled on its own by the even-odd scanline and outlined, and the image is the union - not one scanline over the
+    edges of all polygons together, which cv2 runs: where two polygons of one call overlap, cv2 leaves the overlap unpainted and this
+    paints it.  For polygons that do not overlap (and for a single one) the two readings coincide."""
+    _draw.draw_contours(img, [np.asarray(p) for p in pts], color, FILLED)
+    return img
+
+
+def fillConvexPoly(img, points, color):
+    """cv2.fillConvexPoly: one polygon through the same fill (which does not need it to be convex)."""
+    _draw.draw_contours(img, [np.asarray(points)], color, FILLED)
+    return img
+
+
+def boundingRect(array):
+    """cv2.boundingRect of integer points: (xmin, ymin, xmax - xmin + 1, ymax - ymin + 1); (0, 0, 0, 0) without points."""
+    p = np.asarray(array)
+    if not np.issubdtype(p.dtype, np.integer) or (p.size and p.shape[-1] != 2):
+        raise error("boundingRect: integer points only on this path")
+    p = p.reshape(-1, 2)
+    if len(p) == 0:
+        return (0, 0, 0, 0)
+    x0, y0 = (int(v) for v in p.min(axis=0))
+    x1, y1 = (int(v) for v in p.max(axis=0))
+    return (x0, y0, x1 - x0 + 1, y1 - y0 + 1)
+
+
+def convexHull(points, hull=None, clockwise=False, returnPoints=True):
+    """cv2.convexHull with returnPoints=True: the hull vertices as an (k, 1, 2) array of the input's dtype.  The vertex SET is cv2's
+    (collinear points dropped); the start vertex and the orientation are those of the monotone chain (counter-clockwise from the
+    smallest point), not pinned to cv2's, and `clockwise` is not honoured - contourArea of the result, which is all fill_ratio
+    (vision_common.py:286) takes, does not depend on either."""
+    if not returnPoints:
+        raise error("convexHull: returnPoints=False is outside this path")
+    p = np.asarray(points)
+    out = _convex_hull(p).reshape(-1, 1, 2)
+    return out.astype(p.dtype if p.dtype.kind in "iuf" else np.float64)
 
 
 def install():

@@ -1,7 +1,8 @@
 """Minimal stand-in for the reference utils/draw.py (debug overlays; not part of the accelerated path).
 Only what the in-scope modules call: `draw_contours` (modules/red_buoy.py:39) and `draw_polylines`, as plain numpy
 rasterisation (lines between consecutive contour points, square brush of the requested thickness; -1 fills by even-odd
-scanline).  Pixel-exact agreement with cv2's anti-alias-free line drawing is not claimed."""
+scanline).  Pixel-exact agreement with cv2's anti-alias-free line drawing is not claimed.  The Python loops are the statement; libvp
+draws the same pixels into numpy images (host C) and into images that live on the device (kernels), outlines and fills alike."""
 from enum import Enum
 from typing import List, Tuple
 
@@ -96,21 +97,13 @@ def _native_polylines(mat, polys, closed, color, thickness):
         lib = _vp.lib()
     except Exception:
         return False
-    flat = getattr(polys, "_flat", None)
-    if flat is not None:                            # the tuple find_contours returned: its arrays are views of this one block
-        if len(polys) == 0:
-            return True
-        counts, p32 = polys._counts, flat
-    else:
-        polys = [np.asarray(p).reshape(-1, 2) for p in polys]
-        if not polys:
-            return True
-        counts = np.fromiter((len(p) for p in polys), np.int32, len(polys))
-        p32 = np.ascontiguousarray(np.concatenate(polys) if len(polys) > 1 else polys[0], np.int32)
-    col = np.zeros(4, np.uint8)
-    col[:cn] = np.asarray(color, np.uint8).ravel()[:cn] if np.ndim(color) else np.uint8(color)
+    packed = _packed(polys)
+    if packed is None:
+        return True
+    counts, p32 = packed
+    col = _color_bytes(color, cn)
     return lib.vp_draw_polylines_u8(mat.ctypes.data, mat.strides[0], mat.shape[1], mat.shape[0], cn, p32.ctypes.data, counts.ctypes.data,
-                                    len(polys), int(bool(closed)), col.ctypes.data, int(thickness)) == 0
+                                    len(counts), int(bool(closed)), col.ctypes.data, int(thickness)) == 0
 
 
 def _device_polylines(mat, polys, closed, color, thickness):
@@ -124,23 +117,123 @@ def _device_polylines(mat, polys, closed, color, thickness):
     cn = 1 if mat.ndim == 2 else mat.shape[2]
     if cn > 4 or not mat.device_valid_for(ctx):
         return False
-    flat = getattr(polys, "_flat", None)
-    if flat is not None:
-        if len(polys) == 0:
-            return True
-        counts, p32 = polys._counts, flat
-    else:
-        polys = [np.asarray(p).reshape(-1, 2) for p in polys]
-        if not polys:
-            return True
-        counts = np.fromiter((len(p) for p in polys), np.int32, len(polys))
-        p32 = np.ascontiguousarray(np.concatenate(polys) if len(polys) > 1 else polys[0], np.int32)
-    col = np.zeros(4, np.uint8)
-    col[:cn] = np.asarray(color, np.uint8).ravel()[:cn] if np.ndim(color) else np.uint8(color)
-    mat._before_write()                                  # operators that were deferred on this image read it as it is now
-    _vp.check(_vp.lib().vp_draw_polylines_dev(ctx.handle, mat.dev_ptr, mat.shape[1], mat.shape[0], cn, p32.ctypes.data, counts.ctypes.data, len(counts),
+    packed = _packed(polys)
+    if packed is None:
+        return True
+    counts, p32 = packed
+    col = _color_bytes(color, cn)
+    img = _write_target(mat)
+    _vp.check(_vp.lib().vp_draw_polylines_dev(ctx.handle, img, mat.shape[1], mat.shape[0], cn, p32.ctypes.data, counts.ctypes.data, len(counts),
                                               int(bool(closed)), col.ctypes.data, int(thickness)), ctx.handle)
     mat.binary = False
+    return True
+
+
+def _packed(polys):
+    """(counts, points) of a list of polygons as the int32 arrays libvp takes, or None for an empty list."""
+    flat = getattr(polys, "_flat", None)
+    if flat is not None:                            # the tuple find_contours returned: its arrays are views of this one block
+        return (polys._counts, flat) if len(polys) else None
+    polys = [np.asarray(p).reshape(-1, 2) for p in polys]
+    if not polys:
+        return None
+    counts = np.fromiter((len(p) for p in polys), np.int32, len(polys))
+    return counts, np.ascontiguousarray(np.concatenate(polys) if len(polys) > 1 else polys[0], np.int32)
+
+
+def _color_bytes(color, cn):
+    col = np.zeros(4, np.uint8)
+    col[:cn] = np.asarray(color, np.uint8).ravel()[:cn] if np.ndim(color) else np.uint8(color)
+    return col
+
+
+
+
+def _native_fill(mat, polys, color):
+    """Every polygon filled (even-odd scanline, `_fill`) and outlined at thickness 1 by libvp vp_fill_polys_u8 (host code), the same
+    pixels: returns False when the image cannot be handed over as is or a coordinate lies beyond +-32767 - nothing is painted then."""
+    if not (isinstance(mat, np.ndarray) and mat.dtype == np.uint8 and mat.ndim in (2, 3) and mat.flags.writeable):
+        return False
+    cn = 1 if mat.ndim == 2 else mat.shape[2]
+    if cn > 4 or mat.strides[-1] != 1 or (mat.ndim == 3 and mat.strides[1] != cn) or mat.strides[0] < mat.shape[1] * cn:
+        return False
+    try:
+        from vision import _vp
+        lib = _vp.lib()
+    except Exception:
+        return False
+    packed = _packed(polys)
+    if packed is None:
+        return True
+    counts, p32 = packed
+    col = _color_bytes(color, cn)
+    return lib.vp_fill_polys_u8(mat.ctypes.data, mat.strides[0], mat.shape[1], mat.shape[0], cn, p32.ctypes.data, counts.ctypes.data, len(counts), col.ctypes.data) == _vp.OK
+
+
+def _device_only(mat):
+    """(context, channels) when `mat` is a uint8 image that lives on the device and has no host copy, else None."""
+    from vision.devmat import DeviceMat
+    if not isinstance(mat, DeviceMat) or mat.dtype != np.uint8 or mat.ndim not in (2, 3) or mat._host is not None:
+        return None
+    from vision import _vp
+    ctx = _vp.default_context()
+    cn = 1 if mat.ndim == 2 else mat.shape[2]
+    if cn > 4 or not mat.device_valid_for(ctx):
+        return None
+    return ctx, cn
+
+
+def _write_target(mat):
+    """Device address of an image about to be written in place.  An image that is itself a pending operator result is computed first -
+    its launch may hand it a bit plane - and only then are the operators that read it run and the bit plane, which describes the
+    contents before the write, dropped."""
+    ptr = mat.dev_ptr
+    mat._before_write()
+    return ptr
+
+
+def _painted(mat, cn, col, was_binary):
+    """After a device write of one colour: a 0/255 mask painted with 0 or 255 is still one."""
+    mat.binary = bool(was_binary and cn == 1 and int(col[0]) in (0, 255))
+
+
+def _device_fill(mat, polys, color):
+    """The same fill by the device into an image that lives there and has no host copy (libvp vp_fill_polys_dev): returns False when the
+    image is not of that kind, a coordinate lies beyond +-32767 or a row has more crossings than the kernel sorts - nothing has been
+    painted then, and it is drawn on the host."""
+    where = _device_only(mat)
+    if where is None:
+        return False
+    ctx, cn = where
+    from vision import _vp
+    packed = _packed(polys)
+    if packed is None:
+        return True
+    counts, p32 = packed
+    col = _color_bytes(color, cn)
+    was_binary = mat.binary
+    img = _write_target(mat)
+    rc = _vp.lib().vp_fill_polys_dev(ctx.handle, img, mat.shape[1], mat.shape[0], cn, p32.ctypes.data, counts.ctypes.data, len(counts), col.ctypes.data)
+    if rc in (_vp.ERR_UNSUPPORTED, _vp.ERR_CAPACITY):   # a coordinate beyond +-32767; a row with too many crossings: nothing was painted
+        return False
+    _vp.check(rc, ctx.handle)
+    _painted(mat, cn, col, was_binary)
+    return True
+
+
+def _device_shape(mat, entry, color, *geometry):
+    """draw_rect / draw_circle with a negative thickness on an image that lives on the device and has no host copy (libvp
+    vp_fill_rect_dev / vp_fill_circle_dev): False when the image is not of that kind or the geometry is beyond the entry's range."""
+    where = _device_only(mat)
+    if where is None or any(abs(int(v)) > (1 << 20) for v in geometry):
+        return False
+    ctx, cn = where
+    from vision import _vp
+    col = _color_bytes(color, cn)
+    was_binary = mat.binary
+    img = _write_target(mat)
+    _vp.check(getattr(_vp.lib(), entry)(ctx.handle, img, mat.shape[1], mat.shape[0], cn, *(int(v) for v in geometry), col.ctypes.data), ctx.handle)
+    _painted(mat, cn, col, was_binary)
     return True
 
 
@@ -156,10 +249,14 @@ def draw_polylines(mat: np.ndarray, points, isClosed: bool = False, color: Tuple
         return
     if thickness >= 0 and _device_polylines(mat, [pts], isClosed, color, max(thickness, 1)):
         return
+    if thickness < 0 and isClosed and _device_fill(mat, [pts], color):
+        return
     mat = to_host(mat)
     if thickness >= 0 and _native_polyline(mat, pts, isClosed, color, max(thickness, 1)):
         return
-    color = np.asarray(color, mat.dtype)[: (mat.shape[2] if mat.ndim == 3 else 1)]
+    if thickness < 0 and isClosed and _native_fill(mat, [pts], color):
+        return
+    color = np.asarray(color, mat.dtype).ravel()[: (mat.shape[2] if mat.ndim == 3 else 1)]
     if mat.ndim == 2:
         color = color[0]
     if thickness < 0:
@@ -177,8 +274,12 @@ def draw_contours(mat: np.ndarray, contours: List[np.ndarray], color: Tuple[int,
     from vision.devmat import to_host
     if thickness >= 0 and _device_polylines(mat, contours, True, color, max(thickness, 1)):
         return
+    if thickness < 0 and _device_fill(mat, contours, color):
+        return
     mat = to_host(mat)
     if thickness >= 0 and _native_polylines(mat, contours, True, color, max(thickness, 1)):
+        return
+    if thickness < 0 and _native_fill(mat, contours, color):
         return
     for c in contours:
         draw_polylines(mat, c, True, color, thickness)
@@ -193,6 +294,8 @@ def draw_rect(mat: np.ndarray, pt1: Tuple[int, int], pt2: Tuple[int, int], color
     """utils/draw.py:147-168 (cv2.rectangle): in place; negative thickness fills."""
     (x0, y0), (x1, y1) = (int(pt1[0]), int(pt1[1])), (int(pt2[0]), int(pt2[1]))
     if thickness < 0:
+        if _device_shape(mat, "vp_fill_rect_dev", color, x0, y0, x1, y1):
+            return
         h, w = mat.shape[:2]
         xa, xb = max(min(x0, x1), 0), min(max(x0, x1), w - 1)
         ya, yb = max(min(y0, y1), 0), min(max(y0, y1), h - 1)
@@ -210,6 +313,8 @@ def draw_circle(mat: np.ndarray, center: Tuple[int, int], radius: int, color: Tu
     if r < 0:
         return
     if thickness < 0:
+        if _device_shape(mat, "vp_fill_circle_dev", color, cx, cy, r):
+            return
         for dy in range(-r, r + 1):
             y = cy + dy
             if 0 <= y < h:

@@ -213,6 +213,50 @@ def min_enclosing_rect(contour: np.ndarray):
     return cv2_facade.minAreaRect(contour)
 
 
+def contour_center(contour: np.ndarray) -> Tuple[float, float]:
+    """vision_common.py:290-292: (m10 / m00, m01 / m00) of cv2.moments, unclamped and unrounded - a contour without area divides by
+    zero, as it does there."""
+    m00, m10, m01 = _polygon_moments(contour)
+    return (m10 / m00, m01 / m00)
+
+
+def is_clipping(mat, contour) -> bool:
+    """vision_common.py:271-280: whether the contour's bounding rectangle comes within 5 pixels of an edge of the view."""
+    from vision import cv2_facade
+    cam_height, cam_width = mat.shape[:2]
+    distance = 5
+    x, y, w, h = cv2_facade.boundingRect(contour)
+    return bool(x <= distance or y <= distance or cam_width - w - x <= distance or cam_height - h - y <= distance)
+
+
+def fill_ratio(mat, contour, threshed):
+    """vision_common.py:282-288: the share of the contour's convex-hull area that is set in `threshed` inside the filled contour -
+    drawContours(mask, [contour], -1, 255, thickness=-1), bitwise_and(threshed, threshed, mask=mask), sum / 255 / hull area.
+    With `threshed` on the device the mask is made, filled and applied there and one number comes back: the non-zero count
+    (vp_count_nonzero_u8_dev) when `threshed` is known to hold only 0 / 255 - sum / 255 is that count then - and otherwise the host sum
+    of the masked image, as in the reference."""
+    from vision import cv2_facade as cv
+    from vision.devmat import lazy_enabled
+    from vision.utils import draw
+    shape = tuple(int(v) for v in mat.shape[:2])
+    hull_area = cv.contourArea(cv.convexHull(contour))
+    threshed = as_mat(threshed)
+    if isinstance(threshed, DeviceMat) and threshed.dtype == np.uint8 and lazy_enabled() and 0 not in shape:
+        ctx = _vp.default_context()
+        fill_mask = DeviceMat(ctx, shape, binary=True)
+        zero = np.zeros(4, np.uint8)
+        _vp.check(_vp.lib().vp_fill_rect_dev(ctx.handle, fill_mask.dev_ptr, shape[1], shape[0], 1, 0, 0, shape[1] - 1, shape[0] - 1, zero.ctypes.data), ctx.handle)
+        draw.draw_contours(fill_mask, [np.asarray(contour)], 255, -1)
+        fill_masked = cv.bitwise_and(threshed, threshed, mask=fill_mask)
+        if threshed.binary:
+            return np.float64(cv.countNonZero(fill_masked)) / hull_area
+        return np.sum(to_host_readonly(fill_masked)) / 255 / hull_area
+    fill_mask = np.zeros(shape, dtype=np.uint8)
+    cv.drawContours(fill_mask, [contour], -1, 255, thickness=-1)
+    fill_masked = cv.bitwise_and(to_host_readonly(threshed), to_host_readonly(threshed), mask=fill_mask)
+    return np.sum(to_host_readonly(fill_masked)) / 255 / hull_area
+
+
 def _outside_path(name):
     def _f(*_a, **_k):
         raise NotImplementedError(f"{name}: outside the accelerated path of this build")

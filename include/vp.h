@@ -29,6 +29,7 @@ extern "C" {
 #define VP_ERR_HIP (-2)         /* HIP runtime error / no device; see vp_last_error() */
 #define VP_ERR_NOMEM (-3)       /* device or host allocation failed */
 #define VP_ERR_UNSUPPORTED (-4) /* valid request outside what the kernels cover */
+#define VP_ERR_CAPACITY (-5)    /* the input exceeds a fixed capacity of the device path; nothing was written (vp_fill_polys_dev) */
 
 typedef struct vp_ctx vp_ctx;
 
@@ -224,6 +225,17 @@ int vp_draw_polyline_u8(uint8_t* img_host, size_t stride, int w, int h, int cn, 
 int vp_draw_polylines_u8(uint8_t* img_host, size_t stride, int w, int h, int cn, const int32_t* pts, const int32_t* counts, int npolys,
                          int closed, const uint8_t* color, int thickness);
 
+/* utils/draw.py `draw_contours` / `draw_polylines` with a negative thickness (cv2.drawContours(mask, [contour], -1, 255, thickness=-1)
+ * of vision_common.py:282-288 `fill_ratio`): every polygon filled by the even-odd scanline of the Python mirror, then outlined, closed,
+ * at thickness 1 - the same pixels, on a HOST image.  Rows max(ymin, 0) .. min(ymax, h - 1); edge (a, b) counts on row y when
+ * min(ya, yb) <= y < max(ya, yb) and crosses it at xa + (y - ya)(xb - xa)/(yb - ya); the sorted crossings pair up and pair (p, q) paints
+ * [ceil(p), floor(q)], clipped.  The crossings are exact integers here and float64 in Python: the two agree when every coordinate lies
+ * within +-VP_FILL_MAX_COORD (distinct crossings then differ by at least 2^-32, the float64 error is below 2^-36), and a polygon with a
+ * coordinate beyond that is refused with VP_ERR_UNSUPPORTED.  Any number of crossings per row. */
+#define VP_FILL_MAX_COORD 32767
+int vp_fill_polys_u8(uint8_t* img_host, size_t stride, int w, int h, int cn, const int32_t* pts, const int32_t* counts, int npolys,
+                     const uint8_t* color);
+
 /* ---- device-resident forms of the per-operator entry points ----------------------------- *
  * Same arithmetic and argument meaning as vp_cvt_color_u8 / vp_inrange_u8 / vp_morph_u8 / vp_find_contours_u8; images are
  * device pointers.  Nothing is copied; the first three enqueue on the context's stream and return without synchronising, so a
@@ -251,6 +263,17 @@ int vp_morph_u8_dev(vp_ctx* ctx, int op, const uint8_t* src_dev, int w, int h, i
  * that an overlay which is only posted (modules/bins.py:20-79) never has to visit the host. */
 int vp_draw_polylines_dev(vp_ctx* ctx, uint8_t* img_dev, int w, int h, int cn, const int32_t* pts, const int32_t* counts, int npolys,
                           int closed, const uint8_t* color, int thickness);
+/* vp_fill_polys_u8 into a packed device image, enqueued on the context's stream (points and counts are host arrays): the same pixels and
+ * the same checks.  The kernel sorts at most 256 crossings per row: when some row of some polygon has more, VP_ERR_CAPACITY comes back
+ * and nothing has been painted (the caller fills on the host). */
+int vp_fill_polys_dev(vp_ctx* ctx, uint8_t* img_dev, int w, int h, int cn, const int32_t* pts, const int32_t* counts, int npolys,
+                      const uint8_t* color);
+/* utils/draw.py `draw_rect` / `draw_circle` with a negative thickness on a packed device image, enqueued: columns min(x0, x1) ..
+ * max(x0, x1) of rows min(y0, y1) .. max(y0, y1); row cy + dy of the disc spans cx -+ floor(sqrt(r r - dy dy)), the root an exact
+ * integer one; both clipped to the image, a negative radius paints nothing.  Coordinates and radius within +-2^20
+ * (VP_ERR_UNSUPPORTED beyond). */
+int vp_fill_rect_dev(vp_ctx* ctx, uint8_t* img_dev, int w, int h, int cn, int x0, int y0, int x1, int y1, const uint8_t* color);
+int vp_fill_circle_dev(vp_ctx* ctx, uint8_t* img_dev, int w, int h, int cn, int cx, int cy, int radius, const uint8_t* color);
 /* cv2.addWeighted(a, alpha, b, beta, gamma) on two device images of n bytes (modules/bins.py:20, the mask overlay):
  * saturate(round-half-even(a*alpha + b*beta + gamma)) in correctly rounded doubles; dst may be one of the sources. */
 int vp_add_weighted_u8_dev(vp_ctx* ctx, const uint8_t* a_dev, double alpha, const uint8_t* b_dev, double beta, double gamma, size_t n,
