@@ -177,7 +177,11 @@ int vp_destroy(vp_ctx* ctx)
 int vp_set_stream(vp_ctx* ctx, void* hip_stream)
 {
     if (!ctx) return VP_ERR_INVALID;
-    ctx->stream = hip_stream ? (hipStream_t)hip_stream : ctx->own_stream;
+    hipStream_t s = hip_stream ? (hipStream_t)hip_stream : ctx->own_stream;
+    // The labelling's accumulator set is kept clean in the order of one stream: another stream starts it anew.  (As for every buffer of
+    // the context, the caller has let the old stream's work finish, or ordered the new stream behind it, before using the new one.)
+    if (s != ctx->stream) ctx->c3_acc_dirty = 1;
+    ctx->stream = s;
     return VP_OK;
 }
 void* vp_get_stream(vp_ctx* ctx) { return ctx ? (void*)ctx->stream : nullptr; }

@@ -66,14 +66,9 @@ struct c2_box { int minx, maxx, miny, maxy; };
 
 size_t vp_ccl_nids(int w, int h)
 {
-    const size_t wb = (size_t)(w + 1) / 2, hb = (size_t)(h + 1) / 2;
-    return (2 * hb * wb + 127) / 128 * 128;
+    return ccl_nids(w, h);
 }
 
-// strips of the strip-local pass never exceed h / 8 + 1 (ccl_make_geom picks 8, 16 or 32 rows)
-static size_t c2_strips_max(int h) { return (size_t)(h + 7) / 8; }
-static size_t c3_strips_cap(int h) { return (size_t)(h + 1) / 2 + 2; }   // vp_ccl3.inl: strips of at least 2 rows, + 1 boundary slot
-#define C3_STATE_BYTES 48
 // which of the two labelling launches takes a strip (vp_ccl3.inl): one byte per (frame, strip)
 static size_t c3_items_bytes(int n, int h) { return (size_t)n * c3_strips_cap(h); }
 
@@ -531,7 +526,6 @@ __global__ __launch_bounds__(256) void k_ccl_final(const ccl_acc* __restrict__ a
 // the dense wordlabel array; only words holding several segments go to the sparse seglabel array.
 // launch bound 8 waves per SIMD: the compiler otherwise takes 74 VGPRs (6 waves); at 62 VGPRs and full occupancy the kernel streams at
 // 5.8 instead of 5.2 TB/s (188 instead of 208 us per 128 frames)
-#define WR_ROWS 4
 #define WR_K 8
 __global__ __launch_bounds__(256, 8) void k_ccl_write(const u64* __restrict__ bits, ccl_geom G, const u32* __restrict__ seglabel,
                                                    const u32* __restrict__ wordlabel, int32_t* __restrict__ labels, u32 total_rows,
@@ -609,35 +603,18 @@ __global__ __launch_bounds__(256, 8) void k_ccl_write(const u64* __restrict__ bi
     }
 }
 
-static void ccl_make_geom(ccl_geom& G, int w, int h, int numbering, int invert, int conn4)
-{
-    G.w = w; G.h = h; G.ww = vp_ww(w); G.wb = (w + 1) / 2; G.numbering = numbering;
-    G.nids = (u32)vp_ccl_nids(w, h);
-    G.nw32 = G.nids / 32;
-    G.invert = invert; G.conn4 = conn4;
-    // Strip height of the strip-local pass.  A block's time grows faster than its strip (64 rows: 75 us, 32: 53 us at 1080p), and
-    // wide rows make strips heavy: at 4K (60 words per row) 16-row strips take k_ccl_local from 116 to 44 us for +4 us of
-    // boundary unions; at 1080p the two cancel.  16 rows need ceil(w/2) even (bitmap slices must not share a word).
-    G.rows = (G.ww > 32 && (G.wb % 2) == 0) ? 16 : 32;
-    if (const char* e = getenv("VP_CL_ROWS")) { const int r = atoi(e); if ((r == 8 || r == 16 || r == 32) && ((u32)r * (u32)G.wb) % 32u == 0) G.rows = r; }
-}
-
+#ifdef VP_PROBE
+static __device__ int vp_dbg_bits;   // the VP_DBG switches of this unit's kernels
+static int g_dbg_bits_host;          // what vp_debug_set last set
+#endif
 #include "vp_ccl3.inl"
 #include "vp_ccl2.inl"
 
-// LDS of the strip-local kernels: lbits | wbase | lparent | lgid (| lmin when it cannot share wbase's words)
-static size_t ccl_local_lds(const ccl_geom& G, size_t& cap)
+// what the environment tunes of the plan and the grids (vp_ccl_plan.h), read on first use
+static const ccl_tuning& ccl_env_tuning()
 {
-    const size_t nwmax = (size_t)G.rows * G.ww;
-    // Foreground: room for one segment per word of the strip (a full mask) + 2, the size of the wbase array whose LDS lmin then
-    // reuses; denser strips (speckle) take the global fallback.  Background pass of the contour code: every empty word is a
-    // segment and every foreground edge adds one, so it gets its own lmin array and 1024 more entries.
-    static const char* cap_env = getenv("VP_CL_CAP");
-    cap = G.invert ? nwmax + 1024 : nwmax + 2;
-    if (cap_env && (size_t)atoi(cap_env) >= 64 && (size_t)atoi(cap_env) < cap) cap = (size_t)atoi(cap_env);
-    size_t lds_local = nwmax * 8 + (nwmax + 2) * 4 + (cap <= nwmax + 2 ? 2 : 3) * cap * 4;
-    if (lds_local > 64 * 1024 && G.invert) { cap = nwmax + 2; lds_local = nwmax * 8 + (nwmax + 2) * 4 + 2 * cap * 4; }
-    return lds_local;
+    static const ccl_tuning T = ccl_tuning_from_env();
+    return T;
 }
 
 // union-find phase only: parent[] (every segment points at a smaller id of its component, roots at themselves)
@@ -652,7 +629,7 @@ static int ccl_roots(vp_ctx* ctx, const u64* d_bits, const ccl_geom& G, int n, u
     hipStream_t s = ctx->stream;
     const int strips = (h + G.rows - 1) / G.rows;
     size_t cap;
-    const size_t lds_local = ccl_local_lds(G, cap);
+    const size_t lds_local = ccl_local_lds(G, cap, ccl_env_tuning());
     if (lds_local <= 64 * 1024) {
         { vp_prof_scope ps(ctx, VPK_CCL_LOCAL); hipLaunchKernelGGL(k_ccl_local, dim3((unsigned)((size_t)n * strips)), dim3(256), lds_local, s, d_bits, G, parent, flags, strips, (int)cap, only, zero_too); }
         if (strips > 1) { vp_prof_scope ps(ctx, VPK_CCL_BOUNDARY); hipLaunchKernelGGL(k_ccl_boundary, dim3((unsigned)(strips - 1), (unsigned)n), dim3(64), 0, s, d_bits, G, parent, flags, only); }
@@ -683,181 +660,184 @@ static int ccl_one_level_tail(vp_ctx* ctx, const u64* d_bits, const ccl_geom& G,
     return VP_OK;
 }
 
+// ---- dispatch --------------------------------------------------------------------------------------------------------------
+// vpk_ccl makes the plan (ccl_make_plan, vp_ccl_plan.h) and hands it to one launcher per path: ccl_two_level, which finishes the
+// frames its merge hands over with ccl_crowded or, where the geometry does not suit those kernels, with the one-level kernels
+// (ccl_roots + ccl_one_level_tail); and the one-level path itself.
+
+struct ccl_call {            // the arguments of vpk_ccl that the launchers pass on
+    const u64* bits; int n; const vp_ccl_ws& ws; int32_t* labels; int32_t* stats; double* cent; int max_labels; int32_t* nlabels;
+};
+
+// Accumulators of the components that span strips, indexed by label: a set of the context's own that is all "empty" between calls -
+// k_ccl3_rows resets exactly the entries it reads - so that no launch writes max_labels entries per frame (268 MB per 128 frames
+// with 65,536 labels allowed: a quarter of what k_ccl3_link stored).  The set is clean only in the order of one stream and only once
+// every launch of a call has been accepted: c3_acc_acquire marks it dirty, c3_acc_commit - after the call's last launch was taken -
+// clean, and a dirty set is reinitialised before its next use.  *acc is left alone when the context has no set of `need` bytes
+// (no memory): the caller then keeps the workspace's set and its clearing per call.
+static int c3_acc_acquire(vp_ctx* ctx, size_t need, hipStream_t s, ccl_acc** acc)
+{
+    if (need > ctx->c3_acc_bytes) {
+        VP_HIP(ctx, hipStreamSynchronize(s));
+        if (ctx->c3_acc) { (void)hipFree(ctx->c3_acc); ctx->c3_acc = nullptr; ctx->c3_acc_bytes = 0; }
+        if (hipMalloc(&ctx->c3_acc, need) == hipSuccess) { ctx->c3_acc_bytes = need; ctx->c3_acc_dirty = 1; }
+        else (void)hipGetLastError();
+    }
+    if (!ctx->c3_acc || need > ctx->c3_acc_bytes) return VP_OK;
+    if (ctx->c3_acc_dirty) {
+        const size_t entries = ctx->c3_acc_bytes / sizeof(ccl_acc);
+        hipLaunchKernelGGL(k_ccl3_acc_init, dim3((unsigned)std::min<size_t>((entries + 255) / 256, 65535)), dim3(256), 0, s, (ccl_acc*)ctx->c3_acc, entries);
+    }
+    ctx->c3_acc_dirty = 1;
+    *acc = (ccl_acc*)ctx->c3_acc;
+    return VP_OK;
+}
+
+static void c3_acc_commit(vp_ctx* ctx)
+{
+#ifdef VP_PROBE
+    if (g_dbg_bits_host) return;   // kernels that skip work do not hand every entry back clean
+#endif
+    ctx->c3_acc_dirty = 0;
+}
+
+// Kernels accept more dynamic LDS than the 64 KB default once told so - per device, hence remembered in the context (grow-only).
+static bool c3_allow_lds(const void* kernel, size_t lds, size_t& allowed)
+{
+    if (lds <= allowed) return true;
+    if (hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess) { (void)hipGetLastError(); return false; }
+    allowed = lds;
+    return true;
+}
+
+// K = 1: strips of up to 8192 ids; K = 2: taller strips, twice the threads per block.  The light labelling instantiation always has
+// 512 threads: at ~120 registers a CU holds 16 waves, i.e. two blocks of eight.
+template <int K>
+static bool c3_allow_plan_lds(vp_ctx* ctx, const ccl_plan& P)
+{
+    size_t* set = ctx->c3_lds_set;
+    return c3_allow_lds((const void*)k_ccl3_link<K * C3_LINK_THREADS>, P.lds3a, set[2 * (K - 1)]) &&
+           c3_allow_lds((const void*)k_ccl3_label<K * C3_LABEL_THREADS, 0, C3_ACC>, P.lds3b, set[2 * (K - 1) + 1]) &&
+           c3_allow_lds((const void*)k_ccl3_label<C3_LABEL_THREADS, C3_LIGHT_ROOTS, C3_LIGHT_ACC>, P.lds3c, set[4]);
+}
+
+// The crowded-frame kernels (vp_ccl3.inl): launches that read the list of handed-over frames and leave at once when it is empty (the
+// usual case).
+template <int K>
+static int ccl_crowded(vp_ctx* ctx, const ccl_plan& P, const ccl_call& c)
+{
+    const ccl_tuning& T = ccl_env_tuning();
+    const ccl_geom& G = P.G;
+    const c3_plan& P3 = P.P3;
+    const vp_ccl_ws& ws = c.ws;
+    hipStream_t s = ctx->stream;
+    const int scap = (int)c3_strips_cap(G.h);
+    ccl_acc* acc3 = (ccl_acc*)ws.acc;
+    if (ctx->chain_streams == 1) {   // sub-batches on several streams would share the context's set: they keep the workspace's
+        const int rc = c3_acc_acquire(ctx, sizeof(ccl_acc) * (size_t)c.max_labels * (size_t)c.n, s, &acc3);
+        if (rc != VP_OK) return rc;
+    }
+    const bool acc3_own = acc3 != (ccl_acc*)ws.acc;
+    { vp_prof_scope ps(ctx, VPK_CCL_LOCAL);
+      hipLaunchKernelGGL(k_ccl3_link<K * C3_LINK_THREADS>, dim3((unsigned)(ctx->num_cu * T.lgrid)), dim3(K * C3_LINK_THREADS), P.lds3a, s, c.bits, G, P3, ws.c3_ncrowded,
+                         ws.c3_clist, ws.parent, ws.flags, ws.c3_child, ws.c3_lroot, ws.seglabel, acc3, c.max_labels, acc3_own ? 0 : 1); }
+    { vp_prof_scope ps(ctx, VPK_CCL_BOUNDARY);
+      const size_t span = (size_t)2 * G.wb + 4;     // u16 roots of the two rows (row pairs) that meet: span entries each
+      hipLaunchKernelGGL(k_ccl3_bound, dim3((unsigned)(ctx->num_cu * T.bgrid)), dim3(256), span * 4 + 16, s, c.bits, G, P3, ws.c3_ncrowded, ws.c3_clist, ws.parent, ws.flags,
+                         ws.c3_child, ws.seglabel); }
+    { vp_prof_scope ps(ctx, VPK_CCL_RANK);
+      hipLaunchKernelGGL(k_ccl3_rank, dim3((unsigned)(ctx->num_cu * 4)), dim3(256), 0, s, G, P3, ws.c3_ncrowded, ws.c3_clist, ws.flags, ws.prefix, ws.c3_barr, ws.c3_lroot, ws.parent,
+                         ws.c3_items); }
+    { vp_prof_scope ps(ctx, VPK_CCL_STATS);
+      // two instantiations, each taking the strips k_ccl3_rank marked for it: LIGHT first - two blocks per CU - then HEAVY
+      auto label = [&](auto kernel, int blocks_per_cu, int threads, size_t lds) {
+          hipLaunchKernelGGL(kernel, dim3((unsigned)(ctx->num_cu * blocks_per_cu)), dim3(threads), lds, s, c.bits, G, P3, ws.c3_ncrowded, ws.c3_items, ws.c3_clist, ws.parent,
+                             ws.flags, ws.c3_child, ws.prefix, ws.c3_lroot, ws.seglabel, ws.c3_barr, (c3_state*)ws.c3_state, (contrib*)ws.c3_tot, scap, c.nlabels, acc3,
+                             c.max_labels, c.labels, c.stats, c.cent);
+      };
+      label(k_ccl3_label<C3_LABEL_THREADS, C3_LIGHT_ROOTS, C3_LIGHT_ACC>, T.agrid_light, C3_LABEL_THREADS, P.lds3c);
+      label(k_ccl3_label<K * C3_LABEL_THREADS, 0, C3_ACC>, T.agrid, K * C3_LABEL_THREADS, P.lds3b); }
+    if (c.stats || c.cent || acc3_own) {
+        vp_prof_scope ps(ctx, VPK_CCL_FINAL);
+        hipLaunchKernelGGL(k_ccl3_rows, dim3((unsigned)(ctx->num_cu * 4)), dim3(256), 0, s, G, P3, ws.c3_ncrowded, ws.c3_clist, ws.flags, ws.c3_child, ws.prefix,
+                           ws.c3_barr, (const c3_state*)ws.c3_state, (const contrib*)ws.c3_tot, scap, acc3, c.max_labels, c.stats, c.cent, acc3_own ? 1 : 0);
+    }
+    VP_HIP(ctx, hipGetLastError());
+    if (acc3_own) c3_acc_commit(ctx);   // every launch was taken: k_ccl3_rows hands back clean every entry the labelling launches touch
+    return VP_OK;
+}
+
+// The two-level path (vp_ccl2.inl): strips resolved in LDS, one merge block per frame; frames the merge hands over go to the
+// crowded-frame kernels when the geometry suits them (it does for every frame up to 8192 px wide) and the device allows their LDS,
+// otherwise to the one-level kernels.
+static int ccl_two_level(vp_ctx* ctx, const ccl_plan& P, const ccl_call& c)
+{
+    const ccl_geom& G = P.G;
+    const vp_ccl_ws& ws = c.ws;
+    hipStream_t s = ctx->stream;
+    const int n = c.n;
+    const bool c3_ok = P.P3.ok && (P.c3_tall ? c3_allow_plan_lds<2>(ctx, P) : c3_allow_plan_lds<1>(ctx, P));
+    const int c3_strips = c3_ok ? P.P3.strips : 0;
+    { vp_prof_scope ps(ctx, VPK_CCL2_LOCAL);
+      hipLaunchKernelGGL(k_ccl2_local, dim3((unsigned)((size_t)n * P.strips)), dim3(256), P.lds2, s, c.bits, G, P.strips, (int)P.cap2, (int)P.rc, (int)P.tail_words, ws.c2_ncomp,
+                         (contrib*)ws.c2_recs, (c2_box*)ws.c2_bgbox, ws.wordlabel, ws.seglabel, ws.c3_ncrowded); }
+    { vp_prof_scope ps(ctx, VPK_CCL2_MERGE);
+      hipLaunchKernelGGL(k_ccl2_merge, dim3((unsigned)n), dim3(C2_THREADS), 0, s, c.bits, G, P.strips, P.mcap, ws.c2_ncomp, (const contrib*)ws.c2_recs,
+                         (const c2_box*)ws.c2_bgbox, ws.wordlabel, ws.seglabel, ws.c2_label, ws.c2_crowded, c.nlabels, c.stats, c.cent, c.max_labels,
+                         ws.c3_ncrowded, ws.c3_clist, (c3_state*)ws.c3_state, ws.c3_barr, c3_strips); }
+    VP_HIP(ctx, hipGetLastError());
+    int rc;
+    if (c3_ok) {
+        rc = P.c3_tall ? ccl_crowded<2>(ctx, P, c) : ccl_crowded<1>(ctx, P, c);
+    } else {
+        // the one-level kernels, launched whatever the frames hold (the flags live on the device); they leave at once for frames the merge resolved
+        rc = ccl_roots(ctx, c.bits, G, n, ws.parent, ws.flags, ws.c2_crowded);
+        if (rc == VP_OK) rc = ccl_one_level_tail(ctx, c.bits, G, n, ws, c.stats, c.cent, c.max_labels, c.nlabels, ws.c2_crowded);
+    }
+    if (rc != VP_OK) return rc;
+    if (c.labels) {
+        vp_prof_scope ps(ctx, VPK_CCL2_WRITE);
+        const dim3 wr_grid((unsigned)((G.h + WR_ROWS - 1) / WR_ROWS), (unsigned)n);
+        hipLaunchKernelGGL(k_ccl2_write<0>, wr_grid, dim3(256), 0, s, c.bits, G, P.strips, (int)P.rc, ws.seglabel, ws.wordlabel, ws.c2_label, ws.c2_crowded, c.labels, P.gpr, P.magic,
+                           c3_ok ? 1 : 0);
+    }
+    VP_HIP(ctx, hipGetLastError());
+    return VP_OK;
+}
+
 int vpk_ccl(vp_ctx* ctx, const u64* d_bits, int w, int h, int n, int numbering, const vp_ccl_ws& ws, int32_t* d_labels,
             int32_t* d_stats, double* d_centroids, int max_labels, int32_t* d_nlabels)
 {
     if (numbering != VP_CCL_BLOCK2X2 && numbering != VP_CCL_PIXEL) return vp_fail(ctx, VP_ERR_INVALID, "numbering");
     if (max_labels < 1) return vp_fail(ctx, VP_ERR_INVALID, "max_labels");
-    ccl_geom G;
-    ccl_make_geom(G, w, h, numbering, 0, 0);
-    hipStream_t s = ctx->stream;
-    const int strips = (h + G.rows - 1) / G.rows;
-    const u32 gpr = (u32)((w + 3) / 4);
-    const u32 magic = (u32)((0x100000000ull + gpr - 1) / gpr);
+    const ccl_plan P = ccl_make_plan(w, h, numbering, ctx->ccl_levels, ctx->ccl_mcap, ccl_env_tuning());
+    const ccl_call c = {d_bits, n, ws, d_labels, d_stats, d_centroids, max_labels, d_nlabels};
+    if (P.two_level) return ccl_two_level(ctx, P, c);
 
-    // ---- two-level path (vp_ccl2.inl) ----------------------------------------------------------------------------------
-    const size_t nwmax = (size_t)G.rows * G.ww;
-    const size_t cap2 = nwmax + 2;
-    const size_t rc = 96;   // components per strip with LDS accumulators (44 B each)
-    size_t tail_words = std::max(rc * 11, cap2);    // union queue, then root -> list place (cap words), then the accumulators
-    tail_words += tail_words & 1;
-    const size_t list_words = nwmax + (nwmax + 1) / 2 + ((nwmax + (nwmax + 1) / 2) & 1);   // wbase + word list, padded to 8 bytes
-    const size_t lds2 = nwmax * 8 + (list_words + cap2 + tail_words) * 4;                   // 1080p: 21.8 KB, seven blocks per CU
-    const bool two_level = ctx->ccl_levels == 2 && lds2 <= 64 * 1024 && G.ww <= 64 && G.rows <= CL_ROWS && strips <= C2_MAXSTRIPS &&
-                           (G.rows % WR_ROWS) == 0 && (G.rows % 8) == 0 && (size_t)strips <= c2_strips_max(h);
-    if (two_level) {
-        const int mcap = (ctx->ccl_mcap >= 0 && ctx->ccl_mcap < C2_MCAP) ? ctx->ccl_mcap : C2_MCAP;
-        // frames the merge hands over go to the crowded-frame kernels of vp_ccl3.inl when the geometry suits them (it does for every
-        // frame up to 8192 px wide), otherwise to the one-level kernels
-        static const u32 c3_max_ids = getenv("VP_C3_IDS") ? (u32)atoi(getenv("VP_C3_IDS")) : (u32)C3_IDS;
-        c3_plan P3 = c3_make_plan(G, std::min<u32>(c3_max_ids, C3_IDS));
-        const bool c3_tall = P3.ids > 8192;           // taller strips: twice the threads per block (one word per thread still)
-        static const bool c3_off = getenv("VP_CCL3") && atoi(getenv("VP_CCL3")) == 0;
-        size_t lds3a = 0, lds3b = 0, lds3c = 0;
-        if (P3.ok && !c3_off && (size_t)P3.strips + 1 <= c3_strips_cap(h) && sizeof(c3_state) == C3_STATE_BYTES) {
-            lds3a = c3_link_lds(G, P3);
-            lds3b = c3_label_lds(G, P3, 0, C3_ACC);
-            lds3c = c3_label_lds(G, P3, C3_LIGHT_ROOTS, C3_LIGHT_ACC);
-            // (grow-only; kernels accept more dynamic LDS than the 64 KB default once told so - per device, hence kept in the context)
-            const void* fa_ = c3_tall ? (const void*)k_ccl3_link<2 * C3_LINK_THREADS> : (const void*)k_ccl3_link<C3_LINK_THREADS>;
-            const void* fb_ = c3_tall ? (const void*)k_ccl3_label<2 * C3_LABEL_THREADS, 0, C3_ACC> : (const void*)k_ccl3_label<C3_LABEL_THREADS, 0, C3_ACC>;
-            const void* fc_ = (const void*)k_ccl3_label<C3_LABEL_THREADS, C3_LIGHT_ROOTS, C3_LIGHT_ACC>;
-            size_t& ra = ctx->c3_lds_set[c3_tall ? 2 : 0]; size_t& rb = ctx->c3_lds_set[c3_tall ? 3 : 1]; size_t& rc_ = ctx->c3_lds_set[4];
-            if (lds3a > ra) { if (hipFuncSetAttribute(fa_, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds3a) == hipSuccess) ra = lds3a; else { (void)hipGetLastError(); P3.ok = 0; } }
-            if (P3.ok && lds3b > rb) { if (hipFuncSetAttribute(fb_, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds3b) == hipSuccess) rb = lds3b; else { (void)hipGetLastError(); P3.ok = 0; } }
-            if (P3.ok && lds3c > rc_) { if (hipFuncSetAttribute(fc_, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds3c) == hipSuccess) rc_ = lds3c; else { (void)hipGetLastError(); P3.ok = 0; } }
-        } else {
-            P3.ok = 0;
-        }
-        const int c3_strips = P3.ok ? P3.strips : 0;
-        if (P3.ok && getenv("VP_CCL3_OCC")) {   // diagnosis: blocks per CU the runtime grants the crowded-frame kernels
-            int oa = 0, ob = 0, oc = 0;
-            if (c3_tall) {
-                hipOccupancyMaxActiveBlocksPerMultiprocessor(&oa, k_ccl3_link<2 * C3_LINK_THREADS>, 2 * C3_LINK_THREADS, lds3a);
-                hipOccupancyMaxActiveBlocksPerMultiprocessor(&ob, k_ccl3_label<2 * C3_LABEL_THREADS, 0, C3_ACC>, 2 * C3_LABEL_THREADS, lds3b);
-                hipOccupancyMaxActiveBlocksPerMultiprocessor(&oc, k_ccl3_label<C3_LABEL_THREADS, C3_LIGHT_ROOTS, C3_LIGHT_ACC>, C3_LABEL_THREADS, lds3c);
-            } else {
-                hipOccupancyMaxActiveBlocksPerMultiprocessor(&oa, k_ccl3_link<C3_LINK_THREADS>, C3_LINK_THREADS, lds3a);
-                hipOccupancyMaxActiveBlocksPerMultiprocessor(&ob, k_ccl3_label<C3_LABEL_THREADS, 0, C3_ACC>, C3_LABEL_THREADS, lds3b);
-                hipOccupancyMaxActiveBlocksPerMultiprocessor(&oc, k_ccl3_label<C3_LABEL_THREADS, C3_LIGHT_ROOTS, C3_LIGHT_ACC>, C3_LABEL_THREADS, lds3c);
-            }
-            hipFuncAttributes fb2, fc2;
-            hipFuncGetAttributes(&fb2, c3_tall ? (const void*)k_ccl3_label<2 * C3_LABEL_THREADS, 0, C3_ACC> : (const void*)k_ccl3_label<C3_LABEL_THREADS, 0, C3_ACC>);
-            hipFuncGetAttributes(&fc2, (const void*)k_ccl3_label<C3_LABEL_THREADS, C3_LIGHT_ROOTS, C3_LIGHT_ACC>);
-            fprintf(stderr, "ccl3 occupancy: link %d blocks/CU (LDS %zu), label heavy %d blocks/CU (LDS %zu + %zu static, %d regs), light %d blocks/CU (LDS %zu + %zu static, %d regs), CUs %d\n",
-                    oa, lds3a, ob, lds3b, fb2.sharedSizeBytes, fb2.numRegs, oc, lds3c, fc2.sharedSizeBytes, fc2.numRegs, ctx->num_cu);
-        }
-        { vp_prof_scope ps(ctx, VPK_CCL2_LOCAL);
-          hipLaunchKernelGGL(k_ccl2_local, dim3((unsigned)((size_t)n * strips)), dim3(256), lds2, s, d_bits, G, strips, (int)cap2, (int)rc, (int)tail_words, ws.c2_ncomp,
-                             (contrib*)ws.c2_recs, (c2_box*)ws.c2_bgbox, ws.wordlabel, ws.seglabel, ws.c3_ncrowded); }
-        { vp_prof_scope ps(ctx, VPK_CCL2_MERGE);
-          hipLaunchKernelGGL(k_ccl2_merge, dim3((unsigned)n), dim3(C2_THREADS), 0, s, d_bits, G, strips, mcap, ws.c2_ncomp, (const contrib*)ws.c2_recs,
-                             (const c2_box*)ws.c2_bgbox, ws.wordlabel, ws.seglabel, ws.c2_label, ws.c2_crowded, d_nlabels, d_stats, d_centroids, max_labels,
-                             ws.c3_ncrowded, ws.c3_clist, (c3_state*)ws.c3_state, ws.c3_barr, c3_strips); }
-        VP_HIP(ctx, hipGetLastError());
-        static const int c3_dbg = getenv("VP_CCL3_DBG") ? atoi(getenv("VP_CCL3_DBG")) : 0;   // timing experiments only: parts of the kernels skipped
-        static const int c3_dry = getenv("VP_CCL3_DRY") ? atoi(getenv("VP_CCL3_DRY")) : 0;   // experiments: 1 no launches, 2 no link, 3 no label
-        // Accumulators of the components that span strips, indexed by label: a set of the context's own that is all "empty" between
-        // calls - k_ccl3_rows resets exactly the entries it reads - so that no launch writes max_labels entries per frame (268 MB per 128
-        // frames with 65,536 labels allowed: a quarter of what k_ccl3_link stored).  Sub-batches on several streams would share it: they
-        // keep the per-call workspace and its clearing.
-        ccl_acc* acc3 = (ccl_acc*)ws.acc;
-        bool acc3_own = false;
-        if (P3.ok && c3_dry != 1 && ctx->chain_streams == 1) {
-            const size_t need = sizeof(ccl_acc) * (size_t)max_labels * (size_t)n;
-            if (need > ctx->c3_acc_bytes) {
-                VP_HIP(ctx, hipStreamSynchronize(s));
-                if (ctx->c3_acc) { (void)hipFree(ctx->c3_acc); ctx->c3_acc = nullptr; ctx->c3_acc_bytes = 0; }
-                if (hipMalloc(&ctx->c3_acc, need) == hipSuccess) { ctx->c3_acc_bytes = need; ctx->c3_acc_dirty = 1; }
-                else (void)hipGetLastError();                  // no memory for it: the workspace's set, cleared per call
-            }
-            if (ctx->c3_acc && need <= ctx->c3_acc_bytes) {
-                if (ctx->c3_acc_dirty) {
-                    const size_t entries = ctx->c3_acc_bytes / sizeof(ccl_acc);
-                    hipLaunchKernelGGL(k_ccl3_acc_init, dim3((unsigned)std::min<size_t>((entries + 255) / 256, 65535)), dim3(256), 0, s, (ccl_acc*)ctx->c3_acc, entries);
-                }
-                ctx->c3_acc_dirty = 1;                         // until k_ccl3_rows of this call has been queued
-                acc3 = (ccl_acc*)ctx->c3_acc;
-                acc3_own = true;
-            }
-        }
-        if (P3.ok && c3_dry != 1) {
-            // two launches that read the list of handed-over frames and leave at once when it is empty (the usual case)
-            if (c3_dry != 2) { vp_prof_scope ps(ctx, VPK_CCL_LOCAL);
-              static const int lgrid = getenv("VP_C3_LGRID") ? atoi(getenv("VP_C3_LGRID")) : 16;
-              if (c3_tall) hipLaunchKernelGGL(k_ccl3_link<2 * C3_LINK_THREADS>, dim3((unsigned)(ctx->num_cu * lgrid)), dim3(2 * C3_LINK_THREADS), lds3a, s, d_bits, G, P3, ws.c3_ncrowded, ws.c3_clist, ws.parent,
-                                 ws.flags, ws.c3_child, ws.c3_lroot, ws.seglabel, acc3, max_labels, acc3_own ? 0 : 1, c3_dbg);
-              else hipLaunchKernelGGL(k_ccl3_link<C3_LINK_THREADS>, dim3((unsigned)(ctx->num_cu * lgrid)), dim3(C3_LINK_THREADS), lds3a, s, d_bits, G, P3, ws.c3_ncrowded, ws.c3_clist, ws.parent,
-                                 ws.flags, ws.c3_child, ws.c3_lroot, ws.seglabel, acc3, max_labels, acc3_own ? 0 : 1, c3_dbg); }
-            { vp_prof_scope ps(ctx, VPK_CCL_BOUNDARY);
-              const size_t span = (size_t)2 * G.wb + 4;     // u16 roots of the two rows (row pairs) that meet: span entries each
-              static const int bgrid = getenv("VP_C3_BGRID") ? atoi(getenv("VP_C3_BGRID")) : 64;   // blocks per CU in the grid: items differ a lot in cost, the dispatcher balances
-              hipLaunchKernelGGL(k_ccl3_bound, dim3((unsigned)(ctx->num_cu * bgrid)), dim3(256), span * 4 + 16, s, d_bits, G, P3, ws.c3_ncrowded, ws.c3_clist, ws.parent, ws.flags,
-                                 ws.c3_child, ws.seglabel, c3_dbg); }
-            { vp_prof_scope ps(ctx, VPK_CCL_RANK);
-              hipLaunchKernelGGL(k_ccl3_rank, dim3((unsigned)(ctx->num_cu * 4)), dim3(256), 0, s, G, P3, ws.c3_ncrowded, ws.c3_clist, ws.flags, ws.prefix, ws.c3_barr, ws.c3_lroot, ws.parent,
-                                 ws.c3_items); }
-            if (c3_dry != 3) { vp_prof_scope ps(ctx, VPK_CCL_STATS);
-              // two instantiations, each taking the strips k_ccl3_rank marked for it: LIGHT first - two blocks per CU - then HEAVY
-              static const int agrid = getenv("VP_C3_AGRID") ? atoi(getenv("VP_C3_AGRID")) : 2;
-              static const int agrid_light = getenv("VP_C3_AGRID_LIGHT") ? atoi(getenv("VP_C3_AGRID_LIGHT")) : 4;
-#define C3_LABEL_ARGS d_bits, G, P3, ws.c3_ncrowded, ws.c3_items, ws.c3_clist, ws.parent, ws.flags, ws.c3_child, ws.prefix, ws.c3_lroot, ws.seglabel, ws.c3_barr, \
-                             (c3_state*)ws.c3_state, (contrib*)ws.c3_tot, (int)c3_strips_cap(h), d_nlabels, acc3, max_labels, d_labels, d_stats, d_centroids, c3_dbg
-              // (the light instantiation always with 512 threads: at ~120 registers a CU holds 16 waves, i.e. two blocks of eight)
-              hipLaunchKernelGGL((k_ccl3_label<C3_LABEL_THREADS, C3_LIGHT_ROOTS, C3_LIGHT_ACC>), dim3((unsigned)(ctx->num_cu * agrid_light)), dim3(C3_LABEL_THREADS), lds3c, s, C3_LABEL_ARGS);
-              if (c3_tall) hipLaunchKernelGGL((k_ccl3_label<2 * C3_LABEL_THREADS, 0, C3_ACC>), dim3((unsigned)(ctx->num_cu * agrid)), dim3(2 * C3_LABEL_THREADS), lds3b, s, C3_LABEL_ARGS);
-              else hipLaunchKernelGGL((k_ccl3_label<C3_LABEL_THREADS, 0, C3_ACC>), dim3((unsigned)(ctx->num_cu * agrid)), dim3(C3_LABEL_THREADS), lds3b, s, C3_LABEL_ARGS);
-#undef C3_LABEL_ARGS
-            }
-            if (d_stats || d_centroids || acc3_own) {
-                vp_prof_scope ps(ctx, VPK_CCL_FINAL);
-                hipLaunchKernelGGL(k_ccl3_rows, dim3((unsigned)(ctx->num_cu * 4)), dim3(256), 0, s, G, P3, ws.c3_ncrowded, ws.c3_clist, ws.flags, ws.c3_child, ws.prefix,
-                                   ws.c3_barr, (const c3_state*)ws.c3_state, (const contrib*)ws.c3_tot, (int)c3_strips_cap(h), acc3, max_labels, d_stats, d_centroids,
-                                   acc3_own ? 1 : 0);
-                if (acc3_own && c3_dry == 0 && c3_dbg == 0) ctx->c3_acc_dirty = 0;   // every entry the labelling launch touched has been handed back clean
-            }
-            VP_HIP(ctx, hipGetLastError());
-        } else if (!P3.ok) {
-            // the one-level kernels, launched whatever the frames hold (the flags live on the device); they leave at once for frames the merge resolved
-            int rc2 = ccl_roots(ctx, d_bits, G, n, ws.parent, ws.flags, ws.c2_crowded);
-            if (rc2 == VP_OK) rc2 = ccl_one_level_tail(ctx, d_bits, G, n, ws, d_stats, d_centroids, max_labels, d_nlabels, ws.c2_crowded);
-            if (rc2 != VP_OK) return rc2;
-        }
-        if (c3_dry == 4) {   // diagnosis: which frames were handed over, and why
-            std::vector<u32> cr(n), nc((size_t)n * strips);
-            hipStreamSynchronize(s);
-            hipMemcpy(cr.data(), ws.c2_crowded, (size_t)n * 4, hipMemcpyDeviceToHost);
-            hipMemcpy(nc.data(), ws.c2_ncomp, (size_t)n * strips * 4, hipMemcpyDeviceToHost);
-            for (int f = 0; f < n; f++)
-                if (cr[f]) { fprintf(stderr, "crowded frame %d of %d:", f, n); for (int k = 0; k < strips; k++) fprintf(stderr, " %u", nc[(size_t)f * strips + k]); fprintf(stderr, "\n"); }
-        }
-        if (d_labels) {
-            vp_prof_scope ps(ctx, VPK_CCL2_WRITE);
-            const dim3 wr_grid((unsigned)((h + WR_ROWS - 1) / WR_ROWS), (unsigned)n);
-            hipLaunchKernelGGL(k_ccl2_write<0>, wr_grid, dim3(256), 0, s, d_bits, G, strips, (int)rc, ws.seglabel, ws.wordlabel, ws.c2_label, ws.c2_crowded, d_labels, gpr, magic,
-                               P3.ok ? 1 : 0);
-        }
-        VP_HIP(ctx, hipGetLastError());
-        return VP_OK;
-    }
-
-    // ---- one-level path -------------------------------------------------------------------------------------------------
-    int rc1 = ccl_roots(ctx, d_bits, G, n, ws.parent, ws.flags);
-    if (rc1 != VP_OK) return rc1;
-    rc1 = ccl_one_level_tail(ctx, d_bits, G, n, ws, d_stats, d_centroids, max_labels, d_nlabels, nullptr);
-    if (rc1 != VP_OK) return rc1;
+    int rc = ccl_roots(ctx, d_bits, P.G, n, ws.parent, ws.flags);
+    if (rc != VP_OK) return rc;
+    rc = ccl_one_level_tail(ctx, d_bits, P.G, n, ws, d_stats, d_centroids, max_labels, d_nlabels, nullptr);
+    if (rc != VP_OK) return rc;
     if (d_labels) {
         vp_prof_scope ps(ctx, VPK_CCL_WRITE);
         const u32 total_rows = (u32)((size_t)n * h);
-        hipLaunchKernelGGL(k_ccl_write, dim3((total_rows + WR_ROWS - 1) / WR_ROWS), dim3(256), 0, s, d_bits, G, ws.seglabel, ws.wordlabel, d_labels,
-                           total_rows, gpr, magic);
+        hipLaunchKernelGGL(k_ccl_write, dim3((total_rows + WR_ROWS - 1) / WR_ROWS), dim3(256), 0, ctx->stream, d_bits, P.G, ws.seglabel, ws.wordlabel, d_labels,
+                           total_rows, P.gpr, P.magic);
     }
     VP_HIP(ctx, hipGetLastError());
     return VP_OK;
 }
 
 #ifdef VP_PROBE
-// measurement builds: per probe point, the ticks summed over the blocks that reached point 15 (ran to the end) in out[k*16 + i],
+// measurement builds: the VP_DBG_* switches of vp_internal.h, for the kernels of this unit and of vp_morph.hip
+extern "C" int vp_debug_set(int bits)
+{
+    g_dbg_bits_host = bits;
+    if (hipMemcpyToSymbol(HIP_SYMBOL(vp_dbg_bits), &bits, sizeof bits) != hipSuccess) return -1;
+    return vp_morph_debug_set(bits);
+}
+
+// per probe point, the ticks summed over the blocks that reached point 15 (ran to the end) in out[k*16 + i],
 // their number in out[k*16 + 15]; slots are cleared afterwards
 extern "C" int vp_debug_probe(double* out32)
 {
@@ -874,9 +854,7 @@ extern "C" int vp_debug_probe(double* out32)
     std::fill(h.begin(), h.end(), 0u);
     return hipMemcpyToSymbol(HIP_SYMBOL(g_c2_probe), h.data(), h.size() * 4) == hipSuccess ? 0 : -1;
 }
-#endif
 
-#ifdef VP_PROBE
 // crowded-frame kernels (link, bound, label): out[k * 16 + i] = ticks (10 ns) of phase i summed over blocks and items, out[k * 16 + 15] = blocks that ran
 extern "C" int vp_debug_probe3(double* out32 /* 48 */)
 {

@@ -28,8 +28,7 @@ __device__ unsigned int g_c2_probe[2][C2_PROBE_BLOCKS][16];
 #define C2_PROBE(k, i) do { } while (0)
 #endif
 
-#define C2_MCAP 2048           // strip components of one frame held in the merge block's LDS
-#define C2_MAXSTRIPS 256
+// C2_MCAP, C2_MAXSTRIPS: vp_ccl_plan.h
 #define C2_DENSE 0xffffffffu   // ncomp value of a strip the strip-local pass could not resolve
 #define C2_THREADS 1024
 #define C2_PER (C2_MCAP / C2_THREADS)

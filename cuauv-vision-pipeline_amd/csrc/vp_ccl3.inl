@@ -26,14 +26,10 @@
 // block that finishes a frame's last boundary ranks the frame"): every per-frame stage then ran on ONE block (ranks 3 ms, rows 6 ms
 // per 128 frames), agent-scope fences around every hand-over cost another 2.5 ms, and second arrivers were 1.7 x busier than the
 // average block.  Kernel boundaries are the cheaper seam here.
-#define C3_IDS 16384           // most segment ids per strip = entries of the LDS union-find (1080p: 16 rows = 15,360; VP_C3_IDS=8192: 8 rows)
+// C3_IDS, C3_ACC, C3_LIGHT_ROOTS, C3_LIGHT_ACC, C3_MAX_STRIPS: vp_ccl_plan.h, with c3_plan and the LDS sizes of the kernels below
 #define C3_LINK_THREADS 512    // k_ccl3_link, strips of up to 8192 ids; twice that for taller ones: a thread per 32-bit HALF of a word
 #define C3_LABEL_THREADS 512   // k_ccl3_label, likewise
-#define C3_ACC 2304            // local components whose statistics are accumulated per pass over the strip (the labelling launch has a CU's LDS to itself either way: one pass for raw noise at 10 % and 50 %)
-#define C3_LIGHT_ROOTS 1024    // strips with at most this many local roots are labelled by the LIGHT instantiation of k_ccl3_label: tables for that many roots
-#define C3_LIGHT_ACC 768       // ... and accumulators for that many per pass: ~72 KB of LDS, two blocks per CU hide each other's fixed latencies
 #define C3_TAB 128             // entries of a strip's table of partial components (beyond it: straight to global memory)
-#define C3_MAX_STRIPS 512      // per-strip root counts of a frame are scanned in LDS by every block of the later launches
 
 #ifdef VP_PROBE   // measurement builds only: time per phase (100 MHz wall clock ticks), summed over a block's items
 __device__ unsigned long long g_c3_probe[3][2048][16];
@@ -53,25 +49,7 @@ struct c3_state {              // per frame; zeroed by k_ccl2_merge when it hand
     int bg_minx, bg_maxx, bg_miny, bg_maxy;
 };
 
-struct c3_plan {
-    int R, strips;             // rows per strip (even), strips per frame
-    u32 ids;                   // R * wb: multiple of 32, <= C3_IDS
-    int ok;
-};
-
-static c3_plan c3_make_plan(const ccl_geom& G, u32 max_ids)
-{
-    c3_plan P = {0, 0, 0, 0};
-    for (int R = 32; R >= 2; R >>= 1) {
-        const u32 ids = (u32)R * (u32)G.wb;
-        if (ids <= max_ids && (ids % 32u) == 0 && R * G.ww <= 512) { P.R = R; P.ids = ids; break; }
-    }
-    if (!P.R || G.ww > 64) return P;
-    P.strips = (G.h + P.R - 1) / P.R;
-    P.ok = P.strips <= C3_MAX_STRIPS ? 1 : 0;
-    return P;
-}
-static size_t c3_max_strips(int h) { return (size_t)(h + 1) / 2 + 1; }
+static_assert(sizeof(c3_state) == C3_STATE_BYTES, "the workspace is carved for c3_state of C3_STATE_BYTES");
 
 // strip-relative segment id of the segment starting at pixel x of strip row r (strips start at even rows, so r and y have the same parity)
 __device__ __forceinline__ u32 c3_rel(const ccl_geom& G, int r, int x)
@@ -113,10 +91,10 @@ __device__ __forceinline__ void c3_unite(u32* p, u32* flags, u32* child, u32 a, 
 // atomicMin on parent[larger] settles them without a find (parents only ever decrease, so the pointers stay a forest).  When the
 // larger id already hung under something else, that something and the smaller id are one component: a real union
 // (compare-and-swap union-find with its finds) - a third of the contacts in raw noise instead of all of them.
-__device__ __forceinline__ void c3_contact(u32* lpar, u32 a, u32 b, int dbg = 0)
+__device__ __forceinline__ void c3_contact(u32* lpar, u32 a, u32 b)
 {
     const u32 hi = max(a, b), lo0 = min(a, b);
-    if (dbg & 2) { if (hi == 0xfffffff0u) lpar[0] = lo0; return; }     // (timing experiments: the walk over the contacts alone)
+    if (VP_DBG(VP_DBG_C3_WALK_ONLY)) { if (hi == 0xfffffff0u) lpar[0] = lo0; return; }     // (timing experiments: the walk over the contacts alone)
     // ... under where the smaller end points NOW, up to four levels up (any ancestor of it will do): the rows of a strip are linked
     // all at once, so the forest of first links would otherwise be as deep as the strip has rows, and the finds of the real unions walk
     // it (strip union-find of 50 % noise: 1,055 -> 820 us per 128 frames)
@@ -128,7 +106,7 @@ __device__ __forceinline__ void c3_contact(u32* lpar, u32 a, u32 b, int dbg = 0)
         lo = q;
     }
     const u32 old = atomicMin(lpar + hi, lo);
-    if (old != hi && old != lo && !(dbg & 4)) lds_unite(lpar, old, lo);  // (dbg 4: ... with the first links, without the real unions)
+    if (old != hi && old != lo && !VP_DBG(VP_DBG_C3_NO_UNIONS)) lds_unite(lpar, old, lo);  // (the switch: ... with the first links, without the real unions)
 }
 
 // first bit of the run of 1s of `w` that holds set bit x, on 32-bit halves (64-bit shifts and counts run at a quarter of the rate)
@@ -289,7 +267,7 @@ template <int LT>
 __global__ __launch_bounds__(LT, 8) void k_ccl3_link(const u64* __restrict__ bits, ccl_geom G, c3_plan P, const u32* __restrict__ ncrowded,
                                                                const u32* __restrict__ clist, u32* __restrict__ parent, u32* __restrict__ flags,
                                                                u32* __restrict__ child, u32* __restrict__ lrootbits, u32* __restrict__ root16,
-                                                               ccl_acc* __restrict__ acc, int max_labels, int acc_clear, int dbg)
+                                                               ccl_acc* __restrict__ acc, int max_labels, int acc_clear)
 {
     const u32 nc = *ncrowded;
     if (nc == 0) return;                                      // the common case: nothing was handed over
@@ -343,7 +321,7 @@ __global__ __launch_bounds__(LT, 8) void k_ccl3_link(const u64* __restrict__ bit
             const u64 w = lbits[i];
             if (!w) continue;
             if (half == 0 && (w & 1ull) && j > 0 && (lbits[i - 1] >> 63))
-                c3_contact(lpar, c3_rel(G, r, 64 * j), c3_rel(G, r, 64 * (j - 1) + c3_run_start(lbits[i - 1], 63)), dbg);
+                c3_contact(lpar, c3_rel(G, r, 64 * j), c3_rel(G, r, 64 * (j - 1) + c3_run_start(lbits[i - 1], 63)));
             if (r == 0) continue;
             const u64 um = lbits[i - ww];
             const u64 ul = j > 0 ? lbits[i - ww - 1] : 0ull;
@@ -356,18 +334,18 @@ __global__ __launch_bounds__(LT, 8) void k_ccl3_link(const u64* __restrict__ bit
             while (vs) {
                 const int x = __ffs((int)vs) - 1 + 32 * half;
                 vs &= vs - 1;
-                c3_contact(lpar, c3_rel(G, r, 64 * j + c3_run_start(w, x)), c3_rel(G, r - 1, 64 * j + c3_run_start(um, x)), dbg);
+                c3_contact(lpar, c3_rel(G, r, 64 * j + c3_run_start(w, x)), c3_rel(G, r - 1, 64 * j + c3_run_start(um, x)));
             }
             while (dr) {
                 const int x = __ffs((int)dr) - 1 + 32 * half;
                 dr &= dr - 1;
-                c3_contact(lpar, c3_rel(G, r, 64 * j + c3_run_start(w, x)), c3_rel(G, r - 1, 64 * j + x + 1), dbg);
+                c3_contact(lpar, c3_rel(G, r, 64 * j + c3_run_start(w, x)), c3_rel(G, r - 1, 64 * j + x + 1));
             }
             while (dl) {
                 const int x = __ffs((int)dl) - 1 + 32 * half;
                 dl &= dl - 1;
                 const u32 b = x > 0 ? c3_rel(G, r - 1, 64 * j + c3_run_start(um, x - 1)) : c3_rel(G, r - 1, 64 * (j - 1) + c3_run_start(ul, 63));
-                c3_contact(lpar, c3_rel(G, r, 64 * j + x), b, dbg);
+                c3_contact(lpar, c3_rel(G, r, 64 * j + x), b);
             }
         }
         __syncthreads();
@@ -427,7 +405,7 @@ __global__ __launch_bounds__(LT, 8) void k_ccl3_link(const u64* __restrict__ bit
 // dynamic LDS: the u16 roots of the two rows that meet, two per word
 __global__ __launch_bounds__(256) void k_ccl3_bound(const u64* __restrict__ bits, ccl_geom G, c3_plan P, const u32* __restrict__ ncrowded,
                                                     const u32* __restrict__ clist, u32* __restrict__ parent, u32* __restrict__ flags,
-                                                    u32* __restrict__ child, const u32* __restrict__ root16, int dbg)
+                                                    u32* __restrict__ child, const u32* __restrict__ root16)
 {
     const u32 nc = *ncrowded;
     if (nc == 0 || P.strips < 2) return;
@@ -472,7 +450,7 @@ __global__ __launch_bounds__(256) void k_ccl3_bound(const u64* __restrict__ bits
         const unsigned short* lo16 = reinterpret_cast<const unsigned short*>(s_lo);
         const unsigned short* up16 = reinterpret_cast<const unsigned short*>(s_up16) + upoff;
         // eight threads share a word of the boundary row: one byte each of the three contact masks (see k_ccl3_link)
-        for (int j = tid >> 3; j < ww && !(dbg & 1); j += NT / 8) {
+        for (int j = tid >> 3; j < ww && !VP_DBG(VP_DBG_C3_NO_BOUND); j += NT / 8) {
             const size_t idx = (size_t)y * ww + j;
             const u64 w = fb[idx];
             if (!w) continue;
@@ -583,7 +561,7 @@ __global__ __launch_bounds__(AT, 4) void k_ccl3_label(const u64* __restrict__ bi
                                                                  c3_state* __restrict__ state, contrib* __restrict__ tot, int tot_stride,
                                                                  int32_t* __restrict__ nlabels,
                                                                  ccl_acc* __restrict__ acc, int max_labels, int32_t* __restrict__ labels,
-                                                                 int32_t* __restrict__ stats, double* __restrict__ cent, int dbg)
+                                                                 int32_t* __restrict__ stats, double* __restrict__ cent)
 {
     const u32 nc = *ncrowded;
     if (nc == 0) return;
@@ -775,7 +753,7 @@ __global__ __launch_bounds__(AT, 4) void k_ccl3_label(const u64* __restrict__ bi
         // ---- statistics per local component, ACCN components per pass ---------------------------------------------------------------
         contrib tot_c;
         contrib_zero(tot_c);
-        for (u32 c0 = 0; c0 < nroots && !(dbg & 8); c0 += ACCN) {
+        for (u32 c0 = 0; c0 < nroots && !VP_DBG(VP_DBG_C3_NO_STATS); c0 += ACCN) {
             for (u32 k = tid; k < ACCN; k += NT) { a_pack[k] = 0ull; a_minx[k] = 0xffffffffu; a_maxx[k] = 0; a_rows[k] = 0; }
             __syncthreads();
             // Every segment adds to its component's accumulators.  A wave's lanes mostly name the same component when one is large (half
@@ -888,7 +866,7 @@ __global__ __launch_bounds__(AT, 4) void k_ccl3_label(const u64* __restrict__ bi
             if (t_label[k]) acc_commit(facc + t_label[k], t_rec[k]);
         C3_PROBE(5);   // table flushed
         // ---- the strip's part of the label image: one lane = 4 px = one 16-byte store, labels from LDS --------------------------------
-        if (labels && !(dbg & 16)) {
+        if (labels && !VP_DBG(VP_DBG_C3_NO_LABELS)) {
             int32_t* lrow0 = labels + ((size_t)f * G.h + y0) * G.w;
             const bool vec = (G.w & 3) == 0 && ((((uintptr_t)lrow0) & 15) == 0);
             const u32 ngroups = (u32)nrows * gpr;
@@ -1038,11 +1016,4 @@ __global__ __launch_bounds__(256) void k_ccl3_rows(ccl_geom G, c3_plan P, const 
             }
         }
     }
-}
-
-static size_t c3_link_lds(const ccl_geom& G, const c3_plan& P) { return (size_t)P.R * G.ww * 8 + (size_t)P.ids * 4 + (size_t)P.ids / 32 * 4; }
-static size_t c3_label_lds(const ccl_geom& G, const c3_plan& P, size_t nrcap, size_t accn)
-{
-    const size_t nrmax = nrcap ? nrcap : (size_t)P.ids / 2;
-    return (size_t)P.R * G.ww * 8 + nrmax * 4 + (size_t)P.ids * 2 + nrmax * 2 + (size_t)P.ids / 32 * 4 * 5 + 8 + accn * 4 * 5;
 }

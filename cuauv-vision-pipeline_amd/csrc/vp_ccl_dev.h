@@ -2,15 +2,7 @@
 // labelling kernel in vp_morph.hip.  See vp_ccl.hip for the algorithm.
 #pragma once
 #include "vp_internal.h"
-
-struct ccl_geom {
-    int w, h, ww, wb, numbering;
-    u32 nids;   // multiple of 128
-    u32 nw32;   // nids / 32
-    int rows;   // rows per strip of the strip-local pass: 32, or 16 for wide frames (see ccl_make_geom)
-    int invert; // label the zero pixels instead (background regions, for hole borders)
-    int conn4;  // 4-connectivity (background of an 8-connected foreground)
-};
+#include "vp_ccl_plan.h"   // ccl_geom, CL_ROWS
 
 // word j of a row as the labelling sees it
 __device__ __forceinline__ u64 ccl_word(const ccl_geom& G, const u64* __restrict__ fb, int idx, int j)
@@ -128,7 +120,6 @@ __device__ __forceinline__ void global_link_word(const u64* __restrict__ fb, con
 }
 
 // ---- strip-local union-find in LDS ------------------------------------------------------------------
-#define CL_ROWS 32    // largest strip height; G.rows is the one in use
 #define CL_CAP 512    // default segments per strip handled in LDS (foreground); denser strips fall back to global memory
 
 __device__ __forceinline__ u32 lds_find(volatile u32* p, u32 x)

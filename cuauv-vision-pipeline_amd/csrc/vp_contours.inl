@@ -1438,7 +1438,7 @@ int vpk_find_contours(vp_ctx* ctx, const u64* d_bits, int w, int h, int n, int m
     if (method != 1 && method != 2) return vp_fail(ctx, VP_ERR_INVALID, "contour approximation");
     if ((size_t)w * h >= (1u << 29)) return vp_fail(ctx, VP_ERR_INVALID, "contours: image too large");
     ctj_args A;
-    ccl_make_geom(A.G, w, h, VP_CCL_PIXEL, 0, 0);
+    ccl_make_geom(A.G, w, h, VP_CCL_PIXEL, 0, 0, ccl_env_tuning());
     const ccl_geom& G = A.G;
     const int nwords = h * G.ww;
     const size_t words = (size_t)n * nwords;

@@ -70,7 +70,7 @@ struct vp_ctx {
     size_t c3_lds_set[6];         // dynamic LDS the crowded-frame kernels have been allowed on THIS device (link, label; short and tall strips): the attribute is per device
     void* c3_acc;                 // crowded-frame labelling: accumulators of components that span strips, all empty between calls (vp_ccl.hip)
     size_t c3_acc_bytes;
-    int c3_acc_dirty;             // a call was cut short after its labelling launch: reinitialise before the next use
+    int c3_acc_dirty;             // not known to be all empty (a call cut short, another stream): c3_acc_acquire reinitialises it before use
     int hough_global;             // 1: every Hough vote is a global atomic (VP_OPT_HOUGH_LDS 0); 0 (default): rows counted in LDS where they fit
     int blur_onepass;             // VP_OPT_BLUR_ONEPASS: -1 (default) the measured choice, 1 the one-pass kernel wherever its tile fits, 0 always two passes
     int hc_global;                // 1: HoughCircles radius histograms always in device memory (VP_OPT_HOUGH_CIRCLES_LDS 0); 0 (default): in LDS where they fit
@@ -325,6 +325,17 @@ int vpk_find_contours(vp_ctx* ctx, const u64* d_bits, int w, int h, int n, int m
                       uint32_t* d_nheads_out = nullptr, const vp_contour_mirror* host = nullptr, bool defer_big = false, int32_t* d_hier = nullptr);
 int vpk_ccl(vp_ctx* ctx, const u64* d_bits, int w, int h, int n, int numbering, const vp_ccl_ws& ws, int32_t* d_labels,
             int32_t* d_stats, double* d_centroids, int max_labels, int32_t* d_nlabels);
+
+// Timing switches of the measurement build (-DVP_PROBE, tools/build_probe.sh): kernels skip the named part of their work, so results
+// are wrong while one is set.  vp_debug_set (vp_ccl.hip) sets them; the product build compiles every test to `false`.
+enum { VP_DBG_C3_NO_BOUND = 1, VP_DBG_C3_WALK_ONLY = 2, VP_DBG_C3_NO_UNIONS = 4, VP_DBG_C3_NO_STATS = 8, VP_DBG_C3_NO_LABELS = 16,   // vp_ccl3.inl
+       VP_DBG_MORPH_NO_STAGES = 0x100, VP_DBG_MORPH_NO_LOAD = 0x200, VP_DBG_MORPH_NO_BITS = 0x400, VP_DBG_MORPH_NO_MASK = 0x800 };  // k_morph_bits_sym
+#ifdef VP_PROBE
+#define VP_DBG(bit) ((vp_dbg_bits & (bit)) != 0)     // vp_dbg_bits: a __device__ int of each unit that tests it (vp_ccl.hip, vp_morph.hip)
+int vp_morph_debug_set(int bits);                   // vp_morph.hip's copy
+#else
+#define VP_DBG(bit) false
+#endif
 
 // 16-byte streaming store for write-once outputs (masks, labels).  VP_NT_STORES selects the nontemporal form.
 #ifndef VP_NT_STORES

@@ -24,6 +24,9 @@
 
 #define MB_THREADS 512
 #define MB_STRIP 32
+#ifdef VP_PROBE
+static __device__ int vp_dbg_bits;   // the VP_DBG switches of k_morph_bits_sym
+#endif
 
 
 // 64-bit funnel shifts built from v_alignbit_b32 (full rate) instead of 64-bit variable shifts (quarter rate):
@@ -350,7 +353,7 @@ __device__ __forceinline__ void mb_stage(u64* __restrict__ A, u64* __restrict__ 
 // into straight-line LDS reads.  KIND bit k = stage k dilates.
 template <int NS, int R0, int R1, int R2, int KIND, int STRIP>
 __global__ __launch_bounds__(MB_THREADS, 8) void k_morph_bits_sym(const u64* __restrict__ in, int w, int h, int ww, int strips,
-                                                               u64* __restrict__ out_bits, uint8_t* __restrict__ out_mask, int dbg)
+                                                               u64* __restrict__ out_bits, uint8_t* __restrict__ out_mask)
 {
     extern __shared__ __attribute__((aligned(16))) u64 lds[];
     constexpr int HALO = R0 + (NS > 1 ? R1 : 0) + (NS > 2 ? R2 : 0);
@@ -366,21 +369,21 @@ __global__ __launch_bounds__(MB_THREADS, 8) void k_morph_bits_sym(const u64* __r
     const int lo_r = max(0, -ybase), hi_r = min(rows - 1, h - 1 - ybase);      // the staged rows that are rows of the image
     MB_FOR_WORDS(r, j, i) {
         const int y = ybase + r;
-        A[i] = (y >= 0 && y < h && !(dbg & 2)) ? fin[(size_t)y * ww + j] : 0ull;
+        A[i] = (y >= 0 && y < h && !VP_DBG(VP_DBG_MORPH_NO_LOAD)) ? fin[(size_t)y * ww + j] : 0ull;
     }
     __syncthreads();
-    if (!(dbg & 1)) {
+    if (!VP_DBG(VP_DBG_MORPH_NO_STAGES)) {
         mb_stage<R0, (KIND & 1) != 0, rows>(A, B, ww, ybase, h, lastmask, lo_r, hi_r);
         if constexpr (NS > 1) mb_stage<R1, ((KIND >> 1) & 1) != 0, rows>(A, B, ww, ybase, h, lastmask, lo_r, hi_r);
         if constexpr (NS > 2) mb_stage<R2, ((KIND >> 2) & 1) != 0, rows>(A, B, ww, ybase, h, lastmask, lo_r, hi_r);
     }
     const int nout_rows = min(STRIP, h - y0);
-    if (out_bits && !(dbg & 4)) {
+    if (out_bits && !VP_DBG(VP_DBG_MORPH_NO_BITS)) {
         u64* fo = out_bits + (size_t)frame * h * ww;
         for (int r = threadIdx.x >> 5; r < nout_rows; r += MB_THREADS / 32)
             for (int j = threadIdx.x & 31; j < ww; j += 32) fo[(size_t)(y0 + r) * ww + j] = A[(HALO + r) * ww + j];
     }
-    if (out_mask && !(dbg & 8)) {
+    if (out_mask && !VP_DBG(VP_DBG_MORPH_NO_MASK)) {
         uint8_t* fm = out_mask + (size_t)frame * h * w;
         const int gpr = ww * 4;
         for (int r = threadIdx.x >> 7; r < nout_rows; r += MB_THREADS / 128) {
@@ -402,7 +405,7 @@ static int launch_sym_strip(vp_ctx* ctx, const u64* d_in, int w, int h, int n, u
     if (lds > 64 * 1024) return VP_ERR_UNSUPPORTED;
     vp_prof_scope prof(ctx, VPK_MORPH);
     hipLaunchKernelGGL((k_morph_bits_sym<NS, R0, R1, R2, KIND, STRIP>), dim3((unsigned)((size_t)n * strips)), dim3(MB_THREADS), lds, ctx->stream, d_in, w, h,
-                       ww, strips, d_out_bits, d_out_mask, getenv("VP_MORPH_DBG") ? atoi(getenv("VP_MORPH_DBG")) : 0);
+                       ww, strips, d_out_bits, d_out_mask);
     VP_HIP(ctx, hipGetLastError());
     return VP_OK;
 }
@@ -712,3 +715,7 @@ int vpk_absdiff_sub_u8(vp_ctx* ctx, const uint8_t* a, const uint8_t* b, size_t n
     VP_HIP(ctx, hipGetLastError());
     return VP_OK;
 }
+
+#ifdef VP_PROBE
+int vp_morph_debug_set(int bits) { return hipMemcpyToSymbol(HIP_SYMBOL(vp_dbg_bits), &bits, sizeof bits) == hipSuccess ? 0 : -1; }
+#endif

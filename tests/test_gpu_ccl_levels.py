@@ -199,3 +199,31 @@ def test_4k_noise_frame(ccl_ctx, oracle, lo, numbering):
     assert np.array_equal(out["centroids"][1][:on].view(np.uint64), oce.view(np.uint64))
     assert not out["stats"][1][on:].any()
     assert int(out["nlabels"][0]) == 1 and not out["labels"][0].any()
+
+
+def test_stream_switch_between_handed_over_frames(vp, oracle):
+    """Labelling of handed-over frames on a second stream and back: a frame is labelled, the context moves to a second stream, another
+    frame is labelled there, the context moves back and the first frame is labelled again.  33 x 65 at 50 % noise with the merge
+    capacity at 0 is the smallest frame that is handed over and crosses a 64-pixel word and a strip boundary; all three results equal
+    the oracle's labels, stats and centroids.  Every call here has finished before the stream changes, so the test shows that the
+    crowded-frame kernels work on either stream; it does not tell whether vp_set_stream restarted their accumulator set."""
+    import torch
+    ctx = vp.default_context()
+    rng = np.random.default_rng(33 * 31 + 65)
+    a, b = F.random_mask(rng, 33, 65, 0.5), F.random_mask(rng, 33, 65, 0.5)
+    assert not np.array_equal(a, b)
+    side = torch.cuda.Stream()
+    ctx.set_option(vp.OPT_CCL_LEVELS, 2)
+    ctx.set_option(vp.OPT_CCL_MERGE_CAP, 0)
+    try:
+        _check(oracle, a, 2)
+        ctx.synchronize()
+        ctx.set_stream(side.cuda_stream)
+        _check(oracle, b, 2)
+        ctx.synchronize()
+        ctx.set_stream(None)
+        _check(oracle, a, 2)
+    finally:
+        ctx.synchronize()
+        ctx.set_stream(None)
+        ctx.set_option(vp.OPT_CCL_MERGE_CAP, -1)

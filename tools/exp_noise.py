@@ -1,5 +1,6 @@
 """Crowded-frame labelling alone: noise at one density through grey >= lo -> CCL (+ stats, labels), per-kernel times.
-usage: exp_noise.py [lo=190] ; env B (frames, default 128), K (steps), ML (max labels)"""
+usage: exp_noise.py [lo=190] ; env B (frames, default 128), K (steps), ML (max labels); DBG (VP_DBG_* bits of csrc/vp_internal.h: parts of
+the kernels skipped, results wrong - a probe build only, tools/build_probe.sh with VP_LIB=.../libvp_probe.so)"""
 import json, os, sys, time
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 for p in (ROOT, os.path.join(ROOT, "cuauv-vision-pipeline_amd"), os.path.join(ROOT, "tests")):
@@ -11,6 +12,8 @@ W, H = 1920, 1080
 B = int(os.environ.get("B", "128")); K = int(os.environ.get("K", "5")); ML = int(os.environ.get("ML", "65536"))
 lo = int(sys.argv[1]) if len(sys.argv) > 1 else 190
 ctx = _vp.Context(0)
+DBG = int(os.environ.get("DBG", "0"), 0)
+if DBG: assert _vp.lib().vp_debug_set(DBG) == 0   # (no such symbol in the product build)
 d = torch.from_numpy(np.stack([F.s3_noise(i % 8, W, H) for i in range(B)])).cuda()
 t = {"thr": torch.empty((B, H, W), dtype=torch.uint8, device="cuda"), "lab": torch.empty((B, H, W), dtype=torch.int32, device="cuda"),
      "st": torch.zeros((B, ML, 5), dtype=torch.int32, device="cuda"), "ce": torch.zeros((B, ML, 2), dtype=torch.float64, device="cuda"),
@@ -25,5 +28,5 @@ ctx.synchronize(); dt = (time.perf_counter() - t0) / K
 ctx.profile_begin(K * 24)
 for _ in range(K): ctx.chain_run(desc, b, B)
 pr = ctx.profile_end()
-print(json.dumps({"lo": lo, "dbg": os.environ.get("VP_CCL3_DBG", "0"), "ms_per_step": round(1e3 * dt, 3), "labels": int(t["nl"][0]),
+print(json.dumps({"lo": lo, "dbg": DBG, "ms_per_step": round(1e3 * dt, 3), "labels": int(t["nl"][0]),
                   "kernels_us": {k.replace("k_", ""): round(1e3 * v[0] / v[1], 1) for k, v in pr.items()}}), flush=True)

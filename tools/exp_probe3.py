@@ -1,5 +1,6 @@
 """Phase costs inside k_ccl3_link / k_ccl3_label from a probe build (tools/build_probe.sh; VP_LIB=.../libvp_probe.so): microseconds per
-block summed over its items, noise at the density given.  usage: exp_probe3.py [lo]"""
+block summed over its items, noise at the density given.  usage: exp_probe3.py [lo] ; env DBG: VP_DBG_* bits (csrc/vp_internal.h) set through
+vp_debug_set before the runs - parts of the kernels skipped, results wrong"""
 import ctypes as C, os, sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 for p in (ROOT, os.path.join(ROOT, "cuauv-vision-pipeline_amd"), os.path.join(ROOT, "tests")):
@@ -12,6 +13,7 @@ lo = int(sys.argv[1]) if len(sys.argv) > 1 else 190
 ctx = _vp.Context(0)
 L = _vp.lib()
 L.vp_debug_probe3.argtypes = [C.c_void_p]
+if int(os.environ.get("DBG", "0"), 0): assert L.vp_debug_set(int(os.environ["DBG"], 0)) == 0
 d = torch.from_numpy(np.stack([F.s3_noise(i % 8, W, H) for i in range(B)])).cuda()
 t = {"thr": torch.empty((B, H, W), dtype=torch.uint8, device="cuda"), "lab": torch.empty((B, H, W), dtype=torch.int32, device="cuda"),
      "st": torch.zeros((B, ML, 5), dtype=torch.int32, device="cuda"), "ce": torch.zeros((B, ML, 2), dtype=torch.float64, device="cuda"),
