@@ -186,6 +186,46 @@ int vp_gaussian_blur_dev(vp_ctx* ctx, const uint8_t* d_src, size_t src_stride, i
     return rc;
 }
 
+// cv2.medianBlur: odd windows 1..255, 1..4 channels at every size (cv2's own limits on channels are the caller's business)
+static int median_args(vp_ctx* ctx, const char* who, const void* src, const void* dst, int w, int h, int cn, int ksize)
+{
+    if (!src || !dst || w <= 0 || h <= 0 || h > 65535 || cn < 1 || cn > 4 || (size_t)w * cn > ((size_t)1 << 30) || ksize <= 0 || !(ksize & 1) || ksize > 255)
+        return vp_fail(ctx, VP_ERR_INVALID, who);
+    return VP_OK;
+}
+
+int vp_median_blur_u8(vp_ctx* ctx, const uint8_t* src, int w, int h, int cn, int ksize, uint8_t* dst)
+{
+    VP_TRY(check_ctx(ctx));
+    VP_TRY(median_args(ctx, "vp_median_blur_u8 arguments", src, dst, w, h, cn, ksize));
+    const size_t rowbytes = (size_t)w * cn, nbytes = rowbytes * h;
+    VP_TRY(vp_ws_reserve(ctx, 2 * vp_align(nbytes) + 1024));
+    TAKE(d_src, uint8_t*, nbytes);
+    TAKE(d_dst, uint8_t*, nbytes);
+    VP_TRY(h2d(ctx, d_src, src, nbytes));
+    VP_TRY(vpk_median_blur(ctx, d_src, rowbytes, w, h, cn, ksize, 0, nullptr, d_dst, nullptr, nullptr));
+    VP_TRY(d2h(ctx, dst, d_dst, nbytes));
+    return vp_synchronize(ctx);
+}
+
+int vp_median_blur_dev(vp_ctx* ctx, const uint8_t* d_src, size_t src_stride, int w, int h, int cn, int ksize, int binary_hint,
+                       const unsigned long long* d_src_bits, uint8_t* d_dst, unsigned long long* d_dst_bits, int* made_bits)
+{
+    VP_TRY(check_ctx(ctx));
+    VP_TRY(median_args(ctx, "vp_median_blur_dev arguments", d_src, d_dst, w, h, cn, ksize));
+    const size_t rowbytes = (size_t)w * cn, nbytes = rowbytes * h, sbytes = strided_bytes(src_stride, rowbytes, h);
+    if (src_stride < rowbytes || dev_overlap(d_src, sbytes, d_dst, nbytes))
+        return vp_fail(ctx, VP_ERR_INVALID, "vp_median_blur_dev: src_stride, or dst overlaps src");
+    const size_t pbytes = (size_t)vp_ww(w) * 8 * h;
+    if (((uintptr_t)d_src_bits | (uintptr_t)d_dst_bits) & 7u) return vp_fail(ctx, VP_ERR_INVALID, "vp_median_blur_dev: a bit plane is not 8-byte aligned");
+    if ((d_src_bits && dev_overlap(d_src_bits, pbytes, d_dst, nbytes)) ||
+        (d_dst_bits && (dev_overlap(d_dst_bits, pbytes, d_dst, nbytes) || dev_overlap(d_dst_bits, pbytes, d_src, sbytes) ||
+                        (d_src_bits && dev_overlap(d_dst_bits, pbytes, d_src_bits, pbytes)))))
+        return vp_fail(ctx, VP_ERR_INVALID, "vp_median_blur_dev: a bit plane overlaps an image it is not the plane of");
+    return vpk_median_blur(ctx, d_src, src_stride, w, h, cn, ksize, binary_hint != 0, reinterpret_cast<const u64*>(d_src_bits), d_dst,
+                           reinterpret_cast<u64*>(d_dst_bits), made_bits);
+}
+
 static int resize_args(vp_ctx* ctx, const char* who, const void* src, const void* dst, int w, int h, int cn, int dw, int dh, double inv_sx, double inv_sy)
 {
     if (!src || !dst || w <= 0 || h <= 0 || dw <= 0 || dh <= 0 || dh > 65535 || cn < 1 || cn > 4 || !std::isfinite(inv_sx) || !std::isfinite(inv_sy) ||

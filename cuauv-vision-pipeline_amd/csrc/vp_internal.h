@@ -73,6 +73,7 @@ struct vp_ctx {
     int c3_acc_dirty;             // not known to be all empty (a call cut short, another stream): c3_acc_acquire reinitialises it before use
     int hough_global;             // 1: every Hough vote is a global atomic (VP_OPT_HOUGH_LDS 0); 0 (default): rows counted in LDS where they fit
     int blur_onepass;             // VP_OPT_BLUR_ONEPASS: -1 (default) the measured choice, 1 the one-pass kernel wherever its tile fits, 0 always two passes
+    int median_mask;              // VP_OPT_MEDIAN_MASK: -1 (default) the measured choice, 1 the mask kernel for every mask it can serve, 0 never
     int hc_global;                // 1: HoughCircles radius histograms always in device memory (VP_OPT_HOUGH_CIRCLES_LDS 0); 0 (default): in LDS where they fit
     void* hc_hist;                // HoughCircles radius histograms of the global form: grow-only, sized per call by its centre count
     size_t hc_hist_bytes;
@@ -194,6 +195,13 @@ int vpk_gaussian_blur(vp_ctx* ctx, const uint8_t* d_src, int w, int h, int cn, c
 // the blur in one launch, the 8.8 intermediate kept in LDS (k_gauss_onepass); kernels for which vp_gaussian_onepass_fits only
 bool vp_gaussian_onepass_fits(int kw, int kh);
 int vpk_gaussian_blur_onepass(vp_ctx* ctx, const uint8_t* d_src, size_t sstride, int w, int h, int cn, const uint16_t* d_taps, int kw, int kh, uint8_t* d_dst);
+
+// ---- median filter (vp_median.hip) -------------------------------------------------------------------
+// cv2.medianBlur, ksize odd 1..255, borders replicated; sstride: bytes between source rows.  binary_hint: the source holds only 0 / 255;
+// d_src_bits / d_dst_bits (nullable): bit planes of such a single-channel mask, read / written by the mask kernel; *made_bits
+// (nullable) says whether the result's plane was written, and is left alone when the launch fails
+int vpk_median_blur(vp_ctx* ctx, const uint8_t* d_src, size_t sstride, int w, int h, int cn, int ksize, int binary_hint, const u64* d_src_bits, uint8_t* d_dst,
+                    u64* d_dst_bits, int* made_bits);
 
 // ---- morphology (vp_morph.hip) ---------------------------------------------------------------
 struct vp_bitstage { int dilate; int l, r, u, d; };  // window [-l, r] x [-u, d]

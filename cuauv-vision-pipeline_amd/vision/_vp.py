@@ -39,6 +39,7 @@ OPT_FLAT_OPS = 4
 OPT_HOUGH_LDS = 5
 OPT_HOUGH_CIRCLES_LDS = 6
 OPT_BLUR_ONEPASS = 7
+OPT_MEDIAN_MASK = 8
 THRESH_BINARY, THRESH_BINARY_INV, THRESH_TRUNC, THRESH_TOZERO, THRESH_TOZERO_INV = 0, 1, 2, 3, 4
 HOUGH_GRADIENT = 3
 # return codes of include/vp.h
@@ -214,6 +215,9 @@ _SIGS = {
     "vp_split_u8_dev": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "vp_merge_u8_dev": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_int, C.c_void_p]),
     "vp_count_nonzero_u8_dev": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.POINTER(C.c_uint64)]),
+    "vp_median_blur_u8": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p]),
+    "vp_median_blur_dev": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p,
+                                     C.POINTER(C.c_int)]),
 }
 
 

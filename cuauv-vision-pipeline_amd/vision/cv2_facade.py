@@ -710,6 +710,30 @@ def _gaussian_blur(src, ksize, sigmaX, sigmaY, borderType):
     return out
 
 
+def medianBlur(src, ksize, dst=None):
+    """cv2.medianBlur on uint8 images: the exact order statistic over a replicated border, on the GPU (libvp vp_median_blur_*).
+    Positional order as in cv2: (src, ksize, dst).  A DeviceMat stays in HBM (vision.utils.transform.median_blur)."""
+    src, _ = _device_source(src)
+    try:
+        k = int(ksize)
+    except (TypeError, ValueError):
+        raise error("medianBlur: ksize must be an integer") from None
+    if k <= 0 or k % 2 == 0:
+        raise error("medianBlur: ksize must be odd and greater than 0")
+    if k > 255:
+        raise error("medianBlur: ksize above 255 is outside the accelerated path")
+    if src.dtype != np.uint8:
+        raise error("medianBlur: only uint8 images are on the accelerated path")
+    if src.ndim not in (2, 3) or src.size == 0:
+        raise error("medianBlur: expected a non-empty (h, w) or (h, w, c) image")
+    cn = 1 if src.ndim == 2 else src.shape[2]
+    if cn > 4:
+        raise error("medianBlur: at most 4 channels")
+    if cn == 2 and k > 5:
+        raise error("medianBlur: 2 channels only with ksize 3 or 5 (cv2 asserts 1, 3 or 4 channels above)")
+    return _into(dst, _transform.median_blur(src, k))
+
+
 INTER_LINEAR = 1
 WARP_INVERSE_MAP = 16
 

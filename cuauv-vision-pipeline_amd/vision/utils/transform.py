@@ -116,6 +116,44 @@ def simple_gaussian_blur(mat: np.ndarray, kernel_size: int, std_dev: float) -> n
     return cv2_facade.GaussianBlur(mat, (kernel_size, kernel_size), std_dev)
 
 
+def median_blur(mat: np.ndarray, ksize: int) -> np.ndarray:
+    """cv2.medianBlur on uint8 images of 1..4 channels, ksize odd in 1..255 (libvp vp_median_blur_u8 / vp_median_blur_dev).  Not a name
+    of the reference's utils/transform.py: the despeckling step in front of a labelling or a contour pass that keeps thin structures
+    (OPEN 5x5 eats them).  numpy in gives numpy out; a DeviceMat gives a DeviceMat and stays in HBM.  On a mask this library made
+    (`binary`) the filter is a majority vote on the mask's bit plane, the result is a mask again and brings its own bit plane where
+    rows are whole words, so range_threshold -> median_blur -> connected_components / find_contours never unpacks a bit."""
+    mat = as_mat(mat)
+    if not isinstance(mat, (np.ndarray, DeviceMat)) or mat.dtype != np.uint8 or mat.ndim not in (2, 3) or mat.size == 0:
+        raise TypeError("expected a non-empty uint8 (h, w) or (h, w, c) image")
+    cn = 1 if mat.ndim == 2 else mat.shape[2]
+    if cn > 4:
+        raise ValueError("at most 4 channels")
+    ksize = int(ksize)
+    if ksize <= 0 or ksize % 2 == 0 or ksize > 255:
+        raise ValueError("ksize must be an odd integer in 1..255")
+    ctx = _vp.default_context()
+    h, w = mat.shape[:2]
+    if isinstance(mat, DeviceMat):
+        from vision.devmat import _DevBuf
+        mat.refresh_device(ctx)
+        src_ptr = mat.dev_ptr                            # (launches a deferred source: its bit plane comes out of that launch)
+        binary = mat.binary                              # the median of 0 / 255 values is 0 or 255, whatever the channels and the window
+        vote = binary and cn == 1 and 3 <= ksize <= 63   # what the bit-plane kernel serves: only then is a plane of use (the hint is ignored elsewhere)
+        plane = mat.bit_plane(ctx) if (vote and mat.ndim == 2) else None
+        out = DeviceMat(ctx, mat.shape, binary=binary)
+        bits = _DevBuf(ctx, h * (w // 64) * 8) if (vote and mat.ndim == 2 and w % 64 == 0) else None
+        made = _vp.C.c_int(0)
+        _vp.check(_vp.lib().vp_median_blur_dev(ctx.handle, src_ptr, w * cn, w, h, cn, ksize, 1 if binary else 0, None if plane is None else plane.ptr,
+                                               out.dev_ptr, None if bits is None else bits.ptr, _vp.C.byref(made)), ctx.handle)
+        if made.value:
+            out._bits = bits
+        return out
+    src = np.ascontiguousarray(mat)
+    out = np.empty_like(src)
+    _vp.check(_vp.lib().vp_median_blur_u8(ctx.handle, _vp.ptr(src), w, h, cn, ksize, _vp.ptr(out)), ctx.handle)
+    return out
+
+
 def rotate(mat: np.ndarray, degrees: float) -> np.ndarray:
     """utils/transform.py:180-196: rotation about the image centre, positive = counterclockwise, borders replicated."""
     from vision import cv2_facade

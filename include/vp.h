@@ -84,9 +84,13 @@ int vp_synchronize(vp_ctx* ctx);
  * (160 KiB); 0 keeps it in device memory, as for more bins than that (the tests reach that path at small sizes).  Results are identical.
  * VP_OPT_BLUR_ONEPASS (1, 0 or -1, default -1): which kernels vp_gaussian_blur_dev runs.  1 = the one-pass kernel (rows and halo staged
  * in LDS, the 16-bit intermediate never written to device memory) wherever its tile fits, i.e. kernels up to 31 on both axes; 0 = always
- * the two passes of vp_gaussian_blur_u8; -1 = the measured choice.  Results are identical. */
+ * the two passes of vp_gaussian_blur_u8; -1 = the measured choice.  Results are identical.
+ * VP_OPT_MEDIAN_MASK (1, 0 or -1, default -1; the environment variable of the same name sets 1 or 0 at vp_create): which kernel
+ * vp_median_blur_dev runs on a single-channel image the caller calls a 0/255 mask (binary_hint).  1 = the bit-plane majority vote for
+ * every window it can serve (3..63); 0 = never, the general kernels; -1 = the measured choice (whenever the source's bit plane is
+ * passed, and from window 5 on without one).  Results are identical. */
 enum { VP_OPT_CHAIN_STREAMS = 1, VP_OPT_CCL_LEVELS = 2, VP_OPT_CCL_MERGE_CAP = 3, VP_OPT_FLAT_OPS = 4, VP_OPT_HOUGH_LDS = 5,
-       VP_OPT_HOUGH_CIRCLES_LDS = 6, VP_OPT_BLUR_ONEPASS = 7 };
+       VP_OPT_HOUGH_CIRCLES_LDS = 6, VP_OPT_BLUR_ONEPASS = 7, VP_OPT_MEDIAN_MASK = 8 };
 int vp_set_option(vp_ctx* ctx, int option, int value);
 /* HIP-event stopwatch on the context's stream (bench.py: roofline.achieved). */
 int vp_timer_start(vp_ctx* ctx);
@@ -521,6 +525,23 @@ int vp_ccl_dev(vp_ctx* ctx, const uint8_t* src_dev, size_t src_stride, int w, in
                int32_t* stats_host, double* centroids_host, int max_labels, int32_t* n_labels);
 int vp_ccl_bits_dev(vp_ctx* ctx, const unsigned long long* bits_dev, int w, int h, int numbering, int32_t* labels_dev,
                     int32_t* stats_host, double* centroids_host, int max_labels, int32_t* n_labels);
+
+/* ---- median filter ------------------------------------------------------------------------------------------------------------------ *
+ * cv2.medianBlur on uint8 images of 1..4 interleaved channels: dst[y][x][c] is the median of the ksize x ksize window of channel c
+ * centred on (x, y), coordinates outside the image clamped to the nearest edge pixel (BORDER_REPLICATE).  ksize is odd, 1..255
+ * (1 copies); h <= 65535.  An order statistic: nothing is rounded, the result equals OpenCV's on every code path of its own.
+ * vp_median_blur_u8: packed host images; stages, runs the kernels of the device form and synchronises.
+ * vp_median_blur_dev: src_dev is read in place (row stride in bytes, at least w * cn), dst_dev is packed and must not overlap it
+ *   (VP_ERR_INVALID, nothing is launched); enqueued on the context's stream, never synchronises.  binary_hint != 0 is the caller's
+ *   promise that src holds only 0 and 255, as for vp_morph_u8_dev: a single-channel mask with ksize <= 63 is then filtered as a
+ *   majority vote on bits (see VP_OPT_MEDIAN_MASK).  src_bits_dev (nullable): the mask's bit plane in the layout of
+ *   vp_inrange_u8_bits_dev / vp_bitwise_u8_dev ((w + 63) / 64 words per row, bit x % 64 of word x / 64 is pixel x), read instead of
+ *   the bytes.  dst_bits_dev (nullable): receives the result's bit plane when the mask kernel ran and w % 64 == 0; *made_bits
+ *   (nullable) says whether it did, and is left untouched when the call fails.  The planes are 8-byte aligned and overlap neither
+ *   image nor each other. */
+int vp_median_blur_u8(vp_ctx* ctx, const uint8_t* src_host, int w, int h, int cn, int ksize, uint8_t* dst_host);
+int vp_median_blur_dev(vp_ctx* ctx, const uint8_t* src_dev, size_t src_stride, int w, int h, int cn, int ksize, int binary_hint,
+                       const unsigned long long* src_bits_dev, uint8_t* dst_dev, unsigned long long* dst_bits_dev, int* made_bits);
 
 /* ---- element-wise operators on device images ------------------------------------------------------------------------------------ *
  * Packed uint8 device images; every entry enqueues on the context's stream and returns at once, except vp_count_nonzero_u8_dev.
