@@ -4,6 +4,7 @@
 // and only enqueue (the histogram and the counters bring numbers back and synchronise for them).  Each host / device pair shares
 // one *_args check, which also normalises the parameters; what differs between the forms stays in the entry.
 #include "vp_api_util.h"
+#include "vp_deriv_plan.h"
 
 extern "C" {
 
@@ -224,6 +225,110 @@ int vp_median_blur_dev(vp_ctx* ctx, const uint8_t* d_src, size_t src_stride, int
         return vp_fail(ctx, VP_ERR_INVALID, "vp_median_blur_dev: a bit plane overlaps an image it is not the plane of");
     return vpk_median_blur(ctx, d_src, src_stride, w, h, cn, ksize, binary_hint != 0, reinterpret_cast<const u64*>(d_src_bits), d_dst,
                            reinterpret_cast<u64*>(d_dst_bits), made_bits);
+}
+
+// cv2.Sobel / Scharr / Laplacian / spatialGradient: the plan is the argument check (vp_deriv_plan.h), shared by the four entries
+static int deriv_args(vp_ctx* ctx, const char* who, const void* src, const void* dst, const void* dst2, int w, int h, int cn, int op, int dx, int dy, int ksize,
+                      int ddepth, int border, vp_deriv_plan* P)
+{
+    if (!src || !dst || !dst2 || (op != VP_DERIV_SOBEL && op != VP_DERIV_SCHARR && op != VP_DERIV_LAPLACIAN && op != VP_DV_OP_SPATIAL_GRADIENT))
+        return vp_fail(ctx, VP_ERR_INVALID, who);
+    *P = vp_deriv_make_plan(w, h, cn, op, dx, dy, ksize, ddepth, border);
+    if (!P->ok) return vp_fail(ctx, VP_ERR_INVALID, who);
+    return VP_OK;
+}
+
+// what the device forms add: the stride, the destination's alignment to its element, and no overlap
+static int deriv_dev_args(vp_ctx* ctx, const char* who, const void* d_src, size_t src_stride, size_t rowbytes, int h, const void* d_dst, size_t esize)
+{
+    if (src_stride < rowbytes || ((uintptr_t)d_dst & (esize - 1)) || dev_overlap(d_src, strided_bytes(src_stride, rowbytes, h), d_dst, rowbytes * h * esize))
+        return vp_fail(ctx, VP_ERR_INVALID, who);
+    return VP_OK;
+}
+
+int vp_deriv_u8(vp_ctx* ctx, const uint8_t* src, int w, int h, int cn, int op, int dx, int dy, int ksize, int ddepth, int border, void* dst)
+{
+    VP_TRY(check_ctx(ctx));
+    vp_deriv_plan P;
+    VP_TRY(deriv_args(ctx, "vp_deriv_u8 arguments", src, dst, dst, w, h, cn, op == VP_DV_OP_SPATIAL_GRADIENT ? -1 : op, dx, dy, ksize, ddepth, border, &P));
+    const size_t rowbytes = (size_t)w * cn, nbytes = rowbytes * h, obytes = nbytes * P.esize;
+    VP_TRY(vp_ws_reserve(ctx, vp_align(nbytes) + vp_align(obytes) + 1024));
+    TAKE(d_src, uint8_t*, nbytes);
+    TAKE(d_dst, uint8_t*, obytes);
+    VP_TRY(h2d(ctx, d_src, src, nbytes));
+    VP_TRY(vpk_deriv(ctx, d_src, rowbytes, w, h, cn, P, d_dst, nullptr));
+    VP_TRY(d2h(ctx, dst, d_dst, obytes));
+    return vp_synchronize(ctx);
+}
+
+int vp_deriv_dev(vp_ctx* ctx, const uint8_t* d_src, size_t src_stride, int w, int h, int cn, int op, int dx, int dy, int ksize, int ddepth, int border, void* d_dst)
+{
+    VP_TRY(check_ctx(ctx));
+    vp_deriv_plan P;
+    VP_TRY(deriv_args(ctx, "vp_deriv_dev arguments", d_src, d_dst, d_dst, w, h, cn, op == VP_DV_OP_SPATIAL_GRADIENT ? -1 : op, dx, dy, ksize, ddepth, border, &P));
+    VP_TRY(deriv_dev_args(ctx, "vp_deriv_dev: src_stride, dst is not aligned to its element, or dst overlaps src", d_src, src_stride, (size_t)w * cn, h, d_dst, P.esize));
+    return vpk_deriv(ctx, d_src, src_stride, w, h, cn, P, d_dst, nullptr);
+}
+
+int vp_spatial_gradient_u8(vp_ctx* ctx, const uint8_t* src, int w, int h, int ksize, int border, int16_t* dx, int16_t* dy)
+{
+    VP_TRY(check_ctx(ctx));
+    vp_deriv_plan P;
+    VP_TRY(deriv_args(ctx, "vp_spatial_gradient_u8 arguments", src, dx, dy, w, h, 1, VP_DV_OP_SPATIAL_GRADIENT, 1, 1, ksize, VP_DEPTH_16S, border, &P));
+    const size_t nbytes = (size_t)w * h, obytes = nbytes * 2;
+    VP_TRY(vp_ws_reserve(ctx, vp_align(nbytes) + 2 * vp_align(obytes) + 1024));
+    TAKE(d_src, uint8_t*, nbytes);
+    TAKE(d_dx, uint8_t*, obytes);
+    TAKE(d_dy, uint8_t*, obytes);
+    VP_TRY(h2d(ctx, d_src, src, nbytes));
+    VP_TRY(vpk_deriv(ctx, d_src, (size_t)w, w, h, 1, P, d_dx, d_dy));
+    VP_TRY(d2h(ctx, dx, d_dx, obytes));
+    VP_TRY(d2h(ctx, dy, d_dy, obytes));
+    return vp_synchronize(ctx);
+}
+
+int vp_spatial_gradient_dev(vp_ctx* ctx, const uint8_t* d_src, size_t src_stride, int w, int h, int ksize, int border, int16_t* d_dx, int16_t* d_dy)
+{
+    VP_TRY(check_ctx(ctx));
+    vp_deriv_plan P;
+    VP_TRY(deriv_args(ctx, "vp_spatial_gradient_dev arguments", d_src, d_dx, d_dy, w, h, 1, VP_DV_OP_SPATIAL_GRADIENT, 1, 1, ksize, VP_DEPTH_16S, border, &P));
+    const char* who = "vp_spatial_gradient_dev: src_stride, a plane is not aligned to its element, or the planes overlap src or each other";
+    VP_TRY(deriv_dev_args(ctx, who, d_src, src_stride, (size_t)w, h, d_dx, 2));
+    VP_TRY(deriv_dev_args(ctx, who, d_src, src_stride, (size_t)w, h, d_dy, 2));
+    if (dev_overlap(d_dx, (size_t)w * h * 2, d_dy, (size_t)w * h * 2)) return vp_fail(ctx, VP_ERR_INVALID, who);
+    return vpk_deriv(ctx, d_src, src_stride, w, h, 1, P, d_dx, d_dy);
+}
+
+static int csa_args(vp_ctx* ctx, const char* who, const void* src, const void* dst, int depth, size_t n, size_t* esize)
+{
+    if (!src || !dst || n == 0 || n > ((size_t)1 << 36) || (depth != VP_DEPTH_8U && depth != VP_DEPTH_16S && depth != VP_DEPTH_32F && depth != VP_DEPTH_64F))
+        return vp_fail(ctx, VP_ERR_INVALID, who);
+    *esize = depth == VP_DEPTH_8U ? 1 : depth == VP_DEPTH_16S ? 2 : depth == VP_DEPTH_32F ? 4 : 8;
+    return VP_OK;
+}
+
+int vp_convert_scale_abs_u8(vp_ctx* ctx, const void* src, int depth, size_t n, uint8_t* dst)
+{
+    VP_TRY(check_ctx(ctx));
+    size_t esize;
+    VP_TRY(csa_args(ctx, "vp_convert_scale_abs_u8 arguments", src, dst, depth, n, &esize));
+    VP_TRY(vp_ws_reserve(ctx, vp_align(n * esize) + vp_align(n) + 1024));
+    TAKE(d_src, uint8_t*, n * esize);
+    TAKE(d_dst, uint8_t*, n);
+    VP_TRY(h2d(ctx, d_src, src, n * esize));
+    VP_TRY(vpk_convert_scale_abs(ctx, d_src, depth, n, d_dst));
+    VP_TRY(d2h(ctx, dst, d_dst, n));
+    return vp_synchronize(ctx);
+}
+
+int vp_convert_scale_abs_dev(vp_ctx* ctx, const void* d_src, int depth, size_t n, uint8_t* d_dst)
+{
+    VP_TRY(check_ctx(ctx));
+    size_t esize;
+    VP_TRY(csa_args(ctx, "vp_convert_scale_abs_dev arguments", d_src, d_dst, depth, n, &esize));
+    if (((uintptr_t)d_src & (esize - 1)) || dev_overlap(d_src, n * esize, d_dst, n))
+        return vp_fail(ctx, VP_ERR_INVALID, "vp_convert_scale_abs_dev: src is not aligned to its element, or dst overlaps src");
+    return vpk_convert_scale_abs(ctx, d_src, depth, n, d_dst);
 }
 
 static int resize_args(vp_ctx* ctx, const char* who, const void* src, const void* dst, int w, int h, int cn, int dw, int dh, double inv_sx, double inv_sy)

@@ -256,6 +256,43 @@ __global__ __launch_bounds__(256) void k_count_nonzero_u8(const uint8_t* __restr
     }
 }
 
+// ---- convertScaleAbs (alpha 1, beta 0) --------------------------------------------------------------------------------------------
+// saturate_cast<uchar>(|v|): integers clamp, floats round half to even first (v_rndne) and NaN gives 0
+__device__ __forceinline__ u32 csa_one(uint8_t v) { return v; }
+__device__ __forceinline__ u32 csa_one(int16_t v) { return (u32)min(abs((int)v), 255); }
+__device__ __forceinline__ u32 csa_one(float v) { const float a = fabsf(v); return a == a ? (a >= 255.0f ? 255u : (u32)rintf(a)) : 0u; }
+__device__ __forceinline__ u32 csa_one(double v) { const double a = fabs(v); return a == a ? (a >= 255.0 ? 255u : (u32)rint(a)) : 0u; }
+
+// lane = 16 results = one 16-B store; the 16 source elements are sizeof(S) 16-B loads when al_s (src + head is 16-B aligned), else
+// element loads.  Head and tail (see the top of this file) go element by element through the first lanes of block 0.
+template <typename S>
+__global__ __launch_bounds__(256) void k_convert_scale_abs(const S* __restrict__ src, size_t n, size_t head, size_t ngroups, int al_s, uint8_t* __restrict__ dst)
+{
+    const size_t t = (size_t)blockIdx.x * 256 + threadIdx.x;
+    for (size_t g = t; g < ngroups; g += (size_t)gridDim.x * 256) {
+        const size_t i0 = head + g * 16;
+        union { uint4 q[sizeof(S)]; S v[16]; } in;
+        if (al_s) {
+#pragma unroll
+            for (int j = 0; j < (int)sizeof(S); j++) in.q[j] = reinterpret_cast<const uint4*>(src + i0)[j];
+        } else {
+#pragma unroll
+            for (int k = 0; k < 16; k++) in.v[k] = src[i0 + k];
+        }
+        u32 out[4] = {0, 0, 0, 0};
+#pragma unroll
+        for (int k = 0; k < 16; k++) out[k >> 2] |= csa_one(in.v[k]) << (8 * (k & 3));
+        vp_store16(dst + i0, out[0], out[1], out[2], out[3]);
+    }
+    if (blockIdx.x == 0) {
+        const size_t tail0 = head + ngroups * 16, rest = head + (n - tail0);
+        for (size_t i = threadIdx.x; i < rest; i += 256) {
+            const size_t at = i < head ? i : tail0 + (i - head);
+            dst[at] = (uint8_t)csa_one(src[at]);
+        }
+    }
+}
+
 struct ew_split { size_t head, ngroups; unsigned blocks; };
 
 inline bool al16(const void* p) { return ((uintptr_t)p & 15u) == 0; }
@@ -362,6 +399,26 @@ int vpk_count_nonzero_u8(vp_ctx* ctx, const uint8_t* src, size_t n, u64* d_total
     VP_HIP(ctx, hipMemsetAsync(d_total, 0, sizeof(u64), ctx->stream));
     const ew_split s = ew_plan(ctx, src, n, true);
     hipLaunchKernelGGL(k_count_nonzero_u8, dim3(s.blocks), dim3(256), 0, ctx->stream, src, n, s.head, s.ngroups, d_total);
+    VP_HIP(ctx, hipGetLastError());
+    return VP_OK;
+}
+
+template <typename S>
+static void csa_launch(vp_ctx* ctx, const void* d_src, size_t n, uint8_t* d_dst)
+{
+    const ew_split s = ew_plan(ctx, d_dst, n, true);
+    const S* src = static_cast<const S*>(d_src);
+    hipLaunchKernelGGL(k_convert_scale_abs<S>, dim3(s.blocks), dim3(256), 0, ctx->stream, src, n, s.head, s.ngroups, (int)al16(src + s.head), d_dst);
+}
+
+int vpk_convert_scale_abs(vp_ctx* ctx, const void* d_src, int depth, size_t n, uint8_t* d_dst)
+{
+    switch (depth) {
+        case VP_DEPTH_8U: csa_launch<uint8_t>(ctx, d_src, n, d_dst); break;
+        case VP_DEPTH_16S: csa_launch<int16_t>(ctx, d_src, n, d_dst); break;
+        case VP_DEPTH_32F: csa_launch<float>(ctx, d_src, n, d_dst); break;
+        default: csa_launch<double>(ctx, d_src, n, d_dst); break;
+    }
     VP_HIP(ctx, hipGetLastError());
     return VP_OK;
 }

@@ -203,6 +203,14 @@ int vpk_gaussian_blur_onepass(vp_ctx* ctx, const uint8_t* d_src, size_t sstride,
 int vpk_median_blur(vp_ctx* ctx, const uint8_t* d_src, size_t sstride, int w, int h, int cn, int ksize, int binary_hint, const u64* d_src_bits, uint8_t* d_dst,
                     u64* d_dst_bits, int* made_bits);
 
+// ---- derivative filters (vp_deriv.hip; the plan: vp_deriv_plan.h) --------------------------------------
+// cv2.Sobel / Scharr / Laplacian / spatialGradient as vp_deriv_make_plan accepted them; sstride: bytes between source rows; d_dst packed,
+// P.esize bytes per element; d_dst2: spatialGradient's dy plane (d_dst is dx)
+struct vp_deriv_plan;
+int vpk_deriv(vp_ctx* ctx, const uint8_t* d_src, size_t sstride, int w, int h, int cn, const vp_deriv_plan& P, void* d_dst, void* d_dst2);
+// cv2.convertScaleAbs, alpha 1, beta 0 (vp_elementwise.hip): n elements of depth VP_DEPTH_* to saturate_cast<uchar>(|v|)
+int vpk_convert_scale_abs(vp_ctx* ctx, const void* d_src, int depth, size_t n, uint8_t* d_dst);
+
 // ---- morphology (vp_morph.hip) ---------------------------------------------------------------
 struct vp_bitstage { int dilate; int l, r, u, d; };  // window [-l, r] x [-u, d]
 #define VP_MAX_STAGES 32

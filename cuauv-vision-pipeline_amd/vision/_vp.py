@@ -46,6 +46,9 @@ HOUGH_GRADIENT = 3
 OK, ERR_INVALID, ERR_HIP, ERR_NOMEM, ERR_UNSUPPORTED, ERR_CAPACITY = 0, -1, -2, -3, -4, -5
 BITWISE_AND, BITWISE_OR, BITWISE_XOR, BITWISE_NOT = 0, 1, 2, 3
 ARITH_ADD, ARITH_SUB, ARITH_ABSDIFF = 0, 1, 2
+DERIV_SOBEL, DERIV_SCHARR, DERIV_LAPLACIAN = 0, 1, 2
+DEPTH_8U, DEPTH_16S, DEPTH_32F, DEPTH_64F = 0, 3, 5, 6
+BORDER_CONSTANT, BORDER_REPLICATE, BORDER_REFLECT, BORDER_REFLECT_101, BORDER_ISOLATED = 0, 1, 2, 4, 16
 PROF_KERNELS = 15
 
 
@@ -218,6 +221,12 @@ _SIGS = {
     "vp_median_blur_u8": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p]),
     "vp_median_blur_dev": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p,
                                      C.POINTER(C.c_int)]),
+    "vp_deriv_u8": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p]),
+    "vp_deriv_dev": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p]),
+    "vp_spatial_gradient_u8": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
+    "vp_spatial_gradient_dev": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
+    "vp_convert_scale_abs_u8": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_size_t, C.c_void_p]),
+    "vp_convert_scale_abs_dev": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_size_t, C.c_void_p]),
 }
 
 

@@ -40,6 +40,8 @@ ADAPTIVE_THRESH_MEAN_C, ADAPTIVE_THRESH_GAUSSIAN_C = 0, 1
 THRESH_BINARY, THRESH_BINARY_INV, THRESH_TRUNC, THRESH_TOZERO, THRESH_TOZERO_INV = 0, 1, 2, 3, 4
 THRESH_MASK, THRESH_OTSU, THRESH_TRIANGLE = 7, 8, 16
 CV_32S = 4
+CV_16S, CV_32F, CV_64F = 3, 5, 6
+FILTER_SCHARR = -1
 CV_PI = math.pi
 HOUGH_GRADIENT, HOUGH_GRADIENT_ALT = 3, 4
 
@@ -176,8 +178,11 @@ def getStructuringElement(shape, ksize):
 
 BORDER_CONSTANT = 0
 BORDER_REPLICATE = 1
-BORDER_REFLECT_101 = 4
+BORDER_REFLECT = 2
+BORDER_WRAP = 3
+BORDER_REFLECT_101 = BORDER_REFLECT101 = 4
 BORDER_DEFAULT = 4
+BORDER_ISOLATED = 16
 
 
 def _into(dst, result):
@@ -732,6 +737,66 @@ def medianBlur(src, ksize, dst=None):
     if cn == 2 and k > 5:
         raise error("medianBlur: 2 channels only with ksize 3 or 5 (cv2 asserts 1, 3 or 4 channels above)")
     return _into(dst, _transform.median_blur(src, k))
+
+
+# ---- derivative filters (libvp vp_deriv.hip) ------------------------------------------------------------------------------------------
+def _deriv_call(name, fn, src, ddepth, scale, delta, borderType, *args):
+    """What cv2 rejects, and the two restrictions of this path: scale = 1 and delta = 0 only."""
+    src, _ = _device_source(src)
+    if src.dtype != np.uint8:
+        raise error(f"{name}: only uint8 sources are on the accelerated path")
+    if src.ndim not in (2, 3) or src.size == 0:
+        raise error(f"{name}: expected a non-empty (h, w) or (h, w, c) image")
+    if src.ndim == 3 and src.shape[2] > 4:
+        raise error(f"{name}: at most 4 channels")
+    if scale != 1 or delta != 0:
+        raise error(f"{name}: scale != 1 or delta != 0 takes OpenCV's float paths, which this library does not restate (DESIGN.md section 7)")
+    try:
+        return fn(src, *args, ddepth, BORDER_DEFAULT if borderType is None else borderType)
+    except (TypeError, ValueError) as e:
+        raise error(f"{name}: {e}") from None
+
+
+def Sobel(src, ddepth, dx, dy, dst=None, ksize=3, scale=1, delta=0, borderType=BORDER_DEFAULT):
+    """cv2.Sobel on uint8 images with scale = 1 and delta = 0, on the GPU: the exact integer correlation, cast to ddepth (-1 / CV_8U,
+    CV_16S, CV_32F, CV_64F) as saturate_cast does.  Positional order as in cv2.  A DeviceMat stays in HBM and comes back with the
+    requested dtype."""
+    return _into(dst, _deriv_call("Sobel", _transform.sobel, src, ddepth, scale, delta, borderType, dx, dy, ksize))
+
+
+def Scharr(src, ddepth, dx, dy, dst=None, scale=1, delta=0, borderType=BORDER_DEFAULT):
+    """cv2.Scharr under the rules of Sobel above: [-1 0 1] with [3 10 3], dx + dy == 1."""
+    return _into(dst, _deriv_call("Scharr", _transform.scharr, src, ddepth, scale, delta, borderType, dx, dy))
+
+
+def Laplacian(src, ddepth, dst=None, ksize=1, scale=1, delta=0, borderType=BORDER_DEFAULT):
+    """cv2.Laplacian under the rules of Sobel above: ksize 1, 3 (the 3x3 kernels), 5 or 7 (Sobel(2, 0) + Sobel(0, 2))."""
+    return _into(dst, _deriv_call("Laplacian", _transform.laplacian, src, ddepth, scale, delta, borderType, ksize))
+
+
+def spatialGradient(src, dx=None, dy=None, ksize=3, borderType=BORDER_DEFAULT):
+    """cv2.spatialGradient: (dx, dy) = (Sobel(1, 0, 3), Sobel(0, 1, 3)) as int16 from one pass over a single-channel uint8 image;
+    ksize 3 and BORDER_DEFAULT or BORDER_REPLICATE only, as cv2."""
+    src, _ = _device_source(src)
+    if src.dtype != np.uint8:
+        raise error("spatialGradient: only uint8 sources")
+    try:
+        gx, gy = _transform.spatial_gradient(src, ksize, BORDER_DEFAULT if borderType is None else borderType)
+    except (TypeError, ValueError) as e:
+        raise error(f"spatialGradient: {e}") from None
+    return _into(dx, gx), _into(dy, gy)
+
+
+def convertScaleAbs(src, dst=None, alpha=1, beta=0):
+    """cv2.convertScaleAbs with alpha = 1 and beta = 0: saturate_cast<uchar>(|v|) of a uint8, int16, float32 or float64 image, on the
+    GPU; a device image (the int16 result of Sobel) gives a device uint8 image.  Other alpha / beta: DESIGN.md section 7."""
+    if alpha != 1 or beta != 0:
+        raise error("convertScaleAbs: alpha != 1 or beta != 0 is outside the accelerated path (DESIGN.md section 7)")
+    src, _ = _device_source(src)
+    try:
+        return _into(dst, _transform.convert_scale_abs(src))
+    except (TypeError, ValueError) as e:
+        raise error(f"convertScaleAbs: {e}") from None
 
 
 INTER_LINEAR = 1

@@ -154,6 +154,123 @@ def median_blur(mat: np.ndarray, ksize: int) -> np.ndarray:
     return out
 
 
+_DEPTH_DTYPE = {_vp.DEPTH_8U: np.uint8, _vp.DEPTH_16S: np.int16, _vp.DEPTH_32F: np.float32, _vp.DEPTH_64F: np.float64}
+_BORDERS = (_vp.BORDER_CONSTANT, _vp.BORDER_REPLICATE, _vp.BORDER_REFLECT, _vp.BORDER_REFLECT_101)
+
+
+def _deriv_source(mat):
+    """The checked source of a derivative filter: uint8, (h, w) or (h, w, 1..4), not empty; and its channel count."""
+    mat = as_mat(mat)
+    if not isinstance(mat, (np.ndarray, DeviceMat)) or mat.dtype != np.uint8 or mat.ndim not in (2, 3) or mat.size == 0:
+        raise TypeError("expected a non-empty uint8 (h, w) or (h, w, c) image")
+    cn = 1 if mat.ndim == 2 else mat.shape[2]
+    if cn > 4:
+        raise ValueError("at most 4 channels")
+    return mat, cn
+
+
+def _deriv(mat, op, dx, dy, ksize, ddepth, border):
+    """libvp vp_deriv_u8 / vp_deriv_dev: numpy in gives numpy out, a DeviceMat gives a DeviceMat of the requested dtype and stays in HBM.
+    What the library refuses (orders, kernel sizes, depths, borders) comes back as ValueError before anything is launched."""
+    mat, cn = _deriv_source(mat)
+    dx, dy, ksize, ddepth, border = int(dx), int(dy), int(ksize), int(ddepth), int(border) & ~_vp.BORDER_ISOLATED
+    depth = _vp.DEPTH_8U if ddepth == -1 else ddepth
+    if depth not in _DEPTH_DTYPE:
+        raise ValueError("ddepth must be -1, CV_8U, CV_16S, CV_32F or CV_64F")
+    if border not in _BORDERS:
+        raise ValueError("the border must be BORDER_REFLECT_101, BORDER_REPLICATE, BORDER_REFLECT or BORDER_CONSTANT")
+    if op == _vp.DERIV_SOBEL and ksize == -1:
+        op = _vp.DERIV_SCHARR
+    if op == _vp.DERIV_SCHARR:
+        if dx < 0 or dy < 0 or dx + dy != 1:
+            raise ValueError("Scharr takes dx + dy == 1")
+    elif op == _vp.DERIV_SOBEL:
+        if not (0 <= dx <= 2 and 0 <= dy <= 2 and dx + dy > 0):
+            raise ValueError("dx and dy must be in 0..2 and not both 0")
+        if ksize not in (1, 3, 5, 7):
+            raise ValueError("ksize must be 1, 3, 5 or 7 (or -1 for Scharr)")
+        if ksize > 1 and max(dx, dy) >= ksize:
+            raise ValueError("the derivative order must be below ksize")
+    elif ksize not in (1, 3, 5, 7):
+        raise ValueError("ksize must be 1, 3, 5 or 7")
+    ctx = _vp.default_context()
+    h, w = mat.shape[:2]
+    dtype = _DEPTH_DTYPE[depth]
+    if isinstance(mat, DeviceMat):
+        mat.refresh_device(ctx)
+        out = DeviceMat(ctx, mat.shape, dtype)
+        _vp.check(_vp.lib().vp_deriv_dev(ctx.handle, mat.dev_ptr, w * cn, w, h, cn, op, dx, dy, ksize, depth, border, out.dev_ptr), ctx.handle)
+        return out
+    src = np.ascontiguousarray(mat)
+    out = np.empty(src.shape, dtype)
+    _vp.check(_vp.lib().vp_deriv_u8(ctx.handle, _vp.ptr(src), w, h, cn, op, dx, dy, ksize, depth, border, _vp.ptr(out)), ctx.handle)
+    return out
+
+
+def sobel(mat: np.ndarray, dx: int, dy: int, ksize: int = 3, ddepth: int = _vp.DEPTH_16S, border: int = _vp.BORDER_REFLECT_101) -> np.ndarray:
+    """cv2.Sobel with scale 1 and delta 0 on uint8 images of 1..4 channels: the exact integer correlation with the taps of
+    cv2.getDerivKernels (ksize 1, 3, 5, 7; -1 is Scharr), cast as saturate_cast does to ddepth (a libvp DEPTH_* code = cv2's CV_8U,
+    CV_16S, CV_32F, CV_64F; the default here is int16, which keeps the sign).  Not a name of the reference's utils/transform.py."""
+    return _deriv(mat, _vp.DERIV_SOBEL, dx, dy, ksize, ddepth, border)
+
+
+def scharr(mat: np.ndarray, dx: int, dy: int, ddepth: int = _vp.DEPTH_16S, border: int = _vp.BORDER_REFLECT_101) -> np.ndarray:
+    """cv2.Scharr with scale 1 and delta 0: [-1 0 1] along the differentiated axis, [3 10 3] along the other; dx + dy == 1."""
+    return _deriv(mat, _vp.DERIV_SCHARR, dx, dy, 3, ddepth, border)
+
+
+def laplacian(mat: np.ndarray, ksize: int = 1, ddepth: int = _vp.DEPTH_16S, border: int = _vp.BORDER_REFLECT_101) -> np.ndarray:
+    """cv2.Laplacian with scale 1 and delta 0: the 3x3 kernels of ksize 1 and 3, Sobel(2, 0) + Sobel(0, 2) at ksize 5 and 7."""
+    return _deriv(mat, _vp.DERIV_LAPLACIAN, 0, 0, ksize, ddepth, border)
+
+
+def spatial_gradient(mat: np.ndarray, ksize: int = 3, border: int = _vp.BORDER_REFLECT_101):
+    """cv2.spatialGradient: (Sobel(1, 0, 3), Sobel(0, 1, 3)) of a single-channel uint8 image, both int16, from one pass over the
+    source (libvp vp_spatial_gradient_*).  ksize 3 and BORDER_REFLECT_101 or BORDER_REPLICATE only, as cv2."""
+    mat, cn = _deriv_source(mat)
+    if mat.ndim == 3 and cn == 1:
+        mat = mat.reshaped(mat.shape[:2]) if isinstance(mat, DeviceMat) else mat[:, :, 0]
+    if mat.ndim != 2:
+        raise ValueError("spatial_gradient takes a single-channel image")
+    ksize, border = int(ksize), int(border) & ~_vp.BORDER_ISOLATED
+    if ksize != 3:
+        raise ValueError("ksize must be 3")
+    if border not in (_vp.BORDER_REFLECT_101, _vp.BORDER_REPLICATE):
+        raise ValueError("the border must be BORDER_DEFAULT or BORDER_REPLICATE")
+    ctx = _vp.default_context()
+    h, w = mat.shape
+    if isinstance(mat, DeviceMat):
+        mat.refresh_device(ctx)
+        gx, gy = DeviceMat(ctx, (h, w), np.int16), DeviceMat(ctx, (h, w), np.int16)
+        _vp.check(_vp.lib().vp_spatial_gradient_dev(ctx.handle, mat.dev_ptr, w, w, h, ksize, border, gx.dev_ptr, gy.dev_ptr), ctx.handle)
+        return gx, gy
+    src = np.ascontiguousarray(mat)
+    gx, gy = np.empty((h, w), np.int16), np.empty((h, w), np.int16)
+    _vp.check(_vp.lib().vp_spatial_gradient_u8(ctx.handle, _vp.ptr(src), w, h, ksize, border, _vp.ptr(gx), _vp.ptr(gy)), ctx.handle)
+    return gx, gy
+
+
+def convert_scale_abs(mat: np.ndarray) -> np.ndarray:
+    """cv2.convertScaleAbs with alpha 1 and beta 0: saturate_cast<uchar>(|v|) of a uint8, int16, float32 or float64 image (a float is
+    rounded half to even first).  numpy in gives numpy out; a DeviceMat (a derivative that stayed in HBM) gives a uint8 DeviceMat."""
+    mat = as_mat(mat)
+    depth = {np.dtype(v): k for k, v in _DEPTH_DTYPE.items()}.get(np.dtype(mat.dtype)) if isinstance(mat, (np.ndarray, DeviceMat)) else None
+    if depth is None or mat.ndim not in (2, 3) or mat.size == 0:
+        raise TypeError("expected a non-empty uint8, int16, float32 or float64 (h, w) or (h, w, c) image")
+    if mat.ndim == 3 and mat.shape[2] > 4:
+        raise ValueError("at most 4 channels")
+    ctx = _vp.default_context()
+    if isinstance(mat, DeviceMat):
+        mat.refresh_device(ctx)
+        out = DeviceMat(ctx, mat.shape)
+        _vp.check(_vp.lib().vp_convert_scale_abs_dev(ctx.handle, mat.dev_ptr, depth, mat.size, out.dev_ptr), ctx.handle)
+        return out
+    src = np.ascontiguousarray(mat)
+    out = np.empty(src.shape, np.uint8)
+    _vp.check(_vp.lib().vp_convert_scale_abs_u8(ctx.handle, _vp.ptr(src), depth, src.size, _vp.ptr(out)), ctx.handle)
+    return out
+
+
 def rotate(mat: np.ndarray, degrees: float) -> np.ndarray:
     """utils/transform.py:180-196: rotation about the image centre, positive = counterclockwise, borders replicated."""
     from vision import cv2_facade

@@ -543,6 +543,41 @@ int vp_median_blur_u8(vp_ctx* ctx, const uint8_t* src_host, int w, int h, int cn
 int vp_median_blur_dev(vp_ctx* ctx, const uint8_t* src_dev, size_t src_stride, int w, int h, int cn, int ksize, int binary_hint,
                        const unsigned long long* src_bits_dev, uint8_t* dst_dev, unsigned long long* dst_bits_dev, int* made_bits);
 
+/* ---- derivative filters -------------------------------------------------------------------------------------------------------------- *
+ * cv2.Sobel / Scharr / Laplacian / spatialGradient on uint8 images of 1..4 interleaved channels with scale = 1 and delta = 0:
+ * dst[y][x][c] = saturate_cast<ddepth>(the integer correlation of channel c of the border-extended image with the operator's
+ * unnormalised integer kernel).  uint8 clamps to [0, 255], int16 to [-32768, 32767], float and double hold the integer exactly, so the
+ * result equals OpenCV's on every code path of its own (tests/deriv_restate.py is the statement).
+ * op: VP_DERIV_SOBEL with dx, dy in 0..2, dx + dy > 0, ksize 3, 5 or 7 above both orders (the taps of cv::getDerivKernels), ksize 1
+ *   ([-1 0 1] or [1 -2 1] along a differentiated axis, [1] along the other) or ksize -1 = Scharr; VP_DERIV_SCHARR with dx + dy == 1
+ *   ([-1 0 1] with [3 10 3]; ksize is ignored); VP_DERIV_LAPLACIAN with ksize 1 ([[0 1 0],[1 -4 1],[0 1 0]]), 3 ([[2 0 2],[0 -8 0],
+ *   [2 0 2]]), 5 or 7 (Sobel(2, 0, ksize) + Sobel(0, 2, ksize); dx, dy are ignored).
+ * ddepth: -1 or VP_DEPTH_8U, VP_DEPTH_16S, VP_DEPTH_32F, VP_DEPTH_64F (cv2's CV_8U, CV_16S, CV_32F, CV_64F).
+ * border: VP_BORDER_REFLECT_101 (cv2's default), VP_BORDER_REPLICATE, VP_BORDER_REFLECT, VP_BORDER_CONSTANT (value 0); the
+ *   VP_BORDER_ISOLATED bit is ignored; index maps as cv::borderInterpolate, also for images narrower than the kernel's radius.
+ * h <= 65535.  Anything else is VP_ERR_INVALID and nothing is launched or written.
+ * vp_deriv_u8 / vp_spatial_gradient_u8: packed host images; stage, run the kernel of the device form and synchronise.
+ * vp_deriv_dev / vp_spatial_gradient_dev: src_dev is read in place (row stride in bytes, at least w * cn, no alignment asked of
+ *   pointer or stride), dst_dev is packed (w * cn elements of ddepth per row), aligned to its element size, and must not overlap the
+ *   source; enqueued on the context's stream, never synchronise.
+ * vp_spatial_gradient_*: single channel, ksize 3, VP_BORDER_REFLECT_101 or VP_BORDER_REPLICATE, as cv2; dx = Sobel(1, 0, 3) and
+ *   dy = Sobel(0, 1, 3), both int16, from one pass over the source.
+ * vp_convert_scale_abs_*: cv2.convertScaleAbs with alpha = 1, beta = 0 on n elements of depth VP_DEPTH_8U / 16S / 32F / 64F:
+ *   dst[i] = saturate_cast<uchar>(|src[i]|); a float source is rounded half to even before the clamp (NaN gives 0).  src is aligned
+ *   to its element size and does not overlap dst. */
+enum { VP_DERIV_SOBEL = 0, VP_DERIV_SCHARR = 1, VP_DERIV_LAPLACIAN = 2 };
+enum { VP_DEPTH_8U = 0, VP_DEPTH_16S = 3, VP_DEPTH_32F = 5, VP_DEPTH_64F = 6 };
+enum { VP_BORDER_REFLECT = 2, VP_BORDER_REFLECT_101 = 4, VP_BORDER_ISOLATED = 16 };      /* with VP_BORDER_CONSTANT = 0, VP_BORDER_REPLICATE = 1 */
+int vp_deriv_u8(vp_ctx* ctx, const uint8_t* src_host, int w, int h, int cn, int op, int dx, int dy, int ksize, int ddepth, int border,
+                void* dst_host);
+int vp_deriv_dev(vp_ctx* ctx, const uint8_t* src_dev, size_t src_stride, int w, int h, int cn, int op, int dx, int dy, int ksize, int ddepth,
+                 int border, void* dst_dev);
+int vp_spatial_gradient_u8(vp_ctx* ctx, const uint8_t* src_host, int w, int h, int ksize, int border, int16_t* dx_host, int16_t* dy_host);
+int vp_spatial_gradient_dev(vp_ctx* ctx, const uint8_t* src_dev, size_t src_stride, int w, int h, int ksize, int border, int16_t* dx_dev,
+                            int16_t* dy_dev);
+int vp_convert_scale_abs_u8(vp_ctx* ctx, const void* src_host, int depth, size_t n, uint8_t* dst_host);
+int vp_convert_scale_abs_dev(vp_ctx* ctx, const void* src_dev, int depth, size_t n, uint8_t* dst_dev);
+
 /* ---- element-wise operators on device images ------------------------------------------------------------------------------------ *
  * Packed uint8 device images; every entry enqueues on the context's stream and returns at once, except vp_count_nonzero_u8_dev.
  * Pointers need no alignment (planes of one frame sit at byte offsets inside one allocation): 16-byte accesses are used where the
