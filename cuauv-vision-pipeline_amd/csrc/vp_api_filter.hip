@@ -5,6 +5,7 @@
 // one *_args check, which also normalises the parameters; what differs between the forms stays in the entry.
 #include "vp_api_util.h"
 #include "vp_deriv_plan.h"
+#include "vp_clahe_plan.h"
 
 extern "C" {
 
@@ -113,6 +114,98 @@ int vp_hist_u8_dev(vp_ctx* ctx, const uint8_t* d_src, size_t n, uint32_t* hist)
     VP_TRY(vpk_hist_u8(ctx, d_src, n, d_hist));
     VP_TRY(d2h(ctx, hist, d_hist, 1024));
     return vp_synchronize(ctx);
+}
+
+// cv2.equalizeHist and CLAHE on 8-bit single-channel images.  Their checks are pure host arithmetic and come before the context is
+// looked at, so a rejected call has touched nothing.  What the device forms add: the stride, and no overlap.
+static int plane_args(vp_ctx* ctx, const char* who, const void* src, const void* dst, int w, int h)
+{
+    if (!src || !dst || w <= 0 || h <= 0) return vp_fail(ctx, VP_ERR_INVALID, who);
+    return VP_OK;
+}
+
+static int plane_dev_args(vp_ctx* ctx, const char* who, const void* d_src, size_t src_stride, int w, int h, const void* d_dst)
+{
+    if (src_stride < (size_t)w || dev_overlap(d_src, strided_bytes(src_stride, (size_t)w, h), d_dst, (size_t)w * h)) return vp_fail(ctx, VP_ERR_INVALID, who);
+    return VP_OK;
+}
+
+static int eqhist_args(vp_ctx* ctx, const char* who, const void* src, const void* dst, int w, int h)
+{
+    VP_TRY(plane_args(ctx, who, src, dst, w, h));
+    if ((long long)w * h > CL_MAX_PIXELS) return vp_fail(ctx, VP_ERR_UNSUPPORTED, who);
+    return VP_OK;
+}
+
+// the plan is the argument check (vp_clahe_plan.h)
+static int clahe_args(vp_ctx* ctx, const char* who, const void* src, const void* dst, int w, int h, double clip_limit, int tiles_x, int tiles_y, vp_clahe_plan* P)
+{
+    VP_TRY(plane_args(ctx, who, src, dst, w, h));
+    *P = vp_clahe_make_plan(w, h, clip_limit, tiles_x, tiles_y, ctx ? ctx->clahe_split : 0);
+    if (P->status == VP_CLAHE_INVALID) return vp_fail(ctx, VP_ERR_INVALID, who);
+    if (P->status != VP_CLAHE_OK) return vp_fail(ctx, VP_ERR_UNSUPPORTED, who);
+    return VP_OK;
+}
+
+int vp_equalize_hist_u8(vp_ctx* ctx, const uint8_t* src, int w, int h, uint8_t* dst)
+{
+    VP_TRY(eqhist_args(ctx, "vp_equalize_hist_u8 arguments", src, dst, w, h));
+    VP_TRY(check_ctx(ctx));
+    const size_t n = (size_t)w * h;
+    VP_TRY(vp_ws_reserve(ctx, 2 * vp_align(n) + 4096));
+    TAKE(d_src, uint8_t*, n);
+    TAKE(d_dst, uint8_t*, n);
+    TAKE(d_hist, u32*, 1024);
+    TAKE(d_lut, uint8_t*, 256);
+    VP_TRY(h2d(ctx, d_src, src, n));
+    VP_TRY(vpk_equalize_hist(ctx, d_src, (size_t)w, w, h, d_hist, d_lut, d_dst));
+    VP_TRY(d2h(ctx, dst, d_dst, n));
+    return vp_synchronize(ctx);
+}
+
+// histogram -> table by one wave -> table applied from device memory: three launches, nothing comes back
+int vp_equalize_hist_dev(vp_ctx* ctx, const uint8_t* d_src, size_t src_stride, int w, int h, uint8_t* d_dst)
+{
+    VP_TRY(eqhist_args(ctx, "vp_equalize_hist_dev arguments", d_src, d_dst, w, h));
+    VP_TRY(plane_dev_args(ctx, "vp_equalize_hist_dev: src_stride, or dst overlaps src", d_src, src_stride, w, h, d_dst));
+    VP_TRY(check_ctx(ctx));
+    VP_TRY(vp_ws_reserve(ctx, 4096));
+    TAKE(d_hist, u32*, 1024);
+    TAKE(d_lut, uint8_t*, 256);
+    return vpk_equalize_hist(ctx, d_src, src_stride, w, h, d_hist, d_lut, d_dst);
+}
+
+static size_t clahe_ws_bytes(int tiles) { return vp_align((size_t)tiles * 256) + vp_align((size_t)tiles * 1024) + 1024; }
+
+int vp_clahe_u8(vp_ctx* ctx, const uint8_t* src, int w, int h, double clip_limit, int tiles_x, int tiles_y, uint8_t* dst)
+{
+    vp_clahe_plan P;
+    VP_TRY(clahe_args(ctx, "vp_clahe_u8 arguments", src, dst, w, h, clip_limit, tiles_x, tiles_y, &P));
+    VP_TRY(check_ctx(ctx));
+    const size_t n = (size_t)w * h;
+    const int tiles = tiles_x * tiles_y;
+    VP_TRY(vp_ws_reserve(ctx, 2 * vp_align(n) + clahe_ws_bytes(tiles)));
+    TAKE(d_src, uint8_t*, n);
+    TAKE(d_dst, uint8_t*, n);
+    TAKE(d_luts, uint8_t*, (size_t)tiles * 256);
+    TAKE(d_part, u32*, (size_t)tiles * 1024);
+    VP_TRY(h2d(ctx, d_src, src, n));
+    VP_TRY(vpk_clahe(ctx, d_src, (size_t)w, w, h, tiles_x, tiles_y, P, d_part, d_luts, d_dst));
+    VP_TRY(d2h(ctx, dst, d_dst, n));
+    return vp_synchronize(ctx);
+}
+
+int vp_clahe_dev(vp_ctx* ctx, const uint8_t* d_src, size_t src_stride, int w, int h, double clip_limit, int tiles_x, int tiles_y, uint8_t* d_dst)
+{
+    vp_clahe_plan P;
+    VP_TRY(clahe_args(ctx, "vp_clahe_dev arguments", d_src, d_dst, w, h, clip_limit, tiles_x, tiles_y, &P));
+    VP_TRY(plane_dev_args(ctx, "vp_clahe_dev: src_stride, or dst overlaps src", d_src, src_stride, w, h, d_dst));
+    VP_TRY(check_ctx(ctx));
+    const int tiles = tiles_x * tiles_y;
+    VP_TRY(vp_ws_reserve(ctx, clahe_ws_bytes(tiles)));
+    TAKE(d_luts, uint8_t*, (size_t)tiles * 256);
+    TAKE(d_part, u32*, (size_t)tiles * 1024);
+    return vpk_clahe(ctx, d_src, src_stride, w, h, tiles_x, tiles_y, P, d_part, d_luts, d_dst);
 }
 
 // VP_OPT_BLUR_ONEPASS left at its default: the one-pass kernel serves the classes in which it measured faster than the two passes

@@ -74,6 +74,7 @@ struct vp_ctx {
     int hough_global;             // 1: every Hough vote is a global atomic (VP_OPT_HOUGH_LDS 0); 0 (default): rows counted in LDS where they fit
     int blur_onepass;             // VP_OPT_BLUR_ONEPASS: -1 (default) the measured choice, 1 the one-pass kernel wherever its tile fits, 0 always two passes
     int median_mask;              // VP_OPT_MEDIAN_MASK: -1 (default) the measured choice, 1 the mask kernel for every mask it can serve, 0 never
+    int clahe_split;              // VP_OPT_CLAHE_SPLIT: 0 (default) the measured choice, n >= 1 that many blocks share one CLAHE tile's histogram
     int hc_global;                // 1: HoughCircles radius histograms always in device memory (VP_OPT_HOUGH_CIRCLES_LDS 0); 0 (default): in LDS where they fit
     void* hc_hist;                // HoughCircles radius histograms of the global form: grow-only, sized per call by its centre count
     size_t hc_hist_bytes;
@@ -210,6 +211,16 @@ struct vp_deriv_plan;
 int vpk_deriv(vp_ctx* ctx, const uint8_t* d_src, size_t sstride, int w, int h, int cn, const vp_deriv_plan& P, void* d_dst, void* d_dst2);
 // cv2.convertScaleAbs, alpha 1, beta 0 (vp_elementwise.hip): n elements of depth VP_DEPTH_* to saturate_cast<uchar>(|v|)
 int vpk_convert_scale_abs(vp_ctx* ctx, const void* d_src, int depth, size_t n, uint8_t* d_dst);
+
+// ---- histogram equalisation and CLAHE (vp_clahe.hip; the plan: vp_clahe_plan.h) -------------------------
+// cv2.equalizeHist of a w x h plane (sstride: bytes between source rows): histogram, table and table-apply, three launches, enqueued.
+// d_hist: 256 counters; d_lut: 256 bytes, 4-byte aligned; d_dst packed
+int vpk_equalize_hist(vp_ctx* ctx, const uint8_t* d_src, size_t sstride, int w, int h, u32* d_hist, uint8_t* d_lut, uint8_t* d_dst);
+// cv2.createCLAHE(...).apply as vp_clahe_make_plan accepted it; d_part: tiles * 256 counters (needed when P.split > 1); d_luts: tiles * 256
+// bytes, 16-byte aligned; d_dst packed; enqueued
+struct vp_clahe_plan;
+int vpk_clahe(vp_ctx* ctx, const uint8_t* d_src, size_t sstride, int w, int h, int tiles_x, int tiles_y, const vp_clahe_plan& P, u32* d_part, uint8_t* d_luts,
+              uint8_t* d_dst);
 
 // ---- morphology (vp_morph.hip) ---------------------------------------------------------------
 struct vp_bitstage { int dilate; int l, r, u, d; };  // window [-l, r] x [-u, d]

@@ -40,6 +40,7 @@ OPT_HOUGH_LDS = 5
 OPT_HOUGH_CIRCLES_LDS = 6
 OPT_BLUR_ONEPASS = 7
 OPT_MEDIAN_MASK = 8
+OPT_CLAHE_SPLIT = 9
 THRESH_BINARY, THRESH_BINARY_INV, THRESH_TRUNC, THRESH_TOZERO, THRESH_TOZERO_INV = 0, 1, 2, 3, 4
 HOUGH_GRADIENT = 3
 # return codes of include/vp.h
@@ -227,6 +228,10 @@ _SIGS = {
     "vp_spatial_gradient_dev": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
     "vp_convert_scale_abs_u8": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_size_t, C.c_void_p]),
     "vp_convert_scale_abs_dev": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_size_t, C.c_void_p]),
+    "vp_equalize_hist_u8": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p]),
+    "vp_equalize_hist_dev": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_int, C.c_int, C.c_void_p]),
+    "vp_clahe_u8": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_double, C.c_int, C.c_int, C.c_void_p]),
+    "vp_clahe_dev": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_int, C.c_int, C.c_double, C.c_int, C.c_int, C.c_void_p]),
 }
 
 

@@ -739,6 +739,74 @@ def medianBlur(src, ksize, dst=None):
     return _into(dst, _transform.median_blur(src, k))
 
 
+# ---- histogram equalisation and CLAHE (libvp vp_clahe.hip) ------------------------------------------------------------------------------
+def _grey_u8_source(name, src):
+    src, _ = _device_source(src)
+    if src.dtype != np.uint8:
+        raise error(f"{name}: only uint8 images are on the accelerated path")
+    if src.ndim == 3 and src.shape[2] == 1 and isinstance(src, np.ndarray):
+        src = src[:, :, 0]
+    if src.ndim != 2 or src.size == 0:
+        raise error(f"{name}: expected a non-empty single-channel (h, w) image")
+    return src
+
+
+def equalizeHist(src, dst=None):
+    """cv2.equalizeHist on a uint8 single-channel image, byte for byte, on the GPU (libvp vp_equalize_hist_*).  A DeviceMat stays in HBM."""
+    return _into(dst, _color.equalize_hist(_grey_u8_source("equalizeHist", src)))
+
+
+class CLAHE:
+    """What cv2.createCLAHE returns: apply() runs libvp's vp_clahe_* kernels."""
+
+    def __init__(self, clipLimit=40.0, tileGridSize=(8, 8)):
+        self.setClipLimit(clipLimit)
+        self.setTilesGridSize(tileGridSize)
+
+    def apply(self, src, dst=None):
+        src = _grey_u8_source("CLAHE.apply", src)
+        tx, ty = self._grid
+        if tx > 64 or ty > 64:
+            raise error("CLAHE.apply: more than 64 tiles along an axis is outside the accelerated path")
+        try:
+            return _into(dst, _color.clahe(src, self._clip, self._grid))
+        except (TypeError, ValueError, _vp.VpError) as e:
+            raise error(f"CLAHE.apply: {e}") from None
+
+    def setClipLimit(self, clipLimit):
+        try:
+            clip = float(clipLimit)
+        except (TypeError, ValueError):
+            raise error("CLAHE: clipLimit must be a number") from None
+        if clip != clip:
+            raise error("CLAHE: clipLimit must not be NaN")
+        self._clip = clip
+
+    def getClipLimit(self):
+        return self._clip
+
+    def setTilesGridSize(self, tileGridSize):
+        try:
+            tx, ty = (int(v) for v in tileGridSize)
+        except (TypeError, ValueError):
+            raise error("CLAHE: tileGridSize must be a pair of integers") from None
+        if tx < 1 or ty < 1:
+            raise error("CLAHE: tileGridSize must be at least (1, 1)")
+        self._grid = (tx, ty)
+
+    def getTilesGridSize(self):
+        return self._grid
+
+    def collectGarbage(self):
+        """cv2 frees its cached tables here; this object keeps none."""
+
+
+def createCLAHE(clipLimit=40.0, tileGridSize=(8, 8)):
+    """cv2.createCLAHE: contrast-limited adaptive histogram equalisation of uint8 single-channel images, byte for byte OpenCV's result
+    (DESIGN.md section 4), on the GPU.  apply() of a DeviceMat stays in HBM."""
+    return CLAHE(clipLimit, tileGridSize)
+
+
 # ---- derivative filters (libvp vp_deriv.hip) ------------------------------------------------------------------------------------------
 def _deriv_call(name, fn, src, ddepth, scale, delta, borderType, *args):
     """What cv2 rejects, and the two restrictions of this path: scale = 1 and delta = 0 only."""

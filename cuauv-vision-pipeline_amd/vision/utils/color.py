@@ -412,6 +412,65 @@ def adaptive_threshold_gaussian_inv(mat: np.ndarray, neighborhood_size: int, bia
     return _adaptive_gaussian(mat, neighborhood_size, bias, 1)
 
 
+def _grey_operator(mat, host_call, dev_call):
+    """A uint8 (h, w) image through a host / device pair of libvp, as otsu_threshold and median_blur go: numpy in gives numpy out; a
+    DeviceMat gives a DeviceMat (not a mask) that stays in HBM.  host_call(ctx, src_ptr, w, h, dst_ptr), dev_call(ctx, src_ptr, stride, w,
+    h, dst_ptr)."""
+    mat = as_mat(mat)
+    ctx = _vp.default_context()
+    if isinstance(mat, DeviceMat):
+        if mat.dtype != np.uint8:
+            raise TypeError("expected a uint8 numpy image")
+        src = device_image(ctx, mat, 1)
+        h, w = src.shape
+        dst = DeviceMat(ctx, (h, w), binary=False)
+        _vp.check(dev_call(ctx.handle, src.dev_ptr, w, w, h, dst.dev_ptr), ctx.handle)
+        return dst
+    mat = np.ascontiguousarray(_u8_image(mat, 1))
+    out = np.empty_like(mat)
+    _vp.check(host_call(ctx.handle, _vp.ptr(mat), mat.shape[1], mat.shape[0], _vp.ptr(out)), ctx.handle)
+    return out
+
+
+def equalize_hist(mat: np.ndarray) -> np.ndarray:
+    """cv2.equalizeHist on a uint8 (h, w) image (libvp vp_equalize_hist_u8 / _dev).  An addition to the mirror, not a name of the
+    reference's utils/color.py: the global contrast step.  Integer histogram, one float32 multiply per table entry, a table: byte for
+    byte OpenCV's result.  numpy in gives numpy out; a DeviceMat gives a DeviceMat and stays in HBM (three launches, no wait)."""
+    lib = _vp.lib()
+    return _grey_operator(mat, lib.vp_equalize_hist_u8, lib.vp_equalize_hist_dev)
+
+
+def _clahe_params(clip_limit, tile_grid):
+    try:
+        clip, (tx, ty) = float(clip_limit), (int(tile_grid[0]), int(tile_grid[1]))
+    except (TypeError, ValueError, IndexError):
+        raise ValueError("clip_limit must be a number and tile_grid a pair of integers") from None
+    if clip != clip or tx < 1 or ty < 1:
+        raise ValueError("clip_limit must not be NaN and tile_grid must be at least (1, 1)")
+    return clip, tx, ty
+
+
+def clahe(mat: np.ndarray, clip_limit: float = 2.0, tile_grid=(8, 8)) -> np.ndarray:
+    """cv2.createCLAHE(clip_limit, tile_grid).apply(mat) on a uint8 (h, w) image (libvp vp_clahe_u8 / _dev).  An addition to the mirror,
+    not a name of the reference's utils/color.py: contrast-limited adaptive histogram equalisation, the usual first step on underwater
+    frames.  tile_grid is (tiles_x, tiles_y) as in cv2, up to 64 each.  Byte for byte OpenCV's result, including its padding of images
+    that the grid does not divide.  numpy in gives numpy out; a DeviceMat gives a DeviceMat and stays in HBM."""
+    clip, tx, ty = _clahe_params(clip_limit, tile_grid)
+    lib = _vp.lib()
+    return _grey_operator(mat, lambda c, s, w, h, d: lib.vp_clahe_u8(c, s, w, h, clip, tx, ty, d),
+                          lambda c, s, st, w, h, d: lib.vp_clahe_dev(c, s, st, w, h, clip, tx, ty, d))
+
+
+def clahe_bgr(mat: np.ndarray, clip_limit: float = 2.0, tile_grid=(8, 8)) -> np.ndarray:
+    """CLAHE of the L channel of a BGR image: bgr_to_lab -> split -> clahe(L) -> merge -> lab_to_bgr, each step the operator of that name.
+    An addition to the mirror.  A DeviceMat gives a DeviceMat, and no step visits the host; a numpy image gives what bgr_to_lab gives for
+    one (device images in the lazy mode, numpy otherwise)."""
+    from vision import cv2_facade
+    _clahe_params(clip_limit, tile_grid)
+    _lab, (l, a, b) = bgr_to_lab(mat)
+    return lab_to_bgr(cv2_facade.merge((clahe(l, clip_limit, tile_grid), a, b)))[0]
+
+
 kmeans = _outside_path("kmeans")
 
 

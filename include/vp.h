@@ -88,9 +88,13 @@ int vp_synchronize(vp_ctx* ctx);
  * VP_OPT_MEDIAN_MASK (1, 0 or -1, default -1; the environment variable of the same name sets 1 or 0 at vp_create): which kernel
  * vp_median_blur_dev runs on a single-channel image the caller calls a 0/255 mask (binary_hint).  1 = the bit-plane majority vote for
  * every window it can serve (3..63); 0 = never, the general kernels; -1 = the measured choice (whenever the source's bit plane is
- * passed, and from window 5 on without one).  Results are identical. */
+ * passed, and from window 5 on without one).  Results are identical.
+ * VP_OPT_CLAHE_SPLIT (0..64, default 0; the environment variable of the same name sets 1..64 at vp_create): how many blocks share
+ * the histogram of one CLAHE tile in vp_clahe_u8 / vp_clahe_dev.  1 = one block per tile does histogram, clip, scan and table in one
+ * launch; n > 1 = n blocks (at most one per tile row) add partial histograms with device atomics and a finishing launch makes the
+ * tables; 0 = the measured choice.  Results are identical. */
 enum { VP_OPT_CHAIN_STREAMS = 1, VP_OPT_CCL_LEVELS = 2, VP_OPT_CCL_MERGE_CAP = 3, VP_OPT_FLAT_OPS = 4, VP_OPT_HOUGH_LDS = 5,
-       VP_OPT_HOUGH_CIRCLES_LDS = 6, VP_OPT_BLUR_ONEPASS = 7, VP_OPT_MEDIAN_MASK = 8 };
+       VP_OPT_HOUGH_CIRCLES_LDS = 6, VP_OPT_BLUR_ONEPASS = 7, VP_OPT_MEDIAN_MASK = 8, VP_OPT_CLAHE_SPLIT = 9 };
 int vp_set_option(vp_ctx* ctx, int option, int value);
 /* HIP-event stopwatch on the context's stream (bench.py: roofline.achieved). */
 int vp_timer_start(vp_ctx* ctx);
@@ -525,6 +529,26 @@ int vp_ccl_dev(vp_ctx* ctx, const uint8_t* src_dev, size_t src_stride, int w, in
                int32_t* stats_host, double* centroids_host, int max_labels, int32_t* n_labels);
 int vp_ccl_bits_dev(vp_ctx* ctx, const unsigned long long* bits_dev, int w, int h, int numbering, int32_t* labels_dev,
                     int32_t* stats_host, double* centroids_host, int max_labels, int32_t* n_labels);
+
+/* ---- histogram equalisation and CLAHE ------------------------------------------------------------------------------------------------ *
+ * cv2.equalizeHist and cv2.createCLAHE(clip_limit, (tiles_x, tiles_y)).apply on 8-bit single-channel images, byte for byte (DESIGN.md
+ * section 4 has the arithmetic: integer histograms, one float32 multiply per table entry, and for CLAHE a float32 bilinear blend of
+ * four table entries per pixel in OpenCV's order, no product fused with a sum).
+ * vp_equalize_hist_u8 / vp_clahe_u8: packed host images; stage, run the kernels of the device form and synchronise.
+ * vp_equalize_hist_dev / vp_clahe_dev: src_dev is read in place (row stride in bytes, at least w), dst_dev is packed and must not
+ *   overlap it; enqueued on the context's stream, never synchronise.  equalizeHist is three launches (histogram, table, table-apply).
+ * CLAHE cuts tiles_x x tiles_y tiles from the image, extended right by tiles_x - w % tiles_x and down by tiles_y - h % tiles_y with
+ *   BORDER_REFLECT_101 whenever EITHER dimension fails to divide (so a dimension that does divide grows by a whole tile count, as in
+ *   OpenCV).  clip_limit <= 0 switches clipping off; otherwise the limit per bin is max(int(clip_limit * tile_area / 256), 1).
+ * VP_ERR_INVALID, with nothing launched or written: NULL pointers, w or h <= 0, src_stride < w, dst overlapping src in the device
+ *   forms, tiles_x or tiles_y < 1, a NaN clip_limit.  VP_ERR_UNSUPPORTED: tiles_x or tiles_y > 64, more than 2^28 pixels, an extension
+ *   that is not smaller than the dimension it reflects (only a single reflection is reproduced), clip_limit * tile_area / 256 >= 2^31
+ *   (OpenCV's cast is undefined there).  See VP_OPT_CLAHE_SPLIT for the dispatch of the tile histograms. */
+int vp_equalize_hist_u8(vp_ctx* ctx, const uint8_t* src_host, int w, int h, uint8_t* dst_host);
+int vp_equalize_hist_dev(vp_ctx* ctx, const uint8_t* src_dev, size_t src_stride, int w, int h, uint8_t* dst_dev);
+int vp_clahe_u8(vp_ctx* ctx, const uint8_t* src_host, int w, int h, double clip_limit, int tiles_x, int tiles_y, uint8_t* dst_host);
+int vp_clahe_dev(vp_ctx* ctx, const uint8_t* src_dev, size_t src_stride, int w, int h, double clip_limit, int tiles_x, int tiles_y,
+                 uint8_t* dst_dev);
 
 /* ---- median filter ------------------------------------------------------------------------------------------------------------------ *
  * cv2.medianBlur on uint8 images of 1..4 interleaved channels: dst[y][x][c] is the median of the ksize x ksize window of channel c
