@@ -6,6 +6,7 @@
 #include "vp_api_util.h"
 #include "vp_deriv_plan.h"
 #include "vp_clahe_plan.h"
+#include "vp_remap_plan.h"
 
 extern "C" {
 
@@ -502,6 +503,123 @@ int vp_warp_affine_dev(vp_ctx* ctx, const uint8_t* d_src, size_t src_stride, int
         return vp_fail(ctx, VP_ERR_INVALID, "vp_warp_affine_dev: src_stride, or dst overlaps src");
     // the matrix and the border value travel as kernel arguments
     return vpk_warp_affine_u8(ctx, d_src, w, h, cn, m23, (flags & VP_WARP_INVERSE_MAP) != 0, border_mode, border_value, d_dst, dw, dh, src_stride);
+}
+
+// cv2.remap / convertMaps / warpPerspective (vp_remap.hip).  One check per family; `maps`: the map planes and their bytes, all of
+// which the destination must stay clear of (device forms).
+static int gather_args(vp_ctx* ctx, const char* who, const void* src, const void* dst, int w, int h, int cn, int dw, int dh, int interp, int border_mode)
+{
+    if (!src || !dst || !vp_remap_sizes_ok(w, h, cn, dw, dh) || (interp != VP_INTER_NEAREST && interp != VP_INTER_LINEAR) ||
+        (border_mode != VP_BORDER_CONSTANT && border_mode != VP_BORDER_REPLICATE))
+        return vp_fail(ctx, VP_ERR_INVALID, who);
+    return VP_OK;
+}
+static int gather_dev_args(vp_ctx* ctx, const char* who, const uint8_t* d_src, size_t src_stride, int w, int h, int cn, const uint8_t* d_dst, int dw, int dh,
+                           const void* map0, size_t bytes0, const void* map1, size_t bytes1)
+{
+    const size_t rowbytes = (size_t)w * cn, dbytes = (size_t)dw * dh * cn;
+    if (src_stride < rowbytes || dev_overlap(d_src, strided_bytes(src_stride, rowbytes, h), d_dst, dbytes) || (map0 && dev_overlap(map0, bytes0, d_dst, dbytes)) ||
+        (map1 && dev_overlap(map1, bytes1, d_dst, dbytes)))
+        return vp_fail(ctx, VP_ERR_INVALID, who);
+    return VP_OK;
+}
+
+int vp_convert_maps_dev(vp_ctx* ctx, const float* mapx, const float* mapy, int mw, int mh, int nearest, int16_t* xy_out, uint16_t* frac_out)
+{
+    VP_TRY(check_ctx(ctx));
+    if (!mapx || !xy_out || !vp_remap_map_ok(mw, mh) || (nearest ? frac_out != nullptr : frac_out == nullptr))
+        return vp_fail(ctx, VP_ERR_INVALID, "vp_convert_maps_dev arguments");
+    const size_t n = (size_t)mw * mh, inx = n * (mapy ? 4 : 8);
+    const void* outs[2] = {xy_out, frac_out};
+    const size_t outb[2] = {n * 4, n * 2};
+    for (int o = 0; o < 2; o++)
+        if (outs[o] && (dev_overlap(mapx, inx, outs[o], outb[o]) || (mapy && dev_overlap(mapy, n * 4, outs[o], outb[o]))))
+            return vp_fail(ctx, VP_ERR_INVALID, "vp_convert_maps_dev: an output overlaps a map");
+    if (frac_out && dev_overlap(xy_out, n * 4, frac_out, n * 2)) return vp_fail(ctx, VP_ERR_INVALID, "vp_convert_maps_dev: the outputs overlap");
+    return vpk_convert_maps(ctx, mapx, mapy, mw, mh, nearest != 0, xy_out, frac_out);
+}
+
+int vp_remap_fixed_dev(vp_ctx* ctx, const uint8_t* d_src, size_t src_stride, int w, int h, int cn, const int16_t* xy, const uint16_t* frac, int mw, int mh,
+                       int interp, int border_mode, const uint8_t* border_value, uint8_t* d_dst)
+{
+    VP_TRY(check_ctx(ctx));
+    VP_TRY(gather_args(ctx, "vp_remap_fixed_dev arguments", d_src, d_dst, w, h, cn, mw, mh, interp, border_mode));
+    if (!xy || (interp == VP_INTER_NEAREST ? frac != nullptr : frac == nullptr))
+        return vp_fail(ctx, VP_ERR_INVALID, "vp_remap_fixed_dev: nearest takes the x,y plane alone, linear needs the fraction plane");
+    const size_t n = (size_t)mw * mh;
+    VP_TRY(gather_dev_args(ctx, "vp_remap_fixed_dev: src_stride, or dst overlaps src or a map", d_src, src_stride, w, h, cn, d_dst, mw, mh, xy, n * 4, frac, n * 2));
+    return vpk_remap_fixed(ctx, d_src, src_stride, w, h, cn, xy, frac, mw, mh, interp == VP_INTER_LINEAR, border_mode, border_value, d_dst);
+}
+
+int vp_remap_f32_dev(vp_ctx* ctx, const uint8_t* d_src, size_t src_stride, int w, int h, int cn, const float* mapx, const float* mapy, int mw, int mh, int interp,
+                     int border_mode, const uint8_t* border_value, uint8_t* d_dst)
+{
+    VP_TRY(check_ctx(ctx));
+    VP_TRY(gather_args(ctx, "vp_remap_f32_dev arguments", d_src, d_dst, w, h, cn, mw, mh, interp, border_mode));
+    if (!mapx) return vp_fail(ctx, VP_ERR_INVALID, "vp_remap_f32_dev: no map");
+    const size_t n = (size_t)mw * mh;
+    VP_TRY(gather_dev_args(ctx, "vp_remap_f32_dev: src_stride, or dst overlaps src or a map", d_src, src_stride, w, h, cn, d_dst, mw, mh, mapx, n * (mapy ? 4 : 8),
+                           mapy, n * 4));
+    return vpk_remap_f32(ctx, d_src, src_stride, w, h, cn, mapx, mapy, mw, mh, interp == VP_INTER_LINEAR, border_mode, border_value, d_dst);
+}
+
+int vp_remap_u8(vp_ctx* ctx, const uint8_t* src, int w, int h, int cn, const float* mapx, const float* mapy, int mw, int mh, int interp, int border_mode,
+                const uint8_t* border_value, uint8_t* dst)
+{
+    VP_TRY(check_ctx(ctx));
+    VP_TRY(gather_args(ctx, "vp_remap_u8 arguments", src, dst, w, h, cn, mw, mh, interp, border_mode));
+    if (!mapx) return vp_fail(ctx, VP_ERR_INVALID, "vp_remap_u8: no map");
+    const size_t n = (size_t)mw * mh, sbytes = (size_t)w * h * cn, dbytes = n * cn, xbytes = n * (mapy ? 4 : 8), ybytes = mapy ? n * 4 : 0;
+    VP_TRY(vp_ws_reserve(ctx, vp_align(sbytes) + vp_align(dbytes) + vp_align(xbytes) + vp_align(ybytes) + 1024));
+    TAKE(d_src, uint8_t*, sbytes);
+    TAKE(d_dst, uint8_t*, dbytes);
+    TAKE(d_mx, float*, xbytes);
+    float* d_my = nullptr;
+    if (mapy) {
+        d_my = (float*)vp_ws_take(ctx, ybytes);
+        if (!d_my) return vp_fail(ctx, VP_ERR_NOMEM, "workspace exhausted: d_my");
+    }
+    VP_TRY(h2d(ctx, d_src, src, sbytes));
+    VP_TRY(h2d(ctx, d_mx, mapx, xbytes));
+    if (mapy) VP_TRY(h2d(ctx, d_my, mapy, ybytes));
+    VP_TRY(vpk_remap_f32(ctx, d_src, 0, w, h, cn, d_mx, d_my, mw, mh, interp == VP_INTER_LINEAR, border_mode, border_value, d_dst));
+    VP_TRY(d2h(ctx, dst, d_dst, dbytes));
+    return vp_synchronize(ctx);
+}
+
+static int wp_args(vp_ctx* ctx, const char* who, const void* src, const void* dst, int w, int h, int cn, const double* m33, int flags, int border_mode, int dw, int dh)
+{
+    if (!m33 || (flags & ~(VP_WARP_INVERSE_MAP | VP_INTER_LINEAR))) return vp_fail(ctx, VP_ERR_INVALID, who);
+    VP_TRY(gather_args(ctx, who, src, dst, w, h, cn, dw, dh, flags & ~VP_WARP_INVERSE_MAP, border_mode));
+    for (int i = 0; i < 9; i++)
+        if (!std::isfinite(m33[i])) return vp_fail(ctx, VP_ERR_INVALID, "warp perspective: matrix is not finite");
+    return VP_OK;
+}
+
+int vp_warp_perspective_u8(vp_ctx* ctx, const uint8_t* src, int w, int h, int cn, const double* m33, int flags, int border_mode, const uint8_t* border_value,
+                           uint8_t* dst, int dw, int dh)
+{
+    VP_TRY(check_ctx(ctx));
+    VP_TRY(wp_args(ctx, "vp_warp_perspective_u8 arguments", src, dst, w, h, cn, m33, flags, border_mode, dw, dh));
+    const size_t sbytes = (size_t)w * h * cn, dbytes = (size_t)dw * dh * cn;
+    VP_TRY(vp_ws_reserve(ctx, vp_align(sbytes) + vp_align(dbytes) + 1024));
+    TAKE(d_src, uint8_t*, sbytes);
+    TAKE(d_dst, uint8_t*, dbytes);
+    VP_TRY(h2d(ctx, d_src, src, sbytes));
+    VP_TRY(vpk_warp_perspective(ctx, d_src, 0, w, h, cn, m33, (flags & VP_WARP_INVERSE_MAP) != 0, (flags & VP_INTER_LINEAR) != 0, border_mode, border_value, d_dst,
+                                dw, dh));
+    VP_TRY(d2h(ctx, dst, d_dst, dbytes));
+    return vp_synchronize(ctx);
+}
+
+int vp_warp_perspective_dev(vp_ctx* ctx, const uint8_t* d_src, size_t src_stride, int w, int h, int cn, const double* m33, int flags, int border_mode,
+                            const uint8_t* border_value, uint8_t* d_dst, int dw, int dh)
+{
+    VP_TRY(check_ctx(ctx));
+    VP_TRY(wp_args(ctx, "vp_warp_perspective_dev arguments", d_src, d_dst, w, h, cn, m33, flags, border_mode, dw, dh));
+    VP_TRY(gather_dev_args(ctx, "vp_warp_perspective_dev: src_stride, or dst overlaps src", d_src, src_stride, w, h, cn, d_dst, dw, dh, nullptr, 0, nullptr, 0));
+    return vpk_warp_perspective(ctx, d_src, src_stride, w, h, cn, m33, (flags & VP_WARP_INVERSE_MAP) != 0, (flags & VP_INTER_LINEAR) != 0, border_mode, border_value,
+                                d_dst, dw, dh);
 }
 
 // cv2.adaptiveThreshold, mean (blocks up to 151) and Gaussian (up to VP_AGAUSS_MAX_BLOCK): maxValue rounded into [0, 255], C rounded

@@ -159,6 +159,19 @@ int vpk_warp_affine_u8(vp_ctx* ctx, const uint8_t* d_src, int sw, int sh, int cn
 size_t vp_nms_ws_bytes(int n);
 int vpk_nms(vp_ctx* ctx, const float* d_boxes, const float* d_scores, int n, float thr, int rotated, int max_keep, int* d_keep, int* d_nkeep);
 
+// ---- gathers (vp_remap.hip; the tile: vp_remap_plan.h) ------------------------------------------------
+// cv2.remap from the fixed form (d_xy: int16 x,y pairs; d_frac: fraction indices, NULL for nearest) or from float maps (d_mapy NULL:
+// d_mapx holds interleaved pairs), cv2.convertMaps (float -> fixed) and cv2.warpPerspective.  sstride: bytes between source rows
+// (0: packed); results packed; cval: cn bytes or NULL (0); linear: 1 bilinear, 0 nearest.  All enqueue one launch.
+int vpk_remap_fixed(vp_ctx* ctx, const uint8_t* d_src, size_t sstride, int sw, int sh, int cn, const int16_t* d_xy, const uint16_t* d_frac, int mw, int mh,
+                    int linear, int border, const uint8_t* cval, uint8_t* d_dst);
+int vpk_remap_f32(vp_ctx* ctx, const uint8_t* d_src, size_t sstride, int sw, int sh, int cn, const float* d_mapx, const float* d_mapy, int mw, int mh,
+                  int linear, int border, const uint8_t* cval, uint8_t* d_dst);
+int vpk_convert_maps(vp_ctx* ctx, const float* d_mapx, const float* d_mapy, int mw, int mh, int nearest, int16_t* d_xy, uint16_t* d_frac);
+int vpk_warp_perspective(vp_ctx* ctx, const uint8_t* d_src, size_t sstride, int sw, int sh, int cn, const double* M33, int inverse_map, int linear, int border,
+                         const uint8_t* cval, uint8_t* d_dst, int dw, int dh);
+void vp_invert33(const double* m33, double* out33);   // cv::invert's 3x3 closed form (zeros when singular)
+
 // ---- filters (vp_filter.hip) -----------------------------------------------------------------------
 // d_ithresh (nullable): the threshold comes from that device word (vpk_otsu_scan) instead of ithresh
 int vpk_threshold_u8(vp_ctx* ctx, const uint8_t* d_src, size_t n, int ithresh, int imaxval, int type, uint8_t* d_dst, const int32_t* d_ithresh = nullptr);

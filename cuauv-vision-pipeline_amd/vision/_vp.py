@@ -50,6 +50,8 @@ ARITH_ADD, ARITH_SUB, ARITH_ABSDIFF = 0, 1, 2
 DERIV_SOBEL, DERIV_SCHARR, DERIV_LAPLACIAN = 0, 1, 2
 DEPTH_8U, DEPTH_16S, DEPTH_32F, DEPTH_64F = 0, 3, 5, 6
 BORDER_CONSTANT, BORDER_REPLICATE, BORDER_REFLECT, BORDER_REFLECT_101, BORDER_ISOLATED = 0, 1, 2, 4, 16
+INTER_NEAREST, INTER_LINEAR = 0, 1
+WARP_INVERSE_MAP = 16
 PROF_KERNELS = 15
 
 
@@ -232,6 +234,15 @@ _SIGS = {
     "vp_equalize_hist_dev": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_int, C.c_int, C.c_void_p]),
     "vp_clahe_u8": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_double, C.c_int, C.c_int, C.c_void_p]),
     "vp_clahe_dev": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_int, C.c_int, C.c_double, C.c_int, C.c_int, C.c_void_p]),
+    "vp_convert_maps_dev": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
+    "vp_remap_fixed_dev": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int,
+                                     C.c_void_p, C.c_void_p]),
+    "vp_remap_f32_dev": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int,
+                                   C.c_void_p, C.c_void_p]),
+    "vp_remap_u8": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
+    "vp_warp_perspective_u8": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_int]),
+    "vp_warp_perspective_dev": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p,
+                                          C.c_int, C.c_int]),
 }
 
 

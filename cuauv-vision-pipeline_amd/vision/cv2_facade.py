@@ -921,6 +921,185 @@ def _warp_affine(src, M, dsize, flags, borderMode, borderValue):
     return out
 
 
+INTER_NEAREST = 0
+CV_16UC1, CV_32FC1, CV_16SC2, CV_32FC2 = 2, 5, 11, 13
+
+
+def _gather(name, call):
+    """what vision.utils.transform refuses (TypeError / ValueError, before anything is launched) is a cv2.error here"""
+    try:
+        return call()
+    except (TypeError, ValueError) as e:
+        raise error(f"{name}: {e}") from None
+
+
+def remap(src, map1, map2, interpolation, dst=None, borderMode=BORDER_CONSTANT, borderValue=0):
+    """cv2.remap on uint8 images of 1..4 channels, INTER_LINEAR or INTER_NEAREST, BORDER_CONSTANT or BORDER_REPLICATE: OpenCV's
+    classical fixed-point path byte for byte, on the GPU (libvp vp_remap_*).  Maps (numpy or DeviceMat): two
+    float32 planes; one float32 (h, w, 2) plane with map2 None or empty; convertMaps' fixed form (int16 (h, w, 2) + uint16 (h, w));
+    or, with INTER_NEAREST, an int16 (h, w, 2) plane alone.  A DeviceMat in gives a DeviceMat out, numpy gives numpy."""
+    if interpolation not in (INTER_NEAREST, INTER_LINEAR):
+        raise error("remap: only INTER_NEAREST and INTER_LINEAR are on the accelerated path")
+    if borderMode not in (BORDER_CONSTANT, BORDER_REPLICATE):
+        raise error("remap: only BORDER_CONSTANT and BORDER_REPLICATE are on the accelerated path")
+    src, _ = _device_source(src)
+    return _into(dst, _gather("remap", lambda: _transform._remap(src, map1, map2, interpolation == INTER_NEAREST, borderMode, borderValue)))
+
+
+def warpPerspective(src, M, dsize, dst=None, flags=INTER_LINEAR, borderMode=BORDER_CONSTANT, borderValue=0):
+    """cv2.warpPerspective on uint8 images of 1..4 channels; flags: INTER_LINEAR or INTER_NEAREST, optionally | WARP_INVERSE_MAP.
+    OpenCV's classical fixed-point path byte for byte, on the GPU (libvp vp_warp_perspective_*)."""
+    if flags is None:
+        flags = INTER_LINEAR
+    if (flags & ~WARP_INVERSE_MAP) not in (INTER_NEAREST, INTER_LINEAR):
+        raise error("warpPerspective: only INTER_NEAREST and INTER_LINEAR are on the accelerated path")
+    if borderMode not in (BORDER_CONSTANT, BORDER_REPLICATE):
+        raise error("warpPerspective: only BORDER_CONSTANT and BORDER_REPLICATE are on the accelerated path")
+    src, _ = _device_source(src)
+    try:
+        dw, dh = int(dsize[0]), int(dsize[1])
+    except (TypeError, ValueError, IndexError):
+        raise error("warpPerspective: dsize must be (width, height)") from None
+    return _into(dst, _gather("warpPerspective", lambda: _transform._warp_perspective(src, M, dw, dh, bool(flags & WARP_INVERSE_MAP),
+                                                                                     (flags & ~WARP_INVERSE_MAP) == INTER_NEAREST, borderMode, borderValue)))
+
+
+def convertMaps(map1, map2, dstmap1type, nninterpolation=False):
+    """cv2.convertMaps from float32 maps (two planes, or one (h, w, 2) plane with map2 None or empty) to the fixed form:
+    (int16 (h, w, 2), uint16 (h, w)), or (int16 (h, w, 2) of rounded coordinates, empty) with nninterpolation.  On the GPU (libvp
+    vp_convert_maps_dev), byte for byte; DeviceMat maps give DeviceMat maps.  The other directions are outside the path."""
+    from vision.devmat import DeviceMat
+    if dstmap1type != CV_16SC2:
+        raise error("convertMaps: only the conversion to CV_16SC2 is on the accelerated path")
+    kind = _gather("convertMaps", lambda: _transform._classify_maps(map1, map2))[0]
+    if kind == "fixed":
+        raise error("convertMaps: only float32 source maps are on the accelerated path")
+    on_dev = any(isinstance(_as(m), DeviceMat) for m in (map1, map2) if m is not None)
+    t = _gather("convertMaps", lambda: _transform.RemapTable(map1, map2, bool(nninterpolation)))
+    if on_dev:
+        return t.xy, (np.empty((0,), np.uint16) if t.frac is None else t.frac)
+    return t.xy.host_copy(), (np.empty((0,), np.uint16) if t.frac is None else t.frac.host_copy())
+
+
+def _as(m):
+    from vision.utils.helpers import as_mat
+    return as_mat(m)
+
+
+def _camera(name, cameraMatrix, distCoeffs):
+    """(fx, fy, cx, cy), the 8 rational-model coefficients k1 k2 p1 p2 k3 k4 k5 k6 (missing ones 0), in float64"""
+    A = np.asarray(cameraMatrix, dtype=np.float64)
+    if A.shape != (3, 3) or not np.isfinite(A).all():
+        raise error(f"{name}: the camera matrix must be a finite 3x3 matrix")
+    d = np.zeros(0) if distCoeffs is None else np.asarray(distCoeffs, dtype=np.float64).ravel()
+    if d.size not in (0, 4, 5, 8, 12, 14) or not np.isfinite(d).all():
+        raise error(f"{name}: 4, 5, 8, 12 or 14 finite distortion coefficients")
+    if d.size > 8 and np.any(d[8:] != 0):
+        raise error(f"{name}: the thin-prism (s1..s4) and tilt (tauX, tauY) coefficients are outside the path (DESIGN.md section 7)")
+    k = np.zeros(8)
+    k[:min(d.size, 8)] = d[:8]
+    return A, k
+
+
+def _undistort_coords(name, cameraMatrix, distCoeffs, R, newCameraMatrix, size):
+    """source coordinates (u, v), float64 (h, w) each, of every pixel of the undistorted image: the model of
+    cv2.initUndistortRectifyMap evaluated per pixel (cv2 accumulates the row increments instead: not bit-exact)"""
+    A, k = _camera(name, cameraMatrix, distCoeffs)
+    w, h = int(size[0]), int(size[1])
+    if w <= 0 or h <= 0:
+        raise error(f"{name}: the size must be positive")
+    Ar = A if newCameraMatrix is None else np.asarray(newCameraMatrix, dtype=np.float64)
+    if Ar.shape == (3, 4):
+        Ar = Ar[:, :3]
+    Rm = np.eye(3) if R is None else np.asarray(R, dtype=np.float64)
+    if Ar.shape != (3, 3) or Rm.shape != (3, 3) or not np.isfinite(Ar).all() or not np.isfinite(Rm).all():
+        raise error(f"{name}: R and the new camera matrix must be finite 3x3 matrices")
+    try:
+        ir = np.linalg.inv(Ar @ Rm)
+    except np.linalg.LinAlgError:
+        raise error(f"{name}: newCameraMatrix * R is singular") from None
+    j, i = np.meshgrid(np.arange(w, dtype=np.float64), np.arange(h, dtype=np.float64))
+    X = ir[0, 0] * j + ir[0, 1] * i + ir[0, 2]
+    Y = ir[1, 0] * j + ir[1, 1] * i + ir[1, 2]
+    W = ir[2, 0] * j + ir[2, 1] * i + ir[2, 2]
+    x, y = X / W, Y / W
+    k1, k2, p1, p2, k3, k4, k5, k6 = k
+    x2, y2 = x * x, y * y
+    r2, xy2 = x2 + y2, 2 * x * y
+    kr = (1 + ((k3 * r2 + k2) * r2 + k1) * r2) / (1 + ((k6 * r2 + k5) * r2 + k4) * r2)
+    xd = x * kr + p1 * xy2 + p2 * (r2 + 2 * x2)
+    yd = y * kr + p1 * (r2 + 2 * y2) + p2 * xy2
+    return A[0, 0] * xd + A[0, 2], A[1, 1] * yd + A[1, 2]
+
+
+def _fixed_from_double(u, v):
+    """CV_16SC2 maps from double coordinates: iu = saturate_cast<int>(u * 32), integer part iu >> 5, fraction index from iu & 31.
+    The integer part is saturated to int16 here; cv2 casts it to short without saturating, so the two differ beyond +-32768."""
+    iu = np.clip(np.rint(u * 32), -2147483648, 2147483647).astype(np.int64)
+    iv = np.clip(np.rint(v * 32), -2147483648, 2147483647).astype(np.int64)
+    xy = np.stack([np.clip(iu >> 5, -32768, 32767), np.clip(iv >> 5, -32768, 32767)], axis=-1).astype(np.int16)
+    return np.ascontiguousarray(xy), ((iv & 31) * 32 + (iu & 31)).astype(np.uint16)
+
+
+def initUndistortRectifyMap(cameraMatrix, distCoeffs, R, newCameraMatrix, size, m1type):
+    """cv2.initUndistortRectifyMap for the rational model without thin-prism and tilt terms (4, 5 or 8 coefficients), host numpy in
+    float64: run once per calibration.  m1type CV_32FC1 -> (mapx, mapy), CV_32FC2 -> (interleaved map, empty), CV_16SC2 -> the fixed
+    form.  Within an ulp of float32 of cv2's maps, not bit for bit."""
+    if m1type not in (CV_32FC1, CV_32FC2, CV_16SC2):
+        raise error("initUndistortRectifyMap: m1type must be CV_32FC1, CV_32FC2 or CV_16SC2")
+    u, v = _undistort_coords("initUndistortRectifyMap", cameraMatrix, distCoeffs, R, newCameraMatrix, size)
+    if m1type == CV_32FC1:
+        return u.astype(np.float32), v.astype(np.float32)
+    if m1type == CV_32FC2:
+        return np.ascontiguousarray(np.stack([u, v], axis=-1).astype(np.float32)), np.empty((0,), np.float32)
+    return _fixed_from_double(u, v)
+
+
+def undistort(src, cameraMatrix, distCoeffs, dst=None, newCameraMatrix=None):
+    """cv2.undistort: initUndistortRectifyMap(R = identity, CV_16SC2) of the image's size, then remap(INTER_LINEAR,
+    BORDER_CONSTANT 0) on the GPU.  For a stream of frames build the table once: vision.utils.transform.undistorter."""
+    src, _ = _device_source(src)
+    if src.dtype != np.uint8 or src.ndim not in (2, 3) or src.size == 0:
+        raise error("undistort: expected a non-empty uint8 image")
+    xy, frac = initUndistortRectifyMap(cameraMatrix, distCoeffs, None, newCameraMatrix, (src.shape[1], src.shape[0]), CV_16SC2)
+    return _into(dst, _gather("undistort", lambda: _transform._remap(src, xy, frac, False, BORDER_CONSTANT, 0)))
+
+
+def getPerspectiveTransform(src, dst, solveMethod=0):
+    """cv2.getPerspectiveTransform: the 3x3 float64 matrix (M[2, 2] = 1) that maps four source points to four destination points;
+    the 8x8 system solved in float64 on the host.  Not claimed bit-exact."""
+    s = np.asarray(src, dtype=np.float64).reshape(-1, 2)
+    d = np.asarray(dst, dtype=np.float64).reshape(-1, 2)
+    if s.shape != (4, 2) or d.shape != (4, 2):
+        raise error("getPerspectiveTransform: four source and four destination points")
+    a = np.zeros((8, 8))
+    b = np.zeros(8)
+    for i in range(4):
+        a[i] = [s[i, 0], s[i, 1], 1, 0, 0, 0, -s[i, 0] * d[i, 0], -s[i, 1] * d[i, 0]]
+        a[i + 4] = [0, 0, 0, s[i, 0], s[i, 1], 1, -s[i, 0] * d[i, 1], -s[i, 1] * d[i, 1]]
+        b[i], b[i + 4] = d[i, 0], d[i, 1]
+    try:
+        x = np.linalg.solve(a, b)
+    except np.linalg.LinAlgError:
+        raise error("getPerspectiveTransform: the points are degenerate") from None
+    return np.append(x, 1.0).reshape(3, 3)
+
+
+def perspectiveTransform(src, m, dst=None):
+    """cv2.perspectiveTransform of 2-D points ((N, 1, 2) or (N, 2), float32 or float64) by a 3x3 matrix, host numpy in float64:
+    (x', y') = (m00 x + m01 y + m02, m10 x + m11 y + m12) / w with w = m20 x + m21 y + m22; 0 where w is 0."""
+    p = np.asarray(src)
+    M = np.asarray(m, dtype=np.float64)
+    if p.dtype not in (np.float32, np.float64) or p.ndim not in (2, 3) or p.shape[-1] != 2 or M.shape != (3, 3):
+        raise error("perspectiveTransform: float32 / float64 points of 2 channels and a 3x3 matrix")
+    x, y = p[..., 0].astype(np.float64), p[..., 1].astype(np.float64)
+    w = M[2, 0] * x + M[2, 1] * y + M[2, 2]
+    with np.errstate(divide="ignore", invalid="ignore"):
+        w = np.where(w != 0, 1.0 / w, 0.0)
+    out = np.stack([(M[0, 0] * x + M[0, 1] * y + M[0, 2]) * w, (M[1, 0] * x + M[1, 1] * y + M[1, 2]) * w], axis=-1).astype(p.dtype)
+    return _into(dst, out)
+
+
 def resize(src, dsize, dst=None, fx=None, fy=None, interpolation=INTER_LINEAR):
     """cv2.resize(src, (width, height)) with the default bilinear interpolation, uint8 images (modules/preprocessor.py:136-144).
     Positional order as in cv2: (src, dsize, dst, fx, fy, interpolation); dsize None or (0, 0) takes the size from fx / fy."""

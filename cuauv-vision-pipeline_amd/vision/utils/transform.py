@@ -271,6 +271,175 @@ def convert_scale_abs(mat: np.ndarray) -> np.ndarray:
     return out
 
 
+def _border_bytes(value):
+    """cv2's borderValue (a Scalar: missing entries are 0) as four saturated bytes"""
+    bv = np.zeros(4, np.uint8)
+    vals = np.atleast_1d(np.asarray(value, dtype=np.float64)).ravel()[:4]
+    bv[:len(vals)] = np.clip(np.rint(vals), 0, 255).astype(np.uint8)
+    return bv
+
+
+def _gather_checks(mat, border):
+    mat, cn = _deriv_source(mat)
+    if mat.shape[0] > 32767 or mat.shape[1] > 32767:
+        raise ValueError("the source must be at most 32767 x 32767, as cv2 asserts")
+    if int(border) not in (_vp.BORDER_CONSTANT, _vp.BORDER_REPLICATE):
+        raise ValueError("only BORDER_CONSTANT and BORDER_REPLICATE are on the accelerated path")
+    return mat, cn
+
+
+def _classify_maps(map1, map2):
+    """The map forms of cv2.remap: ("planar", x, y), ("interleaved", xy, None) - float32 - or ("fixed", xy int16, fractions uint16 or
+    None); and the maps' (height, width).  An empty map2 counts as none."""
+    a = as_mat(map1)
+    b = None if map2 is None else as_mat(map2)
+    if b is not None and b.size == 0:
+        b = None
+    ok = lambda m: isinstance(m, (np.ndarray, DeviceMat)) and m.size > 0
+    if not ok(a) or (b is not None and not ok(b)):
+        raise TypeError("the maps must be non-empty arrays")
+    if a.dtype == np.float32 and a.ndim == 2 and b is not None and b.dtype == np.float32 and tuple(b.shape) == tuple(a.shape):
+        return "planar", a, b, tuple(a.shape)
+    if a.dtype == np.float32 and a.ndim == 3 and a.shape[2] == 2 and b is None:
+        return "interleaved", a, None, tuple(a.shape[:2])
+    if a.dtype == np.int16 and a.ndim == 3 and a.shape[2] == 2:
+        if b is None:
+            return "fixed", a, None, tuple(a.shape[:2])
+        if b.dtype in (np.uint16, np.int16) and tuple(b.shape) in (tuple(a.shape[:2]), tuple(a.shape[:2]) + (1,)):
+            return "fixed", a, b, tuple(a.shape[:2])
+    raise TypeError("the maps must be two float32 planes, one float32 (h, w, 2) plane, or an int16 (h, w, 2) plane with an optional uint16 (h, w) plane")
+
+
+def _map_on_device(ctx, m, pending):
+    if isinstance(m, DeviceMat):
+        m.refresh_device(ctx)
+        return m
+    return DeviceMat.from_host(ctx, m, pending=pending)
+
+
+def _remap(mat, map1, map2, nearest, border=_vp.BORDER_CONSTANT, border_value=0):
+    """libvp vp_remap_u8 / vp_remap_f32_dev / vp_remap_fixed_dev.  A DeviceMat source gives a DeviceMat and stays in HBM (maps that are
+    numpy arrays are uploaded); a numpy source gives numpy.  Nothing is launched for arguments outside the path: they raise."""
+    from vision.devmat import finish_uploads
+    mat, cn = _gather_checks(mat, border)
+    kind, a, b, (mh, mw) = _classify_maps(map1, map2)
+    nearest = bool(nearest)
+    if kind == "fixed" and nearest and b is not None:
+        raise ValueError("nearest interpolation takes the int16 x,y plane alone (cv2 rounds by the fraction plane there: DESIGN.md section 7)")
+    if kind == "fixed" and not nearest and b is None:
+        raise ValueError("an int16 x,y plane alone is a nearest-neighbour map: pass INTER_NEAREST, or the fraction plane")
+    if mh > 65535 or mw > (1 << 24) or mh * mw >= (1 << 31):
+        raise ValueError("the maps are larger than 65535 rows, 2^24 columns or 2^31 entries")
+    interp = _vp.INTER_NEAREST if nearest else _vp.INTER_LINEAR
+    bv = _border_bytes(border_value)
+    ctx = _vp.default_context()
+    lib = _vp.lib()
+    h, w = mat.shape[:2]
+    out_shape = (mh, mw) if mat.ndim == 2 else (mh, mw, cn)
+    on_dev = isinstance(mat, DeviceMat)
+    if not on_dev and kind != "fixed" and isinstance(a, np.ndarray) and (b is None or isinstance(b, np.ndarray)):
+        src, a = np.ascontiguousarray(mat), np.ascontiguousarray(a)
+        b = None if b is None else np.ascontiguousarray(b)
+        out = np.empty(out_shape, np.uint8)
+        _vp.check(lib.vp_remap_u8(ctx.handle, _vp.ptr(src), w, h, cn, _vp.ptr(a), None if b is None else _vp.ptr(b), mw, mh, interp, int(border), _vp.ptr(bv),
+                                  _vp.ptr(out)), ctx.handle)
+        return out
+    up = []
+    try:
+        src = _map_on_device(ctx, mat, up)
+        da = _map_on_device(ctx, a, up)
+        db = None if b is None else _map_on_device(ctx, b, up)
+        out = DeviceMat(ctx, out_shape)
+        entry = lib.vp_remap_fixed_dev if kind == "fixed" else lib.vp_remap_f32_dev
+        _vp.check(entry(ctx.handle, src.dev_ptr, w * cn, w, h, cn, da.dev_ptr, None if db is None else db.dev_ptr, mw, mh, interp, int(border), _vp.ptr(bv),
+                        out.dev_ptr), ctx.handle)
+    finally:
+        finish_uploads(ctx, up)
+    return out if on_dev else out.host_copy()
+
+
+def remap(mat: np.ndarray, map_x, map_y=None, nearest: bool = False, border: int = _vp.BORDER_CONSTANT, border_value=0) -> np.ndarray:
+    """cv2.remap on uint8 images of 1..4 channels with bilinear (default) or nearest-neighbour interpolation, OpenCV's classical
+    fixed-point path byte for byte.  Maps, numpy or DeviceMat: two float32 planes; one float32 (h, w, 2)
+    plane; the fixed form of cv2.convertMaps (int16 (h, w, 2) + uint16 (h, w)); or an int16 (h, w, 2) plane alone with nearest=True.
+    The result has the maps' size.  Maps that stay the same from frame to frame belong in a RemapTable.  Not a name of the
+    reference's utils/transform.py."""
+    return _remap(mat, map_x, map_y, nearest, border, border_value)
+
+
+class RemapTable:
+    """Float maps turned once into the fixed form (int16 coordinates + 5 + 5 bit fractions, libvp vp_convert_maps_dev) and kept in
+    HBM: 6 bytes per destination pixel (4 for nearest) instead of 8.  `apply` is one launch (vp_remap_fixed_dev) and gives the bytes
+    `remap` gives from the float maps."""
+
+    def __init__(self, map_x, map_y=None, nearest: bool = False):
+        from vision.devmat import finish_uploads
+        kind, a, b, (mh, mw) = _classify_maps(map_x, map_y)
+        if kind == "fixed":
+            raise TypeError("a RemapTable is built from float32 maps")
+        if mh > 65535 or mw > (1 << 24):
+            raise ValueError("the maps are larger than 65535 rows or 2^24 columns")
+        ctx = _vp.default_context()
+        self.nearest = bool(nearest)
+        self.shape = (mh, mw)
+        up = []
+        try:
+            da = _map_on_device(ctx, a, up)
+            db = None if b is None else _map_on_device(ctx, b, up)
+            self.xy = DeviceMat(ctx, (mh, mw, 2), np.int16)
+            self.frac = None if self.nearest else DeviceMat(ctx, (mh, mw), np.uint16)
+            _vp.check(_vp.lib().vp_convert_maps_dev(ctx.handle, da.dev_ptr, None if db is None else db.dev_ptr, mw, mh, int(self.nearest), self.xy.dev_ptr,
+                                                    None if self.frac is None else self.frac.dev_ptr), ctx.handle)
+        finally:
+            finish_uploads(ctx, up)
+
+    def apply(self, mat, border: int = _vp.BORDER_CONSTANT, border_value=0):
+        """The remapped image: a DeviceMat for a DeviceMat (one launch, nothing copied), numpy for numpy."""
+        return _remap(mat, self.xy, self.frac, self.nearest, border, border_value)
+
+
+def undistorter(camera_matrix, dist_coeffs, size, new_camera_matrix=None) -> RemapTable:
+    """The lens-undistortion table of a calibrated camera, built once: cv2.initUndistortRectifyMap (no rectification; the new camera
+    matrix defaults to the camera matrix) into a RemapTable.  size = (width, height) of the undistorted image.  A module calls
+    `table.apply(frame)` per frame."""
+    from vision import cv2_facade
+    k = camera_matrix if new_camera_matrix is None else new_camera_matrix
+    mx, my = cv2_facade.initUndistortRectifyMap(camera_matrix, dist_coeffs, None, k, size, cv2_facade.CV_32FC1)
+    return RemapTable(mx, my)
+
+
+def _warp_perspective(mat, M, dw, dh, inverse_map=False, nearest=False, border=_vp.BORDER_CONSTANT, border_value=0):
+    """libvp vp_warp_perspective_u8 / vp_warp_perspective_dev"""
+    mat, cn = _gather_checks(mat, border)
+    m = np.ascontiguousarray(np.asarray(M, dtype=np.float64))
+    dw, dh = int(dw), int(dh)
+    if m.shape != (3, 3) or not np.isfinite(m).all():
+        raise ValueError("M must be a finite 3x3 matrix")
+    if dw <= 0 or dh <= 0 or dh > 65535 or dw > (1 << 24) or dw * dh >= (1 << 31):
+        raise ValueError("the size must be positive, at most 65535 rows, 2^24 columns and 2^31 pixels")
+    flags = (_vp.WARP_INVERSE_MAP if inverse_map else 0) | (_vp.INTER_NEAREST if nearest else _vp.INTER_LINEAR)
+    bv = _border_bytes(border_value)
+    ctx = _vp.default_context()
+    h, w = mat.shape[:2]
+    out_shape = (dh, dw) if mat.ndim == 2 else (dh, dw, cn)
+    if isinstance(mat, DeviceMat):
+        mat.refresh_device(ctx)
+        out = DeviceMat(ctx, out_shape)
+        _vp.check(_vp.lib().vp_warp_perspective_dev(ctx.handle, mat.dev_ptr, w * cn, w, h, cn, _vp.ptr(m), flags, int(border), _vp.ptr(bv), out.dev_ptr, dw, dh),
+                  ctx.handle)
+        return out
+    src = np.ascontiguousarray(mat)
+    out = np.empty(out_shape, np.uint8)
+    _vp.check(_vp.lib().vp_warp_perspective_u8(ctx.handle, _vp.ptr(src), w, h, cn, _vp.ptr(m), flags, int(border), _vp.ptr(bv), _vp.ptr(out), dw, dh), ctx.handle)
+    return out
+
+
+def warp_perspective(mat: np.ndarray, M, width: int, height: int) -> np.ndarray:
+    """cv2.warpPerspective(mat, M, (width, height)): bilinear, uncovered pixels 0, M (3x3) maps source to destination; OpenCV's
+    classical fixed-point path byte for byte.  Not a name of the reference's utils/transform.py."""
+    return _warp_perspective(mat, M, width, height)
+
+
 def rotate(mat: np.ndarray, degrees: float) -> np.ndarray:
     """utils/transform.py:180-196: rotation about the image centre, positive = counterclockwise, borders replicated."""
     from vision import cv2_facade

@@ -530,6 +530,41 @@ int vp_ccl_dev(vp_ctx* ctx, const uint8_t* src_dev, size_t src_stride, int w, in
 int vp_ccl_bits_dev(vp_ctx* ctx, const unsigned long long* bits_dev, int w, int h, int numbering, int32_t* labels_dev,
                     int32_t* stats_host, double* centroids_host, int max_labels, int32_t* n_labels);
 
+/* ---- remap, convertMaps and warpPerspective -------------------------------------------------------------------------------------- *
+ * cv2.remap(src, map1, map2, interpolation, borderMode, borderValue), cv2.convertMaps and cv2.warpPerspective on 8-bit images of
+ * cn = 1..4 channels, OpenCV's classical fixed-point path (every release up to 4.10): every source
+ * coordinate becomes an int16 integer part and a 5 + 5 bit fraction index fy * 32 + fx, and a linear sample is the 15-bit bilinear
+ * blend of vp_warp_affine_u8.  interp: VP_INTER_NEAREST or VP_INTER_LINEAR; border_mode: VP_BORDER_CONSTANT (border_value: cn bytes,
+ * NULL = 0) or VP_BORDER_REPLICATE.  The destination has the maps' size (map_w x map_h), packed; the source is w x h, each at most
+ * 32767 as cv2 asserts; map_h <= 65535, map_w <= 2^24 and map_w * map_h < 2^31.  Map planes need only their
+ * element's alignment; 16-byte aligned planes and rows of a multiple of four pixels take the wide loads and stores.
+ * Maps: float32, as two planes (mapx, mapy) or as one plane of interleaved (x, y) pairs (mapy NULL); or the fixed form: xy, int16
+ * (x, y) pairs, plus frac, uint16 fraction indices (only the low 10 bits are read).  Nearest takes xy alone: frac must be NULL then.
+ * Float map values must be finite with |v| * 32 < 2^31; what a NaN or a larger value gives is cv2's x86 cvRound behaviour and is
+ * not promised.  vp_convert_maps_dev turns float maps into the fixed form (nearest != 0: xy_out holds the rounded coordinates and
+ * frac_out must be NULL); remapping from its result gives the bytes vp_remap_f32_dev gives from the float maps.
+ * vp_warp_perspective_*: m33 is the 3x3 matrix, row-major doubles, mapping source to destination unless flags has
+ * VP_WARP_INVERSE_MAP; flags also carries the interpolation (VP_INTER_NEAREST or VP_INTER_LINEAR).  The matrix and the border value
+ * travel as kernel arguments.
+ * The _dev entries copy nothing and wait for nothing: one launch on the context's stream.  vp_remap_u8 and vp_warp_perspective_u8
+ * stage host operands (float maps) and synchronise.  VP_ERR_INVALID before anything is launched: null pointers, cn outside 1..4,
+ * non-positive or oversized dimensions, an unknown interpolation or border, src_stride < w * cn, a destination that overlaps the
+ * source or a map, nearest together with a fraction plane, linear without one, a matrix that is not finite. */
+enum { VP_INTER_NEAREST = 0, VP_INTER_LINEAR = 1 };
+int vp_convert_maps_dev(vp_ctx* ctx, const float* mapx_dev, const float* mapy_dev, int map_w, int map_h, int nearest, int16_t* xy_out_dev,
+                        uint16_t* frac_out_dev);
+int vp_remap_fixed_dev(vp_ctx* ctx, const uint8_t* src_dev, size_t src_stride, int w, int h, int cn, const int16_t* xy_dev,
+                       const uint16_t* frac_dev, int map_w, int map_h, int interp, int border_mode, const uint8_t* border_value,
+                       uint8_t* dst_dev);
+int vp_remap_f32_dev(vp_ctx* ctx, const uint8_t* src_dev, size_t src_stride, int w, int h, int cn, const float* mapx_dev,
+                     const float* mapy_dev, int map_w, int map_h, int interp, int border_mode, const uint8_t* border_value, uint8_t* dst_dev);
+int vp_remap_u8(vp_ctx* ctx, const uint8_t* src_host, int w, int h, int cn, const float* mapx_host, const float* mapy_host, int map_w,
+                int map_h, int interp, int border_mode, const uint8_t* border_value, uint8_t* dst_host);
+int vp_warp_perspective_u8(vp_ctx* ctx, const uint8_t* src_host, int w, int h, int cn, const double* m33, int flags, int border_mode,
+                           const uint8_t* border_value, uint8_t* dst_host, int dst_w, int dst_h);
+int vp_warp_perspective_dev(vp_ctx* ctx, const uint8_t* src_dev, size_t src_stride, int w, int h, int cn, const double* m33, int flags,
+                            int border_mode, const uint8_t* border_value, uint8_t* dst_dev, int dst_w, int dst_h);
+
 /* ---- histogram equalisation and CLAHE ------------------------------------------------------------------------------------------------ *
  * cv2.equalizeHist and cv2.createCLAHE(clip_limit, (tiles_x, tiles_y)).apply on 8-bit single-channel images, byte for byte (DESIGN.md
  * section 4 has the arithmetic: integer histograms, one float32 multiply per table entry, and for CLAHE a float32 bilinear blend of
