@@ -7,6 +7,8 @@
 #include "vp_deriv_plan.h"
 #include "vp_clahe_plan.h"
 #include "vp_remap_plan.h"
+#include "vp_box_plan.h"
+#include <mutex>
 
 extern "C" {
 
@@ -423,6 +425,163 @@ int vp_convert_scale_abs_dev(vp_ctx* ctx, const void* d_src, int depth, size_t n
     if (((uintptr_t)d_src & (esize - 1)) || dev_overlap(d_src, n * esize, d_dst, n))
         return vp_fail(ctx, VP_ERR_INVALID, "vp_convert_scale_abs_dev: src is not aligned to its element, or dst overlaps src");
     return vpk_convert_scale_abs(ctx, d_src, depth, n, d_dst);
+}
+
+// cv2.boxFilter / blur, pyrDown, pyrUp, integral (vp_box_plan.h holds the checks).  An area's admission is enumerated once and kept.
+int vp_box_area_exact(int area)
+{
+    static std::mutex mu;
+    static std::vector<signed char> known;                   // 0: not asked yet, 1: refused, 2: admitted
+    if (area < 1 || area > BX_MAXK * BX_MAXK) return -1;
+    {
+        std::lock_guard<std::mutex> g(mu);
+        if (known.empty()) known.assign((size_t)BX_MAXK * BX_MAXK + 1, 0);
+        if (known[area]) return known[area] - 1;
+    }
+    const int r = vp_box_area_admit(area);
+    std::lock_guard<std::mutex> g(mu);
+    known[area] = (signed char)(r + 1);
+    return r;
+}
+
+static int box_args(vp_ctx* ctx, const char* who, const void* src, const void* dst, int w, int h, int cn, int kw, int kh, int normalize, int ddepth, int border,
+                    vp_box_plan* P)
+{
+    if (!src || !dst) return vp_fail(ctx, VP_ERR_INVALID, who);
+    *P = vp_box_make_plan(w, h, cn, kw, kh, normalize != 0, ddepth, border);
+    if (!P->ok) return vp_fail(ctx, VP_ERR_INVALID, who);
+    if (normalize) {
+        if (vp_box_area_exact(kw * kh) != 1)
+            return vp_fail(ctx, VP_ERR_INVALID, "box filter: OpenCV's roundings of sum / area disagree for this window area, it cannot be restated");
+        P->div = vp_box_make_div(kw * kh);
+    }
+    return VP_OK;
+}
+
+// what the device forms of this family add: the stride, the destination's alignment to its element, and no overlap
+static int box_dev_args(vp_ctx* ctx, const char* who, const void* d_src, size_t src_stride, size_t rowbytes, int h, const void* d_dst, size_t dbytes, size_t esize)
+{
+    if (src_stride < rowbytes || ((uintptr_t)d_dst & (esize - 1)) || dev_overlap(d_src, strided_bytes(src_stride, rowbytes, h), d_dst, dbytes))
+        return vp_fail(ctx, VP_ERR_INVALID, who);
+    return VP_OK;
+}
+
+int vp_box_filter_u8(vp_ctx* ctx, const uint8_t* src, int w, int h, int cn, int kw, int kh, int normalize, int ddepth, int border, void* dst)
+{
+    VP_TRY(check_ctx(ctx));
+    vp_box_plan P;
+    VP_TRY(box_args(ctx, "vp_box_filter_u8 arguments", src, dst, w, h, cn, kw, kh, normalize, ddepth, border, &P));
+    const size_t rowbytes = (size_t)w * cn, nbytes = rowbytes * h, obytes = nbytes * P.esize, mbytes = vp_box_ws_bytes(w, h, cn, P);
+    VP_TRY(vp_ws_reserve(ctx, vp_align(nbytes) + vp_align(obytes) + vp_align(mbytes) + 1024));
+    TAKE(d_src, uint8_t*, nbytes);
+    TAKE(d_dst, uint8_t*, obytes);
+    uint16_t* d_mid = nullptr;
+    if (mbytes) {
+        d_mid = (uint16_t*)vp_ws_take(ctx, mbytes);
+        if (!d_mid) return vp_fail(ctx, VP_ERR_NOMEM, "workspace exhausted: d_mid");
+    }
+    VP_TRY(h2d(ctx, d_src, src, nbytes));
+    VP_TRY(vpk_box_filter(ctx, d_src, rowbytes, w, h, cn, P, d_mid, d_dst));
+    VP_TRY(d2h(ctx, dst, d_dst, obytes));
+    return vp_synchronize(ctx);
+}
+
+int vp_box_filter_dev(vp_ctx* ctx, const uint8_t* d_src, size_t src_stride, int w, int h, int cn, int kw, int kh, int normalize, int ddepth, int border, void* d_dst)
+{
+    VP_TRY(check_ctx(ctx));
+    vp_box_plan P;
+    VP_TRY(box_args(ctx, "vp_box_filter_dev arguments", d_src, d_dst, w, h, cn, kw, kh, normalize, ddepth, border, &P));
+    const size_t rowbytes = (size_t)w * cn, mbytes = vp_box_ws_bytes(w, h, cn, P);
+    VP_TRY(box_dev_args(ctx, "vp_box_filter_dev: src_stride, dst is not aligned to its element, or dst overlaps src", d_src, src_stride, rowbytes, h, d_dst,
+                        rowbytes * h * P.esize, P.esize));
+    uint16_t* d_mid = nullptr;
+    if (mbytes) {
+        VP_TRY(vp_ws_reserve(ctx, vp_align(mbytes) + 1024));
+        d_mid = (uint16_t*)vp_ws_take(ctx, mbytes);
+        if (!d_mid) return vp_fail(ctx, VP_ERR_NOMEM, "workspace exhausted: d_mid");
+    }
+    return vpk_box_filter(ctx, d_src, src_stride, w, h, cn, P, d_mid, d_dst);
+}
+
+static int pyr_args(vp_ctx* ctx, const char* who, const void* src, const void* dst, int w, int h, int cn, int border, bool down)
+{
+    if (!src || !dst || !vp_pyr_sizes_ok(w, h, cn) || (down && !vp_pyr_down_border_ok(border))) return vp_fail(ctx, VP_ERR_INVALID, who);
+    return VP_OK;
+}
+
+int vp_pyr_down_u8(vp_ctx* ctx, const uint8_t* src, int w, int h, int cn, int border, uint8_t* dst)
+{
+    VP_TRY(check_ctx(ctx));
+    VP_TRY(pyr_args(ctx, "vp_pyr_down_u8 arguments", src, dst, w, h, cn, border, true));
+    const size_t nbytes = (size_t)w * cn * h, obytes = (size_t)((w + 1) / 2) * cn * ((h + 1) / 2);
+    VP_TRY(vp_ws_reserve(ctx, vp_align(nbytes) + vp_align(obytes) + 1024));
+    TAKE(d_src, uint8_t*, nbytes);
+    TAKE(d_dst, uint8_t*, obytes);
+    VP_TRY(h2d(ctx, d_src, src, nbytes));
+    VP_TRY(vpk_pyr_down(ctx, d_src, (size_t)w * cn, w, h, cn, border & ~VP_BORDER_ISOLATED, d_dst));
+    VP_TRY(d2h(ctx, dst, d_dst, obytes));
+    return vp_synchronize(ctx);
+}
+
+int vp_pyr_down_dev(vp_ctx* ctx, const uint8_t* d_src, size_t src_stride, int w, int h, int cn, int border, uint8_t* d_dst)
+{
+    VP_TRY(check_ctx(ctx));
+    VP_TRY(pyr_args(ctx, "vp_pyr_down_dev arguments", d_src, d_dst, w, h, cn, border, true));
+    VP_TRY(box_dev_args(ctx, "vp_pyr_down_dev: src_stride, or dst overlaps src", d_src, src_stride, (size_t)w * cn, h, d_dst,
+                        (size_t)((w + 1) / 2) * cn * ((h + 1) / 2), 1));
+    return vpk_pyr_down(ctx, d_src, src_stride, w, h, cn, border & ~VP_BORDER_ISOLATED, d_dst);
+}
+
+int vp_pyr_up_u8(vp_ctx* ctx, const uint8_t* src, int w, int h, int cn, uint8_t* dst)
+{
+    VP_TRY(check_ctx(ctx));
+    VP_TRY(pyr_args(ctx, "vp_pyr_up_u8 arguments", src, dst, w, h, cn, 0, false));
+    const size_t nbytes = (size_t)w * cn * h, obytes = 4 * nbytes;
+    VP_TRY(vp_ws_reserve(ctx, vp_align(nbytes) + vp_align(obytes) + 1024));
+    TAKE(d_src, uint8_t*, nbytes);
+    TAKE(d_dst, uint8_t*, obytes);
+    VP_TRY(h2d(ctx, d_src, src, nbytes));
+    VP_TRY(vpk_pyr_up(ctx, d_src, (size_t)w * cn, w, h, cn, d_dst));
+    VP_TRY(d2h(ctx, dst, d_dst, obytes));
+    return vp_synchronize(ctx);
+}
+
+int vp_pyr_up_dev(vp_ctx* ctx, const uint8_t* d_src, size_t src_stride, int w, int h, int cn, uint8_t* d_dst)
+{
+    VP_TRY(check_ctx(ctx));
+    VP_TRY(pyr_args(ctx, "vp_pyr_up_dev arguments", d_src, d_dst, w, h, cn, 0, false));
+    VP_TRY(box_dev_args(ctx, "vp_pyr_up_dev: src_stride, or dst overlaps src", d_src, src_stride, (size_t)w * cn, h, d_dst, (size_t)4 * w * cn * h, 1));
+    return vpk_pyr_up(ctx, d_src, src_stride, w, h, cn, d_dst);
+}
+
+static int integral_args(vp_ctx* ctx, const char* who, const void* src, const void* dst, int w, int h, int cn)
+{
+    if (!src || !dst || cn < 1 || cn > 4 || w <= 0 || h <= 0) return vp_fail(ctx, VP_ERR_INVALID, who);
+    if (!vp_integral_sizes_ok(w, h, cn)) return vp_fail(ctx, VP_ERR_INVALID, "integral: 255 * w * h does not fit the int32 sums");
+    return VP_OK;
+}
+
+int vp_integral_u8(vp_ctx* ctx, const uint8_t* src, int w, int h, int cn, int32_t* dst)
+{
+    VP_TRY(check_ctx(ctx));
+    VP_TRY(integral_args(ctx, "vp_integral_u8 arguments", src, dst, w, h, cn));
+    const size_t nbytes = (size_t)w * cn * h, obytes = (size_t)(w + 1) * cn * (h + 1) * 4;
+    VP_TRY(vp_ws_reserve(ctx, vp_align(nbytes) + vp_align(obytes) + 1024));
+    TAKE(d_src, uint8_t*, nbytes);
+    TAKE(d_dst, int32_t*, obytes);
+    VP_TRY(h2d(ctx, d_src, src, nbytes));
+    VP_TRY(vpk_integral(ctx, d_src, (size_t)w * cn, w, h, cn, d_dst));
+    VP_TRY(d2h(ctx, dst, d_dst, obytes));
+    return vp_synchronize(ctx);
+}
+
+int vp_integral_dev(vp_ctx* ctx, const uint8_t* d_src, size_t src_stride, int w, int h, int cn, int32_t* d_dst)
+{
+    VP_TRY(check_ctx(ctx));
+    VP_TRY(integral_args(ctx, "vp_integral_dev arguments", d_src, d_dst, w, h, cn));
+    VP_TRY(box_dev_args(ctx, "vp_integral_dev: src_stride, dst is not aligned to int32, or dst overlaps src", d_src, src_stride, (size_t)w * cn, h, d_dst,
+                        (size_t)(w + 1) * cn * (h + 1) * 4, 4));
+    return vpk_integral(ctx, d_src, src_stride, w, h, cn, d_dst);
 }
 
 static int resize_args(vp_ctx* ctx, const char* who, const void* src, const void* dst, int w, int h, int cn, int dw, int dh, double inv_sx, double inv_sy)

@@ -222,6 +222,16 @@ int vpk_median_blur(vp_ctx* ctx, const uint8_t* d_src, size_t sstride, int w, in
 // P.esize bytes per element; d_dst2: spatialGradient's dy plane (d_dst is dx)
 struct vp_deriv_plan;
 int vpk_deriv(vp_ctx* ctx, const uint8_t* d_src, size_t sstride, int w, int h, int cn, const vp_deriv_plan& P, void* d_dst, void* d_dst2);
+
+// ---- box filter, pyramid steps, integral (vp_box.hip, vp_pyr.hip, vp_integral.hip; the plan: vp_box_plan.h) ---------------------------
+// Arguments as the plan header's checks accepted them; sstride: bytes between source rows; destinations packed.  d_mid: vp_box_ws_bytes
+// of workspace for the two-pass box path (0 for the one-pass path).
+struct vp_box_plan;
+size_t vp_box_ws_bytes(int w, int h, int cn, const vp_box_plan& P);
+int vpk_box_filter(vp_ctx* ctx, const uint8_t* d_src, size_t sstride, int w, int h, int cn, const vp_box_plan& P, uint16_t* d_mid, void* d_dst);
+int vpk_pyr_down(vp_ctx* ctx, const uint8_t* d_src, size_t sstride, int w, int h, int cn, int border, uint8_t* d_dst);
+int vpk_pyr_up(vp_ctx* ctx, const uint8_t* d_src, size_t sstride, int w, int h, int cn, uint8_t* d_dst);
+int vpk_integral(vp_ctx* ctx, const uint8_t* d_src, size_t sstride, int w, int h, int cn, int32_t* d_dst);
 // cv2.convertScaleAbs, alpha 1, beta 0 (vp_elementwise.hip): n elements of depth VP_DEPTH_* to saturate_cast<uchar>(|v|)
 int vpk_convert_scale_abs(vp_ctx* ctx, const void* d_src, int depth, size_t n, uint8_t* d_dst);
 

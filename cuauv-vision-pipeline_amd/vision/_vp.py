@@ -49,6 +49,7 @@ BITWISE_AND, BITWISE_OR, BITWISE_XOR, BITWISE_NOT = 0, 1, 2, 3
 ARITH_ADD, ARITH_SUB, ARITH_ABSDIFF = 0, 1, 2
 DERIV_SOBEL, DERIV_SCHARR, DERIV_LAPLACIAN = 0, 1, 2
 DEPTH_8U, DEPTH_16S, DEPTH_32F, DEPTH_64F = 0, 3, 5, 6
+DEPTH_32S = 4
 BORDER_CONSTANT, BORDER_REPLICATE, BORDER_REFLECT, BORDER_REFLECT_101, BORDER_ISOLATED = 0, 1, 2, 4, 16
 INTER_NEAREST, INTER_LINEAR = 0, 1
 WARP_INVERSE_MAP = 16
@@ -243,6 +244,15 @@ _SIGS = {
     "vp_warp_perspective_u8": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_int]),
     "vp_warp_perspective_dev": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p,
                                           C.c_int, C.c_int]),
+    "vp_box_area_exact": (C.c_int, [C.c_int]),
+    "vp_box_filter_u8": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p]),
+    "vp_box_filter_dev": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p]),
+    "vp_pyr_down_u8": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p]),
+    "vp_pyr_down_dev": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p]),
+    "vp_pyr_up_u8": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p]),
+    "vp_pyr_up_dev": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_int, C.c_int, C.c_int, C.c_void_p]),
+    "vp_integral_u8": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p]),
+    "vp_integral_dev": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_int, C.c_int, C.c_int, C.c_void_p]),
 }
 
 

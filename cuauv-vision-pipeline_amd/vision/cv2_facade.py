@@ -867,6 +867,106 @@ def convertScaleAbs(src, dst=None, alpha=1, beta=0):
         raise error(f"convertScaleAbs: {e}") from None
 
 
+# ---- box filter, pyramid steps, integral image (libvp vp_box.hip, vp_pyr.hip, vp_integral.hip) ------------------------------------------
+def _box_source(name, src):
+    src, _ = _device_source(src)
+    if src.dtype != np.uint8:
+        raise error(f"{name}: only uint8 sources are on the accelerated path")
+    if src.ndim not in (2, 3) or src.size == 0:
+        raise error(f"{name}: expected a non-empty (h, w) or (h, w, c) image")
+    if src.ndim == 3 and src.shape[2] > 4:
+        raise error(f"{name}: at most 4 channels")
+    return src
+
+
+def _ksize(name, ksize, anchor):
+    try:
+        kw, kh = (int(v) for v in ksize)
+    except (TypeError, ValueError):
+        raise error(f"{name}: ksize must be a pair of integers") from None
+    if kw < 1 or kh < 1:
+        raise error(f"{name}: ksize must be positive")
+    a = (-1, -1) if anchor is None else tuple(int(v) for v in anchor)
+    if a not in ((-1, -1), (kw // 2, kh // 2)):
+        raise error(f"{name}: only the default anchor (the window's centre) is on the accelerated path")
+    return kw, kh
+
+
+def boxFilter(src, ddepth, ksize, dst=None, anchor=(-1, -1), normalize=True, borderType=BORDER_DEFAULT):
+    """cv2.boxFilter on uint8 images, on the GPU, pure integer arithmetic: unnormalised sums cast to ddepth (-1 / CV_8U, CV_16S, CV_32S,
+    CV_32F, CV_64F); normalised, CV_8U only and only window areas on which OpenCV's own roundings agree.
+    Positional order as in cv2.  A DeviceMat stays in HBM."""
+    src = _box_source("boxFilter", src)
+    kw, kh = _ksize("boxFilter", ksize, anchor)
+    try:
+        return _into(dst, _transform.box_filter(src, kw, kh, ddepth, normalize, BORDER_DEFAULT if borderType is None else borderType))
+    except (TypeError, ValueError) as e:
+        raise error(f"boxFilter: {e}") from None
+
+
+def blur(src, ksize, dst=None, anchor=(-1, -1), borderType=BORDER_DEFAULT):
+    """cv2.blur: the normalised box filter (see boxFilter)."""
+    src = _box_source("blur", src)
+    kw, kh = _ksize("blur", ksize, anchor)
+    try:
+        return _into(dst, _transform.box_filter(src, kw, kh, -1, True, BORDER_DEFAULT if borderType is None else borderType))
+    except (TypeError, ValueError) as e:
+        raise error(f"blur: {e}") from None
+
+
+def _default_dstsize(name, dstsize, want):
+    if dstsize is not None and tuple(int(v) for v in dstsize) not in ((0, 0), want):
+        raise error(f"{name}: only the default dstsize {want} is on the accelerated path")
+
+
+def pyrDown(src, dst=None, dstsize=None, borderType=BORDER_DEFAULT):
+    """cv2.pyrDown on uint8 images, on the GPU: ((w + 1) // 2, (h + 1) // 2); BORDER_DEFAULT, BORDER_REPLICATE or BORDER_REFLECT."""
+    src = _box_source("pyrDown", src)
+    _default_dstsize("pyrDown", dstsize, ((src.shape[1] + 1) // 2, (src.shape[0] + 1) // 2))
+    try:
+        return _into(dst, _transform.pyr_down(src, BORDER_DEFAULT if borderType is None else borderType))
+    except (TypeError, ValueError) as e:
+        raise error(f"pyrDown: {e}") from None
+
+
+def pyrUp(src, dst=None, dstsize=None, borderType=BORDER_DEFAULT):
+    """cv2.pyrUp on uint8 images, on the GPU: (2w, 2h); BORDER_DEFAULT only, as cv2."""
+    src = _box_source("pyrUp", src)
+    _default_dstsize("pyrUp", dstsize, (2 * src.shape[1], 2 * src.shape[0]))
+    try:
+        return _into(dst, _transform.pyr_up(src, BORDER_DEFAULT if borderType is None else borderType))
+    except (TypeError, ValueError) as e:
+        raise error(f"pyrUp: {e}") from None
+
+
+def buildPyramid(src, maxlevel):
+    """cv2.buildPyramid: the list [src, pyrDown(src), ...] of maxlevel + 1 images; a DeviceMat's levels never visit the host."""
+    src = _box_source("buildPyramid", src)
+    try:
+        return _transform.build_pyramid(src, maxlevel)
+    except (TypeError, ValueError) as e:
+        raise error(f"buildPyramid: {e}") from None
+
+
+def integral(src, sum=None, sdepth=-1):
+    """cv2.integral on uint8 images, on the GPU: (h + 1, w + 1[, cn]) int32; sdepth -1 or CV_32S."""
+    if sdepth not in (-1, CV_32S):
+        raise error("integral: only sdepth -1 / CV_32S is on the accelerated path")
+    src = _box_source("integral", src)
+    try:
+        return _into(sum, _transform.integral(src))
+    except (TypeError, ValueError) as e:
+        raise error(f"integral: {e}") from None
+
+
+def integral2(*args, **kwargs):
+    raise error("integral2: the squared sums are outside the accelerated path (DESIGN.md section 7)")
+
+
+def integral3(*args, **kwargs):
+    raise error("integral3: the squared and tilted sums are outside the accelerated path (DESIGN.md section 7)")
+
+
 INTER_LINEAR = 1
 WARP_INVERSE_MAP = 16
 

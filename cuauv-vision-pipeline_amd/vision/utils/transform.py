@@ -271,6 +271,132 @@ def convert_scale_abs(mat: np.ndarray) -> np.ndarray:
     return out
 
 
+_BOX_DTYPE = {_vp.DEPTH_8U: np.uint8, _vp.DEPTH_16S: np.int16, _vp.DEPTH_32S: np.int32, _vp.DEPTH_32F: np.float32, _vp.DEPTH_64F: np.float64}
+BOX_MAX_SIDE = 255
+
+
+def box_filter(mat: np.ndarray, kx: int, ky: Optional[int] = None, ddepth: int = -1, normalize: bool = True, border: int = _vp.BORDER_REFLECT_101):
+    """cv2.boxFilter on uint8 images of 1..4 channels (libvp vp_box_filter_u8 / vp_box_filter_dev): the sum over the ky x kx window
+    anchored at (kx // 2, ky // 2).  Unnormalised it is cast to ddepth (-1 / CV_8U and CV_16S saturate; CV_32S, CV_32F, CV_64F); normalised
+    (uint8 only) it is sum / area rounded as OpenCV rounds, for the areas on which OpenCV's own roundings agree - the others raise
+    ValueError before anything is launched.  numpy in gives numpy out; a DeviceMat gives a DeviceMat of the result's dtype, without
+    the source's mask flag and bit plane: the result is no mask."""
+    mat, cn = _deriv_source(mat)
+    kx = int(kx)
+    ky = kx if ky is None else int(ky)
+    ddepth, border, normalize = int(ddepth), int(border) & ~_vp.BORDER_ISOLATED, bool(normalize)
+    depth = _vp.DEPTH_8U if ddepth == -1 else ddepth
+    if not (1 <= kx <= BOX_MAX_SIDE and 1 <= ky <= BOX_MAX_SIDE):
+        raise ValueError("the window sides must be in 1..255")
+    if depth not in _BOX_DTYPE:
+        raise ValueError("ddepth must be -1, CV_8U, CV_16S, CV_32S, CV_32F or CV_64F")
+    if border not in _BORDERS:
+        raise ValueError("the border must be BORDER_REFLECT_101, BORDER_REPLICATE, BORDER_REFLECT or BORDER_CONSTANT")
+    if normalize:
+        if depth != _vp.DEPTH_8U:
+            raise ValueError("a normalised box filter gives CV_8U only: OpenCV's float scaling of the other depths is not restated")
+        if _vp.lib().vp_box_area_exact(kx * ky) != 1:
+            raise ValueError("OpenCV's roundings of sum / area disagree for a window of %d pixels: it cannot be restated" % (kx * ky))
+    elif depth == _vp.DEPTH_32F and 255 * kx * ky >= 1 << 24:
+        raise ValueError("the window's sum may not be exact in float32: ask for CV_32S or CV_64F")
+    ctx = _vp.default_context()
+    h, w = mat.shape[:2]
+    dtype = _BOX_DTYPE[depth]
+    if isinstance(mat, DeviceMat):
+        mat.refresh_device(ctx)
+        out = DeviceMat(ctx, mat.shape, dtype)
+        _vp.check(_vp.lib().vp_box_filter_dev(ctx.handle, mat.dev_ptr, w * cn, w, h, cn, kx, ky, int(normalize), depth, border, out.dev_ptr), ctx.handle)
+        return out
+    src = np.ascontiguousarray(mat)
+    out = np.empty(src.shape, dtype)
+    _vp.check(_vp.lib().vp_box_filter_u8(ctx.handle, _vp.ptr(src), w, h, cn, kx, ky, int(normalize), depth, border, _vp.ptr(out)), ctx.handle)
+    return out
+
+
+def box_blur(mat: np.ndarray, kx: int, ky: Optional[int] = None) -> np.ndarray:
+    """cv2.blur(mat, (kx, ky)): the normalised box filter with the default border."""
+    return box_filter(mat, kx, ky)
+
+
+def _pyr(mat, down, border):
+    mat, cn = _deriv_source(mat)
+    border = int(border) & ~_vp.BORDER_ISOLATED
+    if down and border not in (_vp.BORDER_REFLECT_101, _vp.BORDER_REPLICATE, _vp.BORDER_REFLECT):
+        raise ValueError("pyrDown takes BORDER_REFLECT_101, BORDER_REPLICATE or BORDER_REFLECT")
+    if not down and border != _vp.BORDER_REFLECT_101:
+        raise ValueError("pyrUp takes BORDER_DEFAULT only")
+    h, w = mat.shape[:2]
+    if h > 32767:
+        raise ValueError("at most 32767 rows")
+    oh, ow = ((h + 1) // 2, (w + 1) // 2) if down else (2 * h, 2 * w)
+    shape = (oh, ow) + tuple(mat.shape[2:])
+    ctx = _vp.default_context()
+    L = _vp.lib()
+    if isinstance(mat, DeviceMat):
+        mat.refresh_device(ctx)
+        out = DeviceMat(ctx, shape)
+        rc = (L.vp_pyr_down_dev(ctx.handle, mat.dev_ptr, w * cn, w, h, cn, border, out.dev_ptr) if down
+              else L.vp_pyr_up_dev(ctx.handle, mat.dev_ptr, w * cn, w, h, cn, out.dev_ptr))
+        _vp.check(rc, ctx.handle)
+        return out
+    src = np.ascontiguousarray(mat)
+    out = np.empty(shape, np.uint8)
+    rc = (L.vp_pyr_down_u8(ctx.handle, _vp.ptr(src), w, h, cn, border, _vp.ptr(out)) if down
+          else L.vp_pyr_up_u8(ctx.handle, _vp.ptr(src), w, h, cn, _vp.ptr(out)))
+    _vp.check(rc, ctx.handle)
+    return out
+
+
+def pyr_down(mat: np.ndarray, border: int = _vp.BORDER_REFLECT_101) -> np.ndarray:
+    """cv2.pyrDown on uint8 images of 1..4 channels: ((w + 1) // 2, (h + 1) // 2), the 5 x 5 binomial kernel at every second pixel
+    (libvp vp_pyr_down_*).  numpy in gives numpy out; a DeviceMat gives a DeviceMat and stays in HBM."""
+    return _pyr(mat, True, border)
+
+
+def pyr_up(mat: np.ndarray, border: int = _vp.BORDER_REFLECT_101) -> np.ndarray:
+    """cv2.pyrUp on uint8 images of 1..4 channels: (2w, 2h), OpenCV's polyphase form of the same kernel (libvp vp_pyr_up_*)."""
+    return _pyr(mat, False, border)
+
+
+def build_pyramid(mat: np.ndarray, levels: int) -> list:
+    """cv2.buildPyramid: [mat, pyr_down(mat), ...], levels + 1 images.  The levels of a DeviceMat are DeviceMats made from each other
+    in HBM; a numpy source is uploaded once, the levels are made on the device and each is brought back."""
+    levels = int(levels)
+    if levels < 0:
+        raise ValueError("levels must not be negative")
+    src, _ = _deriv_source(mat)
+    if isinstance(src, DeviceMat):
+        out = [src]
+        for _ in range(levels):
+            out.append(pyr_down(out[-1]))
+        return out
+    ctx = _vp.default_context()
+    dev = [device_image(ctx, np.ascontiguousarray(src), 0)]
+    for _ in range(levels):
+        dev.append(pyr_down(dev[-1]))
+    return [np.ascontiguousarray(src)] + [d.host_copy() for d in dev[1:]]
+
+
+def integral(mat: np.ndarray) -> np.ndarray:
+    """cv2.integral on uint8 images of 1..4 channels: the (h + 1, w + 1[, cn]) int32 image of sums above and left of every pixel
+    (libvp vp_integral_*); 255 * w * h must fit int32.  numpy in gives numpy out; a DeviceMat gives an int32 DeviceMat."""
+    mat, cn = _deriv_source(mat)
+    h, w = mat.shape[:2]
+    if 255 * w * h > 2 ** 31 - 1:
+        raise ValueError("255 * w * h does not fit the int32 sums")
+    shape = (h + 1, w + 1) + tuple(mat.shape[2:])
+    ctx = _vp.default_context()
+    if isinstance(mat, DeviceMat):
+        mat.refresh_device(ctx)
+        out = DeviceMat(ctx, shape, np.int32)
+        _vp.check(_vp.lib().vp_integral_dev(ctx.handle, mat.dev_ptr, w * cn, w, h, cn, out.dev_ptr), ctx.handle)
+        return out
+    src = np.ascontiguousarray(mat)
+    out = np.empty(shape, np.int32)
+    _vp.check(_vp.lib().vp_integral_u8(ctx.handle, _vp.ptr(src), w, h, cn, _vp.ptr(out)), ctx.handle)
+    return out
+
+
 def _border_bytes(value):
     """cv2's borderValue (a Scalar: missing entries are 0) as four saturated bytes"""
     bv = np.zeros(4, np.uint8)

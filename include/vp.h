@@ -637,6 +637,37 @@ int vp_spatial_gradient_dev(vp_ctx* ctx, const uint8_t* src_dev, size_t src_stri
 int vp_convert_scale_abs_u8(vp_ctx* ctx, const void* src_host, int depth, size_t n, uint8_t* dst_host);
 int vp_convert_scale_abs_dev(vp_ctx* ctx, const void* src_dev, int depth, size_t n, uint8_t* dst_dev);
 
+/* ---- box filter, pyramid steps, integral image ----------------------------------------------------------------------------------------- *
+ * cv2.boxFilter / blur, pyrDown, pyrUp and integral on uint8 images of 1..4 interleaved channels, pure integer arithmetic
+ * (tests/box_pyr_restate.py is the statement).  Borders are codes of VP_BORDER_* (the VP_BORDER_ISOLATED bit is ignored), index maps
+ * as cv::borderInterpolate, also for windows larger than the image.  Host forms (_u8) take packed host images, stage, run the kernels
+ * of the device form and synchronise; device forms (_dev) read src_dev in place (row stride in bytes, at least w * cn, no alignment
+ * asked of pointer or stride), write a packed dst_dev aligned to its element size that must not overlap the source, enqueue on the
+ * context's stream and never synchronise.  Anything refused is VP_ERR_INVALID with a message, and nothing is launched or written.
+ * vp_box_filter_*: the sum over the kh x kw window (1..255 each) anchored at (kw / 2, kh / 2), also for even sizes.  border:
+ *   VP_BORDER_REFLECT_101, REPLICATE, REFLECT or CONSTANT (value 0).  normalize == 0: the sum cast to ddepth -1 / VP_DEPTH_8U or
+ *   VP_DEPTH_16S (saturated), VP_DEPTH_32S, VP_DEPTH_32F (only while 255 * kw * kh < 2^24) or VP_DEPTH_64F.  normalize != 0: ddepth -1
+ *   or VP_DEPTH_8U only, and only areas kw * kh that vp_box_area_exact admits; the result is sum / area rounded half to even.  h <= 65535.
+ * vp_box_area_exact: 1 when OpenCV's three roundings of sum / area (the Q23 reciprocal on 16-bit sums for area <= 256, the float32
+ *   and the double product otherwise) give one byte for every sum 0 .. 255 * area, 0 when not, negative for area < 1 or above
+ *   255 * 255.  Host only, no context, no GPU; enumerates once per area and remembers.
+ * vp_pyr_down_*: dst is ((w + 1) / 2) x ((h + 1) / 2); the 5 x 5 kernel [1 4 6 4 1] x [1 4 6 4 1] at every second pixel, (.. + 128) >> 8.
+ *   border: VP_BORDER_REFLECT_101, REPLICATE or REFLECT (cv2 refuses CONSTANT).  h <= 32767.
+ * vp_pyr_up_*: dst is 2w x 2h; cv2's polyphase form of the same kernel times 4, (.. + 32) >> 6, BORDER_DEFAULT only.  h <= 32767.
+ * vp_integral_*: dst is (h + 1) x (w + 1) x cn int32 with a zero first row and column; 255 * w * h must fit int32. */
+enum { VP_DEPTH_32S = 4 };
+int vp_box_area_exact(int area);
+int vp_box_filter_u8(vp_ctx* ctx, const uint8_t* src_host, int w, int h, int cn, int kw, int kh, int normalize, int ddepth, int border,
+                     void* dst_host);
+int vp_box_filter_dev(vp_ctx* ctx, const uint8_t* src_dev, size_t src_stride, int w, int h, int cn, int kw, int kh, int normalize, int ddepth,
+                      int border, void* dst_dev);
+int vp_pyr_down_u8(vp_ctx* ctx, const uint8_t* src_host, int w, int h, int cn, int border, uint8_t* dst_host);
+int vp_pyr_down_dev(vp_ctx* ctx, const uint8_t* src_dev, size_t src_stride, int w, int h, int cn, int border, uint8_t* dst_dev);
+int vp_pyr_up_u8(vp_ctx* ctx, const uint8_t* src_host, int w, int h, int cn, uint8_t* dst_host);
+int vp_pyr_up_dev(vp_ctx* ctx, const uint8_t* src_dev, size_t src_stride, int w, int h, int cn, uint8_t* dst_dev);
+int vp_integral_u8(vp_ctx* ctx, const uint8_t* src_host, int w, int h, int cn, int32_t* dst_host);
+int vp_integral_dev(vp_ctx* ctx, const uint8_t* src_dev, size_t src_stride, int w, int h, int cn, int32_t* dst_dev);
+
 /* ---- element-wise operators on device images ------------------------------------------------------------------------------------ *
  * Packed uint8 device images; every entry enqueues on the context's stream and returns at once, except vp_count_nonzero_u8_dev.
  * Pointers need no alignment (planes of one frame sit at byte offsets inside one allocation): 16-byte accesses are used where the
