@@ -105,6 +105,7 @@ vp_ctx* vp_create(int device)
     if (const char* env = getenv("VP_OPT_CLAHE_SPLIT")) { const int v = atoi(env); if (v >= 1 && v <= 64) ctx->clahe_split = v; }
     for (size_t& v : ctx->c3_lds_set) v = 0;
     if (const char* env = getenv("VP_CCL_LEVELS")) { const int v = atoi(env); if (v == 1 || v == 2) ctx->ccl_levels = v; }
+    if (const char* env = getenv("VP_OPT_CCL_CROWDED")) { const int v = atoi(env); if (v >= 0 && v <= 2) ctx->ccl_crowded_force = v; }
     // tables: gamma u16[256] | cbrt u16[2048] | sdiv i32[256] | hdiv i32[256]
     std::vector<uint16_t> gamma(256), cbrt(3072);
     std::vector<int32_t> sdiv(256), hdiv(256);
@@ -156,6 +157,8 @@ int vp_destroy(vp_ctx* ctx)
     if (ctx->c3_acc) hipFree(ctx->c3_acc);
     if (ctx->hc_hist) hipFree(ctx->hc_hist);
     if (ctx->ct_hint_host) hipHostFree(ctx->ct_hint_host);
+    if (ctx->ccl_hint_host) hipHostFree(ctx->ccl_hint_host);
+    if (ctx->ccl_zero_dev) hipFree(ctx->ccl_zero_dev);
     for (int i = 0; i < 4; i++) {
         if (ctx->ring_buf[i]) hipHostFree(ctx->ring_buf[i]);
         if (ctx->ring_ev[i]) hipEventDestroy(ctx->ring_ev[i]);
@@ -201,7 +204,15 @@ int vp_set_option(vp_ctx* ctx, int option, int value)
     if (option == VP_OPT_BLUR_ONEPASS && value >= -1 && value <= 1) { ctx->blur_onepass = value; return VP_OK; }
     if (option == VP_OPT_MEDIAN_MASK && value >= -1 && value <= 1) { ctx->median_mask = value; return VP_OK; }
     if (option == VP_OPT_CLAHE_SPLIT && value >= 0 && value <= 64) { ctx->clahe_split = value; return VP_OK; }
+    if (option == VP_OPT_CCL_CROWDED && value >= 0 && value <= 2) { ctx->ccl_crowded_force = value; return VP_OK; }
     return vp_fail(ctx, VP_ERR_INVALID, "vp_set_option");
+}
+
+int vp_ccl_last_launches(vp_ctx* ctx, int32_t* launches)
+{
+    if (!ctx || !launches) return VP_ERR_INVALID;
+    *launches = ctx->ccl_launches;
+    return VP_OK;
 }
 
 int vp_synchronize(vp_ctx* ctx)

@@ -414,7 +414,12 @@ static int chain_core(vp_ctx* ctx, const vp_chain_desc* d, const vp_chain_buffer
         if (ej != hipSuccess) { (void)hipStreamSynchronize(ctx->fb_stream); joined = true; if (rc_ct == VP_OK) rc_ct = vp_fail(ctx, VP_ERR_HIP, "hipEventRecord", ej); }
     }
     int rc_ccl = VP_OK;
+    // (with the contour pass beside it the labelling keeps its six crowded-frame launches, vp_ccl_hint.h: without them the label write
+    // starts ~15 us earlier and saturates memory under the latency-bound contour kernels, the longer of the two branches, for longer -
+    // chain + contours 0.648 -> 0.658 ms per step of 128 frames, EXPERIMENTS.md)
+    ctx->ccl_beside = joined ? 0 : 1;
     if (d->ccl) rc_ccl = vpk_ccl(ctx, ccl_bits, w, h, n, d->numbering, ws, b->labels, b->stats, b->centroids, d->max_labels, b->nlabels ? b->nlabels : d_nl);
+    ctx->ccl_beside = 0;
     if (!joined && hipStreamWaitEvent(s_main, ctx->ev_fb_join, 0) != hipSuccess) { (void)hipGetLastError(); (void)hipStreamSynchronize(ctx->fb_stream); }
     if (rc_ccl != VP_OK) return rc_ccl;
     if (rc_ct != VP_OK) return rc_ct;

@@ -32,6 +32,7 @@
 // accumulators; label write of one half of the batch under the bookkeeping of the other.
 #include "vp_internal.h"
 #include "vp_ccl_dev.h"
+#include "vp_ccl_hint.h"
 #include <limits.h>
 #include <cstdio>
 #include <string.h>
@@ -116,16 +117,18 @@ bool vp_ccl_ws_ok(const vp_ccl_ws& ws)
 }
 
 // ---- whole-image global-memory path (fallback for images too wide for the LDS strip kernel) ---------------
+// The bodies of the one-level kernels are device functions of (block index, frame): the kernels below call them with their own
+// blockIdx, k_ccl2_finish (vp_ccl2.inl) walks the block indices of one frame in a single block.
 // grid: (ceil(h*ww/256), n); flags zeroed by a memset before k_ccl_init
-__global__ __launch_bounds__(256) void k_ccl_init(const u64* __restrict__ bits, ccl_geom G, u32* __restrict__ parent, u32* __restrict__ flags)
+__device__ __forceinline__ void ccl_init_body(const u64* __restrict__ bits, const ccl_geom& G, u32* parent, u32* flags, int vbx, int frame)
 {
-    const int idx = blockIdx.x * 256 + threadIdx.x;
+    const int idx = vbx * 256 + threadIdx.x;
     if (idx >= G.h * G.ww) return;
     const int y = idx / G.ww, j = idx - y * G.ww;
-    const u64 w = ccl_word(G, bits + (size_t)blockIdx.y * G.h * G.ww, idx, j);
+    const u64 w = ccl_word(G, bits + (size_t)frame * G.h * G.ww, idx, j);
     if (!w) return;
-    u32* p = parent + (size_t)blockIdx.y * G.nids;
-    u32* f = flags + (size_t)blockIdx.y * G.nw32;
+    u32* p = parent + (size_t)frame * G.nids;
+    u32* f = flags + (size_t)frame * G.nw32;
     u64 starts = w & ~(w << 1);
     while (starts) {
         const int s = __ffsll((long long)starts) - 1;
@@ -135,16 +138,24 @@ __global__ __launch_bounds__(256) void k_ccl_init(const u64* __restrict__ bits, 
         atomicOr(f + (id >> 5), 1u << (id & 31));
     }
 }
-
-__global__ __launch_bounds__(256) void k_ccl_link(const u64* __restrict__ bits, ccl_geom G, u32* __restrict__ parent, u32* __restrict__ flags)
+__global__ __launch_bounds__(256) void k_ccl_init(const u64* __restrict__ bits, ccl_geom G, u32* __restrict__ parent, u32* __restrict__ flags)
 {
-    const int idx = blockIdx.x * 256 + threadIdx.x;
+    ccl_init_body(bits, G, parent, flags, (int)blockIdx.x, (int)blockIdx.y);
+}
+
+__device__ __forceinline__ void ccl_link_body(const u64* __restrict__ bits, const ccl_geom& G, u32* parent, u32* flags, int vbx, int frame)
+{
+    const int idx = vbx * 256 + threadIdx.x;
     if (idx >= G.h * G.ww) return;
-    const u64* fb = bits + (size_t)blockIdx.y * G.h * G.ww;
+    const u64* fb = bits + (size_t)frame * G.h * G.ww;
     const int y = idx / G.ww, j = idx - y * G.ww;
     const u64 w = ccl_word(G, fb, idx, j);
     if (!w) return;
-    global_link_word(fb, G, parent + (size_t)blockIdx.y * G.nids, flags + (size_t)blockIdx.y * G.nw32, y, j, idx, w, true, true);
+    global_link_word(fb, G, parent + (size_t)frame * G.nids, flags + (size_t)frame * G.nw32, y, j, idx, w, true, true);
+}
+__global__ __launch_bounds__(256) void k_ccl_link(const u64* __restrict__ bits, ccl_geom G, u32* __restrict__ parent, u32* __restrict__ flags)
+{
+    ccl_link_body(bits, G, parent, flags, (int)blockIdx.x, (int)blockIdx.y);
 }
 
 // One block per (frame, strip of CL_ROWS rows).
@@ -225,19 +236,18 @@ __device__ __forceinline__ void wave_combine(contrib& c)
 //   of parts < p (the bitmap is 130 KB per 1080p frame, L2-resident), then scans its own slice; the last part also
 //   publishes nlabels and zeroes the accumulators.
 // blocks [RK_PARTS, RK_PARTS + BG_PARTS): background pixels of a slice of the frame reduced to one record.
-__global__ __launch_bounds__(256) void k_ccl_rank(ccl_geom G, const u32* __restrict__ flags, u32* __restrict__ prefix,
-                                                  int32_t* __restrict__ nlabels, ccl_acc* __restrict__ acc, int max_labels,
-                                                  const u64* __restrict__ bits, contrib* __restrict__ bgpart, const u32* __restrict__ only)
+__device__ __forceinline__ void ccl_rank_body(const ccl_geom& G, const u32* __restrict__ flags, u32* __restrict__ prefix,
+                                              int32_t* __restrict__ nlabels, ccl_acc* __restrict__ acc, int max_labels,
+                                              const u64* __restrict__ bits, contrib* __restrict__ bgpart, int vbx, int frame)
 {
-    if (only && !only[blockIdx.y]) return;
     __shared__ u32 wsum[4];
     __shared__ u32 wsum2[4];
     __shared__ u32 bcast;
     __shared__ contrib part[4];
-    const int f = blockIdx.y, tid = threadIdx.x;
+    const int f = frame, tid = threadIdx.x;
     const int lane = tid & 63, wv = tid >> 6;
-    if (blockIdx.x >= RK_PARTS) {
-        const int bp = blockIdx.x - RK_PARTS;
+    if (vbx >= RK_PARTS) {
+        const int bp = vbx - RK_PARTS;
         const int rper = (G.h + BG_PARTS - 1) / BG_PARTS;
         const int r0 = bp * rper, r1 = min(r0 + rper, G.h);
         const u64* fb = bits + (size_t)f * G.h * G.ww;
@@ -267,7 +277,7 @@ __global__ __launch_bounds__(256) void k_ccl_rank(ccl_geom G, const u32* __restr
         }
         return;
     }
-    const int partno = blockIdx.x;
+    const int partno = vbx;
     const u32 nq = G.nw32 / 4;                               // uint4 words per frame
     const u32 qper = (nq + RK_PARTS - 1) / RK_PARTS;
     const u32 q0 = min((u32)partno * qper, nq), q1 = min(q0 + qper, nq);
@@ -338,6 +348,13 @@ __global__ __launch_bounds__(256) void k_ccl_rank(ccl_geom G, const u32* __restr
         }
     }
 }
+__global__ __launch_bounds__(256) void k_ccl_rank(ccl_geom G, const u32* __restrict__ flags, u32* __restrict__ prefix,
+                                                  int32_t* __restrict__ nlabels, ccl_acc* __restrict__ acc, int max_labels,
+                                                  const u64* __restrict__ bits, contrib* __restrict__ bgpart, const u32* __restrict__ only)
+{
+    if (only && !only[blockIdx.y]) return;
+    ccl_rank_body(G, flags, prefix, nlabels, acc, max_labels, bits, bgpart, (int)blockIdx.x, (int)blockIdx.y);
+}
 
 // ---- per-label statistics ----------------------------------------------------------------------------------
 
@@ -362,16 +379,15 @@ struct st_table {
     int minx[ST_SLOTS], maxx[ST_SLOTS], miny[ST_SLOTS], maxy[ST_SLOTS];
     u64 sx[ST_SLOTS], sy[ST_SLOTS];
 };
-__global__ __launch_bounds__(256) void k_ccl_stats(const u64* __restrict__ bits, ccl_geom G, const u32* __restrict__ parent,
-                                                   const u32* __restrict__ flags, const u32* __restrict__ prefix,
-                                                   u32* __restrict__ seglabel, u32* __restrict__ wordlabel,
-                                                   ccl_acc* __restrict__ acc, int max_labels, const u32* __restrict__ only)
+__device__ __forceinline__ void ccl_stats_body(const u64* __restrict__ bits, const ccl_geom& G, const u32* __restrict__ parent,
+                                               const u32* __restrict__ flags, const u32* __restrict__ prefix,
+                                               u32* __restrict__ seglabel, u32* __restrict__ wordlabel,
+                                               ccl_acc* __restrict__ acc, int max_labels, int vbx, int frame)
 {
-    if (only && !only[blockIdx.y]) return;
     __shared__ st_table T;
-    const int idx = blockIdx.x * 256 + threadIdx.x;
+    const int idx = vbx * 256 + threadIdx.x;
     const bool live = idx < G.h * G.ww;
-    const int f = blockIdx.y;
+    const int f = frame;
     const u64 w = live ? bits[(size_t)f * G.h * G.ww + idx] : 0ull;
     const bool any_fg = __syncthreads_or(w != 0ull);   // block-uniform
     ccl_acc* a = acc + (size_t)f * max_labels;
@@ -481,18 +497,24 @@ __global__ __launch_bounds__(256) void k_ccl_stats(const u64* __restrict__ bits,
         }
     }
 }
-
-// grid: (ceil(max_labels/256), n)
-__global__ __launch_bounds__(256) void k_ccl_final(const ccl_acc* __restrict__ acc, const contrib* __restrict__ bgpart,
-                                                   const int32_t* __restrict__ nlabels, int max_labels, int32_t* __restrict__ stats,
-                                                   double* __restrict__ cent, const u32* __restrict__ only)
+__global__ __launch_bounds__(256) void k_ccl_stats(const u64* __restrict__ bits, ccl_geom G, const u32* __restrict__ parent,
+                                                   const u32* __restrict__ flags, const u32* __restrict__ prefix,
+                                                   u32* __restrict__ seglabel, u32* __restrict__ wordlabel,
+                                                   ccl_acc* __restrict__ acc, int max_labels, const u32* __restrict__ only)
 {
     if (only && !only[blockIdx.y]) return;
-    const int l = blockIdx.x * 256 + threadIdx.x;
+    ccl_stats_body(bits, G, parent, flags, prefix, seglabel, wordlabel, acc, max_labels, (int)blockIdx.x, (int)blockIdx.y);
+}
+
+// grid: (ceil(max_labels/256), n); nl: the frame's label count
+__device__ __forceinline__ void ccl_final_body(const ccl_acc* __restrict__ acc, const contrib* __restrict__ bgpart, int nl, int max_labels,
+                                               int32_t* __restrict__ stats, double* __restrict__ cent, int vbx, int frame)
+{
+    const int l = vbx * 256 + threadIdx.x;
     if (l >= max_labels) return;
-    const int f = blockIdx.y;
+    const int f = frame;
     const size_t o = (size_t)f * max_labels + l;
-    if (l < nlabels[f]) {
+    if (l < nl) {
         ccl_acc a = acc[o];
         if (l == 0) {   // background: merge the per-slice records
             contrib c;
@@ -518,6 +540,13 @@ __global__ __launch_bounds__(256) void k_ccl_final(const ccl_acc* __restrict__ a
         if (cent) { cent[o * 2] = 0.0; cent[o * 2 + 1] = 0.0; }
     }
 }
+__global__ __launch_bounds__(256) void k_ccl_final(const ccl_acc* __restrict__ acc, const contrib* __restrict__ bgpart,
+                                                   const int32_t* __restrict__ nlabels, int max_labels, int32_t* __restrict__ stats,
+                                                   double* __restrict__ cent, const u32* __restrict__ only)
+{
+    if (only && !only[blockIdx.y]) return;
+    ccl_final_body(acc, bgpart, nlabels[blockIdx.y], max_labels, stats, cent, (int)blockIdx.x, (int)blockIdx.y);
+}
 
 // ---- label image -------------------------------------------------------------------------------------------
 // One lane = 4 px = one 16-B store.  A block streams WR_ROWS consecutive rows; a thread owns WR_K groups and runs
@@ -527,12 +556,11 @@ __global__ __launch_bounds__(256) void k_ccl_final(const ccl_acc* __restrict__ a
 // launch bound 8 waves per SIMD: the compiler otherwise takes 74 VGPRs (6 waves); at 62 VGPRs and full occupancy the kernel streams at
 // 5.8 instead of 5.2 TB/s (188 instead of 208 us per 128 frames)
 #define WR_K 8
-__global__ __launch_bounds__(256, 8) void k_ccl_write(const u64* __restrict__ bits, ccl_geom G, const u32* __restrict__ seglabel,
-                                                   const u32* __restrict__ wordlabel, int32_t* __restrict__ labels, u32 total_rows,
-                                                   u32 gpr, u32 gpr_magic)
+// rows [row0, row0 + nrows) of the batch's (n * h) rows
+__device__ __forceinline__ void ccl_write_body(const u64* __restrict__ bits, const ccl_geom& G, const u32* __restrict__ seglabel,
+                                               const u32* __restrict__ wordlabel, int32_t* __restrict__ labels, u32 row0, u32 nrows,
+                                               u32 gpr, u32 gpr_magic)
 {
-    const u32 row0 = blockIdx.x * WR_ROWS;
-    const u32 nrows = min((u32)WR_ROWS, total_rows - row0);
     const u32 ngroups = nrows * gpr;
     const bool vec = (G.w & 3) == 0 && ((((uintptr_t)labels) & 15) == 0);
     const u64* brow0 = bits + (size_t)row0 * G.ww;
@@ -602,6 +630,13 @@ __global__ __launch_bounds__(256, 8) void k_ccl_write(const u64* __restrict__ bi
         }
     }
 }
+__global__ __launch_bounds__(256, 8) void k_ccl_write(const u64* __restrict__ bits, ccl_geom G, const u32* __restrict__ seglabel,
+                                                   const u32* __restrict__ wordlabel, int32_t* __restrict__ labels, u32 total_rows,
+                                                   u32 gpr, u32 gpr_magic)
+{
+    const u32 row0 = blockIdx.x * WR_ROWS;
+    ccl_write_body(bits, G, seglabel, wordlabel, labels, row0, min((u32)WR_ROWS, total_rows - row0), gpr, gpr_magic);
+}
 
 #ifdef VP_PROBE
 static __device__ int vp_dbg_bits;   // the VP_DBG switches of this unit's kernels
@@ -631,11 +666,13 @@ static int ccl_roots(vp_ctx* ctx, const u64* d_bits, const ccl_geom& G, int n, u
     size_t cap;
     const size_t lds_local = ccl_local_lds(G, cap, ccl_env_tuning());
     if (lds_local <= 64 * 1024) {
+        ctx->ccl_launches += strips > 1 ? 2 : 1;
         { vp_prof_scope ps(ctx, VPK_CCL_LOCAL); hipLaunchKernelGGL(k_ccl_local, dim3((unsigned)((size_t)n * strips)), dim3(256), lds_local, s, d_bits, G, parent, flags, strips, (int)cap, only, zero_too); }
         if (strips > 1) { vp_prof_scope ps(ctx, VPK_CCL_BOUNDARY); hipLaunchKernelGGL(k_ccl_boundary, dim3((unsigned)(strips - 1), (unsigned)n), dim3(64), 0, s, d_bits, G, parent, flags, only); }
     } else {
         if (zero_too) { vp_prof_scope ps(ctx, VPK_MEMSET); VP_HIP(ctx, hipMemsetAsync(zero_too, 0, (size_t)G.nw32 * 4 * n, s)); }
         { vp_prof_scope ps(ctx, VPK_MEMSET); VP_HIP(ctx, hipMemsetAsync(flags, 0, (size_t)G.nw32 * 4 * n, s)); }
+        ctx->ccl_launches += 2;
         { vp_prof_scope ps(ctx, VPK_CCL_BOUNDARY); hipLaunchKernelGGL(k_ccl_init, wgrid, dim3(256), 0, s, d_bits, G, parent, flags); }
         { vp_prof_scope ps(ctx, VPK_CCL_LOCAL); hipLaunchKernelGGL(k_ccl_link, wgrid, dim3(256), 0, s, d_bits, G, parent, flags); }
     }
@@ -649,6 +686,7 @@ static int ccl_one_level_tail(vp_ctx* ctx, const u64* d_bits, const ccl_geom& G,
 {
     const dim3 wgrid((unsigned)((G.h * G.ww + 255) / 256), (unsigned)n);
     hipStream_t s = ctx->stream;
+    ctx->ccl_launches += (d_stats || d_centroids) ? 3 : 2;
     { vp_prof_scope ps(ctx, VPK_CCL_RANK); hipLaunchKernelGGL(k_ccl_rank, dim3(RK_PARTS + BG_PARTS, (unsigned)n), dim3(256), 0, s, G, ws.flags, ws.prefix, d_nlabels, (ccl_acc*)ws.acc, max_labels, d_bits, (contrib*)ws.bgpart, only); }
     { vp_prof_scope ps(ctx, VPK_CCL_STATS); hipLaunchKernelGGL(k_ccl_stats, wgrid, dim3(256), 0, s, d_bits, G, ws.parent, ws.flags, ws.prefix, ws.seglabel, ws.wordlabel, (ccl_acc*)ws.acc, max_labels, only); }
     if (d_stats || d_centroids) {
@@ -662,8 +700,9 @@ static int ccl_one_level_tail(vp_ctx* ctx, const u64* d_bits, const ccl_geom& G,
 
 // ---- dispatch --------------------------------------------------------------------------------------------------------------
 // vpk_ccl makes the plan (ccl_make_plan, vp_ccl_plan.h) and hands it to one launcher per path: ccl_two_level, which finishes the
-// frames its merge hands over with ccl_crowded or, where the geometry does not suit those kernels, with the one-level kernels
-// (ccl_roots + ccl_one_level_tail); and the one-level path itself.
+// frames its merge hands over with ccl_crowded (or, while none is expected, with the one launch of k_ccl2_finish: vp_ccl_hint.h) or,
+// where the geometry does not suit those kernels, with the one-level kernels (ccl_roots + ccl_one_level_tail); and the one-level
+// path itself.
 
 struct ccl_call {            // the arguments of vpk_ccl that the launchers pass on
     const u64* bits; int n; const vp_ccl_ws& ws; int32_t* labels; int32_t* stats; double* cent; int max_labels; int32_t* nlabels;
@@ -693,6 +732,8 @@ static int c3_acc_acquire(vp_ctx* ctx, size_t need, hipStream_t s, ccl_acc** acc
     return VP_OK;
 }
 
+// (LEAN mode, ccl_two_level, commits straight after acquiring: it launches nothing that touches the set, so the set is as clean as
+// c3_acc_acquire left it - initialised in stream order - and there is no launch of its own to wait for.)
 static void c3_acc_commit(vp_ctx* ctx)
 {
 #ifdef VP_PROBE
@@ -724,7 +765,9 @@ static bool c3_allow_plan_lds(vp_ctx* ctx, const ccl_plan& P)
 // The crowded-frame kernels (vp_ccl3.inl): launches that read the list of handed-over frames and leave at once when it is empty (the
 // usual case).
 template <int K>
-static int ccl_crowded(vp_ctx* ctx, const ccl_plan& P, const ccl_call& c)
+// prepare: the one run on an empty list that ccl_prepare_crowded queues (ncrowded then points at a zero word): nothing is acquired,
+// counted or written.
+static int ccl_crowded(vp_ctx* ctx, const ccl_plan& P, const ccl_call& c, u32* hint, const u32* ncrowded, bool prepare = false)
 {
     const ccl_tuning& T = ccl_env_tuning();
     const ccl_geom& G = P.G;
@@ -733,33 +776,35 @@ static int ccl_crowded(vp_ctx* ctx, const ccl_plan& P, const ccl_call& c)
     hipStream_t s = ctx->stream;
     const int scap = (int)c3_strips_cap(G.h);
     ccl_acc* acc3 = (ccl_acc*)ws.acc;
-    if (ctx->chain_streams == 1) {   // sub-batches on several streams would share the context's set: they keep the workspace's
+    if (ctx->chain_streams == 1 && !prepare) {   // sub-batches on several streams would share the context's set: they keep the workspace's
         const int rc = c3_acc_acquire(ctx, sizeof(ccl_acc) * (size_t)c.max_labels * (size_t)c.n, s, &acc3);
         if (rc != VP_OK) return rc;
     }
     const bool acc3_own = acc3 != (ccl_acc*)ws.acc;
     { vp_prof_scope ps(ctx, VPK_CCL_LOCAL);
-      hipLaunchKernelGGL(k_ccl3_link<K * C3_LINK_THREADS>, dim3((unsigned)(ctx->num_cu * T.lgrid)), dim3(K * C3_LINK_THREADS), P.lds3a, s, c.bits, G, P3, ws.c3_ncrowded,
-                         ws.c3_clist, ws.parent, ws.flags, ws.c3_child, ws.c3_lroot, ws.seglabel, acc3, c.max_labels, acc3_own ? 0 : 1); }
+      hipLaunchKernelGGL(k_ccl3_link<K * C3_LINK_THREADS>, dim3((unsigned)(ctx->num_cu * T.lgrid)), dim3(K * C3_LINK_THREADS), P.lds3a, s, c.bits, G, P3, ncrowded,
+                         ws.c3_clist, ws.parent, ws.flags, ws.c3_child, ws.c3_lroot, ws.seglabel, acc3, c.max_labels, acc3_own ? 0 : 1, hint); }
     { vp_prof_scope ps(ctx, VPK_CCL_BOUNDARY);
       const size_t span = (size_t)2 * G.wb + 4;     // u16 roots of the two rows (row pairs) that meet: span entries each
-      hipLaunchKernelGGL(k_ccl3_bound, dim3((unsigned)(ctx->num_cu * T.bgrid)), dim3(256), span * 4 + 16, s, c.bits, G, P3, ws.c3_ncrowded, ws.c3_clist, ws.parent, ws.flags,
+      hipLaunchKernelGGL(k_ccl3_bound, dim3((unsigned)(ctx->num_cu * T.bgrid)), dim3(256), span * 4 + 16, s, c.bits, G, P3, ncrowded, ws.c3_clist, ws.parent, ws.flags,
                          ws.c3_child, ws.seglabel); }
     { vp_prof_scope ps(ctx, VPK_CCL_RANK);
-      hipLaunchKernelGGL(k_ccl3_rank, dim3((unsigned)(ctx->num_cu * 4)), dim3(256), 0, s, G, P3, ws.c3_ncrowded, ws.c3_clist, ws.flags, ws.prefix, ws.c3_barr, ws.c3_lroot, ws.parent,
+      hipLaunchKernelGGL(k_ccl3_rank, dim3((unsigned)(ctx->num_cu * 4)), dim3(256), 0, s, G, P3, ncrowded, ws.c3_clist, ws.flags, ws.prefix, ws.c3_barr, ws.c3_lroot, ws.parent,
                          ws.c3_items); }
     { vp_prof_scope ps(ctx, VPK_CCL_STATS);
       // two instantiations, each taking the strips k_ccl3_rank marked for it: LIGHT first - two blocks per CU - then HEAVY
       auto label = [&](auto kernel, int blocks_per_cu, int threads, size_t lds) {
-          hipLaunchKernelGGL(kernel, dim3((unsigned)(ctx->num_cu * blocks_per_cu)), dim3(threads), lds, s, c.bits, G, P3, ws.c3_ncrowded, ws.c3_items, ws.c3_clist, ws.parent,
+          hipLaunchKernelGGL(kernel, dim3((unsigned)(ctx->num_cu * blocks_per_cu)), dim3(threads), lds, s, c.bits, G, P3, ncrowded, ws.c3_items, ws.c3_clist, ws.parent,
                              ws.flags, ws.c3_child, ws.prefix, ws.c3_lroot, ws.seglabel, ws.c3_barr, (c3_state*)ws.c3_state, (contrib*)ws.c3_tot, scap, c.nlabels, acc3,
                              c.max_labels, c.labels, c.stats, c.cent);
       };
       label(k_ccl3_label<C3_LABEL_THREADS, C3_LIGHT_ROOTS, C3_LIGHT_ACC>, T.agrid_light, C3_LABEL_THREADS, P.lds3c);
       label(k_ccl3_label<K * C3_LABEL_THREADS, 0, C3_ACC>, T.agrid, K * C3_LABEL_THREADS, P.lds3b); }
+    if (!prepare) ctx->ccl_launches += 5;
     if (c.stats || c.cent || acc3_own) {
+        if (!prepare) ctx->ccl_launches++;
         vp_prof_scope ps(ctx, VPK_CCL_FINAL);
-        hipLaunchKernelGGL(k_ccl3_rows, dim3((unsigned)(ctx->num_cu * 4)), dim3(256), 0, s, G, P3, ws.c3_ncrowded, ws.c3_clist, ws.flags, ws.c3_child, ws.prefix,
+        hipLaunchKernelGGL(k_ccl3_rows, dim3((unsigned)(ctx->num_cu * 4)), dim3(256), 0, s, G, P3, ncrowded, ws.c3_clist, ws.flags, ws.c3_child, ws.prefix,
                            ws.c3_barr, (const c3_state*)ws.c3_state, (const contrib*)ws.c3_tot, scap, acc3, c.max_labels, c.stats, c.cent, acc3_own ? 1 : 0);
     }
     VP_HIP(ctx, hipGetLastError());
@@ -767,9 +812,41 @@ static int ccl_crowded(vp_ctx* ctx, const ccl_plan& P, const ccl_call& c)
     return VP_OK;
 }
 
+// The context's hint word (vp_ccl_hint.h): pinned host memory the device writes and the host reads without synchronising, made on the
+// first two-level call.  Null when it could not be made: the labelling then always queues the crowded-frame kernels.
+static u32* ccl_hint_word(vp_ctx* ctx)
+{
+    if (!ctx->ccl_hint_host && !ctx->ccl_hint_failed) {
+        void* p = nullptr;
+        if (hipHostMalloc(&p, sizeof(u32), hipHostMallocDefault) != hipSuccess) { (void)hipGetLastError(); ctx->ccl_hint_failed = 1; return nullptr; }
+        *(volatile u32*)p = 0u;
+        ctx->ccl_hint_host = (uint32_t*)p;
+    }
+    return ctx->ccl_hint_host;
+}
+
+// A process that has only run LEAN has never dispatched the crowded-frame kernels, and the call that switches to FULL - in the middle of
+// a crowded run - paid for their first dispatch: ~0.2 ms once per process on top of that call (EXPERIMENTS.md).  The first LEAN call of a
+// context for either strip height therefore queues them once on an empty list (a zero word of the context's in place of the merge's
+// count; six launches that leave at once, ~17 us, never again).  Not part of the labelling sequence vp_ccl_last_launches counts.
+static int ccl_prepare_crowded(vp_ctx* ctx, const ccl_plan& P, const ccl_call& c)
+{
+    int& d = ctx->ccl_prepared[P.c3_tall ? 1 : 0];   // per context: a superset of per process and per device, and free of races
+    if (d) return VP_OK;
+    if (!ctx->ccl_zero_dev) {
+        void* p = nullptr;
+        if (hipMalloc(&p, 256) != hipSuccess) { (void)hipGetLastError(); return VP_OK; }
+        if (hipMemsetAsync(p, 0, 256, ctx->stream) != hipSuccess) { (void)hipGetLastError(); (void)hipFree(p); return VP_OK; }
+        ctx->ccl_zero_dev = (u32*)p;
+    }
+    d = 1;
+    return P.c3_tall ? ccl_crowded<2>(ctx, P, c, nullptr, ctx->ccl_zero_dev, true) : ccl_crowded<1>(ctx, P, c, nullptr, ctx->ccl_zero_dev, true);
+}
+
 // The two-level path (vp_ccl2.inl): strips resolved in LDS, one merge block per frame; frames the merge hands over go to the
 // crowded-frame kernels when the geometry suits them (it does for every frame up to 8192 px wide) and the device allows their LDS,
-// otherwise to the one-level kernels.
+// otherwise to the one-level kernels.  Where the crowded-frame kernels serve, the hint of an earlier call decides whether they are
+// queued at all (FULL) or one launch of k_ccl2_finish stands behind the merge in their place (LEAN): the results are the same.
 static int ccl_two_level(vp_ctx* ctx, const ccl_plan& P, const ccl_call& c)
 {
     const ccl_geom& G = P.G;
@@ -778,6 +855,14 @@ static int ccl_two_level(vp_ctx* ctx, const ccl_plan& P, const ccl_call& c)
     const int n = c.n;
     const bool c3_ok = P.P3.ok && (P.c3_tall ? c3_allow_plan_lds<2>(ctx, P) : c3_allow_plan_lds<1>(ctx, P));
     const int c3_strips = c3_ok ? P.P3.strips : 0;
+    int mode = CCL_MODE_FULL;
+    u32* hint = nullptr;
+    if (c3_ok && (hint = ccl_hint_word(ctx)) != nullptr) {
+        ccl_hint_state st = {ctx->ccl_hint_mode, ctx->ccl_hint_quiet};
+        mode = ccl_hint_decide(st, *(volatile u32*)hint, ctx->ccl_crowded_force, ctx->chain_streams + (ctx->ccl_beside ? 1 : 0));
+        ctx->ccl_hint_mode = st.mode; ctx->ccl_hint_quiet = st.quiet;
+    }
+    ctx->ccl_launches += 2;
     { vp_prof_scope ps(ctx, VPK_CCL2_LOCAL);
       hipLaunchKernelGGL(k_ccl2_local, dim3((unsigned)((size_t)n * P.strips)), dim3(256), P.lds2, s, c.bits, G, P.strips, (int)P.cap2, (int)P.rc, (int)P.tail_words, ws.c2_ncomp,
                          (contrib*)ws.c2_recs, (c2_box*)ws.c2_bgbox, ws.wordlabel, ws.seglabel, ws.c3_ncrowded); }
@@ -786,9 +871,24 @@ static int ccl_two_level(vp_ctx* ctx, const ccl_plan& P, const ccl_call& c)
                          (const c2_box*)ws.c2_bgbox, ws.wordlabel, ws.seglabel, ws.c2_label, ws.c2_crowded, c.nlabels, c.stats, c.cent, c.max_labels,
                          ws.c3_ncrowded, ws.c3_clist, (c3_state*)ws.c3_state, ws.c3_barr, c3_strips); }
     VP_HIP(ctx, hipGetLastError());
-    int rc;
-    if (c3_ok) {
-        rc = P.c3_tall ? ccl_crowded<2>(ctx, P, c) : ccl_crowded<1>(ctx, P, c);
+    int rc = VP_OK;
+    if (c3_ok && mode == CCL_MODE_LEAN) {
+        // The crowded-frame kernels' accumulator set is made and initialised here as well, though k_ccl2_finish works on the workspace's
+        // accumulators and leaves the set alone (hence the commit at once: it is as clean as it was): the call that switches to FULL then
+        // finds it ready instead of paying a synchronisation, hipMalloc and the set's initialisation (200 MB for 32 frames of 131,072
+        // labels: 0.64 ms, measured as the first timed step of bench.py's s3_noise_labelling).
+        rc = ccl_prepare_crowded(ctx, P, c);
+        if (rc != VP_OK) return rc;
+        ccl_acc* set = nullptr;
+        rc = c3_acc_acquire(ctx, sizeof(ccl_acc) * (size_t)c.max_labels * (size_t)n, s, &set);
+        if (rc != VP_OK) return rc;
+        if (set) c3_acc_commit(ctx);
+        ctx->ccl_launches++;
+        vp_prof_scope ps(ctx, VPK_CCL_STATS);
+        hipLaunchKernelGGL(k_ccl2_finish, dim3((unsigned)n), dim3(256), 0, s, c.bits, G, ws.c2_crowded, ws.c3_ncrowded, hint, ws.parent, ws.flags, ws.prefix,
+                           (ccl_acc*)ws.acc, (contrib*)ws.bgpart, ws.seglabel, ws.wordlabel, c.nlabels, c.max_labels, c.labels, c.stats, c.cent, P.gpr, P.magic);
+    } else if (c3_ok) {
+        rc = P.c3_tall ? ccl_crowded<2>(ctx, P, c, hint, ws.c3_ncrowded) : ccl_crowded<1>(ctx, P, c, hint, ws.c3_ncrowded);
     } else {
         // the one-level kernels, launched whatever the frames hold (the flags live on the device); they leave at once for frames the merge resolved
         rc = ccl_roots(ctx, c.bits, G, n, ws.parent, ws.flags, ws.c2_crowded);
@@ -796,6 +896,7 @@ static int ccl_two_level(vp_ctx* ctx, const ccl_plan& P, const ccl_call& c)
     }
     if (rc != VP_OK) return rc;
     if (c.labels) {
+        ctx->ccl_launches++;
         vp_prof_scope ps(ctx, VPK_CCL2_WRITE);
         const dim3 wr_grid((unsigned)((G.h + WR_ROWS - 1) / WR_ROWS), (unsigned)n);
         hipLaunchKernelGGL(k_ccl2_write<0>, wr_grid, dim3(256), 0, s, c.bits, G, P.strips, (int)P.rc, ws.seglabel, ws.wordlabel, ws.c2_label, ws.c2_crowded, c.labels, P.gpr, P.magic,
@@ -812,6 +913,7 @@ int vpk_ccl(vp_ctx* ctx, const u64* d_bits, int w, int h, int n, int numbering, 
     if (max_labels < 1) return vp_fail(ctx, VP_ERR_INVALID, "max_labels");
     const ccl_plan P = ccl_make_plan(w, h, numbering, ctx->ccl_levels, ctx->ccl_mcap, ccl_env_tuning());
     const ccl_call c = {d_bits, n, ws, d_labels, d_stats, d_centroids, max_labels, d_nlabels};
+    ctx->ccl_launches = 0;   // kernels of the labelling sequence this call queues (vp_ccl_last_launches)
     if (P.two_level) return ccl_two_level(ctx, P, c);
 
     int rc = ccl_roots(ctx, d_bits, P.G, n, ws.parent, ws.flags);
@@ -819,6 +921,7 @@ int vpk_ccl(vp_ctx* ctx, const u64* d_bits, int w, int h, int n, int numbering, 
     rc = ccl_one_level_tail(ctx, d_bits, P.G, n, ws, d_stats, d_centroids, max_labels, d_nlabels, nullptr);
     if (rc != VP_OK) return rc;
     if (d_labels) {
+        ctx->ccl_launches++;
         vp_prof_scope ps(ctx, VPK_CCL_WRITE);
         const u32 total_rows = (u32)((size_t)n * h);
         hipLaunchKernelGGL(k_ccl_write, dim3((total_rows + WR_ROWS - 1) / WR_ROWS), dim3(256), 0, ctx->stream, d_bits, P.G, ws.seglabel, ws.wordlabel, d_labels,

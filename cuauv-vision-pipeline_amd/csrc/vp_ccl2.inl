@@ -14,8 +14,9 @@
 //
 // Frames that do not fit (a strip with more segments than its LDS union-find holds or more components than C2_RC, a frame with
 // more than C2_MCAP strip components) are flagged `crowded` by k_ccl2_merge, which appends them to a list; the crowded-frame kernels
-// of vp_ccl3.inl (five launches behind the merge, on the same stream) finish the frames of that list and leave at once when it is
-// empty.  Geometries those kernels do not take fall back to the one-level kernels of vp_ccl.hip (vpk_ccl).
+// of vp_ccl3.inl (six launches behind the merge, on the same stream) finish the frames of that list and leave at once when it is
+// empty; while no crowded frame is expected one launch of k_ccl2_finish (below) stands behind the merge in their place (vp_ccl_hint.h).
+// Geometries those kernels do not take fall back to the one-level kernels of vp_ccl.hip (vpk_ccl).
 
 // C2_RC (vp_ccl.hip): stride of the per-strip component tables; a kernel argument (rc <= C2_RC) bounds the count in use
 #ifdef VP_PROBE   // measurement builds only (tools/build_probe.sh): ticks between probe points, one slot per block (plain stores)
@@ -843,4 +844,50 @@ __global__ __launch_bounds__(256, 8) void k_ccl2_write(const u64* __restrict__ b
             }
         }
     }
+}
+
+// ---- LEAN mode: the one launch that stands behind the merge when no crowded frame is expected (vp_ccl_hint.h) ----------------------------
+// One block per batch frame.  A block whose frame the merge resolved reads the frame's flag and leaves.  A frame that was handed over
+// after all is finished here, by this one block, with the bodies of the one-level kernels (vp_ccl.hip): flat arrays indexed by segment
+// id in global memory, the block walking the block indices of each kernel in turn.  That is the result the crowded-frame kernels
+// produce - cv2's labels, the rows up to max_labels, zeros past the last label, nlabels - at a small fraction of their speed, which
+// is the trade: the frame is a surprise, the next call expects it (the hint) and launches the fast kernels.
+// Phases meet inside the block only: a barrier, with device-scope fences on both sides of it so that what one phase left in global
+// memory (plain stores and atomics) is what the next one reads, whatever the CU's vector cache held before.  Nothing waits for
+// another block.  The accumulators are the workspace's, cleared per frame by the rank phase: the context's own set (c3_acc_acquire)
+// is not touched and stays as clean as it was.
+// Block 0 also leaves the number of handed-over frames in the context's hint word.
+#define C2F_PHASE() do { __threadfence(); __syncthreads(); __threadfence(); } while (0)
+__global__ __launch_bounds__(256) void k_ccl2_finish(const u64* bits, ccl_geom G, const u32* crowded, const u32* c3_ncrowded, u32* hint,
+                                                     u32* parent, u32* flags, u32* prefix, ccl_acc* acc, contrib* bgpart, u32* seglabel,
+                                                     u32* wordlabel, int32_t* nlabels, int max_labels, int32_t* labels, int32_t* stats,
+                                                     double* cent, u32 gpr, u32 gpr_magic)
+{
+    const int f = (int)blockIdx.x, tid = (int)threadIdx.x;
+    if (blockIdx.x == 0 && tid == 0 && hint) *hint = *c3_ncrowded;
+    if (!crowded[f]) return;                                  // block-uniform: the usual case
+    const int wblocks = (G.h * G.ww + 255) / 256;
+    u32* ffl = flags + (size_t)f * G.nw32;
+    for (u32 k = (u32)tid; k < G.nw32; k += 256) ffl[k] = 0u;
+    C2F_PHASE();
+    for (int vb = 0; vb < wblocks; vb++) ccl_init_body(bits, G, parent, flags, vb, f);
+    C2F_PHASE();
+    for (int vb = 0; vb < wblocks; vb++) ccl_link_body(bits, G, parent, flags, vb, f);
+    C2F_PHASE();
+    for (int vb = 0; vb < RK_PARTS + BG_PARTS; vb++) {
+        ccl_rank_body(G, flags, prefix, nlabels, acc, max_labels, bits, bgpart, vb, f);
+        __syncthreads();                                      // the body's LDS is free for the next part
+    }
+    C2F_PHASE();
+    const int nl = (int)(prefix[(size_t)f * G.nw32 + G.nw32 - 1] + (u32)__popc(ffl[G.nw32 - 1])) + 1;   // every root + the background
+    for (int vb = 0; vb < wblocks; vb++) {
+        ccl_stats_body(bits, G, parent, flags, prefix, seglabel, wordlabel, acc, max_labels, vb, f);
+        __syncthreads();
+    }
+    C2F_PHASE();
+    if (stats || cent)
+        for (int vb = 0; vb < (max_labels + 255) / 256; vb++) ccl_final_body(acc, bgpart, nl, max_labels, stats, cent, vb, f);
+    if (labels)
+        for (u32 r0 = 0; r0 < (u32)G.h; r0 += WR_ROWS)
+            ccl_write_body(bits, G, seglabel, wordlabel, labels, (u32)f * (u32)G.h + r0, min((u32)WR_ROWS, (u32)G.h - r0), gpr, gpr_magic);
 }

@@ -19,7 +19,8 @@
 //     local component, rows of components that are complete within the strip written straight to the output (no atomics), the rest
 //     added to per-label accumulators, and the strip's part of the label image stored from LDS.
 //
-// Five short launches, each a fixed number of blocks that loop over (frame, strip) items of the frames k_ccl2_merge handed over and
+// Six short launches (k_ccl3_label runs as two: a light and a heavy instantiation) - the FULL mode of vp_ccl_hint.h; while no crowded frame
+// is expected one launch of k_ccl2_finish, vp_ccl2.inl, stands in for all six.  Each is a fixed number of blocks that loop over (frame, strip) items of the frames k_ccl2_merge handed over and
 // leave at once when there are none: k_ccl3_link (strips), k_ccl3_bound (boundaries), k_ccl3_rank (root counts and prefixes per slice,
 // absorbed roots flattened), k_ccl3_label (labels, statistics, label image), k_ccl3_rows (rows of components that span strips).  A
 // first form chained the stages inside two launches with arrival counters ("the strip that finishes second does the boundary, the
@@ -267,9 +268,10 @@ template <int LT>
 __global__ __launch_bounds__(LT, 8) void k_ccl3_link(const u64* __restrict__ bits, ccl_geom G, c3_plan P, const u32* __restrict__ ncrowded,
                                                                const u32* __restrict__ clist, u32* __restrict__ parent, u32* __restrict__ flags,
                                                                u32* __restrict__ child, u32* __restrict__ lrootbits, u32* __restrict__ root16,
-                                                               ccl_acc* __restrict__ acc, int max_labels, int acc_clear)
+                                                               ccl_acc* __restrict__ acc, int max_labels, int acc_clear, u32* __restrict__ hint)
 {
     const u32 nc = *ncrowded;
+    if (hint && blockIdx.x == 0 && threadIdx.x == 0) *hint = nc;   // the context's pinned word: what the next call expects (vp_ccl_hint.h)
     if (nc == 0) return;                                      // the common case: nothing was handed over
     extern __shared__ __attribute__((aligned(16))) u64 c3_lds[];
     const int NT = LT;

@@ -71,6 +71,14 @@ struct vp_ctx {
     void* c3_acc;                 // crowded-frame labelling: accumulators of components that span strips, all empty between calls (vp_ccl.hip)
     size_t c3_acc_bytes;
     int c3_acc_dirty;             // not known to be all empty (a call cut short, another stream): c3_acc_acquire reinitialises it before use
+    uint32_t* ccl_hint_host;      // pinned: frames the merge of the last two-level labelling call handed over, written by the device, read without synchronising (vp_ccl_hint.h)
+    int ccl_hint_failed;          // the word could not be allocated: the crowded-frame kernels are always queued
+    int ccl_hint_mode, ccl_hint_quiet;   // ccl_hint_state between calls (zero: a new context starts LEAN)
+    int ccl_crowded_force;        // VP_OPT_CCL_CROWDED: 0 (default) by the hint, 1 always the crowded-frame kernels, 2 always the one stand-in launch
+    int ccl_beside;               // set around a vpk_ccl that has other work of the same call on a side stream beside it (the chain's contour pass): counts as a second stream, i.e. FULL
+    int ccl_prepared[2];          // that run has been queued on this context (short / tall strips)
+    u32* ccl_zero_dev;            // a device word that holds 0: the empty list of the crowded-frame kernels' one preparing run (ccl_prepare_crowded, vp_ccl.hip)
+    int ccl_launches;             // kernels of the labelling sequence the last vpk_ccl queued (vp_ccl_last_launches)
     int hough_global;             // 1: every Hough vote is a global atomic (VP_OPT_HOUGH_LDS 0); 0 (default): rows counted in LDS where they fit
     int blur_onepass;             // VP_OPT_BLUR_ONEPASS: -1 (default) the measured choice, 1 the one-pass kernel wherever its tile fits, 0 always two passes
     int median_mask;              // VP_OPT_MEDIAN_MASK: -1 (default) the measured choice, 1 the mask kernel for every mask it can serve, 0 never

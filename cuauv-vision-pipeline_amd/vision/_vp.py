@@ -41,6 +41,7 @@ OPT_HOUGH_CIRCLES_LDS = 6
 OPT_BLUR_ONEPASS = 7
 OPT_MEDIAN_MASK = 8
 OPT_CLAHE_SPLIT = 9
+OPT_CCL_CROWDED = 10     # 0 by the hint of an earlier call, 1 always the crowded-frame kernels, 2 always the one stand-in launch
 THRESH_BINARY, THRESH_BINARY_INV, THRESH_TRUNC, THRESH_TOZERO, THRESH_TOZERO_INV = 0, 1, 2, 3, 4
 HOUGH_GRADIENT = 3
 # return codes of include/vp.h
@@ -98,6 +99,7 @@ _SIGS = {
     "vp_get_stream": (C.c_void_p, [C.c_void_p]),
     "vp_synchronize": (C.c_int, [C.c_void_p]),
     "vp_set_option": (C.c_int, [C.c_void_p, C.c_int, C.c_int]),
+    "vp_ccl_last_launches": (C.c_int, [C.c_void_p, C.POINTER(C.c_int32)]),
     "vp_timer_start": (C.c_int, [C.c_void_p]),
     "vp_timer_stop": (C.c_int, [C.c_void_p, C.POINTER(C.c_float)]),
     "vp_get_tables": (C.c_int, [C.c_void_p] * 5),
@@ -341,6 +343,12 @@ class Context:
 
     def synchronize(self):
         check(lib().vp_synchronize(self.handle), self.handle)
+
+    def ccl_last_launches(self):
+        """Kernels of the labelling sequence the last labelling call of this context queued."""
+        n = C.c_int32()
+        check(lib().vp_ccl_last_launches(self.handle, C.byref(n)), self.handle)
+        return n.value
 
     def timer_start(self):
         check(lib().vp_timer_start(self.handle), self.handle)

@@ -92,10 +92,20 @@ int vp_synchronize(vp_ctx* ctx);
  * VP_OPT_CLAHE_SPLIT (0..64, default 0; the environment variable of the same name sets 1..64 at vp_create): how many blocks share
  * the histogram of one CLAHE tile in vp_clahe_u8 / vp_clahe_dev.  1 = one block per tile does histogram, clip, scan and table in one
  * launch; n > 1 = n blocks (at most one per tile row) add partial histograms with device atomics and a finishing launch makes the
- * tables; 0 = the measured choice.  Results are identical. */
+ * tables; 0 = the measured choice.  Results are identical.
+ * VP_OPT_CCL_CROWDED (0, 1 or 2, default 0; the environment variable of the same name sets it at vp_create): what the two-level
+ * labelling queues behind its merge for frames the merge hands over as crowded.  1 = always the six launches of the crowded-frame
+ * kernels, which leave at once when no frame was handed over; 2 = always one launch that finishes such a frame correctly but slowly
+ * (with VP_OPT_CHAIN_STREAMS above 1: still the six); 0 = by a hint - the number of frames an earlier call handed over, read without
+ * synchronising: the one launch until a call hands a frame over, the six from the next call on, the one again after 32 calls in a
+ * row that handed nothing over; a vp_chain_run_contours call whose contour pass runs beside the labelling always takes the six.
+ * Results are identical. */
 enum { VP_OPT_CHAIN_STREAMS = 1, VP_OPT_CCL_LEVELS = 2, VP_OPT_CCL_MERGE_CAP = 3, VP_OPT_FLAT_OPS = 4, VP_OPT_HOUGH_LDS = 5,
-       VP_OPT_HOUGH_CIRCLES_LDS = 6, VP_OPT_BLUR_ONEPASS = 7, VP_OPT_MEDIAN_MASK = 8, VP_OPT_CLAHE_SPLIT = 9 };
+       VP_OPT_HOUGH_CIRCLES_LDS = 6, VP_OPT_BLUR_ONEPASS = 7, VP_OPT_MEDIAN_MASK = 8, VP_OPT_CLAHE_SPLIT = 9, VP_OPT_CCL_CROWDED = 10 };
 int vp_set_option(vp_ctx* ctx, int option, int value);
+/* Kernels of the labelling sequence that the context's last labelling call queued (vp_ccl_*, vp_chain_run with ccl): tells the tests
+ * which form VP_OPT_CCL_CROWDED = 0 chose.  The one-off initialisation of the crowded-frame kernels' accumulators is not counted. */
+int vp_ccl_last_launches(vp_ctx* ctx, int32_t* launches);
 /* HIP-event stopwatch on the context's stream (bench.py: roofline.achieved). */
 int vp_timer_start(vp_ctx* ctx);
 int vp_timer_stop(vp_ctx* ctx, float* elapsed_ms); /* records, synchronises, returns ms */
