@@ -6,7 +6,10 @@ Image arithmetic (cvtColor, inRange, erode/dilate/morphologyEx, findContours, co
 libvp (HIP); small polygon maths (moments, contourArea, arcLength, minAreaRect, boxPoints, approxPolyDP) is host numpy, as it is
 CPU code in OpenCV too.  The element-wise operators (bitwise_*, add / subtract / absdiff, LUT, split / merge / extractChannel,
 countNonZero) are host numpy for numpy images and libvp kernels as soon as one image operand is a DeviceMat.  Anything else
-raises AttributeError like a missing cv2 symbol would."""
+raises AttributeError like a missing cv2 symbol would.
+
+An image operator's launch lives in the mirror (vision.utils.transform / color), never here: a name of this module is cv2's argument
+order, cv2's own rejections, `_into(dst, ...)` and `_gather`, which turns what the mirror refuses into `error`."""
 import math
 import sys
 
@@ -17,6 +20,7 @@ from vision.utils import color as _color
 from vision.utils import draw as _draw
 from vision.utils import feature as _feature
 from vision.utils import transform as _transform
+from vision.utils.helpers import as_cv2_error as _gather, error, image_source as _image_source, packed_source as _device_source  # noqa: F401
 
 COLOR_BGR2LAB, COLOR_BGR2HSV, COLOR_BGR2GRAY, COLOR_GRAY2BGR, COLOR_HSV2BGR = 44, 40, 6, 8, 54     # cv2's own enum values
 COLOR_BGR2YCrCb, COLOR_BGR2YCR_CB, COLOR_BGR2HLS = 36, 36, 52
@@ -52,10 +56,6 @@ class UMat:   # only so that `from cv2 import UMat` and isinstance checks work
 
     def get(self):
         return self._arr
-
-
-class error(Exception):
-    pass
 
 
 _CVT = {COLOR_BGR2LAB: _color.bgr_to_lab, COLOR_BGR2HSV: _color.bgr_to_hsv, COLOR_BGR2GRAY: _color.bgr_to_gray,
@@ -678,41 +678,19 @@ def LUT(src, lut, dst=None):
 
 def getRotationMatrix2D(center, angle, scale):
     """imgproc/src/imgwarp.cpp getRotationMatrix2D: 2x3 float64 (modules/preprocessor.py:131-133)."""
-    ang = angle * np.pi / 180.0
-    a, b = scale * np.cos(ang), scale * np.sin(ang)
-    cx, cy = float(np.float32(center[0])), float(np.float32(center[1]))   # the centre is a Point2f
-    return np.array([[a, b, (1 - a) * cx - b * cy], [-b, a, b * cx + (1 - a) * cy]], np.float64)
+    return _transform._rotation_matrix_2d(center, angle, scale)
 
 
 def GaussianBlur(src, ksize, sigmaX, dst=None, sigmaY=0, borderType=None):
     """cv2.GaussianBlur on uint8 images (modules/preprocessor.py:110-114): OpenCV's bit-exact fixed-point path on the GPU.
     Positional order as in cv2: (src, ksize, sigmaX, dst, sigmaY, borderType)."""
-    return _into(dst, _gaussian_blur(src, ksize, sigmaX, sigmaY, borderType))
+    return _into(dst, _transform._gaussian_blur(src, ksize, sigmaX, sigmaY, borderType))
 
 
-def _gaussian_blur(src, ksize, sigmaX, sigmaY, borderType):
-    from vision import _vp
-    if borderType not in (None, BORDER_DEFAULT):
-        raise error("GaussianBlur: only BORDER_DEFAULT (reflect 101) is on the accelerated path")
-    src, on_dev = _device_source(src)
-    if src.dtype != np.uint8 or src.ndim not in (2, 3) or src.size == 0:
-        raise error("GaussianBlur: only non-empty uint8 images are on the accelerated path")
-    cn = 1 if src.ndim == 2 else src.shape[2]
-    kw, kh = int(ksize[0]), int(ksize[1])
-    if kw <= 0 or kh <= 0 or kw % 2 == 0 or kh % 2 == 0 or kw > 511 or kh > 511 or cn > 4:
-        raise error("GaussianBlur: kernel sizes must be odd, 1..511")
-    ctx = _vp.default_context()
-    if on_dev:                                       # the image stays in HBM (libvp vp_gaussian_blur_dev)
-        from vision.devmat import DeviceMat
-        src.refresh_device(ctx)
-        out = DeviceMat(ctx, src.shape)
-        _vp.check(_vp.lib().vp_gaussian_blur_dev(ctx.handle, src.dev_ptr, src.shape[1] * cn, src.shape[1], src.shape[0], cn, kw, kh, float(sigmaX),
-                                                 float(sigmaY), out.dev_ptr), ctx.handle)
-        return out
-    out = np.empty_like(src)
-    _vp.check(_vp.lib().vp_gaussian_blur_u8(ctx.handle, _vp.ptr(src), src.shape[1], src.shape[0], cn, kw, kh, float(sigmaX), float(sigmaY),
-                                            _vp.ptr(out)), ctx.handle)
-    return out
+def _source(name, src, dtype_words="only uint8 sources are on the accelerated path"):
+    """The packed source of an operator, checked once (vision.utils.helpers.image_source) and refused in the facade's words."""
+    return _gather(name, _image_source, _device_source(src)[0],
+                   said=(dtype_words, "expected a non-empty (h, w) or (h, w, c) image", "at most 4 channels"))[0]
 
 
 def medianBlur(src, ksize, dst=None):
@@ -727,14 +705,8 @@ def medianBlur(src, ksize, dst=None):
         raise error("medianBlur: ksize must be odd and greater than 0")
     if k > 255:
         raise error("medianBlur: ksize above 255 is outside the accelerated path")
-    if src.dtype != np.uint8:
-        raise error("medianBlur: only uint8 images are on the accelerated path")
-    if src.ndim not in (2, 3) or src.size == 0:
-        raise error("medianBlur: expected a non-empty (h, w) or (h, w, c) image")
-    cn = 1 if src.ndim == 2 else src.shape[2]
-    if cn > 4:
-        raise error("medianBlur: at most 4 channels")
-    if cn == 2 and k > 5:
+    src = _source("medianBlur", src, "only uint8 images are on the accelerated path")
+    if src.ndim == 3 and src.shape[2] == 2 and k > 5:
         raise error("medianBlur: 2 channels only with ksize 3 or 5 (cv2 asserts 1, 3 or 4 channels above)")
     return _into(dst, _transform.median_blur(src, k))
 
@@ -769,8 +741,8 @@ class CLAHE:
         if tx > 64 or ty > 64:
             raise error("CLAHE.apply: more than 64 tiles along an axis is outside the accelerated path")
         try:
-            return _into(dst, _color.clahe(src, self._clip, self._grid))
-        except (TypeError, ValueError, _vp.VpError) as e:
+            return _into(dst, _gather("CLAHE.apply", _color.clahe, src, self._clip, self._grid))
+        except _vp.VpError as e:
             raise error(f"CLAHE.apply: {e}") from None
 
     def setClipLimit(self, clipLimit):
@@ -810,19 +782,10 @@ def createCLAHE(clipLimit=40.0, tileGridSize=(8, 8)):
 # ---- derivative filters (libvp vp_deriv.hip) ------------------------------------------------------------------------------------------
 def _deriv_call(name, fn, src, ddepth, scale, delta, borderType, *args):
     """What cv2 rejects, and the two restrictions of this path: scale = 1 and delta = 0 only."""
-    src, _ = _device_source(src)
-    if src.dtype != np.uint8:
-        raise error(f"{name}: only uint8 sources are on the accelerated path")
-    if src.ndim not in (2, 3) or src.size == 0:
-        raise error(f"{name}: expected a non-empty (h, w) or (h, w, c) image")
-    if src.ndim == 3 and src.shape[2] > 4:
-        raise error(f"{name}: at most 4 channels")
+    src = _source(name, src)
     if scale != 1 or delta != 0:
         raise error(f"{name}: scale != 1 or delta != 0 takes OpenCV's float paths, which this library does not restate (DESIGN.md section 7)")
-    try:
-        return fn(src, *args, ddepth, BORDER_DEFAULT if borderType is None else borderType)
-    except (TypeError, ValueError) as e:
-        raise error(f"{name}: {e}") from None
+    return _gather(name, fn, src, *args, ddepth, BORDER_DEFAULT if borderType is None else borderType)
 
 
 def Sobel(src, ddepth, dx, dy, dst=None, ksize=3, scale=1, delta=0, borderType=BORDER_DEFAULT):
@@ -848,10 +811,7 @@ def spatialGradient(src, dx=None, dy=None, ksize=3, borderType=BORDER_DEFAULT):
     src, _ = _device_source(src)
     if src.dtype != np.uint8:
         raise error("spatialGradient: only uint8 sources")
-    try:
-        gx, gy = _transform.spatial_gradient(src, ksize, BORDER_DEFAULT if borderType is None else borderType)
-    except (TypeError, ValueError) as e:
-        raise error(f"spatialGradient: {e}") from None
+    gx, gy = _gather("spatialGradient", _transform.spatial_gradient, src, ksize, BORDER_DEFAULT if borderType is None else borderType)
     return _into(dx, gx), _into(dy, gy)
 
 
@@ -861,24 +821,10 @@ def convertScaleAbs(src, dst=None, alpha=1, beta=0):
     if alpha != 1 or beta != 0:
         raise error("convertScaleAbs: alpha != 1 or beta != 0 is outside the accelerated path (DESIGN.md section 7)")
     src, _ = _device_source(src)
-    try:
-        return _into(dst, _transform.convert_scale_abs(src))
-    except (TypeError, ValueError) as e:
-        raise error(f"convertScaleAbs: {e}") from None
+    return _into(dst, _gather("convertScaleAbs", _transform.convert_scale_abs, src))
 
 
 # ---- box filter, pyramid steps, integral image (libvp vp_box.hip, vp_pyr.hip, vp_integral.hip) ------------------------------------------
-def _box_source(name, src):
-    src, _ = _device_source(src)
-    if src.dtype != np.uint8:
-        raise error(f"{name}: only uint8 sources are on the accelerated path")
-    if src.ndim not in (2, 3) or src.size == 0:
-        raise error(f"{name}: expected a non-empty (h, w) or (h, w, c) image")
-    if src.ndim == 3 and src.shape[2] > 4:
-        raise error(f"{name}: at most 4 channels")
-    return src
-
-
 def _ksize(name, ksize, anchor):
     try:
         kw, kh = (int(v) for v in ksize)
@@ -896,22 +842,16 @@ def boxFilter(src, ddepth, ksize, dst=None, anchor=(-1, -1), normalize=True, bor
     """cv2.boxFilter on uint8 images, on the GPU, pure integer arithmetic: unnormalised sums cast to ddepth (-1 / CV_8U, CV_16S, CV_32S,
     CV_32F, CV_64F); normalised, CV_8U only and only window areas on which OpenCV's own roundings agree.
     Positional order as in cv2.  A DeviceMat stays in HBM."""
-    src = _box_source("boxFilter", src)
+    src = _source("boxFilter", src)
     kw, kh = _ksize("boxFilter", ksize, anchor)
-    try:
-        return _into(dst, _transform.box_filter(src, kw, kh, ddepth, normalize, BORDER_DEFAULT if borderType is None else borderType))
-    except (TypeError, ValueError) as e:
-        raise error(f"boxFilter: {e}") from None
+    return _into(dst, _gather("boxFilter", _transform.box_filter, src, kw, kh, ddepth, normalize, BORDER_DEFAULT if borderType is None else borderType))
 
 
 def blur(src, ksize, dst=None, anchor=(-1, -1), borderType=BORDER_DEFAULT):
     """cv2.blur: the normalised box filter (see boxFilter)."""
-    src = _box_source("blur", src)
+    src = _source("blur", src)
     kw, kh = _ksize("blur", ksize, anchor)
-    try:
-        return _into(dst, _transform.box_filter(src, kw, kh, -1, True, BORDER_DEFAULT if borderType is None else borderType))
-    except (TypeError, ValueError) as e:
-        raise error(f"blur: {e}") from None
+    return _into(dst, _gather("blur", _transform.box_filter, src, kw, kh, -1, True, BORDER_DEFAULT if borderType is None else borderType))
 
 
 def _default_dstsize(name, dstsize, want):
@@ -921,42 +861,30 @@ def _default_dstsize(name, dstsize, want):
 
 def pyrDown(src, dst=None, dstsize=None, borderType=BORDER_DEFAULT):
     """cv2.pyrDown on uint8 images, on the GPU: ((w + 1) // 2, (h + 1) // 2); BORDER_DEFAULT, BORDER_REPLICATE or BORDER_REFLECT."""
-    src = _box_source("pyrDown", src)
+    src = _source("pyrDown", src)
     _default_dstsize("pyrDown", dstsize, ((src.shape[1] + 1) // 2, (src.shape[0] + 1) // 2))
-    try:
-        return _into(dst, _transform.pyr_down(src, BORDER_DEFAULT if borderType is None else borderType))
-    except (TypeError, ValueError) as e:
-        raise error(f"pyrDown: {e}") from None
+    return _into(dst, _gather("pyrDown", _transform.pyr_down, src, BORDER_DEFAULT if borderType is None else borderType))
 
 
 def pyrUp(src, dst=None, dstsize=None, borderType=BORDER_DEFAULT):
     """cv2.pyrUp on uint8 images, on the GPU: (2w, 2h); BORDER_DEFAULT only, as cv2."""
-    src = _box_source("pyrUp", src)
+    src = _source("pyrUp", src)
     _default_dstsize("pyrUp", dstsize, (2 * src.shape[1], 2 * src.shape[0]))
-    try:
-        return _into(dst, _transform.pyr_up(src, BORDER_DEFAULT if borderType is None else borderType))
-    except (TypeError, ValueError) as e:
-        raise error(f"pyrUp: {e}") from None
+    return _into(dst, _gather("pyrUp", _transform.pyr_up, src, BORDER_DEFAULT if borderType is None else borderType))
 
 
 def buildPyramid(src, maxlevel):
     """cv2.buildPyramid: the list [src, pyrDown(src), ...] of maxlevel + 1 images; a DeviceMat's levels never visit the host."""
-    src = _box_source("buildPyramid", src)
-    try:
-        return _transform.build_pyramid(src, maxlevel)
-    except (TypeError, ValueError) as e:
-        raise error(f"buildPyramid: {e}") from None
+    src = _source("buildPyramid", src)
+    return _gather("buildPyramid", _transform.build_pyramid, src, maxlevel)
 
 
 def integral(src, sum=None, sdepth=-1):
     """cv2.integral on uint8 images, on the GPU: (h + 1, w + 1[, cn]) int32; sdepth -1 or CV_32S."""
     if sdepth not in (-1, CV_32S):
         raise error("integral: only sdepth -1 / CV_32S is on the accelerated path")
-    src = _box_source("integral", src)
-    try:
-        return _into(sum, _transform.integral(src))
-    except (TypeError, ValueError) as e:
-        raise error(f"integral: {e}") from None
+    src = _source("integral", src)
+    return _into(sum, _gather("integral", _transform.integral, src))
 
 
 def integral2(*args, **kwargs):
@@ -971,66 +899,15 @@ INTER_LINEAR = 1
 WARP_INVERSE_MAP = 16
 
 
-def _device_source(src):
-    """(image, True) for a DeviceMat, which the operator reads where it is; (packed numpy array, False) for everything else."""
-    from vision.devmat import DeviceMat
-    from vision.utils.helpers import as_mat
-    src = as_mat(src)
-    if isinstance(src, DeviceMat):
-        return src, True
-    return np.ascontiguousarray(src), False
-
-
 def warpAffine(src, M, dsize, dst=None, flags=INTER_LINEAR, borderMode=BORDER_CONSTANT, borderValue=0):
     """cv2.warpAffine with bilinear interpolation on uint8 images (modules/preprocessor.py:130-135,145-149): OpenCV's classical
     fixed-point path on the GPU (libvp vp_warp_affine_u8).  Positional order as in cv2: (src, M, dsize, dst, flags, borderMode,
     borderValue)."""
-    return _into(dst, _warp_affine(src, M, dsize, flags, borderMode, borderValue))
-
-
-def _warp_affine(src, M, dsize, flags, borderMode, borderValue):
-    from vision import _vp
-    if flags is None:
-        flags = INTER_LINEAR
-    if (flags & ~WARP_INVERSE_MAP) != INTER_LINEAR:
-        raise error("warpAffine: only INTER_LINEAR is on the accelerated path")
-    if borderMode not in (BORDER_CONSTANT, BORDER_REPLICATE):
-        raise error("warpAffine: only BORDER_CONSTANT and BORDER_REPLICATE are on the accelerated path")
-    src, on_dev = _device_source(src)
-    if src.dtype != np.uint8 or src.ndim not in (2, 3) or src.size == 0:
-        raise error("warpAffine: expected a non-empty uint8 image")
-    cn = 1 if src.ndim == 2 else src.shape[2]
-    m = np.ascontiguousarray(np.asarray(M, dtype=np.float64))
-    dw, dh = int(dsize[0]), int(dsize[1])
-    if m.shape != (2, 3) or dw <= 0 or dh <= 0 or cn > 4:
-        raise error("warpAffine: M must be 2x3 and the size positive")
-    bv = np.zeros(4, np.uint8)
-    vals = np.atleast_1d(np.asarray(borderValue, dtype=np.float64))[:4]
-    bv[:len(vals)] = np.clip(np.rint(vals), 0, 255).astype(np.uint8)
-    ctx = _vp.default_context()
-    if on_dev:                                       # the image stays in HBM (libvp vp_warp_affine_dev)
-        from vision.devmat import DeviceMat
-        src.refresh_device(ctx)
-        out = DeviceMat(ctx, (dh, dw) if src.ndim == 2 else (dh, dw, cn))
-        _vp.check(_vp.lib().vp_warp_affine_dev(ctx.handle, src.dev_ptr, src.shape[1] * cn, src.shape[1], src.shape[0], cn, _vp.ptr(m),
-                                               int(flags & WARP_INVERSE_MAP), int(borderMode), _vp.ptr(bv), out.dev_ptr, dw, dh), ctx.handle)
-        return out
-    out = np.empty((dh, dw) if src.ndim == 2 else (dh, dw, cn), np.uint8)
-    _vp.check(_vp.lib().vp_warp_affine_u8(ctx.handle, _vp.ptr(src), src.shape[1], src.shape[0], cn, _vp.ptr(m), int(flags & WARP_INVERSE_MAP),
-                                          int(borderMode), _vp.ptr(bv), _vp.ptr(out), dw, dh), ctx.handle)
-    return out
+    return _into(dst, _transform._warp_affine(src, M, dsize, flags, borderMode, borderValue))
 
 
 INTER_NEAREST = 0
 CV_16UC1, CV_32FC1, CV_16SC2, CV_32FC2 = 2, 5, 11, 13
-
-
-def _gather(name, call):
-    """what vision.utils.transform refuses (TypeError / ValueError, before anything is launched) is a cv2.error here"""
-    try:
-        return call()
-    except (TypeError, ValueError) as e:
-        raise error(f"{name}: {e}") from None
 
 
 def remap(src, map1, map2, interpolation, dst=None, borderMode=BORDER_CONSTANT, borderValue=0):
@@ -1043,7 +920,7 @@ def remap(src, map1, map2, interpolation, dst=None, borderMode=BORDER_CONSTANT, 
     if borderMode not in (BORDER_CONSTANT, BORDER_REPLICATE):
         raise error("remap: only BORDER_CONSTANT and BORDER_REPLICATE are on the accelerated path")
     src, _ = _device_source(src)
-    return _into(dst, _gather("remap", lambda: _transform._remap(src, map1, map2, interpolation == INTER_NEAREST, borderMode, borderValue)))
+    return _into(dst, _gather("remap", _transform._remap, src, map1, map2, interpolation == INTER_NEAREST, borderMode, borderValue))
 
 
 def warpPerspective(src, M, dsize, dst=None, flags=INTER_LINEAR, borderMode=BORDER_CONSTANT, borderValue=0):
@@ -1060,8 +937,8 @@ def warpPerspective(src, M, dsize, dst=None, flags=INTER_LINEAR, borderMode=BORD
         dw, dh = int(dsize[0]), int(dsize[1])
     except (TypeError, ValueError, IndexError):
         raise error("warpPerspective: dsize must be (width, height)") from None
-    return _into(dst, _gather("warpPerspective", lambda: _transform._warp_perspective(src, M, dw, dh, bool(flags & WARP_INVERSE_MAP),
-                                                                                     (flags & ~WARP_INVERSE_MAP) == INTER_NEAREST, borderMode, borderValue)))
+    return _into(dst, _gather("warpPerspective", _transform._warp_perspective, src, M, dw, dh, bool(flags & WARP_INVERSE_MAP),
+                              (flags & ~WARP_INVERSE_MAP) == INTER_NEAREST, borderMode, borderValue))
 
 
 def convertMaps(map1, map2, dstmap1type, nninterpolation=False):
@@ -1071,11 +948,11 @@ def convertMaps(map1, map2, dstmap1type, nninterpolation=False):
     from vision.devmat import DeviceMat
     if dstmap1type != CV_16SC2:
         raise error("convertMaps: only the conversion to CV_16SC2 is on the accelerated path")
-    kind = _gather("convertMaps", lambda: _transform._classify_maps(map1, map2))[0]
+    kind = _gather("convertMaps", _transform._classify_maps, map1, map2)[0]
     if kind == "fixed":
         raise error("convertMaps: only float32 source maps are on the accelerated path")
     on_dev = any(isinstance(_as(m), DeviceMat) for m in (map1, map2) if m is not None)
-    t = _gather("convertMaps", lambda: _transform.RemapTable(map1, map2, bool(nninterpolation)))
+    t = _gather("convertMaps", _transform.RemapTable, map1, map2, bool(nninterpolation))
     if on_dev:
         return t.xy, (np.empty((0,), np.uint16) if t.frac is None else t.frac)
     return t.xy.host_copy(), (np.empty((0,), np.uint16) if t.frac is None else t.frac.host_copy())
@@ -1086,83 +963,26 @@ def _as(m):
     return as_mat(m)
 
 
-def _camera(name, cameraMatrix, distCoeffs):
-    """(fx, fy, cx, cy), the 8 rational-model coefficients k1 k2 p1 p2 k3 k4 k5 k6 (missing ones 0), in float64"""
-    A = np.asarray(cameraMatrix, dtype=np.float64)
-    if A.shape != (3, 3) or not np.isfinite(A).all():
-        raise error(f"{name}: the camera matrix must be a finite 3x3 matrix")
-    d = np.zeros(0) if distCoeffs is None else np.asarray(distCoeffs, dtype=np.float64).ravel()
-    if d.size not in (0, 4, 5, 8, 12, 14) or not np.isfinite(d).all():
-        raise error(f"{name}: 4, 5, 8, 12 or 14 finite distortion coefficients")
-    if d.size > 8 and np.any(d[8:] != 0):
-        raise error(f"{name}: the thin-prism (s1..s4) and tilt (tauX, tauY) coefficients are outside the path (DESIGN.md section 7)")
-    k = np.zeros(8)
-    k[:min(d.size, 8)] = d[:8]
-    return A, k
-
-
-def _undistort_coords(name, cameraMatrix, distCoeffs, R, newCameraMatrix, size):
-    """source coordinates (u, v), float64 (h, w) each, of every pixel of the undistorted image: the model of
-    cv2.initUndistortRectifyMap evaluated per pixel (cv2 accumulates the row increments instead: not bit-exact)"""
-    A, k = _camera(name, cameraMatrix, distCoeffs)
-    w, h = int(size[0]), int(size[1])
-    if w <= 0 or h <= 0:
-        raise error(f"{name}: the size must be positive")
-    Ar = A if newCameraMatrix is None else np.asarray(newCameraMatrix, dtype=np.float64)
-    if Ar.shape == (3, 4):
-        Ar = Ar[:, :3]
-    Rm = np.eye(3) if R is None else np.asarray(R, dtype=np.float64)
-    if Ar.shape != (3, 3) or Rm.shape != (3, 3) or not np.isfinite(Ar).all() or not np.isfinite(Rm).all():
-        raise error(f"{name}: R and the new camera matrix must be finite 3x3 matrices")
-    try:
-        ir = np.linalg.inv(Ar @ Rm)
-    except np.linalg.LinAlgError:
-        raise error(f"{name}: newCameraMatrix * R is singular") from None
-    j, i = np.meshgrid(np.arange(w, dtype=np.float64), np.arange(h, dtype=np.float64))
-    X = ir[0, 0] * j + ir[0, 1] * i + ir[0, 2]
-    Y = ir[1, 0] * j + ir[1, 1] * i + ir[1, 2]
-    W = ir[2, 0] * j + ir[2, 1] * i + ir[2, 2]
-    x, y = X / W, Y / W
-    k1, k2, p1, p2, k3, k4, k5, k6 = k
-    x2, y2 = x * x, y * y
-    r2, xy2 = x2 + y2, 2 * x * y
-    kr = (1 + ((k3 * r2 + k2) * r2 + k1) * r2) / (1 + ((k6 * r2 + k5) * r2 + k4) * r2)
-    xd = x * kr + p1 * xy2 + p2 * (r2 + 2 * x2)
-    yd = y * kr + p1 * (r2 + 2 * y2) + p2 * xy2
-    return A[0, 0] * xd + A[0, 2], A[1, 1] * yd + A[1, 2]
-
-
-def _fixed_from_double(u, v):
-    """CV_16SC2 maps from double coordinates: iu = saturate_cast<int>(u * 32), integer part iu >> 5, fraction index from iu & 31.
-    The integer part is saturated to int16 here; cv2 casts it to short without saturating, so the two differ beyond +-32768."""
-    iu = np.clip(np.rint(u * 32), -2147483648, 2147483647).astype(np.int64)
-    iv = np.clip(np.rint(v * 32), -2147483648, 2147483647).astype(np.int64)
-    xy = np.stack([np.clip(iu >> 5, -32768, 32767), np.clip(iv >> 5, -32768, 32767)], axis=-1).astype(np.int16)
-    return np.ascontiguousarray(xy), ((iv & 31) * 32 + (iu & 31)).astype(np.uint16)
-
-
 def initUndistortRectifyMap(cameraMatrix, distCoeffs, R, newCameraMatrix, size, m1type):
     """cv2.initUndistortRectifyMap for the rational model without thin-prism and tilt terms (4, 5 or 8 coefficients), host numpy in
     float64: run once per calibration.  m1type CV_32FC1 -> (mapx, mapy), CV_32FC2 -> (interleaved map, empty), CV_16SC2 -> the fixed
     form.  Within an ulp of float32 of cv2's maps, not bit for bit."""
     if m1type not in (CV_32FC1, CV_32FC2, CV_16SC2):
         raise error("initUndistortRectifyMap: m1type must be CV_32FC1, CV_32FC2 or CV_16SC2")
-    u, v = _undistort_coords("initUndistortRectifyMap", cameraMatrix, distCoeffs, R, newCameraMatrix, size)
+    u, v = _transform._undistort_coords("initUndistortRectifyMap", cameraMatrix, distCoeffs, R, newCameraMatrix, size)
     if m1type == CV_32FC1:
         return u.astype(np.float32), v.astype(np.float32)
     if m1type == CV_32FC2:
         return np.ascontiguousarray(np.stack([u, v], axis=-1).astype(np.float32)), np.empty((0,), np.float32)
-    return _fixed_from_double(u, v)
+    return _transform._fixed_from_double(u, v)
 
 
 def undistort(src, cameraMatrix, distCoeffs, dst=None, newCameraMatrix=None):
     """cv2.undistort: initUndistortRectifyMap(R = identity, CV_16SC2) of the image's size, then remap(INTER_LINEAR,
     BORDER_CONSTANT 0) on the GPU.  For a stream of frames build the table once: vision.utils.transform.undistorter."""
-    src, _ = _device_source(src)
-    if src.dtype != np.uint8 or src.ndim not in (2, 3) or src.size == 0:
-        raise error("undistort: expected a non-empty uint8 image")
+    src, _ = _transform._plain_source("undistort", src, "expected a non-empty uint8 image")
     xy, frac = initUndistortRectifyMap(cameraMatrix, distCoeffs, None, newCameraMatrix, (src.shape[1], src.shape[0]), CV_16SC2)
-    return _into(dst, _gather("undistort", lambda: _transform._remap(src, xy, frac, False, BORDER_CONSTANT, 0)))
+    return _into(dst, _gather("undistort", _transform._remap, src, xy, frac, False, BORDER_CONSTANT, 0))
 
 
 def getPerspectiveTransform(src, dst, solveMethod=0):
@@ -1203,42 +1023,7 @@ def perspectiveTransform(src, m, dst=None):
 def resize(src, dsize, dst=None, fx=None, fy=None, interpolation=INTER_LINEAR):
     """cv2.resize(src, (width, height)) with the default bilinear interpolation, uint8 images (modules/preprocessor.py:136-144).
     Positional order as in cv2: (src, dsize, dst, fx, fy, interpolation); dsize None or (0, 0) takes the size from fx / fy."""
-    from vision import _vp
-    if interpolation != INTER_LINEAR:
-        raise error("resize: only INTER_LINEAR is on the accelerated path")
-    src, on_dev = _device_source(src)
-    scaled = dsize is None or tuple(dsize) == (0, 0)
-    if scaled:
-        if not fx or not fy or not (fx > 0 and fy > 0):
-            raise error("resize: dsize or both fx and fy (positive) are needed")
-        fx, fy = float(fx), float(fy)                # cv2 keeps them as the inverse scales: the tables use 1 / fx, not size / dsize
-        dsize = (int(round(src.shape[1] * fx)), int(round(src.shape[0] * fy)))   # cv2: saturate_cast<int>(cols * fx): round half to even
-    # (cv2 ignores fx / fy when dsize is given)
-    if src.dtype != np.uint8 or src.ndim not in (2, 3) or src.size == 0:
-        raise error("resize: expected a non-empty uint8 image")
-    cn = 1 if src.ndim == 2 else src.shape[2]
-    dw, dh = int(dsize[0]), int(dsize[1])
-    if dw <= 0 or dh <= 0 or cn > 4:
-        raise error("resize: bad size")
-    ctx = _vp.default_context()
-    lib = _vp.lib()
-    if on_dev:
-        from vision.devmat import DeviceMat
-        out = DeviceMat(ctx, (dh, dw) if src.ndim == 2 else (dh, dw, cn))
-    else:
-        out = np.empty((dh, dw) if src.ndim == 2 else (dh, dw, cn), np.uint8)
-    try:
-        if on_dev:                                   # the image stays in HBM (libvp vp_resize_dev; scales <= 0: dsize / ssize)
-            src.refresh_device(ctx)
-            _vp.check(lib.vp_resize_dev(ctx.handle, src.dev_ptr, src.shape[1] * cn, src.shape[1], src.shape[0], cn, dw, dh, fx if scaled else 0.0,
-                                        fy if scaled else 0.0, out.dev_ptr), ctx.handle)
-        elif scaled:
-            _vp.check(lib.vp_resize_u8_scaled(ctx.handle, _vp.ptr(src), src.shape[1], src.shape[0], cn, dw, dh, fx, fy, _vp.ptr(out)), ctx.handle)
-        else:
-            _vp.check(lib.vp_resize_u8(ctx.handle, _vp.ptr(src), src.shape[1], src.shape[0], cn, dw, dh, _vp.ptr(out)), ctx.handle)
-    except _vp.VpError as e:                         # scale 2 with a partial edge cell: not reproduced
-        raise error(f"resize: {e}") from e
-    return _into(dst, out)
+    return _into(dst, _transform._resize(src, dsize, fx, fy, interpolation))
 
 
 def Canny(image, threshold1, threshold2, apertureSize=3, L2gradient=False):

@@ -12,7 +12,7 @@ import numpy as np
 
 from vision import _vp
 from vision.devmat import DeviceMat, finish_uploads, lazy_enabled, to_host
-from vision.utils.helpers import as_mat, device_image
+from vision.utils.helpers import as_mat, device_image, run_operator
 
 
 def _u8_image(mat, channels):
@@ -412,32 +412,30 @@ def adaptive_threshold_gaussian_inv(mat: np.ndarray, neighborhood_size: int, bia
     return _adaptive_gaussian(mat, neighborhood_size, bias, 1)
 
 
-def _grey_operator(mat, host_call, dev_call):
-    """A uint8 (h, w) image through a host / device pair of libvp, as otsu_threshold and median_blur go: numpy in gives numpy out; a
-    DeviceMat gives a DeviceMat (not a mask) that stays in HBM.  host_call(ctx, src_ptr, w, h, dst_ptr), dev_call(ctx, src_ptr, stride, w,
-    h, dst_ptr)."""
+def _grey_source(mat):
+    """The checked uint8 (h, w) source of equalize_hist and clahe, numpy or DeviceMat ((h, w, 1) comes back as (h, w)), in the words of
+    _u8_image and device_image."""
     mat = as_mat(mat)
-    ctx = _vp.default_context()
-    if isinstance(mat, DeviceMat):
-        if mat.dtype != np.uint8:
-            raise TypeError("expected a uint8 numpy image")
-        src = device_image(ctx, mat, 1)
-        h, w = src.shape
-        dst = DeviceMat(ctx, (h, w), binary=False)
-        _vp.check(dev_call(ctx.handle, src.dev_ptr, w, w, h, dst.dev_ptr), ctx.handle)
-        return dst
-    mat = np.ascontiguousarray(_u8_image(mat, 1))
-    out = np.empty_like(mat)
-    _vp.check(host_call(ctx.handle, _vp.ptr(mat), mat.shape[1], mat.shape[0], _vp.ptr(out)), ctx.handle)
-    return out
+    if not isinstance(mat, (np.ndarray, DeviceMat)) or mat.dtype != np.uint8:
+        raise TypeError("expected a uint8 numpy image")
+    if mat.ndim == 3 and mat.shape[2] == 1:
+        mat = mat.reshaped(mat.shape[:2]) if isinstance(mat, DeviceMat) else mat[:, :, 0]
+    if mat.ndim != 2:
+        raise ValueError("expected an (h, w) image")
+    if mat.shape[0] == 0 or mat.shape[1] == 0:
+        raise ValueError("empty image")
+    return mat
 
 
 def equalize_hist(mat: np.ndarray) -> np.ndarray:
     """cv2.equalizeHist on a uint8 (h, w) image (libvp vp_equalize_hist_u8 / _dev).  An addition to the mirror, not a name of the
     reference's utils/color.py: the global contrast step.  Integer histogram, one float32 multiply per table entry, a table: byte for
     byte OpenCV's result.  numpy in gives numpy out; a DeviceMat gives a DeviceMat and stays in HBM (three launches, no wait)."""
+    mat = _grey_source(mat)
+    h, w = mat.shape
     lib = _vp.lib()
-    return _grey_operator(mat, lib.vp_equalize_hist_u8, lib.vp_equalize_hist_dev)
+    return run_operator(mat, (h, w), np.uint8, lambda ctx, s, d: lib.vp_equalize_hist_u8(ctx.handle, s, w, h, d),
+                        lambda ctx, s, d: lib.vp_equalize_hist_dev(ctx.handle, s, w, w, h, d))
 
 
 def _clahe_params(clip_limit, tile_grid):
@@ -456,9 +454,11 @@ def clahe(mat: np.ndarray, clip_limit: float = 2.0, tile_grid=(8, 8)) -> np.ndar
     frames.  tile_grid is (tiles_x, tiles_y) as in cv2, up to 64 each.  Byte for byte OpenCV's result, including its padding of images
     that the grid does not divide.  numpy in gives numpy out; a DeviceMat gives a DeviceMat and stays in HBM."""
     clip, tx, ty = _clahe_params(clip_limit, tile_grid)
+    mat = _grey_source(mat)
+    h, w = mat.shape
     lib = _vp.lib()
-    return _grey_operator(mat, lambda c, s, w, h, d: lib.vp_clahe_u8(c, s, w, h, clip, tx, ty, d),
-                          lambda c, s, st, w, h, d: lib.vp_clahe_dev(c, s, st, w, h, clip, tx, ty, d))
+    return run_operator(mat, (h, w), np.uint8, lambda ctx, s, d: lib.vp_clahe_u8(ctx.handle, s, w, h, clip, tx, ty, d),
+                        lambda ctx, s, d: lib.vp_clahe_dev(ctx.handle, s, w, w, h, clip, tx, ty, d))
 
 
 def clahe_bgr(mat: np.ndarray, clip_limit: float = 2.0, tile_grid=(8, 8)) -> np.ndarray:

@@ -9,8 +9,8 @@ from typing import Optional
 import numpy as np
 
 from vision import _vp
-from vision.devmat import DeviceMat, defer_enabled, lazy_enabled
-from vision.utils.helpers import as_mat, device_image
+from vision.devmat import DeviceMat, _DevBuf, defer_enabled, finish_uploads, lazy_enabled
+from vision.utils.helpers import as_cv2_error, as_mat, device_image, error, image_source, packed_source, run_operator
 
 
 def _structuring_element(shape, x, y):
@@ -103,17 +103,67 @@ def morph_borders(mat: np.ndarray, kernel: np.ndarray, iterations: int = 1) -> n
 
 def resize(mat: np.ndarray, width: int, height: int) -> np.ndarray:
     """utils/transform.py:167-179 (cv2.resize, default bilinear interpolation) on the GPU (libvp vp_resize_u8)."""
-    from vision import cv2_facade
-    return cv2_facade.resize(mat, (width, height))
+    return _resize(mat, (width, height))
 
+
+def _plain_source(name, src, words):
+    """The source of the operators that came with cv2's names and refuse in cv2's way (cv2.error, one sentence for a wrong dtype, a
+    wrong shape and no pixels; more than 4 channels is refused with the operator's sizes)."""
+    return as_cv2_error(name, image_source, packed_source(src)[0], said=(words, words, None))
+
+
+def _resize(src, dsize, fx=None, fy=None, interpolation=_vp.INTER_LINEAR):
+    """cv2.resize without dst (libvp vp_resize_u8 / vp_resize_u8_scaled / vp_resize_dev); dsize None or (0, 0) takes the size from fx / fy."""
+    if interpolation != _vp.INTER_LINEAR:
+        raise error("resize: only INTER_LINEAR is on the accelerated path")
+    src, _ = packed_source(src)
+    scaled = dsize is None or tuple(dsize) == (0, 0)
+    if scaled:
+        if not fx or not fy or not (fx > 0 and fy > 0):
+            raise error("resize: dsize or both fx and fy (positive) are needed")
+        fx, fy = float(fx), float(fy)                # cv2 keeps them as the inverse scales: the tables use 1 / fx, not size / dsize
+        dsize = (int(round(src.shape[1] * fx)), int(round(src.shape[0] * fy)))   # cv2: saturate_cast<int>(cols * fx): round half to even
+    # (cv2 ignores fx / fy when dsize is given)
+    src, cn = _plain_source("resize", src, "expected a non-empty uint8 image")
+    dw, dh = int(dsize[0]), int(dsize[1])
+    if dw <= 0 or dh <= 0 or cn > 4:
+        raise error("resize: bad size")
+    h, w = src.shape[:2]
+    lib = _vp.lib()
+    sx, sy = (fx, fy) if scaled else (0.0, 0.0)      # the device entry takes scales <= 0 as dsize / ssize
+
+    def host_call(ctx, s, d):
+        if scaled:
+            return lib.vp_resize_u8_scaled(ctx.handle, s, w, h, cn, dw, dh, fx, fy, d)
+        return lib.vp_resize_u8(ctx.handle, s, w, h, cn, dw, dh, d)
+    try:
+        return run_operator(src, (dh, dw) + tuple(src.shape[2:]), np.uint8, host_call,
+                            lambda ctx, s, d: lib.vp_resize_dev(ctx.handle, s, w * cn, w, h, cn, dw, dh, sx, sy, d))
+    except _vp.VpError as e:                         # scale 2 with a partial edge cell: not reproduced
+        raise error(f"resize: {e}") from e
+
+
+def _gaussian_blur(src, ksize, sigma_x, sigma_y=0, border=None):
+    """cv2.GaussianBlur without dst: OpenCV's bit-exact fixed-point path (libvp vp_gaussian_blur_u8 / vp_gaussian_blur_dev)."""
+    if border not in (None, _vp.BORDER_REFLECT_101):
+        raise error("GaussianBlur: only BORDER_DEFAULT (reflect 101) is on the accelerated path")
+    src, cn = _plain_source("GaussianBlur", src, "only non-empty uint8 images are on the accelerated path")
+    kw, kh = int(ksize[0]), int(ksize[1])
+    if kw <= 0 or kh <= 0 or kw % 2 == 0 or kh % 2 == 0 or kw > 511 or kh > 511 or cn > 4:
+        raise error("GaussianBlur: kernel sizes must be odd, 1..511")
+    h, w = src.shape[:2]
+    sx, sy = float(sigma_x), float(sigma_y)
+    lib = _vp.lib()
+    return run_operator(src, src.shape, np.uint8,
+                        lambda ctx, s, d: lib.vp_gaussian_blur_u8(ctx.handle, s, w, h, cn, kw, kh, sx, sy, d),
+                        lambda ctx, s, d: lib.vp_gaussian_blur_dev(ctx.handle, s, w * cn, w, h, cn, kw, kh, sx, sy, d))
 
 
 def simple_gaussian_blur(mat: np.ndarray, kernel_size: int, std_dev: float) -> np.ndarray:
     """utils/transform.py:3-25 (cv2.GaussianBlur with a square kernel); ValueError for an even kernel size as in the reference."""
     if kernel_size % 2 == 0:
         raise ValueError("kernel_size must be an odd integer")
-    from vision import cv2_facade
-    return cv2_facade.GaussianBlur(mat, (kernel_size, kernel_size), std_dev)
+    return _gaussian_blur(mat, (kernel_size, kernel_size), std_dev)
 
 
 def median_blur(mat: np.ndarray, ksize: int) -> np.ndarray:
@@ -122,57 +172,37 @@ def median_blur(mat: np.ndarray, ksize: int) -> np.ndarray:
     (OPEN 5x5 eats them).  numpy in gives numpy out; a DeviceMat gives a DeviceMat and stays in HBM.  On a mask this library made
     (`binary`) the filter is a majority vote on the mask's bit plane, the result is a mask again and brings its own bit plane where
     rows are whole words, so range_threshold -> median_blur -> connected_components / find_contours never unpacks a bit."""
-    mat = as_mat(mat)
-    if not isinstance(mat, (np.ndarray, DeviceMat)) or mat.dtype != np.uint8 or mat.ndim not in (2, 3) or mat.size == 0:
-        raise TypeError("expected a non-empty uint8 (h, w) or (h, w, c) image")
-    cn = 1 if mat.ndim == 2 else mat.shape[2]
-    if cn > 4:
-        raise ValueError("at most 4 channels")
+    mat, cn = image_source(mat)
     ksize = int(ksize)
     if ksize <= 0 or ksize % 2 == 0 or ksize > 255:
         raise ValueError("ksize must be an odd integer in 1..255")
-    ctx = _vp.default_context()
     h, w = mat.shape[:2]
-    if isinstance(mat, DeviceMat):
-        from vision.devmat import _DevBuf
-        mat.refresh_device(ctx)
-        src_ptr = mat.dev_ptr                            # (launches a deferred source: its bit plane comes out of that launch)
-        binary = mat.binary                              # the median of 0 / 255 values is 0 or 255, whatever the channels and the window
-        vote = binary and cn == 1 and 3 <= ksize <= 63   # what the bit-plane kernel serves: only then is a plane of use (the hint is ignored elsewhere)
-        plane = mat.bit_plane(ctx) if (vote and mat.ndim == 2) else None
-        out = DeviceMat(ctx, mat.shape, binary=binary)
-        bits = _DevBuf(ctx, h * (w // 64) * 8) if (vote and mat.ndim == 2 and w % 64 == 0) else None
-        made = _vp.C.c_int(0)
-        _vp.check(_vp.lib().vp_median_blur_dev(ctx.handle, src_ptr, w * cn, w, h, cn, ksize, 1 if binary else 0, None if plane is None else plane.ptr,
-                                               out.dev_ptr, None if bits is None else bits.ptr, _vp.C.byref(made)), ctx.handle)
-        if made.value:
-            out._bits = bits
-        return out
-    src = np.ascontiguousarray(mat)
-    out = np.empty_like(src)
-    _vp.check(_vp.lib().vp_median_blur_u8(ctx.handle, _vp.ptr(src), w, h, cn, ksize, _vp.ptr(out)), ctx.handle)
+    lib = _vp.lib()
+    binary = isinstance(mat, DeviceMat) and mat.binary   # the median of 0 / 255 values is 0 or 255, whatever the channels and the window
+    vote = binary and mat.ndim == 2 and 3 <= ksize <= 63   # what the bit-plane kernel serves: only then is a plane of use (the hint is ignored elsewhere)
+    made, bits = _vp.C.c_int(0), None
+
+    def dev_call(ctx, s, d):                             # (the source has been launched by now: its bit plane comes out of that launch)
+        nonlocal bits
+        plane = mat.bit_plane(ctx) if vote else None
+        bits = _DevBuf(ctx, h * (w // 64) * 8) if (vote and w % 64 == 0) else None
+        return lib.vp_median_blur_dev(ctx.handle, s, w * cn, w, h, cn, ksize, 1 if binary else 0, None if plane is None else plane.ptr, d,
+                                      None if bits is None else bits.ptr, _vp.C.byref(made))
+    out = run_operator(mat, mat.shape, np.uint8, lambda ctx, s, d: lib.vp_median_blur_u8(ctx.handle, s, w, h, cn, ksize, d), dev_call, binary)
+    if made.value:
+        out._bits = bits
     return out
 
 
 _DEPTH_DTYPE = {_vp.DEPTH_8U: np.uint8, _vp.DEPTH_16S: np.int16, _vp.DEPTH_32F: np.float32, _vp.DEPTH_64F: np.float64}
+_DTYPE_DEPTH = {np.dtype(v): k for k, v in _DEPTH_DTYPE.items()}
 _BORDERS = (_vp.BORDER_CONSTANT, _vp.BORDER_REPLICATE, _vp.BORDER_REFLECT, _vp.BORDER_REFLECT_101)
-
-
-def _deriv_source(mat):
-    """The checked source of a derivative filter: uint8, (h, w) or (h, w, 1..4), not empty; and its channel count."""
-    mat = as_mat(mat)
-    if not isinstance(mat, (np.ndarray, DeviceMat)) or mat.dtype != np.uint8 or mat.ndim not in (2, 3) or mat.size == 0:
-        raise TypeError("expected a non-empty uint8 (h, w) or (h, w, c) image")
-    cn = 1 if mat.ndim == 2 else mat.shape[2]
-    if cn > 4:
-        raise ValueError("at most 4 channels")
-    return mat, cn
 
 
 def _deriv(mat, op, dx, dy, ksize, ddepth, border):
     """libvp vp_deriv_u8 / vp_deriv_dev: numpy in gives numpy out, a DeviceMat gives a DeviceMat of the requested dtype and stays in HBM.
     What the library refuses (orders, kernel sizes, depths, borders) comes back as ValueError before anything is launched."""
-    mat, cn = _deriv_source(mat)
+    mat, cn = image_source(mat)
     dx, dy, ksize, ddepth, border = int(dx), int(dy), int(ksize), int(ddepth), int(border) & ~_vp.BORDER_ISOLATED
     depth = _vp.DEPTH_8U if ddepth == -1 else ddepth
     if depth not in _DEPTH_DTYPE:
@@ -193,18 +223,11 @@ def _deriv(mat, op, dx, dy, ksize, ddepth, border):
             raise ValueError("the derivative order must be below ksize")
     elif ksize not in (1, 3, 5, 7):
         raise ValueError("ksize must be 1, 3, 5 or 7")
-    ctx = _vp.default_context()
     h, w = mat.shape[:2]
-    dtype = _DEPTH_DTYPE[depth]
-    if isinstance(mat, DeviceMat):
-        mat.refresh_device(ctx)
-        out = DeviceMat(ctx, mat.shape, dtype)
-        _vp.check(_vp.lib().vp_deriv_dev(ctx.handle, mat.dev_ptr, w * cn, w, h, cn, op, dx, dy, ksize, depth, border, out.dev_ptr), ctx.handle)
-        return out
-    src = np.ascontiguousarray(mat)
-    out = np.empty(src.shape, dtype)
-    _vp.check(_vp.lib().vp_deriv_u8(ctx.handle, _vp.ptr(src), w, h, cn, op, dx, dy, ksize, depth, border, _vp.ptr(out)), ctx.handle)
-    return out
+    lib = _vp.lib()
+    return run_operator(mat, mat.shape, _DEPTH_DTYPE[depth],
+                        lambda ctx, s, d: lib.vp_deriv_u8(ctx.handle, s, w, h, cn, op, dx, dy, ksize, depth, border, d),
+                        lambda ctx, s, d: lib.vp_deriv_dev(ctx.handle, s, w * cn, w, h, cn, op, dx, dy, ksize, depth, border, d))
 
 
 def sobel(mat: np.ndarray, dx: int, dy: int, ksize: int = 3, ddepth: int = _vp.DEPTH_16S, border: int = _vp.BORDER_REFLECT_101) -> np.ndarray:
@@ -227,48 +250,29 @@ def laplacian(mat: np.ndarray, ksize: int = 1, ddepth: int = _vp.DEPTH_16S, bord
 def spatial_gradient(mat: np.ndarray, ksize: int = 3, border: int = _vp.BORDER_REFLECT_101):
     """cv2.spatialGradient: (Sobel(1, 0, 3), Sobel(0, 1, 3)) of a single-channel uint8 image, both int16, from one pass over the
     source (libvp vp_spatial_gradient_*).  ksize 3 and BORDER_REFLECT_101 or BORDER_REPLICATE only, as cv2."""
-    mat, cn = _deriv_source(mat)
-    if mat.ndim == 3 and cn == 1:
-        mat = mat.reshaped(mat.shape[:2]) if isinstance(mat, DeviceMat) else mat[:, :, 0]
-    if mat.ndim != 2:
-        raise ValueError("spatial_gradient takes a single-channel image")
+    mat, _ = image_source(mat, single="spatial_gradient takes a single-channel image")
     ksize, border = int(ksize), int(border) & ~_vp.BORDER_ISOLATED
     if ksize != 3:
         raise ValueError("ksize must be 3")
     if border not in (_vp.BORDER_REFLECT_101, _vp.BORDER_REPLICATE):
         raise ValueError("the border must be BORDER_DEFAULT or BORDER_REPLICATE")
-    ctx = _vp.default_context()
     h, w = mat.shape
-    if isinstance(mat, DeviceMat):
-        mat.refresh_device(ctx)
-        gx, gy = DeviceMat(ctx, (h, w), np.int16), DeviceMat(ctx, (h, w), np.int16)
-        _vp.check(_vp.lib().vp_spatial_gradient_dev(ctx.handle, mat.dev_ptr, w, w, h, ksize, border, gx.dev_ptr, gy.dev_ptr), ctx.handle)
-        return gx, gy
-    src = np.ascontiguousarray(mat)
-    gx, gy = np.empty((h, w), np.int16), np.empty((h, w), np.int16)
-    _vp.check(_vp.lib().vp_spatial_gradient_u8(ctx.handle, _vp.ptr(src), w, h, ksize, border, _vp.ptr(gx), _vp.ptr(gy)), ctx.handle)
-    return gx, gy
+    lib = _vp.lib()
+    return run_operator(mat, (h, w), np.int16,
+                        lambda ctx, s, gx, gy: lib.vp_spatial_gradient_u8(ctx.handle, s, w, h, ksize, border, gx, gy),
+                        lambda ctx, s, gx, gy: lib.vp_spatial_gradient_dev(ctx.handle, s, w, w, h, ksize, border, gx, gy), pair=True)
 
 
 def convert_scale_abs(mat: np.ndarray) -> np.ndarray:
     """cv2.convertScaleAbs with alpha 1 and beta 0: saturate_cast<uchar>(|v|) of a uint8, int16, float32 or float64 image (a float is
     rounded half to even first).  numpy in gives numpy out; a DeviceMat (a derivative that stayed in HBM) gives a uint8 DeviceMat."""
-    mat = as_mat(mat)
-    depth = {np.dtype(v): k for k, v in _DEPTH_DTYPE.items()}.get(np.dtype(mat.dtype)) if isinstance(mat, (np.ndarray, DeviceMat)) else None
-    if depth is None or mat.ndim not in (2, 3) or mat.size == 0:
-        raise TypeError("expected a non-empty uint8, int16, float32 or float64 (h, w) or (h, w, c) image")
-    if mat.ndim == 3 and mat.shape[2] > 4:
-        raise ValueError("at most 4 channels")
-    ctx = _vp.default_context()
-    if isinstance(mat, DeviceMat):
-        mat.refresh_device(ctx)
-        out = DeviceMat(ctx, mat.shape)
-        _vp.check(_vp.lib().vp_convert_scale_abs_dev(ctx.handle, mat.dev_ptr, depth, mat.size, out.dev_ptr), ctx.handle)
-        return out
-    src = np.ascontiguousarray(mat)
-    out = np.empty(src.shape, np.uint8)
-    _vp.check(_vp.lib().vp_convert_scale_abs_u8(ctx.handle, _vp.ptr(src), depth, src.size, _vp.ptr(out)), ctx.handle)
-    return out
+    mat, _ = image_source(mat, dtypes=_DTYPE_DEPTH)
+    depth = _DTYPE_DEPTH[mat.dtype]
+    n = mat.size
+    lib = _vp.lib()
+    return run_operator(mat, mat.shape, np.uint8,
+                        lambda ctx, s, d: lib.vp_convert_scale_abs_u8(ctx.handle, s, depth, n, d),
+                        lambda ctx, s, d: lib.vp_convert_scale_abs_dev(ctx.handle, s, depth, n, d))
 
 
 _BOX_DTYPE = {_vp.DEPTH_8U: np.uint8, _vp.DEPTH_16S: np.int16, _vp.DEPTH_32S: np.int32, _vp.DEPTH_32F: np.float32, _vp.DEPTH_64F: np.float64}
@@ -281,7 +285,7 @@ def box_filter(mat: np.ndarray, kx: int, ky: Optional[int] = None, ddepth: int =
     (uint8 only) it is sum / area rounded as OpenCV rounds, for the areas on which OpenCV's own roundings agree - the others raise
     ValueError before anything is launched.  numpy in gives numpy out; a DeviceMat gives a DeviceMat of the result's dtype, without
     the source's mask flag and bit plane: the result is no mask."""
-    mat, cn = _deriv_source(mat)
+    mat, cn = image_source(mat)
     kx = int(kx)
     ky = kx if ky is None else int(ky)
     ddepth, border, normalize = int(ddepth), int(border) & ~_vp.BORDER_ISOLATED, bool(normalize)
@@ -299,18 +303,11 @@ def box_filter(mat: np.ndarray, kx: int, ky: Optional[int] = None, ddepth: int =
             raise ValueError("OpenCV's roundings of sum / area disagree for a window of %d pixels: it cannot be restated" % (kx * ky))
     elif depth == _vp.DEPTH_32F and 255 * kx * ky >= 1 << 24:
         raise ValueError("the window's sum may not be exact in float32: ask for CV_32S or CV_64F")
-    ctx = _vp.default_context()
     h, w = mat.shape[:2]
-    dtype = _BOX_DTYPE[depth]
-    if isinstance(mat, DeviceMat):
-        mat.refresh_device(ctx)
-        out = DeviceMat(ctx, mat.shape, dtype)
-        _vp.check(_vp.lib().vp_box_filter_dev(ctx.handle, mat.dev_ptr, w * cn, w, h, cn, kx, ky, int(normalize), depth, border, out.dev_ptr), ctx.handle)
-        return out
-    src = np.ascontiguousarray(mat)
-    out = np.empty(src.shape, dtype)
-    _vp.check(_vp.lib().vp_box_filter_u8(ctx.handle, _vp.ptr(src), w, h, cn, kx, ky, int(normalize), depth, border, _vp.ptr(out)), ctx.handle)
-    return out
+    lib = _vp.lib()
+    return run_operator(mat, mat.shape, _BOX_DTYPE[depth],
+                        lambda ctx, s, d: lib.vp_box_filter_u8(ctx.handle, s, w, h, cn, kx, ky, int(normalize), depth, border, d),
+                        lambda ctx, s, d: lib.vp_box_filter_dev(ctx.handle, s, w * cn, w, h, cn, kx, ky, int(normalize), depth, border, d))
 
 
 def box_blur(mat: np.ndarray, kx: int, ky: Optional[int] = None) -> np.ndarray:
@@ -319,7 +316,7 @@ def box_blur(mat: np.ndarray, kx: int, ky: Optional[int] = None) -> np.ndarray:
 
 
 def _pyr(mat, down, border):
-    mat, cn = _deriv_source(mat)
+    mat, cn = image_source(mat)
     border = int(border) & ~_vp.BORDER_ISOLATED
     if down and border not in (_vp.BORDER_REFLECT_101, _vp.BORDER_REPLICATE, _vp.BORDER_REFLECT):
         raise ValueError("pyrDown takes BORDER_REFLECT_101, BORDER_REPLICATE or BORDER_REFLECT")
@@ -330,21 +327,12 @@ def _pyr(mat, down, border):
         raise ValueError("at most 32767 rows")
     oh, ow = ((h + 1) // 2, (w + 1) // 2) if down else (2 * h, 2 * w)
     shape = (oh, ow) + tuple(mat.shape[2:])
-    ctx = _vp.default_context()
     L = _vp.lib()
-    if isinstance(mat, DeviceMat):
-        mat.refresh_device(ctx)
-        out = DeviceMat(ctx, shape)
-        rc = (L.vp_pyr_down_dev(ctx.handle, mat.dev_ptr, w * cn, w, h, cn, border, out.dev_ptr) if down
-              else L.vp_pyr_up_dev(ctx.handle, mat.dev_ptr, w * cn, w, h, cn, out.dev_ptr))
-        _vp.check(rc, ctx.handle)
-        return out
-    src = np.ascontiguousarray(mat)
-    out = np.empty(shape, np.uint8)
-    rc = (L.vp_pyr_down_u8(ctx.handle, _vp.ptr(src), w, h, cn, border, _vp.ptr(out)) if down
-          else L.vp_pyr_up_u8(ctx.handle, _vp.ptr(src), w, h, cn, _vp.ptr(out)))
-    _vp.check(rc, ctx.handle)
-    return out
+    if down:
+        return run_operator(mat, shape, np.uint8, lambda ctx, s, d: L.vp_pyr_down_u8(ctx.handle, s, w, h, cn, border, d),
+                            lambda ctx, s, d: L.vp_pyr_down_dev(ctx.handle, s, w * cn, w, h, cn, border, d))
+    return run_operator(mat, shape, np.uint8, lambda ctx, s, d: L.vp_pyr_up_u8(ctx.handle, s, w, h, cn, d),
+                        lambda ctx, s, d: L.vp_pyr_up_dev(ctx.handle, s, w * cn, w, h, cn, d))
 
 
 def pyr_down(mat: np.ndarray, border: int = _vp.BORDER_REFLECT_101) -> np.ndarray:
@@ -364,7 +352,7 @@ def build_pyramid(mat: np.ndarray, levels: int) -> list:
     levels = int(levels)
     if levels < 0:
         raise ValueError("levels must not be negative")
-    src, _ = _deriv_source(mat)
+    src, _ = image_source(mat)
     if isinstance(src, DeviceMat):
         out = [src]
         for _ in range(levels):
@@ -380,21 +368,14 @@ def build_pyramid(mat: np.ndarray, levels: int) -> list:
 def integral(mat: np.ndarray) -> np.ndarray:
     """cv2.integral on uint8 images of 1..4 channels: the (h + 1, w + 1[, cn]) int32 image of sums above and left of every pixel
     (libvp vp_integral_*); 255 * w * h must fit int32.  numpy in gives numpy out; a DeviceMat gives an int32 DeviceMat."""
-    mat, cn = _deriv_source(mat)
+    mat, cn = image_source(mat)
     h, w = mat.shape[:2]
     if 255 * w * h > 2 ** 31 - 1:
         raise ValueError("255 * w * h does not fit the int32 sums")
     shape = (h + 1, w + 1) + tuple(mat.shape[2:])
-    ctx = _vp.default_context()
-    if isinstance(mat, DeviceMat):
-        mat.refresh_device(ctx)
-        out = DeviceMat(ctx, shape, np.int32)
-        _vp.check(_vp.lib().vp_integral_dev(ctx.handle, mat.dev_ptr, w * cn, w, h, cn, out.dev_ptr), ctx.handle)
-        return out
-    src = np.ascontiguousarray(mat)
-    out = np.empty(shape, np.int32)
-    _vp.check(_vp.lib().vp_integral_u8(ctx.handle, _vp.ptr(src), w, h, cn, _vp.ptr(out)), ctx.handle)
-    return out
+    lib = _vp.lib()
+    return run_operator(mat, shape, np.int32, lambda ctx, s, d: lib.vp_integral_u8(ctx.handle, s, w, h, cn, d),
+                        lambda ctx, s, d: lib.vp_integral_dev(ctx.handle, s, w * cn, w, h, cn, d))
 
 
 def _border_bytes(value):
@@ -406,9 +387,7 @@ def _border_bytes(value):
 
 
 def _gather_checks(mat, border):
-    mat, cn = _deriv_source(mat)
-    if mat.shape[0] > 32767 or mat.shape[1] > 32767:
-        raise ValueError("the source must be at most 32767 x 32767, as cv2 asserts")
+    mat, cn = image_source(mat, max_side=32767)
     if int(border) not in (_vp.BORDER_CONSTANT, _vp.BORDER_REPLICATE):
         raise ValueError("only BORDER_CONSTANT and BORDER_REPLICATE are on the accelerated path")
     return mat, cn
@@ -446,7 +425,6 @@ def _map_on_device(ctx, m, pending):
 def _remap(mat, map1, map2, nearest, border=_vp.BORDER_CONSTANT, border_value=0):
     """libvp vp_remap_u8 / vp_remap_f32_dev / vp_remap_fixed_dev.  A DeviceMat source gives a DeviceMat and stays in HBM (maps that are
     numpy arrays are uploaded); a numpy source gives numpy.  Nothing is launched for arguments outside the path: they raise."""
-    from vision.devmat import finish_uploads
     mat, cn = _gather_checks(mat, border)
     kind, a, b, (mh, mw) = _classify_maps(map1, map2)
     nearest = bool(nearest)
@@ -461,27 +439,23 @@ def _remap(mat, map1, map2, nearest, border=_vp.BORDER_CONSTANT, border_value=0)
     ctx = _vp.default_context()
     lib = _vp.lib()
     h, w = mat.shape[:2]
-    out_shape = (mh, mw) if mat.ndim == 2 else (mh, mw, cn)
     on_dev = isinstance(mat, DeviceMat)
-    if not on_dev and kind != "fixed" and isinstance(a, np.ndarray) and (b is None or isinstance(b, np.ndarray)):
-        src, a = np.ascontiguousarray(mat), np.ascontiguousarray(a)
-        b = None if b is None else np.ascontiguousarray(b)
-        out = np.empty(out_shape, np.uint8)
-        _vp.check(lib.vp_remap_u8(ctx.handle, _vp.ptr(src), w, h, cn, _vp.ptr(a), None if b is None else _vp.ptr(b), mw, mh, interp, int(border), _vp.ptr(bv),
-                                  _vp.ptr(out)), ctx.handle)
-        return out
+    on_host = not on_dev and kind != "fixed" and isinstance(a, np.ndarray) and (b is None or isinstance(b, np.ndarray))
+    entry = lib.vp_remap_fixed_dev if kind == "fixed" else lib.vp_remap_f32_dev
     up = []
     try:
-        src = _map_on_device(ctx, mat, up)
-        da = _map_on_device(ctx, a, up)
-        db = None if b is None else _map_on_device(ctx, b, up)
-        out = DeviceMat(ctx, out_shape)
-        entry = lib.vp_remap_fixed_dev if kind == "fixed" else lib.vp_remap_f32_dev
-        _vp.check(entry(ctx.handle, src.dev_ptr, w * cn, w, h, cn, da.dev_ptr, None if db is None else db.dev_ptr, mw, mh, interp, int(border), _vp.ptr(bv),
-                        out.dev_ptr), ctx.handle)
+        if on_host:                                      # the host entry reads the float maps where they are
+            src, a, b = mat, np.ascontiguousarray(a), None if b is None else np.ascontiguousarray(b)
+        else:                                            # whatever is not on the device yet is uploaded, the source included
+            src = mat if on_dev else DeviceMat.from_host(ctx, mat, pending=up)
+            a, b = _map_on_device(ctx, a, up), None if b is None else _map_on_device(ctx, b, up)
+        out = run_operator(src, (mh, mw) + tuple(mat.shape[2:]), np.uint8,
+                           lambda ctx, s, d: lib.vp_remap_u8(ctx.handle, s, w, h, cn, _vp.ptr(a), _vp.ptr(b), mw, mh, interp, int(border), _vp.ptr(bv), d),
+                           lambda ctx, s, d: entry(ctx.handle, s, w * cn, w, h, cn, a.dev_ptr, None if b is None else b.dev_ptr, mw, mh, interp,
+                                                   int(border), _vp.ptr(bv), d))
     finally:
         finish_uploads(ctx, up)
-    return out if on_dev else out.host_copy()
+    return out if on_dev or on_host else out.host_copy()
 
 
 def remap(mat: np.ndarray, map_x, map_y=None, nearest: bool = False, border: int = _vp.BORDER_CONSTANT, border_value=0) -> np.ndarray:
@@ -499,7 +473,6 @@ class RemapTable:
     `remap` gives from the float maps."""
 
     def __init__(self, map_x, map_y=None, nearest: bool = False):
-        from vision.devmat import finish_uploads
         kind, a, b, (mh, mw) = _classify_maps(map_x, map_y)
         if kind == "fixed":
             raise TypeError("a RemapTable is built from float32 maps")
@@ -528,10 +501,64 @@ def undistorter(camera_matrix, dist_coeffs, size, new_camera_matrix=None) -> Rem
     """The lens-undistortion table of a calibrated camera, built once: cv2.initUndistortRectifyMap (no rectification; the new camera
     matrix defaults to the camera matrix) into a RemapTable.  size = (width, height) of the undistorted image.  A module calls
     `table.apply(frame)` per frame."""
-    from vision import cv2_facade
     k = camera_matrix if new_camera_matrix is None else new_camera_matrix
-    mx, my = cv2_facade.initUndistortRectifyMap(camera_matrix, dist_coeffs, None, k, size, cv2_facade.CV_32FC1)
-    return RemapTable(mx, my)
+    u, v = _undistort_coords("initUndistortRectifyMap", camera_matrix, dist_coeffs, None, k, size)
+    return RemapTable(u.astype(np.float32), v.astype(np.float32))
+
+
+def _camera(name, cameraMatrix, distCoeffs):
+    """(fx, fy, cx, cy), the 8 rational-model coefficients k1 k2 p1 p2 k3 k4 k5 k6 (missing ones 0), in float64"""
+    A = np.asarray(cameraMatrix, dtype=np.float64)
+    if A.shape != (3, 3) or not np.isfinite(A).all():
+        raise error(f"{name}: the camera matrix must be a finite 3x3 matrix")
+    d = np.zeros(0) if distCoeffs is None else np.asarray(distCoeffs, dtype=np.float64).ravel()
+    if d.size not in (0, 4, 5, 8, 12, 14) or not np.isfinite(d).all():
+        raise error(f"{name}: 4, 5, 8, 12 or 14 finite distortion coefficients")
+    if d.size > 8 and np.any(d[8:] != 0):
+        raise error(f"{name}: the thin-prism (s1..s4) and tilt (tauX, tauY) coefficients are outside the path (DESIGN.md section 7)")
+    k = np.zeros(8)
+    k[:min(d.size, 8)] = d[:8]
+    return A, k
+
+
+def _undistort_coords(name, cameraMatrix, distCoeffs, R, newCameraMatrix, size):
+    """source coordinates (u, v), float64 (h, w) each, of every pixel of the undistorted image: the model of
+    cv2.initUndistortRectifyMap evaluated per pixel (cv2 accumulates the row increments instead: not bit-exact)"""
+    A, k = _camera(name, cameraMatrix, distCoeffs)
+    w, h = int(size[0]), int(size[1])
+    if w <= 0 or h <= 0:
+        raise error(f"{name}: the size must be positive")
+    Ar = A if newCameraMatrix is None else np.asarray(newCameraMatrix, dtype=np.float64)
+    if Ar.shape == (3, 4):
+        Ar = Ar[:, :3]
+    Rm = np.eye(3) if R is None else np.asarray(R, dtype=np.float64)
+    if Ar.shape != (3, 3) or Rm.shape != (3, 3) or not np.isfinite(Ar).all() or not np.isfinite(Rm).all():
+        raise error(f"{name}: R and the new camera matrix must be finite 3x3 matrices")
+    try:
+        ir = np.linalg.inv(Ar @ Rm)
+    except np.linalg.LinAlgError:
+        raise error(f"{name}: newCameraMatrix * R is singular") from None
+    j, i = np.meshgrid(np.arange(w, dtype=np.float64), np.arange(h, dtype=np.float64))
+    X = ir[0, 0] * j + ir[0, 1] * i + ir[0, 2]
+    Y = ir[1, 0] * j + ir[1, 1] * i + ir[1, 2]
+    W = ir[2, 0] * j + ir[2, 1] * i + ir[2, 2]
+    x, y = X / W, Y / W
+    k1, k2, p1, p2, k3, k4, k5, k6 = k
+    x2, y2 = x * x, y * y
+    r2, xy2 = x2 + y2, 2 * x * y
+    kr = (1 + ((k3 * r2 + k2) * r2 + k1) * r2) / (1 + ((k6 * r2 + k5) * r2 + k4) * r2)
+    xd = x * kr + p1 * xy2 + p2 * (r2 + 2 * x2)
+    yd = y * kr + p1 * (r2 + 2 * y2) + p2 * xy2
+    return A[0, 0] * xd + A[0, 2], A[1, 1] * yd + A[1, 2]
+
+
+def _fixed_from_double(u, v):
+    """CV_16SC2 maps from double coordinates: iu = saturate_cast<int>(u * 32), integer part iu >> 5, fraction index from iu & 31.
+    The integer part is saturated to int16 here; cv2 casts it to short without saturating, so the two differ beyond +-32768."""
+    iu = np.clip(np.rint(u * 32), -2147483648, 2147483647).astype(np.int64)
+    iv = np.clip(np.rint(v * 32), -2147483648, 2147483647).astype(np.int64)
+    xy = np.stack([np.clip(iu >> 5, -32768, 32767), np.clip(iv >> 5, -32768, 32767)], axis=-1).astype(np.int16)
+    return np.ascontiguousarray(xy), ((iv & 31) * 32 + (iu & 31)).astype(np.uint16)
 
 
 def _warp_perspective(mat, M, dw, dh, inverse_map=False, nearest=False, border=_vp.BORDER_CONSTANT, border_value=0):
@@ -545,19 +572,11 @@ def _warp_perspective(mat, M, dw, dh, inverse_map=False, nearest=False, border=_
         raise ValueError("the size must be positive, at most 65535 rows, 2^24 columns and 2^31 pixels")
     flags = (_vp.WARP_INVERSE_MAP if inverse_map else 0) | (_vp.INTER_NEAREST if nearest else _vp.INTER_LINEAR)
     bv = _border_bytes(border_value)
-    ctx = _vp.default_context()
     h, w = mat.shape[:2]
-    out_shape = (dh, dw) if mat.ndim == 2 else (dh, dw, cn)
-    if isinstance(mat, DeviceMat):
-        mat.refresh_device(ctx)
-        out = DeviceMat(ctx, out_shape)
-        _vp.check(_vp.lib().vp_warp_perspective_dev(ctx.handle, mat.dev_ptr, w * cn, w, h, cn, _vp.ptr(m), flags, int(border), _vp.ptr(bv), out.dev_ptr, dw, dh),
-                  ctx.handle)
-        return out
-    src = np.ascontiguousarray(mat)
-    out = np.empty(out_shape, np.uint8)
-    _vp.check(_vp.lib().vp_warp_perspective_u8(ctx.handle, _vp.ptr(src), w, h, cn, _vp.ptr(m), flags, int(border), _vp.ptr(bv), _vp.ptr(out), dw, dh), ctx.handle)
-    return out
+    lib = _vp.lib()
+    return run_operator(mat, (dh, dw) + tuple(mat.shape[2:]), np.uint8,
+                        lambda ctx, s, d: lib.vp_warp_perspective_u8(ctx.handle, s, w, h, cn, _vp.ptr(m), flags, int(border), _vp.ptr(bv), d, dw, dh),
+                        lambda ctx, s, d: lib.vp_warp_perspective_dev(ctx.handle, s, w * cn, w, h, cn, _vp.ptr(m), flags, int(border), _vp.ptr(bv), d, dw, dh))
 
 
 def warp_perspective(mat: np.ndarray, M, width: int, height: int) -> np.ndarray:
@@ -566,18 +585,46 @@ def warp_perspective(mat: np.ndarray, M, width: int, height: int) -> np.ndarray:
     return _warp_perspective(mat, M, width, height)
 
 
+def _rotation_matrix_2d(center, angle, scale):
+    """imgproc/src/imgwarp.cpp getRotationMatrix2D: 2x3 float64 (modules/preprocessor.py:131-133)."""
+    ang = angle * np.pi / 180.0
+    a, b = scale * np.cos(ang), scale * np.sin(ang)
+    cx, cy = float(np.float32(center[0])), float(np.float32(center[1]))   # the centre is a Point2f
+    return np.array([[a, b, (1 - a) * cx - b * cy], [-b, a, b * cx + (1 - a) * cy]], np.float64)
+
+
+def _warp_affine(src, M, dsize, flags=_vp.INTER_LINEAR, border=_vp.BORDER_CONSTANT, border_value=0):
+    """cv2.warpAffine without dst: OpenCV's classical fixed-point path (libvp vp_warp_affine_u8 / vp_warp_affine_dev)."""
+    if flags is None:
+        flags = _vp.INTER_LINEAR
+    if (flags & ~_vp.WARP_INVERSE_MAP) != _vp.INTER_LINEAR:
+        raise error("warpAffine: only INTER_LINEAR is on the accelerated path")
+    if border not in (_vp.BORDER_CONSTANT, _vp.BORDER_REPLICATE):
+        raise error("warpAffine: only BORDER_CONSTANT and BORDER_REPLICATE are on the accelerated path")
+    src, cn = _plain_source("warpAffine", src, "expected a non-empty uint8 image")
+    m = np.ascontiguousarray(np.asarray(M, dtype=np.float64))
+    dw, dh = int(dsize[0]), int(dsize[1])
+    if m.shape != (2, 3) or dw <= 0 or dh <= 0 or cn > 4:
+        raise error("warpAffine: M must be 2x3 and the size positive")
+    bv = _border_bytes(border_value)
+    h, w = src.shape[:2]
+    inverse, border = int(flags & _vp.WARP_INVERSE_MAP), int(border)
+    lib = _vp.lib()
+    return run_operator(src, (dh, dw) + tuple(src.shape[2:]), np.uint8,
+                        lambda ctx, s, d: lib.vp_warp_affine_u8(ctx.handle, s, w, h, cn, _vp.ptr(m), inverse, border, _vp.ptr(bv), d, dw, dh),
+                        lambda ctx, s, d: lib.vp_warp_affine_dev(ctx.handle, s, w * cn, w, h, cn, _vp.ptr(m), inverse, border, _vp.ptr(bv), d, dw, dh))
+
+
 def rotate(mat: np.ndarray, degrees: float) -> np.ndarray:
     """utils/transform.py:180-196: rotation about the image centre, positive = counterclockwise, borders replicated."""
-    from vision import cv2_facade
-    rot_mat = cv2_facade.getRotationMatrix2D((mat.shape[1] / 2, mat.shape[0] / 2), degrees, 1)
-    return cv2_facade.warpAffine(mat, rot_mat, (mat.shape[1], mat.shape[0]), borderMode=cv2_facade.BORDER_REPLICATE)
+    rot_mat = _rotation_matrix_2d((mat.shape[1] / 2, mat.shape[0] / 2), degrees, 1)
+    return _warp_affine(mat, rot_mat, (mat.shape[1], mat.shape[0]), border=_vp.BORDER_REPLICATE)
 
 
 def translate(mat: np.ndarray, x: int, y: int) -> np.ndarray:
     """utils/transform.py:199-215: shift by (x, y); uncovered pixels become 0.  The matrix goes through float32 as in the reference."""
-    from vision import cv2_facade
     trans_mat = np.float32([[1, 0, x], [0, 1, y]])
-    return cv2_facade.warpAffine(mat, trans_mat, (mat.shape[1], mat.shape[0]))
+    return _warp_affine(mat, trans_mat, (mat.shape[1], mat.shape[0]))
 
 
 def decode_normal(mat: np.ndarray) -> np.ndarray:

@@ -1,6 +1,6 @@
 """Times the operators that take a device image, on 1080p frames that a device operator produced.
 
-    python tools/exp_dev_ops.py [--part ops|blur|body|all] [--iters N] [--regions R] [--root DIR]
+    python tools/exp_dev_ops.py [--part ops|blur|body|calls|all] [--iters N] [--regions R] [--root DIR]
 
 One process, one GPU.  Every figure is the median over R regions of N back-to-back calls, each region bracketed by HIP events on the
 context's stream (host time spent inside a call that waits for the device is part of the region, as it is for a module).  One JSON line
@@ -11,14 +11,18 @@ per part.
         module would); the producer's own time is measured alone and subtracted.
   blur  vp_gaussian_blur_dev with VP_OPT_BLUR_ONEPASS 1 against 0 in the same run, cn 1 and 3, k 3 .. 31 (builds with the option only).
   body  the red_buoy harness body behind a leading simple_gaussian_blur(image, 5, 0), posts off and on, frame given as a DeviceMat.
+  calls calls per second of the device form of every operator of the Python operator layer on a 64 x 64
+        image, where a call is bound by its launch and by the Python around it: host time of N back-to-back calls and one wait for
+        the device.  Not part of `all`: it is run on two checkouts in turn (--root), several times each.
 
 --root DIR imports the package (and tests/frames.py, tests/module_harness.py) of another checkout, built there, so that the same script
-times the parent commit: `ops` and `body` use only names the mirror has always had."""
+times the parent commit: `ops`, `body` and `calls` use only names the mirror has always had."""
 import argparse
 import json
 import os
 import statistics
 import sys
+import time
 
 ap = argparse.ArgumentParser()
 ap.add_argument("--part", default="all")
@@ -137,7 +141,44 @@ def part_body():
     print(json.dumps(out), flush=True)
 
 
+def part_calls():
+    from vision import cv2_facade as f
+    rng = np.random.default_rng(64)
+    grey = DeviceMat.from_host(ctx, rng.integers(0, 256, (64, 64), dtype=np.uint8))
+    bgr = DeviceMat.from_host(ctx, rng.integers(0, 256, (64, 64, 3), dtype=np.uint8))
+    mask = DeviceMat.from_host(ctx, np.where(rng.random((64, 64)) < 0.4, 255, 0).astype(np.uint8), binary=True)
+    signed = transform.sobel(grey, 1, 0)
+    mx, my = (DeviceMat.from_host(ctx, (rng.random((64, 64), dtype=np.float32) * 66 - 1).astype(np.float32)) for _ in range(2))
+    M = np.array([[1.05, 0.08, -0.6], [-0.04, 0.97, 0.8], [0.0003, -0.0002, 1.0]])
+    ops = [("simple_gaussian_blur", lambda: transform.simple_gaussian_blur(bgr, 5, 0)), ("GaussianBlur", lambda: f.GaussianBlur(bgr, (5, 5), 0)),
+           ("resize", lambda: transform.resize(bgr, 48, 40)), ("rotate", lambda: transform.rotate(bgr, 10.0)), ("translate", lambda: transform.translate(bgr, 3, 2)),
+           ("median_blur", lambda: transform.median_blur(bgr, 3)), ("median_blur_mask", lambda: transform.median_blur(mask, 3)),
+           ("sobel", lambda: transform.sobel(bgr, 1, 0)), ("Sobel", lambda: f.Sobel(bgr, f.CV_16S, 1, 0)), ("scharr", lambda: transform.scharr(bgr, 1, 0)),
+           ("laplacian", lambda: transform.laplacian(bgr, 3)), ("spatial_gradient", lambda: transform.spatial_gradient(grey)),
+           ("convert_scale_abs", lambda: transform.convert_scale_abs(signed)), ("box_filter", lambda: transform.box_filter(bgr, 3)),
+           ("blur", lambda: f.blur(bgr, (3, 3))), ("pyr_down", lambda: transform.pyr_down(bgr)), ("pyr_up", lambda: transform.pyr_up(bgr)),
+           ("integral", lambda: transform.integral(bgr)), ("equalize_hist", lambda: color.equalize_hist(grey)), ("clahe", lambda: color.clahe(grey, 2.0, (4, 4))),
+           ("remap", lambda: transform.remap(bgr, mx, my)), ("warp_perspective", lambda: transform.warp_perspective(bgr, M, 64, 64))]
+    n = args.iters * 25
+    res = {}
+    for name, op in ops:
+        for _ in range(20):
+            op()
+        ctx.synchronize()
+        t = []
+        for _ in range(args.regions):
+            t0 = time.perf_counter()
+            for _ in range(n):
+                op()
+            ctx.synchronize()
+            t.append(n / (time.perf_counter() - t0))
+        res[name] = round(statistics.median(t))
+    print(json.dumps({"part": "calls", "image": [64, 64], "calls": n, "regions": args.regions, "root": ROOT, "calls_per_s": res}), flush=True)
+
+
 if __name__ == "__main__":
+    if args.part == "calls":
+        part_calls()
     for name, fn in (("ops", part_ops), ("blur", part_blur), ("body", part_body)):
         if args.part in (name, "all"):
             fn()
