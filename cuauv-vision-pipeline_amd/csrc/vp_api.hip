@@ -101,6 +101,7 @@ vp_ctx* vp_create(int device)
     ctx->flat_ops = 1;
     ctx->blur_onepass = -1;
     ctx->median_mask = -1;
+    ctx->label_moments_lds = -1;
     if (const char* env = getenv("VP_OPT_MEDIAN_MASK")) { const int v = atoi(env); if (v == 0 || v == 1) ctx->median_mask = v; }
     if (const char* env = getenv("VP_OPT_CLAHE_SPLIT")) { const int v = atoi(env); if (v >= 1 && v <= 64) ctx->clahe_split = v; }
     for (size_t& v : ctx->c3_lds_set) v = 0;
@@ -205,6 +206,7 @@ int vp_set_option(vp_ctx* ctx, int option, int value)
     if (option == VP_OPT_MEDIAN_MASK && value >= -1 && value <= 1) { ctx->median_mask = value; return VP_OK; }
     if (option == VP_OPT_CLAHE_SPLIT && value >= 0 && value <= 64) { ctx->clahe_split = value; return VP_OK; }
     if (option == VP_OPT_CCL_CROWDED && value >= 0 && value <= 2) { ctx->ccl_crowded_force = value; return VP_OK; }
+    if (option == VP_OPT_LABEL_MOMENTS_LDS && value >= -1 && value <= 1) { ctx->label_moments_lds = value; return VP_OK; }
     return vp_fail(ctx, VP_ERR_INVALID, "vp_set_option");
 }
 

@@ -83,6 +83,7 @@ struct vp_ctx {
     int blur_onepass;             // VP_OPT_BLUR_ONEPASS: -1 (default) the measured choice, 1 the one-pass kernel wherever its tile fits, 0 always two passes
     int median_mask;              // VP_OPT_MEDIAN_MASK: -1 (default) the measured choice, 1 the mask kernel for every mask it can serve, 0 never
     int clahe_split;              // VP_OPT_CLAHE_SPLIT: 0 (default) the measured choice, n >= 1 that many blocks share one CLAHE tile's histogram
+    int label_moments_lds;        // VP_OPT_LABEL_MOMENTS_LDS: -1 (default) the measured choice, 1 the block's LDS table wherever it fits, 0 always device atomics
     int hc_global;                // 1: HoughCircles radius histograms always in device memory (VP_OPT_HOUGH_CIRCLES_LDS 0); 0 (default): in LDS where they fit
     void* hc_hist;                // HoughCircles radius histograms of the global form: grow-only, sized per call by its centre count
     size_t hc_hist_bytes;
@@ -252,6 +253,14 @@ int vpk_equalize_hist(vp_ctx* ctx, const uint8_t* d_src, size_t sstride, int w, 
 struct vp_clahe_plan;
 int vpk_clahe(vp_ctx* ctx, const uint8_t* d_src, size_t sstride, int w, int h, int tiles_x, int tiles_y, const vp_clahe_plan& P, u32* d_part, uint8_t* d_luts,
               uint8_t* d_dst);
+
+// ---- moments (vp_moments.hip; the plan: vp_moments_plan.h) ------------------------------------------------
+// The ten sums m00 m10 m01 m20 m11 m02 m30 m21 m12 m03 as unsigned 64-bit integers, of sizes vp_moments_refusal accepted; one launch
+// behind the zeroing of the result, enqueued.  vpk_moments_u8: d_bits (nullable) is the mask's bit plane, read instead of its bytes
+// (binary only).  vpk_label_moments_i32: d_table is (nlabels, 10); stride in bytes, a multiple of 4.
+int vpk_moments_u8(vp_ctx* ctx, const uint8_t* d_src, size_t stride, int w, int h, int binary, const u64* d_bits, u64* d_out10);
+int vp_label_moments_lds_rows(const vp_ctx* ctx, int nlabels);   // rows of the table each block keeps in LDS
+int vpk_label_moments_i32(vp_ctx* ctx, const int32_t* d_labels, size_t stride, int w, int h, int nlabels, u64* d_table);
 
 // ---- morphology (vp_morph.hip) ---------------------------------------------------------------
 struct vp_bitstage { int dilate; int l, r, u, d; };  // window [-l, r] x [-u, d]

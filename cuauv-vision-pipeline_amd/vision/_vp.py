@@ -42,6 +42,7 @@ OPT_BLUR_ONEPASS = 7
 OPT_MEDIAN_MASK = 8
 OPT_CLAHE_SPLIT = 9
 OPT_CCL_CROWDED = 10     # 0 by the hint of an earlier call, 1 always the crowded-frame kernels, 2 always the one stand-in launch
+OPT_LABEL_MOMENTS_LDS = 11   # -1 the measured choice, 1 the block's LDS table wherever it fits, 0 always device atomics
 THRESH_BINARY, THRESH_BINARY_INV, THRESH_TRUNC, THRESH_TOZERO, THRESH_TOZERO_INV = 0, 1, 2, 3, 4
 HOUGH_GRADIENT = 3
 # return codes of include/vp.h
@@ -255,6 +256,12 @@ _SIGS = {
     "vp_pyr_up_dev": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_int, C.c_int, C.c_int, C.c_void_p]),
     "vp_integral_u8": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p]),
     "vp_integral_dev": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_int, C.c_int, C.c_int, C.c_void_p]),
+    "vp_moments_u8": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_int, C.c_int, C.c_int, C.c_void_p]),
+    "vp_moments_dev": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
+    "vp_label_moments_i32": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_int, C.c_int, C.c_int, C.c_void_p]),
+    "vp_label_moments_dev": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_int, C.c_int, C.c_int, C.c_void_p]),
+    "vp_polygon_moments": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_void_p]),
+    "vp_moments_complete": (C.c_int, [C.c_void_p, C.c_void_p]),
 }
 
 

@@ -246,9 +246,28 @@ def connectedComponentsWithStats(image, connectivity=8, ltype=CV_32S):
         cap = n
 
 
-def moments(contour):
-    m00, m10, m01 = _feature._polygon_moments(contour)
-    return {"m00": m00, "m10": m10, "m01": m01}
+def moments(array, binaryImage=False):
+    """cv2.moments, cv2's 24-key dictionary.  An (N, 2) or (N, 1, 2) int32 or float32 array is a contour (contourMoments' float64 loop,
+    host code; binaryImage is ignored, as in cv2); a 2-D uint8 array or DeviceMat is an image, summed on the GPU in exact integers."""
+    from vision.devmat import DeviceMat
+    from vision.utils.helpers import as_mat
+    a = as_mat(array)
+    if isinstance(a, DeviceMat):
+        if a.dtype == np.uint8 and (a.ndim == 2 or (a.ndim == 3 and a.shape[2] == 1)) and a.size:
+            return _feature.moments_dict(_gather("moments", _feature.image_moments, a, bool(binaryImage)))
+    elif isinstance(a, np.ndarray):
+        if a.dtype in (np.int32, np.float32) and ((a.ndim == 2 and a.shape[1] == 2) or (a.ndim == 3 and a.shape[1:] == (1, 2))):
+            return _feature.moments_dict(_feature.contour_moments(a))
+        if a.dtype == np.uint8 and a.ndim == 2 and a.size:
+            return _feature.moments_dict(_gather("moments", _feature.image_moments, a, bool(binaryImage)))
+    raise error("moments: only int32 / float32 contours and single-channel uint8 images are on the accelerated path")
+
+
+def HuMoments(m, hu=None):
+    """cv2.HuMoments of a moments dictionary: float64 (7, 1)."""
+    if not isinstance(m, dict) or any(k not in m for k in _feature.MOMENT_FIELDS[17:]):
+        raise error("HuMoments: expected the dictionary cv2.moments returns")
+    return _into(hu, _feature.hu_moments(m).reshape(7, 1))
 
 
 def contourArea(contour, oriented=False):
@@ -1192,7 +1211,8 @@ def convexHull(points, hull=None, clockwise=False, returnPoints=True):
 
 
 def install():
-    """Registers this facade as `cv2` when no real OpenCV is importable.  Returns the module that `import cv2` yields."""
+    """Registers this facade as `cv2` when no real OpenCV is importable.  Returns the module that `import cv2` yields.  Every public
+    name of this module is then cv2's: the shape descriptors `moments` and `HuMoments` (vision_common.py:131-132) among them."""
     try:
         import cv2 as real
         return real

@@ -7,6 +7,7 @@ utils/feature.py:240-265) are float64 scalar arithmetic on a handful of points a
 """
 from typing import List, Tuple
 
+import math
 import threading
 
 import numpy as np
@@ -164,6 +165,154 @@ def _polygon_moments_float(pts):
             db1_2, db1_6 = -0.5, -1.0 / 6
         return a00 * db1_2, a10 * db1_6, a01 * db1_6
     return 0.0, 0.0, 0.0
+
+
+# cv2.moments' dictionary, in its order: ten spatial, seven central, seven normalised central moments
+MOMENT_FIELDS = ("m00", "m10", "m01", "m20", "m11", "m02", "m30", "m21", "m12", "m03", "mu20", "mu11", "mu02", "mu30", "mu21", "mu12", "mu03",
+                 "nu20", "nu11", "nu02", "nu30", "nu21", "nu12", "nu03")
+
+
+def _complete_moments(sums) -> np.ndarray:
+    """(..., 10) spatial moments -> (..., 24) float64 rows in MOMENT_FIELDS order (libvp vp_moments_complete: completeMomentState, host
+    code).  Integer sums are rounded to float64 once, here."""
+    m = np.ascontiguousarray(sums, np.float64)
+    out = np.empty(m.shape[:-1] + (24,), np.float64)
+    fn = _vp.lib().vp_moments_complete
+    m2, o2 = m.reshape(-1, 10), out.reshape(-1, 24)
+    for i in range(len(m2)):
+        if fn(m2[i].ctypes.data, o2[i].ctypes.data) != 0:
+            raise _vp.VpError("vp_moments_complete: invalid argument")
+    return out
+
+
+def image_moment_sums(mat, binary: bool = False) -> Tuple[int, ...]:
+    """The ten spatial moments of a uint8 (h, w) image as exact Python ints, m00 m10 m01 m20 m11 m02 m30 m21 m12 m03: sum x^p y^q v with
+    v the pixel, or 1 for a non-zero pixel when `binary` (cv2's binaryImage).  One pass on the GPU (libvp vp_moments_u8 / _dev); a
+    DeviceMat is read where it is, and a mask that still carries its bit plane is read through that - the test
+    _connected_components_dev uses."""
+    mat = as_mat(mat)
+    ctx = _vp.default_context()
+    out = np.zeros(10, np.uint64)
+    if isinstance(mat, DeviceMat):
+        src = device_image(ctx, mat, 1)
+        h, w = src.shape
+        bits = src.bit_plane(ctx) if binary else None
+        bp = bits.ptr if (bits is not None and src._dev_ok and src._ctx is ctx) else None
+        _vp.check(_vp.lib().vp_moments_dev(ctx.handle, src.dev_ptr, w, w, h, int(bool(binary)), bp, _vp.ptr(out)), ctx.handle)
+    else:
+        mat = to_host_readonly(mat)
+        if not isinstance(mat, np.ndarray) or mat.dtype != np.uint8:
+            raise TypeError("expected a uint8 single-channel image")
+        if mat.ndim == 3 and mat.shape[2] == 1:
+            mat = mat[:, :, 0]
+        if mat.ndim != 2 or mat.size == 0:
+            raise ValueError("expected a non-empty (h, w) image")
+        h, w = mat.shape
+        if mat.strides[1] != 1 or (h > 1 and mat.strides[0] < w):
+            mat = np.ascontiguousarray(mat)
+        _vp.check(_vp.lib().vp_moments_u8(ctx.handle, _vp.ptr(mat), mat.strides[0] if h > 1 else w, w, h, int(bool(binary)), _vp.ptr(out)), ctx.handle)
+    return tuple(int(v) for v in out)
+
+
+def image_moments(mat, binary: bool = False) -> np.ndarray:
+    """cv2.moments(image, binaryImage=binary) as a float64 (24,) row in MOMENT_FIELDS order: the exact integer sums of
+    image_moment_sums, each rounded to float64 once, then completeMomentState.  `moments_dict` makes cv2's dictionary of it."""
+    return _complete_moments(np.array(image_moment_sums(mat, binary), np.uint64))
+
+
+def component_moment_sums(labels, nlabels: int) -> np.ndarray:
+    """(nlabels, 10) uint64: the ten spatial moments of every label value 0 .. nlabels - 1 of an int32 label image, each pixel counting
+    1 - one pass on the GPU over all components at once (libvp vp_label_moments_i32 / _dev).  Row 0 is the background; a label outside
+    the range counts nowhere.  `labels` is numpy or the DeviceMat connected_components returns."""
+    labels = as_mat(labels)
+    nlabels = int(nlabels)
+    if nlabels < 1:
+        raise ValueError("nlabels must be at least 1")
+    ctx = _vp.default_context()
+    out = np.zeros((nlabels, 10), np.uint64)
+    if isinstance(labels, DeviceMat):
+        if labels.dtype != np.int32 or labels.ndim != 2 or labels.size == 0:
+            raise TypeError("expected a non-empty int32 (h, w) label image")
+        labels.refresh_device(ctx)
+        h, w = labels.shape
+        _vp.check(_vp.lib().vp_label_moments_dev(ctx.handle, labels.dev_ptr, 4 * w, w, h, nlabels, _vp.ptr(out)), ctx.handle)
+    else:
+        labels = to_host_readonly(labels)
+        if not isinstance(labels, np.ndarray) or labels.dtype != np.int32 or labels.ndim != 2 or labels.size == 0:
+            raise TypeError("expected a non-empty int32 (h, w) label image")
+        labels = np.ascontiguousarray(labels)
+        h, w = labels.shape
+        _vp.check(_vp.lib().vp_label_moments_i32(ctx.handle, _vp.ptr(labels), 4 * w, w, h, nlabels, _vp.ptr(out)), ctx.handle)
+    return out
+
+
+def component_moments(labels, nlabels: int):
+    """(float64 (nlabels, 24) array, MOMENT_FIELDS): cv2.moments(labels == k, binaryImage=True) for every k < nlabels at once, row 0 the
+    background.  m00 is the component's area and (m10 / m00, m01 / m00) its centroid, as connected_components reports them."""
+    return _complete_moments(component_moment_sums(labels, nlabels)), MOMENT_FIELDS
+
+
+def contour_moments(contour) -> np.ndarray:
+    """cv2.moments(contour) with all 24 fields, a float64 row in MOMENT_FIELDS order: contourMoments' float64 loop (libvp
+    vp_polygon_moments, host code) for an (N, 2) or (N, 1, 2) contour of int32 (any integer type) or float32 points, then
+    completeMomentState."""
+    pts = np.asarray(contour)
+    if pts.dtype.kind in "iu":
+        pts = np.ascontiguousarray(pts.reshape(-1, 2), np.int32)
+    elif pts.dtype == np.float32:
+        pts = np.ascontiguousarray(pts.reshape(-1, 2))
+    else:
+        raise TypeError("expected a contour of int32 or float32 points")
+    m = np.empty(10, np.float64)
+    if _vp.lib().vp_polygon_moments(pts.ctypes.data if len(pts) else None, int(pts.dtype == np.float32), len(pts), m.ctypes.data) != 0:
+        raise _vp.VpError("vp_polygon_moments: invalid argument")
+    return _complete_moments(m)
+
+
+def moments_dict(row) -> dict:
+    """cv2.moments' dictionary (24 Python floats, cv2's key order) of one row of image_moments / component_moments / contour_moments."""
+    row = np.asarray(row, np.float64).reshape(24)
+    return dict(zip(MOMENT_FIELDS, row.tolist()))
+
+
+def _nu(m):
+    if isinstance(m, dict):
+        return tuple(float(m[k]) for k in MOMENT_FIELDS[17:])
+    return tuple(np.asarray(m, np.float64).reshape(24)[17:].tolist())
+
+
+def hu_moments(m) -> np.ndarray:
+    """cv2.HuMoments of a moments dictionary or 24-field row: float64 (7,), cv::HuMoments' operations in its order."""
+    nu20, nu11, nu02, nu30, nu21, nu12, nu03 = _nu(m)
+    t0 = nu30 + nu12
+    t1 = nu21 + nu03
+    q0 = t0 * t0
+    q1 = t1 * t1
+    n4 = 4 * nu11
+    s = nu20 + nu02
+    d = nu20 - nu02
+    hu = [0.0] * 7
+    hu[0] = s
+    hu[1] = d * d + n4 * nu11
+    hu[3] = q0 + q1
+    hu[5] = d * (q0 - q1) + n4 * t0 * t1
+    t0 *= q0 - 3 * q1
+    t1 *= 3 * q0 - q1
+    q0 = nu30 - 3 * nu12
+    q1 = 3 * nu21 - nu03
+    hu[2] = q0 * q0 + q1 * q1
+    hu[4] = q0 * t0 + q1 * t1
+    hu[6] = q1 * t0 - q0 * t1
+    return np.array(hu, np.float64)
+
+
+def orientation(m) -> float:
+    """Angle of the major axis of a blob from its central moments, 0.5 * atan2(2 mu11, mu20 - mu02), in radians."""
+    if isinstance(m, dict):
+        mu20, mu11, mu02 = float(m["mu20"]), float(m["mu11"]), float(m["mu02"])
+    else:
+        mu20, mu11, mu02 = np.asarray(m, np.float64).reshape(24)[10:13].tolist()
+    return 0.5 * math.atan2(2 * mu11, mu20 - mu02)
 
 
 def contour_centroid(contour: np.ndarray) -> Tuple[int, int]:

@@ -99,9 +99,14 @@ int vp_synchronize(vp_ctx* ctx);
  * (with VP_OPT_CHAIN_STREAMS above 1: still the six); 0 = by a hint - the number of frames an earlier call handed over, read without
  * synchronising: the one launch until a call hands a frame over, the six from the next call on, the one again after 32 calls in a
  * row that handed nothing over; a vp_chain_run_contours call whose contour pass runs beside the labelling always takes the six.
- * Results are identical. */
+ * Results are identical.
+ * VP_OPT_LABEL_MOMENTS_LDS (1, 0 or -1, default -1): where vp_label_moments_* keeps its (nlabels, 10) table while it adds.  1 = in
+ * each block's LDS, flushed with device atomics - the whole table when nlabels * 80 bytes fit (768 labels), else its first 64 rows,
+ * the background's among them, the other rows taking device atomics; 0 = device atomics for every run; -1 = the measured choice
+ * (that of 1).  Results are identical. */
 enum { VP_OPT_CHAIN_STREAMS = 1, VP_OPT_CCL_LEVELS = 2, VP_OPT_CCL_MERGE_CAP = 3, VP_OPT_FLAT_OPS = 4, VP_OPT_HOUGH_LDS = 5,
-       VP_OPT_HOUGH_CIRCLES_LDS = 6, VP_OPT_BLUR_ONEPASS = 7, VP_OPT_MEDIAN_MASK = 8, VP_OPT_CLAHE_SPLIT = 9, VP_OPT_CCL_CROWDED = 10 };
+       VP_OPT_HOUGH_CIRCLES_LDS = 6, VP_OPT_BLUR_ONEPASS = 7, VP_OPT_MEDIAN_MASK = 8, VP_OPT_CLAHE_SPLIT = 9, VP_OPT_CCL_CROWDED = 10,
+       VP_OPT_LABEL_MOMENTS_LDS = 11 };
 int vp_set_option(vp_ctx* ctx, int option, int value);
 /* Kernels of the labelling sequence that the context's last labelling call queued (vp_ccl_*, vp_chain_run with ccl): tells the tests
  * which form VP_OPT_CCL_CROWDED = 0 chose.  The one-off initialisation of the crowded-frame kernels' accumulators is not counted. */
@@ -706,6 +711,33 @@ int vp_split_u8_dev(vp_ctx* ctx, const uint8_t* src_dev, size_t n_px, int cn, ui
 int vp_merge_u8_dev(vp_ctx* ctx, const uint8_t* p0_dev, const uint8_t* p1_dev, const uint8_t* p2_dev, const uint8_t* p3_dev, size_t n_px,
                     int cn, uint8_t* dst_dev);
 int vp_count_nonzero_u8_dev(vp_ctx* ctx, const uint8_t* src_dev, size_t n_bytes, uint64_t* count_host);
+
+/* ---- moments: cv2.moments and cv2.HuMoments --------------------------------------------------------------------------------------- *
+ * Order everywhere, cv::Moments': m00 m10 m01 m20 m11 m02 m30 m21 m12 m03, m_pq = sum x^p y^q v, x the column, y the row.
+ * vp_moments_u8 / vp_moments_dev: the ten sums of a uint8 image as exact integers into out10_host, v the pixel value, or 1 for a
+ *   non-zero pixel when `binary` is set (cv2's binaryImage).  One pass at one byte per pixel; the source is read in place with any row
+ *   stride (bytes, at least w) and any pointer alignment.  bits_dev (nullable, `binary` only): the mask's bit plane in the layout of
+ *   vp_inrange_u8_bits_dev ((w + 63) / 64 words per row, bit x % 64 of word x / 64 is pixel x; bits past w are ignored), read instead
+ *   of the bytes - src_dev may then be NULL.  The host form stages the image; both synchronise.
+ * vp_label_moments_i32 / vp_label_moments_dev: the same ten sums with v = 1 for every label value 0 .. nlabels - 1 of an int32 label
+ *   image (row stride in bytes, a multiple of 4, at least 4 w) into out_host, (nlabels, 10) uint64; row 0 is the background, as in
+ *   cv2.connectedComponentsWithStats.  A label outside that range counts nowhere.  One pass at four bytes per pixel; see
+ *   VP_OPT_LABEL_MOMENTS_LDS.  Both synchronise.
+ * Refused with VP_ERR_INVALID before anything is launched (the message names the reason): w or h below 1, h > 65535, a stride below
+ *   the row, nlabels < 1, a binary bit plane without `binary`, and sizes whose worst-case m30 or m03 - 255 (1 when binary, and for
+ *   labels) * h * sum_{x < w} x^3, and the transpose - reaches 2^63.  Below that bound no sum wraps; cv2's doubles are exact only below
+ *   2^53, where the two agree (a binary 1080p mask is far below).
+ * vp_polygon_moments: cv2.moments of a contour of n points, int32 or float32 (x, y) pairs - contourMoments' float64 loop in its
+ *   operation order, out10 = the ten spatial moments; all zero for n = 0 or |a00| <= FLT_EPSILON.  Host code, no context.
+ * vp_moments_complete: completeMomentState - out24 = the ten spatial moments, mu20 mu11 mu02 mu30 mu21 mu12 mu03 and nu20 .. nu03, the
+ *   order of cv2's dictionary.  Host code, no context.  Both are compiled without contraction: the doubles are OpenCV's bit for bit. */
+int vp_moments_u8(vp_ctx* ctx, const uint8_t* src_host, size_t stride, int w, int h, int binary, uint64_t* out10_host);
+int vp_moments_dev(vp_ctx* ctx, const uint8_t* src_dev, size_t stride, int w, int h, int binary, const unsigned long long* bits_dev,
+                   uint64_t* out10_host);
+int vp_label_moments_i32(vp_ctx* ctx, const int32_t* labels_host, size_t stride, int w, int h, int nlabels, uint64_t* out_host);
+int vp_label_moments_dev(vp_ctx* ctx, const int32_t* labels_dev, size_t stride, int w, int h, int nlabels, uint64_t* out_host);
+int vp_polygon_moments(const void* pts, int is_float32, int n, double* out10);
+int vp_moments_complete(const double* m10, double* out24);
 
 /* ---- device memory helpers (so a host program needs no HIP binding of its own) --------- */
 int vp_dev_alloc(vp_ctx* ctx, size_t bytes, void** dev_ptr);
