@@ -262,6 +262,14 @@ int vpk_moments_u8(vp_ctx* ctx, const uint8_t* d_src, size_t stride, int w, int 
 int vp_label_moments_lds_rows(const vp_ctx* ctx, int nlabels);   // rows of the table each block keeps in LDS
 int vpk_label_moments_i32(vp_ctx* ctx, const int32_t* d_labels, size_t stride, int w, int h, int nlabels, u64* d_table);
 
+// ---- corners (vp_corners.hip; the plan: vp_corners_plan.h) -------------------------------------------------
+// The float32 response map of cv2.cornerMinEigenVal (harris 0) or cornerHarris, arguments as vp_corner_response_refusal admitted them;
+// d_dst packed; one launch, enqueued.  vpk_corner_candidates: the masked maximum and goodFeaturesToTrack's candidates of a response
+// map as sortable words (d_cnt: two words, the maximum's key and the true candidate count); two launches, enqueued.
+int vpk_corner_response(vp_ctx* ctx, const uint8_t* d_src, size_t stride, int w, int h, int block_size, int harris, double k, int border, float* d_dst);
+int vpk_corner_candidates(vp_ctx* ctx, const float* d_resp, int w, int h, const uint8_t* d_mask, size_t mstride, const u64* d_bits, double quality,
+                          u32* d_cnt, u64* d_keys, size_t kcap);
+
 // ---- morphology (vp_morph.hip) ---------------------------------------------------------------
 struct vp_bitstage { int dilate; int l, r, u, d; };  // window [-l, r] x [-u, d]
 #define VP_MAX_STAGES 32

@@ -1097,6 +1097,35 @@ def HoughCircles(image, method, dp, minDist, circles=None, param1=100, param2=10
         raise error(f"HoughCircles: {e}") from e
 
 
+# ---- corners (libvp vp_corners.hip): the exact value of what OpenCV's float32 code approximates, DESIGN.md section 4.24 ----------------
+def cornerMinEigenVal(src, blockSize, dst=None, ksize=3, borderType=BORDER_DEFAULT):
+    """cv2.cornerMinEigenVal on a uint8 single-channel image in cv2's positional order: float32 (h, w), the smaller eigenvalue of the
+    structure tensor from exact integer sums (ksize 3 only; blockSize 1..31).  A DeviceMat stays in HBM."""
+    src = _source("cornerMinEigenVal", src, "only uint8 images are on the accelerated path")
+    return _into(dst, _gather("cornerMinEigenVal", _feature.corner_min_eigen_val, src, blockSize, ksize, BORDER_DEFAULT if borderType is None else borderType))
+
+
+def cornerHarris(src, blockSize, ksize, k, dst=None, borderType=BORDER_DEFAULT):
+    """cv2.cornerHarris under the rules of cornerMinEigenVal above: det - k trace^2 of the same structure tensor."""
+    src = _source("cornerHarris", src, "only uint8 images are on the accelerated path")
+    return _into(dst, _gather("cornerHarris", _feature.corner_harris, src, blockSize, ksize, k, BORDER_DEFAULT if borderType is None else borderType))
+
+
+def goodFeaturesToTrack(image, maxCorners, qualityLevel, minDistance, corners=None, mask=None, blockSize=3, useHarrisDetector=False, k=0.04,
+                        gradientSize=3):
+    """cv2.goodFeaturesToTrack (utils/feature.py `find_corners`) in cv2's positional order on a uint8 single-channel image: float32
+    (N, 1, 2) of (x, y), strongest first, or None when there is no corner.  gradientSize 3 only."""
+    if gradientSize != 3:
+        raise error("goodFeaturesToTrack: only gradientSize 3 is on the accelerated path (DESIGN.md section 7)")
+    image = _source("goodFeaturesToTrack", image, "only uint8 images are on the accelerated path")
+    try:
+        found = _gather("goodFeaturesToTrack", _feature.good_features_to_track, image, maxCorners, qualityLevel, minDistance, mask, blockSize,
+                        useHarrisDetector, k)
+    except _vp.VpError as e:
+        raise error(f"goodFeaturesToTrack: {e}") from e
+    return found if found is None else _into(corners, found)
+
+
 def adaptiveThreshold(src, maxValue, adaptiveMethod, thresholdType, blockSize, C, dst=None):
     """cv2.adaptiveThreshold (utils/color.py:220-292) in cv2's positional order on CV_8UC1 images.  ADAPTIVE_THRESH_MEAN_C: the mean
     path (libvp vp_adaptive_threshold_mean_*, block sizes 3..151); ADAPTIVE_THRESH_GAUSSIAN_C: the exact Gaussian-weighted mean

@@ -15,7 +15,7 @@ from collections.abc import Sequence as _SequenceABC
 
 from vision import _vp
 from vision.devmat import DeviceMat, to_host_readonly
-from vision.utils.helpers import as_mat, device_image
+from vision.utils.helpers import as_mat, device_image, image_source, run_operator
 
 
 def connected_components(mat: np.ndarray, numbering: int = _vp.CCL_BLOCK2X2, max_labels: int = 4096,
@@ -448,15 +448,115 @@ def simple_canny(mat: np.ndarray, sigma: float = 0.33, use_mean: bool = False) -
     upper = int(min(255, (1.0 + sigma) * mid))
     return canny(mat, lower, upper)
 # Outside the path on purpose: cv2.HoughLinesP (find_line_segments) draws its points in the order of a seeded RNG and removes each
-# segment's votes before the next draw, a serial algorithm by definition; cv2.goodFeaturesToTrack (find_corners) goes through OpenCV's
-# SIMD float paths, which cannot be restated bit for bit.  find_circles still raises because the tests of this build pin that it does;
-# the transform it wraps is here as hough_circles (and cv2_facade.HoughCircles).
+# segment's votes before the next draw, a serial algorithm by definition.  find_corners and find_circles still raise because the tests of
+# this build pin that they do; the operators they wrap are here under their own names: cv2.goodFeaturesToTrack as
+# good_features_to_track (with corner_min_eigen_val and corner_harris, the response maps it selects from; cv2_facade.goodFeaturesToTrack,
+# cornerMinEigenVal, cornerHarris) - OpenCV's float32 SIMD arithmetic cannot be restated bit for bit, so the contract is the exact value
+# of what it approximates, rounded once - and cv2.HoughCircles as hough_circles (cv2_facade.HoughCircles).
 find_corners = _outside_path("find_corners")
 find_circles = _outside_path("find_circles")
 find_line_segments = _outside_path("find_line_segments")
 
 _lines_cap = threading.local()
 _circles_cap = threading.local()
+_corners_cap = threading.local()
+
+_CORNER_BORDERS = (_vp.BORDER_REFLECT_101, _vp.BORDER_REPLICATE, _vp.BORDER_REFLECT, _vp.BORDER_CONSTANT)
+CORNER_MAX_BLOCK = 31
+
+
+def _corner_block(block_size, ksize=3):
+    block_size, ksize = int(block_size), int(ksize)
+    if not 1 <= block_size <= CORNER_MAX_BLOCK:
+        raise ValueError("blockSize must be in 1..31")
+    if ksize != 3:
+        raise ValueError("only the 3x3 Sobel (ksize 3) is restated: ksize 5, 7 and -1 (Scharr) are outside the accelerated path")
+    return block_size
+
+
+def _corner_response(name, mat, block_size, ksize, harris, k, border):
+    mat, _ = image_source(mat, single=f"{name} takes a single-channel image", max_side=65535)
+    block_size = _corner_block(block_size, ksize)
+    k, border = float(k), int(border) & ~_vp.BORDER_ISOLATED
+    if not math.isfinite(k):
+        raise ValueError("k must be finite")
+    if border not in _CORNER_BORDERS:
+        raise ValueError("the border must be BORDER_REFLECT_101, BORDER_REPLICATE, BORDER_REFLECT or BORDER_CONSTANT")
+    h, w = mat.shape
+    lib = _vp.lib()
+    return run_operator(mat, (h, w), np.float32,
+                        lambda ctx, s, d: lib.vp_corner_response_u8(ctx.handle, s, w, w, h, block_size, 3, harris, k, border, d),
+                        lambda ctx, s, d: lib.vp_corner_response_dev(ctx.handle, s, w, w, h, block_size, 3, harris, k, border, d))
+
+
+def corner_min_eigen_val(mat, block_size: int = 3, ksize: int = 3, border: int = _vp.BORDER_REFLECT_101):
+    """cv2.cornerMinEigenVal of a uint8 single-channel image as this library defines it: the smaller eigenvalue
+    of the block_size x block_size structure tensor of the 3x3 Sobel derivatives - exact integer sums, the eigenvalue in float64 in a
+    fixed order, rounded to float32 once - where cv2 runs float32 code that lands near it.  float32 (h, w); numpy in gives numpy out, a
+    DeviceMat gives a DeviceMat that stays in HBM (libvp vp_corner_response_*).  Exactly 0 on flat regions and straight edges."""
+    return _corner_response("corner_min_eigen_val", mat, block_size, ksize, 0, 0.0, border)
+
+
+def corner_harris(mat, block_size: int, ksize: int = 3, k: float = 0.04, border: int = _vp.BORDER_REFLECT_101):
+    """cv2.cornerHarris under the contract of corner_min_eigen_val: det(M) - k trace(M)^2 of the same structure tensor."""
+    return _corner_response("corner_harris", mat, block_size, ksize, 1, k, border)
+
+
+def good_features_to_track(mat, max_corners: int, quality_thresh: float = 0.01, min_distance: float = 10, mask=None, block_size: int = 3,
+                           use_harris: bool = False, k: float = 0.04):
+    """cv2.goodFeaturesToTrack(mat, max_corners, quality_thresh, min_distance, mask=mask, blockSize=block_size,
+    useHarrisDetector=use_harris, k=k) on the response map of corner_min_eigen_val / corner_harris (utils/feature.py `find_corners`):
+    float32 (N, 1, 2) of (x, y), strongest first, or None when there is no corner.  Response, maximum, threshold with the 3 x 3 test and
+    the ordering run on the GPU (libvp vp_good_features_*); a device image and a device mask are read where they are (a mask that still
+    carries its bit plane through that), and the corners always come back as numpy.  max_corners <= 0 keeps all."""
+    mat, _ = image_source(mat, single="good_features_to_track takes a single-channel image", max_side=65535)
+    block_size = _corner_block(block_size)
+    max_corners, quality, min_distance, k = int(max_corners), float(quality_thresh), float(min_distance), float(k)
+    if not (quality > 0 and math.isfinite(quality)):
+        raise ValueError("qualityLevel must be positive and finite")
+    if not min_distance >= 0:
+        raise ValueError("minDistance must be at least 0")
+    if not math.isfinite(k):
+        raise ValueError("k must be finite")
+    h, w = mat.shape
+    if mask is not None:
+        mask, _ = image_source(mask, single="the mask must be a single-channel image",
+                               said=("the mask must be uint8", "the mask must be a non-empty (h, w) image", None))
+        if tuple(mask.shape) != (h, w):
+            raise ValueError("the mask must have the size of the image")
+    ctx = _vp.default_context()
+    lib = _vp.lib()
+    on_device = isinstance(mat, DeviceMat)
+    mp, bp = None, None
+    if on_device:
+        mat.refresh_device(ctx)
+        if mask is not None:
+            mask = device_image(ctx, mask, 1)
+            bits = mask.bit_plane(ctx)
+            bp = bits.ptr if (bits is not None and mask._dev_ok and mask._ctx is ctx) else None
+            mp = mask.dev_ptr
+    else:
+        mat = np.ascontiguousarray(mat)
+        if mask is not None:
+            mask = np.ascontiguousarray(to_host_readonly(mask))
+            mp = mask.ctypes.data
+    head = (max_corners, quality, min_distance, mp, w, w if mask is not None else 0, h if mask is not None else 0)
+    tail = (block_size, int(bool(use_harris)), k)
+    cap = getattr(_corners_cap, "n", 1024)
+    if max_corners > 0:
+        cap = max_corners
+    while True:
+        out = np.empty((max(cap, 1), 1, 2), np.float32)
+        n = _vp.C.c_int(0)
+        if on_device:
+            rc = lib.vp_good_features_dev(ctx.handle, mat.dev_ptr, w, w, h, *head, bp, *tail, _vp.ptr(out), cap, _vp.C.byref(n))
+        else:
+            rc = lib.vp_good_features_u8(ctx.handle, mat.ctypes.data, w, w, h, *head, *tail, _vp.ptr(out), cap, _vp.C.byref(n))
+        _vp.check(rc, ctx.handle)
+        if n.value <= cap:
+            break
+        cap = _corners_cap.n = n.value                 # the true count came back: once more with room for all of them
+    return out[:n.value].copy() if n.value else None
 
 
 def hough_circles(mat, dp: float, min_dist: float, param1: float = 100, param2: float = 100, min_radius: int = 0, max_radius: int = 0):

@@ -739,6 +739,40 @@ int vp_label_moments_dev(vp_ctx* ctx, const int32_t* labels_dev, size_t stride, 
 int vp_polygon_moments(const void* pts, int is_float32, int n, double* out10);
 int vp_moments_complete(const double* m10, double* out24);
 
+/* ---- corners: cv2.cornerMinEigenVal, cv2.cornerHarris and cv2.goodFeaturesToTrack ------------------------------------------------- *
+ * On uint8 single-channel images with the 3x3 Sobel (ksize 3).  OpenCV's float32 code is not restated; what it approximates is
+ * (tests/corners_restate.py): Dx, Dy the integer Sobel derivatives under `border`; Sxx, Sxy, Syy the
+ * unnormalised block_size x block_size box sums (anchor block_size / 2) of Dx Dx, Dx Dy, Dy Dy, the same border applied to the
+ * product image - all exact in int32; then in IEEE double, in this order, s = 1 / (4 block_size 255):
+ *   harris 0: a = Sxx 0.5, b = Sxy, c = Syy 0.5, response = (float)(((a + c) - sqrt((a - c)(a - c) + b b)) (s s))
+ *   harris 1: a = Sxx, b = Sxy, c = Syy, response = (float)(((a c - b b) - k ((a + c)(a + c))) ((s s)(s s)))
+ * vp_corner_response_u8 / vp_corner_response_dev: the float32 map, packed, from a source of any row stride (bytes, at least w) and
+ *   pointer alignment.  border: VP_BORDER_REFLECT_101 (cv2's default), REPLICATE, REFLECT or CONSTANT (the ISOLATED bit is ignored).
+ *   The host form stages the image and synchronises; the device form enqueues one launch and never synchronises, dst_dev must be
+ *   4-byte aligned and must not overlap the source.
+ * vp_good_features_u8 / vp_good_features_dev: goodFeaturesToTrack's selection on that map (border REFLECT_101).  The maximum is taken
+ *   over the pixels where the mask (nullable; mask_w x mask_h bytes, rows of mask_stride) is non-zero; t = (float)((double)max *
+ *   quality_level); a candidate is an interior pixel (1 <= x <= w - 2, 1 <= y <= h - 2) admitted by the mask with response > t, != 0
+ *   and >= every one of its eight neighbours that is > t; candidates are ordered by response descending, equal responses by larger
+ *   y w + x first, and kept greedily: dropped when a kept corner lies at dx dx + dy dy < min_distance^2, until max_corners > 0 are
+ *   kept (max_corners <= 0: all).  corners_host receives the first `capacity` (x, y) float32 pairs, *n_corners the true count: a
+ *   caller with too small a buffer learns the size it needs.  mask_bits_dev (nullable): the mask's bit plane in the layout of
+ *   vp_inrange_u8_bits_dev, read instead of its bytes.  Images with w < 3 or h < 3 give 0.  Both synchronise.
+ * Refused with VP_ERR_INVALID before anything is launched or written (the message names the reason): a missing pointer, w or h below
+ *   1 or above 65535, more than 2^28 pixels, a stride below the row, block_size outside 1..31, ksize != 3, an unsupported border, a
+ *   k that is not finite, quality_level <= 0 or not finite, min_distance < 0 or NaN, a negative capacity, a mask whose size differs
+ *   from the image's or whose stride is below its row. */
+int vp_corner_response_u8(vp_ctx* ctx, const uint8_t* src_host, size_t stride, int w, int h, int block_size, int ksize, int harris, double k, int border,
+                          float* dst_host);
+int vp_corner_response_dev(vp_ctx* ctx, const uint8_t* src_dev, size_t stride, int w, int h, int block_size, int ksize, int harris, double k, int border,
+                           float* dst_dev);
+int vp_good_features_u8(vp_ctx* ctx, const uint8_t* src_host, size_t stride, int w, int h, int max_corners, double quality_level, double min_distance,
+                        const uint8_t* mask_host, size_t mask_stride, int mask_w, int mask_h, int block_size, int harris, double k, float* corners_host,
+                        int capacity, int* n_corners);
+int vp_good_features_dev(vp_ctx* ctx, const uint8_t* src_dev, size_t stride, int w, int h, int max_corners, double quality_level, double min_distance,
+                         const uint8_t* mask_dev, size_t mask_stride, int mask_w, int mask_h, const unsigned long long* mask_bits_dev, int block_size,
+                         int harris, double k, float* corners_host, int capacity, int* n_corners);
+
 /* ---- device memory helpers (so a host program needs no HIP binding of its own) --------- */
 int vp_dev_alloc(vp_ctx* ctx, size_t bytes, void** dev_ptr);
 int vp_dev_free(vp_ctx* ctx, void* dev_ptr);    /* ctx may be NULL (memory that outlived its context) */

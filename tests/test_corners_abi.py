@@ -1,0 +1,192 @@
+"""CPU suite for the surface of the corner operators: the four C entries are exported by libvp.so and declared in include/vp.h with the
+prototypes vision/_vp.py binds; the two units are built; the plan's tile constants are readable; the facade has cv2's signatures and
+defaults; every refusal comes from the arguments alone - VP_ERR_INVALID with its reason from the C entries, cv2_facade.error from the
+facade, no device needed, nothing written; and find_corners still raises."""
+import ctypes as C
+import inspect
+import os
+import re
+
+import numpy as np
+import pytest
+
+from test_dev_ops_abi import _header_prototypes
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+NEW = ["vp_corner_response_u8", "vp_corner_response_dev", "vp_good_features_u8", "vp_good_features_dev"]
+
+
+def test_corner_symbols_are_exported_declared_and_bound_alike():
+    from vision import _vp
+    protos = _header_prototypes()
+    lib = C.CDLL(_vp.LIB_PATH)
+    for name in NEW:
+        assert hasattr(lib, name), f"libvp.so does not export {name}"
+        assert name in protos, f"include/vp.h does not declare {name}"
+        assert name in _vp._SIGS, f"vision/_vp.py does not bind {name}"
+        ret, types = protos[name]
+        res, args = _vp._SIGS[name]
+        assert ret == "int" and res is C.c_int
+        assert list(args) == types, (name, args, types)
+        assert name in _vp.exported_symbols()
+    assert len(protos["vp_corner_response_dev"][1]) == 11 and len(protos["vp_good_features_u8"][1]) == 18 and len(protos["vp_good_features_dev"][1]) == 19
+    built = open(os.path.join(ROOT, "cuauv-vision-pipeline_amd", "build.py")).read()
+    for src in ("vp_corners.hip", "vp_api_corners.hip"):
+        assert f'"{src}"' in built, f"{src} is not among VP_SOURCES"
+        assert os.path.exists(os.path.join(ROOT, "cuauv-vision-pipeline_amd", "csrc", src))
+
+
+def test_plan_constants_are_readable_and_prove_the_bounds():
+    plan = open(os.path.join(ROOT, "cuauv-vision-pipeline_amd", "csrc", "vp_corners_plan.h")).read()
+    num = lambda n: int(re.search(r"#define " + n + r" (\d+)", plan).group(1))
+    tw, th, seg, mb, md = num("CR_TW"), num("CR_TH"), num("CR_SEG"), num("CR_MAX_BLOCK"), num("CR_MAX_DERIV")
+    assert tw == 64 and th % 4 == 0 and tw % seg == 0 and mb == 31 and md == 4 * 255
+    assert mb * mb * md * md < 2 ** 31 and "static_assert((long long)CR_MAX_BLOCK * CR_MAX_BLOCK * CR_MAX_DERIV * CR_MAX_DERIV < (1ll << 31)" in plan
+    assert num("CR_MAX_SIDE") == 65535 and num("CR_MAX_PIXELS") == 2 ** 28
+    pw, ph = tw + mb - 1, th + mb - 1                   # the kernel's LDS at the largest block: source bytes, Sobel pairs, three row-sum planes
+    assert (ph + 2) * ((pw + 2 + 3) & ~3) + ph * (pw | 1) * 4 + 3 * ph * (tw + 1) * 4 <= 64 * 1024
+    assert "vp_deriv_border_index" in open(os.path.join(ROOT, "cuauv-vision-pipeline_amd", "csrc", "vp_corners.hip")).read()
+
+
+def test_facade_signatures_and_defaults_are_cv2s():
+    from vision import cv2_facade as f
+    from vision.utils import feature
+    sig = lambda fn: [(p.name, p.default) for p in inspect.signature(fn).parameters.values()]
+    E = inspect.Parameter.empty
+    assert sig(f.cornerMinEigenVal) == [("src", E), ("blockSize", E), ("dst", None), ("ksize", 3), ("borderType", 4)]
+    assert sig(f.cornerHarris) == [("src", E), ("blockSize", E), ("ksize", E), ("k", E), ("dst", None), ("borderType", 4)]
+    assert sig(f.goodFeaturesToTrack) == [("image", E), ("maxCorners", E), ("qualityLevel", E), ("minDistance", E), ("corners", None), ("mask", None),
+                                          ("blockSize", 3), ("useHarrisDetector", False), ("k", 0.04), ("gradientSize", 3)]
+    assert sig(feature.corner_min_eigen_val) == [("mat", E), ("block_size", 3), ("ksize", 3), ("border", 4)]
+    assert sig(feature.corner_harris) == [("mat", E), ("block_size", E), ("ksize", 3), ("k", 0.04), ("border", 4)]
+    assert sig(feature.good_features_to_track) == [("mat", E), ("max_corners", E), ("quality_thresh", 0.01), ("min_distance", 10), ("mask", None),
+                                                   ("block_size", 3), ("use_harris", False), ("k", 0.04)]
+    m = f.install()
+    assert all(hasattr(m, n) for n in ("goodFeaturesToTrack", "cornerMinEigenVal", "cornerHarris"))
+
+
+def test_outside_path_names_still_raise_and_point_at_the_new_ones():
+    from vision.utils import feature
+    for name in ("find_corners", "find_circles", "find_line_segments"):
+        with pytest.raises(NotImplementedError):
+            getattr(feature, name)(np.zeros((8, 8), np.uint8))
+    text = open(os.path.join(ROOT, "cuauv-vision-pipeline_amd", "vision", "utils", "feature.py")).read()
+    above = text[:text.index('find_corners = _outside_path("find_corners")')][-1200:]
+    assert "good_features_to_track" in above and "corner_min_eigen_val" in above and "4.24" in above
+
+
+def test_facade_refuses_what_is_outside_the_contract_before_it_needs_a_device():
+    from vision import cv2_facade as f
+    img = np.zeros((9, 11), np.uint8)
+    bad_images = (np.zeros((9, 11), np.uint16), np.zeros((9, 11), np.float32), np.zeros((9, 11, 3), np.uint8), np.zeros((0, 11), np.uint8), None)
+    for bad in bad_images:
+        for call in (lambda: f.cornerMinEigenVal(bad, 3), lambda: f.cornerHarris(bad, 3, 3, 0.04), lambda: f.goodFeaturesToTrack(bad, 10, 0.01, 5)):
+            with pytest.raises(f.error):
+                call()
+    for call in (lambda: f.cornerMinEigenVal(img, 0), lambda: f.cornerMinEigenVal(img, 32), lambda: f.cornerMinEigenVal(img, 3, ksize=5),
+                 lambda: f.cornerMinEigenVal(img, 3, ksize=7), lambda: f.cornerMinEigenVal(img, 3, ksize=-1), lambda: f.cornerMinEigenVal(img, 3, borderType=f.BORDER_WRAP),
+                 lambda: f.cornerMinEigenVal(img, 3, borderType=5), lambda: f.cornerHarris(img, 3, 5, 0.04), lambda: f.cornerHarris(img, 3, 3, float("nan")),
+                 lambda: f.cornerHarris(img, 32, 3, 0.04), lambda: f.cornerHarris(img, 3, 3, 0.04, borderType=f.BORDER_WRAP),
+                 lambda: f.goodFeaturesToTrack(img, 10, 0.01, 5, gradientSize=5), lambda: f.goodFeaturesToTrack(img, 10, 0.0, 5),
+                 lambda: f.goodFeaturesToTrack(img, 10, -1.0, 5), lambda: f.goodFeaturesToTrack(img, 10, float("inf"), 5),
+                 lambda: f.goodFeaturesToTrack(img, 10, float("nan"), 5), lambda: f.goodFeaturesToTrack(img, 10, 0.01, -1),
+                 lambda: f.goodFeaturesToTrack(img, 10, 0.01, float("nan")), lambda: f.goodFeaturesToTrack(img, 10, 0.01, 5, blockSize=0),
+                 lambda: f.goodFeaturesToTrack(img, 10, 0.01, 5, blockSize=32), lambda: f.goodFeaturesToTrack(img, 10, 0.01, 5, mask=np.zeros((9, 10), np.uint8)),
+                 lambda: f.goodFeaturesToTrack(img, 10, 0.01, 5, mask=np.zeros((9, 11), np.float32)),
+                 lambda: f.goodFeaturesToTrack(img, 10, 0.01, 5, mask=np.zeros((9, 11, 3), np.uint8)),
+                 lambda: f.goodFeaturesToTrack(img, 10, 0.01, 5, k=float("inf"))):
+        with pytest.raises(f.error):
+            call()
+
+
+def test_c_refusals_come_from_the_arguments_alone_and_write_nothing():
+    """Without a context an admitted call fails too (VP_ERR_INVALID, silently): what tells the refusals apart is the reason they leave in
+    vp_last_error(NULL), which an admitted call does not touch."""
+    from vision import _vp
+    lib = C.CDLL(_vp.LIB_PATH)
+    for name in NEW + ["vp_last_error"]:
+        fn = getattr(lib, name)
+        fn.restype, fn.argtypes = _vp._SIGS[name]
+    src = np.arange(35, dtype=np.uint8).reshape(5, 7)
+    mask = np.full((5, 7), 255, np.uint8)
+    dst = np.full((5, 7), 77.0, np.float32)
+    xy = np.full((16, 2), 77.0, np.float32)
+    n = C.c_int(77)
+    p = lambda a: a.ctypes.data
+    why = lambda: lib.vp_last_error(None).decode()
+    INF, NAN = float("inf"), float("nan")
+
+    def put_marker():
+        assert lib.vp_corner_response_u8(None, None, 7, 7, 5, 3, 3, 0, 0.04, 4, p(dst)) == _vp.ERR_INVALID
+        return why()
+
+    marker = put_marker()
+    assert "pointer" in marker
+
+    def admitted(rc):
+        assert rc == _vp.ERR_INVALID and why() == marker, why()
+
+    def refused(rc, words):
+        assert rc == _vp.ERR_INVALID and words in why(), (words, why())
+        assert put_marker() == marker
+
+    for fn in (lib.vp_corner_response_u8, lib.vp_corner_response_dev):
+        call = lambda stride=7, w=7, h=5, block=3, ksize=3, harris=0, k=0.04, border=4: fn(None, p(src), stride, w, h, block, ksize, harris, k, border, p(dst))
+        admitted(call())
+        for border in (0, 1, 2, 4, 4 | 16):
+            admitted(call(border=border))
+        for block in (1, 2, 31):
+            admitted(call(block=block, harris=1))
+        admitted(call(stride=9))
+        refused(call(w=0), "at least 1")
+        refused(call(h=-1), "at least 1")
+        refused(call(w=65536, stride=65536), "65535")
+        refused(call(h=65536), "65535")
+        refused(call(w=65535, stride=65535, h=65535), "2^28")
+        refused(call(stride=6), "stride")
+        refused(call(block=0), "1..31")
+        refused(call(block=32), "1..31")
+        for ksize in (5, 7, -1, 1):
+            refused(call(ksize=ksize), "ksize 3")
+        refused(call(border=3), "border")
+        refused(call(border=5), "border")
+        refused(call(harris=1, k=NAN), "finite")
+        refused(call(harris=1, k=INF), "finite")
+        refused(fn(None, p(src), 7, 7, 5, 3, 3, 0, 0.04, 4, None), "pointer")
+    refused(lib.vp_corner_response_dev(None, p(dst), 28, 7, 5, 3, 3, 0, 0.04, 4, p(dst)), "overlaps")
+    refused(lib.vp_corner_response_dev(None, p(src), 7, 7, 5, 3, 3, 0, 0.04, 4, p(dst) + 2), "aligned")
+
+    def host(stride=7, w=7, h=5, mc=0, q=0.01, md=1.0, m=None, ms=0, mw=0, mh=0, block=3, harris=0, k=0.04, cap=16, out=xy, cnt=n):
+        return lib.vp_good_features_u8(None, p(src), stride, w, h, mc, q, md, None if m is None else p(m), ms, mw, mh, block, harris, k,
+                                       None if out is None else p(out), cap, None if cnt is None else C.byref(cnt))
+
+    def dev(stride=7, w=7, h=5, mc=0, q=0.01, md=1.0, m=None, ms=0, mw=0, mh=0, block=3, harris=0, k=0.04, cap=16, out=xy, cnt=n, bits=None):
+        return lib.vp_good_features_dev(None, p(src), stride, w, h, mc, q, md, None if m is None else p(m), ms, mw, mh, bits, block, harris, k,
+                                        None if out is None else p(out), cap, None if cnt is None else C.byref(cnt))
+
+    for call in (host, dev):
+        admitted(call())
+        admitted(call(m=mask, ms=7, mw=7, mh=5))
+        admitted(call(m=mask, ms=9, mw=7, mh=5, md=0.0, mc=-3, q=5.0, harris=1, block=31))
+        admitted(call(cap=0, out=None))
+        admitted(call(md=INF))
+        refused(call(w=0), "at least 1")
+        refused(call(h=65536), "65535")
+        refused(call(stride=6), "stride")
+        refused(call(block=0), "1..31")
+        refused(call(block=32), "1..31")
+        for q in (0.0, -0.5, INF, NAN):
+            refused(call(q=q), "qualityLevel")
+        refused(call(md=-0.5), "minDistance")
+        refused(call(md=NAN), "minDistance")
+        refused(call(k=NAN, harris=1), "finite")
+        refused(call(cap=-1), "capacity")
+        refused(call(m=mask, ms=7, mw=6, mh=5), "size of the image")
+        refused(call(m=mask, ms=7, mw=7, mh=6), "size of the image")
+        refused(call(m=mask, ms=6, mw=7, mh=5), "mask's stride")
+        refused(call(out=None), "pointer")
+        refused(call(cnt=None), "pointer")
+    admitted(dev(bits=p(mask), mw=7, mh=5))
+    refused(dev(bits=p(mask) + 4, mw=7, mh=5), "8-byte")
+    refused(dev(bits=p(mask), mw=7, mh=4), "size of the image")
+    assert (dst == 77.0).all() and (xy == 77.0).all() and n.value == 77, "a result was written without a context"
