@@ -261,16 +261,24 @@ int vpk_letterbox(vp_ctx* ctx, const uint8_t* d_src, int sw, int sh, int dw, int
 }
 
 // ---- NMS ----------------------------------------------------------------------------------------------------------------------
-// rank[i] = position of box i in descending score order (ties: lower index first); order[rank[i]] = i
+// rank[i] = position of box i in the score order; order[rank[i]] = i.  The order is total for every float32 input: numbers descending
+// (+inf first, -inf last, -0.0 == 0.0 a tie), every number before every NaN, ties and NaNs among themselves by lower index.  That is
+// the lexicographic order of the key (is NaN, -score, index), whose last part differs for any two boxes: of two boxes exactly one
+// precedes the other and "precedes" is transitive, so the n counts below are a permutation of 0..n-1 and every slot of order[0..n)
+// is written exactly once.  (With the bare `t > s || (t == s && j < i)` every NaN-scored box counted 0 and the slots they should
+// have taken stayed unwritten.)  A NaN-scored box is an ordinary candidate at the end of the order.
 __global__ __launch_bounds__(256) void k_nms_rank(const float* __restrict__ scores, int n, int* __restrict__ order)
 {
     const int i = blockIdx.x * 256 + threadIdx.x;
     if (i >= n) return;
     const float s = scores[i];
+    const bool s_nan = s != s;
     int r = 0;
     for (int j = 0; j < n; j++) {
         const float t = scores[j];
-        r += (t > s || (t == s && j < i)) ? 1 : 0;
+        const bool t_nan = t != t;
+        const bool before = s_nan ? (!t_nan || j < i) : (t > s || (t == s && j < i));   // (a NaN t compares false both ways)
+        r += before ? 1 : 0;
     }
     order[r] = i;
 }

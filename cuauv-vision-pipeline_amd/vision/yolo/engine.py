@@ -20,6 +20,7 @@ from vision.yolo import ops
 
 DEFAULT_NAMES = ("torpedo_board", "shark_hole", "saw_hole", "pole_red", "pole_white", "shark", "saw", "gate_behind", "bin_shark", "bin_saw",
                  "bin", "spoon", "cup", "pink_basket", "yellow_basket")     # the classes modules/yolo.py:130-151 dispatches on
+MAX_NMS = 16384                   # candidates that go into the suppression: the capacity of vp_nms_* (the published default is 30000)
 
 
 def letterbox_shape(h, w, imgsz=640, stride=32):
@@ -154,15 +155,18 @@ class YOLO:
         return t.unsqueeze(0), geom
 
     def postprocess(self, pred, geom, orig_shape, track=False):
-        """(4 + nc + 1, anchors) raw output of one frame -> Results."""
+        """(4 + nc + 1, anchors) raw output of one frame -> Results.  At most MAX_NMS candidates, the most confident ones, go into the
+        suppression.  The published default for that cut is 30000; it is 16384 here because that is what the suppression kernel takes
+        (vp_nms_*: n <= 16384) - with 30000, a frame with 16385..30000 candidates above the threshold raised instead of returning
+        detections."""
         import torch
         nc = len(self.names)
         p = pred.t()                                                  # (A, 4 + nc + 1)
         conf, cls = p[:, 4:4 + nc].max(1)
         keep = conf > self.conf
         p, conf, cls = p[keep], conf[keep], cls[keep]
-        if p.shape[0] > 30000:
-            top = conf.topk(30000).indices
+        if p.shape[0] > MAX_NMS:
+            top = conf.topk(MAX_NMS).indices
             p, conf, cls = p[top], conf[top], cls[top]
         boxes = torch.cat([p[:, :4], p[:, -1:]], 1)
         if boxes.shape[0]:
@@ -203,7 +207,10 @@ class YOLO:
                         self.model(static_in)
                 torch.cuda.current_stream(self.device).wait_stream(side)
                 graph = torch.cuda.CUDAGraph()
-                with torch.cuda.graph(graph):
+                # thread_local: inside a module the capture runs beside the runtime's frame feeder, a native thread that uploads every
+                # arriving frame on a stream of its own.  Under the default mode ("global") a HIP call of any other thread can
+                # invalidate the capture, and the first frame of a module then failed whenever an upload fell into it.
+                with torch.cuda.graph(graph, capture_error_mode="thread_local"):
                     static_out = self.model(static_in)
                 g = self._graphs[key] = (graph, static_in, static_out)
             graph, static_in, static_out = g

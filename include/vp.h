@@ -407,9 +407,12 @@ int vp_chain_run_contours_host(vp_ctx* ctx, const vp_chain_desc* desc, const vp_
  * vp_letterbox_*: src (h,w,3) BGR uint8 -> dst (3,dst_h,dst_w) float32 RGB in [0,1]; the resize is cv2.resize INTER_LINEAR's
  * 8-bit arithmetic; geom_out (3 floats, may be NULL) = {scale r, left pad, top pad} for mapping boxes back.
  * vp_nms_*: boxes (n,4) x1,y1,x2,y2 (rotated: (n,5) x,y,w,h,angle[rad]), scores (n); keep_out receives up to max_keep original
- * indices in descending score order (ties: lower index first).  rotated = 0: greedy, suppress IoU > thr.  rotated = 1:
+ * indices in descending score order (ties: lower index first).  The order is total for any float32 scores: +inf first, -inf
+ * last among the numbers, -0.0 == 0.0 a tie, every number before every NaN, NaNs among themselves by lower index; a NaN-scored
+ * box is an ordinary candidate at the end of the order (kept if nothing suppresses it and max_keep allows).  rotated = 0:
+ * greedy, suppress IoU > thr.  rotated = 1:
  * probabilistic IoU of the boxes' Gaussian models; a box is dropped when any higher-scored box overlaps it by >= thr.
- * n <= 16384.  The _dev forms take device pointers (e.g. tensors of a PyTorch-ROCm model via data_ptr()), enqueue on the
+ * n <= 16384 (VP_ERR_UNSUPPORTED above).  The _dev forms take device pointers (e.g. tensors of a PyTorch-ROCm model via data_ptr()), enqueue on the
  * context's stream and return without synchronising. */
 /* cv2.threshold(src, thresh, maxval, type)[1] on 8-bit data of any channel count (utils/color.py:124-199: binary_threshold,
  * binary_threshold_inv, max_threshold, above_threshold, below_threshold): the comparison is against floor(thresh), maxval is
