@@ -270,6 +270,16 @@ int vpk_corner_response(vp_ctx* ctx, const uint8_t* d_src, size_t stride, int w,
 int vpk_corner_candidates(vp_ctx* ctx, const float* d_resp, int w, int h, const uint8_t* d_mask, size_t mstride, const u64* d_bits, double quality,
                           u32* d_cnt, u64* d_keys, size_t kcap);
 
+// ---- distance transform and min / max search (vp_dist.hip; the plan: vp_dist_plan.h) --------------------------
+// cv2.distanceTransform of sizes vp_distance_transform_refusal admitted: zero pixels are the sources; d_bits (nullable) is the source's
+// bit plane, read instead of its bytes; d_g: vp_dist_ws_bytes(w, h) of workspace; d_dst: rows of dstride bytes, float32 or uint8 by
+// depth.  Two launches, enqueued.  vpk_min_max_loc: d_out receives the two keys vp_min_max_loc_decode reads; d_mask (rows of mstride
+// bytes) or d_mbits (its bit plane) admit pixels, both nullable; one launch behind the zeroing of d_out, enqueued.
+int vpk_distance_transform(vp_ctx* ctx, const uint8_t* d_src, size_t stride, int w, int h, const unsigned long long* d_bits, int metric, int depth, uint16_t* d_g,
+                           void* d_dst, size_t dstride);
+int vpk_min_max_loc(vp_ctx* ctx, const void* d_src, size_t stride, int w, int h, int depth, const uint8_t* d_mask, size_t mstride,
+                    const unsigned long long* d_mbits, unsigned long long* d_out);
+
 // ---- morphology (vp_morph.hip) ---------------------------------------------------------------
 struct vp_bitstage { int dilate; int l, r, u, d; };  // window [-l, r] x [-u, d]
 #define VP_MAX_STAGES 32

@@ -54,6 +54,7 @@ DEPTH_8U, DEPTH_16S, DEPTH_32F, DEPTH_64F = 0, 3, 5, 6
 DEPTH_32S = 4
 BORDER_CONSTANT, BORDER_REPLICATE, BORDER_REFLECT, BORDER_REFLECT_101, BORDER_ISOLATED = 0, 1, 2, 4, 16
 INTER_NEAREST, INTER_LINEAR = 0, 1
+DIST_L1, DIST_L2, DIST_C = 1, 2, 3
 WARP_INVERSE_MAP = 16
 PROF_KERNELS = 15
 
@@ -268,6 +269,11 @@ _SIGS = {
                                       C.c_int, C.c_int, C.c_int, C.c_double, C.c_void_p, C.c_int, C.c_void_p]),
     "vp_good_features_dev": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_int, C.c_int, C.c_int, C.c_double, C.c_double, C.c_void_p, C.c_size_t, C.c_int,
                                        C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_double, C.c_void_p, C.c_int, C.c_void_p]),
+    "vp_distance_transform_u8": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p]),
+    "vp_distance_transform_dev": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_size_t]),
+    "vp_min_max_loc_u8": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_size_t, C.c_int, C.c_int, C.c_void_p]),
+    "vp_min_max_loc_dev": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_size_t, C.c_int, C.c_int, C.c_void_p,
+                                     C.c_void_p]),
 }
 
 

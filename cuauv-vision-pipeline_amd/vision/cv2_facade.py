@@ -1126,6 +1126,35 @@ def goodFeaturesToTrack(image, maxCorners, qualityLevel, minDistance, corners=No
     return found if found is None else _into(corners, found)
 
 
+# ---- distances (libvp vp_dist.hip): exact L2, L1 and C distances to the nearest zero pixel, DESIGN.md section 4.25 -------------------------
+DIST_USER, DIST_L1, DIST_L2, DIST_C, DIST_L12, DIST_FAIR, DIST_WELSCH, DIST_HUBER = -1, 1, 2, 3, 4, 5, 6, 7
+DIST_MASK_3, DIST_MASK_5, DIST_MASK_PRECISE = 3, 5, 0
+
+
+def distanceTransform(src, distanceType, maskSize, dst=None, dstType=CV_32F):
+    """cv2.distanceTransform on a uint8 single-channel image in cv2's positional order.  DIST_L2 with DIST_MASK_PRECISE: the correctly
+    rounded float32 root of the exact squared distance; DIST_L1 and DIST_C with any mask size (cv2 forces 3): exact integers, DIST_L1
+    also as CV_8U.  DIST_L2 with a 3x3 or 5x5 mask is cv2's chamfer approximation, which is not restated.  An
+    image without a zero pixel gives +inf (255) everywhere.  A DeviceMat stays in HBM (vision.utils.feature.distance_transform)."""
+    if distanceType not in (DIST_L1, DIST_L2, DIST_C):
+        raise error("distanceTransform: only DIST_L1, DIST_L2 and DIST_C are on the accelerated path")
+    if maskSize not in (DIST_MASK_3, DIST_MASK_5, DIST_MASK_PRECISE):
+        raise error("distanceTransform: maskSize must be DIST_MASK_3, DIST_MASK_5 or DIST_MASK_PRECISE")
+    if distanceType == DIST_L2 and maskSize != DIST_MASK_PRECISE:
+        raise error("distanceTransform: DIST_L2 only with DIST_MASK_PRECISE - the 3x3 and 5x5 chamfer approximations are not restated "
+                    "(DESIGN.md section 7)")
+    if dstType not in (CV_8U, CV_32F):
+        raise error("distanceTransform: dstType must be CV_8U or CV_32F")
+    src = _source("distanceTransform", src, "only uint8 images are on the accelerated path")
+    return _into(dst, _gather("distanceTransform", _feature.distance_transform, src, distanceType, np.uint8 if dstType == CV_8U else np.float32))
+
+
+def minMaxLoc(src, mask=None):
+    """cv2.minMaxLoc on a uint8 or float32 single-channel image: (minVal, maxVal, minLoc, maxLoc), ties to the first pixel in raster
+    order.  NaN pixels take no part; an empty mask gives (0.0, 0.0, (-1, -1), (-1, -1))."""
+    return _gather("minMaxLoc", _feature.min_max_loc, _device_source(src)[0], mask)
+
+
 def adaptiveThreshold(src, maxValue, adaptiveMethod, thresholdType, blockSize, C, dst=None):
     """cv2.adaptiveThreshold (utils/color.py:220-292) in cv2's positional order on CV_8UC1 images.  ADAPTIVE_THRESH_MEAN_C: the mean
     path (libvp vp_adaptive_threshold_mean_*, block sizes 3..151); ADAPTIVE_THRESH_GAUSSIAN_C: the exact Gaussian-weighted mean

@@ -559,6 +559,104 @@ def good_features_to_track(mat, max_corners: int, quality_thresh: float = 0.01, 
     return out[:n.value].copy() if n.value else None
 
 
+# ---- distances (libvp vp_dist.hip) ---------------------------------------------------------------------------
+DIST_L1, DIST_L2, DIST_C = _vp.DIST_L1, _vp.DIST_L2, _vp.DIST_C
+DIST_MAX_SIDE = 4096
+_FLOAT_OR_BYTE = (np.dtype(np.uint8), np.dtype(np.float32))
+
+
+def _valid_bit_plane(mat, ctx):
+    """the device pointer of the bit plane a known 0 / 255 mask still carries on ctx, or None"""
+    if not mat.binary:
+        return None
+    bits = mat.bit_plane(ctx)
+    return bits.ptr if (bits is not None and mat._dev_ok and mat._ctx is ctx) else None
+
+
+def _dist_side(mat):
+    if max(mat.shape) > DIST_MAX_SIDE:
+        raise ValueError("sides above 4096 are outside the accelerated path")
+
+
+def distance_transform(mat, metric: int = DIST_L2, dst_type=np.float32):
+    """cv2.distanceTransform of a uint8 single-channel image: the distance of every pixel to the nearest zero
+    pixel.  DIST_L2 is cv2's DIST_MASK_PRECISE value, the correctly rounded float32 root of the exact integer dx^2 + dy^2; DIST_L1 is
+    |dx| + |dy| and DIST_C max(|dx|, |dy|), exact integers.  float32 (h, w), or uint8 min(d, 255) for DIST_L1 with dst_type uint8.
+    An image without a zero pixel gives +inf (255) everywhere, the distance to the empty set.  Sides up to 4096.  numpy in gives numpy
+    out, a DeviceMat gives a DeviceMat that stays in HBM (libvp vp_distance_transform_*); a mask that still carries its bit plane is
+    read through that, at an eighth of a byte per pixel."""
+    mat, _ = image_source(mat, single="distance_transform takes a single-channel image")
+    _dist_side(mat)
+    metric, dst_type = int(metric), np.dtype(dst_type)
+    if metric not in (DIST_L1, DIST_L2, DIST_C):
+        raise ValueError("the metric must be DIST_L1, DIST_L2 or DIST_C")
+    if dst_type not in _FLOAT_OR_BYTE:
+        raise ValueError("the result must be CV_8U or CV_32F")
+    if dst_type == np.uint8 and metric != DIST_L1:
+        raise ValueError("a CV_8U result only with DIST_L1")
+    depth = _vp.DEPTH_8U if dst_type == np.uint8 else _vp.DEPTH_32F
+    h, w = mat.shape
+    lib = _vp.lib()
+
+    def on_device(ctx, s, d):
+        return lib.vp_distance_transform_dev(ctx.handle, s, w, w, h, _valid_bit_plane(mat, ctx), metric, depth, d, w * dst_type.itemsize)
+
+    return run_operator(mat, (h, w), dst_type, lambda ctx, s, d: lib.vp_distance_transform_u8(ctx.handle, s, w, h, metric, depth, d), on_device)
+
+
+class _MinMaxLoc(_vp.C.Structure):
+    _fields_ = [("min_val", _vp.C.c_double), ("max_val", _vp.C.c_double), ("min_x", _vp.C.c_int), ("min_y", _vp.C.c_int), ("max_x", _vp.C.c_int),
+                ("max_y", _vp.C.c_int)]
+
+
+def min_max_loc(mat, mask=None):
+    """cv2.minMaxLoc of a uint8 or float32 single-channel image: (minVal, maxVal, minLoc, maxLoc), Python floats and (x, y) pairs; among
+    equal values the first pixel in raster order, at both ends.  mask (uint8, the image's size): only its non-zero pixels take part.
+    float32 NaN pixels take no part; +inf and -inf order as numbers.  When no pixel takes part: (0.0, 0.0, (-1, -1), (-1, -1)).  One
+    reduction on the GPU (libvp vp_min_max_loc_*): a device image and a device mask are read where they are (a mask that still
+    carries its bit plane through that), and 32 bytes come back."""
+    mat, _ = image_source(mat, _FLOAT_OR_BYTE, single="min_max_loc takes a single-channel image")
+    _dist_side(mat)
+    h, w = mat.shape
+    if mask is not None:
+        mask, _ = image_source(mask, single="the mask must be a single-channel image",
+                               said=("the mask must be uint8", "the mask must be a non-empty (h, w) image", None))
+        if tuple(mask.shape) != (h, w):
+            raise ValueError("the mask must have the size of the image")
+    depth = _vp.DEPTH_8U if mat.dtype == np.uint8 else _vp.DEPTH_32F
+    ctx = _vp.default_context()
+    lib = _vp.lib()
+    out = _MinMaxLoc()
+    mw, mh = (w, h) if mask is not None else (0, 0)
+    if isinstance(mat, DeviceMat):
+        mat.refresh_device(ctx)
+        mp = bp = None
+        if mask is not None:
+            mask = device_image(ctx, mask, 1)
+            bp = _valid_bit_plane(mask, ctx)
+            mp = mask.dev_ptr
+        rc = lib.vp_min_max_loc_dev(ctx.handle, mat.dev_ptr, w * mat.itemsize, w, h, depth, mp, w, mw, mh, bp, _vp.C.addressof(out))
+    else:
+        mat = np.ascontiguousarray(mat)
+        if mask is not None:
+            mask = np.ascontiguousarray(to_host_readonly(mask))
+        rc = lib.vp_min_max_loc_u8(ctx.handle, mat.ctypes.data, w * mat.itemsize, w, h, depth, None if mask is None else mask.ctypes.data, w, mw, mh,
+                                   _vp.C.addressof(out))
+    _vp.check(rc, ctx.handle)
+    return out.min_val, out.max_val, (out.min_x, out.min_y), (out.max_x, out.max_y)
+
+
+def largest_inscribed_circle(mask):
+    """((x, y), radius) of the largest circle inside the non-zero region of a uint8 mask: distance_transform (DIST_L2) followed by
+    min_max_loc, the first deepest pixel in raster order.  The radius is the distance from that pixel's centre to the centre of the
+    nearest zero pixel, so a disc drawn with it just touches that pixel.  A DeviceMat mask never visits the host in between: the float32
+    map stays in HBM and 32 bytes come back.  A mask without a zero pixel is refused (ValueError): the radius would be infinite."""
+    _, radius, _, centre = min_max_loc(distance_transform(mask, DIST_L2))
+    if math.isinf(radius):
+        raise ValueError("the mask has no zero pixel: the largest inscribed circle is unbounded")
+    return centre, radius
+
+
 def hough_circles(mat, dp: float, min_dist: float, param1: float = 100, param2: float = 100, min_radius: int = 0, max_radius: int = 0):
     """cv2.HoughCircles(mat, cv2.HOUGH_GRADIENT, dp, min_dist, None, param1, param2, min_radius, max_radius) on the GPU (libvp
     vp_hough_circles_*): (1, N, 3) float32 (x, y, r) in cv2's order, or None when no circle is found.  A device image is read where it

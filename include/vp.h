@@ -776,6 +776,32 @@ int vp_good_features_dev(vp_ctx* ctx, const uint8_t* src_dev, size_t stride, int
                          const uint8_t* mask_dev, size_t mask_stride, int mask_w, int mask_h, const unsigned long long* mask_bits_dev, int block_size,
                          int harris, double k, float* corners_host, int capacity, int* n_corners);
 
+/* ---- distances: cv2.distanceTransform (DIST_L2 with DIST_MASK_PRECISE, DIST_L1, DIST_C) and cv2.minMaxLoc ------------------------- *
+ * vp_distance_transform_u8 / vp_distance_transform_dev: zero pixels of the uint8 source are the sources; every pixel gets its distance
+ *   to the nearest one (tests/dist_restate.py).  metric VP_DIST_L2: sqrtf((float)D2), D2 the minimum of
+ *   dx dx + dy dy in integers, the root correctly rounded; VP_DIST_L1: |dx| + |dy|; VP_DIST_C: max(|dx|, |dy|).  dst_depth VP_DEPTH_32F,
+ *   or VP_DEPTH_8U with VP_DIST_L1 only: min(d, 255).  An image without a zero pixel gives +inf everywhere (255 for VP_DEPTH_8U).
+ *   The host form takes a packed image, gives a packed result and synchronises.  The device form reads rows of `stride` bytes and
+ *   writes rows of dst_stride bytes, enqueues two launches and never synchronises; src_bits_dev (nullable) is the source's bit plane
+ *   in the layout of vp_inrange_u8_bits_dev, read instead of its bytes - its bits past w are not looked at.
+ * vp_min_max_loc_u8 / vp_min_max_loc_dev: cv2.minMaxLoc of a single-channel image of depth VP_DEPTH_8U or VP_DEPTH_32F, rows of
+ *   `stride` bytes.  out receives struct { double min_val, max_val; int min_x, min_y, max_x, max_y; } (host memory).  Among equal
+ *   values the first pixel in raster order wins at both ends.  Only pixels where the mask (nullable; mask_w x mask_h bytes, rows of
+ *   mask_stride) is non-zero take part; mask_bits_dev (nullable) is the mask's bit plane, read instead of its bytes.  NaN pixels take
+ *   no part; +inf and -inf order as numbers.  When no pixel takes part: (0, 0, (-1, -1), (-1, -1)).  Both synchronise.
+ * Refused with VP_ERR_INVALID before anything is launched or written (the message names the reason): a missing pointer, a bit plane
+ *   without its source, w or h outside 1..4096, a stride below the row, a result or float32 stride that is not a multiple of the
+ *   element size, an unknown metric, VP_DEPTH_8U with anything but VP_DIST_L1, a depth other than 8U or 32F, a mask whose size differs
+ *   from the image's or whose stride is below its row, a result that overlaps the source. */
+enum { VP_DIST_L1 = 1, VP_DIST_L2 = 2, VP_DIST_C = 3 };
+int vp_distance_transform_u8(vp_ctx* ctx, const uint8_t* src_host, int w, int h, int metric, int dst_depth, void* dst_host);
+int vp_distance_transform_dev(vp_ctx* ctx, const uint8_t* src_dev, size_t stride, int w, int h, const unsigned long long* src_bits_dev, int metric,
+                              int dst_depth, void* dst_dev, size_t dst_stride);
+int vp_min_max_loc_u8(vp_ctx* ctx, const void* src_host, size_t stride, int w, int h, int depth, const uint8_t* mask_host, size_t mask_stride, int mask_w,
+                      int mask_h, void* out_host);
+int vp_min_max_loc_dev(vp_ctx* ctx, const void* src_dev, size_t stride, int w, int h, int depth, const uint8_t* mask_dev, size_t mask_stride, int mask_w,
+                       int mask_h, const unsigned long long* mask_bits_dev, void* out_host);
+
 /* ---- device memory helpers (so a host program needs no HIP binding of its own) --------- */
 int vp_dev_alloc(vp_ctx* ctx, size_t bytes, void** dev_ptr);
 int vp_dev_free(vp_ctx* ctx, void* dev_ptr);    /* ctx may be NULL (memory that outlived its context) */
