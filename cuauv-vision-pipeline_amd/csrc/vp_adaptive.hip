@@ -113,32 +113,39 @@ static int agauss_int_taps(int n, u32* t, int* e_out)
 // used; slot `keep` (one the same call still needs, or -1) is never the one replaced.
 static int agauss_slot(vp_ctx* ctx, int n, int keep, int* slot, const u32** d_taps, u32* h_taps, int* e)
 {
-    if (!ctx->agauss_taps) {
+    if (!ctx->agauss.taps) {
         void* p = nullptr;
         VP_HIP(ctx, hipMalloc(&p, 8 * AG_HALF * sizeof(u32)));
-        ctx->agauss_taps = (u32*)p;
+        ctx->agauss.taps = (u32*)p;
     }
     for (int s = 0; s < 8; s++)
-        if (ctx->agauss_n[s] == n) {
-            *d_taps = ctx->agauss_taps + s * AG_HALF;
-            *e = ctx->agauss_e[s];
-            memcpy(h_taps, ctx->agauss_host[s], (n / 2 + 1) * sizeof(u32));
+        if (ctx->agauss.n[s] == n) {
+            *d_taps = ctx->agauss.taps + s * AG_HALF;
+            *e = ctx->agauss.e[s];
+            memcpy(h_taps, ctx->agauss.host[s], (n / 2 + 1) * sizeof(u32));
             *slot = s;
             return VP_OK;
         }
     if (agauss_int_taps(n, h_taps, e) != VP_OK) return vp_fail(ctx, VP_ERR_UNSUPPORTED, "adaptive threshold: taps outside the integer form");
-    int s = ctx->agauss_next;
+    int s = ctx->agauss.next;
     if (s == keep) s = (s + 1) & 7;
-    ctx->agauss_next = (s + 1) & 7;
+    ctx->agauss.next = (s + 1) & 7;
     VP_HIP(ctx, hipStreamSynchronize(ctx->stream));      // work queued earlier may still read the slot
-    ctx->agauss_n[s] = 0;
-    VP_HIP(ctx, hipMemcpy(ctx->agauss_taps + s * AG_HALF, h_taps, (n / 2 + 1) * sizeof(u32), hipMemcpyHostToDevice));
-    memcpy(ctx->agauss_host[s], h_taps, (n / 2 + 1) * sizeof(u32));
-    ctx->agauss_n[s] = n;
-    ctx->agauss_e[s] = *e;
-    *d_taps = ctx->agauss_taps + s * AG_HALF;
+    ctx->agauss.n[s] = 0;
+    VP_HIP(ctx, hipMemcpy(ctx->agauss.taps + s * AG_HALF, h_taps, (n / 2 + 1) * sizeof(u32), hipMemcpyHostToDevice));
+    memcpy(ctx->agauss.host[s], h_taps, (n / 2 + 1) * sizeof(u32));
+    ctx->agauss.n[s] = n;
+    ctx->agauss.e[s] = *e;
+    *d_taps = ctx->agauss.taps + s * AG_HALF;
     *slot = s;
     return VP_OK;
+}
+
+void vp_adaptive_teardown(vp_ctx* ctx)
+{
+    if (ctx->agauss.taps) (void)hipFree(ctx->agauss.taps);
+    ctx->agauss.taps = nullptr;
+    for (int& n : ctx->agauss.n) n = 0;     // no slot holds taps any more
 }
 
 size_t vp_agauss_ws_bytes(int w, int h, int n) { return vp_align((size_t)w * h * n * 8); }

@@ -18,6 +18,25 @@ int vp_fail(vp_ctx* ctx, int code, const char* what, hipError_t e)
     return code;
 }
 
+// the profile's records: the events that exist among its 2 * cap, and the two arrays (vp_profile_begin, vp_destroy)
+static void prof_release(vp_prof& P)
+{
+    for (int i = 0; P.ev && i < 2 * P.cap; i++)
+        if (P.ev[i]) (void)hipEventDestroy(P.ev[i]);
+    free(P.ev);
+    free(P.ids);
+    P = vp_prof{};
+}
+
+// Every failure after the allocation leaves through create_failed: the error text set at the failure stays (vp_destroy sets none)
+// and vp_destroy frees exactly what exists by then.
+static vp_ctx* create_failed(vp_ctx* ctx, int code, const char* what, hipError_t e = hipSuccess)
+{
+    vp_fail(nullptr, code, what, e);
+    vp_destroy(ctx);
+    return nullptr;
+}
+
 extern "C" {
 
 int vp_version(void) { return 100; }
@@ -78,56 +97,44 @@ vp_ctx* vp_create(int device)
     if (!ctx) return nullptr;
     memset(ctx, 0, sizeof *ctx);
     ctx->device = device;
+    vp_options_defaults(&ctx->opt, getenv);
     hipDeviceProp_t prop;
-    if ((e = hipGetDeviceProperties(&prop, device)) != hipSuccess) { vp_fail(nullptr, VP_ERR_HIP, "hipGetDeviceProperties", e); delete ctx; return nullptr; }
+    if ((e = hipGetDeviceProperties(&prop, device)) != hipSuccess) return create_failed(ctx, VP_ERR_HIP, "hipGetDeviceProperties", e);
     ctx->num_cu = prop.multiProcessorCount > 0 ? prop.multiProcessorCount : 256;
-    if ((e = hipStreamCreateWithFlags(&ctx->own_stream, hipStreamNonBlocking)) != hipSuccess) { vp_fail(nullptr, VP_ERR_HIP, "hipStreamCreate", e); delete ctx; return nullptr; }
+    if ((e = hipStreamCreateWithFlags(&ctx->own_stream, hipStreamNonBlocking)) != hipSuccess) return create_failed(ctx, VP_ERR_HIP, "hipStreamCreate", e);
     ctx->stream = ctx->own_stream;
-    hipEventCreate(&ctx->ev0);
-    hipEventCreate(&ctx->ev1);
-    ctx->chain_streams = 1;
-    if (const char* env = getenv("VP_CHAIN_STREAMS")) { const int v = atoi(env); if (v >= 1 && v <= 4) ctx->chain_streams = v; }
+    if ((e = hipEventCreate(&ctx->ev0)) != hipSuccess || (e = hipEventCreate(&ctx->ev1)) != hipSuccess) return create_failed(ctx, VP_ERR_HIP, "timer events", e);
     for (int i = 0; i < 4; i++) {
-        if (hipStreamCreateWithFlags(&ctx->aux[i], hipStreamNonBlocking) != hipSuccess) { vp_fail(nullptr, VP_ERR_HIP, "aux stream"); delete ctx; return nullptr; }
-        hipEventCreateWithFlags(&ctx->ev_join[i], hipEventDisableTiming);
+        if ((e = hipStreamCreateWithFlags(&ctx->chain.aux[i], hipStreamNonBlocking)) != hipSuccess) return create_failed(ctx, VP_ERR_HIP, "aux stream", e);
+        if ((e = hipEventCreateWithFlags(&ctx->chain.ev_join[i], hipEventDisableTiming)) != hipSuccess) return create_failed(ctx, VP_ERR_HIP, "aux event", e);
     }
-    hipEventCreateWithFlags(&ctx->ev_fork, hipEventDisableTiming);
-    if (hipStreamCreateWithFlags(&ctx->fb_stream, hipStreamNonBlocking) != hipSuccess) { vp_fail(nullptr, VP_ERR_HIP, "side stream"); delete ctx; return nullptr; }
-    hipEventCreateWithFlags(&ctx->ev_fb_fork, hipEventDisableTiming);
-    hipEventCreateWithFlags(&ctx->ev_fb_join, hipEventDisableTiming);
-    hipEventCreateWithFlags(&ctx->ev_upload, hipEventDisableTiming);
-    ctx->ccl_levels = 2;
-    ctx->ccl_mcap = -1;
-    ctx->flat_ops = 1;
-    ctx->blur_onepass = -1;
-    ctx->median_mask = -1;
-    ctx->label_moments_lds = -1;
-    if (const char* env = getenv("VP_OPT_MEDIAN_MASK")) { const int v = atoi(env); if (v == 0 || v == 1) ctx->median_mask = v; }
-    if (const char* env = getenv("VP_OPT_CLAHE_SPLIT")) { const int v = atoi(env); if (v >= 1 && v <= 64) ctx->clahe_split = v; }
-    for (size_t& v : ctx->c3_lds_set) v = 0;
-    if (const char* env = getenv("VP_CCL_LEVELS")) { const int v = atoi(env); if (v == 1 || v == 2) ctx->ccl_levels = v; }
-    if (const char* env = getenv("VP_OPT_CCL_CROWDED")) { const int v = atoi(env); if (v >= 0 && v <= 2) ctx->ccl_crowded_force = v; }
+    if ((e = hipEventCreateWithFlags(&ctx->chain.ev_fork, hipEventDisableTiming)) != hipSuccess) return create_failed(ctx, VP_ERR_HIP, "aux event", e);
+    if ((e = hipStreamCreateWithFlags(&ctx->chain.fb_stream, hipStreamNonBlocking)) != hipSuccess) return create_failed(ctx, VP_ERR_HIP, "side stream", e);
+    if ((e = hipEventCreateWithFlags(&ctx->chain.ev_fb_fork, hipEventDisableTiming)) != hipSuccess ||
+        (e = hipEventCreateWithFlags(&ctx->chain.ev_fb_join, hipEventDisableTiming)) != hipSuccess)
+        return create_failed(ctx, VP_ERR_HIP, "side stream event", e);
+    if ((e = hipEventCreateWithFlags(&ctx->ev_upload, hipEventDisableTiming)) != hipSuccess) return create_failed(ctx, VP_ERR_HIP, "upload event", e);
     // tables: gamma u16[256] | cbrt u16[2048] | sdiv i32[256] | hdiv i32[256]
     std::vector<uint16_t> gamma(256), cbrt(3072);
     std::vector<int32_t> sdiv(256), hdiv(256);
     int32_t labC[9];
     vp_host_tables(gamma.data(), cbrt.data(), sdiv.data(), hdiv.data(), labC);
     static const int32_t expectC[9] = {1777, 1541, 778, 871, 2929, 296, 73, 448, 3575};
-    if (memcmp(labC, expectC, sizeof labC) != 0) { vp_fail(nullptr, VP_ERR_INVALID, "Lab coefficient table mismatch"); delete ctx; return nullptr; }
+    if (memcmp(labC, expectC, sizeof labC) != 0) return create_failed(ctx, VP_ERR_INVALID, "Lab coefficient table mismatch");
     const size_t bytes = 512 + 4096 + 1024 + 1024;
-    if ((e = hipMalloc(&ctx->d_tables, bytes + 256)) != hipSuccess) { vp_fail(nullptr, VP_ERR_NOMEM, "hipMalloc tables", e); delete ctx; return nullptr; }
+    if ((e = hipMalloc(&ctx->d_tables, bytes + 256)) != hipSuccess) return create_failed(ctx, VP_ERR_NOMEM, "hipMalloc tables", e);
     uint8_t* base = (uint8_t*)ctx->d_tables;
     hipMemcpy(base, gamma.data(), 512, hipMemcpyHostToDevice);
     hipMemcpy(base + 512, cbrt.data(), 4096, hipMemcpyHostToDevice);
     hipMemcpy(base + 512 + 4096, sdiv.data(), 1024, hipMemcpyHostToDevice);
     e = hipMemcpy(base + 512 + 4096 + 1024, hdiv.data(), 1024, hipMemcpyHostToDevice);
-    if (e != hipSuccess) { vp_fail(nullptr, VP_ERR_HIP, "table upload", e); hipFree(ctx->d_tables); delete ctx; return nullptr; }
+    if (e != hipSuccess) return create_failed(ctx, VP_ERR_HIP, "table upload", e);
     ctx->tab.gamma = (const uint16_t*)base;
     ctx->tab.cbrt = (const uint16_t*)(base + 512);
     ctx->tab.sdiv = (const int32_t*)(base + 512 + 4096);
     ctx->tab.hdiv = (const int32_t*)(base + 512 + 4096 + 1024);
-    ctx->cb_folds_own = (u32*)(base + bytes);       // a word of the context's own: workspace pointers do not survive a later call
-    hipMemset(ctx->cb_folds_own, 0, 4);
+    ctx->cb.folds_own = (u32*)(base + bytes);       // a word of the context's own: workspace pointers do not survive a later call
+    hipMemset(ctx->cb.folds_own, 0, 4);
     // Lab -> BGR tables: abToXZ_b i32[VP_LAB_AB_TAB] | LabToYF_b u16[512] | inverse gamma as bytes [4096]
     {
         std::vector<int32_t> abxz(VP_LAB_AB_TAB);
@@ -136,11 +143,11 @@ vp_ctx* vp_create(int device)
         vp_host_lab_inv_tables(yf.data(), abxz.data(), invg16.data(), nullptr);
         for (int i = 0; i < 4096; i++) invg[i] = (uint8_t)invg16[i];
         const size_t nab = (size_t)VP_LAB_AB_TAB * 4;
-        if ((e = hipMalloc(&ctx->d_labinv, nab + 1024 + 4096)) != hipSuccess) { vp_fail(nullptr, VP_ERR_NOMEM, "hipMalloc Lab -> BGR tables", e); vp_destroy(ctx); return nullptr; }
+        if ((e = hipMalloc(&ctx->d_labinv, nab + 1024 + 4096)) != hipSuccess) return create_failed(ctx, VP_ERR_NOMEM, "hipMalloc Lab -> BGR tables", e);
         uint8_t* lb = (uint8_t*)ctx->d_labinv;
         hipMemcpy(lb, abxz.data(), nab, hipMemcpyHostToDevice);
         hipMemcpy(lb + nab, yf.data(), 1024, hipMemcpyHostToDevice);
-        if ((e = hipMemcpy(lb + nab + 1024, invg.data(), 4096, hipMemcpyHostToDevice)) != hipSuccess) { vp_fail(nullptr, VP_ERR_HIP, "Lab -> BGR table upload", e); vp_destroy(ctx); return nullptr; }
+        if ((e = hipMemcpy(lb + nab + 1024, invg.data(), 4096, hipMemcpyHostToDevice)) != hipSuccess) return create_failed(ctx, VP_ERR_HIP, "Lab -> BGR table upload", e);
         ctx->tab.abxz = (const int32_t*)lb;
         ctx->tab.yf = (const uint16_t*)(lb + nab);
         ctx->tab.invg = lb + nab + 1024;
@@ -148,35 +155,38 @@ vp_ctx* vp_create(int device)
     return ctx;
 }
 
+// Frees whatever exists, so that it also serves a context vp_create could not finish: no HIP call on a null handle, and no error text
+// of its own (the one set at a failure stays for vp_last_error(NULL)).
 int vp_destroy(vp_ctx* ctx)
 {
     if (!ctx) return VP_ERR_INVALID;
-    hipSetDevice(ctx->device);
-    hipStreamSynchronize(ctx->stream);
+    (void)hipSetDevice(ctx->device);
+    if (ctx->stream) (void)hipStreamSynchronize(ctx->stream);
     vp_post_teardown(ctx);
-    if (ctx->ws) hipFree(ctx->ws);
-    if (ctx->c3_acc) hipFree(ctx->c3_acc);
-    if (ctx->hc_hist) hipFree(ctx->hc_hist);
-    if (ctx->ct_hint_host) hipHostFree(ctx->ct_hint_host);
-    if (ctx->ccl_hint_host) hipHostFree(ctx->ccl_hint_host);
-    if (ctx->ccl_zero_dev) hipFree(ctx->ccl_zero_dev);
+    vp_ccl_teardown(ctx);
+    vp_contours_teardown(ctx);
+    vp_hough_circles_teardown(ctx);
+    vp_adaptive_teardown(ctx);
+    if (ctx->ws) (void)hipFree(ctx->ws);
     for (int i = 0; i < 4; i++) {
-        if (ctx->ring_buf[i]) hipHostFree(ctx->ring_buf[i]);
-        if (ctx->ring_ev[i]) hipEventDestroy(ctx->ring_ev[i]);
+        if (ctx->ring_buf[i]) (void)hipHostFree(ctx->ring_buf[i]);
+        if (ctx->ring_ev[i]) (void)hipEventDestroy(ctx->ring_ev[i]);
     }
-    if (ctx->hstage) hipHostFree(ctx->hstage);
-    if (ctx->d_tables) hipFree(ctx->d_tables);
-    if (ctx->d_labinv) hipFree(ctx->d_labinv);
-    if (ctx->agauss_taps) hipFree(ctx->agauss_taps);
-    hipEventDestroy(ctx->ev0);
-    hipEventDestroy(ctx->ev1);
-    for (int i = 0; i < 4; i++) { hipStreamDestroy(ctx->aux[i]); hipEventDestroy(ctx->ev_join[i]); }
-    hipEventDestroy(ctx->ev_fork);
-    hipStreamDestroy(ctx->fb_stream);
-    hipEventDestroy(ctx->ev_fb_fork);
-    hipEventDestroy(ctx->ev_fb_join);
-    hipEventDestroy(ctx->ev_upload);
-    hipStreamDestroy(ctx->own_stream);
+    if (ctx->hstage) (void)hipHostFree(ctx->hstage);
+    if (ctx->d_tables) (void)hipFree(ctx->d_tables);
+    if (ctx->d_labinv) (void)hipFree(ctx->d_labinv);
+    prof_release(ctx->prof);
+    auto drop_event = [](hipEvent_t ev) { if (ev) (void)hipEventDestroy(ev); };
+    auto drop_stream = [](hipStream_t s) { if (s) (void)hipStreamDestroy(s); };
+    drop_event(ctx->ev0);
+    drop_event(ctx->ev1);
+    for (int i = 0; i < 4; i++) { drop_stream(ctx->chain.aux[i]); drop_event(ctx->chain.ev_join[i]); }
+    drop_event(ctx->chain.ev_fork);
+    drop_stream(ctx->chain.fb_stream);
+    drop_event(ctx->chain.ev_fb_fork);
+    drop_event(ctx->chain.ev_fb_join);
+    drop_event(ctx->ev_upload);
+    drop_stream(ctx->own_stream);
     delete ctx;
     return VP_OK;
 }
@@ -187,7 +197,7 @@ int vp_set_stream(vp_ctx* ctx, void* hip_stream)
     hipStream_t s = hip_stream ? (hipStream_t)hip_stream : ctx->own_stream;
     // The labelling's accumulator set is kept clean in the order of one stream: another stream starts it anew.  (As for every buffer of
     // the context, the caller has let the old stream's work finish, or ordered the new stream behind it, before using the new one.)
-    if (s != ctx->stream) ctx->c3_acc_dirty = 1;
+    if (s != ctx->stream) ctx->ccl.c3_acc_dirty = 1;
     ctx->stream = s;
     return VP_OK;
 }
@@ -196,24 +206,13 @@ void* vp_get_stream(vp_ctx* ctx) { return ctx ? (void*)ctx->stream : nullptr; }
 int vp_set_option(vp_ctx* ctx, int option, int value)
 {
     if (!ctx) return VP_ERR_INVALID;
-    if (option == VP_OPT_CHAIN_STREAMS && value >= 1 && value <= 4) { ctx->chain_streams = value; return VP_OK; }
-    if (option == VP_OPT_CCL_LEVELS && (value == 1 || value == 2)) { ctx->ccl_levels = value; return VP_OK; }
-    if (option == VP_OPT_CCL_MERGE_CAP && value >= -1) { ctx->ccl_mcap = value; return VP_OK; }
-    if (option == VP_OPT_FLAT_OPS && (value == 0 || value == 1)) { ctx->flat_ops = value; return VP_OK; }
-    if (option == VP_OPT_HOUGH_LDS && (value == 0 || value == 1)) { ctx->hough_global = !value; return VP_OK; }
-    if (option == VP_OPT_HOUGH_CIRCLES_LDS && (value == 0 || value == 1)) { ctx->hc_global = !value; return VP_OK; }
-    if (option == VP_OPT_BLUR_ONEPASS && value >= -1 && value <= 1) { ctx->blur_onepass = value; return VP_OK; }
-    if (option == VP_OPT_MEDIAN_MASK && value >= -1 && value <= 1) { ctx->median_mask = value; return VP_OK; }
-    if (option == VP_OPT_CLAHE_SPLIT && value >= 0 && value <= 64) { ctx->clahe_split = value; return VP_OK; }
-    if (option == VP_OPT_CCL_CROWDED && value >= 0 && value <= 2) { ctx->ccl_crowded_force = value; return VP_OK; }
-    if (option == VP_OPT_LABEL_MOMENTS_LDS && value >= -1 && value <= 1) { ctx->label_moments_lds = value; return VP_OK; }
-    return vp_fail(ctx, VP_ERR_INVALID, "vp_set_option");
+    return vp_options_set(&ctx->opt, option, value) ? VP_OK : vp_fail(ctx, VP_ERR_INVALID, "vp_set_option");
 }
 
 int vp_ccl_last_launches(vp_ctx* ctx, int32_t* launches)
 {
     if (!ctx || !launches) return VP_ERR_INVALID;
-    *launches = ctx->ccl_launches;
+    *launches = ctx->ccl.launches;
     return VP_OK;
 }
 
@@ -244,14 +243,15 @@ int vp_profile_begin(vp_ctx* ctx, int max_records)
     if (!ctx || max_records <= 0) return VP_ERR_INVALID;
     vp_prof& P = ctx->prof;
     if (P.cap < max_records) {
-        for (int i = 0; i < 2 * P.cap; i++) (void)hipEventDestroy(P.ev[i]);
-        free(P.ev);
-        free(P.ids);
-        P.ev = (hipEvent_t*)malloc(sizeof(hipEvent_t) * 2 * max_records);
+        prof_release(P);
+        P.ev = (hipEvent_t*)calloc(2 * (size_t)max_records, sizeof(hipEvent_t));
         P.ids = (int*)malloc(sizeof(int) * max_records);
-        if (!P.ev || !P.ids) { P.cap = 0; return vp_fail(ctx, VP_ERR_NOMEM, "profile records"); }
-        for (int i = 0; i < 2 * max_records; i++) VP_HIP(ctx, hipEventCreate(&P.ev[i]));
-        P.cap = max_records;
+        if (!P.ev || !P.ids) { prof_release(P); return vp_fail(ctx, VP_ERR_NOMEM, "profile records"); }
+        P.cap = max_records;                       // from here on prof_release knows the events: the ones not made yet are null
+        for (int i = 0; i < 2 * max_records; i++) {
+            const hipError_t e = hipEventCreate(&P.ev[i]);
+            if (e != hipSuccess) { prof_release(P); return vp_fail(ctx, VP_ERR_HIP, "hipEventCreate(&P.ev[i])", e); }
+        }
     }
     P.used = 0;
     P.on = true;

@@ -56,9 +56,9 @@ int vp_color_balance_last_folds(vp_ctx* ctx, int32_t* tiles_folded)
     VP_TRY(check_ctx(ctx));
     if (!tiles_folded) return vp_fail(ctx, VP_ERR_INVALID, "vp_color_balance_last_folds arguments");
     *tiles_folded = 0;
-    if (!ctx->cb_folds_dev) return VP_OK;
+    if (!ctx->cb.folds_dev) return VP_OK;
     uint32_t v = 0;
-    VP_HIP(ctx, hipMemcpyAsync(&v, ctx->cb_folds_dev, 4, hipMemcpyDeviceToHost, ctx->stream));
+    VP_HIP(ctx, hipMemcpyAsync(&v, ctx->cb.folds_dev, 4, hipMemcpyDeviceToHost, ctx->stream));
     VP_HIP(ctx, hipStreamSynchronize(ctx->stream));
     *tiles_folded = (int32_t)v;
     return VP_OK;

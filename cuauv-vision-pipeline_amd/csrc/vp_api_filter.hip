@@ -144,7 +144,7 @@ static int eqhist_args(vp_ctx* ctx, const char* who, const void* src, const void
 static int clahe_args(vp_ctx* ctx, const char* who, const void* src, const void* dst, int w, int h, double clip_limit, int tiles_x, int tiles_y, vp_clahe_plan* P)
 {
     VP_TRY(plane_args(ctx, who, src, dst, w, h));
-    *P = vp_clahe_make_plan(w, h, clip_limit, tiles_x, tiles_y, ctx ? ctx->clahe_split : 0);
+    *P = vp_clahe_make_plan(w, h, clip_limit, tiles_x, tiles_y, ctx ? ctx->opt.v[VP_OPT_CLAHE_SPLIT] : 0);
     if (P->status == VP_CLAHE_INVALID) return vp_fail(ctx, VP_ERR_INVALID, who);
     if (P->status != VP_CLAHE_OK) return vp_fail(ctx, VP_ERR_UNSUPPORTED, who);
     return VP_OK;
@@ -262,7 +262,7 @@ int vp_gaussian_blur_dev(vp_ctx* ctx, const uint8_t* d_src, size_t src_stride, i
         VP_HIP(ctx, hipMemcpy2DAsync(d_dst, rowbytes, d_src, src_stride, rowbytes, h, hipMemcpyDeviceToDevice, ctx->stream));
         return VP_OK;
     }
-    const bool one = vp_gaussian_onepass_fits(kw, kh) && (ctx->blur_onepass == 1 || (ctx->blur_onepass < 0 && blur_onepass_measured_faster(cn, kw, kh)));
+    const bool one = vp_gaussian_onepass_fits(kw, kh) && (ctx->opt.v[VP_OPT_BLUR_ONEPASS] == 1 || (ctx->opt.v[VP_OPT_BLUR_ONEPASS] < 0 && blur_onepass_measured_faster(cn, kw, kh)));
     VP_TRY(vp_ws_reserve(ctx, (one ? 0 : vp_align(nbytes * 2)) + 4096));
     TAKE(d_taps, uint16_t*, 2048);
     // the taps go over in a pinned chunk of the context's ring: the copy is enqueued, nothing waits for it

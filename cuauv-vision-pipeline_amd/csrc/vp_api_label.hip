@@ -119,7 +119,7 @@ static int find_contours_impl(vp_ctx* ctx, const uint8_t* src, bool src_on_devic
     // (more border segments than the block's LDS tables hold: 8192): then it is launched over the chip (VP_CT_MANY=0 / 1: never / always)
     const char* many_s = getenv("VP_CT_MANY");
     const int many_env = many_s ? atoi(many_s) : -1;
-    const bool many = many_env >= 0 ? many_env != 0 : ctx->ct_heads_hint > 8192u;
+    const bool many = many_env >= 0 ? many_env != 0 : ctx->ct.heads_hint > 8192u;
     // The header and the first points come back without a copy: the kernels that make them write them into the pinned staging
     // buffer as well, and the call only synchronises (longer point lists take a copy afterwards).  VP_CT_MIRROR=0: a copy, as before.
     const size_t spec_pts = points ? (size_t)std::min<long long>(mp, 8192) : 0;
@@ -156,7 +156,7 @@ static int find_contours_impl(vp_ctx* ctx, const uint8_t* src, bool src_on_devic
         }
         VP_HIP(ctx, hipStreamSynchronize(ctx->stream));
         info = reinterpret_cast<const int32_t*>(hs);
-        ctx->ct_heads_hint = (uint32_t)info[2];
+        ctx->ct.heads_hint = (uint32_t)info[2];
         if (info[0] != -1 || many_now) break;
         many_now = true;
     }
@@ -247,7 +247,7 @@ unsigned int vp_contours_last_heads(vp_ctx* ctx)
 {
     if (!ctx) return 0;
     const uint32_t b = vp_ct_batch_hint(ctx);
-    return b > ctx->ct_heads_hint ? b : ctx->ct_heads_hint;
+    return b > ctx->ct.heads_hint ? b : ctx->ct.heads_hint;
 }
 
 int vp_find_contours_bits_dev(vp_ctx* ctx, const unsigned long long* d_bits, int w, int h, int mode, int method, int32_t* points, int64_t max_points,

@@ -399,28 +399,28 @@ static int chain_core(vp_ctx* ctx, const vp_chain_desc* d, const vp_chain_buffer
     // soon as the mask exists and runs beside the labelling and its label write (latency-bound launches beside a bandwidth-bound one);
     // the caller's stream joins it at the end.  One pass for the whole batch only (the scratch is carved once).  VP_CT_SIDE=0: in a row.
     static const bool ct_side_off = getenv("VP_CT_SIDE") && atoi(getenv("VP_CT_SIDE")) == 0;
-    const bool ct_side = cd && d->ccl && !ct_side_off && ctx->chain_streams == 1 && ct_group_for(w, h, cd->max_contours) >= n;
+    const bool ct_side = cd && d->ccl && !ct_side_off && ctx->opt.v[VP_OPT_CHAIN_STREAMS] == 1 && ct_group_for(w, h, cd->max_contours) >= n;
     int rc_ct = VP_OK;
     bool joined = true;
     hipStream_t s_main = ctx->stream;
     if (ct_side) {
-        VP_HIP(ctx, hipEventRecord(ctx->ev_fb_fork, s_main));
-        VP_HIP(ctx, hipStreamWaitEvent(ctx->fb_stream, ctx->ev_fb_fork, 0));
-        ctx->stream = ctx->fb_stream;
+        VP_HIP(ctx, hipEventRecord(ctx->chain.ev_fb_fork, s_main));
+        VP_HIP(ctx, hipStreamWaitEvent(ctx->chain.fb_stream, ctx->chain.ev_fb_fork, 0));
+        ctx->stream = ctx->chain.fb_stream;
         rc_ct = contours_of_batch();
-        const hipError_t ej = hipEventRecord(ctx->ev_fb_join, ctx->fb_stream);
+        const hipError_t ej = hipEventRecord(ctx->chain.ev_fb_join, ctx->chain.fb_stream);
         ctx->stream = s_main;
         joined = false;
-        if (ej != hipSuccess) { (void)hipStreamSynchronize(ctx->fb_stream); joined = true; if (rc_ct == VP_OK) rc_ct = vp_fail(ctx, VP_ERR_HIP, "hipEventRecord", ej); }
+        if (ej != hipSuccess) { (void)hipStreamSynchronize(ctx->chain.fb_stream); joined = true; if (rc_ct == VP_OK) rc_ct = vp_fail(ctx, VP_ERR_HIP, "hipEventRecord", ej); }
     }
     int rc_ccl = VP_OK;
     // (with the contour pass beside it the labelling keeps its six crowded-frame launches, vp_ccl_hint.h: without them the label write
     // starts ~15 us earlier and saturates memory under the latency-bound contour kernels, the longer of the two branches, for longer -
     // chain + contours 0.648 -> 0.658 ms per step of 128 frames, EXPERIMENTS.md)
-    ctx->ccl_beside = joined ? 0 : 1;
+    ctx->ccl.beside = joined ? 0 : 1;
     if (d->ccl) rc_ccl = vpk_ccl(ctx, ccl_bits, w, h, n, d->numbering, ws, b->labels, b->stats, b->centroids, d->max_labels, b->nlabels ? b->nlabels : d_nl);
-    ctx->ccl_beside = 0;
-    if (!joined && hipStreamWaitEvent(s_main, ctx->ev_fb_join, 0) != hipSuccess) { (void)hipGetLastError(); (void)hipStreamSynchronize(ctx->fb_stream); }
+    ctx->ccl.beside = 0;
+    if (!joined && hipStreamWaitEvent(s_main, ctx->chain.ev_fb_join, 0) != hipSuccess) { (void)hipGetLastError(); (void)hipStreamSynchronize(ctx->chain.fb_stream); }
     if (rc_ccl != VP_OK) return rc_ccl;
     if (rc_ct != VP_OK) return rc_ct;
     if (cd && !ct_side) VP_TRY(contours_of_batch());
@@ -442,13 +442,13 @@ static int check_cdesc(vp_ctx* ctx, const vp_contour_desc* cd, const vp_contour_
 // caller-visible stream).  Frames are independent, so the split changes scheduling only.
 static int chain_split(vp_ctx* ctx, const vp_chain_desc* d, const vp_chain_buffers* b, int n)
 {
-    int S = ctx->chain_streams;
+    int S = ctx->opt.v[VP_OPT_CHAIN_STREAMS];
     if (S > n / 4) S = n / 4;      // keep sub-batches worth a launch
     if (S <= 1) return chain_core(ctx, d, b, n);
     const size_t npx = (size_t)d->width * d->height;
     const size_t ml = (size_t)(d->ccl ? d->max_labels : 0);
     hipStream_t user = ctx->stream;
-    VP_HIP(ctx, hipEventRecord(ctx->ev_fork, user));
+    VP_HIP(ctx, hipEventRecord(ctx->chain.ev_fork, user));
     int rc = VP_OK;
     int f0 = 0;
     for (int s = 0; s < S && rc == VP_OK; s++) {
@@ -461,14 +461,14 @@ static int chain_split(vp_ctx* ctx, const vp_chain_desc* d, const vp_chain_buffe
         if (b->stats) sb.stats = b->stats + (size_t)f0 * ml * 5;
         if (b->centroids) sb.centroids = b->centroids + (size_t)f0 * ml * 2;
         if (b->nlabels) sb.nlabels = b->nlabels + f0;
-        hipError_t e = hipStreamWaitEvent(ctx->aux[s], ctx->ev_fork, 0);
+        hipError_t e = hipStreamWaitEvent(ctx->chain.aux[s], ctx->chain.ev_fork, 0);
         if (e != hipSuccess) { rc = vp_fail(ctx, VP_ERR_HIP, "hipStreamWaitEvent", e); break; }
-        ctx->stream = ctx->aux[s];
+        ctx->stream = ctx->chain.aux[s];
         rc = chain_core(ctx, d, &sb, cnt);
         ctx->stream = user;
         // join whatever was queued on the side stream, also after an error: it must not still run when the next call reuses the workspace
-        const hipError_t e1 = hipEventRecord(ctx->ev_join[s], ctx->aux[s]);
-        const hipError_t e2 = e1 == hipSuccess ? hipStreamWaitEvent(user, ctx->ev_join[s], 0) : e1;
+        const hipError_t e1 = hipEventRecord(ctx->chain.ev_join[s], ctx->chain.aux[s]);
+        const hipError_t e2 = e1 == hipSuccess ? hipStreamWaitEvent(user, ctx->chain.ev_join[s], 0) : e1;
         if (rc != VP_OK) break;
         if (e1 != hipSuccess) { rc = vp_fail(ctx, VP_ERR_HIP, "hipEventRecord", e1); break; }
         if (e2 != hipSuccess) { rc = vp_fail(ctx, VP_ERR_HIP, "hipStreamWaitEvent", e2); break; }

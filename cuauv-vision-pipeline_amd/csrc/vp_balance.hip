@@ -679,8 +679,8 @@ int vpk_color_balance(vp_ctx* ctx, const uint8_t* d_src, uint8_t* d_dst, int w, 
         VP_HIP(ctx, hipMemcpyAsync(powtab, host_tab, sizeof host_tab, hipMemcpyHostToDevice, s));
     }
     hipLaunchKernelGGL(k_cb_plan1, dim3((unsigned)n), dim3(256), 0, s, P, hist, neq, d_src, plans, lut, folds, force_fold, (const double*)powtab);
-    VP_HIP(ctx, hipMemcpyAsync(ctx->cb_folds_own, folds, 4, hipMemcpyDeviceToDevice, s));
-    ctx->cb_folds_dev = ctx->cb_folds_own;
+    VP_HIP(ctx, hipMemcpyAsync(ctx->cb.folds_own, folds, 4, hipMemcpyDeviceToDevice, s));
+    ctx->cb.folds_dev = ctx->cb.folds_own;
     if (hsv) {
         VP_HIP(ctx, hipMemsetAsync(svhist, 0, (size_t)n * 512 * 4, s));
         if (tiled) hipLaunchKernelGGL((k_cb_hsvhist<true>), grid, dim3(256), 0, s, d_src, P, ctx->tab, lut, svhist);

@@ -666,13 +666,13 @@ static int ccl_roots(vp_ctx* ctx, const u64* d_bits, const ccl_geom& G, int n, u
     size_t cap;
     const size_t lds_local = ccl_local_lds(G, cap, ccl_env_tuning());
     if (lds_local <= 64 * 1024) {
-        ctx->ccl_launches += strips > 1 ? 2 : 1;
+        ctx->ccl.launches += strips > 1 ? 2 : 1;
         { vp_prof_scope ps(ctx, VPK_CCL_LOCAL); hipLaunchKernelGGL(k_ccl_local, dim3((unsigned)((size_t)n * strips)), dim3(256), lds_local, s, d_bits, G, parent, flags, strips, (int)cap, only, zero_too); }
         if (strips > 1) { vp_prof_scope ps(ctx, VPK_CCL_BOUNDARY); hipLaunchKernelGGL(k_ccl_boundary, dim3((unsigned)(strips - 1), (unsigned)n), dim3(64), 0, s, d_bits, G, parent, flags, only); }
     } else {
         if (zero_too) { vp_prof_scope ps(ctx, VPK_MEMSET); VP_HIP(ctx, hipMemsetAsync(zero_too, 0, (size_t)G.nw32 * 4 * n, s)); }
         { vp_prof_scope ps(ctx, VPK_MEMSET); VP_HIP(ctx, hipMemsetAsync(flags, 0, (size_t)G.nw32 * 4 * n, s)); }
-        ctx->ccl_launches += 2;
+        ctx->ccl.launches += 2;
         { vp_prof_scope ps(ctx, VPK_CCL_BOUNDARY); hipLaunchKernelGGL(k_ccl_init, wgrid, dim3(256), 0, s, d_bits, G, parent, flags); }
         { vp_prof_scope ps(ctx, VPK_CCL_LOCAL); hipLaunchKernelGGL(k_ccl_link, wgrid, dim3(256), 0, s, d_bits, G, parent, flags); }
     }
@@ -686,7 +686,7 @@ static int ccl_one_level_tail(vp_ctx* ctx, const u64* d_bits, const ccl_geom& G,
 {
     const dim3 wgrid((unsigned)((G.h * G.ww + 255) / 256), (unsigned)n);
     hipStream_t s = ctx->stream;
-    ctx->ccl_launches += (d_stats || d_centroids) ? 3 : 2;
+    ctx->ccl.launches += (d_stats || d_centroids) ? 3 : 2;
     { vp_prof_scope ps(ctx, VPK_CCL_RANK); hipLaunchKernelGGL(k_ccl_rank, dim3(RK_PARTS + BG_PARTS, (unsigned)n), dim3(256), 0, s, G, ws.flags, ws.prefix, d_nlabels, (ccl_acc*)ws.acc, max_labels, d_bits, (contrib*)ws.bgpart, only); }
     { vp_prof_scope ps(ctx, VPK_CCL_STATS); hipLaunchKernelGGL(k_ccl_stats, wgrid, dim3(256), 0, s, d_bits, G, ws.parent, ws.flags, ws.prefix, ws.seglabel, ws.wordlabel, (ccl_acc*)ws.acc, max_labels, only); }
     if (d_stats || d_centroids) {
@@ -716,19 +716,19 @@ struct ccl_call {            // the arguments of vpk_ccl that the launchers pass
 // (no memory): the caller then keeps the workspace's set and its clearing per call.
 static int c3_acc_acquire(vp_ctx* ctx, size_t need, hipStream_t s, ccl_acc** acc)
 {
-    if (need > ctx->c3_acc_bytes) {
+    if (need > ctx->ccl.c3_acc_bytes) {
         VP_HIP(ctx, hipStreamSynchronize(s));
-        if (ctx->c3_acc) { (void)hipFree(ctx->c3_acc); ctx->c3_acc = nullptr; ctx->c3_acc_bytes = 0; }
-        if (hipMalloc(&ctx->c3_acc, need) == hipSuccess) { ctx->c3_acc_bytes = need; ctx->c3_acc_dirty = 1; }
+        if (ctx->ccl.c3_acc) { (void)hipFree(ctx->ccl.c3_acc); ctx->ccl.c3_acc = nullptr; ctx->ccl.c3_acc_bytes = 0; }
+        if (hipMalloc(&ctx->ccl.c3_acc, need) == hipSuccess) { ctx->ccl.c3_acc_bytes = need; ctx->ccl.c3_acc_dirty = 1; }
         else (void)hipGetLastError();
     }
-    if (!ctx->c3_acc || need > ctx->c3_acc_bytes) return VP_OK;
-    if (ctx->c3_acc_dirty) {
-        const size_t entries = ctx->c3_acc_bytes / sizeof(ccl_acc);
-        hipLaunchKernelGGL(k_ccl3_acc_init, dim3((unsigned)std::min<size_t>((entries + 255) / 256, 65535)), dim3(256), 0, s, (ccl_acc*)ctx->c3_acc, entries);
+    if (!ctx->ccl.c3_acc || need > ctx->ccl.c3_acc_bytes) return VP_OK;
+    if (ctx->ccl.c3_acc_dirty) {
+        const size_t entries = ctx->ccl.c3_acc_bytes / sizeof(ccl_acc);
+        hipLaunchKernelGGL(k_ccl3_acc_init, dim3((unsigned)std::min<size_t>((entries + 255) / 256, 65535)), dim3(256), 0, s, (ccl_acc*)ctx->ccl.c3_acc, entries);
     }
-    ctx->c3_acc_dirty = 1;
-    *acc = (ccl_acc*)ctx->c3_acc;
+    ctx->ccl.c3_acc_dirty = 1;
+    *acc = (ccl_acc*)ctx->ccl.c3_acc;
     return VP_OK;
 }
 
@@ -739,7 +739,7 @@ static void c3_acc_commit(vp_ctx* ctx)
 #ifdef VP_PROBE
     if (g_dbg_bits_host) return;   // kernels that skip work do not hand every entry back clean
 #endif
-    ctx->c3_acc_dirty = 0;
+    ctx->ccl.c3_acc_dirty = 0;
 }
 
 // Kernels accept more dynamic LDS than the 64 KB default once told so - per device, hence remembered in the context (grow-only).
@@ -756,7 +756,7 @@ static bool c3_allow_lds(const void* kernel, size_t lds, size_t& allowed)
 template <int K>
 static bool c3_allow_plan_lds(vp_ctx* ctx, const ccl_plan& P)
 {
-    size_t* set = ctx->c3_lds_set;
+    size_t* set = ctx->ccl.c3_lds_set;
     return c3_allow_lds((const void*)k_ccl3_link<K * C3_LINK_THREADS>, P.lds3a, set[2 * (K - 1)]) &&
            c3_allow_lds((const void*)k_ccl3_label<K * C3_LABEL_THREADS, 0, C3_ACC>, P.lds3b, set[2 * (K - 1) + 1]) &&
            c3_allow_lds((const void*)k_ccl3_label<C3_LABEL_THREADS, C3_LIGHT_ROOTS, C3_LIGHT_ACC>, P.lds3c, set[4]);
@@ -776,7 +776,7 @@ static int ccl_crowded(vp_ctx* ctx, const ccl_plan& P, const ccl_call& c, u32* h
     hipStream_t s = ctx->stream;
     const int scap = (int)c3_strips_cap(G.h);
     ccl_acc* acc3 = (ccl_acc*)ws.acc;
-    if (ctx->chain_streams == 1 && !prepare) {   // sub-batches on several streams would share the context's set: they keep the workspace's
+    if (ctx->opt.v[VP_OPT_CHAIN_STREAMS] == 1 && !prepare) {   // sub-batches on several streams would share the context's set: they keep the workspace's
         const int rc = c3_acc_acquire(ctx, sizeof(ccl_acc) * (size_t)c.max_labels * (size_t)c.n, s, &acc3);
         if (rc != VP_OK) return rc;
     }
@@ -800,9 +800,9 @@ static int ccl_crowded(vp_ctx* ctx, const ccl_plan& P, const ccl_call& c, u32* h
       };
       label(k_ccl3_label<C3_LABEL_THREADS, C3_LIGHT_ROOTS, C3_LIGHT_ACC>, T.agrid_light, C3_LABEL_THREADS, P.lds3c);
       label(k_ccl3_label<K * C3_LABEL_THREADS, 0, C3_ACC>, T.agrid, K * C3_LABEL_THREADS, P.lds3b); }
-    if (!prepare) ctx->ccl_launches += 5;
+    if (!prepare) ctx->ccl.launches += 5;
     if (c.stats || c.cent || acc3_own) {
-        if (!prepare) ctx->ccl_launches++;
+        if (!prepare) ctx->ccl.launches++;
         vp_prof_scope ps(ctx, VPK_CCL_FINAL);
         hipLaunchKernelGGL(k_ccl3_rows, dim3((unsigned)(ctx->num_cu * 4)), dim3(256), 0, s, G, P3, ncrowded, ws.c3_clist, ws.flags, ws.c3_child, ws.prefix,
                            ws.c3_barr, (const c3_state*)ws.c3_state, (const contrib*)ws.c3_tot, scap, acc3, c.max_labels, c.stats, c.cent, acc3_own ? 1 : 0);
@@ -816,13 +816,13 @@ static int ccl_crowded(vp_ctx* ctx, const ccl_plan& P, const ccl_call& c, u32* h
 // first two-level call.  Null when it could not be made: the labelling then always queues the crowded-frame kernels.
 static u32* ccl_hint_word(vp_ctx* ctx)
 {
-    if (!ctx->ccl_hint_host && !ctx->ccl_hint_failed) {
+    if (!ctx->ccl.hint_host && !ctx->ccl.hint_failed) {
         void* p = nullptr;
-        if (hipHostMalloc(&p, sizeof(u32), hipHostMallocDefault) != hipSuccess) { (void)hipGetLastError(); ctx->ccl_hint_failed = 1; return nullptr; }
+        if (hipHostMalloc(&p, sizeof(u32), hipHostMallocDefault) != hipSuccess) { (void)hipGetLastError(); ctx->ccl.hint_failed = 1; return nullptr; }
         *(volatile u32*)p = 0u;
-        ctx->ccl_hint_host = (uint32_t*)p;
+        ctx->ccl.hint_host = (uint32_t*)p;
     }
-    return ctx->ccl_hint_host;
+    return ctx->ccl.hint_host;
 }
 
 // A process that has only run LEAN has never dispatched the crowded-frame kernels, and the call that switches to FULL - in the middle of
@@ -831,16 +831,25 @@ static u32* ccl_hint_word(vp_ctx* ctx)
 // count; six launches that leave at once, ~17 us, never again).  Not part of the labelling sequence vp_ccl_last_launches counts.
 static int ccl_prepare_crowded(vp_ctx* ctx, const ccl_plan& P, const ccl_call& c)
 {
-    int& d = ctx->ccl_prepared[P.c3_tall ? 1 : 0];   // per context: a superset of per process and per device, and free of races
+    int& d = ctx->ccl.prepared[P.c3_tall ? 1 : 0];   // per context: a superset of per process and per device, and free of races
     if (d) return VP_OK;
-    if (!ctx->ccl_zero_dev) {
+    if (!ctx->ccl.zero_dev) {
         void* p = nullptr;
         if (hipMalloc(&p, 256) != hipSuccess) { (void)hipGetLastError(); return VP_OK; }
         if (hipMemsetAsync(p, 0, 256, ctx->stream) != hipSuccess) { (void)hipGetLastError(); (void)hipFree(p); return VP_OK; }
-        ctx->ccl_zero_dev = (u32*)p;
+        ctx->ccl.zero_dev = (u32*)p;
     }
     d = 1;
-    return P.c3_tall ? ccl_crowded<2>(ctx, P, c, nullptr, ctx->ccl_zero_dev, true) : ccl_crowded<1>(ctx, P, c, nullptr, ctx->ccl_zero_dev, true);
+    return P.c3_tall ? ccl_crowded<2>(ctx, P, c, nullptr, ctx->ccl.zero_dev, true) : ccl_crowded<1>(ctx, P, c, nullptr, ctx->ccl.zero_dev, true);
+}
+
+// what c3_acc_acquire, ccl_hint_word and ccl_prepare_crowded made (vp_destroy; the context's stream is idle)
+void vp_ccl_teardown(vp_ctx* ctx)
+{
+    if (ctx->ccl.c3_acc) (void)hipFree(ctx->ccl.c3_acc);
+    if (ctx->ccl.hint_host) (void)hipHostFree(ctx->ccl.hint_host);
+    if (ctx->ccl.zero_dev) (void)hipFree(ctx->ccl.zero_dev);
+    ctx->ccl = vp_ccl_state{};
 }
 
 // The two-level path (vp_ccl2.inl): strips resolved in LDS, one merge block per frame; frames the merge hands over go to the
@@ -858,11 +867,11 @@ static int ccl_two_level(vp_ctx* ctx, const ccl_plan& P, const ccl_call& c)
     int mode = CCL_MODE_FULL;
     u32* hint = nullptr;
     if (c3_ok && (hint = ccl_hint_word(ctx)) != nullptr) {
-        ccl_hint_state st = {ctx->ccl_hint_mode, ctx->ccl_hint_quiet};
-        mode = ccl_hint_decide(st, *(volatile u32*)hint, ctx->ccl_crowded_force, ctx->chain_streams + (ctx->ccl_beside ? 1 : 0));
-        ctx->ccl_hint_mode = st.mode; ctx->ccl_hint_quiet = st.quiet;
+        ccl_hint_state st = {ctx->ccl.hint_mode, ctx->ccl.hint_quiet};
+        mode = ccl_hint_decide(st, *(volatile u32*)hint, ctx->opt.v[VP_OPT_CCL_CROWDED], ctx->opt.v[VP_OPT_CHAIN_STREAMS] + (ctx->ccl.beside ? 1 : 0));
+        ctx->ccl.hint_mode = st.mode; ctx->ccl.hint_quiet = st.quiet;
     }
-    ctx->ccl_launches += 2;
+    ctx->ccl.launches += 2;
     { vp_prof_scope ps(ctx, VPK_CCL2_LOCAL);
       hipLaunchKernelGGL(k_ccl2_local, dim3((unsigned)((size_t)n * P.strips)), dim3(256), P.lds2, s, c.bits, G, P.strips, (int)P.cap2, (int)P.rc, (int)P.tail_words, ws.c2_ncomp,
                          (contrib*)ws.c2_recs, (c2_box*)ws.c2_bgbox, ws.wordlabel, ws.seglabel, ws.c3_ncrowded); }
@@ -883,7 +892,7 @@ static int ccl_two_level(vp_ctx* ctx, const ccl_plan& P, const ccl_call& c)
         rc = c3_acc_acquire(ctx, sizeof(ccl_acc) * (size_t)c.max_labels * (size_t)n, s, &set);
         if (rc != VP_OK) return rc;
         if (set) c3_acc_commit(ctx);
-        ctx->ccl_launches++;
+        ctx->ccl.launches++;
         vp_prof_scope ps(ctx, VPK_CCL_STATS);
         hipLaunchKernelGGL(k_ccl2_finish, dim3((unsigned)n), dim3(256), 0, s, c.bits, G, ws.c2_crowded, ws.c3_ncrowded, hint, ws.parent, ws.flags, ws.prefix,
                            (ccl_acc*)ws.acc, (contrib*)ws.bgpart, ws.seglabel, ws.wordlabel, c.nlabels, c.max_labels, c.labels, c.stats, c.cent, P.gpr, P.magic);
@@ -896,7 +905,7 @@ static int ccl_two_level(vp_ctx* ctx, const ccl_plan& P, const ccl_call& c)
     }
     if (rc != VP_OK) return rc;
     if (c.labels) {
-        ctx->ccl_launches++;
+        ctx->ccl.launches++;
         vp_prof_scope ps(ctx, VPK_CCL2_WRITE);
         const dim3 wr_grid((unsigned)((G.h + WR_ROWS - 1) / WR_ROWS), (unsigned)n);
         hipLaunchKernelGGL(k_ccl2_write<0>, wr_grid, dim3(256), 0, s, c.bits, G, P.strips, (int)P.rc, ws.seglabel, ws.wordlabel, ws.c2_label, ws.c2_crowded, c.labels, P.gpr, P.magic,
@@ -911,9 +920,9 @@ int vpk_ccl(vp_ctx* ctx, const u64* d_bits, int w, int h, int n, int numbering, 
 {
     if (numbering != VP_CCL_BLOCK2X2 && numbering != VP_CCL_PIXEL) return vp_fail(ctx, VP_ERR_INVALID, "numbering");
     if (max_labels < 1) return vp_fail(ctx, VP_ERR_INVALID, "max_labels");
-    const ccl_plan P = ccl_make_plan(w, h, numbering, ctx->ccl_levels, ctx->ccl_mcap, ccl_env_tuning());
+    const ccl_plan P = ccl_make_plan(w, h, numbering, ctx->opt.v[VP_OPT_CCL_LEVELS], ctx->opt.v[VP_OPT_CCL_MERGE_CAP], ccl_env_tuning());
     const ccl_call c = {d_bits, n, ws, d_labels, d_stats, d_centroids, max_labels, d_nlabels};
-    ctx->ccl_launches = 0;   // kernels of the labelling sequence this call queues (vp_ccl_last_launches)
+    ctx->ccl.launches = 0;   // kernels of the labelling sequence this call queues (vp_ccl_last_launches)
     if (P.two_level) return ccl_two_level(ctx, P, c);
 
     int rc = ccl_roots(ctx, d_bits, P.G, n, ws.parent, ws.flags);
@@ -921,7 +930,7 @@ int vpk_ccl(vp_ctx* ctx, const u64* d_bits, int w, int h, int n, int numbering, 
     rc = ccl_one_level_tail(ctx, d_bits, P.G, n, ws, d_stats, d_centroids, max_labels, d_nlabels, nullptr);
     if (rc != VP_OK) return rc;
     if (d_labels) {
-        ctx->ccl_launches++;
+        ctx->ccl.launches++;
         vp_prof_scope ps(ctx, VPK_CCL_WRITE);
         const u32 total_rows = (u32)((size_t)n * h);
         hipLaunchKernelGGL(k_ccl_write, dim3((total_rows + WR_ROWS - 1) / WR_ROWS), dim3(256), 0, ctx->stream, d_bits, P.G, ws.seglabel, ws.wordlabel, d_labels,

@@ -559,7 +559,7 @@ template <int CODE, bool SWIN = false, bool SWOUT = false>
 static void launch_cvt(vp_ctx* ctx, const uint8_t* d_src, size_t stride, int w, int h, uint8_t* d_dst, uint8_t* d_p0, uint8_t* d_p1, uint8_t* d_p2)
 {
     const size_t npx = (size_t)w * h, ngroups = npx / 16;
-    const bool flat = ctx->flat_ops && (stride == (size_t)w * 3 || h == 1) && ngroups > 0 && aligned16(d_src) && aligned16(d_dst) && aligned16(d_p0) &&
+    const bool flat = ctx->opt.v[VP_OPT_FLAT_OPS] && (stride == (size_t)w * 3 || h == 1) && ngroups > 0 && aligned16(d_src) && aligned16(d_dst) && aligned16(d_p0) &&
                       aligned16(d_p1) && aligned16(d_p2);
     if (!flat) { launch_cvt_generic<CODE, SWIN, SWOUT>(ctx, d_src, stride, w, h, d_dst, d_p0, d_p1, d_p2); return; }
     const dim3 grid((unsigned)std::min<size_t>((ngroups + 255) / 256, (size_t)ctx->num_cu * 32));
@@ -671,7 +671,7 @@ template <int SCN, int DCN, bool SWAP>
 static void launch_reorder(vp_ctx* ctx, const uint8_t* d_src, size_t stride, int w, int h, uint8_t* d_dst, uint8_t* d_p0, uint8_t* d_p1, uint8_t* d_p2)
 {
     const size_t npx = (size_t)w * h, ngroups = npx / 16;
-    const bool flat = ctx->flat_ops && (stride == (size_t)w * SCN || h == 1) && ngroups > 0 && aligned16(d_src) && aligned16(d_dst) && aligned16(d_p0) &&
+    const bool flat = ctx->opt.v[VP_OPT_FLAT_OPS] && (stride == (size_t)w * SCN || h == 1) && ngroups > 0 && aligned16(d_src) && aligned16(d_dst) && aligned16(d_p0) &&
                       aligned16(d_p1) && aligned16(d_p2);
     if (!flat) {
         hipLaunchKernelGGL((k_reorder<SCN, DCN, SWAP>), dim3((unsigned)((w + 255) / 256), (unsigned)h), dim3(256), 0, ctx->stream, d_src, stride, w, h, d_dst,
@@ -734,7 +734,7 @@ int vpk_cvt_color(vp_ctx* ctx, int code, const uint8_t* d_src, size_t stride, in
         case VP_LAB2BGR: launch_cvt<VP_LAB2BGR>(ctx, d_src, stride, w, h, d_dst, d_p0, d_p1, d_p2); break;
         case VP_GRAY2BGR: {
             const size_t npx = (size_t)w * h, ngroups = npx / 16;
-            const bool flat = ctx->flat_ops && (stride == (size_t)w || h == 1) && ngroups > 0 && aligned16(d_src) && aligned16(d_dst) && aligned16(d_p0) &&
+            const bool flat = ctx->opt.v[VP_OPT_FLAT_OPS] && (stride == (size_t)w || h == 1) && ngroups > 0 && aligned16(d_src) && aligned16(d_dst) && aligned16(d_p0) &&
                               aligned16(d_p1) && aligned16(d_p2);
             if (!flat) {
                 hipLaunchKernelGGL(k_gray2bgr, dim3((unsigned)((w + 255) / 256), (unsigned)h), dim3(256), 0, ctx->stream, d_src, stride, w, h, d_dst, d_p0, d_p1, d_p2);
@@ -819,7 +819,7 @@ __global__ __launch_bounds__(256) void k_inrange_u8_flat(const uint8_t* __restri
 int vpk_inrange_u8(vp_ctx* ctx, const uint8_t* d_src, size_t stride, int w, int h, int cn, const vp_range3& q, uint8_t* d_dst, u64* d_bits, int* made_bits)
 {
     const size_t npx = (size_t)w * h, ngroups = npx / 16;
-    const bool flat = ctx->flat_ops && (cn == 1 || cn == 3) && (stride == (size_t)w * cn || h == 1) && ngroups > 0 && aligned16(d_src) && aligned16(d_dst);
+    const bool flat = ctx->opt.v[VP_OPT_FLAT_OPS] && (cn == 1 || cn == 3) && (stride == (size_t)w * cn || h == 1) && ngroups > 0 && aligned16(d_src) && aligned16(d_dst);
     const bool wbits = flat && d_bits && (w % 64) == 0;
     if (made_bits) *made_bits = wbits ? 1 : 0;
     if (flat) {

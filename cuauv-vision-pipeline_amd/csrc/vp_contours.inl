@@ -1407,20 +1407,25 @@ size_t vp_contours_ws_bytes(int w, int h, int n, int max_contours)
 // a call late, possibly of another mask: a guess, which the results do not depend on.
 static u32* vp_ct_hint_slots(vp_ctx* ctx, int n)
 {
-    if (!ctx->ct_hint_host) {
+    if (!ctx->ct.hint_host) {
         void* p = nullptr;
         if (hipHostMalloc(&p, 64 * sizeof(u32), hipHostMallocDefault) != hipSuccess) { (void)hipGetLastError(); return nullptr; }
         memset(p, 0, 64 * sizeof(u32));
-        ctx->ct_hint_host = (uint32_t*)p;
+        ctx->ct.hint_host = (uint32_t*)p;
     }
-    ctx->ct_hint_n = n < 64 ? n : 64;
-    return ctx->ct_hint_host;
+    ctx->ct.hint_n = n < 64 ? n : 64;
+    return ctx->ct.hint_host;
+}
+void vp_contours_teardown(vp_ctx* ctx)
+{
+    if (ctx->ct.hint_host) (void)hipHostFree(ctx->ct.hint_host);
+    ctx->ct = vp_contour_state{};
 }
 uint32_t vp_ct_batch_hint(vp_ctx* ctx)
 {
     uint32_t m = 0;
-    if (ctx->ct_hint_host)
-        for (int i = 0; i < ctx->ct_hint_n; i++) { const uint32_t v = *(volatile uint32_t*)(ctx->ct_hint_host + i); m = v > m ? v : m; }
+    if (ctx->ct.hint_host)
+        for (int i = 0; i < ctx->ct.hint_n; i++) { const uint32_t v = *(volatile uint32_t*)(ctx->ct.hint_host + i); m = v > m ? v : m; }
     return m;
 }
 
@@ -1487,9 +1492,9 @@ int vpk_find_contours(vp_ctx* ctx, const u64* d_bits, int w, int h, int n, int m
             return vp_fail(ctx, VP_ERR_NOMEM, "contour hierarchy workspace");
     }
     const size_t jump_lds = (size_t)CTJ_LDS_HEADS * 16;
-    if (!ctx->ct_lds_set) {                               // (per context = per device: the attribute belongs to the device's copy of the kernel)
+    if (!ctx->ct.lds_set) {                               // (per context = per device: the attribute belongs to the device's copy of the kernel)
         VP_HIP(ctx, hipFuncSetAttribute(reinterpret_cast<const void*>(k_ct_jump), hipFuncAttributeMaxDynamicSharedMemorySize, (int)jump_lds));
-        ctx->ct_lds_set = 1;
+        ctx->ct.lds_set = 1;
     }
     A.hkey = hkey; A.hbase = hbase; A.cnt8 = cnt8; A.head_pix = head_pix; A.hcap = hcap;
     A.counts = tree ? const_cast<int32_t*>(T.tcounts) : d_counts;
@@ -1519,7 +1524,7 @@ int vpk_find_contours(vp_ctx* ctx, const u64* d_bits, int w, int h, int n, int m
     // (one image: the head count of the context's last single-image pass sizes the grid - two items per head, half as much again -
     // instead of a thousand blocks of which thirty find work; the loops stride over the grid, so a wrong guess only costs time)
     size_t hblocks = (size_t)std::max(32, std::min(1024, 8192 / n));
-    if (n == 1 && ctx->ct_heads_hint) hblocks = std::min<size_t>(hblocks, std::max<size_t>(32, ((size_t)ctx->ct_heads_hint * 3 + 255) / 256));
+    if (n == 1 && ctx->ct.heads_hint) hblocks = std::min<size_t>(hblocks, std::max<size_t>(32, ((size_t)ctx->ct.heads_hint * 3 + 255) / 256));
     const dim3 hgrid((unsigned)std::min<size_t>((hcap + 255) / 256, hblocks), (unsigned)n);
     if (many_heads) hipLaunchKernelGGL(k_ct_headmaps<true>, wgrid, dim3(256), 0, s, d_bits, G, hmaps, partsum, cnt8);
     else hipLaunchKernelGGL(k_ct_headmaps<false>, wgrid, dim3(256), 0, s, d_bits, G, hmaps, partsum, cnt8);

@@ -320,11 +320,11 @@ int vpk_bitwise_u8(vp_ctx* ctx, int op, const uint8_t* a, const uint8_t* b, int 
     const ew_split s = ew_plan(ctx, dst, n, true);
     const int mcn = mask ? cn : 0;
     // the bit plane: one byte per pixel, whole words per row, nothing in front of the first group
-    const bool wbits = d_bits && bits_w > 0 && bits_w % 64 == 0 && mcn <= 1 && ctx->flat_ops && s.head == 0 && n % (size_t)bits_w == 0 && al16(d_bits);
+    const bool wbits = d_bits && bits_w > 0 && bits_w % 64 == 0 && mcn <= 1 && ctx->opt.v[VP_OPT_FLAT_OPS] && s.head == 0 && n % (size_t)bits_w == 0 && al16(d_bits);
     if (made_bits) *made_bits = wbits ? 1 : 0;
     const u32 sw = (u32)(scalar & 255) * 0x01010101u;
-    const int al_a = al16(a + s.head) && ctx->flat_ops, al_b = b && al16(b + s.head) && ctx->flat_ops;
-    const int al_m = mcn == 1 && al16(mask + s.head) && ctx->flat_ops;
+    const int al_a = al16(a + s.head) && ctx->opt.v[VP_OPT_FLAT_OPS], al_b = b && al16(b + s.head) && ctx->opt.v[VP_OPT_FLAT_OPS];
+    const int al_m = mcn == 1 && al16(mask + s.head) && ctx->opt.v[VP_OPT_FLAT_OPS];
     const dim3 grid(s.blocks), block(256);
 #define EW_BITWISE(M, W) hipLaunchKernelGGL((k_bitwise_u8<M, W>), grid, block, 0, ctx->stream, op, a, b, sw, mask, n, s.head, s.ngroups, al_a, al_b, al_m, dst, d_bits)
     switch (mcn) {
@@ -342,8 +342,8 @@ int vpk_bitwise_u8(vp_ctx* ctx, int op, const uint8_t* a, const uint8_t* b, int 
 int vpk_arith_u8(vp_ctx* ctx, int op, const uint8_t* a, const uint8_t* b, size_t n, uint8_t* dst)
 {
     const ew_split s = ew_plan(ctx, dst, n, true);
-    hipLaunchKernelGGL(k_arith_u8, dim3(s.blocks), dim3(256), 0, ctx->stream, op, a, b, n, s.head, s.ngroups, (int)(al16(a + s.head) && ctx->flat_ops),
-                       (int)(al16(b + s.head) && ctx->flat_ops), dst);
+    hipLaunchKernelGGL(k_arith_u8, dim3(s.blocks), dim3(256), 0, ctx->stream, op, a, b, n, s.head, s.ngroups, (int)(al16(a + s.head) && ctx->opt.v[VP_OPT_FLAT_OPS]),
+                       (int)(al16(b + s.head) && ctx->opt.v[VP_OPT_FLAT_OPS]), dst);
     VP_HIP(ctx, hipGetLastError());
     return VP_OK;
 }
@@ -354,7 +354,7 @@ int vpk_lut_u8(vp_ctx* ctx, const uint8_t* src, size_t n, int cn, const uint8_t*
     memset(&L, 0, sizeof(L));
     memcpy(&L, lut_host, (size_t)cn * 256);
     const ew_split s = ew_plan(ctx, dst, n, true);
-    const int al_s = al16(src + s.head) && ctx->flat_ops;
+    const int al_s = al16(src + s.head) && ctx->opt.v[VP_OPT_FLAT_OPS];
     const dim3 grid(s.blocks), block(256);
     switch (cn) {
         case 1: hipLaunchKernelGGL(k_lut_u8<1>, grid, block, 0, ctx->stream, src, L, n, s.head, s.ngroups, al_s, dst); break;
@@ -368,7 +368,7 @@ int vpk_lut_u8(vp_ctx* ctx, const uint8_t* src, size_t n, int cn, const uint8_t*
 
 int vpk_split_u8(vp_ctx* ctx, const uint8_t* src, size_t npx, int cn, uint8_t* p0, uint8_t* p1, uint8_t* p2, uint8_t* p3)
 {
-    const int vec = ctx->flat_ops && al16(src) && al16(p0) && al16(p1) && al16(p2) && al16(p3);     // (a null plane counts as aligned)
+    const int vec = ctx->opt.v[VP_OPT_FLAT_OPS] && al16(src) && al16(p0) && al16(p1) && al16(p2) && al16(p3);     // (a null plane counts as aligned)
     const ew_split s = ew_plan(ctx, src, npx, false);
     const dim3 grid(s.blocks), block(256);
     switch (cn) {
@@ -382,7 +382,7 @@ int vpk_split_u8(vp_ctx* ctx, const uint8_t* src, size_t npx, int cn, uint8_t* p
 
 int vpk_merge_u8(vp_ctx* ctx, const uint8_t* p0, const uint8_t* p1, const uint8_t* p2, const uint8_t* p3, size_t npx, int cn, uint8_t* dst)
 {
-    const int vec = ctx->flat_ops && al16(dst) && al16(p0) && al16(p1) && al16(p2) && al16(p3);
+    const int vec = ctx->opt.v[VP_OPT_FLAT_OPS] && al16(dst) && al16(p0) && al16(p1) && al16(p2) && al16(p3);
     const ew_split s = ew_plan(ctx, dst, npx, false);
     const dim3 grid(s.blocks), block(256);
     switch (cn) {

@@ -325,7 +325,7 @@ int vp_hough_run(vp_ctx* ctx, const uint8_t* d_src, const uint8_t* h_src, size_t
     VP_HIP(ctx, hipGetLastError());
 
     const size_t rowbytes = (size_t)(g.numrho + 2) * 4;
-    const bool lds = !ctx->hough_global && rowbytes <= HV_LDS_BYTES;
+    const bool lds = ctx->opt.v[VP_OPT_HOUGH_LDS] && rowbytes <= HV_LDS_BYTES;
     const int A = lds ? (int)std::min<size_t>(16, HV_LDS_BYTES / rowbytes) : 16;
     const int slabs = (g.numangle + A - 1) / A;
     const int cu = ctx->num_cu > 0 ? ctx->num_cu : 256;

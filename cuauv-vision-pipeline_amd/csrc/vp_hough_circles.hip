@@ -326,7 +326,7 @@ int vp_hough_circles_run(vp_ctx* ctx, const uint8_t* d_src, const uint8_t* h_src
     const float min_r2 = (float)min_radius * (float)min_radius, max_r2 = (float)max_radius * (float)max_radius;
     // two neighbours of a row cannot both be centres
     const size_t kcap = std::max<size_t>(1, (size_t)arows * (size_t)((acols + 1) / 2));
-    const bool lds = !ctx->hc_global && (size_t)nbins * 4 <= HC_LDS_MAX;
+    const bool lds = ctx->opt.v[VP_OPT_HOUGH_CIRCLES_LDS] && (size_t)nbins * 4 <= HC_LDS_MAX;
     const size_t ocap = std::min(kcap, (size_t)max_circles);
     const bool packed = h_src || stride == (size_t)w;
     const size_t bytes = (packed && !h_src ? 0 : vp_align(npx)) + vp_align(npx) + vp_canny_ws_bytes(w, h) + vp_align(npx * sizeof(hc_ray)) +
@@ -396,13 +396,13 @@ int vp_hough_circles_run(vp_ctx* ctx, const uint8_t* d_src, const uint8_t* h_src
     if (!lds) {
         ghist_blocks = std::max<size_t>(1, std::min<size_t>({(size_t)ncent, 1024, HC_GHIST_BYTES / ((size_t)nbins * 4)}));
         const size_t gbytes = ghist_blocks * (size_t)nbins * 4;
-        if (gbytes > ctx->hc_hist_bytes) {
-            if (ctx->hc_hist) { VP_HIP(ctx, hipFree(ctx->hc_hist)); ctx->hc_hist = nullptr; ctx->hc_hist_bytes = 0; }   // stream idle: synchronised above
-            VP_HIP(ctx, hipMalloc(&ctx->hc_hist, gbytes));
-            ctx->hc_hist_bytes = gbytes;
+        if (gbytes > ctx->hc.hist_bytes) {
+            if (ctx->hc.hist) { VP_HIP(ctx, hipFree(ctx->hc.hist)); ctx->hc.hist = nullptr; ctx->hc.hist_bytes = 0; }   // stream idle: synchronised above
+            VP_HIP(ctx, hipMalloc(&ctx->hc.hist, gbytes));
+            ctx->hc.hist_bytes = gbytes;
         }
     }
-    int* d_ghist = (int*)ctx->hc_hist;
+    int* d_ghist = (int*)ctx->hc.hist;
     u64* d_keys = nullptr;
     rc = vpk_hough_sort_keys(ctx, d_k0, d_k1, kcap, d_cnt + 1, 1, ncent, &d_keys);
     if (rc != VP_OK) return rc;
@@ -438,4 +438,10 @@ int vp_hough_circles_run(vp_ctx* ctx, const uint8_t* d_src, const uint8_t* h_src
     *n_circles = (int)kept;
     if (circles && max_circles > 0) memcpy(circles, hl + 1, std::min((size_t)kept, (size_t)max_circles) * 12);
     return VP_OK;
+}
+
+void vp_hough_circles_teardown(vp_ctx* ctx)
+{
+    if (ctx->hc.hist) (void)hipFree(ctx->hc.hist);
+    ctx->hc = vp_hough_circles_state{};
 }

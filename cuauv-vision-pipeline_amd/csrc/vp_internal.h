@@ -4,6 +4,7 @@
 #include <stdint.h>
 #include <stddef.h>
 #include "../../include/vp.h"
+#include "vp_options.h"
 
 typedef unsigned long long u64;
 typedef unsigned int u32;
@@ -28,7 +29,10 @@ struct vp_prof {
     int* ids;
 };
 
-struct vp_ctx {
+// A context's state, by owner.  Every struct here is plain data with no default member initialisers: vp_create zero-fills the whole
+// context (post.lock relies on that), and a unit that keeps lazily allocated state frees it in its own vp_<unit>_teardown.
+
+struct vp_runtime {           // the runtime's own (vp_api.hip); vp_ctx derives from it, so these read as ctx->stream, ctx->ws, ...
     int device;
     hipStream_t stream;
     hipStream_t own_stream;
@@ -48,54 +52,76 @@ struct vp_ctx {
     hipEvent_t ring_ev[4];
     int ring_busy[4];
     int ring_next;
-    int ct_lds_set;               // k_ct_jump's LDS attribute has been set on this context's device
-    uint32_t* ct_hint_host;       // pinned: head counts of the last batched contour pass (vp_contours.inl vp_ct_hint_slots)
-    int ct_hint_n;
-    uint32_t ct_heads_hint;   // border segments the last single-image contour pass counted (vp_find_contours_*: which form of the bookkeeping to launch)
     int num_cu;
-    int chain_streams;            // sub-batches of a chain run on this many internal streams (>= 1)
-    hipStream_t aux[4];
+    hipEvent_t ev_upload;         // recorded after an enqueued host-to-device copy (vp_memcpy_h2d_async / vp_wait_uploads)
+    vp_prof prof;
+    char err[256];
+};
+
+struct vp_chain_state {       // the chain's side streams (vp_api_morph_chain.hip), made by vp_create
+    hipStream_t aux[4];           // sub-batches of a chain run on these (VP_OPT_CHAIN_STREAMS of them)
     hipEvent_t ev_fork, ev_join[4];
     hipStream_t fb_stream;        // side stream of the labelling: the one-level kernels for crowded frames run here, beside the label write
     hipEvent_t ev_fb_fork, ev_fb_join;
-    hipEvent_t ev_upload;         // recorded after an enqueued host-to-device copy (vp_memcpy_h2d_async / vp_wait_uploads)
-    hipStream_t post_stream[4];   // posts by DMA (vp_post.hip): device image -> ring slot copies run on these lanes, beside the context's stream; made on first use
-    hipEvent_t post_fork;         // "the image as it is now" on the context's stream
-    hipEvent_t post_free[32];     // end-of-copy events handed back by vp_post_free
-    int post_nfree;
-    int post_lock;                // spin lock of the three fields above (a context is zero-filled at creation: no constructors in here)
-    const u32* cb_folds_dev;      // colour balance: device counter of tiles whose running mean had to be folded (last call); null or cb_folds_own
-    u32* cb_folds_own;            // context-owned device word the counter is copied to (the workspace it is made in is carved anew per call)
-    int ccl_levels;               // 2: two-level labelling with the one-level kernels as fallback (default); 1: one-level only
+};
+
+struct vp_ccl_state {         // labelling (vp_ccl.hip, vp_ccl3.inl)
     size_t c3_lds_set[6];         // dynamic LDS the crowded-frame kernels have been allowed on THIS device (link, label; short and tall strips): the attribute is per device
     void* c3_acc;                 // crowded-frame labelling: accumulators of components that span strips, all empty between calls (vp_ccl.hip)
     size_t c3_acc_bytes;
     int c3_acc_dirty;             // not known to be all empty (a call cut short, another stream): c3_acc_acquire reinitialises it before use
-    uint32_t* ccl_hint_host;      // pinned: frames the merge of the last two-level labelling call handed over, written by the device, read without synchronising (vp_ccl_hint.h)
-    int ccl_hint_failed;          // the word could not be allocated: the crowded-frame kernels are always queued
-    int ccl_hint_mode, ccl_hint_quiet;   // ccl_hint_state between calls (zero: a new context starts LEAN)
-    int ccl_crowded_force;        // VP_OPT_CCL_CROWDED: 0 (default) by the hint, 1 always the crowded-frame kernels, 2 always the one stand-in launch
-    int ccl_beside;               // set around a vpk_ccl that has other work of the same call on a side stream beside it (the chain's contour pass): counts as a second stream, i.e. FULL
-    int ccl_prepared[2];          // that run has been queued on this context (short / tall strips)
-    u32* ccl_zero_dev;            // a device word that holds 0: the empty list of the crowded-frame kernels' one preparing run (ccl_prepare_crowded, vp_ccl.hip)
-    int ccl_launches;             // kernels of the labelling sequence the last vpk_ccl queued (vp_ccl_last_launches)
-    int hough_global;             // 1: every Hough vote is a global atomic (VP_OPT_HOUGH_LDS 0); 0 (default): rows counted in LDS where they fit
-    int blur_onepass;             // VP_OPT_BLUR_ONEPASS: -1 (default) the measured choice, 1 the one-pass kernel wherever its tile fits, 0 always two passes
-    int median_mask;              // VP_OPT_MEDIAN_MASK: -1 (default) the measured choice, 1 the mask kernel for every mask it can serve, 0 never
-    int clahe_split;              // VP_OPT_CLAHE_SPLIT: 0 (default) the measured choice, n >= 1 that many blocks share one CLAHE tile's histogram
-    int label_moments_lds;        // VP_OPT_LABEL_MOMENTS_LDS: -1 (default) the measured choice, 1 the block's LDS table wherever it fits, 0 always device atomics
-    int hc_global;                // 1: HoughCircles radius histograms always in device memory (VP_OPT_HOUGH_CIRCLES_LDS 0); 0 (default): in LDS where they fit
-    void* hc_hist;                // HoughCircles radius histograms of the global form: grow-only, sized per call by its centre count
-    size_t hc_hist_bytes;
-    int flat_ops;                 // 1 (default): the per-operator kernels take their 16-px-per-lane forms when rows are packed and pointers aligned; 0: always the generic kernels (tests)
-    int ccl_mcap;                 // components per frame the merge block accepts (-1: its LDS capacity); tests lower it to force the fallback
-    u32* agauss_taps;             // Gaussian adaptive threshold: 8 slots of 256 integer taps (half kernels), made on first use
-    int agauss_n[8];              // block size held by each slot (0: empty)
-    int agauss_e[8];              // its scale: tap i = agauss_taps[slot][i] * 2^-agauss_e
-    u32 agauss_host[8][256];      // host copy of each slot
-    int agauss_next;              // slot replaced next
-    vp_prof prof;
-    char err[256];
+    uint32_t* hint_host;          // pinned: frames the merge of the last two-level labelling call handed over, written by the device, read without synchronising (vp_ccl_hint.h)
+    int hint_failed;              // the word could not be allocated: the crowded-frame kernels are always queued
+    int hint_mode, hint_quiet;    // ccl_hint_state between calls (zero: a new context starts LEAN)
+    int beside;                   // set around a vpk_ccl that has other work of the same call on a side stream beside it (the chain's contour pass): counts as a second stream, i.e. FULL
+    int prepared[2];              // that run has been queued on this context (short / tall strips)
+    u32* zero_dev;                // a device word that holds 0: the empty list of the crowded-frame kernels' one preparing run (ccl_prepare_crowded, vp_ccl.hip)
+    int launches;                 // kernels of the labelling sequence the last vpk_ccl queued (vp_ccl_last_launches)
+};
+
+struct vp_contour_state {     // contours (vp_contours.inl)
+    int lds_set;                  // k_ct_jump's LDS attribute has been set on this context's device
+    uint32_t* hint_host;          // pinned: head counts of the last batched contour pass (vp_contours.inl vp_ct_hint_slots)
+    int hint_n;
+    uint32_t heads_hint;      // border segments the last single-image contour pass counted (vp_find_contours_*: which form of the bookkeeping to launch)
+};
+
+struct vp_hough_circles_state {   // HoughCircles (vp_hough_circles.hip)
+    void* hist;                   // HoughCircles radius histograms of the global form: grow-only, sized per call by its centre count
+    size_t hist_bytes;
+};
+
+struct vp_agauss_state {      // Gaussian adaptive threshold (vp_adaptive.hip)
+    u32* taps;                    // Gaussian adaptive threshold: 8 slots of 256 integer taps (half kernels), made on first use
+    int n[8];                     // block size held by each slot (0: empty)
+    int e[8];                     // its scale: tap i = taps[slot][i] * 2^-e
+    u32 host[8][256];             // host copy of each slot
+    int next;                     // slot replaced next
+};
+
+struct vp_post_state {        // posts by DMA (vp_post.hip)
+    hipStream_t stream[4];        // device image -> ring slot copies run on these lanes, beside the context's stream; made on first use
+    hipEvent_t fork;              // "the image as it is now" on the context's stream
+    int ready;                    // the four lanes and the fork event all exist (post_setup)
+    hipEvent_t free_ev[32];       // end-of-copy events handed back by vp_post_free
+    int nfree;
+    int lock;                     // spin lock of the fields above (a context is zero-filled at creation: no constructors in here)
+};
+
+struct vp_balance_state {     // colour balance (vp_balance.hip)
+    const u32* folds_dev;         // colour balance: device counter of tiles whose running mean had to be folded (last call); null or folds_own
+    u32* folds_own;               // context-owned device word the counter is copied to (the workspace it is made in is carved anew per call); lives behind d_tables
+};
+
+struct vp_ctx : vp_runtime {
+    vp_options opt;               // indexed by VP_OPT_* (vp_options.h); written by vp_create and vp_set_option only
+    vp_chain_state chain;
+    vp_ccl_state ccl;
+    vp_contour_state ct;
+    vp_hough_circles_state hc;
+    vp_agauss_state agauss;
+    vp_post_state post;
+    vp_balance_state cb;
 };
 
 // brackets one kernel launch with events when profiling is on
@@ -116,7 +142,13 @@ struct vp_prof_scope {
     }
 };
 
-void vp_post_teardown(vp_ctx* ctx);                        // vp_post.hip: joins and frees the post stream (vp_destroy)
+// What a unit set up lazily on the context, freed beside the code that allocates it (vp_destroy calls them).  Each is safe on state
+// that was never set up and safe to call twice.
+void vp_post_teardown(vp_ctx* ctx);                        // vp_post.hip: joins and frees the post lanes
+void vp_ccl_teardown(vp_ctx* ctx);                         // vp_ccl.hip (vp_ccl3.inl's state as well)
+void vp_contours_teardown(vp_ctx* ctx);                    // vp_contours.inl
+void vp_hough_circles_teardown(vp_ctx* ctx);               // vp_hough_circles.hip
+void vp_adaptive_teardown(vp_ctx* ctx);                    // vp_adaptive.hip
 
 // ---- workspace ---------------------------------------------------------------------------
 int vp_ws_reserve(vp_ctx* ctx, size_t bytes);               // may reallocate (synchronises)

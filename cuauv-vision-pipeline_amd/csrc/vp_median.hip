@@ -267,7 +267,7 @@ __global__ __launch_bounds__(256) void k_median_mask(const uint8_t* __restrict__
 int vpk_median_blur(vp_ctx* ctx, const uint8_t* d_src, size_t sstride, int w, int h, int cn, int ksize, int binary_hint, const u64* d_src_bits, uint8_t* d_dst,
                     u64* d_dst_bits, int* made_bits)
 {
-    const vp_median_plan P = vp_median_make_plan(w, h, cn, ksize, binary_hint, d_src_bits != nullptr, d_dst_bits != nullptr, ctx->median_mask);
+    const vp_median_plan P = vp_median_make_plan(w, h, cn, ksize, binary_hint, d_src_bits != nullptr, d_dst_bits != nullptr, ctx->opt.v[VP_OPT_MEDIAN_MASK]);
     const size_t rowbytes = (size_t)w * cn;
     vp_prof_scope ps(ctx, VPK_OTHER);
     const dim3 grid(P.gx, P.gy), block(P.block);

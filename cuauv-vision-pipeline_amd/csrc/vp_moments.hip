@@ -197,7 +197,7 @@ int vpk_moments_u8(vp_ctx* ctx, const uint8_t* d_src, size_t stride, int w, int 
 // one row every block adds to, and measured alone it serialises the device atomics; 0 with VP_OPT_LABEL_MOMENTS_LDS 0
 int vp_label_moments_lds_rows(const vp_ctx* ctx, int nlabels)
 {
-    if (ctx->label_moments_lds == 0) return 0;
+    if (ctx->opt.v[VP_OPT_LABEL_MOMENTS_LDS] == 0) return 0;
     if (nlabels <= LM_LDS_LABELS) return nlabels;
     return LM_HOT_LABELS;
 }

@@ -16,22 +16,35 @@
 #include "vp_internal.h"
 
 namespace {
-constexpr int kPostEvents = (int)(sizeof(((vp_ctx*)nullptr)->post_free) / sizeof(hipEvent_t));
+constexpr int kPostEvents = (int)(sizeof(vp_post_state::free_ev) / sizeof(hipEvent_t));
 
 struct PostLock {
     int* w;
-    explicit PostLock(vp_ctx* ctx) : w(&ctx->post_lock) { while (__atomic_exchange_n(w, 1, __ATOMIC_ACQUIRE)) __builtin_ia32_pause(); }
+    explicit PostLock(vp_ctx* ctx) : w(&ctx->post.lock) { while (__atomic_exchange_n(w, 1, __ATOMIC_ACQUIRE)) __builtin_ia32_pause(); }
     ~PostLock() { __atomic_store_n(w, 0, __ATOMIC_RELEASE); }
 };
 
-constexpr int kLanes = (int)(sizeof(((vp_ctx*)nullptr)->post_stream) / sizeof(hipStream_t));
+constexpr int kLanes = (int)(sizeof(vp_post_state::stream) / sizeof(hipStream_t));
 
+// frees whichever lanes and fork event exist (the caller holds the lock, or is vp_destroy)
+void post_release(vp_ctx* ctx)
+{
+    ctx->post.ready = 0;
+    if (ctx->post.fork) { (void)hipEventDestroy(ctx->post.fork); ctx->post.fork = nullptr; }
+    for (int i = 0; i < kLanes; i++)
+        if (ctx->post.stream[i]) { (void)hipStreamDestroy(ctx->post.stream[i]); ctx->post.stream[i] = nullptr; }
+}
+
+// ready only once all four lanes and the fork event exist: a failure part-way leaves nothing behind and the next call starts anew
 int post_setup(vp_ctx* ctx)
 {
-    if (ctx->post_stream[0]) return VP_OK;
+    if (ctx->post.ready) return VP_OK;
     (void)hipSetDevice(ctx->device);
-    for (int i = kLanes - 1; i >= 0; i--) VP_HIP(ctx, hipStreamCreateWithFlags(&ctx->post_stream[i], hipStreamNonBlocking));
-    VP_HIP(ctx, hipEventCreateWithFlags(&ctx->post_fork, hipEventDisableTiming));
+    hipError_t e = hipSuccess;
+    for (int i = kLanes - 1; i >= 0 && e == hipSuccess; i--) e = hipStreamCreateWithFlags(&ctx->post.stream[i], hipStreamNonBlocking);
+    if (e == hipSuccess) e = hipEventCreateWithFlags(&ctx->post.fork, hipEventDisableTiming);
+    if (e != hipSuccess) { post_release(ctx); return vp_fail(ctx, VP_ERR_HIP, "post lanes", e); }
+    ctx->post.ready = 1;
     return VP_OK;
 }
 }  // namespace
@@ -46,15 +59,15 @@ int vp_post_d2h(vp_ctx* ctx, int lane, void* host_dst, const void* dev_src, size
         PostLock g(ctx);
         const int rc = post_setup(ctx);
         if (rc != VP_OK) return rc;
-        if (ctx->post_nfree > 0) ev = ctx->post_free[--ctx->post_nfree];
+        if (ctx->post.nfree > 0) ev = ctx->post.free_ev[--ctx->post.nfree];
     }
     if (!ev) VP_HIP(ctx, hipEventCreateWithFlags(&ev, hipEventDisableTiming));
     // "the image as it is now": everything queued so far on the context's stream, nothing queued later.  Copies of one lane run in
     // the order they were queued (a block keeps its lane, so a slot is never written by two copies at once); different lanes run
     // side by side on the copy engines - a copy has ~30 us of fixed latency, and a module's posts of one frame go to different blocks.
-    hipStream_t ps = ctx->post_stream[lane % kLanes];
-    hipError_t e = hipEventRecord(ctx->post_fork, ctx->stream);
-    if (e == hipSuccess) e = hipStreamWaitEvent(ps, ctx->post_fork, 0);
+    hipStream_t ps = ctx->post.stream[lane % kLanes];
+    hipError_t e = hipEventRecord(ctx->post.fork, ctx->stream);
+    if (e == hipSuccess) e = hipStreamWaitEvent(ps, ctx->post.fork, 0);
     if (e == hipSuccess) e = hipMemcpyAsync(host_dst, dev_src, bytes, hipMemcpyDeviceToHost, ps);
     if (e == hipSuccess) e = hipEventRecord(ev, ps);
     if (e != hipSuccess) {
@@ -95,7 +108,7 @@ int vp_post_free(vp_ctx* ctx, void* done)
     if (!done) return VP_ERR_INVALID;
     if (ctx) {
         PostLock g(ctx);
-        if (ctx->post_nfree < kPostEvents) { ctx->post_free[ctx->post_nfree++] = (hipEvent_t)done; return VP_OK; }
+        if (ctx->post.nfree < kPostEvents) { ctx->post.free_ev[ctx->post.nfree++] = (hipEvent_t)done; return VP_OK; }
     }
     (void)hipEventDestroy((hipEvent_t)done);
     return VP_OK;
@@ -105,10 +118,9 @@ int vp_post_free(vp_ctx* ctx, void* done)
 
 void vp_post_teardown(vp_ctx* ctx)
 {
-    if (!ctx->post_stream[0]) return;
-    for (int i = 0; i < kLanes; i++) (void)hipStreamSynchronize(ctx->post_stream[i]);
-    for (int i = 0; i < ctx->post_nfree; i++) (void)hipEventDestroy(ctx->post_free[i]);
-    ctx->post_nfree = 0;
-    (void)hipEventDestroy(ctx->post_fork);
-    for (int i = 0; i < kLanes; i++) { (void)hipStreamDestroy(ctx->post_stream[i]); ctx->post_stream[i] = nullptr; }
+    for (int i = 0; i < kLanes; i++)
+        if (ctx->post.stream[i]) (void)hipStreamSynchronize(ctx->post.stream[i]);
+    for (int i = 0; i < ctx->post.nfree; i++) (void)hipEventDestroy(ctx->post.free_ev[i]);
+    ctx->post.nfree = 0;
+    post_release(ctx);
 }

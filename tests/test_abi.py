@@ -7,6 +7,8 @@ import re
 import numpy as np
 import pytest
 
+from abi_header import _header_prototypes, _header_text, header_options
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
@@ -24,6 +26,28 @@ def test_libvp_exports_every_declared_symbol():
     for n in names:
         assert hasattr(lib, n), f"libvp.so does not export {n}"
     assert set(_vp.exported_symbols()) == set(names), set(_vp.exported_symbols()) ^ set(names)
+
+
+def test_every_prototype_is_bound_as_declared():
+    """Return type and argument list of every prototype of include/vp.h against vision/_vp.py's _SIGS, and every VP_OPT_* against its
+    OPT_*: the one place that says "declared and bound alike" (the *_abi files keep what is their family's own)."""
+    from vision import _vp
+    protos, header = _header_prototypes(), _header_text()
+    assert set(protos) == set(n for n in _declared("vp.h") if n.startswith("vp_")), "a declaration the prototype parser does not read"
+    assert set(protos) == set(_vp._SIGS), set(protos) ^ set(_vp._SIGS)
+    returns = {"int": C.c_int, "const char*": C.c_char_p, "void*": C.c_void_p, "vp_ctx*": C.c_void_p, "vp_feeder*": C.c_void_p,
+               "unsigned int": C.c_uint, "uint64_t": C.c_uint64}
+    for name, (ret, types) in protos.items():
+        res, args = _vp._SIGS[name]
+        assert ret in returns and res is returns[ret], (name, ret, res)
+        # a typed pointer or a char* binds a pointer argument as well as void* does
+        bound = [C.c_void_p if a is C.c_char_p or (isinstance(a, type) and issubclass(a, C._Pointer)) else a for a in args]
+        assert bound == types, (name, bound, types)
+        if re.search(name + r"\s*\(\s*(const\s+)?vp_ctx\s*\*", header):
+            assert args[0] is C.c_void_p, (name, "the context is bound as void*")
+    options = header_options()
+    assert len(options) == 11 and sorted(options.values()) == list(range(1, 12))
+    assert options == {n[4:]: getattr(_vp, n) for n in dir(_vp) if n.startswith("OPT_")}
 
 
 def test_host_only_entry_points(oracle):

@@ -8,56 +8,20 @@ import re
 import numpy as np
 import pytest
 
+from abi_header import _header_prototypes
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 NEW = ["vp_gaussian_blur_dev", "vp_resize_dev", "vp_warp_affine_dev", "vp_threshold_u8_dev", "vp_otsu_threshold_dev",
        "vp_adaptive_threshold_mean_dev", "vp_hist_u8_dev", "vp_ccl_dev", "vp_ccl_bits_dev"]
 
 
-def _header_prototypes():
-    """name -> list of ctypes argument types, from the declarations of include/vp.h (pointers are void*, as _vp.py binds them)."""
-    txt = open(os.path.join(ROOT, "include", "vp.h")).read()
-    txt = re.sub(r"/\*.*?\*/", "", txt, flags=re.S)
-    txt = " ".join(l for l in txt.splitlines() if not l.strip().startswith("#"))
-    out = {}
-    for ret, name, args in re.findall(r"\b(int|void\s*\*|uint64_t|unsigned int|const char\s*\*)\s+(vp_[a-z0-9_]+)\s*\(([^)]*)\)\s*;", txt):
-        types = []
-        for a in args.split(","):
-            a = a.strip()
-            if a in ("void", ""):
-                continue
-            if "*" in a:
-                types.append(C.c_void_p)
-            elif re.match(r"(const\s+)?size_t\b", a):
-                types.append(C.c_size_t)
-            elif re.match(r"(const\s+)?double\b", a):
-                types.append(C.c_double)
-            elif re.match(r"(const\s+)?float\b", a):
-                types.append(C.c_float)
-            elif re.match(r"(const\s+)?int64_t\b", a):
-                types.append(C.c_int64)
-            elif re.match(r"(const\s+)?int\b", a):
-                types.append(C.c_int)
-            else:
-                types.append(a)
-        out[name] = (ret, types)
-    return out
-
-
 def test_new_symbols_are_exported_declared_and_bound_alike():
     from vision import _vp
     protos = _header_prototypes()
     lib = C.CDLL(_vp.LIB_PATH)
-    for name in NEW:
-        assert hasattr(lib, name), f"libvp.so does not export {name}"
-        assert name in protos, f"include/vp.h does not declare {name}"
-        assert name in _vp._SIGS, f"vision/_vp.py does not bind {name}"
-        ret, types = protos[name]
-        res, args = _vp._SIGS[name]
-        assert ret == "int" and res is C.c_int
-        bound = [C.c_void_p if (isinstance(a, type) and issubclass(a, C._Pointer)) else a for a in args[1:]]   # args[0]: the context
-        assert bound == types[1:], (name, bound, types[1:])
-        assert args[0] is C.c_void_p
+    for name in NEW:      # that each is bound as declared: test_abi.py::test_every_prototype_is_bound_as_declared
+        assert hasattr(lib, name) and name in protos and name in _vp._SIGS, name
 
 
 def test_blur_onepass_option_is_declared():
