@@ -4,73 +4,39 @@
 
 // ---- morphology planning ---------------------------------------------------------------------------
 
-struct rect_se { int kw, kh, ax, ay; };
+// the stage planner (splits at extent 31, merges neighbours of one kind) and the grouping into launches: vp_morph_plan.h
+typedef mb_rect rect_se;
+static_assert(MB_OP_ERODE == VP_MORPH_ERODE && MB_OP_DILATE == VP_MORPH_DILATE && MB_OP_OPEN == VP_MORPH_OPEN && MB_OP_CLOSE == VP_MORPH_CLOSE,
+              "vp_morph_plan.h: operation codes");
+static void push_rect_stage(std::vector<vp_bitstage>& v, int dilate, const rect_se& k) { mb_push_rect_stage(v, dilate, k); }
+static int stages_for_op(std::vector<vp_bitstage>& v, int op, const rect_se& k) { return mb_stages_for_op(v, op, k) ? VP_OK : VP_ERR_INVALID; }
 
-// Adds one rect erode/dilate to a stage list, split so that every stage has extents <= 31 (the kernels' funnel shifts).
-static void push_rect_stage(std::vector<vp_bitstage>& v, int dilate, const rect_se& k)
-{
-    int l = k.ax, r = k.kw - 1 - k.ax, u = k.ay, d = k.kh - 1 - k.ay;
-    // merge with the previous stage of the same kind (erode∘erode / dilate∘dilate with cv2's border
-    // rule equal one pass with summed extents: the image is a box, clamping an intermediate sample
-    // into it never increases a coordinate distance)
-    if (!v.empty() && v.back().dilate == dilate) {
-        l += v.back().l; r += v.back().r; u += v.back().u; d += v.back().d;
-        v.pop_back();
-    }
-    do {
-        vp_bitstage s;
-        s.dilate = dilate;
-        s.l = l > 31 ? 31 : l; s.r = r > 31 ? 31 : r; s.u = u > 31 ? 31 : u; s.d = d > 31 ? 31 : d;
-        l -= s.l; r -= s.r; u -= s.u; d -= s.d;
-        v.push_back(s);
-    } while (l | r | u | d);
-}
-
-// Runs a stage list over bit images, grouping stages into launches whose halo fits LDS.
-// bits_a holds the input; bits_b is scratch of equal size.  The final launch writes out_bits /
-// out_mask (either may be NULL).  With an empty list the input is forwarded.
-static int run_bit_stages(vp_ctx* ctx, const std::vector<vp_bitstage>& st, u64* bits_a, u64* bits_b, int w, int h, int n,
-                          u64* out_bits, uint8_t* out_mask)
+// Runs a stage list over bit images, in the launches mb_group_stages makes of it (each one's halo fits LDS).  bits_in holds the
+// input and is only read: no launch writes it, however many there are.  bits_scratch and bits_out are planes of equal size that the
+// launches before the last alternate between (the last one reads bits_scratch); it writes bits_out when write_bits is set, and
+// out_mask when that is not NULL.  With an empty list the input is forwarded.
+static int run_bit_stages(vp_ctx* ctx, const std::vector<vp_bitstage>& st, const u64* bits_in, u64* bits_scratch, u64* bits_out, bool write_bits,
+                          int w, int h, int n, uint8_t* out_mask)
 {
     const size_t words = (size_t)n * h * vp_ww(w);
     if (st.empty()) {
-        if (out_bits && out_bits != bits_a) VP_HIP(ctx, hipMemcpyAsync(out_bits, bits_a, words * 8, hipMemcpyDeviceToDevice, ctx->stream));
-        if (out_mask) VP_TRY(vpk_unpack_bits(ctx, bits_a, w, h, n, out_mask));
+        if (write_bits) VP_HIP(ctx, hipMemcpyAsync(bits_out, bits_in, words * 8, hipMemcpyDeviceToDevice, ctx->stream));
+        if (out_mask) VP_TRY(vpk_unpack_bits(ctx, bits_in, w, h, n, out_mask));
         return VP_OK;
     }
-    const size_t lds_limit = 150 * 1024;
-    const int ww = vp_ww(w);
-    size_t i = 0;
-    u64* cur = bits_a;
-    u64* other = bits_b;
-    while (i < st.size()) {
+    std::vector<mb_launch> launches;
+    if (!mb_group_stages(st, vp_ww(w), launches)) return vp_fail(ctx, VP_ERR_UNSUPPORTED, "image too wide for the LDS bit-morphology strip");
+    u64* const plane[4] = {nullptr /* MB_BUF_IN: never a destination */, bits_scratch, bits_out /* MB_BUF_SCRATCH2 */, write_bits ? bits_out : nullptr};
+    for (size_t k = 0; k < launches.size(); k++) {
+        const mb_launch& L = launches[k];
+        const bool last = k + 1 == launches.size();
         vp_bitplan plan;
-        plan.n = 0;
-        int halo = 0;
-        while (i < st.size() && plan.n < VP_MAX_STAGES) {
-            const int nh = halo + st[i].u + st[i].d;
-            const size_t lds = (size_t)2 * (32 + nh) * ww * 8;
-            if (plan.n > 0 && lds > lds_limit) break;
-            if (plan.n == 0 && lds > lds_limit) return vp_fail(ctx, VP_ERR_UNSUPPORTED, "image too wide for the LDS bit-morphology strip");
-            plan.s[plan.n++] = st[i++];
-            halo = nh;
-        }
-        const bool last = i == st.size();
-        u64* dst_bits = last ? out_bits : other;
-        VP_TRY(vpk_morph_bits(ctx, plan, cur, w, h, n, dst_bits, last ? out_mask : nullptr));
-        if (!last) { u64* t = cur; cur = other; other = t; }
-    }
-    return VP_OK;
-}
-
-static int stages_for_op(std::vector<vp_bitstage>& v, int op, const rect_se& k)
-{
-    switch (op) {
-        case VP_MORPH_ERODE: push_rect_stage(v, 0, k); break;
-        case VP_MORPH_DILATE: push_rect_stage(v, 1, k); break;
-        case VP_MORPH_OPEN: push_rect_stage(v, 0, k); push_rect_stage(v, 1, k); break;
-        case VP_MORPH_CLOSE: push_rect_stage(v, 1, k); push_rect_stage(v, 0, k); break;
-        default: return VP_ERR_INVALID;
+        plan.n = L.count;
+        for (int i = 0; i < L.count; i++) plan.s[i] = st[(size_t)L.first + i];
+        const u64* src = L.src == MB_BUF_IN ? bits_in : plane[L.src];
+        u64* dst = plane[L.dst];
+        if (L.dst == MB_BUF_IN || L.src == L.dst || src == dst || (!last && !dst)) return vp_fail(ctx, VP_ERR_INVALID, "bit morphology: launch planes");
+        VP_TRY(vpk_morph_bits(ctx, plan, src, w, h, n, dst, last ? out_mask : nullptr));
     }
     return VP_OK;
 }
@@ -134,7 +100,7 @@ int vp_structuring_element(int shape, int kw, int kh, uint8_t* out)
 
 // one erode or dilate (after cv2 normalisation) on a device image; result in d_out
 static int morph_basic_dev(vp_ctx* ctx, int dilate, const norm_se& se, const uint8_t* d_in, int w, int h, int cn, bool binary,
-                           uint8_t* d_out, uint8_t* d_tmp, u64* bits_a, u64* bits_b, int16_t* d_offs, uint8_t* d_tab = nullptr)
+                           uint8_t* d_out, uint8_t* d_tmp, u64* bits_a, u64* bits_b, u64* bits_c, int16_t* d_offs, uint8_t* d_tab = nullptr)
 {
     const size_t nbytes = (size_t)w * h * cn;
     if (se.iterations == 0 || se.kw * se.kh == 1) {
@@ -146,7 +112,7 @@ static int morph_basic_dev(vp_ctx* ctx, int dilate, const norm_se& se, const uin
         rect_se k = {se.kw, se.kh, se.ax, se.ay};
         push_rect_stage(st, dilate, k);
         VP_TRY(vpk_pack_bits(ctx, d_in, (size_t)w, w, h, 1, bits_a, nullptr));
-        return run_bit_stages(ctx, st, bits_a, bits_b, w, h, 1, nullptr, d_out);
+        return run_bit_stages(ctx, st, bits_a, bits_b, bits_c, false, w, h, 1, d_out);
     }
     // generic: offsets of the structuring element (all-ones kernels are applied separably)
     std::vector<int16_t> offs;
@@ -206,7 +172,7 @@ static size_t morph_ws_bytes(const norm_se& se, int w, int h, int cn)
     const size_t bitbytes = (size_t)h * vp_ww(w) * 8;
     const size_t offbytes = ((size_t)se.kw * se.kh + se.kw + se.kh) * 4 + 64;
     const size_t tabbytes = se.allones ? 0 : 7 * nbytes;   // running min/max tables of the span form
-    return 4 * vp_align(nbytes) + 2 * vp_align(bitbytes) + vp_align(offbytes) + vp_align(tabbytes) + 4096;
+    return 4 * vp_align(nbytes) + 3 * vp_align(bitbytes) + vp_align(offbytes) + vp_align(tabbytes) + 4096;
 }
 
 // One morphology operation between device images (d_dst may equal neither d_src nor overlap it); temporaries are carved from the
@@ -225,6 +191,7 @@ static int morph_core(vp_ctx* ctx, int op, const norm_se& se, const uint8_t* d_s
     TAKE(d_tmp, uint8_t*, nbytes);
     TAKE(bits_a, u64*, bitbytes);
     TAKE(bits_b, u64*, bitbytes);
+    TAKE(bits_c, u64*, bitbytes);   // a plan of three or more launches alternates between bits_b and bits_c: bits_a is only read
     TAKE(d_offs, int16_t*, offbytes);
     TAKE(d_flag, int*, 4);
     bool binary = false;
@@ -247,16 +214,16 @@ static int morph_core(vp_ctx* ctx, int op, const norm_se& se, const uint8_t* d_s
         std::vector<vp_bitstage> st;
         rect_se k = {se.kw, se.kh, se.ax, se.ay};
         if (!(se.iterations == 0 || se.kw * se.kh == 1)) stages_for_op(st, op, k);
-        VP_TRY(run_bit_stages(ctx, st, bits_a, bits_b, w, h, 1, nullptr, d_dst));
+        VP_TRY(run_bit_stages(ctx, st, bits_a, bits_b, bits_c, false, w, h, 1, d_dst));
     } else if (op == VP_MORPH_ERODE || op == VP_MORPH_DILATE) {
-        VP_TRY(morph_basic_dev(ctx, op == VP_MORPH_DILATE, se, d_src, w, h, cn, binary, d_dst, d_tmp, bits_a, bits_b, d_offs, d_tab));
+        VP_TRY(morph_basic_dev(ctx, op == VP_MORPH_DILATE, se, d_src, w, h, cn, binary, d_dst, d_tmp, bits_a, bits_b, bits_c, d_offs, d_tab));
     } else if (op == VP_MORPH_OPEN || op == VP_MORPH_CLOSE) {
         const int first = op == VP_MORPH_CLOSE;
-        VP_TRY(morph_basic_dev(ctx, first, se, d_src, w, h, cn, binary, d_b, d_tmp, bits_a, bits_b, d_offs, d_tab));
-        VP_TRY(morph_basic_dev(ctx, !first, se, d_b, w, h, cn, binary, d_dst, d_tmp, bits_a, bits_b, d_offs, d_tab));
+        VP_TRY(morph_basic_dev(ctx, first, se, d_src, w, h, cn, binary, d_b, d_tmp, bits_a, bits_b, bits_c, d_offs, d_tab));
+        VP_TRY(morph_basic_dev(ctx, !first, se, d_b, w, h, cn, binary, d_dst, d_tmp, bits_a, bits_b, bits_c, d_offs, d_tab));
     } else {  // GRADIENT = dilate - erode
-        VP_TRY(morph_basic_dev(ctx, 1, se, d_src, w, h, cn, binary, d_b, d_tmp, bits_a, bits_b, d_offs, d_tab));
-        VP_TRY(morph_basic_dev(ctx, 0, se, d_src, w, h, cn, binary, d_c, d_tmp, bits_a, bits_b, d_offs, d_tab));
+        VP_TRY(morph_basic_dev(ctx, 1, se, d_src, w, h, cn, binary, d_b, d_tmp, bits_a, bits_b, bits_c, d_offs, d_tab));
+        VP_TRY(morph_basic_dev(ctx, 0, se, d_src, w, h, cn, binary, d_c, d_tmp, bits_a, bits_b, bits_c, d_offs, d_tab));
         VP_TRY(vpk_absdiff_sub_u8(ctx, d_b, d_c, nbytes, d_dst));
     }
     return VP_OK;
@@ -369,8 +336,9 @@ static int chain_core(vp_ctx* ctx, const vp_chain_desc* d, const vp_chain_buffer
         if (st.empty()) {
             VP_TRY(vpk_unpack_bits(ctx, bits_t, w, h, n, b->cleaned));
         } else {
-            // bits_t must survive when CCL labels the threshold mask; run_bit_stages only reads its input
-            VP_TRY(run_bit_stages(ctx, st, bits_t, bits_b, w, h, n, need_clean_bits ? bits_a : nullptr, b->cleaned));
+            // bits_t must survive: CCL (ccl = 2) and contours (source = threshed) read it afterwards.  run_bit_stages never writes its
+            // input, whatever the number of launches (mb_group_stages: they alternate between bits_b and bits_a)
+            VP_TRY(run_bit_stages(ctx, st, bits_t, bits_b, bits_a, need_clean_bits, w, h, n, b->cleaned));
             if (need_clean_bits) clean_bits = bits_a;
             if (d->ccl == 1) ccl_bits = bits_a;
         }

@@ -5,6 +5,7 @@
 #include <stddef.h>
 #include "../../include/vp.h"
 #include "vp_options.h"
+#include "vp_morph_plan.h"
 
 typedef unsigned long long u64;
 typedef unsigned int u32;
@@ -312,12 +313,7 @@ int vpk_distance_transform(vp_ctx* ctx, const uint8_t* d_src, size_t stride, int
 int vpk_min_max_loc(vp_ctx* ctx, const void* d_src, size_t stride, int w, int h, int depth, const uint8_t* d_mask, size_t mstride,
                     const unsigned long long* d_mbits, unsigned long long* d_out);
 
-// ---- morphology (vp_morph.hip) ---------------------------------------------------------------
-struct vp_bitstage { int dilate; int l, r, u, d; };  // window [-l, r] x [-u, d]
-#define VP_MAX_STAGES 32
-struct vp_bitplan { int n; vp_bitstage s[VP_MAX_STAGES]; };
-// words per row of a bit image
-static inline int vp_ww(int w) { return (w + 63) / 64; }
+// ---- morphology (vp_morph.hip; the plan: vp_morph_plan.h, with vp_bitstage, vp_bitplan and vp_ww) --------------
 // u8 (non-zero = 1) -> bits; d_flags[0] |= 1 if any byte is neither 0 nor 255
 int vpk_pack_bits(vp_ctx* ctx, const uint8_t* d_src, size_t stride, int w, int h, int n, u64* d_bits,
                   int* d_flags /*nullable*/);

@@ -22,8 +22,7 @@
 #include <cstdlib>
 #include <cstring>
 
-#define MB_THREADS 512
-#define MB_STRIP 32
+// MB_THREADS, MB_STRIP, the specialised shapes, the strip heights and the LDS limits: vp_morph_plan.h
 #ifdef VP_PROBE
 static __device__ int vp_dbg_bits;   // the VP_DBG switches of k_morph_bits_sym
 #endif
@@ -397,12 +396,9 @@ __global__ __launch_bounds__(MB_THREADS, 8) void k_morph_bits_sym(const u64* __r
 }
 
 template <int NS, int R0, int R1, int R2, int KIND, int STRIP>
-static int launch_sym_strip(vp_ctx* ctx, const u64* d_in, int w, int h, int n, u64* d_out_bits, uint8_t* d_out_mask)
+static int launch_sym_strip(vp_ctx* ctx, const u64* d_in, int w, int h, int n, size_t lds, u64* d_out_bits, uint8_t* d_out_mask)
 {
-    constexpr int HALO = R0 + (NS > 1 ? R1 : 0) + (NS > 2 ? R2 : 0);
     const int ww = vp_ww(w), strips = (h + STRIP - 1) / STRIP;
-    const size_t lds = (size_t)2 * (STRIP + 2 * HALO) * ww * sizeof(u64);
-    if (lds > 64 * 1024) return VP_ERR_UNSUPPORTED;
     vp_prof_scope prof(ctx, VPK_MORPH);
     hipLaunchKernelGGL((k_morph_bits_sym<NS, R0, R1, R2, KIND, STRIP>), dim3((unsigned)((size_t)n * strips)), dim3(MB_THREADS), lds, ctx->stream, d_in, w, h,
                        ww, strips, d_out_bits, d_out_mask);
@@ -410,54 +406,30 @@ static int launch_sym_strip(vp_ctx* ctx, const u64* d_in, int w, int h, int n, u
     return VP_OK;
 }
 
-// 64-row strips when they fit 40 KB of LDS (four blocks per CU; 1080p: 38 KB): the halo rows every stage recomputes are then 20 % of the
-// strip instead of 33 % (74 instead of 78 us per 128 frames); wider frames keep 32 rows
+// the strip height is the plan's (mb_sym_strip: 64 rows when they fit 40 KB of LDS, else 32)
 template <int NS, int R0, int R1, int R2, int KIND>
-static int launch_sym(vp_ctx* ctx, const u64* d_in, int w, int h, int n, u64* d_out_bits, uint8_t* d_out_mask)
+static int launch_sym(vp_ctx* ctx, const mb_kernel& K, const u64* d_in, int w, int h, int n, u64* d_out_bits, uint8_t* d_out_mask)
 {
-    constexpr int HALO = R0 + (NS > 1 ? R1 : 0) + (NS > 2 ? R2 : 0);
-    static const bool tall_ok = getenv("VP_MORPH_STRIP32") == nullptr;
-    if (tall_ok && h > 64 && (size_t)2 * (64 + 2 * HALO) * vp_ww(w) * sizeof(u64) <= 40 * 1024)
-        return launch_sym_strip<NS, R0, R1, R2, KIND, 64>(ctx, d_in, w, h, n, d_out_bits, d_out_mask);
-    return launch_sym_strip<NS, R0, R1, R2, KIND, MB_STRIP>(ctx, d_in, w, h, n, d_out_bits, d_out_mask);
-}
-
-// returns VP_ERR_UNSUPPORTED when the plan is not one of the specialised shapes
-static int try_sym(vp_ctx* ctx, const vp_bitplan& plan, const u64* d_in, int w, int h, int n, u64* ob, uint8_t* om)
-{
-    if (plan.n < 1 || plan.n > 3) return VP_ERR_UNSUPPORTED;
-    int rad[3] = {0, 0, 0}, kind = 0;
-    for (int i = 0; i < plan.n; i++) {
-        const vp_bitstage& s = plan.s[i];
-        if (s.l != s.r || s.l != s.u || s.l != s.d) return VP_ERR_UNSUPPORTED;
-        rad[i] = s.l;
-        kind |= (s.dilate ? 1 : 0) << i;
-    }
-#define SYM(NS, A, B, C, K) if (plan.n == NS && rad[0] == A && rad[1] == B && rad[2] == C && kind == K) return launch_sym<NS, A, B, C, K>(ctx, d_in, w, h, n, ob, om)
-    SYM(3, 2, 4, 2, 2);   // OPEN 5x5 + CLOSE 5x5  (erode, dilate x2 merged, erode)      — modules/red_buoy.py:31-33
-    SYM(3, 2, 4, 2, 5);   // CLOSE 5x5 + OPEN 5x5
-    SYM(2, 2, 2, 0, 2);   // OPEN 5x5                                                   — modules/bins.py:23-24
-    SYM(2, 2, 2, 0, 1);   // CLOSE 5x5
-    SYM(3, 1, 2, 1, 2);   // OPEN 3x3 + CLOSE 3x3
-    SYM(3, 1, 2, 1, 5);
-    SYM(2, 1, 1, 0, 2);   // OPEN 3x3
-    SYM(2, 1, 1, 0, 1);   // CLOSE 3x3
-    SYM(1, 1, 0, 0, 0); SYM(1, 1, 0, 0, 1);   // erode / dilate 3x3
-    SYM(1, 2, 0, 0, 0); SYM(1, 2, 0, 0, 1);   // erode / dilate 5x5
-#undef SYM
-    return VP_ERR_UNSUPPORTED;
+    if (K.strip == MB_TALL_STRIP) return launch_sym_strip<NS, R0, R1, R2, KIND, MB_TALL_STRIP>(ctx, d_in, w, h, n, K.lds, d_out_bits, d_out_mask);
+    return launch_sym_strip<NS, R0, R1, R2, KIND, MB_STRIP>(ctx, d_in, w, h, n, K.lds, d_out_bits, d_out_mask);
 }
 
 int vpk_morph_bits(vp_ctx* ctx, const vp_bitplan& plan, const u64* d_in, int w, int h, int n, u64* d_out_bits,
                    uint8_t* d_out_mask)
 {
     for (int i = 0; i < plan.n; i++)
-        if (plan.s[i].l > 31 || plan.s[i].r > 31 || plan.s[i].l < 0 || plan.s[i].r < 0 || plan.s[i].u < 0 || plan.s[i].d < 0)
-            return vp_fail(ctx, VP_ERR_INVALID, "bit stage extent");
-    {
-        static const bool no_sym = getenv("VP_NO_SYM") != nullptr;
-        const int rc = no_sym ? VP_ERR_UNSUPPORTED : try_sym(ctx, plan, d_in, w, h, n, d_out_bits, d_out_mask);
-        if (rc != VP_ERR_UNSUPPORTED) return rc;
+        if (!mb_stage_ok(plan.s[i])) return vp_fail(ctx, VP_ERR_INVALID, "bit stage extent");
+    static const bool sym_ok = getenv("VP_NO_SYM") == nullptr;
+    static const bool tall_ok = getenv("VP_MORPH_STRIP32") == nullptr;
+    const mb_kernel K = mb_choose_kernel(plan, w, h, sym_ok, tall_ok);
+    if (!K.ok) return VP_ERR_UNSUPPORTED;  // caller splits the plan
+    if (K.sym >= 0) {
+        // one case per specialised shape, in the order of mb_sym_shapes (the list both are made from)
+        int k = 0;
+#define SYM(NS, A, B, C, KIND) if (K.sym == k++) return launch_sym<NS, A, B, C, KIND>(ctx, K, d_in, w, h, n, d_out_bits, d_out_mask);
+        MB_SYM_SHAPES(SYM)
+#undef SYM
+        return vp_fail(ctx, VP_ERR_INVALID, "bit morphology: specialised shape");
     }
     mb_params P;
     P.w = w;
@@ -466,19 +438,15 @@ int vpk_morph_bits(vp_ctx* ctx, const vp_bitplan& plan, const u64* d_in, int w, 
     P.plan = plan;
     P.halo_top = P.halo_bot = 0;
     for (int i = 0; i < plan.n; i++) {
-        if (plan.s[i].l > 31 || plan.s[i].r > 31 || plan.s[i].l < 0 || plan.s[i].r < 0 || plan.s[i].u < 0 || plan.s[i].d < 0)
-            return vp_fail(ctx, VP_ERR_INVALID, "bit stage extent");
         P.halo_top += plan.s[i].u;
         P.halo_bot += plan.s[i].d;
     }
     P.rows = MB_STRIP + P.halo_top + P.halo_bot;
     P.strips = (h + MB_STRIP - 1) / MB_STRIP;
-    const size_t lds = (size_t)2 * P.rows * P.ww * sizeof(u64);
-    if (lds > 160 * 1024) return VP_ERR_UNSUPPORTED;  // caller splits the plan
-    if (lds > 64 * 1024)
-        VP_HIP(ctx, hipFuncSetAttribute(reinterpret_cast<const void*>(k_morph_bits), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    if (K.lds > MB_SYM_LDS)
+        VP_HIP(ctx, hipFuncSetAttribute(reinterpret_cast<const void*>(k_morph_bits), hipFuncAttributeMaxDynamicSharedMemorySize, (int)K.lds));
     vp_prof_scope prof(ctx, VPK_MORPH);
-    hipLaunchKernelGGL(k_morph_bits, dim3((unsigned)((size_t)n * P.strips)), dim3(MB_THREADS), lds, ctx->stream, d_in, P,
+    hipLaunchKernelGGL(k_morph_bits, dim3((unsigned)((size_t)n * P.strips)), dim3(MB_THREADS), K.lds, ctx->stream, d_in, P,
                        d_out_bits, d_out_mask);
     VP_HIP(ctx, hipGetLastError());
     return VP_OK;
