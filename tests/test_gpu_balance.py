@@ -1,8 +1,13 @@
 """GPU parity for the colour balance (utils/color_correction/color_balance.cpp process_frame, modules/color_balance.py
 balance) and the 8-bit HSV -> BGR conversion it uses, against the oracle's statement-by-statement restatement."""
+import os
+import subprocess
+import sys
+
 import numpy as np
 import pytest
 
+import balance_cases as BC
 import frames as F
 
 pytestmark = pytest.mark.gpu
@@ -138,7 +143,8 @@ def test_running_mean_is_reproduced_not_approximated(vp, oracle):
     """The reference's tile mean is a sequential fold (avg += (x - avg) / count, cpp:466-468).  The kernels build the gain tables
     from the exact mean only after checking that no value within a rigorous bound of it could change a table entry or a decision;
     otherwise they run the fold.  Both routes must give the reference's result (oracle mean_mode=0) - here on frames made to need
-    the fold, and with the fold forced for every tile."""
+    the fold; with the fold forced for every tile (every tiling of balance_cases, and batches) in
+    test_fold_forced_in_a_fresh_process, since libvp reads VP_CB_FORCE_FOLD once per process."""
     from vision.modules.color_balance import balance
     rng = np.random.default_rng(7)
     # 1. ordinary frames take the certified route: no tile folded
@@ -198,3 +204,98 @@ def test_process_frame_symbol_and_tilings_that_do_not_divide(vp, oracle, capfd):
     assert "do not divide" in err
     rc2, got2 = run(f, 3, 7)                                   # neither divides: same decision, reported once per kind of failure
     assert np.array_equal(got2, got)
+
+
+HSI_FLAG_SETS = [dict(hsi_contrast_correct=True, hsv_contrast_correct=False), dict(hsi_contrast_correct=True),
+                 dict(hsi_contrast_correct=True, hsv_contrast_correct=False, equalize_rgb=False, rgb_extrema_clipping=False)]   # as test_balance_hsi_stage_within_one
+
+
+def test_tiles_keep_their_own_means(vp, oracle):
+    """Frames whose tiles each have their own cast, inside the 1/6 band of cpp:474, so that every tile's own means reach its table
+    (tests/test_balance_cases.py proves that from the oracle alone): a wrong tile lookup, table offset or per-tile histogram offset
+    changes bytes.  Tile widths, frame widths and pixel counts that are no multiple of 4: the four-pixel groups of the three passes
+    straddle tile edges and row ends, and the tail pixels run in the tiled kernels."""
+    from vision.modules.color_balance import balance
+    for name, f, hb, vb in BC.tiled_cases():
+        for kw in (dict(), dict(hsv_contrast_correct=False), dict(rgb_contrast_correct=True), dict(adaptive_cast_correction=True)):
+            got = balance(f, horizontal_blocks=hb, vertical_blocks=vb, **kw)
+            BC.assert_exact(got, oracle.color_balance(f, horizontal_blocks=hb, vertical_blocks=vb, mean_mode=0, **kw), (name, kw))
+        # without equalize_rgb the tiling is never read (cpp:441): one that does not divide the frame is taken as 1 x 1
+        nhb, nvb = BC.NOT_DIVIDING[f.shape[:2]]
+        assert f.shape[1] % nhb and f.shape[0] % nvb
+        for kw in (dict(equalize_rgb=False), dict(equalize_rgb=False, rgb_contrast_correct=True)):
+            got = balance(f, horizontal_blocks=nhb, vertical_blocks=nvb, **kw)
+            BC.assert_exact(got, oracle.color_balance(f, mean_mode=0, **kw), (name, nhb, nvb, kw))
+
+
+def test_small_frames(vp, oracle):
+    """Frames of 1, 7 and 4 pixels: no full four-pixel group (or one group and a tail), ranges that collapse, percentile bounds of 0.
+    The oracle returns a result for every non-HSI flag set at each of these sizes (tests/test_balance_cases.py checks it), so none is
+    left out."""
+    from vision.modules.color_balance import balance
+    for i, (h, w) in enumerate(BC.SMALL_FRAMES):
+        for f in (F.s1_buoy(i, w, h), F.s3_noise(i, w, h), F.s3_noise(10 + i, w, h) // 2 + 60):
+            for flags in FLAG_SETS:
+                BC.assert_exact(balance(f, **flags), oracle.color_balance(f, mean_mode=0, **flags), (h, w, flags))
+
+
+@pytest.mark.parametrize("hb,vb", BC.BATCH_TILINGS)
+def test_batch_every_stage_against_the_oracle(vp, oracle, hb, vb):
+    """vp_color_balance_dev with n = 3 different frames, every stage, tiled and not, to a second buffer and in place: every frame
+    against the oracle directly (the per-frame offsets into the histograms, tables, plans and HSI state), the source unchanged when
+    it is not the destination, and nothing written past the destination."""
+    frames = BC.batch_frames()
+    exact = FLAG_SETS + [dict(adaptive_cast_correction=True)]
+    for flags in exact + HSI_FLAG_SETS:
+        exp = [oracle.color_balance(f, horizontal_blocks=hb, vertical_blocks=vb, mean_mode=0, **flags) for f in frames]
+        for in_place in (False, True):
+            rc, got, back, guard = BC.run_dev(vp, frames, BC.flag_bits(vp, **flags), hb, vb, in_place)
+            assert rc == vp.OK, (flags, in_place, rc)
+            for k in range(len(frames)):
+                if flags in exact:
+                    BC.assert_exact(got[k], exp[k], (flags, hb, vb, in_place, k))
+                else:
+                    BC.assert_hsi(got[k], exp[k], (flags, hb, vb, in_place, k))
+            if not in_place:
+                assert np.array_equal(back, frames), (flags, "the source was written")
+            assert (guard == BC.FILL).all(), (flags, in_place, "bytes after the destination were written")
+
+
+def test_tile_limit_and_refusals_through_the_c_abi(vp, oracle):
+    """1024 tiles (one-pixel tiles: a tile count of 1 per histogram) are accepted, 1025 refused; batched frames that do not start
+    4-byte aligned and, with equalize_rgb, a tiling that does not divide the frame are refused; a refusal writes nothing."""
+    from vision.modules.color_balance import balance
+    for (h, w), (hb, vb) in [((32, 32), (32, 32)), ((16, 64), (64, 16))]:
+        f = BC.tiled_frame(h, w, hb, vb, 7)
+        exp = oracle.color_balance(f, horizontal_blocks=hb, vertical_blocks=vb, mean_mode=0)
+        assert not np.array_equal(exp, oracle.color_balance(f, mean_mode=0))        # the tiles' own means matter here too
+        for in_place in (False, True):
+            rc, got, back, guard = BC.run_dev(vp, f[None], vp.CB_DEFAULT, hb, vb, in_place)
+            assert rc == vp.OK, (h, w, rc)
+            BC.assert_exact(got[0], exp, (h, w, hb, vb, in_place))
+            assert (guard == BC.FILL).all()
+        BC.assert_exact(balance(f, horizontal_blocks=hb, vertical_blocks=vb), exp, (h, w, "host entry"))
+    refused = [
+        (BC.tiled_frame(25, 41, 1, 1, 8)[None], 41, 25),                                            # 1025 tiles
+        (np.stack([F.s3_noise(0, 5, 3), F.s3_noise(1, 5, 3)]), 1, 1),                                # 45-byte frames in a batch
+        (F.s1_buoy(0, 32, 32)[None], 3, 1),                                                          # 32 % 3 != 0 with equalize_rgb
+    ]
+    for frames, hb, vb in refused:
+        rc, got, back, guard = BC.run_dev(vp, frames, vp.CB_DEFAULT, hb, vb, False)
+        assert rc == vp.ERR_UNSUPPORTED, (frames.shape, hb, vb, rc)
+        assert (got == BC.FILL).all() and (guard == BC.FILL).all(), (frames.shape, hb, vb, "a refused call wrote to the destination")
+        assert np.array_equal(back, frames)
+    with pytest.raises(vp.VpError):
+        balance(BC.tiled_frame(25, 41, 1, 1, 8), horizontal_blocks=41, vertical_blocks=25)
+
+
+def test_fold_forced_in_a_fresh_process():
+    """VP_CB_FORCE_FOLD=1 makes k_cb_plan1 run the reference's sequential fold for every tile; libvp reads it once per process, so a
+    fresh child runs every tiling of balance_cases and the batch of three against the oracle, checks after each call that every tile
+    of every frame was folded, and exits non-zero at the first mismatch."""
+    env = dict(os.environ)
+    env["VP_CB_FORCE_FOLD"] = "1"
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    r = subprocess.run([sys.executable, os.path.join(root, "tests", "_balance_fold_worker.py")], env=env, capture_output=True, text=True, timeout=300)
+    assert r.returncode == 0, (r.returncode, r.stdout[-1500:], r.stderr[-1500:])
+    assert "DONE 23" in r.stdout and "MISMATCH" not in r.stdout, r.stdout[-1500:]
