@@ -3,6 +3,7 @@
 // before the plan had a header of its own).  Built with -fsanitize=address,undefined by tests/test_ccl_plan_host.py.
 #include "vp_ccl_plan.h"
 #include <cstdio>
+#include <cstdlib>
 
 static void line(const char* env, int h, int w, int levels, int mcap, const ccl_tuning& T)
 {
@@ -29,5 +30,26 @@ int main()
     unsetenv("VP_C3_IDS");
     setenv("VP_CL_ROWS", "16", 1);
     line("VP_CL_ROWS=16", 1080, 1920, 2, -1, ccl_tuning_from_env());
+    unsetenv("VP_CL_ROWS");
+    // the shapes of tests/ccl_cases.py (masks on the two sides of every capacity) and the environment settings its child processes run under
+    static const int hw2[][2] = {{65, 200}, {65, 64}, {40, 2112}, {704, 200}, {64, 200}, {64, 400}, {64, 640}, {8192, 64}, {8193, 64}, {20, 4096}, {1024, 64},
+                                 {1026, 64}};
+    for (const auto& c : hw2)
+        for (int levels = 1; levels <= 2; levels++)
+            for (int mcap : {-1, 0, 6}) line("-", c[0], c[1], levels, mcap, T0);
+    struct tuned { const char* name; const char* value; int h, w, levels, mcap; };
+    static const tuned tn[] = {{"VP_CCL3", "0", 65, 200, 2, -1},      {"VP_CCL3", "0", 64, 200, 2, -1},       {"VP_C3_IDS", "8192", 20, 4096, 2, -1},
+                               {"VP_C3_IDS", "4096", 20, 4096, 2, -1}, {"VP_C3_IDS", "64", 1024, 64, 2, 0},   {"VP_C3_IDS", "64", 1026, 64, 2, 0},
+                               {"VP_CL_ROWS", "8", 65, 200, 1, -1},    {"VP_CL_ROWS", "8", 65, 200, 2, -1},    {"VP_CL_ROWS", "8", 40, 2112, 1, -1},
+                               {"VP_CL_ROWS", "8", 40, 2112, 2, -1},   {"VP_CL_ROWS", "16", 65, 200, 1, -1},   {"VP_CL_ROWS", "16", 65, 200, 2, -1},
+                               {"VP_CL_ROWS", "16", 40, 2112, 1, -1},  {"VP_CL_ROWS", "16", 40, 2112, 2, -1},  {"VP_CL_CAP", "64", 65, 200, 1, -1},
+                               {"VP_CL_CAP", "64", 65, 200, 2, -1}};
+    for (const tuned& t : tn) {
+        char env[64];
+        snprintf(env, sizeof env, "%s=%s", t.name, t.value);
+        setenv(t.name, t.value, 1);
+        line(env, t.h, t.w, t.levels, t.mcap, ccl_tuning_from_env());
+        unsetenv(t.name);
+    }
     return 0;
 }

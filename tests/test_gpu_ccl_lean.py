@@ -6,6 +6,7 @@ with either form forced and in automatic mode, where the number of launches the 
 import numpy as np
 import pytest
 
+import ccl_cases as CC
 import frames as F
 
 pytestmark = pytest.mark.gpu
@@ -31,20 +32,17 @@ def _ref(oracle, m, numbering):
     return _CACHE[key]
 
 
-def _segments(rows):
-    """Word segments of a strip: runs of set pixels, cut at every 64-pixel word boundary."""
-    b = rows > 0
-    start = b.copy()
-    start[:, 1:] &= ~b[:, :-1]
-    start[:, ::64] = b[:, ::64]
-    return int(start.sum())
+_segments = CC.segments
 
 
 def _crowded_strip(oracle, m):
-    """True when some 32-row strip holds more than 96 components or more than 962 word segments (what hands a frame over)."""
-    for y in range(0, m.shape[0], 32):
-        rows = np.ascontiguousarray(m[y:y + 32])
-        if oracle.ccl(rows, block=2)[0] - 1 > 96 or _segments(rows) > 962:
+    """True when some strip of the strip-local pass holds more than rc components or more than cap2 word segments (what hands a frame
+    over); strip height and cap2 are the frame's own (ccl_cases.geom, ccl_cases.cap2)."""
+    h, w = m.shape
+    rows, cap2 = CC.geom(h, w)[0], CC.cap2(h, w)
+    for y in range(0, h, rows):
+        part = np.ascontiguousarray(m[y:y + rows])
+        if oracle.ccl(part, block=2)[0] - 1 > CC.RC or _segments(part) > cap2:
             return True
     return False
 
@@ -96,7 +94,7 @@ def test_noise_frames(vp, oracle, forced, numbering, w, h):
         if (w, h) != SIZES[0]:
             assert _crowded_strip(oracle, m), (w, h, p)
         elif p == DENSITIES[0]:
-            assert not _crowded_strip(oracle, m) and _segments(m[:32]) <= 32 * 2 + 2      # not handed over: resolved by the merge
+            assert not _crowded_strip(oracle, m) and _segments(m[:32]) <= CC.cap2(h, w) == 32 * 2 + 2      # not handed over: resolved by the merge
         _check_one(vp, ctx, oracle, m, numbering)
         assert ctx.ccl_last_launches() == _launches(mode)
         _check_one(vp, ctx, oracle, m, numbering, want_labels=False)                      # statistics only
