@@ -313,6 +313,16 @@ int vpk_distance_transform(vp_ctx* ctx, const uint8_t* d_src, size_t stride, int
 int vpk_min_max_loc(vp_ctx* ctx, const void* d_src, size_t stride, int w, int h, int depth, const uint8_t* d_mask, size_t mstride,
                     const unsigned long long* d_mbits, unsigned long long* d_out);
 
+// ---- colour k-means and label masks (vp_kmeans.hip; the plan: vp_kmeans_plan.h) ---------------------------------
+// The whole loop of tests/kmeans_restate.py for arguments vp_kmeans_refusal admitted, enqueued: one launch that sets the table up from
+// d_cinit (k * cn floats) or d_seeds (k raster indices), one of them NULL, then max_iter assign and update launches that return at
+// once after the run has ended, then the label write when d_labels is given.  d_table: vp_kmeans_table_bytes(k, cn) bytes in the
+// layout of the plan header; lstride in int32 elements.  vpk_label_select: 255 where select[label] != 0 (select: k host bytes, passed
+// by value), the bit plane as well when d_bits is given and w % 64 == 0; one launch, enqueued.
+int vpk_kmeans(vp_ctx* ctx, const uint8_t* d_src, size_t stride, int w, int h, int cn, int k, const float* d_cinit, const int32_t* d_seeds, int max_iter,
+               double eps, uint8_t* d_table, int32_t* d_labels, size_t lstride);
+int vpk_label_select(vp_ctx* ctx, const int32_t* d_labels, size_t lstride, int w, int h, const uint8_t* select, int k, uint8_t* d_mask, size_t mstride, u64* d_bits);
+
 // ---- morphology (vp_morph.hip; the plan: vp_morph_plan.h, with vp_bitstage, vp_bitplan and vp_ww) --------------
 // u8 (non-zero = 1) -> bits; d_flags[0] |= 1 if any byte is neither 0 nor 255
 int vpk_pack_bits(vp_ctx* ctx, const uint8_t* d_src, size_t stride, int w, int h, int n, u64* d_bits,

@@ -1155,6 +1155,64 @@ def minMaxLoc(src, mask=None):
     return _gather("minMaxLoc", _feature.min_max_loc, _device_source(src)[0], mask)
 
 
+# ---- k-means (libvp vp_kmeans.hip): the exact value of what cv2.kmeans approximates, DESIGN.md section 4.26 -------------------------------
+KMEANS_RANDOM_CENTERS, KMEANS_USE_INITIAL_LABELS, KMEANS_PP_CENTERS = 0, 1, 2
+TERM_CRITERIA_COUNT = TERM_CRITERIA_MAX_ITER = 1
+TERM_CRITERIA_EPS = 2
+_FLT_EPSILON = 1.1920928955078125e-07
+
+
+def _kmeans_image_shape(n):
+    """(h, w), both at most 4096, with h w == n: the samples are clustered as the pixels of such an image (the raster order, and with
+    it every result, is the same for every such shape); None when n has no such pair of factors"""
+    for w in range(min(n, 4096), 0, -1):
+        if n % w == 0:
+            return (n // w, w) if n // w <= 4096 else None
+    return None
+
+
+def kmeans(data, K, bestLabels, criteria, attempts, flags, centers=None):
+    """cv2.kmeans in cv2's positional order on (N, d) samples, d <= 4, uint8 or float32 holding integers in 0..255 (the pixels of an
+    image, `img.reshape(-1, 3)`), N <= 2^24 with N = h w for some h, w <= 4096: (compactness, labels (N, 1) int32, centers (K, d)
+    float32), computed on the GPU as DESIGN.md section 4.26 states it (vision.utils.color.kmeans).  criteria is read as OpenCV reads
+    it: without the COUNT bit 100 iterations, with it maxCount clamped to 2..100; without the EPS bit eps = FLT_EPSILON.
+    KMEANS_RANDOM_CENTERS starts every attempt a from K distinct samples drawn from np.random.default_rng(a) - OpenCV draws K points
+    uniformly in the bounding box of the data from cv::theRNG(), which no restatement can follow -, and the attempt with the smallest
+    compactness wins.  KMEANS_PP_CENTERS and KMEANS_USE_INITIAL_LABELS are outside the accelerated path."""
+    if flags != KMEANS_RANDOM_CENTERS:
+        raise error("kmeans: only KMEANS_RANDOM_CENTERS is on the accelerated path (KMEANS_PP_CENTERS and KMEANS_USE_INITIAL_LABELS are outside it)")
+    from vision.devmat import to_host_readonly
+    data = to_host_readonly(data)
+    if not isinstance(data, np.ndarray) or data.ndim != 2 or data.dtype not in (np.uint8, np.float32) or 0 in data.shape:
+        raise error("kmeans: (N, d) uint8 or float32 samples only; anything else is outside the accelerated path")
+    n, d = data.shape
+    if d > 4:
+        raise error("kmeans: more than 4 dimensions is outside the accelerated path")
+    if n > 1 << 24:
+        raise error("kmeans: more than 2^24 samples is outside the accelerated path")
+    if data.dtype == np.float32:
+        if not (np.isfinite(data).all() and (data >= 0).all() and (data <= 255).all() and (data == np.floor(data)).all()):
+            raise error("kmeans: float32 samples that are not integers in 0..255 are outside the accelerated path")
+        data = data.astype(np.uint8)
+    K, attempts = int(K), int(attempts)
+    if K < 1 or K > n:
+        raise error("kmeans: K must be in 1..N")
+    if K > 256:
+        raise error("kmeans: K above 256 is outside the accelerated path")
+    if attempts < 1:
+        raise error("kmeans: attempts must be at least 1")
+    kind, max_count, eps = int(criteria[0]), int(criteria[1]), float(criteria[2])
+    max_count = min(max(max_count, 2), 100) if kind & TERM_CRITERIA_COUNT else 100
+    eps = max(eps, 0.0) if kind & TERM_CRITERIA_EPS else _FLT_EPSILON
+    shape = _kmeans_image_shape(n)
+    if shape is None:
+        raise error("kmeans: N is not h x w with both sides at most 4096: outside the accelerated path")
+    image = np.ascontiguousarray(data).reshape(shape + (d,))
+    compactness, labels, found = _gather("kmeans", _color.kmeans, image, K, max_count, eps, seed=0, attempts=attempts)
+    labels = np.ascontiguousarray(to_host_readonly(labels)).reshape(n, 1).copy()
+    return compactness, _into(bestLabels, labels), _into(centers, found)
+
+
 def adaptiveThreshold(src, maxValue, adaptiveMethod, thresholdType, blockSize, C, dst=None):
     """cv2.adaptiveThreshold (utils/color.py:220-292) in cv2's positional order on CV_8UC1 images.  ADAPTIVE_THRESH_MEAN_C: the mean
     path (libvp vp_adaptive_threshold_mean_*, block sizes 3..151); ADAPTIVE_THRESH_GAUSSIAN_C: the exact Gaussian-weighted mean

@@ -12,7 +12,7 @@ import numpy as np
 
 from vision import _vp
 from vision.devmat import DeviceMat, finish_uploads, lazy_enabled, to_host
-from vision.utils.helpers import as_mat, device_image, run_operator
+from vision.utils.helpers import as_mat, device_image, image_source, run_operator
 
 
 def _u8_image(mat, channels):
@@ -263,15 +263,9 @@ def thresh_color_distance(split: List[np.ndarray], color, distance: float, auto_
     return range_threshold(d2, 0, distance), sq
 
 
-def _outside_path(name):
-    def _f(*_a, **_k):
-        raise NotImplementedError(f"{name}: outside the accelerated path of this build")
-    _f.__name__ = name
-    return _f
-
-
-# the rest of the reference's utils/color.py (:156-392): names kept so that `from vision.utils.color import ...` lines of existing modules
-# import; calling them fails loudly instead of falling back to a CPU implementation
+# the rest of the reference's utils/color.py (:156-392).  Every name of it is implemented here now: the thresholds, Otsu and the adaptive
+# thresholds, kmeans with its two mask helpers (libvp vp_kmeans_*, vp_label_select_dev) and the white balances; only bgr_to_luv above
+# still fails loudly instead of falling back to a CPU implementation
 
 
 def _threshold(mat: np.ndarray, thresh: float, maxval: float, kind: int) -> np.ndarray:
@@ -471,11 +465,134 @@ def clahe_bgr(mat: np.ndarray, clip_limit: float = 2.0, tile_grid=(8, 8)) -> np.
     return lab_to_bgr(cv2_facade.merge((clahe(l, clip_limit, tile_grid), a, b)))[0]
 
 
-kmeans = _outside_path("kmeans")
+# ---- colour k-means (libvp vp_kmeans.hip) ------------------------------------------------------------------------
+KMEANS_MAX_SIDE, KMEANS_MAX_K, KMEANS_MAX_ITER = 4096, 256, 100
+
+
+def kmeans_seed_indices(n: int, k: int, seed: int) -> np.ndarray:
+    """The k distinct raster indices of the initial centres of a seeded run: drawn without replacement from
+    np.random.default_rng(seed), sorted, int32."""
+    return np.sort(np.random.default_rng(seed).choice(n, size=k, replace=False)).astype(np.int32)
+
+
+def kmeans_run(mat, k: int, max_iter: int, eps: float, centers=None, seed_index=None, labels=True):
+    """One run of libvp's vp_kmeans_* on a uint8 image, (h, w) or (h, w, 1..4): (compactness, labels, centres (k, cn) float32, counts
+    (k,) uint32, assign passes).  The initial centres are `centers` (k x cn values) or the pixels at the raster indices `seed_index`.
+    A DeviceMat (or the lazy mode) is clustered where it is and gives int32 labels that stay in HBM; labels=False asks for the
+    statistics alone (None in their place)."""
+    mat, cn = image_source(mat)
+    h, w = mat.shape[:2]
+    k, max_iter, eps = int(k), int(max_iter), float(eps)
+    if max(h, w) > KMEANS_MAX_SIDE:
+        raise ValueError("sides above 4096 are outside the accelerated path")
+    if not 1 <= k <= KMEANS_MAX_K:
+        raise ValueError("the number of centres must be in 1..256")
+    if k > h * w:
+        raise ValueError("more centres than pixels")
+    if not 1 <= max_iter <= KMEANS_MAX_ITER:
+        raise ValueError("the iterations must be in 1..100")
+    if not (eps >= 0.0 and np.isfinite(eps)):
+        raise ValueError("epsilon must be finite and not negative")
+    if (centers is None) == (seed_index is None):
+        raise ValueError("exactly one of centers and seed_index must be given")
+    if centers is not None:
+        init = np.ascontiguousarray(np.asarray(centers, dtype=np.float32).reshape(-1))
+        if init.size != k * cn or not np.isfinite(init).all():
+            raise ValueError("the initial centres must be k x channels finite values")
+        cptr, sptr = init.ctypes.data, None
+    else:
+        init = np.ascontiguousarray(np.asarray(seed_index).reshape(-1).astype(np.int64))
+        if init.size != k or init.min() < 0 or init.max() >= h * w:
+            raise ValueError("the seed indices must be k raster indices of the image")
+        init = init.astype(np.int32)
+        cptr, sptr = None, init.ctypes.data
+    out = np.zeros(16 + 4 * k * cn + 4 * k, np.uint8)
+    ctx = _vp.default_context()
+    lib = _vp.lib()
+    if lazy_enabled() or isinstance(mat, DeviceMat):
+        up = []
+        try:
+            if isinstance(mat, DeviceMat):
+                mat.refresh_device(ctx)
+            else:
+                mat = DeviceMat.from_host(ctx, mat, pending=up)
+            lab = DeviceMat(ctx, (h, w), np.int32) if labels else None
+            _vp.check(lib.vp_kmeans_dev(ctx.handle, mat.dev_ptr, w * cn, w, h, cn, k, cptr, sptr, max_iter, eps, None if lab is None else lab.dev_ptr, w * 4,
+                                        out.ctypes.data), ctx.handle)
+        finally:
+            finish_uploads(ctx, up)
+    else:
+        mat = np.ascontiguousarray(mat)
+        lab = np.empty((h, w), np.int32) if labels else None
+        _vp.check(lib.vp_kmeans_u8(ctx.handle, mat.ctypes.data, w, h, cn, k, cptr, sptr, max_iter, eps, None if lab is None else lab.ctypes.data,
+                                   out.ctypes.data), ctx.handle)
+    compactness = float(out[:8].view(np.float64)[0])
+    passes = int(out[8:12].view(np.int32)[0])
+    centres = out[16:16 + 4 * k * cn].view(np.float32).reshape(k, cn).copy()
+    counts = out[16 + 4 * k * cn:].view(np.uint32).copy()
+    return compactness, lab, centres, counts, passes
+
+
+def kmeans(mat: np.ndarray, num_centeroids: int, iterations: int = 10, epsilon: float = 1.0, *, centers=None, seed: int = 0,
+           attempts: int = 1) -> Tuple[float, np.ndarray, np.ndarray]:
+    """utils/color.py:295-323 as it was meant (the reference body cannot run: it reshapes to (-1, 2), calls np.reshape without an array
+    and hard-codes 10 iterations and epsilon 1.0 whatever it is given): clusters the colours of a uint8 image, (h, w) or (h, w, 1..4),
+    around num_centeroids centres on the GPU and returns (compactness, labels (h, w) int32, centers (k, channels) float32).
+    `iterations` (1..100) and `epsilon` are honoured.  What is computed is stated in DESIGN.md section 4.26 and tests/kmeans_restate.py;
+    it is what cv2.kmeans approximates, not its bits: distances in double, ties to the lowest index, exact integer sums, and an empty
+    cluster keeps its centre where OpenCV re-seeds it.
+
+    Additions to the mirror: `centers`, k x channels initial centres; without it the initial centres are num_centeroids distinct pixels
+    drawn from np.random.default_rng(seed + attempt), sorted by raster index and gathered on the device.  With attempts > 1 the run with
+    the smallest compactness wins, the first one on ties.  A DeviceMat in, or the lazy mode, gives a DeviceMat of labels that stays
+    in HBM; numpy in otherwise gives numpy out."""
+    attempts = int(attempts)
+    if attempts < 1:
+        raise ValueError("attempts must be at least 1")
+    mat, _cn = image_source(mat)
+    n, k = mat.shape[0] * mat.shape[1], int(num_centeroids)
+    if not 1 <= k <= min(n, KMEANS_MAX_K):
+        raise ValueError("the number of centres must be in 1..256 and at most the number of pixels")
+    if centers is not None:
+        return kmeans_run(mat, k, iterations, epsilon, centers=centers)[:3]
+    best = None
+    for attempt in range(attempts):
+        run = kmeans_run(mat, k, iterations, epsilon, seed_index=kmeans_seed_indices(n, k, int(seed) + attempt))
+        if best is None or run[0] < best[0]:
+            best = run
+    return best[0], best[1], best[2]
+
+
+def _label_mask(ctx, labels: DeviceMat, select: np.ndarray) -> DeviceMat:
+    """libvp vp_label_select_dev: the 0 / 255 mask of the labels whose byte in `select` is set, with its bit plane where the width
+    allows (as range_threshold's masks carry one)."""
+    from vision.devmat import _DevBuf
+    h, w = labels.shape
+    out = DeviceMat(ctx, (h, w), binary=True)
+    bits = _DevBuf(ctx, h * (w // 64) * 8) if w % 64 == 0 else None
+    _vp.check(_vp.lib().vp_label_select_dev(ctx.handle, labels.dev_ptr, w * 4, w, h, select.ctypes.data, len(select), out.dev_ptr, w,
+                                            None if bits is None else bits.ptr), ctx.handle)
+    out._bits = bits
+    return out
+
+
+def _device_labels(labels, centers):
+    """the context when `labels` is a device label image vp_label_select_dev takes for these centres, else None"""
+    if not (isinstance(labels, DeviceMat) and labels.dtype == np.int32 and labels.ndim == 2 and 1 <= len(centers) <= KMEANS_MAX_K
+            and 0 not in labels.shape and max(labels.shape) <= KMEANS_MAX_SIDE):
+        return None
+    ctx = _vp.default_context()
+    labels.refresh_device(ctx)
+    return ctx
 
 
 def mask_from_labels(labels: np.ndarray, centers: np.ndarray) -> List[np.ndarray]:
-    """utils/color.py:326-345: one 0 / 255 mask per centre (plain numpy in the reference as well)."""
+    """utils/color.py:326-345: one 0 / 255 mask per centre.  numpy labels: plain numpy, as in the reference.  The DeviceMat of labels
+    that kmeans returns: one mask per centre on the device (libvp vp_label_select_dev), each a DeviceMat known to be binary that
+    carries its bit plane when the width is a multiple of 64, so erode, distance_transform or median_blur read it packed."""
+    ctx = _device_labels(labels, centers)
+    if ctx is not None:
+        return [_label_mask(ctx, labels, (np.arange(len(centers)) == i).astype(np.uint8)) for i in range(len(centers))]
     acc = []
     for i, _c in enumerate(centers):
         mask = np.zeros(labels.shape, dtype=np.uint8)
@@ -484,7 +601,21 @@ def mask_from_labels(labels: np.ndarray, centers: np.ndarray) -> List[np.ndarray
     return acc
 
 
-mask_from_labels_target_color = _outside_path("mask_from_labels_target_color")
+def mask_from_labels_target_color(labels: np.ndarray, centers: np.ndarray, target_color, distance_func: Callable = color_dist) -> np.ndarray:
+    """utils/color.py:347-368 as it was meant: the 0 / 255 mask of the cluster whose centre is nearest to target_color, by
+    distance_func(centre, target_color), the lowest index on ties.  The reference hands the (index, centre) tuple of enumerate() to
+    distance_func and compares the labels with that tuple, which is a bug: its mask is always empty.  A DeviceMat of labels gives a
+    DeviceMat (see mask_from_labels)."""
+    if len(centers) == 0:
+        raise ValueError("no centres")
+    dists = [distance_func(c, target_color) for c in centers]
+    target = min(range(len(dists)), key=lambda i: dists[i])          # min keeps the first of equal keys
+    ctx = _device_labels(labels, centers)
+    if ctx is not None:
+        return _label_mask(ctx, labels, (np.arange(len(centers)) == target).astype(np.uint8))
+    ret = np.zeros(labels.shape, dtype=np.uint8)
+    ret[labels == target] = 255
+    return ret
 
 
 def _white_balance(bgr_img, kernel_size, ab_mean_out=None):

@@ -802,6 +802,37 @@ int vp_min_max_loc_u8(vp_ctx* ctx, const void* src_host, size_t stride, int w, i
 int vp_min_max_loc_dev(vp_ctx* ctx, const void* src_dev, size_t stride, int w, int h, int depth, const uint8_t* mask_dev, size_t mask_stride, int mask_w,
                        int mask_h, const unsigned long long* mask_bits_dev, void* out_host);
 
+/* ---- colour k-means (utils/color.py `kmeans`, cv2.kmeans) and the masks of a label image ------------------------------------------ *
+ * vp_kmeans_u8 / vp_kmeans_dev: clusters the pixels of a uint8 image of cn = 1..4 channels (w, h <= 4096, so N = w h <= 2^24) around
+ *   k = 1..256 centres (k <= N), as DESIGN.md section 4.26 and tests/kmeans_restate.py state it: a pixel goes to the centre with the
+ *   smallest sum over the channels of (double(p) - double(c))^2, the lowest index on ties; n, S1 = sum p and S2 = sum p^2 of every
+ *   cluster are exact integers; a centre moves to float32(double(S1) / double(n)), an empty cluster keeps its centre; the loop stops
+ *   after max_iter (1..100) assign passes, or with the pass after the largest squared shift of a centre fell to eps^2 or below.
+ *   The initial centres are centers_init (k * cn finite floats) or the pixels at the k raster indices seed_index (0..N-1): host
+ *   arrays, exactly one of them given.  labels (nullable): int32 (h, w), the index of every pixel's centre among the returned ones.
+ *   out_host receives struct { double compactness; int32_t iterations; int32_t k; float centers[k * cn]; uint32_t counts[k]; }
+ *   (host memory): the sum of squared distances of the last pass - computed on the host from its exact sums, the same bits on
+ *   every run -, the assign passes that ran, k, the centres, and the pixels of every cluster.
+ *   The host form takes a packed image and gives packed labels.  The device form reads rows of `stride` bytes and writes label rows
+ *   of labels_stride bytes; it enqueues the whole loop without visiting the host and synchronises once, at the end, to hand the
+ *   table back.
+ * vp_label_select_dev: mask = 255 where select_host[label] != 0, else 0, for int32 labels (rows of labels_stride bytes); select_host
+ *   holds k bytes; a label outside 0..k-1 gives 0.  mask_bits_dev (nullable): when w % 64 == 0 the mask's bit plane is written as
+ *   well, in the layout of vp_inrange_u8_bits_dev (h * w / 64 words); with any other width it is left alone.  One launch, never
+ *   synchronises.
+ * Refused with VP_ERR_INVALID before anything is launched or written (the message names the reason): a missing pointer, w or h
+ *   outside 1..4096, cn outside 1..4, k outside 1..256 or above w h, both or neither of the initialisers, an initial centre that is
+ *   not finite, a seed index outside 0..N-1, max_iter outside 1..100, eps negative or not finite, a stride below the row, a label
+ *   stride below the row or not a multiple of 4, labels that are not 4-byte aligned, a bit plane that is not 8-byte aligned, labels
+ *   that overlap the source (a mask that overlaps the labels). */
+enum { VP_KMEANS_MAX_K = 256, VP_KMEANS_MAX_ITER = 100 };
+int vp_kmeans_u8(vp_ctx* ctx, const uint8_t* src_host, int w, int h, int cn, int k, const float* centers_init, const int32_t* seed_index, int max_iter,
+                 double eps, int32_t* labels_host, void* out_host);
+int vp_kmeans_dev(vp_ctx* ctx, const uint8_t* src_dev, size_t stride, int w, int h, int cn, int k, const float* centers_init, const int32_t* seed_index,
+                  int max_iter, double eps, int32_t* labels_dev, size_t labels_stride, void* out_host);
+int vp_label_select_dev(vp_ctx* ctx, const int32_t* labels_dev, size_t labels_stride, int w, int h, const uint8_t* select_host, int k, uint8_t* mask_dev,
+                        size_t mask_stride, unsigned long long* mask_bits_dev);
+
 /* ---- device memory helpers (so a host program needs no HIP binding of its own) --------- */
 int vp_dev_alloc(vp_ctx* ctx, size_t bytes, void** dev_ptr);
 int vp_dev_free(vp_ctx* ctx, void* dev_ptr);    /* ctx may be NULL (memory that outlived its context) */
