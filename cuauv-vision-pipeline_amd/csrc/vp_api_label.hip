@@ -164,12 +164,8 @@ static int find_contours_impl(vp_ctx* ctx, const uint8_t* src, bool src_on_devic
     const int K = info[0];
     const int64_t P = info[1];
     *n_contours = K;
-    if (K > max_contours) {   // the point total is only known for the contours that were traced
-        *n_points = P > max_points ? P : max_points;
-        return VP_OK;
-    }
-    *n_points = P;
-    if (P > max_points || K == 0) return VP_OK;
+    *n_points = P;            // (the bookkeeping counts the points of every border, those beyond max_contours included)
+    if (K > max_contours || P > max_points || K == 0) return VP_OK;
     std::vector<int32_t> hc(K), ho(K);
     std::vector<uint8_t> hh(K);
     memcpy(hc.data(), hs + 16, (size_t)K * 4);

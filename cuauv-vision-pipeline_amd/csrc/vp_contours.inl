@@ -466,10 +466,13 @@ struct ct_mirror {
 
 // per frame: contour lengths from the leaders, exclusive scan -> offsets, total -> out[f].n_points.  `dist`: per head of the frame,
 // low 32 bits = a leader's distance around its border = the length of its contour.  All NT threads of the block take part.
+// `marks`: per head of the frame (H of them), the rank of the border it leads | CT_UNSEL | CT_NONE - read only when the frame has more
+// borders than max_contours: the total then still counts the points of every returned border (vp.h), those without a row included.
 template <int NT, typename DT>
 __device__ __forceinline__ void ct_offsets_body(int nsel, const u32* __restrict__ starts, const u32* __restrict__ shead,
                                                 const DT* dist, int32_t* __restrict__ counts, uint8_t* __restrict__ is_hole_out,
-                                                int32_t* __restrict__ offsets, ct_frame_out* __restrict__ out, int max_contours, const ct_mirror& M)
+                                                int32_t* __restrict__ offsets, ct_frame_out* __restrict__ out, int max_contours, const ct_mirror& M,
+                                                u32 H, const u32* marks)
 {
     __shared__ u32 wsum[NT / 64];
     __shared__ u32 carry;
@@ -501,6 +504,15 @@ __device__ __forceinline__ void ct_offsets_body(int nsel, const u32* __restrict_
         __syncthreads();
         if (tid == NT - 1) carry += woff + inc;
         __syncthreads();
+    }
+    if (nsel > max_contours) {                            // (the same for every thread of the block)
+        u32 s = 0;
+        for (u32 k = tid; k < H; k += NT) s += marks[k] < CT_UNSEL ? (u32)dist[k] : 0u;
+#pragma unroll
+        for (int d = 32; d >= 1; d >>= 1) s += __shfl_xor(s, d);
+        if (lane == 0) wsum[wv] = s;
+        __syncthreads();
+        if (tid == 0) { u32 t = 0; for (int q = 0; q < NT / 64; q++) t += wsum[q]; carry = t; }
     }
     if (tid == 0) {
         out[f].n_contours = nsel; out[f].n_points = (int32_t)carry;
@@ -700,7 +712,7 @@ __device__ __forceinline__ void ctj_body(const ccl_geom& G, ctj_frame F, u32* ke
         for (u32 k = tid; k < H; k += 1024) F.nd[k] = t[k];
     __threadfence_block();
     __syncthreads();               // the block's own stores to node[] are visible to all its threads from here on
-    ct_offsets_body<1024>((int)nsel, starts, shead, F.nd, counts, is_hole_out, offsets, out, max_contours, M);
+    ct_offsets_body<1024>((int)nsel, starts, shead, F.nd, counts, is_hole_out, offsets, out, max_contours, M, H, F.hr);
 }
 
 struct ctj_args {
@@ -978,7 +990,7 @@ __device__ __forceinline__ void ctj_body_lds(const ctj_args& A, int f, u32 H, un
         const u32 k = tid + 1024u * i;
         if (k < H) nd[k] = v[i];
     }
-    ct_offsets_body<1024>((int)nsel, A.starts, A.shead, tab, A.counts, A.is_hole, A.offsets, A.out, A.max_contours, A.mirror);
+    ct_offsets_body<1024>((int)nsel, A.starts, A.shead, tab, A.counts, A.is_hole, A.offsets, A.out, A.max_contours, A.mirror, H, a1);
 #ifdef VP_CT_PROBE
     CT_STAMP();
     if (tid == 0 && f == 0) {
@@ -1139,12 +1151,28 @@ __global__ __launch_bounds__(1024) void k_ctm_scan(ctj_args A)
         }
         if (c == nchunks - 1 && tid == 1023) {
             if (WHAT == 0) A.aux[f].nsel = excl + v;
-            else {
+            else if (nsel <= (u32)A.max_contours) {
                 A.out[f].n_contours = (int32_t)nsel; A.out[f].n_points = (int32_t)(excl + v);
                 if (A.mirror.info) { A.mirror.info[0] = (int32_t)nsel; A.mirror.info[1] = (int32_t)(excl + v); }
             }
         }
         __syncthreads();
+    }
+    // more borders than max_contours: the total still counts the points of every returned border (vp.h) - one block adds up the
+    // lengths the leaders with a rank carry (see ct_offsets_body)
+    if (WHAT == 1 && nsel > (u32)A.max_contours && blockIdx.x == 0) {
+        u32 s = 0;
+        for (u32 k = tid; k < F.H; k += 1024) s += ctj_gld(F.hr + k) < CT_UNSEL ? (u32)ctj_ld<false>(F.nd, k) : 0u;
+#pragma unroll
+        for (int d = 32; d >= 1; d >>= 1) s += __shfl_xor(s, d);
+        if (lane == 0) s_w[wv] = s;
+        __syncthreads();
+        if (tid == 0) {
+            u32 t = 0;
+            for (int q = 0; q < 16; q++) t += s_w[q];
+            A.out[f].n_contours = (int32_t)nsel; A.out[f].n_points = (int32_t)t;
+            if (A.mirror.info) { A.mirror.info[0] = (int32_t)nsel; A.mirror.info[1] = (int32_t)t; }
+        }
     }
 }
 

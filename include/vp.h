@@ -379,7 +379,7 @@ typedef struct vp_contour_desc {
 } vp_contour_desc;
 
 typedef struct vp_contour_buffers {  /* device pointers (vp_chain_run_contours) / host pointers (.._host) */
-    int32_t* info;         /* (n,2): contours found in the frame; points of the contours that fit */
+    int32_t* info;         /* (n,2): contours found in the frame; points of all of them (both totals whatever the capacities) */
     int32_t* counts;       /* (n,max_contours) points per contour, in discovery order = raster order of
                               the start pixel; cv2 returns the reverse order */
     int32_t* offsets;      /* (n,max_contours) first point of the contour within the frame's point list */
@@ -391,8 +391,8 @@ typedef struct vp_contour_buffers {  /* device pointers (vp_chain_run_contours) 
 } vp_contour_buffers;
 
 /* Contours beyond max_contours are counted in info[.][0] but not traced; a contour whose points
- * would pass max_points is skipped (info[.][1] still counts them), so a caller can repeat with
- * larger capacities.  Enqueues and returns without synchronising. */
+ * would pass max_points is skipped (info[.][1] counts the points of both kinds), so a caller can
+ * repeat with larger capacities.  Enqueues and returns without synchronising. */
 int vp_chain_run_contours(vp_ctx* ctx, const vp_chain_desc* desc, const vp_chain_buffers* dev, const vp_contour_desc* cdesc,
                           const vp_contour_buffers* cdev, int n_frames);
 /* Host buffers: H2D, chain, contours, D2H, synchronised on return. */
