@@ -323,6 +323,14 @@ int vpk_kmeans(vp_ctx* ctx, const uint8_t* d_src, size_t stride, int w, int h, i
                double eps, uint8_t* d_table, int32_t* d_labels, size_t lstride);
 int vpk_label_select(vp_ctx* ctx, const int32_t* d_labels, size_t lstride, int w, int h, const uint8_t* select, int k, uint8_t* d_mask, size_t mstride, u64* d_bits);
 
+// ---- template matching (vp_match.hip; the plan: vp_match_plan.h) ---------------------------------------------------
+// cv2.matchTemplate for arguments vp_match_template_refusal admitted and the plan vp_match_make_plan made of them, enqueued: the
+// template's statistics and packed form, the window sums the method reads, the correlation with its epilogue.  d_ws: P.ws_bytes of
+// workspace, 256-byte aligned; strides in bytes.
+struct vp_match_plan;
+int vpk_match_template(vp_ctx* ctx, const uint8_t* d_src, size_t stride, int w, int h, int cn, const uint8_t* d_templ, size_t tstride, int tw, int th, int method,
+                       const vp_match_plan& P, uint8_t* d_ws, float* d_dst, size_t dstride);
+
 // ---- morphology (vp_morph.hip; the plan: vp_morph_plan.h, with vp_bitstage, vp_bitplan and vp_ww) --------------
 // u8 (non-zero = 1) -> bits; d_flags[0] |= 1 if any byte is neither 0 nor 255
 int vpk_pack_bits(vp_ctx* ctx, const uint8_t* d_src, size_t stride, int w, int h, int n, u64* d_bits,

@@ -55,6 +55,7 @@ DEPTH_32S = 4
 BORDER_CONSTANT, BORDER_REPLICATE, BORDER_REFLECT, BORDER_REFLECT_101, BORDER_ISOLATED = 0, 1, 2, 4, 16
 INTER_NEAREST, INTER_LINEAR = 0, 1
 DIST_L1, DIST_L2, DIST_C = 1, 2, 3
+TM_SQDIFF, TM_SQDIFF_NORMED, TM_CCORR, TM_CCORR_NORMED, TM_CCOEFF, TM_CCOEFF_NORMED = 0, 1, 2, 3, 4, 5
 WARP_INVERSE_MAP = 16
 PROF_KERNELS = 15
 
@@ -278,6 +279,9 @@ _SIGS = {
     "vp_kmeans_dev": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_double, C.c_void_p,
                                 C.c_size_t, C.c_void_p]),
     "vp_label_select_dev": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_size_t, C.c_void_p]),
+    "vp_match_template_u8": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p]),
+    "vp_match_template_dev": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_size_t, C.c_int, C.c_int, C.c_int,
+                                        C.c_void_p, C.c_size_t]),
 }
 
 

@@ -1155,6 +1155,25 @@ def minMaxLoc(src, mask=None):
     return _gather("minMaxLoc", _feature.min_max_loc, _device_source(src)[0], mask)
 
 
+# ---- template matching (libvp vp_match.hip): the exact value of what cv2.matchTemplate approximates, DESIGN.md section 4.27 -------------
+TM_SQDIFF, TM_SQDIFF_NORMED, TM_CCORR, TM_CCORR_NORMED, TM_CCOEFF, TM_CCOEFF_NORMED = 0, 1, 2, 3, 4, 5
+
+
+def matchTemplate(image, templ, method, result=None, mask=None):
+    """cv2.matchTemplate on uint8 images of 1..4 channels in cv2's positional order: the float32 map of (H - h + 1, W - w + 1) scores.
+    The sums under a score are exact integers and the steps after them cv2's in double arithmetic; cv2's own values differ from these
+    by the error of its float32 DFT.  mask=, float32 images, templates above 65536 bytes and a template larger than the image are
+    refused.  A DeviceMat image stays in HBM (vision.utils.feature.match_template)."""
+    if mask is not None:
+        raise error("matchTemplate: mask= is not on the accelerated path")
+    if method not in (TM_SQDIFF, TM_SQDIFF_NORMED, TM_CCORR, TM_CCORR_NORMED, TM_CCOEFF, TM_CCOEFF_NORMED):
+        raise error("matchTemplate: the method must be one of the six TM_* values")
+    image = _source("matchTemplate", image, "only uint8 images are on the accelerated path")
+    if not isinstance(templ, _feature.DeviceCrop):
+        templ = _source("matchTemplate", templ, "only uint8 templates are on the accelerated path")
+    return _into(result, _gather("matchTemplate", _feature.match_template, image, templ, method))
+
+
 # ---- k-means (libvp vp_kmeans.hip): the exact value of what cv2.kmeans approximates, DESIGN.md section 4.26 -------------------------------
 KMEANS_RANDOM_CENTERS, KMEANS_USE_INITIAL_LABELS, KMEANS_PP_CENTERS = 0, 1, 2
 TERM_CRITERIA_COUNT = TERM_CRITERIA_MAX_ITER = 1

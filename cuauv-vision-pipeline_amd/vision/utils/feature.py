@@ -657,6 +657,86 @@ def largest_inscribed_circle(mask):
     return centre, radius
 
 
+# ---- template matching (libvp vp_match.hip) --------------------------------------------------------------------
+TM_SQDIFF, TM_SQDIFF_NORMED, TM_CCORR, TM_CCORR_NORMED, TM_CCOEFF, TM_CCOEFF_NORMED = range(6)
+MATCH_MAX_SIDE, MATCH_MAX_ELEMS = 4096, 65536
+
+
+class DeviceCrop:
+    """The window (x, y, w, h) of a device image, as a template that match_template reads where it lies (no copy is made): a patch of
+    an earlier frame that is still in HBM."""
+    __slots__ = ("mat", "x", "y", "w", "h")
+
+    def __init__(self, mat, x: int, y: int, w: int, h: int):
+        if not isinstance(mat, DeviceMat) or mat.dtype != np.uint8 or mat.ndim not in (2, 3):
+            raise TypeError("a DeviceCrop is a window of a uint8 DeviceMat image")
+        x, y, w, h = int(x), int(y), int(w), int(h)
+        if w < 1 or h < 1 or x < 0 or y < 0 or x + w > mat.shape[1] or y + h > mat.shape[0]:
+            raise ValueError("the window must lie inside the image and hold a pixel")
+        self.mat, self.x, self.y, self.w, self.h = mat, x, y, w, h
+
+    @property
+    def shape(self):
+        return (self.h, self.w) + tuple(self.mat.shape[2:])
+
+
+def _match_template_args(mat, templ, method):
+    """the checked image, template and their sizes; everything match_template refuses is refused here, before a device is needed"""
+    mat, cn = image_source(mat, max_side=MATCH_MAX_SIDE)
+    crop = templ if isinstance(templ, DeviceCrop) else None
+    if crop is None:
+        templ, tcn = image_source(templ, said=("the template must be uint8", "the template must be a non-empty (h, w) or (h, w, c) image", "at most 4 channels"))
+        th, tw = templ.shape[:2]
+    else:
+        tcn = 1 if crop.mat.ndim == 2 else crop.mat.shape[2]
+        th, tw = crop.h, crop.w
+    method = int(method)
+    if method not in range(6):
+        raise ValueError("the method must be one of the six TM_* values")
+    if tcn != cn:
+        raise ValueError("the image and the template must have the same number of channels")
+    h, w = mat.shape[:2]
+    if th > h or tw > w:
+        raise ValueError("the template is larger than the image")
+    if tw * th * cn > MATCH_MAX_ELEMS:
+        raise ValueError("templates above 65536 bytes (tw * th * channels) are outside the accelerated path")
+    return mat, templ, cn, w, h, tw, th, method
+
+
+def match_template(mat, templ, method: int = TM_CCOEFF_NORMED):
+    """cv2.matchTemplate of a uint8 image and a uint8 template of the same 1..4 channels: the float32 map of
+    (h - th + 1, w - tw + 1) scores by one of the six TM_* methods.  The sums under every score are exact integers and the arithmetic
+    after them is cv2's in double, rounded to float32 once; cv2 itself correlates by a float32 DFT and approximates these values.
+    Image sides up to 4096, templates up to 65536 bytes.  numpy in gives numpy out; a DeviceMat image gives a DeviceMat that stays in
+    HBM (libvp vp_match_template_*).  A numpy template is uploaded; a DeviceMat or a DeviceCrop template is read where it lies."""
+    mat, templ, cn, w, h, tw, th, method = _match_template_args(mat, templ, method)
+    lib = _vp.lib()
+    if not isinstance(mat, DeviceMat):
+        t = np.ascontiguousarray(to_host_readonly(templ.mat)[templ.y:templ.y + th, templ.x:templ.x + tw] if isinstance(templ, DeviceCrop)
+                                 else to_host_readonly(templ))
+        return run_operator(mat, (h - th + 1, w - tw + 1), np.float32,
+                            lambda ctx, s, d: lib.vp_match_template_u8(ctx.handle, s, w, h, cn, t.ctypes.data, tw, th, method, d), None)
+
+    def on_device(ctx, s, d):
+        if isinstance(templ, DeviceCrop):
+            templ.mat.refresh_device(ctx)
+            tp, ts = templ.mat.dev_ptr + (templ.y * templ.mat.shape[1] + templ.x) * cn, templ.mat.shape[1] * cn
+        else:
+            held = device_image(ctx, templ, 0)               # (an uploaded template lives until the call is queued)
+            tp, ts = held.dev_ptr, tw * cn
+        return lib.vp_match_template_dev(ctx.handle, s, w * cn, w, h, cn, tp, ts, tw, th, method, d, (w - tw + 1) * 4)
+
+    return run_operator(mat, (h - th + 1, w - tw + 1), np.float32, None, on_device)
+
+
+def best_match(mat, templ, method: int = TM_CCOEFF_NORMED):
+    """((x, y), score) of the best match of templ in mat: match_template followed by min_max_loc - the minimum for the two SQDIFF
+    methods, the maximum otherwise, the first pixel in raster order among equal scores.  (x, y) is the top-left corner of the matched
+    window.  With a device image the score map never visits the host: it stays in HBM and 32 bytes come back."""
+    lo, hi, lo_at, hi_at = min_max_loc(match_template(mat, templ, method))
+    return (lo_at, lo) if int(method) in (TM_SQDIFF, TM_SQDIFF_NORMED) else (hi_at, hi)
+
+
 def hough_circles(mat, dp: float, min_dist: float, param1: float = 100, param2: float = 100, min_radius: int = 0, max_radius: int = 0):
     """cv2.HoughCircles(mat, cv2.HOUGH_GRADIENT, dp, min_dist, None, param1, param2, min_radius, max_radius) on the GPU (libvp
     vp_hough_circles_*): (1, N, 3) float32 (x, y, r) in cv2's order, or None when no circle is found.  A device image is read where it

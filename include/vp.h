@@ -833,6 +833,23 @@ int vp_kmeans_dev(vp_ctx* ctx, const uint8_t* src_dev, size_t stride, int w, int
 int vp_label_select_dev(vp_ctx* ctx, const int32_t* labels_dev, size_t labels_stride, int w, int h, const uint8_t* select_host, int k, uint8_t* mask_dev,
                         size_t mask_stride, unsigned long long* mask_bits_dev);
 
+/* ---- template matching: cv2.matchTemplate, the six TM_* methods ------------------------------------------------------------------- *
+ * vp_match_template_u8 / vp_match_template_dev: slides a uint8 template of tw x th pixels over a uint8 image of w x h pixels, both of
+ *   cn = 1..4 channels, and gives the float32 map of (h - th + 1) x (w - tw + 1) scores as DESIGN.md section 4.27 and
+ *   tests/match_template_restate.py state it.  Per result pixel C = sum I T, S2 = sum I^2 and S1_c = sum I per channel, over the window
+ *   and all channels, are exact integers; the steps after them are cv2's (templmatch.cpp common_matchTemplate) in double arithmetic,
+ *   in one fixed order, rounded to float32 once.  cv2 computes C by a float32 DFT: its values approximate these.
+ *   The host form takes packed images, gives a packed result and synchronises.  The device form reads rows of `stride` and
+ *   templ_stride bytes (a template may be a window of another device image), writes rows of dst_stride bytes, enqueues two to four
+ *   launches and never synchronises.
+ * Refused with VP_ERR_INVALID before anything is launched or written (the message names the reason): a missing pointer, w or h outside
+ *   1..4096, cn outside 1..4, a template without pixels or larger than the image, tw * th * cn above 65536, an unknown method, a
+ *   stride below its row, a result stride that is not a multiple of 4, a result that is not 4-byte aligned or overlaps an input. */
+enum { VP_TM_SQDIFF = 0, VP_TM_SQDIFF_NORMED = 1, VP_TM_CCORR = 2, VP_TM_CCORR_NORMED = 3, VP_TM_CCOEFF = 4, VP_TM_CCOEFF_NORMED = 5 };
+int vp_match_template_u8(vp_ctx* ctx, const uint8_t* src_host, int w, int h, int cn, const uint8_t* templ_host, int tw, int th, int method, float* dst_host);
+int vp_match_template_dev(vp_ctx* ctx, const uint8_t* src_dev, size_t stride, int w, int h, int cn, const uint8_t* templ_dev, size_t templ_stride, int tw, int th,
+                          int method, float* dst_dev, size_t dst_stride);
+
 /* ---- device memory helpers (so a host program needs no HIP binding of its own) --------- */
 int vp_dev_alloc(vp_ctx* ctx, size_t bytes, void** dev_ptr);
 int vp_dev_free(vp_ctx* ctx, void* dev_ptr);    /* ctx may be NULL (memory that outlived its context) */
