@@ -331,6 +331,19 @@ struct vp_match_plan;
 int vpk_match_template(vp_ctx* ctx, const uint8_t* d_src, size_t stride, int w, int h, int cn, const uint8_t* d_templ, size_t tstride, int tw, int th, int method,
                        const vp_match_plan& P, uint8_t* d_ws, float* d_dst, size_t dstride);
 
+// ---- colour-histogram tracking (vp_hist.hip; the plan: vp_hist_plan.h) ---------------------------------------------
+// cv2.calcHist, cv2.calcBackProject and cv2.meanShift for arguments the plan header's checks admitted and the plan vp_hist_make_plan
+// made of them; all enqueued.  vpk_calc_hist: zeroes the P.total counters and counts into them; d_mask (rows of mstride bytes) or
+// d_mbits (its bit plane, rows of ceil(w / 64) words) admit pixels, both nullable.  vpk_back_project_fold: float32 histogram ->
+// byte table.  vpk_back_project: the gather from a table of P.total bytes (a plan made for back-projection).  vpk_mean_shift: one
+// block per window of d_windows (n x 4), the whole loop inside; d_out: n x 5 (x, y, w, h, iterations).
+struct vp_hist_plan;
+int vpk_calc_hist(vp_ctx* ctx, const uint8_t* d_src, size_t stride, int w, int h, const vp_hist_plan& P, const uint8_t* d_mask, size_t mstride, const u64* d_mbits,
+                  u32* d_hist);
+int vpk_back_project_fold(vp_ctx* ctx, const float* d_hist, int total, double scale, uint8_t* d_table);
+int vpk_back_project(vp_ctx* ctx, const uint8_t* d_src, size_t stride, int w, int h, const vp_hist_plan& P, const uint8_t* d_table, uint8_t* d_dst, size_t dstride);
+int vpk_mean_shift(vp_ctx* ctx, const uint8_t* d_src, size_t stride, int w, int h, const int32_t* d_windows, int n, int niters, int eps2, int32_t* d_out);
+
 // ---- morphology (vp_morph.hip; the plan: vp_morph_plan.h, with vp_bitstage, vp_bitplan and vp_ww) --------------
 // u8 (non-zero = 1) -> bits; d_flags[0] |= 1 if any byte is neither 0 nor 255
 int vpk_pack_bits(vp_ctx* ctx, const uint8_t* d_src, size_t stride, int w, int h, int n, u64* d_bits,

@@ -1232,6 +1232,78 @@ def kmeans(data, K, bestLabels, criteria, attempts, flags, centers=None):
     return compactness, _into(bestLabels, labels), _into(centers, found)
 
 
+# ---- colour-histogram tracking (libvp vp_hist.hip): calcHist, calcBackProject, meanShift, CamShift, DESIGN.md section 4.28 ----------------
+NORM_INF, NORM_L1, NORM_L2, NORM_MINMAX = 1, 2, 4, 32
+
+
+def _one_image(name, images):
+    if isinstance(images, (np.ndarray,)) or not isinstance(images, (list, tuple)) or len(images) != 1:
+        raise error(f"{name}: a list of exactly one image is on the accelerated path (DESIGN.md section 7)")
+    return _source(name, images[0], "only uint8 images are on the accelerated path")
+
+
+def _vp_call(name, call, *args, **kwargs):
+    """what the mirror refuses, and what libvp's entries refuse behind it, is a cv2.error"""
+    try:
+        return _gather(name, call, *args, **kwargs)
+    except _vp.VpError as e:
+        raise error(f"{name}: {e}") from e
+
+
+def calcHist(images, channels, mask, histSize, ranges, hist=None, accumulate=False):
+    """cv2.calcHist in cv2's positional order: one uint8 image of 1..4 channels in the list, 1..3 dimensions of 1..256 uniform bins,
+    ranges = [low0, high0, ...] with exclusive upper ends; float32 counts, exact.  accumulate, several images, non-uniform ranges and
+    non-uint8 images are refused.  A DeviceMat is counted where it is (vision.utils.color.color_histogram)."""
+    if accumulate:
+        raise error("calcHist: accumulate is not on the accelerated path")
+    image = _one_image("calcHist", images)
+    return _into(hist, _vp_call("calcHist", _color.color_histogram, image, channels, histSize, ranges, mask))
+
+
+def calcBackProject(images, channels, hist, ranges, scale, dst=None):
+    """cv2.calcBackProject in cv2's positional order: one uint8 image in the list and a dense float32 histogram of 1..3 dimensions;
+    uint8 (h, w).  A DeviceMat image gives a DeviceMat that stays in HBM (vision.utils.color.back_project)."""
+    image = _one_image("calcBackProject", images)
+    return _into(dst, _vp_call("calcBackProject", _color.back_project, image, channels, hist, ranges, scale))
+
+
+def _shift_criteria(name, criteria):
+    """(max_iter, eps) as cv2's meanShift reads a TermCriteria: without the COUNT bit 100 iterations, without the EPS bit eps = 1"""
+    try:
+        kind, max_count, eps = int(criteria[0]), int(criteria[1]), float(criteria[2])
+    except (TypeError, ValueError, IndexError):
+        raise error(f"{name}: criteria is (type, maxCount, epsilon)") from None
+    return (max(max_count, 1) if kind & TERM_CRITERIA_COUNT else 100), (max(eps, 0.0) if kind & TERM_CRITERIA_EPS else 1.0)
+
+
+def meanShift(probImage, window, criteria):
+    """cv2.meanShift on a uint8 single-channel image: (iterations, window), the loop on the GPU (vision.utils.feature.mean_shift).  A
+    window of non-positive size, or with nothing of it inside the image, is refused."""
+    max_iter, eps = _shift_criteria("meanShift", criteria)
+    return _vp_call("meanShift", _feature.mean_shift, _source("meanShift", probImage, "only uint8 images are on the accelerated path"), window, max_iter, eps)
+
+
+def CamShift(probImage, window, criteria):
+    """cv2.CamShift on a uint8 single-channel image: (((cx, cy), (w, h), angle), window).  The window search and the moments are
+    exact integers from the GPU; the box is cv2's double arithmetic on them, through the host's libm."""
+    max_iter, eps = _shift_criteria("CamShift", criteria)
+    return _vp_call("CamShift", _feature.cam_shift, _source("CamShift", probImage, "only uint8 images are on the accelerated path"), window, max_iter, eps)
+
+
+def normalize(src, dst=None, alpha=1.0, beta=0.0, norm_type=NORM_L2, dtype=-1, mask=None):
+    """cv2.normalize for NORM_MINMAX on float32 host arrays - what a histogram goes through before calcBackProject: the stretch onto
+    [min(alpha, beta), max(alpha, beta)] in double, rounded once (vision.utils.color.normalize_hist; cv2 takes the same steps in
+    float32)."""
+    if norm_type != NORM_MINMAX:
+        raise error("normalize: only NORM_MINMAX is on the accelerated path")
+    if mask is not None or dtype not in (-1, CV_32F):
+        raise error("normalize: mask= and a dtype other than CV_32F are not on the accelerated path")
+    if not isinstance(src, np.ndarray) or src.dtype != np.float32:
+        raise error("normalize: only float32 host arrays are on the accelerated path")
+    lo, hi = min(float(alpha), float(beta)), max(float(alpha), float(beta))
+    return _into(dst, _gather("normalize", _color.normalize_hist, src, hi, lo))
+
+
 def adaptiveThreshold(src, maxValue, adaptiveMethod, thresholdType, blockSize, C, dst=None):
     """cv2.adaptiveThreshold (utils/color.py:220-292) in cv2's positional order on CV_8UC1 images.  ADAPTIVE_THRESH_MEAN_C: the mean
     path (libvp vp_adaptive_threshold_mean_*, block sizes 3..151); ADAPTIVE_THRESH_GAUSSIAN_C: the exact Gaussian-weighted mean

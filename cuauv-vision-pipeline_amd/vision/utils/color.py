@@ -658,3 +658,190 @@ def white_balance_bgr_blur(bgr_img, kernel_size):
         from vision.cv2_facade import error
         raise error(f"white_balance_bgr_blur: kernel size {k} is not positive")
     return _white_balance(bgr_img, k)
+
+
+# ---- colour-histogram tracking (libvp vp_hist.hip) ---------------------------------------------------------------
+HIST_MAX_SIDE, HIST_MAX_DIMS, HIST_MAX_SIZE = 4096, 3, 256
+
+
+class _HistDesc:
+    """The checked description of a histogram: dims, channel indices, sizes and (low, high) ranges as the arrays libvp reads.
+    Everything the C entries refuse about a description is refused here, before a device is needed."""
+    __slots__ = ("dims", "channels", "sizes", "ranges", "shape")
+
+    def __init__(self, cn, channels, hist_size, ranges):
+        try:
+            channels = [int(c) for c in np.asarray(channels).reshape(-1)]
+            sizes = [int(s) for s in np.asarray(hist_size).reshape(-1)]
+            flat = [float(r) for r in np.asarray(ranges, dtype=np.float64).reshape(-1)]
+        except (TypeError, ValueError):
+            raise ValueError("channels, sizes and ranges must be lists of numbers; non-uniform ranges are outside the accelerated path") from None
+        dims = len(channels)
+        if not 1 <= dims <= HIST_MAX_DIMS:
+            raise ValueError("a histogram has 1 to 3 dimensions")
+        if len(sizes) != dims:
+            raise ValueError("one histogram size per dimension")
+        if len(flat) != 2 * dims:
+            raise ValueError("one (low, high) pair per dimension: non-uniform ranges are outside the accelerated path")
+        if any(c < 0 or c >= cn for c in channels):
+            raise ValueError("a channel index is outside the image's channels")
+        if any(not 1 <= s <= HIST_MAX_SIZE for s in sizes):
+            raise ValueError("a histogram size must be 1 to 256")
+        if any(not (np.isfinite(flat[2 * d]) and np.isfinite(flat[2 * d + 1]) and flat[2 * d] < flat[2 * d + 1]) for d in range(dims)):
+            raise ValueError("a range needs finite ends with low < high")
+        self.dims, self.shape = dims, tuple(sizes)
+        self.channels, self.sizes, self.ranges = np.array(channels, np.int32), np.array(sizes, np.int32), np.array(flat, np.float64)
+
+    def args(self):
+        return self.dims, self.channels.ctypes.data, self.sizes.ctypes.data, self.ranges.ctypes.data
+
+
+def _hist_source(mat):
+    """(image or DeviceCrop, channels, w, h)"""
+    from vision.utils.feature import DeviceCrop
+    if isinstance(mat, DeviceCrop):
+        return mat, (1 if mat.mat.ndim == 2 else mat.mat.shape[2]), mat.w, mat.h
+    mat, cn = image_source(mat, max_side=HIST_MAX_SIDE)
+    return mat, cn, mat.shape[1], mat.shape[0]
+
+
+def _hist_mask(mask, w, h):
+    if mask is None:
+        return None
+    mask, _ = image_source(mask, single="the mask must be a single-channel image",
+                           said=("the mask must be uint8", "the mask must be a non-empty (h, w) image", None))
+    if tuple(mask.shape) != (h, w):
+        raise ValueError("the mask must have the size of the image")
+    return mask
+
+
+def color_histogram(mat, channels, hist_size, ranges, mask=None) -> np.ndarray:
+    """cv2.calcHist of one uint8 image of 1..4 channels: the float32 histogram of 1..3 dimensions over the
+    given channel indices, `hist_size` uniform bins per dimension over ranges = [low0, high0, low1, high1, ...], the upper ends
+    exclusive.  mask (uint8, the image's size): only its non-zero pixels are counted.  The counts are exact integers, counted on the
+    GPU (libvp vp_calc_hist_*): a DeviceMat - or a DeviceCrop, the window of one - is read where it is, a device mask that still
+    carries its bit plane through that, and only the counts come back."""
+    from vision.utils.feature import DeviceCrop
+    mat, cn, w, h = _hist_source(mat)
+    desc = _HistDesc(cn, channels, hist_size, ranges)
+    mask = _hist_mask(mask, w, h)
+    ctx = _vp.default_context()
+    lib = _vp.lib()
+    if not isinstance(mat, (DeviceMat, DeviceCrop)):
+        mat = np.ascontiguousarray(mat)
+        out = np.empty(desc.shape, np.float32)
+        m = None if mask is None else np.ascontiguousarray(to_host(mask) if isinstance(mask, DeviceMat) else mask)
+        _vp.check(lib.vp_calc_hist_u8(ctx.handle, mat.ctypes.data, w, h, cn, *desc.args(), None if m is None else m.ctypes.data, w if m is not None else 0,
+                                      h if m is not None else 0, out.ctypes.data), ctx.handle)
+        return out
+    if isinstance(mat, DeviceCrop):
+        mat.mat.refresh_device(ctx)
+        full_w = mat.mat.shape[1]
+        ptr, stride = mat.mat.dev_ptr + (mat.y * full_w + mat.x) * cn, full_w * cn
+    else:
+        mat.refresh_device(ctx)
+        ptr, stride = mat.dev_ptr, w * cn
+    mp = bp = None
+    if mask is not None:
+        mask = device_image(ctx, mask, 1)
+        mp = mask.dev_ptr
+        if mask.binary:
+            bits = mask.bit_plane(ctx)
+            bp = bits.ptr if (bits is not None and mask._dev_ok and mask._ctx is ctx) else None
+    counts = np.empty(desc.shape, np.uint32)
+    _vp.check(lib.vp_calc_hist_dev(ctx.handle, ptr, stride, w, h, cn, *desc.args(), mp, w, w if mask is not None else 0, h if mask is not None else 0, bp,
+                                   None, counts.ctypes.data), ctx.handle)
+    return counts.astype(np.float32)              # exact: a count is at most 2^24
+
+
+def normalize_hist(hist, top: float = 255.0, low: float = 0.0) -> np.ndarray:
+    """The min-max stretch of a float32 array onto [low, top]: float32(low + (double(v) - min) * ((top - low) / (max - min))), one
+    rounding; all `low` when max == min.  This library's own arithmetic: cv2.normalize(NORM_MINMAX) computes the same in float32 steps."""
+    hist = np.asarray(hist)
+    if hist.dtype != np.float32 or hist.size == 0 or not np.isfinite(hist).all():
+        raise ValueError("expected a non-empty float32 array of finite values")
+    top, low = float(top), float(low)
+    if not (np.isfinite(top) and np.isfinite(low)):
+        raise ValueError("the ends of the stretch must be finite")
+    v = hist.astype(np.float64)
+    lo, hi = v.min(), v.max()
+    if not hi > lo:
+        return np.full(hist.shape, low, np.float64).astype(np.float32)
+    return (low + (v - lo) * ((top - low) / (hi - lo))).astype(np.float32)
+
+
+def fold_hist(hist, scale: float = 1.0) -> np.ndarray:
+    """The byte table of a back-projection: saturate_u8(round_half_even(double(hist) * scale)) per bin (a NaN product gives 0) - what
+    libvp's fold computes, here for a histogram that is on the host."""
+    with np.errstate(invalid="ignore", over="ignore"):
+        r = np.rint(np.asarray(hist, dtype=np.float32).astype(np.float64) * float(scale))
+    out = np.zeros(r.shape, np.uint8)
+    pos = r > 0
+    out[pos] = np.minimum(r[pos], 255.0).astype(np.uint8)
+    return out
+
+
+def _checked_hist(hist, desc):
+    hist = to_host(hist) if isinstance(hist, DeviceMat) else np.asarray(hist)
+    if hist.dtype != np.float32:
+        raise TypeError("the histogram must be float32")
+    if hist.ndim == desc.dims + 1 and hist.shape[-1] == 1:
+        hist = hist.reshape(hist.shape[:-1])
+    if tuple(hist.shape) != desc.shape:
+        raise ValueError("the histogram's shape must be the histogram sizes (sparse histograms are outside the accelerated path)")
+    return np.ascontiguousarray(hist)
+
+
+def back_project(mat, channels, hist, ranges, scale: float = 1.0):
+    """cv2.calcBackProject of one uint8 image of 1..4 channels: every pixel becomes
+    saturate_u8(round_half_even(double(hist[bin]) * scale)) of its bin in the float32 histogram `hist` (its shape gives the sizes), 0
+    when it falls into none.  numpy in gives numpy out; a DeviceMat gives a DeviceMat that stays in HBM (libvp vp_back_project_*): the
+    histogram is folded into a byte table on the device and the image gathers from it."""
+    mat, cn = image_source(mat, max_side=HIST_MAX_SIDE)
+    h, w = mat.shape[:2]
+    hshape = np.shape(hist)
+    nd = len(np.asarray(channels).reshape(-1))
+    desc = _HistDesc(cn, channels, hshape[:nd], ranges)
+    hist = _checked_hist(hist, desc)
+    scale = float(scale)
+    if not np.isfinite(scale):
+        raise ValueError("the scale must be finite")
+    lib = _vp.lib()
+
+    def on_device(ctx, s, d):
+        held = DeviceMat.from_host(ctx, hist)                # (lives until the call is queued)
+        return lib.vp_back_project_dev(ctx.handle, s, w * cn, w, h, cn, *desc.args(), held.dev_ptr, scale, d, w)
+
+    return run_operator(mat, (h, w), np.uint8, lambda ctx, s, d: lib.vp_back_project_u8(ctx.handle, s, w, h, cn, *desc.args(), hist.ctypes.data, scale, d),
+                        on_device)
+
+
+class HistModel:
+    """A colour model kept in HBM: the folded byte table of a histogram with its channels and ranges, as RemapTable holds a
+    calibration's maps.  `apply` back-projects a frame with one launch and no synchronisation (libvp vp_back_project_table_dev)."""
+    __slots__ = ("channels", "hist_size", "ranges", "hist", "table")
+
+    def __init__(self, hist, channels, ranges, scale: float = 1.0):
+        nd = len(np.asarray(channels).reshape(-1))
+        desc = _HistDesc(4, channels, np.shape(hist)[:nd], ranges)      # (the channel indices are checked against each frame)
+        self.hist = _checked_hist(hist, desc)
+        self.channels, self.hist_size, self.ranges = tuple(int(c) for c in desc.channels), desc.shape, tuple(float(r) for r in desc.ranges)
+        self.table = DeviceMat.from_host(_vp.default_context(), fold_hist(self.hist, scale))
+
+    @classmethod
+    def from_patch(cls, mat, channels, hist_size, ranges, mask=None, top: float = 255.0):
+        """The model of a sample patch - an image, or a DeviceCrop of a frame in HBM: its histogram, stretched onto [0, top]
+        (normalize_hist)."""
+        return cls(normalize_hist(color_histogram(mat, channels, hist_size, ranges, mask), top), channels, ranges)
+
+    def apply(self, mat):
+        """The back-projection of the model onto a frame: a DeviceMat gives a DeviceMat, numpy gives numpy."""
+        mat, cn = image_source(mat, max_side=HIST_MAX_SIDE)
+        desc = _HistDesc(cn, self.channels, self.hist_size, self.ranges)
+        h, w = mat.shape[:2]
+        ctx = _vp.default_context()
+        src = device_image(ctx, mat, 0)
+        self.table.refresh_device(ctx)
+        out = DeviceMat(ctx, (h, w), np.uint8)
+        _vp.check(_vp.lib().vp_back_project_table_dev(ctx.handle, src.dev_ptr, w * cn, w, h, cn, *desc.args(), self.table.dev_ptr, out.dev_ptr, w), ctx.handle)
+        return out if isinstance(mat, DeviceMat) else out.host_copy()

@@ -737,6 +737,118 @@ def best_match(mat, templ, method: int = TM_CCOEFF_NORMED):
     return (lo_at, lo) if int(method) in (TM_SQDIFF, TM_SQDIFF_NORMED) else (hi_at, hi)
 
 
+# ---- mean shift and CamShift (libvp vp_hist.hip) ----------------------------------------------------------------
+MEAN_SHIFT_MAX_SIDE, MEAN_SHIFT_MAX_WINDOWS, MEAN_SHIFT_MAX_ITER = 4096, 4096, 100000
+CAM_SHIFT_TOLERANCE = 10
+
+
+def _clip_window(win, cols, rows):
+    """(x, y, w, h) cut to the image, or None when nothing is left"""
+    x, y, w, h = win
+    x0, y0, x1, y1 = max(x, 0), max(y, 0), min(x + w, cols), min(y + h, rows)
+    return (x0, y0, x1 - x0, y1 - y0) if x1 > x0 and y1 > y0 else None
+
+
+def _mean_shift_args(prob, windows, max_iter, eps):
+    """the checked image and windows; everything vp_mean_shift_dev refuses is refused here, before a device is needed"""
+    prob, _ = image_source(prob, single="mean shift takes a single-channel image", max_side=MEAN_SHIFT_MAX_SIDE)
+    rows, cols = prob.shape
+    try:
+        wins = np.array([[int(v) for v in win] for win in windows], np.int64).reshape(-1, 4)
+    except (TypeError, ValueError):
+        raise ValueError("a window is four integers (x, y, w, h)") from None
+    if not 1 <= len(wins) <= MEAN_SHIFT_MAX_WINDOWS:
+        raise ValueError("1 to 4096 windows")
+    if np.abs(wins).max() >= 2 ** 31:
+        raise ValueError("a window is four 32-bit integers")
+    for win in wins:
+        if win[2] <= 0 or win[3] <= 0:
+            raise ValueError("a window has a non-positive size")
+        if _clip_window(tuple(int(v) for v in win), cols, rows) is None:
+            raise ValueError("a window is empty inside the image")
+    max_iter, eps = int(max_iter), float(eps)
+    if max_iter > MEAN_SHIFT_MAX_ITER:
+        raise ValueError("more than 100000 iterations are outside the accelerated path")
+    return prob, np.ascontiguousarray(wins.astype(np.int32)), max_iter, (eps if eps == eps else 0.0)
+
+
+def mean_shift_many(prob, windows, max_iter: int = 10, eps: float = 1.0):
+    """cv2.meanShift of a batch of windows (x, y, w, h) over one uint8 single-channel image, in one launch with one block per window
+    and the whole loop on the GPU (libvp vp_mean_shift_dev): a list of (iterations, window).  A DeviceMat is
+    read where it is; only five integers per window come back.  max_iter below 1 counts as 1; eps below 0 as 0."""
+    prob, wins, max_iter, eps = _mean_shift_args(prob, windows, max_iter, eps)
+    rows, cols = prob.shape
+    ctx = _vp.default_context()
+    src = device_image(ctx, prob, 1)
+    out = np.empty((len(wins), 5), np.int32)
+    _vp.check(_vp.lib().vp_mean_shift_dev(ctx.handle, src.dev_ptr, cols, cols, rows, wins.ctypes.data, len(wins), max_iter, eps, None, out.ctypes.data), ctx.handle)
+    return [(int(r[4]), (int(r[0]), int(r[1]), int(r[2]), int(r[3]))) for r in out]
+
+
+def mean_shift(prob, window, max_iter: int = 10, eps: float = 1.0):
+    """cv2.meanShift(prob, window, (COUNT | EPS, max_iter, eps)): (iterations, window) - mean_shift_many of one window."""
+    return mean_shift_many(prob, [window], max_iter, eps)[0]
+
+
+def _round_half_even(v: float) -> int:
+    return int(np.rint(v))
+
+
+def cam_shift_box(sums, window, cols: int, rows: int):
+    """The finishing arithmetic of cv2.CamShift, in double on the host, from the ten exact raster sums of the grown window
+    (x, y, w, h): (((cx, cy), (w, h), angle), window).  atan2, cos, sin and sqrt are the host's libm."""
+    m00, m10, m01, m20, m11, m02 = (float(int(s)) for s in sums[:6])
+    x, y, w, h = window
+    if abs(m00) < 2.220446049250313e-16:
+        return ((0.0, 0.0), (0.0, 0.0), 0.0), window
+    inv_m00 = 1.0 / m00
+    mx, my = m10 * inv_m00, m01 * inv_m00
+    mu20, mu11, mu02 = m20 - m10 * mx, m11 - m10 * my, m02 - m01 * my
+    xc, yc = _round_half_even(m10 * inv_m00 + x), _round_half_even(m01 * inv_m00 + y)
+    a, b, c = mu20 * inv_m00, mu11 * inv_m00, mu02 * inv_m00
+    square = math.sqrt(4 * b * b + (a - c) * (a - c))
+    theta = math.atan2(2 * b, a - c + square)
+    cs, sn = math.cos(theta), math.sin(theta)
+    rotate_a = max(0.0, cs * cs * mu20 + 2 * cs * sn * mu11 + sn * sn * mu02)
+    rotate_c = max(0.0, sn * sn * mu20 - 2 * cs * sn * mu11 + cs * cs * mu02)
+    length, width = math.sqrt(rotate_a * inv_m00) * 4, math.sqrt(rotate_c * inv_m00) * 4
+    if length < width:
+        length, width = width, length
+        cs, sn = sn, cs
+        theta = math.pi * 0.5 - theta
+    t0 = max(_round_half_even(abs(length * cs)), _round_half_even(abs(width * sn))) + 2
+    w = min(t0, (cols - xc) * 2)
+    t0 = max(_round_half_even(abs(length * sn)), _round_half_even(abs(width * cs))) + 2
+    h = min(t0, (rows - yc) * 2)
+    x, y = max(0, xc - int(w / 2)), max(0, yc - int(h / 2))
+    w, h = min(cols - x, w), min(rows - y, h)
+    angle = np.float32((math.pi * 0.5 + theta) * 180.0 / math.pi)
+    while angle < 0:
+        angle = np.float32(angle + np.float32(360))
+    while angle >= 360:
+        angle = np.float32(angle - np.float32(360))
+    if angle >= 180:
+        angle = np.float32(angle - np.float32(180))
+    centre = (float(np.float32(x) + np.float32(w) * np.float32(0.5)), float(np.float32(y) + np.float32(h) * np.float32(0.5)))
+    return (centre, (float(np.float32(width)), float(np.float32(length))), float(angle)), (x, y, w, h)
+
+
+def cam_shift(prob, window, max_iter: int = 10, eps: float = 1.0):
+    """cv2.CamShift(prob, window, (COUNT | EPS, max_iter, eps)): (((cx, cy), (w, h), angle), window).  mean_shift, then the exact
+    raster sums of the found window grown by 10 pixels on every side (libvp vp_moments_dev on that part of the device image) - the
+    integers come from the GPU; the double arithmetic after them (cam_shift_box) runs on the host and goes through its libm."""
+    prob = _mean_shift_args(prob, [window], max_iter, eps)[0]
+    rows, cols = prob.shape
+    ctx = _vp.default_context()
+    src = device_image(ctx, prob, 1)
+    _, (x, y, w, h) = mean_shift(src, window, max_iter, eps)
+    x, y = max(x - CAM_SHIFT_TOLERANCE, 0), max(y - CAM_SHIFT_TOLERANCE, 0)
+    w, h = min(w + 2 * CAM_SHIFT_TOLERANCE, cols - x), min(h + 2 * CAM_SHIFT_TOLERANCE, rows - y)
+    sums = np.zeros(10, np.uint64)
+    _vp.check(_vp.lib().vp_moments_dev(ctx.handle, src.dev_ptr + y * cols + x, cols, w, h, 0, None, sums.ctypes.data), ctx.handle)
+    return cam_shift_box(sums, (x, y, w, h), cols, rows)
+
+
 def hough_circles(mat, dp: float, min_dist: float, param1: float = 100, param2: float = 100, min_radius: int = 0, max_radius: int = 0):
     """cv2.HoughCircles(mat, cv2.HOUGH_GRADIENT, dp, min_dist, None, param1, param2, min_radius, max_radius) on the GPU (libvp
     vp_hough_circles_*): (1, N, 3) float32 (x, y, r) in cv2's order, or None when no circle is found.  A device image is read where it

@@ -850,6 +850,46 @@ int vp_match_template_u8(vp_ctx* ctx, const uint8_t* src_host, int w, int h, int
 int vp_match_template_dev(vp_ctx* ctx, const uint8_t* src_dev, size_t stride, int w, int h, int cn, const uint8_t* templ_dev, size_t templ_stride, int tw, int th,
                           int method, float* dst_dev, size_t dst_stride);
 
+/* ---- colour-histogram tracking: cv2.calcHist, cv2.calcBackProject, cv2.meanShift -------------------------------------------------- *
+ * DESIGN.md section 4.28 and tests/hist_restate.py state all of it.  An image is uint8 of cn = 1..4 interleaved channels, w, h <= 4096.
+ * A histogram is described by dims = 1..3, a channel index per dimension, hist_size[d] = 1..256 bins and ranges[2 d], ranges[2 d + 1] =
+ * (low, high) per dimension - host arrays.  As in cv2's calcHistLookupTables_8u, a = hist_size / (high - low) and b = -a * low in
+ * double, byte value j falls into bin floor(j * a + b), and a pixel with a bin outside [0, hist_size) in any dimension takes no part:
+ * the upper end of a range is exclusive.  The first dimension is the slowest, like a C array.
+ * vp_calc_hist_u8 / vp_calc_hist_dev: the exact count per bin.  mask (nullable, mask_w x mask_h bytes): only its non-zero pixels are
+ *   counted; mask_bits_dev (nullable) is the mask's bit plane in the layout of vp_inrange_u8_bits_dev (rows of ceil(w / 64) words),
+ *   read instead of its bytes - its bits past w are not looked at.  The host form takes packed arrays, gives float32 counts (exact: an
+ *   image has at most 2^24 pixels) and synchronises.  The device form leaves uint32 counts in counts_dev and / or counts_host (at least
+ *   one of them); it synchronises only to fill counts_host.
+ * vp_back_project_u8 / vp_back_project_dev / vp_back_project_table_dev: dst (uint8, one channel) = saturate_u8(round_half_even(
+ *   double(hist[bin]) * scale)) for a pixel's bin, 0 for a pixel without one (a NaN product gives 0).  The result depends on the bin
+ *   alone, so the float32 histogram is first folded into a table of one byte per bin - on the host by the host form, by a small kernel
+ *   from hist_dev by the device form - and the image kernel gathers from it.  The _table form takes such a table (device memory, one
+ *   byte per bin): one launch per frame.  The host form synchronises; the device forms enqueue and never synchronise.
+ * vp_mean_shift_dev: cv2.meanShift of n windows (x, y, w, h; host int32) over a single-channel uint8 device image, one block per
+ *   window with the whole loop inside it: W = window cut to the image; up to max(max_iter, 1) times: the sums m00, m10, m01 of the
+ *   current window as exact integers, stop when m00 == 0, move by round_half_even(m10 / m00 - W.w / 2) and the same in y, clamped into
+ *   the image, stop when the squared step is below round_half_even(max(eps, 0)^2).  The result is n rows (x, y, w, h, iterations) of
+ *   int32 in out_dev and / or out_host (at least one of them); the call is enqueued and synchronises only to fill out_host.
+ * Refused with VP_ERR_INVALID before anything is launched or written (the message names the reason): a missing pointer, w or h outside
+ *   1..4096, cn outside 1..4, a stride below its row, dims outside 1..3, a channel index outside the image's channels, a hist_size
+ *   outside 1..256, a range without finite ends low < high, a mask of another size than the image, a bit plane that is not 8-byte
+ *   aligned, a scale that is not finite, counters or a histogram that are not 4-byte aligned, a result that overlaps an input, n outside
+ *   1..4096, a window of non-positive size or with nothing of it inside the image.  max_iter above 100000: VP_ERR_UNSUPPORTED. */
+int vp_calc_hist_u8(vp_ctx* ctx, const uint8_t* src_host, int w, int h, int cn, int dims, const int32_t* channels, const int32_t* hist_size, const double* ranges,
+                    const uint8_t* mask_host, int mask_w, int mask_h, float* hist_host);
+int vp_calc_hist_dev(vp_ctx* ctx, const uint8_t* src_dev, size_t stride, int w, int h, int cn, int dims, const int32_t* channels, const int32_t* hist_size,
+                     const double* ranges, const uint8_t* mask_dev, size_t mask_stride, int mask_w, int mask_h, const unsigned long long* mask_bits_dev,
+                     uint32_t* counts_dev, uint32_t* counts_host);
+int vp_back_project_u8(vp_ctx* ctx, const uint8_t* src_host, int w, int h, int cn, int dims, const int32_t* channels, const int32_t* hist_size, const double* ranges,
+                       const float* hist_host, double scale, uint8_t* dst_host);
+int vp_back_project_dev(vp_ctx* ctx, const uint8_t* src_dev, size_t stride, int w, int h, int cn, int dims, const int32_t* channels, const int32_t* hist_size,
+                        const double* ranges, const float* hist_dev, double scale, uint8_t* dst_dev, size_t dst_stride);
+int vp_back_project_table_dev(vp_ctx* ctx, const uint8_t* src_dev, size_t stride, int w, int h, int cn, int dims, const int32_t* channels, const int32_t* hist_size,
+                              const double* ranges, const uint8_t* table_dev, uint8_t* dst_dev, size_t dst_stride);
+int vp_mean_shift_dev(vp_ctx* ctx, const uint8_t* src_dev, size_t stride, int w, int h, const int32_t* windows_host, int n, int max_iter, double eps,
+                      int32_t* out_dev, int32_t* out_host);
+
 /* ---- device memory helpers (so a host program needs no HIP binding of its own) --------- */
 int vp_dev_alloc(vp_ctx* ctx, size_t bytes, void** dev_ptr);
 int vp_dev_free(vp_ctx* ctx, void* dev_ptr);    /* ctx may be NULL (memory that outlived its context) */
