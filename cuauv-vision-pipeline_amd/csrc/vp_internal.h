@@ -344,6 +344,15 @@ int vpk_back_project_fold(vp_ctx* ctx, const float* d_hist, int total, double sc
 int vpk_back_project(vp_ctx* ctx, const uint8_t* d_src, size_t stride, int w, int h, const vp_hist_plan& P, const uint8_t* d_table, uint8_t* d_dst, size_t dstride);
 int vpk_mean_shift(vp_ctx* ctx, const uint8_t* d_src, size_t stride, int w, int h, const int32_t* d_windows, int n, int niters, int eps2, int32_t* d_out);
 
+// ---- sparse optical flow (vp_flow.hip; the plan: vp_flow_plan.h) ----------------------------------------------------
+// cv2.calcOpticalFlowPyrLK for arguments the plan header's checks admitted: one launch, one wave per point, all P.levels levels of L
+// inside it; enqueued.  d_pts: n (x, y) float32; d_guess (nullable): n starting positions; max_count and eps2 already clamped;
+// d_out: n x 4 words (x, y, err as float32 bits, status).
+struct vp_lk_levels;
+struct vp_lk_plan;
+int vpk_lk_flow(vp_ctx* ctx, const vp_lk_levels& L, const vp_lk_plan& P, int win_w, int win_h, int max_count, double eps2, int flags, double min_eig,
+                const float* d_pts, const float* d_guess, u32* d_out);
+
 // ---- morphology (vp_morph.hip; the plan: vp_morph_plan.h, with vp_bitstage, vp_bitplan and vp_ww) --------------
 // u8 (non-zero = 1) -> bits; d_flags[0] |= 1 if any byte is neither 0 nor 255
 int vpk_pack_bits(vp_ctx* ctx, const uint8_t* d_src, size_t stride, int w, int h, int n, u64* d_bits,

@@ -1290,6 +1290,37 @@ def CamShift(probImage, window, criteria):
     return _vp_call("CamShift", _feature.cam_shift, _source("CamShift", probImage, "only uint8 images are on the accelerated path"), window, max_iter, eps)
 
 
+OPTFLOW_USE_INITIAL_FLOW = 4
+OPTFLOW_LK_GET_MIN_EIGENVALS = 8
+
+
+def calcOpticalFlowPyrLK(prevImg, nextImg, prevPts, nextPts, status=None, err=None, winSize=(21, 21), maxLevel=3,
+                         criteria=(TERM_CRITERIA_COUNT + TERM_CRITERIA_EPS, 30, 0.01), flags=0, minEigThreshold=1e-4):
+    """cv2.calcOpticalFlowPyrLK in cv2's positional order on two uint8 single-channel images of one size: (nextPts (N, 1, 2) float32,
+    status (N, 1) uint8, err (N, 1) float32), every level and iteration on the GPU (vision.utils.feature.track_points; DESIGN.md
+    sections 4.29 and 7).  The images may be numpy arrays, DeviceMats or FlowPyramids.  nextPts is read only with
+    OPTFLOW_USE_INITIAL_FLOW.  Without the COUNT bit the criteria mean 30 iterations, without the EPS bit 0.01, as in cv2."""
+    try:
+        kind, max_count, eps = int(criteria[0]), int(criteria[1]), float(criteria[2])
+    except (TypeError, ValueError, IndexError):
+        raise error("calcOpticalFlowPyrLK: criteria is (type, maxCount, epsilon)") from None
+    try:
+        flags = int(flags)
+    except (TypeError, ValueError):
+        raise error("calcOpticalFlowPyrLK: flags must be an integer") from None
+    if flags & ~(OPTFLOW_USE_INITIAL_FLOW | OPTFLOW_LK_GET_MIN_EIGENVALS):
+        raise error("calcOpticalFlowPyrLK: unknown flag bits")
+    if flags & OPTFLOW_USE_INITIAL_FLOW and nextPts is None:
+        raise error("calcOpticalFlowPyrLK: OPTFLOW_USE_INITIAL_FLOW needs nextPts")
+    images = [img if isinstance(img, _feature.FlowPyramid) else _source("calcOpticalFlowPyrLK", img, "only uint8 images are on the accelerated path")
+              for img in (prevImg, nextImg)]
+    found, ok, e = _vp_call("calcOpticalFlowPyrLK", _feature.track_points, images[0], images[1], prevPts, nextPts if flags & OPTFLOW_USE_INITIAL_FLOW else None,
+                            winSize, maxLevel, max_count if kind & TERM_CRITERIA_COUNT else 30, eps if kind & TERM_CRITERIA_EPS else 0.01, minEigThreshold,
+                            bool(flags & OPTFLOW_LK_GET_MIN_EIGENVALS))
+    return (_into(nextPts, found), _into(status, ok.astype(np.uint8).reshape(-1, 1)),
+            _into(err, e.reshape(-1, 1)))
+
+
 def normalize(src, dst=None, alpha=1.0, beta=0.0, norm_type=NORM_L2, dtype=-1, mask=None):
     """cv2.normalize for NORM_MINMAX on float32 host arrays - what a histogram goes through before calcBackProject: the stretch onto
     [min(alpha, beta), max(alpha, beta)] in double, rounded once (vision.utils.color.normalize_hist; cv2 takes the same steps in

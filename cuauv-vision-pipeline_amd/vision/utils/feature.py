@@ -849,6 +849,160 @@ def cam_shift(prob, window, max_iter: int = 10, eps: float = 1.0):
     return cam_shift_box(sums, (x, y, w, h), cols, rows)
 
 
+# ---- sparse optical flow (libvp vp_flow.hip) --------------------------------------------------------------------
+OPTFLOW_USE_INITIAL_FLOW, OPTFLOW_LK_GET_MIN_EIGENVALS = 4, 8
+FLOW_MAX_SIDE, FLOW_MAX_POINTS, FLOW_MIN_WIN, FLOW_MAX_WIN, FLOW_MAX_LEVEL = 4096, 1 << 20, 3, 63, 15
+
+
+def _flow_window(win_size):
+    try:
+        ww, wh = (int(v) for v in win_size)
+    except (TypeError, ValueError):
+        raise ValueError("the window is two integers (width, height)") from None
+    if not (FLOW_MIN_WIN <= ww <= FLOW_MAX_WIN and FLOW_MIN_WIN <= wh <= FLOW_MAX_WIN):
+        raise ValueError("a window side must be 3 to 63")
+    return ww, wh
+
+
+def _flow_max_level(max_level):
+    max_level = int(max_level)
+    if not 0 <= max_level <= FLOW_MAX_LEVEL:
+        raise ValueError("maxLevel must be 0 to 15")
+    return max_level
+
+
+def flow_level_count(w: int, h: int, win_size=(21, 21), max_level: int = 3) -> int:
+    """How many pyramid levels track_points uses on a w x h image: level l exists while its width is above the window's and its height
+    above the window's, up to max_level; 0 when the image itself is not larger than the window."""
+    ww, wh = win_size
+    n = 0
+    while n <= max_level and w > ww and h > wh:
+        n, w, h = n + 1, (w + 1) // 2, (h + 1) // 2
+    return n
+
+
+def _flow_source(mat):
+    """the checked level 0 of a pyramid - a numpy image, a DeviceMat or a DeviceCrop - and its (h, w); no device is needed"""
+    if isinstance(mat, DeviceCrop):
+        if mat.mat.ndim != 2:
+            raise ValueError("track_points takes single-channel images")
+        if max(mat.h, mat.w) > FLOW_MAX_SIDE:
+            raise ValueError(f"the source must be at most {FLOW_MAX_SIDE} x {FLOW_MAX_SIDE}")
+        return mat, (mat.h, mat.w)
+    mat, _ = image_source(mat, single="track_points takes single-channel images", max_side=FLOW_MAX_SIDE)
+    return mat, tuple(mat.shape)
+
+
+class FlowPyramid:
+    """The levels of one frame for track_points, kept in HBM: level 0 is the frame (a numpy image is uploaded once, a DeviceMat or a
+    DeviceCrop - a window of a wider device image - is read where it lies), level l + 1 is pyr_down of level l.  Only the levels
+    that exist for `win_size` up to `max_level` are made.  The pyramid of frame t + 1 serves as `next` in one call and as `prev` in
+    the following one: each frame is reduced once."""
+
+    def __init__(self, mat, max_level: int = 3, win_size=(21, 21)):
+        ww, wh = _flow_window(win_size)
+        max_level = _flow_max_level(max_level)
+        mat, (h, w) = _flow_source(mat)
+        crop = mat if isinstance(mat, DeviceCrop) else None
+        count = flow_level_count(w, h, (ww, wh), max_level)
+        if count == 0:
+            raise ValueError("the image must be larger than the window")
+        ctx = _vp.default_context()
+        lib = _vp.lib()
+        if crop is not None:
+            crop.mat.refresh_device(ctx)
+            held, ptr, stride = crop.mat, crop.mat.dev_ptr + crop.y * crop.mat.shape[1] + crop.x, crop.mat.shape[1]
+        else:
+            held = device_image(ctx, mat, 1)
+            ptr, stride = held.dev_ptr, w
+        self.ctx, self.shape, self.win_size, self.max_level = ctx, (h, w), (ww, wh), max_level
+        self.levels = [(ptr, stride, w, h)]           # (device pointer, bytes between rows, columns, rows)
+        self._held = [held]
+        for _ in range(count - 1):
+            ptr, stride, w, h = self.levels[-1]
+            down = DeviceMat(ctx, ((h + 1) // 2, (w + 1) // 2))
+            _vp.check(lib.vp_pyr_down_dev(ctx.handle, ptr, stride, w, h, 1, _vp.BORDER_REFLECT_101, down.dev_ptr), ctx.handle)
+            self.levels.append((down.dev_ptr, (w + 1) // 2, (w + 1) // 2, (h + 1) // 2))
+            self._held.append(down)
+
+    def __len__(self):
+        return len(self.levels)
+
+
+def _flow_points(pts, what):
+    try:
+        pts = np.asarray(pts, np.float32)
+    except (TypeError, ValueError):
+        raise ValueError(f"{what} must be float32 (x, y) pairs") from None
+    if pts.size % 2 or (pts.ndim and pts.shape[-1] != 2 and pts.size):
+        raise ValueError(f"{what} must be float32 (x, y) pairs")
+    return np.ascontiguousarray(pts.reshape(-1, 2))
+
+
+def _flow_launch(P, Q, count, pts, guess, win, max_level, max_count, eps, flags, min_eig):
+    """one launch over `count` levels of the pyramids P (first image) and Q (second): (positions (n, 2), status (n,) bool, err (n,))"""
+    ctx = P.ctx
+    n = len(pts)
+    ptrs = lambda pyr: ((_vp.C.c_void_p * count)(*[lv[0] for lv in pyr.levels[:count]]), (_vp.C.c_size_t * count)(*[lv[1] for lv in pyr.levels[:count]]))
+    (pp, ps), (qp, qs) = ptrs(P), ptrs(Q)
+    out = np.empty((n, 4), np.uint32)
+    h, w = P.shape
+    _vp.check(_vp.lib().vp_lk_flow_dev(ctx.handle, pp, ps, qp, qs, count, w, h, pts.ctypes.data, None if guess is None else guess.ctypes.data, n, win[0], win[1],
+                                       max_level, max_count, eps, flags, min_eig, None, out.ctypes.data), ctx.handle)
+    return out[:, :2].copy().view(np.float32), out[:, 3] != 0, out[:, 2].copy().view(np.float32)
+
+
+def track_points(prev, next, pts, next_pts=None, win_size=(21, 21), max_level: int = 3, max_count: int = 30, eps: float = 0.01, min_eig_threshold: float = 1e-4,
+                 min_eigenvals: bool = False, back_check=None):
+    """cv2.calcOpticalFlowPyrLK: follows the points `pts` of the uint8 single-channel image `prev` into `next` by pyramidal
+    Lucas-Kanade (libvp vp_lk_flow_dev, one launch with one wave per point and every level inside it).
+    Returns (next_pts (N, 1, 2) float32, status (N,) bool, err (N,) float32) as numpy.  The window sums are exact integers and what
+    follows them is cv2's sequence in double in one fixed order: the exact value of what cv2's float32 code approximates.
+    prev and next are numpy images, DeviceMats, DeviceCrops or FlowPyramids; a FlowPyramid is used as it is, so that a frame is
+    reduced once however many calls it takes part in.  next_pts: starting positions (cv2's OPTFLOW_USE_INITIAL_FLOW).  max_count is
+    clamped to 0..100 and eps to 0..10, as cv2 clamps its TermCriteria.  err is the mean absolute difference of the window at the
+    final position (0 for a lost point), or with min_eigenvals the minimum eigenvalue at level 0.  back_check=t tracks the results
+    back into `prev` (a second launch over the same pyramids) and clears the status of points that return more than t pixels from
+    their start, or not at all.  A point with a coordinate that is not finite or beyond +-2^24 is lost and comes back unchanged."""
+    win = _flow_window(win_size)
+    max_level = _flow_max_level(max_level)
+    max_count, eps, min_eig = int(max_count), float(eps), float(min_eig_threshold)
+    if not (math.isfinite(eps) and math.isfinite(min_eig)):
+        raise ValueError("epsilon and minEigThreshold must be finite")
+    if back_check is not None:
+        back_check = float(back_check)
+        if not back_check >= 0:
+            raise ValueError("back_check must be at least 0")
+    pts = _flow_points(pts, "the points")
+    guess = None
+    if next_pts is not None:
+        guess = _flow_points(next_pts, "the initial positions")
+        if guess.shape != pts.shape:
+            raise ValueError("as many initial positions as points")
+    if len(pts) > FLOW_MAX_POINTS:
+        raise ValueError("more than 1048576 points are outside the accelerated path")
+    shapes = [x.shape if isinstance(x, FlowPyramid) else _flow_source(x)[1] for x in (prev, next)]
+    if shapes[0] != shapes[1]:
+        raise ValueError("the two images must have the same size")
+    count = flow_level_count(shapes[0][1], shapes[0][0], win, max_level)
+    if count == 0:
+        raise ValueError("the image must be larger than the window")
+    P = prev if isinstance(prev, FlowPyramid) else FlowPyramid(prev, max_level, win)       # (everything above is refused before a device is needed)
+    Q = next if isinstance(next, FlowPyramid) else FlowPyramid(next, max_level, win)
+    if min(len(P), len(Q)) < count or P.ctx is not Q.ctx:
+        raise ValueError("a FlowPyramid holds fewer levels than this call uses (or lives on another context): make it with this window and maxLevel")
+    if len(pts) == 0:
+        return np.empty((0, 1, 2), np.float32), np.empty(0, bool), np.empty(0, np.float32)
+    flags = (OPTFLOW_USE_INITIAL_FLOW if guess is not None else 0) | (OPTFLOW_LK_GET_MIN_EIGENVALS if min_eigenvals else 0)
+    found, status, err = _flow_launch(P, Q, count, pts, guess, win, max_level, max_count, eps, flags, min_eig)
+    if back_check is not None:
+        back, back_ok, _ = _flow_launch(Q, P, count, np.ascontiguousarray(found), None, win, max_level, max_count, eps, 0, min_eig)
+        d = back.astype(np.float64) - pts.astype(np.float64)
+        with np.errstate(all="ignore"):
+            status = status & back_ok & ~(d[:, 0] * d[:, 0] + d[:, 1] * d[:, 1] > back_check * back_check)
+    return found.reshape(-1, 1, 2), status, err
+
+
 def hough_circles(mat, dp: float, min_dist: float, param1: float = 100, param2: float = 100, min_radius: int = 0, max_radius: int = 0):
     """cv2.HoughCircles(mat, cv2.HOUGH_GRADIENT, dp, min_dist, None, param1, param2, min_radius, max_radius) on the GPU (libvp
     vp_hough_circles_*): (1, N, 3) float32 (x, y, r) in cv2's order, or None when no circle is found.  A device image is read where it

@@ -890,6 +890,34 @@ int vp_back_project_table_dev(vp_ctx* ctx, const uint8_t* src_dev, size_t stride
 int vp_mean_shift_dev(vp_ctx* ctx, const uint8_t* src_dev, size_t stride, int w, int h, const int32_t* windows_host, int n, int max_iter, double eps,
                       int32_t* out_dev, int32_t* out_host);
 
+/* ---- sparse optical flow: cv2.calcOpticalFlowPyrLK ------------------------------------------------------------------------------- *
+ * Pyramidal Lucas-Kanade tracking of n points between two uint8 single-channel images of one size (the
+ * statement: tests/flow_restate.py).  The window sums are exact integers; OpenCV's remaining steps run in double in one fixed order
+ * and are rounded to float32 where OpenCV holds a float: the exact value of what cv2's float32 code approximates.
+ * Level 0 is the image, level l + 1 is vp_pyr_down of level l with VP_BORDER_REFLECT_101, (w + 1) / 2 x (h + 1) / 2.  Level l exists
+ * while its width is above win_w and its height above win_h; the levels used are the existing ones at or below max_level.
+ * vp_lk_flow_levels: how many that is (0: level 0 itself is not larger than the window).  Host only, no context.
+ * vp_lk_flow_dev: prev_levels / next_levels are host arrays of n_levels device pointers with their row strides in bytes; levels
+ *   min(n_levels, vp_lk_flow_levels(..)) of them are read, so one pyramid serves calls with a smaller max_level.  prev_pts: n (x, y)
+ *   float32 pairs on the host; init_pts: n starting positions, read only with VP_LK_USE_INITIAL_FLOW.  max_count is clamped to
+ *   0..100 and eps to 0..10 as cv2 clamps its TermCriteria.  The result is n rows of four 32-bit words - x, y, err (float32) and
+ *   status (uint32, 0 or 1) - in out_dev and / or out_host (at least one of them); the call is one launch, enqueued, and
+ *   synchronises only to fill out_host.  err is sum |diff| / (32 win_w win_h) at the final position, or level 0's minimum eigenvalue
+ *   with VP_LK_GET_MIN_EIGENVALS; it is 0 whenever status is 0 and that flag is off.  A point (or initial position) with a
+ *   coordinate that is not finite or beyond +-2^24 gets status 0, err 0 and its starting position back.
+ * vp_lk_flow_u8: two packed host images; stages them, builds both pyramids with vp_pyr_down_dev, runs and synchronises.
+ * Refused with VP_ERR_INVALID before anything is launched or written (the message names the reason): a missing pointer, w or h outside
+ *   1..4096, a stride below its row, a window side outside 3..63, an image not larger than the window, n outside 1..2^20, max_level
+ *   outside 0..15, n_levels outside 1..16, unknown flag bits, a min_eig_threshold or eps that is not finite, an out_dev that is not
+ *   4-byte aligned or overlaps a level. */
+enum { VP_LK_USE_INITIAL_FLOW = 4, VP_LK_GET_MIN_EIGENVALS = 8 };
+int vp_lk_flow_levels(int w, int h, int win_w, int win_h, int max_level);
+int vp_lk_flow_dev(vp_ctx* ctx, const uint8_t* const* prev_levels, const size_t* prev_strides, const uint8_t* const* next_levels, const size_t* next_strides,
+                   int n_levels, int w, int h, const float* prev_pts_host, const float* init_pts_host, int n, int win_w, int win_h, int max_level, int max_count,
+                   double eps, int flags, double min_eig_threshold, void* out_dev, void* out_host);
+int vp_lk_flow_u8(vp_ctx* ctx, const uint8_t* prev_host, const uint8_t* next_host, int w, int h, const float* prev_pts_host, const float* init_pts_host, int n,
+                  int win_w, int win_h, int max_level, int max_count, double eps, int flags, double min_eig_threshold, void* out_host);
+
 /* ---- device memory helpers (so a host program needs no HIP binding of its own) --------- */
 int vp_dev_alloc(vp_ctx* ctx, size_t bytes, void** dev_ptr);
 int vp_dev_free(vp_ctx* ctx, void* dev_ptr);    /* ctx may be NULL (memory that outlived its context) */
