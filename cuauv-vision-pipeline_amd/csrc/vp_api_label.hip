@@ -91,22 +91,27 @@ static int find_contours_impl(vp_ctx* ctx, const uint8_t* src, bool src_on_devic
     const long long mp = max_points > 0 ? max_points : 1;
     // RETR_CCOMP / RETR_TREE (the tree entries only): the header carries the hierarchy rows [mc][4] between the offsets and the hole flags
     const bool tree = tree_entry && (mode == VP_RETR_CCOMP || mode == VP_RETR_TREE);
-    const size_t hier_bytes = tree ? (size_t)mc * 16 : 0;
-    VP_TRY(vp_ws_reserve(ctx, vp_align(npx) + vp_align(bitbytes) + vp_contours_ws_bytes(w, h, 1, mc) + vp_align(16 + (size_t)mc * 9 + hier_bytes) +
+    const ct_hdr_layout L = ct_hdr(mc, tree);            // the result header, one block so that one copy brings it back (vp_contours_plan.h)
+    const size_t hdr_bytes = L.bytes;
+    VP_TRY(vp_ws_reserve(ctx, vp_align(npx) + vp_align(bitbytes) + vp_contours_ws_bytes(w, h, 1, mc) + vp_align(hdr_bytes) +
                                   vp_align((size_t)mp * 8) + (tree ? vp_contour_tree_ws_bytes(mc) : 0) + 8192));
     TAKE(d_stage, uint8_t*, npx);
     const uint8_t* d_src = d_stage;
     size_t d_stride = (size_t)w;
     TAKE(d_bits, u64*, bitbytes);
-    // result header, one block so that one copy brings it back: info[2] (16 B) | counts[mc] | offsets[mc] | (tree: hierarchy[mc][4]) | is_hole[mc]
-    const size_t hdr_bytes = 16 + (size_t)mc * 9 + hier_bytes;
     TAKE(d_hdr, uint8_t*, hdr_bytes);
     TAKE(d_points, int32_t*, (size_t)mp * 8);
-    int32_t* d_info = reinterpret_cast<int32_t*>(d_hdr);
-    int32_t* d_counts = reinterpret_cast<int32_t*>(d_hdr + 16);
-    int32_t* d_offsets = d_counts + mc;
-    int32_t* d_hier = tree ? d_offsets + mc : nullptr;
-    uint8_t* d_hole = reinterpret_cast<uint8_t*>(d_offsets + mc + (tree ? 4 * (size_t)mc : 0));
+    // the header's arrays in the workspace block, or in the pinned one the kernels mirror them into
+    auto hdr_at = [&](uint8_t* base) {
+        vp_contour_mirror m = {};
+        m.info = reinterpret_cast<int32_t*>(base);
+        m.counts = reinterpret_cast<int32_t*>(base + L.counts);
+        m.offsets = reinterpret_cast<int32_t*>(base + L.offsets);
+        m.hier = tree ? reinterpret_cast<int32_t*>(base + L.hier) : nullptr;
+        m.is_hole = base + L.is_hole;
+        return m;
+    };
+    const vp_contour_mirror dh = hdr_at(d_hdr);
     const u64* bits_use = d_bits;
     if (bits_in) {
         bits_use = bits_in;                               // the caller made the bit plane with the mask (vp_inrange_u8_bits_dev): no packing launch
@@ -116,10 +121,9 @@ static int find_contours_impl(vp_ctx* ctx, const uint8_t* src, bool src_on_devic
         VP_TRY(vpk_pack_bits(ctx, d_src, d_stride, w, h, 1, d_bits, nullptr));
     }
     // one block does the bookkeeping between the two follower passes - unless the last pass of this context met a speckled mask
-    // (more border segments than the block's LDS tables hold: 8192): then it is launched over the chip (VP_CT_MANY=0 / 1: never / always)
-    const char* many_s = getenv("VP_CT_MANY");
-    const int many_env = many_s ? atoi(many_s) : -1;
-    const bool many = many_env >= 0 ? many_env != 0 : ctx->ct.heads_hint > 8192u;
+    // (more border segments than the block's LDS tables hold): then it is launched over the chip (VP_CT_MANY=0 / 1: never / always)
+    bool many_forced;
+    const bool many = ct_want_many(ctx->ct.heads_hint, &many_forced);
     // The header and the first points come back without a copy: the kernels that make them write them into the pinned staging
     // buffer as well, and the call only synchronises (longer point lists take a copy afterwards).  VP_CT_MIRROR=0: a copy, as before.
     const size_t spec_pts = points ? (size_t)std::min<long long>(mp, 8192) : 0;
@@ -127,12 +131,7 @@ static int find_contours_impl(vp_ctx* ctx, const uint8_t* src, bool src_on_devic
     uint8_t* hs = (uint8_t*)vp_hstage(ctx, hdr_pad + spec_pts * 8);
     if (!hs) return vp_fail(ctx, VP_ERR_NOMEM, "pinned staging");
     static const bool mirror_off = getenv("VP_CT_MIRROR") && atoi(getenv("VP_CT_MIRROR")) == 0;
-    vp_contour_mirror hm;
-    hm.info = reinterpret_cast<int32_t*>(hs);
-    hm.counts = reinterpret_cast<int32_t*>(hs + 16);
-    hm.offsets = hm.counts + mc;
-    hm.hier = tree ? hm.offsets + mc : nullptr;
-    hm.is_hole = reinterpret_cast<uint8_t*>(hm.offsets + mc + (tree ? 4 * (size_t)mc : 0));
+    vp_contour_mirror hm = hdr_at(hs);
     hm.points = spec_pts ? reinterpret_cast<int32_t*>(hs + hdr_pad) : nullptr;
     hm.points_cap = (long long)spec_pts;
     // One block only up to what its LDS tables hold: a mask that turns out to have more heads than that while none was expected says so
@@ -142,10 +141,10 @@ static int find_contours_impl(vp_ctx* ctx, const uint8_t* src, bool src_on_devic
     const size_t ws_mark = ctx->ws_off;
     const int32_t* info = nullptr;
     for (;;) {
-        const bool defer = !many_now && many_env < 0;
+        const bool defer = !many_now && !many_forced;
         ctx->ws_off = ws_mark;
-        VP_TRY(vpk_find_contours(ctx, bits_use, w, h, 1, mode, method, d_counts, d_hole, d_offsets, d_points, mc, mp, d_info, many_now,
-                                 reinterpret_cast<uint32_t*>(d_info + 2), mirror_off ? nullptr : &hm, defer, d_hier));
+        VP_TRY(vpk_find_contours(ctx, bits_use, w, h, 1, mode, method, dh.counts, dh.is_hole, dh.offsets, d_points, mc, mp, dh.info, many_now,
+                                 reinterpret_cast<uint32_t*>(dh.info + 2), mirror_off ? nullptr : &hm, defer, dh.hier));
         if (mirror_off) {
             if (spec_pts && reinterpret_cast<uint8_t*>(d_points) == d_hdr + hdr_pad) {
                 VP_TRY(d2h(ctx, hs, d_hdr, hdr_pad + spec_pts * 8));           // header and points lie back to back in the workspace: one copy
@@ -168,12 +167,12 @@ static int find_contours_impl(vp_ctx* ctx, const uint8_t* src, bool src_on_devic
     if (K > max_contours || P > max_points || K == 0) return VP_OK;
     std::vector<int32_t> hc(K), ho(K);
     std::vector<uint8_t> hh(K);
-    memcpy(hc.data(), hs + 16, (size_t)K * 4);
-    memcpy(ho.data(), hs + 16 + (size_t)mc * 4, (size_t)K * 4);
-    memcpy(hh.data(), hs + 16 + (size_t)mc * 8 + hier_bytes, (size_t)K);
+    memcpy(hc.data(), hs + L.counts, (size_t)K * 4);
+    memcpy(ho.data(), hs + L.offsets, (size_t)K * 4);
+    memcpy(hh.data(), hs + L.is_hole, (size_t)K);
     if (hierarchy) {
         // RETR_CCOMP / RETR_TREE: the rows came in cv2's order; the flat modes: each contour the next one's newer sibling
-        if (tree) memcpy(hierarchy, hs + 16 + (size_t)mc * 8, (size_t)K * 16);
+        if (tree) memcpy(hierarchy, hs + L.hier, (size_t)K * 16);
         else
             for (int j = 0; j < K; j++) {
                 hierarchy[4 * j] = j + 1 < K ? j + 1 : -1;

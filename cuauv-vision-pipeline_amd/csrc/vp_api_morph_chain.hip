@@ -351,8 +351,7 @@ static int chain_core(vp_ctx* ctx, const vp_chain_desc* d, const vp_chain_buffer
         const int group = ct_group_for(w, h, cd->max_contours);
         // speckled frames in the last batch (its prefix kernel left the head counts in pinned memory): the bookkeeping as launches over
         // the chip instead of one block per frame (VP_CT_MANY=0 / 1: never / always)
-        const char* many_s = getenv("VP_CT_MANY");
-        const bool many = many_s ? atoi(many_s) != 0 : vp_ct_batch_hint(ctx) > 8192u;
+        const bool many = ct_want_many(vp_ct_batch_hint(ctx));
         for (int f0 = 0; f0 < n; f0 += group) {
             const int g = std::min(group, n - f0);
             ctx->ws_off = mark;   // every group reuses the same scratch (stream order keeps them apart)

@@ -76,8 +76,7 @@ template <bool SPARSE> struct ct_cut {
 };
 
 struct ct_aux { u32 nheads; u32 nsel; };
-
-__host__ __device__ inline size_t ct_hcap(int w, int h) { const size_t npx = (size_t)w * h; return (npx + npx / 4 + 64 + 63) / 64 * 64; }
+static_assert(sizeof(ct_aux) == 8, "vp_contours_plan.h sizes the aux array");
 
 // neighbour bitmaps of word (y, j): bit b of f[d] = neighbour of pixel (y, 64j + b) in direction d of {E, NE, N, NW, W, SW, S, SE}
 __device__ __forceinline__ void ct_neighbours(const ccl_geom& G, const u64* __restrict__ fb, int y, int j, u64& c, u64 f[8])
@@ -771,8 +770,7 @@ __device__ __forceinline__ ctj_frame ctj_make_frame(const ctj_args& A, int f, un
 // (Steps (1) and (4) as ONE sequence on 16-byte entries (J, D, m, dm, leader) was built and measured: a 16-byte jump costs twice an
 // 8-byte one, 12.8 us against 8.1 + 5.6 - not worth entries whose halves another wave might see apart.)
 // 16 B of LDS per head: tab (8): the pairs of step (1), then of step (4); a1 (4): keys, then (after the ranks are out) the marks;
-// a2 (4): the look to the left / step (2)'s answers, then step (3)'s counts.
-#define CTJ_LDS_HEADS 8192
+// a2 (4): the look to the left / step (2)'s answers, then step (3)'s counts.  (CTJ_LDS_HEADS: vp_contours_plan.h)
 #define CTJ_ITEMS (CTJ_LDS_HEADS / 1024)
 #ifndef CTJ_HOPS
 #define CTJ_HOPS 4
@@ -1036,8 +1034,7 @@ __global__ __launch_bounds__(1024) void k_ct_jump(ctj_args A)
 
 // ---- the same steps as launches over the chip (grid (blocks, n) x 256) ----
 // flags[f][i]: launch i of a round sequence changed something.  Slot 0 of each sequence is set by the launch before it.
-#define CTM_SEQ 32
-#define CTM_NFLAGS (3 * CTM_SEQ)
+// (CTM_SEQ slots per sequence, CTM_NFLAGS per frame: vp_contours_plan.h)
 enum { CTM_LEAD_INIT, CTM_LEAD, CTM_EXT_INIT, CTM_EXT, CTM_RANK, CTM_MARK, CTM_DIST };
 
 template <int PH>
@@ -1399,35 +1396,25 @@ int vpk_contour_features(vp_ctx* ctx, const int32_t* d_info, const int32_t* d_co
     return VP_OK;
 }
 
-// sort key = parent + 1 in [0, max_contours], max_contours + 1 past the borders
-static int ctt_key_bits(int max_contours)
+// scratch the hierarchy pass's radix sort asks for: the one input of the plan (vp_contours_plan.h) that takes the runtime to find
+static hipError_t ctt_sort_bytes(int max_contours, size_t& bytes)
 {
-    int b = 1;
-    while (b < 31 && ((u32)max_contours + 1u) >> b) b++;
-    return b;
+    u32* p = nullptr;
+    bytes = 0;
+    return hipcub::DeviceRadixSort::SortPairs(nullptr, bytes, p, p, p, p, max_contours, 0, ct_key_bits(max_contours));
 }
 
+// what a pass carves: the plan's workspace table (vp_contours_plan.h), which vpk_find_contours walks
 size_t vp_contour_tree_ws_bytes(int max_contours)
 {
-    const size_t mc = (size_t)max_contours;
-    size_t sort_bytes = 0;
-    u32* p = nullptr;
-    if (hipcub::DeviceRadixSort::SortPairs(nullptr, sort_bytes, p, p, p, p, max_contours, 0, ctt_key_bits(max_contours)) != hipSuccess) {
+    size_t sort_bytes;
+    if (ctt_sort_bytes(max_contours, sort_bytes) != hipSuccess) {
         (void)hipGetLastError();
-        sort_bytes = mc * 16 + (1 << 20);
+        sort_bytes = (size_t)max_contours * 16 + (1 << 20);
     }
-    return 2 * vp_align(mc * 4) + vp_align(mc) + 8 * vp_align(mc * 4) + vp_align((mc + 1) * 4) + vp_align((2 * mc + 2) * 8) + vp_align(sort_bytes) +
-           4096;
+    return ct_ws_tree_bytes(max_contours, sort_bytes);
 }
-
-size_t vp_contours_ws_bytes(int w, int h, int n, int max_contours)
-{
-    const size_t words = (size_t)n * h * vp_ww(w);
-    const size_t hcap = ct_hcap(w, h) * n;
-    return vp_align(words * 32) + vp_align(words * 4) + vp_align(words) + 4 * vp_align(hcap * 4) + 2 * vp_align(hcap * 8) +
-           2 * vp_align((size_t)n * max_contours * 4) + vp_align(sizeof(ct_aux) * n) + vp_align(words / 64 + 4 * n) +
-           vp_align((size_t)n * CTM_NFLAGS * 4) + vp_align((ct_hcap(w, h) / 1024 + 2) * 4 * n) + 8192;
-}
+size_t vp_contours_ws_bytes(int w, int h, int n, int max_contours) { return ct_ws_base_bytes(w, h, n, max_contours); }
 
 
 // Head counts of the frames of the last batched pass (up to 64 of them), written by its prefix kernel into a pinned array of the
@@ -1459,65 +1446,44 @@ uint32_t vp_ct_batch_hint(vp_ctx* ctx)
 
 // d_counts / d_is_hole / d_offsets: [n][max_contours]; d_points: [n][max_points][2]; d_info: [n] {n_contours, n_points}.  Contours are
 // stored in discovery order (raster order of the start pixel); cv2 returns them reversed - the caller reverses.
-// Five launches on the context's stream.  `many_heads` (one image whose last pass counted very many heads - the caller's guess, the
-// results do not depend on it): the bookkeeping between the follower passes as launches over the chip instead of one block.
+// Everything decided on the host - refusals, the workspace table, grids, rounds - comes from ct_make_plan (vp_contours_plan.h), before
+// anything is carved or launched.  Launches on the context's stream, r = the plan's `rounds` (13 at 1080p):
+//   one block per frame:  5 - head maps, prefix, follow, k_ct_jump, follow again and write
+//   `many_heads`:         12 + 2 r, RETR_EXTERNAL 13 + 3 r - k_ct_jump's steps as k_ctm launches over the chip (one image whose last
+//                         pass counted very many heads - the caller's guess, the results do not depend on it)
+//   the hierarchy pass:   5 + 2 `rounds_tree` more, and the radix sort's own
 // d_nheads_out (nullable, [n]): the frames' head counts.
 int vpk_find_contours(vp_ctx* ctx, const u64* d_bits, int w, int h, int n, int mode, int method, int32_t* d_counts, uint8_t* d_is_hole,
                       int32_t* d_offsets, int32_t* d_points, int max_contours, long long max_points, int32_t* d_info, bool many_heads,
                       uint32_t* d_nheads_out, const vp_contour_mirror* host, bool defer_big, int32_t* d_hier)
 {
-    const bool tree = (mode == 2 || mode == 3) && d_hier && n == 1;
-    if (mode != 0 && mode != 1 && !tree) return vp_fail(ctx, VP_ERR_INVALID, "contour mode");
-    if (method != 1 && method != 2) return vp_fail(ctx, VP_ERR_INVALID, "contour approximation");
-    if ((size_t)w * h >= (1u << 29)) return vp_fail(ctx, VP_ERR_INVALID, "contours: image too large");
+    size_t sort_bytes = 0;
+    if (d_hier) VP_HIP(ctx, ctt_sort_bytes(max_contours, sort_bytes));
+    const ct_plan P = ct_make_plan(w, h, n, mode, method, max_contours, d_hier != nullptr, host != nullptr, many_heads, defer_big, ctx->ct.heads_hint,
+                                   sort_bytes);
+    if (P.status != VP_OK) return vp_fail(ctx, P.status, P.why);
+    void* ws[CTW_ALL] = {};
+    for (int i = 0; i < P.nws; i++)
+        if (!(ws[i] = vp_ws_take(ctx, P.ws[i].bytes)))
+            return vp_fail(ctx, VP_ERR_NOMEM, i < CTW_BASE ? "contour workspace" : "contour hierarchy workspace");
+    u64* hmaps = (u64*)ws[CTW_HMAPS];
+    u32 *hbase = (u32*)ws[CTW_HBASE], *head_pix = (u32*)ws[CTW_HEAD_PIX], *hkey = (u32*)ws[CTW_HKEY], *partsum = (u32*)ws[CTW_PARTSUM];
+    uint8_t* cnt8 = (uint8_t*)ws[CTW_CNT8];
+    const size_t hcap = P.hcap;
+    const int nwords = P.nwords;
     ctj_args A;
     ccl_make_geom(A.G, w, h, VP_CCL_PIXEL, 0, 0, ccl_env_tuning());
     const ccl_geom& G = A.G;
-    const int nwords = h * G.ww;
-    const size_t words = (size_t)n * nwords;
-    const size_t hcap = ct_hcap(w, h);
-    u64* hmaps = (u64*)vp_ws_take(ctx, words * 32);
-    u32* hbase = (u32*)vp_ws_take(ctx, words * 4);
-    uint8_t* cnt8 = (uint8_t*)vp_ws_take(ctx, words);
-    u32* head_pix = (u32*)vp_ws_take(ctx, hcap * n * 4);
-    A.hrank = (u32*)vp_ws_take(ctx, hcap * n * 4);
-    u32* hkey = (u32*)vp_ws_take(ctx, hcap * n * 4);
-    A.hext = (u32*)vp_ws_take(ctx, hcap * n * 4);
-    A.node = (unsigned long long*)vp_ws_take(ctx, hcap * n * 8);
-    A.node2 = (unsigned long long*)vp_ws_take(ctx, hcap * n * 8);
-    A.starts = (u32*)vp_ws_take(ctx, (size_t)n * max_contours * 4);
-    A.shead = (u32*)vp_ws_take(ctx, (size_t)n * max_contours * 4);
-    A.aux = (ct_aux*)vp_ws_take(ctx, sizeof(ct_aux) * n);
-    const size_t nparts = (size_t)(nwords + 255) / 256;
-    u32* partsum = (u32*)vp_ws_take(ctx, nparts * n * 4);
-    A.flags = (u32*)vp_ws_take(ctx, (size_t)n * CTM_NFLAGS * 4);
-    A.csum = (u32*)vp_ws_take(ctx, (hcap / 1024 + 2) * 4 * n);
-    if (!hmaps || !hbase || !cnt8 || !head_pix || !A.hrank || !hkey || !A.hext || !A.node || !A.node2 || !A.starts || !A.shead || !A.aux || !partsum ||
-        !A.flags || !A.csum)
-        return vp_fail(ctx, VP_ERR_NOMEM, "contour workspace");
+    A.hrank = (u32*)ws[CTW_HRANK]; A.hext = (u32*)ws[CTW_HEXT];
+    A.node = (unsigned long long*)ws[CTW_NODE]; A.node2 = (unsigned long long*)ws[CTW_NODE2];
+    A.starts = (u32*)ws[CTW_STARTS]; A.shead = (u32*)ws[CTW_SHEAD];
+    A.aux = (ct_aux*)ws[CTW_AUX]; A.flags = (u32*)ws[CTW_FLAGS]; A.csum = (u32*)ws[CTW_CSUM];
     // RETR_CCOMP / RETR_TREE: the bookkeeping runs as for RETR_LIST into workspace arrays, the hierarchy pass permutes them into the caller's
     ctt_args T;
-    size_t sort_bytes = 0;
-    void* sort_tmp = nullptr;
-    if (tree) {
-        const size_t mc = (size_t)max_contours;
-        T.tcounts = (int32_t*)vp_ws_take(ctx, mc * 4);
-        T.toffsets = (int32_t*)vp_ws_take(ctx, mc * 4);
-        T.thole = (uint8_t*)vp_ws_take(ctx, mc);
-        T.par = (u32*)vp_ws_take(ctx, mc * 4);
-        T.key = (u32*)vp_ws_take(ctx, mc * 4);
-        T.val = (u32*)vp_ws_take(ctx, mc * 4);
-        T.skey = (u32*)vp_ws_take(ctx, mc * 4);
-        T.sval = (u32*)vp_ws_take(ctx, mc * 4);
-        T.fc = (u32*)vp_ws_take(ctx, (mc + 1) * 4);
-        T.ns = (u32*)vp_ws_take(ctx, mc * 4);
-        T.nw = (u32*)vp_ws_take(ctx, mc * 4);
-        T.tour = (unsigned long long*)vp_ws_take(ctx, (2 * mc + 2) * 8);
-        VP_HIP(ctx, hipcub::DeviceRadixSort::SortPairs(nullptr, sort_bytes, T.key, T.skey, T.val, T.sval, max_contours, 0, ctt_key_bits(max_contours),
-                                                       ctx->stream));
-        sort_tmp = vp_ws_take(ctx, sort_bytes);
-        if (!T.tcounts || !T.toffsets || !T.thole || !T.par || !T.key || !T.val || !T.skey || !T.sval || !T.fc || !T.ns || !T.nw || !T.tour || !sort_tmp)
-            return vp_fail(ctx, VP_ERR_NOMEM, "contour hierarchy workspace");
+    if (P.tree) {
+        T.tcounts = (int32_t*)ws[CTW_TCOUNTS]; T.toffsets = (int32_t*)ws[CTW_TOFFSETS]; T.thole = (uint8_t*)ws[CTW_THOLE];
+        T.par = (u32*)ws[CTW_PAR]; T.key = (u32*)ws[CTW_KEY]; T.val = (u32*)ws[CTW_VAL]; T.skey = (u32*)ws[CTW_SKEY]; T.sval = (u32*)ws[CTW_SVAL];
+        T.fc = (u32*)ws[CTW_FC]; T.ns = (u32*)ws[CTW_NS]; T.nw = (u32*)ws[CTW_NW]; T.tour = (unsigned long long*)ws[CTW_TOUR];
     }
     const size_t jump_lds = (size_t)CTJ_LDS_HEADS * 16;
     if (!ctx->ct.lds_set) {                               // (per context = per device: the attribute belongs to the device's copy of the kernel)
@@ -1525,51 +1491,41 @@ int vpk_find_contours(vp_ctx* ctx, const u64* d_bits, int w, int h, int n, int m
         ctx->ct.lds_set = 1;
     }
     A.hkey = hkey; A.hbase = hbase; A.cnt8 = cnt8; A.head_pix = head_pix; A.hcap = hcap;
-    A.counts = tree ? const_cast<int32_t*>(T.tcounts) : d_counts;
-    A.is_hole = tree ? const_cast<uint8_t*>(T.thole) : d_is_hole;
-    A.offsets = tree ? const_cast<int32_t*>(T.toffsets) : d_offsets;
+    A.counts = P.tree ? const_cast<int32_t*>(T.tcounts) : d_counts;
+    A.is_hole = P.tree ? const_cast<uint8_t*>(T.thole) : d_is_hole;
+    A.offsets = P.tree ? const_cast<int32_t*>(T.toffsets) : d_offsets;
     A.points = d_points;
     A.out = reinterpret_cast<ct_frame_out*>(d_info);
-    A.max_contours = max_contours; A.max_points = max_points; A.mode = mode == 0 ? 0 : 1; A.lds_heads = CTJ_LDS_HEADS; A.nheads_out = d_nheads_out;
-    A.hops = 3;
-    A.defer_big = (defer_big && n == 1 && !many_heads) ? 1 : 0;
+    A.max_contours = max_contours; A.max_points = max_points; A.mode = P.seg_mode; A.lds_heads = CTJ_LDS_HEADS; A.nheads_out = d_nheads_out;
+    A.hops = CT_HOPS;
+    A.defer_big = P.defer_big;
     A.mirror = ct_mirror{nullptr, nullptr, nullptr, nullptr, nullptr, 0};
-    if (host && n == 1) A.mirror = ct_mirror{host->info, host->counts, host->offsets, host->is_hole, host->points, host->points_cap};
-    if (tree) {
+    if (P.mirror) A.mirror = ct_mirror{host->info, host->counts, host->offsets, host->is_hole, host->points, host->points_cap};
+    if (P.tree) {
         T.M = A.mirror;
         T.mhier = host ? host->hier : nullptr;
         A.mirror.counts = nullptr; A.mirror.offsets = nullptr; A.mirror.hole = nullptr;     // (the rows the bookkeeping writes are not the caller's order)
         T.G = A.G; T.bits = d_bits; T.hmaps = hmaps; T.hbase = hbase; T.hrank = A.hrank; T.starts = A.starts; T.node = A.node; T.out = A.out;
-        T.max_contours = max_contours; T.mode = mode; T.counts = d_counts; T.offsets = d_offsets; T.hole = d_is_hole; T.hier = d_hier; T.hops = 3;
+        T.max_contours = max_contours; T.mode = mode; T.counts = d_counts; T.offsets = d_offsets; T.hole = d_is_hole; T.hier = d_hier; T.hops = CT_HOPS;
     }
-    const int seg_mode = A.mode;
+    const int seg_mode = P.seg_mode;
     int32_t* seg_offsets = A.offsets;
+    const u32 skip_above = P.skip_above;
     hipStream_t s = ctx->stream;
     vp_prof_scope ps(ctx, VPK_OTHER);
-    const dim3 wgrid((unsigned)((nwords + 255) / 256), (unsigned)n);
-    // heads per frame are not known on the host: a fixed number of blocks per frame walks the head list (a real mask has a few
-    // thousand heads; empty blocks of a grid sized for the worst case would cost more than the work)
-    // (one image: the head count of the context's last single-image pass sizes the grid - two items per head, half as much again -
-    // instead of a thousand blocks of which thirty find work; the loops stride over the grid, so a wrong guess only costs time)
-    size_t hblocks = (size_t)std::max(32, std::min(1024, 8192 / n));
-    if (n == 1 && ctx->ct.heads_hint) hblocks = std::min<size_t>(hblocks, std::max<size_t>(32, ((size_t)ctx->ct.heads_hint * 3 + 255) / 256));
-    const dim3 hgrid((unsigned)std::min<size_t>((hcap + 255) / 256, hblocks), (unsigned)n);
+    const dim3 wgrid(P.wgrid, (unsigned)n), hgrid(P.hgrid, (unsigned)n);
     if (many_heads) hipLaunchKernelGGL(k_ct_headmaps<true>, wgrid, dim3(256), 0, s, d_bits, G, hmaps, partsum, cnt8);
     else hipLaunchKernelGGL(k_ct_headmaps<false>, wgrid, dim3(256), 0, s, d_bits, G, hmaps, partsum, cnt8);
     hipLaunchKernelGGL(k_ct_prefix, wgrid, dim3(256), 0, s, hmaps, 4, nwords, partsum, hbase, &A.aux->nheads, 2, w, G.ww, head_pix, hcap, cnt8,
-                       (n > 1 || !host) ? vp_ct_hint_slots(ctx, n) : nullptr);
+                       P.hint_slots ? vp_ct_hint_slots(ctx, n) : nullptr);
 #define CT_SEG_ARGS d_bits, G, hmaps, hbase, head_pix, A.hrank, hcap, A.aux, A.node, hkey, A.hext, seg_mode, method, seg_offsets, d_points, max_contours, max_points
-    const u32 skip_above = A.defer_big ? (u32)CTJ_LDS_HEADS : 0u;
     if (many_heads) hipLaunchKernelGGL((k_ct_seg<false, true>), hgrid, dim3(256), 0, s, CT_SEG_ARGS, (int32_t*)nullptr, 0ll, skip_above);
     else hipLaunchKernelGGL((k_ct_seg<false, false>), hgrid, dim3(256), 0, s, CT_SEG_ARGS, (int32_t*)nullptr, 0ll, skip_above);
     if (!many_heads) {
         hipLaunchKernelGGL(k_ct_jump, dim3((unsigned)n), dim3(1024), jump_lds, s, A);
     } else {
-        // a launch of `hops` steps multiplies the shortest window (distance jumped) by hops + 1 at least: rounds that always suffice
-        int rounds = 2;
-        for (size_t reach = 1; reach < hcap; reach *= (size_t)(A.hops + 1)) rounds++;
-        if (rounds >= CTM_SEQ) return vp_fail(ctx, VP_ERR_INVALID, "contours: image too large");
-        const dim3 mg((unsigned)std::max(32, std::min(1024, 8192 / n)), (unsigned)n), sg((unsigned)std::max(8, std::min(256, 2048 / n)), (unsigned)n);
+        const int rounds = P.rounds;
+        const dim3 mg(P.mg, (unsigned)n), sg(P.sg, (unsigned)n);
         hipLaunchKernelGGL((k_ctm<CTM_LEAD_INIT>), mg, dim3(256), 0, s, A, 0);
         for (int i = 1; i <= rounds; i++) hipLaunchKernelGGL((k_ctm<CTM_LEAD>), mg, dim3(256), 0, s, A, i);
         if (A.mode == 0) {
@@ -1585,16 +1541,14 @@ int vpk_find_contours(vp_ctx* ctx, const u64* d_bits, int w, int h, int n, int m
         hipLaunchKernelGGL((k_ctm_sums<1>), sg, dim3(1024), 0, s, A);
         hipLaunchKernelGGL((k_ctm_scan<1>), sg, dim3(1024), 0, s, A);
     }
-    if (tree) {
-        int rounds = 2;
-        for (size_t reach = 1; reach < 2 * (size_t)max_contours + 2; reach *= (size_t)(T.hops + 1)) rounds++;
-        const unsigned nb = (unsigned)((max_contours + 256) / 256), tb = (unsigned)((2 * (size_t)max_contours + 2 + 255) / 256);
-        const unsigned jb = std::min(nb, 1024u), jtb = std::min(tb, 1024u);
+    if (P.tree) {
+        const int rounds = P.rounds_tree;
+        const unsigned nb = P.nb, tb = P.tb, jb = P.jb, jtb = P.jtb;
         if (many_heads) hipLaunchKernelGGL(k_ctt_parent<true>, dim3(nb), dim3(256), 0, s, T);
         else hipLaunchKernelGGL(k_ctt_parent<false>, dim3(nb), dim3(256), 0, s, T);
         for (int i = 0; i < rounds; i++) hipLaunchKernelGGL(k_ctt_jump_par, dim3(jb), dim3(256), 0, s, T);
         hipLaunchKernelGGL(k_ctt_keys, dim3(nb), dim3(256), 0, s, T);
-        VP_HIP(ctx, hipcub::DeviceRadixSort::SortPairs(sort_tmp, sort_bytes, T.key, T.skey, T.val, T.sval, max_contours, 0, ctt_key_bits(max_contours), s));
+        VP_HIP(ctx, hipcub::DeviceRadixSort::SortPairs(ws[CTW_SORT], sort_bytes, T.key, T.skey, T.val, T.sval, max_contours, 0, P.key_bits, s));
         hipLaunchKernelGGL(k_ctt_links, dim3(nb), dim3(256), 0, s, T);
         hipLaunchKernelGGL(k_ctt_tour, dim3(tb), dim3(256), 0, s, T);
         for (int i = 0; i < rounds; i++) hipLaunchKernelGGL(k_ctt_jump_tour, dim3(jtb), dim3(256), 0, s, T);
@@ -1606,3 +1560,4 @@ int vpk_find_contours(vp_ctx* ctx, const u64* d_bits, int w, int h, int n, int m
     VP_HIP(ctx, hipGetLastError());
     return VP_OK;
 }
+

@@ -6,6 +6,7 @@
 #include "../../include/vp.h"
 #include "vp_options.h"
 #include "vp_morph_plan.h"
+#include "vp_contours_plan.h"
 
 typedef unsigned long long u64;
 typedef unsigned int u32;
@@ -459,11 +460,15 @@ bool vp_ccl_ws_ok(const vp_ccl_ws& ws);
 size_t vp_ccl_nids(int w, int h);   // multiple of 32
 size_t vp_ccl_ws_bytes(int w, int h, int n, int max_labels);
 void vp_ccl_ws_carve(vp_ctx* ctx, int w, int h, int n, int max_labels, vp_ccl_ws* out);
+// scratch of a contour pass over n frames / of the hierarchy pass of one image: the totals of the workspace table of vp_contours_plan.h,
+// which vpk_find_contours carves entry by entry
 size_t vp_contours_ws_bytes(int w, int h, int n, int max_contours);
+size_t vp_contour_tree_ws_bytes(int max_contours);
 int vpk_contour_features(vp_ctx* ctx, const int32_t* d_info, const int32_t* d_counts, const int32_t* d_offsets, const int32_t* d_points, int n,
                          int max_contours, long long max_points, double* d_features);
-// contours of n bit images (no labelling involved: vp_contours.inl).  many_heads: the caller expects a frame with very many border
-// segments (its last pass said so through d_nheads_out) - a choice between two forms of the same steps, not of the result.
+// contours of n bit images (no labelling involved: vp_contours.inl; every host decision: ct_make_plan, vp_contours_plan.h).  many_heads:
+// the caller expects a frame with very many border segments (ct_want_many of its last pass's count, d_nheads_out / vp_ct_batch_hint) - a
+// choice between two forms of the same steps, not of the result.
 // host (n == 1 only): pinned, device-visible buffers the producing kernels write the results into as well - info {n_contours,
 // n_points, heads}, counts / offsets / is_hole [max_contours], the first points_cap points - so that the caller only synchronises.
 // defer_big (n == 1, not many_heads): a frame with more heads than the one block's LDS tables hold reports n_contours = -1 and nothing
@@ -472,7 +477,6 @@ uint32_t vp_ct_batch_hint(vp_ctx* ctx);      // largest head count the last batc
 // d_hier (n == 1 only, [max_contours][4]): RETR_CCOMP / RETR_TREE, which need it - the hierarchy rows in cv2's order (the contour arrays
 // stay in device order, reversed by the caller); the modes 0 / 1 take it as NULL.  host->hier: the same rows in the pinned buffer.
 struct vp_contour_mirror { int32_t* info; int32_t* counts; int32_t* offsets; uint8_t* is_hole; int32_t* points; long long points_cap; int32_t* hier; };
-size_t vp_contour_tree_ws_bytes(int max_contours);
 int vpk_find_contours(vp_ctx* ctx, const u64* d_bits, int w, int h, int n, int mode, int method, int32_t* d_counts, uint8_t* d_is_hole,
                       int32_t* d_offsets, int32_t* d_points, int max_contours, long long max_points, int32_t* d_info, bool many_heads = false,
                       uint32_t* d_nheads_out = nullptr, const vp_contour_mirror* host = nullptr, bool defer_big = false, int32_t* d_hier = nullptr);

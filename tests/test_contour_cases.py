@@ -10,6 +10,7 @@ import contour_cases as CC
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 _SRC = open(os.path.join(ROOT, "cuauv-vision-pipeline_amd", "csrc", "vp_contours.inl")).read()
+_PLAN = open(os.path.join(ROOT, "cuauv-vision-pipeline_amd", "csrc", "vp_contours_plan.h")).read()      # the constants host and device share
 
 
 def _mask(h, w, pixels):
@@ -21,7 +22,8 @@ def _mask(h, w, pixels):
 
 def test_constants_are_the_kernels():
     """the boundaries of the cases are the ones k_ct_jump compares the head count with"""
-    assert int(re.search(r"#define CTJ_LDS_HEADS (\d+)", _SRC).group(1)) == CC.LDS_HEADS == CC.BOUNDARIES[-1]
+    assert int(re.search(r"#define CTJ_LDS_HEADS (\d+)", _PLAN).group(1)) == CC.LDS_HEADS == CC.BOUNDARIES[-1]
+    assert "#define CTJ_LDS_HEADS" not in _SRC            # one definition
     picks = re.findall(r"if \(H <= (\d+)u\) ctj_body_lds<(\d+)>", _SRC)
     assert [(int(b), int(i)) for b, i in picks] == list(zip(CC.BOUNDARIES[:-1], CC.ITEMS[:-1]))
     assert "else ctj_body_lds<CTJ_ITEMS>" in _SRC and CC.ITEMS[-1] == CC.LDS_HEADS // 1024
