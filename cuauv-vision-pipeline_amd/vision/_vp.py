@@ -57,6 +57,7 @@ INTER_NEAREST, INTER_LINEAR = 0, 1
 DIST_L1, DIST_L2, DIST_C = 1, 2, 3
 TM_SQDIFF, TM_SQDIFF_NORMED, TM_CCORR, TM_CCORR_NORMED, TM_CCOEFF, TM_CCOEFF_NORMED = 0, 1, 2, 3, 4, 5
 WARP_INVERSE_MAP = 16
+MODEL_SIMILARITY, MODEL_AFFINE, MODEL_HOMOGRAPHY = 0, 1, 2
 PROF_KERNELS = 15
 
 
@@ -298,6 +299,17 @@ _SIGS = {
                                  C.c_int, C.c_int, C.c_int, C.c_double, C.c_int, C.c_double, C.c_void_p, C.c_void_p]),
     "vp_lk_flow_u8": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_double,
                                 C.c_int, C.c_double, C.c_void_p]),
+    "vp_model_round_size": (C.c_int, []),
+    "vp_model_stage_points": (C.c_int, []),
+    "vp_estimate_model_f32": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_double, C.c_int, C.c_double, C.c_uint32, C.c_void_p, C.c_void_p,
+                                        C.c_void_p, C.c_void_p]),
+    "vp_estimate_model_dev": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_double, C.c_int, C.c_double, C.c_uint32, C.c_void_p, C.c_void_p,
+                                        C.c_void_p, C.c_void_p]),
+    "vp_estimate_model_host": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_double, C.c_int, C.c_double, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p,
+                                         C.c_void_p]),
+    "vp_model_hypothesis": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_uint32, C.c_int, C.c_void_p, C.c_void_p]),
+    "vp_model_stop_table": (C.c_int, [C.c_int, C.c_int, C.c_double, C.c_int, C.c_void_p, C.c_int, C.c_void_p]),
+    "vp_model_refit": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p]),
 }
 
 

@@ -1321,6 +1321,59 @@ def calcOpticalFlowPyrLK(prevImg, nextImg, prevPts, nextPts, status=None, err=No
             _into(err, e.reshape(-1, 1)))
 
 
+LMEDS, RANSAC, RHO = 4, 8, 16
+
+
+def _motion(name, model, from_, to, method, threshold, maxIters, confidence, allow_plain):
+    """(3 x 3 or 2 x 3 float64, (N, 1) uint8 mask), or (None, None) when there is no model"""
+    try:
+        method = int(method)
+    except (TypeError, ValueError):
+        raise error(f"{name}: the method must be an integer") from None
+    if method in (LMEDS, RHO):
+        raise error(f"{name}: LMEDS and RHO are outside the accelerated path (DESIGN.md section 7)")
+    if method != RANSAC and not (allow_plain and method == 0):
+        raise error(f"{name}: unknown method")
+    try:
+        src, dst = _feature._motion_pairs(from_, to, _feature._motion_model(model))
+        if method == 0:
+            M = _feature.refit_motion(src, dst, model)
+            return (None, None) if M is None else (M, np.ones((len(src), 1), np.uint8))
+    except (ValueError, _vp.VpError) as e:
+        raise error(f"{name}: {e}") from None
+    try:
+        M, inl = _feature.estimate_motion(src, dst, model, threshold, maxIters, confidence)
+    except (ValueError, TypeError) as e:
+        raise error(f"{name}: {e}") from None
+    except _vp.VpError as e:
+        raise error(f"{name}: {e}") from e
+    return (None, None) if M is None else (M, inl.astype(np.uint8).reshape(-1, 1))
+
+
+def findHomography(srcPoints, dstPoints, method=0, ransacReprojThreshold=3.0, mask=None, maxIters=2000, confidence=0.995):
+    """cv2.findHomography in cv2's positional order for method 0 (the least squares over all pairs, a mask of ones) and RANSAC (the
+    search on the GPU, vision.utils.feature.estimate_motion): (H 3 x 3 float64 with H[2, 2] = 1, mask (N, 1) uint8), or (None, None)
+    when there is no model.  The contract is the statement of DESIGN.md section 4.30, not cv2's random sequence: the inlier set
+    agrees with cv2's where the data decide it; H is the least-squares fit to the inliers without cv2's Levenberg-Marquardt
+    polish.  LMEDS and RHO raise."""
+    H, inl = _motion("findHomography", "homography", srcPoints, dstPoints, method, ransacReprojThreshold, maxIters, confidence, True)
+    return H, (None if inl is None else _into(mask, inl))
+
+
+def estimateAffine2D(from_, to, inliers=None, method=RANSAC, ransacReprojThreshold=3.0, maxIters=2000, confidence=0.99, refineIters=10):
+    """cv2.estimateAffine2D with RANSAC: (M 2 x 3 float64, inliers (N, 1) uint8), or (None, None).  refineIters is accepted and has
+    no effect beyond the least-squares fit to the inliers."""
+    M, inl = _motion("estimateAffine2D", "affine", from_, to, method, ransacReprojThreshold, maxIters, confidence, False)
+    return M, (None if inl is None else _into(inliers, inl))
+
+
+def estimateAffinePartial2D(from_, to, inliers=None, method=RANSAC, ransacReprojThreshold=3.0, maxIters=2000, confidence=0.99, refineIters=10):
+    """cv2.estimateAffinePartial2D with RANSAC: rotation, uniform scale and translation as (M 2 x 3 float64, inliers (N, 1) uint8),
+    or (None, None)."""
+    M, inl = _motion("estimateAffinePartial2D", "similarity", from_, to, method, ransacReprojThreshold, maxIters, confidence, False)
+    return M, (None if inl is None else _into(inliers, inl))
+
+
 def normalize(src, dst=None, alpha=1.0, beta=0.0, norm_type=NORM_L2, dtype=-1, mask=None):
     """cv2.normalize for NORM_MINMAX on float32 host arrays - what a histogram goes through before calcBackProject: the stretch onto
     [min(alpha, beta), max(alpha, beta)] in double, rounded once (vision.utils.color.normalize_hist; cv2 takes the same steps in

@@ -1003,6 +1003,84 @@ def track_points(prev, next, pts, next_pts=None, win_size=(21, 21), max_level: i
     return found.reshape(-1, 1, 2), status, err
 
 
+# ---- robust motion estimation from point pairs (libvp vp_model.hip) ------------------------------------------
+MOTION_MODELS = {"similarity": _vp.MODEL_SIMILARITY, "affine": _vp.MODEL_AFFINE, "homography": _vp.MODEL_HOMOGRAPHY}
+MOTION_MAX_POINTS, MOTION_MAX_ITERS = 1 << 20, 65536
+
+
+def _motion_model(model):
+    if model not in MOTION_MODELS:
+        raise ValueError("the model is 'similarity', 'affine' or 'homography'")
+    return MOTION_MODELS[model]
+
+
+def _motion_pairs(src_pts, dst_pts, model, status=None):
+    """the checked (N, 2) float32 pairs of a motion model, lost points left out; no device is needed"""
+    src, dst = _flow_points(src_pts, "the source points"), _flow_points(dst_pts, "the destination points")
+    if len(src) != len(dst):
+        raise ValueError("as many destination points as source points")
+    if status is not None:
+        keep = np.asarray(status).reshape(-1) != 0
+        if len(keep) != len(src):
+            raise ValueError("one status per point pair")
+        src, dst = np.ascontiguousarray(src[keep]), np.ascontiguousarray(dst[keep])
+    if len(src) < model + 2:
+        raise ValueError(f"the model needs at least {model + 2} point pairs")
+    if len(src) > MOTION_MAX_POINTS:
+        raise ValueError("more than 1048576 point pairs are outside the accelerated path")
+    return src, dst
+
+
+def _motion_matrix(model, nine):
+    return nine.reshape(3, 3).copy() if model == _vp.MODEL_HOMOGRAPHY else nine.reshape(3, 3)[:2].copy()
+
+
+def estimate_motion(src_pts, dst_pts, model: str = "similarity", threshold: float = 3.0, max_iters: int = 2000, confidence: float = 0.99, seed: int = 0,
+                    status=None):
+    """The motion between two point sets by RANSAC on the GPU - what cv2.estimateAffinePartial2D ("similarity"), estimateAffine2D
+    ("affine") and findHomography ("homography") make of point pairs (libvp vp_estimate_model_f32).  Returns
+    (M, inliers): M is 2 x 3 float64 for the similarity and the affine model and 3 x 3 for the homography, the least-squares fit to
+    the inlier set of the best hypothesis; inliers is (N,) bool.  (None, None) when there is no model.  The points are (N, 2) or
+    (N, 1, 2), float32 or convertible; status= takes track_points' status and leaves lost points out (inliers then has one entry per
+    kept point).  The result is a function of the arguments alone, bit for bit (tests/model_restate.py): hypothesis j draws its
+    sample from (seed, j), ties go to the lowest j, and the search ends by cv2's rule for `confidence`, checked every 256 hypotheses."""
+    kind = _motion_model(model)
+    threshold, max_iters, confidence, seed = float(threshold), int(max_iters), float(confidence), int(seed)
+    if not (math.isfinite(threshold) and threshold > 0):
+        raise ValueError("the threshold must be finite and above 0")
+    if not 1 <= max_iters <= MOTION_MAX_ITERS:
+        raise ValueError("max_iters must be 1 to 65536")
+    if not 0 < confidence < 1:
+        raise ValueError("the confidence must be above 0 and below 1")
+    if not 0 <= seed < 1 << 32:
+        raise ValueError("the seed is an unsigned 32-bit integer")
+    src, dst = _motion_pairs(src_pts, dst_pts, kind, status)
+    ctx = _vp.default_context()
+    nine, mask = np.empty(9, np.float64), np.empty(len(src), np.uint8)
+    count, taken = _vp.C.c_int(), _vp.C.c_int()
+    _vp.check(_vp.lib().vp_estimate_model_f32(ctx.handle, src.ctypes.data, dst.ctypes.data, len(src), kind, threshold, max_iters, confidence, seed, nine.ctypes.data,
+                                              mask.ctypes.data, _vp.C.addressof(count), _vp.C.addressof(taken)), ctx.handle)
+    if count.value == 0:
+        return None, None
+    return _motion_matrix(kind, nine), mask != 0
+
+
+def refit_motion(src_pts, dst_pts, model: str = "similarity", mask=None):
+    """The plain least-squares model over the pairs whose mask entry is not 0 (all without a mask), in double on the host in index
+    order (libvp vp_model_refit): 2 x 3 or 3 x 3 float64, or None when the points do not determine the model."""
+    kind = _motion_model(model)
+    src, dst = _motion_pairs(src_pts, dst_pts, kind)
+    if mask is not None:
+        mask = np.ascontiguousarray(np.asarray(mask).reshape(-1) != 0, np.uint8)
+        if len(mask) != len(src):
+            raise ValueError("one mask entry per point pair")
+    nine = np.empty(9, np.float64)
+    rc = _vp.lib().vp_model_refit(src.ctypes.data, dst.ctypes.data, len(src), None if mask is None else mask.ctypes.data, kind, nine.ctypes.data)
+    if rc < 0:
+        _vp.check(rc)
+    return _motion_matrix(kind, nine) if rc == 1 else None
+
+
 def hough_circles(mat, dp: float, min_dist: float, param1: float = 100, param2: float = 100, min_radius: int = 0, max_radius: int = 0):
     """cv2.HoughCircles(mat, cv2.HOUGH_GRADIENT, dp, min_dist, None, param1, param2, min_radius, max_radius) on the GPU (libvp
     vp_hough_circles_*): (1, N, 3) float32 (x, y, r) in cv2's order, or None when no circle is found.  A device image is read where it

@@ -918,6 +918,38 @@ int vp_lk_flow_dev(vp_ctx* ctx, const uint8_t* const* prev_levels, const size_t*
 int vp_lk_flow_u8(vp_ctx* ctx, const uint8_t* prev_host, const uint8_t* next_host, int w, int h, const float* prev_pts_host, const float* init_pts_host, int n,
                   int win_w, int win_h, int max_level, int max_count, double eps, int flags, double min_eig_threshold, void* out_host);
 
+/* ---- robust motion estimation from point pairs: cv2.findHomography, estimateAffine2D, estimateAffinePartial2D --------------------- *
+ * RANSAC over n pairs src[i] -> dst[i] of float32 (x, y).  The contract is the statement
+ * tests/model_restate.py, reproduced bit for bit, not cv2's random sequence: hypothesis j draws its 2 / 3 / 4 distinct indices from a
+ * counter-based function of (seed, j); degenerate samples are void; the minimal solvers, the squared reprojection distance and the
+ * test err <= threshold^2 run in double in one written order; the score is the integer inlier count, ties go to the lowest j.
+ * Hypotheses are taken in rounds of vp_model_round_size(); after round r the search stops once the best count has reached the r-th
+ * entry of the stop table (cv2's RANSACUpdateNumIters, computed on the host), at the latest at max_iters.  inliers (n bytes of 0 / 1,
+ * nullable) is the inlier set of the best hypothesis; model_out (nine doubles, a row-major 3 x 3 whose last row is 0 0 1 for the
+ * similarity and the affine model) is the least-squares refit over that set, made on the host in index order.  *n_inliers is 0, and
+ * model_out and inliers are zeros, when there is no model; *n_hypotheses is the number of hypotheses taken.
+ * vp_estimate_model_f32 stages host points; vp_estimate_model_dev reads two device arrays (8-byte aligned); both enqueue every round
+ * at once and synchronise once.  vp_estimate_model_host is the same statement as a host loop: no device, no context.
+ * vp_model_hypothesis: hypothesis j as the kernel forms it - sample (four indices, -1 where unused) and its nine doubles; returns 1,
+ *   or 0 for a void hypothesis (zeros).  vp_model_stop_table: the table, `capacity` at least ceil(max_iters / round size) entries.
+ * vp_model_refit: the refit alone over the points whose mask byte is not 0 (mask NULL: all); returns 1, or 0 when there is no model.
+ * vp_model_stage_points: the points a scoring block stages at once.
+ * Refused with VP_ERR_INVALID before anything is launched or written (the message names the reason): a missing pointer, an unknown
+ *   model, n below the model's sample size or above 2^20, a threshold that is not finite and above 0, max_iters outside 1..65536, a
+ *   confidence outside (0, 1), device points that are not 8-byte aligned, a hypothesis index outside 0..65535, a table too short. */
+enum { VP_MODEL_SIMILARITY = 0, VP_MODEL_AFFINE = 1, VP_MODEL_HOMOGRAPHY = 2 };
+int vp_model_round_size(void);
+int vp_model_stage_points(void);
+int vp_estimate_model_f32(vp_ctx* ctx, const float* src_host, const float* dst_host, int n, int model, double threshold, int max_iters, double confidence,
+                          uint32_t seed, double* model_out, uint8_t* inliers_host, int* n_inliers, int* n_hypotheses);
+int vp_estimate_model_dev(vp_ctx* ctx, const float* src_dev, const float* dst_dev, int n, int model, double threshold, int max_iters, double confidence,
+                          uint32_t seed, double* model_out, uint8_t* inliers_host, int* n_inliers, int* n_hypotheses);
+int vp_estimate_model_host(const float* src, const float* dst, int n, int model, double threshold, int max_iters, double confidence, uint32_t seed,
+                           double* model_out, uint8_t* inliers, int* n_inliers, int* n_hypotheses);
+int vp_model_hypothesis(const float* src, const float* dst, int n, int model, uint32_t seed, int j, int32_t* sample, double* model_out);
+int vp_model_stop_table(int n, int model, double confidence, int max_iters, int32_t* need, int capacity, int* rounds);
+int vp_model_refit(const float* src, const float* dst, int n, const uint8_t* mask, int model, double* model_out);
+
 /* ---- device memory helpers (so a host program needs no HIP binding of its own) --------- */
 int vp_dev_alloc(vp_ctx* ctx, size_t bytes, void** dev_ptr);
 int vp_dev_free(vp_ctx* ctx, void* dev_ptr);    /* ctx may be NULL (memory that outlived its context) */
