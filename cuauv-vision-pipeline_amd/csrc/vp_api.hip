@@ -167,6 +167,7 @@ int vp_destroy(vp_ctx* ctx)
     vp_contours_teardown(ctx);
     vp_hough_circles_teardown(ctx);
     vp_adaptive_teardown(ctx);
+    vp_features_teardown(ctx);
     if (ctx->ws) (void)hipFree(ctx->ws);
     for (int i = 0; i < 4; i++) {
         if (ctx->ring_buf[i]) (void)hipHostFree(ctx->ring_buf[i]);

@@ -115,6 +115,10 @@ struct vp_balance_state {     // colour balance (vp_balance.hip)
     u32* folds_own;               // context-owned device word the counter is copied to (the workspace it is made in is carved anew per call); lives behind d_tables
 };
 
+struct vp_features_state {    // descriptors (vp_api_features.hip)
+    int8_t* pattern;              // the 32 steered patterns followed by the blur's taps, uploaded on the first describe call
+};
+
 struct vp_ctx : vp_runtime {
     vp_options opt;               // indexed by VP_OPT_* (vp_options.h); written by vp_create and vp_set_option only
     vp_chain_state chain;
@@ -124,6 +128,7 @@ struct vp_ctx : vp_runtime {
     vp_agauss_state agauss;
     vp_post_state post;
     vp_balance_state cb;
+    vp_features_state ft;
 };
 
 // brackets one kernel launch with events when profiling is on
@@ -151,6 +156,7 @@ void vp_ccl_teardown(vp_ctx* ctx);                         // vp_ccl.hip (vp_ccl
 void vp_contours_teardown(vp_ctx* ctx);                    // vp_contours.inl
 void vp_hough_circles_teardown(vp_ctx* ctx);               // vp_hough_circles.hip
 void vp_adaptive_teardown(vp_ctx* ctx);                    // vp_adaptive.hip
+void vp_features_teardown(vp_ctx* ctx);                    // vp_api_features.hip
 
 // ---- workspace ---------------------------------------------------------------------------
 int vp_ws_reserve(vp_ctx* ctx, size_t bytes);               // may reallocate (synchronises)
@@ -353,6 +359,20 @@ struct vp_lk_levels;
 struct vp_lk_plan;
 int vpk_lk_flow(vp_ctx* ctx, const vp_lk_levels& L, const vp_lk_plan& P, int win_w, int win_h, int max_count, double eps2, int flags, double min_eig,
                 const float* d_pts, const float* d_guess, u32* d_out);
+
+// ---- features (vp_features.hip; the plan: vp_features_plan.h) ---------------------------------------------------------
+// FAST-9, the steered binary descriptor and the Hamming matcher for arguments the plan header's checks admitted and the plans made of
+// them; all enqueued.  vpk_fast: four launches; the count and the first P.out_cap corners in raster order are left in d_ws at the
+// plan's offsets.  vpk_describe: one wave per point; d_blur is the packed 7 x 7 blur of the source.  vpk_hamming_knn: the best k <= 2
+// train rows of every query by (distance, index); d_partial: P.partial_bytes.  vpk_hamming_cross: clears the matches that are not mutual.
+struct vp_fast_plan;
+struct vp_hamming_plan_t;
+int vpk_fast(vp_ctx* ctx, const uint8_t* d_src, size_t stride, int w, int h, int threshold, int nonmax, const vp_fast_plan& P, uint8_t* d_ws);
+int vpk_describe(vp_ctx* ctx, const uint8_t* d_src, size_t stride, const uint8_t* d_blur, int w, int h, const float* d_pts, int n, const int8_t* d_pattern,
+                 unsigned grid, uint8_t* d_desc, uint8_t* d_bin, uint8_t* d_status);
+int vpk_hamming_knn(vp_ctx* ctx, const uint8_t* d_q, size_t qstride, int nq, const uint8_t* d_t, size_t tstride, int nt, const vp_hamming_plan_t& P, int k,
+                    int32_t* d_idx, int32_t* d_dist, void* d_partial);
+int vpk_hamming_cross(vp_ctx* ctx, int32_t* d_idx, const int32_t* d_rev, int nq);
 
 // ---- morphology (vp_morph.hip; the plan: vp_morph_plan.h, with vp_bitstage, vp_bitplan and vp_ww) --------------
 // u8 (non-zero = 1) -> bits; d_flags[0] |= 1 if any byte is neither 0 nor 255

@@ -1501,6 +1501,85 @@ def convexHull(points, hull=None, clockwise=False, returnPoints=True):
     return out.astype(p.dtype if p.dtype.kind in "iuf" else np.float64)
 
 
+# ---- keypoints, FAST, brute-force Hamming matching (vision.utils.feature) ---------------------------------
+NORM_HAMMING = 6
+FAST_FEATURE_DETECTOR_TYPE_9_16 = 2
+
+
+class KeyPoint:
+    """cv2.KeyPoint: pt (x, y), size, angle (-1: none), response, octave, class_id."""
+    __slots__ = ("pt", "size", "angle", "response", "octave", "class_id")
+
+    def __init__(self, x=0.0, y=0.0, size=0.0, angle=-1.0, response=0.0, octave=0, class_id=-1):
+        self.pt, self.size, self.angle, self.response, self.octave, self.class_id = (float(x), float(y)), float(size), float(angle), float(response), int(octave), int(class_id)
+
+    def __repr__(self):
+        return f"KeyPoint(pt={self.pt}, size={self.size}, angle={self.angle}, response={self.response})"
+
+
+class DMatch:
+    """cv2.DMatch: queryIdx, trainIdx, imgIdx, distance."""
+    __slots__ = ("queryIdx", "trainIdx", "imgIdx", "distance")
+
+    def __init__(self, queryIdx=-1, trainIdx=-1, imgIdx=-1, distance=float("inf")):
+        self.queryIdx, self.trainIdx, self.imgIdx, self.distance = int(queryIdx), int(trainIdx), int(imgIdx), float(distance)
+
+    def __repr__(self):
+        return f"DMatch(queryIdx={self.queryIdx}, trainIdx={self.trainIdx}, distance={self.distance})"
+
+
+KEYPOINT_SIZE = 7.0      # the diameter of the FAST ring, as cv2 reports it
+
+
+def keypoints_of(pts, scores):
+    """the KeyPoint list of fast_corners' arrays: size 7, angle -1, response the score"""
+    return [KeyPoint(float(p[0]), float(p[1]), KEYPOINT_SIZE, -1.0, float(s), 0, -1) for p, s in zip(pts, scores)]
+
+
+class FastFeatureDetector:
+    """cv2.FastFeatureDetector for TYPE_9_16 (vision.utils.feature.fast_corners)."""
+
+    def __init__(self, threshold, nonmaxSuppression, type):
+        if type != FAST_FEATURE_DETECTOR_TYPE_9_16:
+            raise error("FastFeatureDetector_create: only TYPE_9_16 is on the accelerated path (DESIGN.md section 7)")
+        self.threshold, self.nonmax = threshold, bool(nonmaxSuppression)
+
+    def detect(self, image, mask=None):
+        if mask is not None:
+            raise error("FastFeatureDetector.detect: a mask is outside the accelerated path (DESIGN.md section 7)")
+        pts, scores = _gather("FastFeatureDetector.detect", _feature.fast_corners, image, self.threshold, self.nonmax)
+        return keypoints_of(pts, scores)
+
+
+def FastFeatureDetector_create(threshold=10, nonmaxSuppression=True, type=FAST_FEATURE_DETECTOR_TYPE_9_16):
+    return FastFeatureDetector(threshold, nonmaxSuppression, type)
+
+
+class BFMatcher:
+    """cv2.BFMatcher for NORM_HAMMING on uint8 descriptors (vision.utils.feature.match_descriptors): ties between equal distances go
+    to the lower train index.  cv2's default NORM_L2 is not served: a float descriptor has no producer here."""
+
+    def __init__(self, normType=NORM_L2, crossCheck=False):
+        if normType != NORM_HAMMING:
+            raise error("BFMatcher: only NORM_HAMMING is on the accelerated path; pass it explicitly (DESIGN.md section 7)")
+        self.crossCheck = bool(crossCheck)
+
+    def knnMatch(self, queryDescriptors, trainDescriptors, k, mask=None, compactResult=False):
+        if mask is not None:
+            raise error("BFMatcher.knnMatch: a mask is outside the accelerated path")
+        if k > 2:
+            raise error("BFMatcher.knnMatch: k above 2 is outside the accelerated path (DESIGN.md section 7)")
+        idx, dist = _gather("BFMatcher.knnMatch", _feature.match_descriptors, queryDescriptors, trainDescriptors, k, self.crossCheck)
+        return [[DMatch(q, int(j), 0, float(d)) for j, d in zip(idx[q], dist[q]) if j >= 0] for q in range(len(idx))]
+
+    def match(self, queryDescriptors, trainDescriptors, mask=None):
+        return [m[0] for m in self.knnMatch(queryDescriptors, trainDescriptors, 1, mask) if m]
+
+
+def BFMatcher_create(normType=NORM_L2, crossCheck=False):
+    return BFMatcher(normType, crossCheck)
+
+
 def install():
     """Registers this facade as `cv2` when no real OpenCV is importable.  Returns the module that `import cv2` yields.  Every public
     name of this module is then cv2's: the shape descriptors `moments` and `HuMoments` (vision_common.py:131-132) among them."""

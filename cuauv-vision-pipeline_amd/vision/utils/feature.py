@@ -1081,6 +1081,144 @@ def refit_motion(src_pts, dst_pts, model: str = "similarity", mask=None):
     return _motion_matrix(kind, nine) if rc == 1 else None
 
 
+# ---- FAST corners, steered binary descriptors, Hamming matching (libvp vp_features.hip) ----------------------
+FEATURE_MAX_SIDE, FEATURE_MAX_PIXELS, FEATURE_MAX_POINTS = 65535, 1 << 28, 1 << 20
+FAST_MIN_SIDE, DESCRIBE_MIN_SIDE, DESCRIPTOR_BYTES = 7, 31, 32
+HAMMING_MAX_BYTES, HAMMING_MAX_ROWS = 128, 1 << 20
+_fast_cap = threading.local()
+
+
+def _feature_image(mat, name, min_side):
+    mat, _ = image_source(mat, single=f"{name} takes a single-channel image", max_side=FEATURE_MAX_SIDE)
+    h, w = mat.shape
+    if min(h, w) < min_side:
+        raise ValueError(f"{name}: width and height must be at least {min_side}")
+    if h * w > FEATURE_MAX_PIXELS:
+        raise ValueError(f"{name}: more than 2^28 pixels are outside the accelerated path")
+    return mat
+
+
+def _image_call(mat, host_entry, dev_entry):
+    """(ctx, entry, source pointer) of an operator whose results come back as host arrays whichever kind the image is"""
+    ctx = _vp.default_context()
+    if isinstance(mat, DeviceMat):
+        mat.refresh_device(ctx)
+        return ctx, dev_entry, mat.dev_ptr, mat
+    mat = np.ascontiguousarray(mat)
+    return ctx, host_entry, mat.ctypes.data, mat
+
+
+def fast_corners(mat, threshold: int = 10, nonmax: bool = True, max_points=None):
+    """cv2.FastFeatureDetector_create(threshold, nonmax, TYPE_9_16).detect on a uint8 single-channel image (numpy, or a DeviceMat that
+    stays in HBM): (pts float32 (n, 2) of (x, y), scores int32 (n,)) in raster order - y, then x.  A pixel at least 3 from every border
+    is a corner when nine contiguous pixels of its radius-3 ring are all brighter than it by more than `threshold`, or all darker; its
+    score is the largest threshold at which it still is one.  nonmax keeps the corners whose score is strictly above that of all eight
+    neighbours (two adjacent corners of equal score both go); without it every corner is kept and scores 0.  max_points keeps the
+    highest scores, ties to the earlier raster position, and the result is in raster order again.  DESIGN.md section 4.31."""
+    mat = _feature_image(mat, "fast_corners", FAST_MIN_SIDE)
+    threshold = int(threshold)
+    if not 0 <= threshold <= 255:
+        raise ValueError("the threshold must be 0 to 255")
+    if max_points is not None:
+        max_points = int(max_points)
+        if max_points < 0:
+            raise ValueError("max_points must be at least 0")
+    h, w = mat.shape
+    lib = _vp.lib()
+    ctx, entry, src, mat = _image_call(mat, lib.vp_fast_u8, lib.vp_fast_dev)
+    cap = getattr(_fast_cap, "n", 4096)
+    while True:
+        xy, val = np.empty((max(cap, 1), 2), np.int32), np.empty(max(cap, 1), np.int32)
+        n = _vp.C.c_int(0)
+        _vp.check(entry(ctx.handle, src, w, w, h, threshold, int(bool(nonmax)), xy.ctypes.data, val.ctypes.data, cap, _vp.C.addressof(n)), ctx.handle)
+        if n.value <= cap:
+            break
+        cap = _fast_cap.n = n.value                    # the true count came back: once more with room for all of them
+    xy, val = xy[:n.value], val[:n.value]
+    if max_points is not None and n.value > max_points:
+        keep = np.sort(np.argsort(-val.astype(np.int64), kind="stable")[:max_points])
+        xy, val = xy[keep], val[keep]
+    return xy.astype(np.float32), val.copy()
+
+
+def describe_points(mat, pts):
+    """The library's 256-bit binary descriptor of the points `pts` ((N, 2) or (N, 1, 2), (x, y)) of a uint8 single-channel image (numpy,
+    or a DeviceMat that stays in HBM): (kept_pts float32 (m, 2), desc uint8 (m, 32), kept_index (m,)).  A point is rounded to its
+    pixel; points closer than 15 to a border, or not finite, are dropped, as cv2's `compute` drops them - kept_index says which stayed.
+    Orientation: the intensity centroid over the disc of radius 15, quantised to 32 directions in integers; bits: 256 comparisons of
+    the 7 x 7 Gaussian blur (sigma 2) at pattern points steered to that direction.  Not cv2.ORB's bits: the pattern is this library's
+    (DESIGN.md section 4.31).  Tolerates in-plane rotation and small changes of scale; single scale."""
+    mat = _feature_image(mat, "describe_points", DESCRIBE_MIN_SIDE)
+    pts = _flow_points(pts, "the points")
+    n = len(pts)
+    if n > FEATURE_MAX_POINTS:
+        raise ValueError("more than 1048576 points are outside the accelerated path")
+    if n == 0:
+        return np.empty((0, 2), np.float32), np.empty((0, DESCRIPTOR_BYTES), np.uint8), np.empty(0, np.intp)
+    h, w = mat.shape
+    lib = _vp.lib()
+    ctx, entry, src, mat = _image_call(mat, lib.vp_describe_u8, lib.vp_describe_dev)
+    desc, bins, status = np.empty((n, DESCRIPTOR_BYTES), np.uint8), np.empty(n, np.uint8), np.empty(n, np.uint8)
+    _vp.check(entry(ctx.handle, src, w, w, h, pts.ctypes.data, n, desc.ctypes.data, bins.ctypes.data, status.ctypes.data), ctx.handle)
+    keep = np.flatnonzero(status)
+    return pts[keep], desc[keep], keep
+
+
+def _descriptors(a, what):
+    a = to_host_readonly(as_mat(a))
+    if not isinstance(a, np.ndarray) or a.dtype != np.uint8 or a.ndim != 2:
+        raise TypeError(f"{what} must be a uint8 (n, D) array")
+    return a
+
+
+def match_descriptors(query, train, k: int = 2, cross_check: bool = False):
+    """cv2.BFMatcher(NORM_HAMMING, crossCheck).knnMatch(query, train, k) as arrays: (idx int32 (nq, k), dist int32 (nq, k)).  For each
+    query row the train rows are ordered by (Hamming distance, index) and the first k taken; -1 / -1 where there are fewer than k.
+    cross_check (k = 1): idx is -1 where the train row's own best query, by (distance, query index), is another one.  uint8 (n, D)
+    arrays, D up to 128 bytes (rows are zero-padded to a multiple of 8, which leaves distances unchanged).  libvp vp_hamming_knn_u8."""
+    query, train = _descriptors(query, "the query descriptors"), _descriptors(train, "the train descriptors")
+    k = int(k)
+    if k not in (1, 2):
+        raise ValueError("k must be 1 or 2")
+    if cross_check and k != 1:
+        raise ValueError("cross_check goes with k = 1")
+    nq, nt = len(query), len(train)
+    D = query.shape[1] if nq or not nt else train.shape[1]
+    if nq and nt and train.shape[1] != D:
+        raise ValueError("query and train descriptors must have the same length")
+    if not 1 <= D <= HAMMING_MAX_BYTES:
+        raise ValueError("descriptors of 1 to 128 bytes")
+    if max(nq, nt) > HAMMING_MAX_ROWS:
+        raise ValueError("more than 1048576 descriptors are outside the accelerated path")
+    idx, dist = np.full((nq, k), -1, np.int32), np.full((nq, k), -1, np.int32)
+    if nq == 0 or nt == 0:
+        return idx, dist
+    Dp = (D + 7) // 8 * 8
+
+    def rows(a):
+        if Dp == D:
+            return np.ascontiguousarray(a)
+        out = np.zeros((len(a), Dp), np.uint8)
+        out[:, :D] = a
+        return out
+    q, t = rows(query), rows(train)
+    ctx = _vp.default_context()
+    _vp.check(_vp.lib().vp_hamming_knn_u8(ctx.handle, q.ctypes.data, Dp, nq, t.ctypes.data, Dp, nt, Dp, k, int(bool(cross_check)), idx.ctypes.data, dist.ctypes.data),
+              ctx.handle)
+    return idx, dist
+
+
+def ratio_test(idx, dist, ratio: float = 0.7):
+    """Lowe's ratio test on match_descriptors(k=2): (query indices, train indices) of the rows with dist[:, 0] < ratio * dist[:, 1] in
+    float64.  Rows without a second neighbour are dropped."""
+    idx, dist = np.asarray(idx), np.asarray(dist)
+    if idx.ndim != 2 or idx.shape[1] != 2 or dist.shape != idx.shape:
+        raise ValueError("the ratio test takes (n, 2) indices and distances")
+    keep = (idx[:, 0] >= 0) & (idx[:, 1] >= 0) & (dist[:, 0].astype(np.float64) < float(ratio) * dist[:, 1].astype(np.float64))
+    q = np.flatnonzero(keep)
+    return q, idx[q, 0].astype(np.intp)
+
+
 def hough_circles(mat, dp: float, min_dist: float, param1: float = 100, param2: float = 100, min_radius: int = 0, max_radius: int = 0):
     """cv2.HoughCircles(mat, cv2.HOUGH_GRADIENT, dp, min_dist, None, param1, param2, min_radius, max_radius) on the GPU (libvp
     vp_hough_circles_*): (1, N, 3) float32 (x, y, r) in cv2's order, or None when no circle is found.  A device image is read where it

@@ -950,6 +950,51 @@ int vp_model_hypothesis(const float* src, const float* dst, int n, int model, ui
 int vp_model_stop_table(int n, int model, double confidence, int max_iters, int32_t* need, int capacity, int* rounds);
 int vp_model_refit(const float* src, const float* dst, int n, const uint8_t* mask, int model, double* model_out);
 
+/* ---- features: FAST-9 corners, a steered 256-bit binary descriptor, brute-force Hamming matching ------------------------------------
+ * What utils/sift.py needs in front of vp_estimate_model_*: detect, describe, match.  All integer arithmetic, byte for byte against
+ * tests/features_restate.py; DESIGN.md section 4.31.  Images are uint8, single channel, rows of `stride` bytes.
+ * vp_fast_*: cv2.FastFeatureDetector_create(threshold, nonmax, TYPE_9_16).detect on a w x h image, w, h >= 7.  Ring: the 16 pixels of
+ *   the radius-3 circle in the order (0,3) (1,3) (2,2) (3,1) (3,0) (3,-1) ... (-1,3) as (dx, dy).  M of a pixel with
+ *   3 <= x <= w - 4, 3 <= y <= h - 4: the maximum, over the 16 cyclic arcs of 9 contiguous ring pixels and both signs s, of the arc's
+ *   minimum of s (centre - ring).  Corner iff M > threshold (0..255); score M - 1.  nonmax != 0: a corner is kept iff its score is
+ *   strictly above the score of each of its eight neighbours (a non-corner scores 0), and reports its score; nonmax == 0: every corner
+ *   is kept and reports 0.  *n_found is the number kept; the first min(*n_found, capacity) in raster order (y, then x) are written as
+ *   (x, y) pairs to xy_host and scores to score_host, both host arrays; capacity 0 with NULL arrays counts.  Synchronises.
+ * vp_describe_*: the library's own descriptor of n points (host float32 (x, y) pairs, both forms) on a w x h image, w, h >= 31.  A point
+ *   is rounded to the pixel p = floor((double)v + 0.5); closer than 15 to a border, or not finite: status 0, bin 0, 32 zero bytes.
+ *   Otherwise status 1; m10 = sum dx I(p + d), m01 = sum dy I(p + d) over dx dx + dy dy <= 225; bin = the k in 0..31 that maximises
+ *   m10 C[k] + m01 S[k] in 64-bit integers (C, S: 16384 cos / sin(2 pi k / 32) rounded half away from zero; ties to the lowest k);
+ *   bit i = B(p + a'_i) < B(p + b'_i), B the 7 x 7 GaussianBlur of the image at sigma 2 (BORDER_REFLECT_101) made in the workspace,
+ *   (a'_i, b'_i) pair i of the pattern steered to the bin; test 8 j + b is bit b of byte j.  desc (n x 32), bin (n), status (n) are
+ *   host arrays.  Synchronises.
+ * vp_describe_pattern: the table of 32 x 256 x 4 int8 (bin, pair, ax ay bx by); no device, no context.  Base pairs: coordinates
+ *   d1 + d2 - 10 from consecutive draws d = (s >> 16) % 11 of s <- s 1664525 + 1013904223 (mod 2^32, from 0x9E3779B9, advanced before
+ *   each draw), four per candidate in the order ax ay bx by; a == b or a pair already taken (either order) is dropped; 256 are kept.
+ *   Steering: x' = rdiv(x C[k] - y S[k]), y' = rdiv(x S[k] + y C[k]), rdiv(v) = sign(v) ((|v| + 8192) >> 14).
+ * vp_hamming_knn_*: cv2.BFMatcher(NORM_HAMMING).knnMatch of (nq, D) query against (nt, D) train descriptors, D a multiple of 8 in
+ *   8..128, strides at least D and multiples of 8, k 1 or 2: for each query the first k train rows by (distance, index) ascending into
+ *   idx and dist, both (nq, k) int32; entries beyond nt are -1 / -1.  cross_check (k = 1): idx becomes -1 where the train row's best
+ *   query by (distance, query index) is another one (dist stays).  nq or nt of 0 launches nothing.  _u8: host arrays in and out,
+ *   synchronises; _dev: device arrays in (8-byte aligned) and out (4-byte aligned), enqueued.
+ * vp_hamming_plan: the grid the matcher uses - blocks of 256 queries, and the number of splits of the train set (more than one when
+ *   the query blocks alone would not fill the device); no device, no context.
+ * Refused with VP_ERR_INVALID before anything is launched or written (the message names the reason): a missing pointer, a side
+ *   below 7 (FAST) or 31 (describe) or above 65535, more than 2^28 pixels, a stride below the row, a threshold outside 0..255, a
+ *   negative capacity or count, more than 2^20 points or rows, D not a multiple of 8 or outside 8..128, a matcher stride that is
+ *   not a multiple of 8, k outside 1..2, cross_check with k = 2, misaligned device arrays. */
+int vp_fast_u8(vp_ctx* ctx, const uint8_t* src, size_t stride, int w, int h, int threshold, int nonmax, int32_t* xy_host, int32_t* score_host, int capacity,
+               int* n_found);
+int vp_fast_dev(vp_ctx* ctx, const uint8_t* src_dev, size_t stride, int w, int h, int threshold, int nonmax, int32_t* xy_host, int32_t* score_host, int capacity,
+                int* n_found);
+int vp_describe_pattern(int8_t* out);
+int vp_describe_u8(vp_ctx* ctx, const uint8_t* src, size_t stride, int w, int h, const float* pts, int n, uint8_t* desc, uint8_t* bin, uint8_t* status);
+int vp_describe_dev(vp_ctx* ctx, const uint8_t* src_dev, size_t stride, int w, int h, const float* pts, int n, uint8_t* desc, uint8_t* bin, uint8_t* status);
+int vp_hamming_plan(int nq, int nt, int D, int* query_tiles, int* train_splits);
+int vp_hamming_knn_u8(vp_ctx* ctx, const uint8_t* query, size_t query_stride, int nq, const uint8_t* train, size_t train_stride, int nt, int D, int k,
+                      int cross_check, int32_t* idx, int32_t* dist);
+int vp_hamming_knn_dev(vp_ctx* ctx, const uint8_t* query_dev, size_t query_stride, int nq, const uint8_t* train_dev, size_t train_stride, int nt, int D, int k,
+                       int cross_check, int32_t* idx_dev, int32_t* dist_dev);
+
 /* ---- device memory helpers (so a host program needs no HIP binding of its own) --------- */
 int vp_dev_alloc(vp_ctx* ctx, size_t bytes, void** dev_ptr);
 int vp_dev_free(vp_ctx* ctx, void* dev_ptr);    /* ctx may be NULL (memory that outlived its context) */
