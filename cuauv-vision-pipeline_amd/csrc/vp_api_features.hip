@@ -87,6 +87,64 @@ int describe_run(vp_ctx* ctx, const uint8_t* d_src, size_t stride, int w, int h,
     return vp_synchronize(ctx);
 }
 
+// Level 0 from d_src (device rows of stride bytes) or h_src (host rows), the other levels by the resize kernel, each from the one
+// before, every level's B by the two-pass blur; then vpk_pyr_features, whose launches do not depend on the number of levels; the whole
+// capacity of every list comes back, so the one synchronisation is the last thing queued.  P: at least one level, capacity >= 1.
+int pyr_run(vp_ctx* ctx, const uint8_t* d_src, const uint8_t* h_src, size_t stride, int w, int h, int threshold, const vp_pyr_plan& P, float* xy0_host, int32_t* lxy_host,
+            int32_t* score_host, uint8_t* bin_host, uint8_t* desc_host, uint8_t* desc_dev, int* n_found)
+{
+    VP_TRY(ft_pattern_ready(ctx));
+    const uint16_t* d_taps = reinterpret_cast<const uint16_t*>(ctx->ft.pattern + FT_PATTERN_BYTES);
+    VP_TRY(vp_ws_reserve(ctx, P.ws_bytes + 1024));
+    TAKE(d_ws, uint8_t*, P.ws_bytes);
+    const vp_pyr_table& T = P.T;
+    uint8_t* d_img = d_ws + P.off_img;
+    if (h_src) {
+        VP_TRY(h2d_rows(ctx, d_img, (size_t)w, h_src, stride, (size_t)w, h));
+    } else {
+        VP_HIP(ctx, hipMemcpy2DAsync(d_img, (size_t)w, d_src, stride, (size_t)w, h, hipMemcpyDeviceToDevice, ctx->stream));
+    }
+    for (int l = 1; l < T.n_levels; l++) {
+        const vp_pyr_level &A = T.L[l - 1], &B = T.L[l];
+        VP_TRY(vpk_resize_u8(ctx, d_img + A.off, A.w, A.h, 1, B.w, B.h, (double)B.w / A.w, (double)B.h / A.h, d_img + B.off));
+    }
+    for (int l = 0; l < T.n_levels; l++)
+        VP_TRY(vpk_gaussian_blur(ctx, d_img + T.L[l].off, T.L[l].w, T.L[l].h, 1, d_taps, FT_BLUR_K, FT_BLUR_K, reinterpret_cast<uint16_t*>(d_ws + P.off_tmp),
+                                 d_ws + P.off_blur + T.L[l].off));
+    uint8_t* d_desc = desc_dev ? desc_dev : d_ws + P.off_desc;
+    VP_TRY(vpk_pyr_features(ctx, P, threshold, ctx->ft.pattern, d_ws, d_desc));
+    u32* hs = (u32*)vp_hstage(ctx, 16);
+    if (!hs) return vp_fail(ctx, VP_ERR_NOMEM, "pinned staging");
+    VP_TRY(d2h(ctx, hs, d_ws + P.off_gt + P.chunks * 4, 4));
+    VP_TRY(d2h(ctx, lxy_host, d_ws + P.off_lxy, P.cap * 12));
+    VP_TRY(d2h(ctx, score_host, d_ws + P.off_val, P.cap * 4));
+    VP_TRY(d2h(ctx, bin_host, d_ws + P.off_bin, P.cap));
+    VP_TRY(d2h(ctx, desc_host, d_desc, P.cap * FT_DESC_BYTES));
+    VP_TRY(vp_synchronize(ctx));
+    const size_t n = hs[0];
+    if (n > P.cap) return vp_fail(ctx, VP_ERR_HIP, "pyramid features: point count above the capacity");
+    for (size_t i = 0; i < n; i++) {
+        const int32_t l = lxy_host[3 * i];
+        if (l < 0 || l >= T.n_levels) return vp_fail(ctx, VP_ERR_HIP, "pyramid features: a point's level is outside the pyramid");
+        // level 0 coordinates in double, in this order, rounded to float32 once (the compile has no contraction)
+        xy0_host[2 * i] = (float)(((double)lxy_host[3 * i + 1] + 0.5) * ((double)w / T.L[l].w) - 0.5);
+        xy0_host[2 * i + 1] = (float)(((double)lxy_host[3 * i + 2] + 0.5) * ((double)h / T.L[l].h) - 0.5);
+    }
+    *n_found = (int)n;
+    return VP_OK;
+}
+
+// what both forms of vp_pyr_features_* check before they need a device; *P is made when NULL comes back
+const char* pyr_checks(const void* src, size_t stride, int w, int h, int levels, int threshold, int max_points, const float* xy0, const int32_t* lxy, const int32_t* score,
+                       const uint8_t* bin, const uint8_t* desc, const uint8_t* desc_dev, const int* n_found, vp_pyr_plan* P)
+{
+    if (!src || !n_found || (max_points > 0 && (!xy0 || !lxy || !score || !bin || !desc))) return "pyramid features: a pointer is missing";
+    if (const char* why = vp_pyr_refusal(w, h, stride, levels, threshold, max_points)) return why;
+    if ((uintptr_t)desc_dev % 8) return "pyramid features: the device descriptors must be 8-byte aligned";
+    vp_pyr_make_plan(w, h, levels, max_points, P);
+    return nullptr;
+}
+
 // workspace of a matcher call beyond what the caller stages: the partial results of both directions and the reverse matches
 size_t hamming_ws_bytes(const vp_hamming_plan_t& P, const vp_hamming_plan_t& R, int nt, int cross_check)
 {
@@ -190,6 +248,45 @@ int vp_describe_dev(vp_ctx* ctx, const uint8_t* d_src, size_t stride, int w, int
     VP_TRY(vp_ws_reserve(ctx, P.ws_bytes + 1024));
     TAKE(d_ws, uint8_t*, P.ws_bytes);
     return describe_run(ctx, d_src, stride, w, h, pts, n, P, d_ws, desc, bin, status);
+}
+
+int vp_pyr_features_plan(int w, int h, int levels, int max_points, int* n_levels, int32_t* level_wh, int32_t* quota)
+{
+    if (!n_levels || !level_wh || !quota) return vp_fail(nullptr, VP_ERR_INVALID, "vp_pyr_features_plan: a pointer is missing");
+    if (const char* why = vp_pyr_refusal(w, h, (size_t)(w > 0 ? w : 0), levels, 0, max_points)) return vp_fail(nullptr, VP_ERR_INVALID, why);
+    vp_pyr_plan P;
+    vp_pyr_make_plan(w, h, levels, max_points, &P);
+    *n_levels = P.T.n_levels;
+    for (int l = 0; l < P.T.n_levels; l++) {
+        level_wh[2 * l] = P.T.L[l].w;
+        level_wh[2 * l + 1] = P.T.L[l].h;
+        quota[l] = (int32_t)P.T.L[l].quota;
+    }
+    return VP_OK;
+}
+
+int vp_pyr_features_u8(vp_ctx* ctx, const uint8_t* src, size_t stride, int w, int h, int levels, int threshold, int max_points, float* xy0_host, int32_t* lxy_host,
+                       int32_t* score_host, uint8_t* bin_host, uint8_t* desc_host, uint8_t* desc_dev, int* n_found)
+{
+    vp_pyr_plan P;
+    if (const char* why = pyr_checks(src, stride, w, h, levels, threshold, max_points, xy0_host, lxy_host, score_host, bin_host, desc_host, desc_dev, n_found, &P))
+        return vp_fail(ctx, VP_ERR_INVALID, why);
+    VP_TRY(check_ctx(ctx));
+    *n_found = 0;
+    if (max_points == 0 || P.T.n_levels == 0) return VP_OK;
+    return pyr_run(ctx, nullptr, src, stride, w, h, threshold, P, xy0_host, lxy_host, score_host, bin_host, desc_host, desc_dev, n_found);
+}
+
+int vp_pyr_features_dev(vp_ctx* ctx, const uint8_t* d_src, size_t stride, int w, int h, int levels, int threshold, int max_points, float* xy0_host, int32_t* lxy_host,
+                        int32_t* score_host, uint8_t* bin_host, uint8_t* desc_host, uint8_t* desc_dev, int* n_found)
+{
+    vp_pyr_plan P;
+    if (const char* why = pyr_checks(d_src, stride, w, h, levels, threshold, max_points, xy0_host, lxy_host, score_host, bin_host, desc_host, desc_dev, n_found, &P))
+        return vp_fail(ctx, VP_ERR_INVALID, why);
+    VP_TRY(check_ctx(ctx));
+    *n_found = 0;
+    if (max_points == 0 || P.T.n_levels == 0) return VP_OK;
+    return pyr_run(ctx, d_src, nullptr, stride, w, h, threshold, P, xy0_host, lxy_host, score_host, bin_host, desc_host, desc_dev, n_found);
 }
 
 int vp_hamming_plan(int nq, int nt, int D, int* query_tiles, int* train_splits)

@@ -164,6 +164,119 @@ static inline int vp_ft_build_pattern(int8_t* out)
 static_assert(709ll * 15 * 255 < (1ll << 31) && 709ll * 15 * 255 * 16384 * 2 < (1ll << 62), "describe: a moment or a bin score overflows");
 static_assert(FT_PAIRS == 4 * 64, "describe: four ballots of one wave give the 256 bits");
 
+// ---- the scale pyramid (tests/pyr_features_restate.py is the statement) --------------------------------------
+// Levels of a step of 1.2: w_l = (5 w_{l-1} + 3) / 6, each resized from the one before, kept while both sides are at least 31.  Every
+// region of the workspace that holds one byte per pixel (the levels, their scores, the kept scores, the blurs) lays the levels out one
+// after the other, each packed (stride = width) and starting at a multiple of FT_SEL_BLOCK pixels: a selection block of FT_SEL_BLOCK
+// lanes, and each of its waves, lies inside one level, and the concatenated raster is in the order level, y, x.
+#define FT_PYR_MAX_LEVELS 8
+#define FT_PYR_MAX_PIXELS (1 << 26)  // of level 0
+#define FT_PYR_NUM 5                 // w_l = (FT_PYR_NUM w + FT_PYR_DEN / 2) / FT_PYR_DEN
+#define FT_PYR_DEN 6
+
+struct vp_pyr_level {
+    uint32_t off;                    // first pixel of the level in every per-pixel region, a multiple of FT_SEL_BLOCK
+    int32_t w, h;
+    uint32_t quota;                  // q_l: the corners the level may keep
+    uint32_t tile_begin, tiles_x;    // the level's FT_TW x FT_TH tiles are tile_begin .. tile_begin + tiles_x tiles_y - 1 of the score grid
+};
+
+struct vp_pyr_table {                // passed to the kernels by value
+    int32_t n_levels;
+    uint32_t total_px;               // padded pixels of all levels: a multiple of FT_SEL_BLOCK
+    uint32_t total_tiles;            // grid of the score launch
+    vp_pyr_level L[FT_PYR_MAX_LEVELS];
+};
+
+struct vp_pyr_plan {
+    vp_pyr_table T;
+    uint32_t tiles_y[FT_PYR_MAX_LEVELS];
+    size_t chunks;                   // waves of the selection = counters of each of the three arrays: total_px / FT_CHUNK
+    unsigned sel_blocks;             // grid of the three selection launches: total_px / FT_SEL_BLOCK
+    size_t scan_per_lane;
+    size_t cap;                      // max_points
+    unsigned desc_grid;              // blocks of FT_DESC_WAVES waves for cap points
+    size_t off_img, off_score, off_keep, off_blur, off_tmp, off_hist, off_gt, off_eq, off_epre, off_lxy, off_val, off_bin, off_desc, ws_bytes;
+};
+#define FT_PYR_HIST_BYTES (FT_PYR_MAX_LEVELS * 256 * 4 + FT_PYR_MAX_LEVELS * 8)   // the histograms, then (cutoff score, equal-score corners kept) per level
+
+static inline const char* vp_pyr_refusal(int w, int h, size_t stride, int levels, int threshold, int max_points)
+{
+    if (w < 1 || h < 1) return "pyramid features: width and height must be at least 1";
+    if (w > FT_MAX_SIDE || h > FT_MAX_SIDE) return "pyramid features: width and height must be at most 65535";
+    if ((long long)w * h > FT_PYR_MAX_PIXELS) return "pyramid features: more than 2^26 pixels";
+    if (stride < (size_t)w) return "pyramid features: the stride is below the row";
+    if (levels < 1 || levels > FT_PYR_MAX_LEVELS) return "pyramid features: levels must be 1 to 8";
+    if (threshold < 0 || threshold > 255) return "pyramid features: the threshold must be 0 to 255";
+    if (max_points < 0) return "pyramid features: max_points is negative";
+    if (max_points > FT_MAX_POINTS) return "pyramid features: at most 1048576 points";
+    return nullptr;
+}
+
+// arguments as vp_pyr_refusal admitted them.  T.n_levels may be 0 (a side below 31): then nothing else is meaningful.
+static inline void vp_pyr_make_plan(int w, int h, int levels, int max_points, vp_pyr_plan* P)
+{
+    vp_pyr_table& T = P->T;
+    T.n_levels = 0;
+    T.total_px = T.total_tiles = 0;
+    long long area = 0;
+    int lw = w, lh = h;
+    for (int l = 0; l < levels && lw >= FT_DESC_MIN_SIDE && lh >= FT_DESC_MIN_SIDE; l++) {
+        vp_pyr_level& L = T.L[l];
+        L.off = T.total_px;
+        L.w = lw;
+        L.h = lh;
+        L.tile_begin = T.total_tiles;
+        L.tiles_x = (uint32_t)((lw + FT_TW - 1) / FT_TW);
+        P->tiles_y[l] = (uint32_t)((lh + FT_TH - 1) / FT_TH);
+        T.total_tiles += L.tiles_x * P->tiles_y[l];
+        T.total_px += (uint32_t)(((size_t)lw * lh + FT_SEL_BLOCK - 1) / FT_SEL_BLOCK * FT_SEL_BLOCK);
+        area += (long long)lw * lh;
+        T.n_levels = l + 1;
+        lw = (FT_PYR_NUM * lw + FT_PYR_DEN / 2) / FT_PYR_DEN;
+        lh = (FT_PYR_NUM * lh + FT_PYR_DEN / 2) / FT_PYR_DEN;
+    }
+    long long rest = max_points;
+    for (int l = 1; l < T.n_levels; l++) {
+        T.L[l].quota = (uint32_t)((long long)max_points * ((long long)T.L[l].w * T.L[l].h) / area);
+        rest -= T.L[l].quota;
+    }
+    if (T.n_levels) T.L[0].quota = (uint32_t)rest;
+    const size_t px = T.total_px, np = (size_t)(max_points > 0 ? max_points : 1);
+    P->chunks = px / FT_CHUNK;
+    P->sel_blocks = (unsigned)(px / FT_SEL_BLOCK);
+    P->scan_per_lane = (P->chunks + FT_SCAN_LANES - 1) / FT_SCAN_LANES;
+    P->cap = (size_t)max_points;
+    P->desc_grid = (unsigned)((np + FT_DESC_WAVES - 1) / FT_DESC_WAVES);
+    size_t off = 0;
+    P->off_img = off;   off += vp_ft_align(px);
+    P->off_score = off; off += vp_ft_align(px);
+    P->off_keep = off;  off += vp_ft_align(px);
+    P->off_blur = off;  off += vp_ft_align(px);
+    P->off_tmp = off;   off += vp_ft_align((size_t)w * h * 2);       // the blur's 8.8 intermediate, one level at a time: level 0 is the largest
+    P->off_hist = off;  off += vp_ft_align(FT_PYR_HIST_BYTES);
+    P->off_gt = off;    off += vp_ft_align((P->chunks + 1) * 4);
+    P->off_eq = off;    off += vp_ft_align((P->chunks + 1) * 4);
+    P->off_epre = off;  off += vp_ft_align((P->chunks + 1) * 4);
+    P->off_lxy = off;   off += vp_ft_align(np * 12);
+    P->off_val = off;   off += vp_ft_align(np * 4);
+    P->off_bin = off;   off += vp_ft_align(np);
+    P->off_desc = off;  off += vp_ft_align(np * FT_DESC_BYTES);
+    P->ws_bytes = off + 256;
+}
+
+// A level is at most the one before, so all levels hold at most FT_PYR_MAX_LEVELS times level 0's padded pixels: the offsets fit 32
+// bits, the selection grid fits a launch, and the workspace (four bytes a pixel, the 16-bit intermediate, three counters a wave and the
+// point lists) stays far inside size_t.
+#define FT_PYR_PX_BOUND ((unsigned long long)FT_PYR_MAX_LEVELS * (FT_PYR_MAX_PIXELS + FT_SEL_BLOCK))
+static_assert(FT_PYR_PX_BOUND < (1ull << 32) && FT_PYR_PX_BOUND / FT_SEL_BLOCK < (1ull << 31), "pyramid: a pixel offset leaves 32 bits or the selection grid a launch");
+static_assert(FT_PYR_PX_BOUND / (FT_TW * FT_TH) + FT_PYR_MAX_LEVELS * 2ull * (FT_MAX_SIDE / FT_TH + 1 + FT_MAX_SIDE / FT_TW + 1) < (1ull << 31), "pyramid: the score grid fits a launch");
+static_assert(4 * FT_PYR_PX_BOUND + 2ull * FT_PYR_MAX_PIXELS + 3 * (FT_PYR_PX_BOUND / FT_CHUNK + 1) * 4 + (unsigned long long)FT_MAX_POINTS * 64 + (1ull << 20) < (1ull << 40) &&
+                  sizeof(size_t) >= 8,
+              "pyramid: the workspace stays inside size_t");
+static_assert((long long)FT_MAX_POINTS * FT_PYR_MAX_PIXELS < (1ll << 62), "pyramid: a quota's product stays inside 64 bits");
+static_assert(FT_SEL_BLOCK == 256, "pyramid: a selection block owns one 256-bin histogram, a lane a bin");
+
 // ---- brute-force Hamming matcher ---------------------------------------------------------------------------------------------------
 #define HM_MIN_D 8
 #define HM_MAX_D 128

@@ -373,6 +373,10 @@ int vpk_describe(vp_ctx* ctx, const uint8_t* d_src, size_t stride, const uint8_t
 int vpk_hamming_knn(vp_ctx* ctx, const uint8_t* d_q, size_t qstride, int nq, const uint8_t* d_t, size_t tstride, int nt, const vp_hamming_plan_t& P, int k,
                     int32_t* d_idx, int32_t* d_dist, void* d_partial);
 int vpk_hamming_cross(vp_ctx* ctx, int32_t* d_idx, const int32_t* d_rev, int nq);
+// The scale pyramid: score, suppression, the per-level cut, selection and description of all levels of a plan
+// with at least one level and one point of capacity, from the levels and blurs already in d_ws; one memset and seven launches.
+struct vp_pyr_plan;
+int vpk_pyr_features(vp_ctx* ctx, const vp_pyr_plan& P, int threshold, const int8_t* d_pattern, uint8_t* d_ws, uint8_t* d_desc);
 
 // ---- morphology (vp_morph.hip; the plan: vp_morph_plan.h, with vp_bitstage, vp_bitplan and vp_ww) --------------
 // u8 (non-zero = 1) -> bits; d_flags[0] |= 1 if any byte is neither 0 nor 255

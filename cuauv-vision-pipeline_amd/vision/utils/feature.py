@@ -1176,7 +1176,11 @@ def match_descriptors(query, train, k: int = 2, cross_check: bool = False):
     query row the train rows are ordered by (Hamming distance, index) and the first k taken; -1 / -1 where there are fewer than k.
     cross_check (k = 1): idx is -1 where the train row's own best query, by (distance, query index), is another one.  uint8 (n, D)
     arrays, D up to 128 bytes (rows are zero-padded to a multiple of 8, which leaves distances unchanged).  libvp vp_hamming_knn_u8."""
-    query, train = _descriptors(query, "the query descriptors"), _descriptors(train, "the train descriptors")
+    query, train = as_mat(query), as_mat(train)
+    on_device = (isinstance(query, DeviceMat) and isinstance(train, DeviceMat) and query.dtype == train.dtype == np.uint8 and query.ndim == train.ndim == 2
+                 and query.shape[1] == train.shape[1] and query.shape[1] % 8 == 0)
+    if not on_device:
+        query, train = _descriptors(query, "the query descriptors"), _descriptors(train, "the train descriptors")
     k = int(k)
     if k not in (1, 2):
         raise ValueError("k must be 1 or 2")
@@ -1193,6 +1197,8 @@ def match_descriptors(query, train, k: int = 2, cross_check: bool = False):
     idx, dist = np.full((nq, k), -1, np.int32), np.full((nq, k), -1, np.int32)
     if nq == 0 or nt == 0:
         return idx, dist
+    if on_device:
+        return _match_descriptors_dev(query, train, k, cross_check)
     Dp = (D + 7) // 8 * 8
 
     def rows(a):
@@ -1206,6 +1212,66 @@ def match_descriptors(query, train, k: int = 2, cross_check: bool = False):
     _vp.check(_vp.lib().vp_hamming_knn_u8(ctx.handle, q.ctypes.data, Dp, nq, t.ctypes.data, Dp, nt, Dp, k, int(bool(cross_check)), idx.ctypes.data, dist.ctypes.data),
               ctx.handle)
     return idx, dist
+
+
+def _match_descriptors_dev(query, train, k, cross_check):
+    """match_descriptors of two DeviceMat arrays of the same row length, a multiple of 8 (what pyramid_features(device_descriptors=True)
+    returns): libvp vp_hamming_knn_dev reads them where they are, and only the (nq, k) indices and distances come back."""
+    ctx = _vp.default_context()
+    query.refresh_device(ctx)
+    train.refresh_device(ctx)
+    nq, nt, D = len(query), len(train), query.shape[1]
+    idx, dist = DeviceMat(ctx, (nq, k), np.int32), DeviceMat(ctx, (nq, k), np.int32)
+    _vp.check(_vp.lib().vp_hamming_knn_dev(ctx.handle, query.dev_ptr, D, nq, train.dev_ptr, D, nt, D, k, int(bool(cross_check)), idx.dev_ptr, dist.dev_ptr), ctx.handle)
+    return idx.host_copy(), dist.host_copy()
+
+
+PYRAMID_MAX_LEVELS, PYRAMID_MAX_PIXELS = 8, 1 << 26
+
+
+def pyramid_level_sizes(w: int, h: int, levels: int = 8):
+    """The (w, h) of the pyramid levels pyramid_features builds on a w x h image: a step of 1.2 in integers, w_l = (5 w_{l-1} + 3) // 6,
+    for as long as both sides are at least 31 and at most `levels` of them."""
+    out = []
+    while len(out) < levels and min(w, h) >= DESCRIBE_MIN_SIDE:
+        out.append((w, h))
+        w, h = (5 * w + 3) // 6, (5 * h + 3) // 6
+    return out
+
+
+def pyramid_features(mat, threshold: int = 20, max_points: int = 2000, levels: int = 8, device_descriptors: bool = False):
+    """FAST-9 corners and the steered 256-bit descriptor of describe_points over a scale pyramid of a uint8 single-channel image (numpy,
+    or a DeviceMat that stays in HBM): (pts0 float32 (n, 2), desc uint8 (n, 32), level int32 (n,), score int32 (n,), bin uint8 (n,)),
+    n <= max_points, ordered by level, then y, then x.  Level l is the INTER_LINEAR resize of level l - 1 to (5 side + 3) // 6 - a step
+    of 1.2 - and exists while both sides are at least 31, up to `levels` (1..8) of them; an image below 31 on a side gives no point.
+    Each level keeps its share of max_points - in proportion to its area, level 0 taking the remainder - of its highest-scoring
+    corners, ties to the earlier raster position.  A point is detected and described on its own level; pts0 are its coordinates in the
+    image, ((x + 0.5) w_0 / w_l - 0.5 in double).  All levels are scored, selected and described by the same few launches, and the
+    points never visit the host in between (libvp vp_pyr_features_*).  device_descriptors: desc is a DeviceMat,
+    for match_descriptors between two of them."""
+    mat, _ = image_source(mat, single="pyramid_features takes a single-channel image", max_side=FEATURE_MAX_SIDE)
+    h, w = mat.shape
+    if h * w > PYRAMID_MAX_PIXELS:
+        raise ValueError("pyramid_features: more than 2^26 pixels are outside the accelerated path")
+    threshold, max_points, levels = int(threshold), int(max_points), int(levels)
+    if not 0 <= threshold <= 255:
+        raise ValueError("the threshold must be 0 to 255")
+    if not 0 <= max_points <= FEATURE_MAX_POINTS:
+        raise ValueError("max_points must be 0 to 1048576")
+    if not 1 <= levels <= PYRAMID_MAX_LEVELS:
+        raise ValueError("levels must be 1 to 8")
+    lib = _vp.lib()
+    ctx, entry, src, mat = _image_call(mat, lib.vp_pyr_features_u8, lib.vp_pyr_features_dev)
+    cap = max(max_points, 1)
+    xy0, lxy, val = np.empty((cap, 2), np.float32), np.empty((cap, 3), np.int32), np.empty(cap, np.int32)
+    bins, desc = np.empty(cap, np.uint8), np.empty((cap, DESCRIPTOR_BYTES), np.uint8)
+    held = DeviceMat(ctx, (cap, DESCRIPTOR_BYTES), np.uint8) if device_descriptors else None
+    n = _vp.C.c_int(0)
+    _vp.check(entry(ctx.handle, src, w, w, h, levels, threshold, max_points, xy0.ctypes.data, lxy.ctypes.data, val.ctypes.data, bins.ctypes.data, desc.ctypes.data,
+                    held.dev_ptr if held is not None else None, _vp.C.addressof(n)), ctx.handle)
+    n = n.value
+    out_desc = DeviceMat.over_buffer(ctx, held._buf, held._off, (n, DESCRIPTOR_BYTES), np.uint8) if held is not None else desc[:n].copy()
+    return xy0[:n].copy(), out_desc, lxy[:n, 0].copy(), val[:n].copy(), bins[:n].copy()
 
 
 def ratio_test(idx, dist, ratio: float = 0.7):

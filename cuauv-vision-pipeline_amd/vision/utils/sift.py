@@ -5,7 +5,12 @@ What the class is: single-scale binary features under the reference's interface.
 descriptor, brute-force Hamming matching with the ratio test, then findHomography by RANSAC - all on the GPU
 (vision.utils.feature: fast_corners, describe_points, match_descriptors, ratio_test, estimate_motion).
 They tolerate in-plane rotation and small changes of scale.  They are not scale-invariant SIFT: there is no scale space, the
-descriptors are 32 bytes of bits and not 128 floats, and a source seen at half or twice its size will not be found."""
+descriptors are 32 bytes of bits and not 128 floats, and a source seen at half or twice its size will not be found.
+
+`PyramidSIFT` is the same class over a scale pyramid (vision.utils.feature.pyramid_features): the corners are
+found and described on up to eight levels a factor 1.2 apart and reported in the coordinates of the image, so a source is also found
+at half or twice its size - the property the reference's use (an object the vehicle drives towards) depends on.  Still binary
+features, still not SIFT's scale space or its 128 floats."""
 import numpy as np
 
 from vision import cv2_facade as _cv2
@@ -69,3 +74,23 @@ class SIFT:
             dst = np.int32(_cv2.perspectiveTransform(corners, M))
             matched.append((val["name"], good, dst, inliers.astype(np.uint8).tolist(), None))
         return matched, kp, des
+
+
+class PyramidSIFT(SIFT):
+    """SIFT's interface over pyramid_features: every image is searched on `levels` scales a factor 1.2 apart, each keypoint carries
+    its level as `octave`, the patch's diameter in the image as `size` (31 w_0 / w_l) and its orientation bin as `angle` (11.25
+    degrees a bin), and its position is in the image's own coordinates, so `match` maps the source's corners as before."""
+
+    def __init__(self, checks=50, levels=8):
+        """checks: as SIFT's, accepted and unused.  levels: pyramid levels asked for, 1 to 8."""
+        super().__init__(checks)
+        self.levels = int(levels)
+
+    def _detect(self, img):
+        """(keypoint list, descriptors (n, 32) uint8, positions (n, 2) float32 in the image's coordinates)"""
+        pts, des, level, scores, bins = _feature.pyramid_features(img, FAST_THRESHOLD, MAX_POINTS, self.levels)
+        w0 = img.shape[1]
+        widths = [w for w, _ in _feature.pyramid_level_sizes(w0, img.shape[0], self.levels)]
+        kp = [_cv2.KeyPoint(float(p[0]), float(p[1]), float(np.float32(31.0 * w0 / widths[l])), 11.25 * int(b), float(s), int(l), -1)
+              for p, l, s, b in zip(pts, level, scores, bins)]
+        return kp, des, pts

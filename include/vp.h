@@ -995,6 +995,30 @@ int vp_hamming_knn_u8(vp_ctx* ctx, const uint8_t* query, size_t query_stride, in
 int vp_hamming_knn_dev(vp_ctx* ctx, const uint8_t* query_dev, size_t query_stride, int nq, const uint8_t* train_dev, size_t train_stride, int nt, int D, int k,
                        int cross_check, int32_t* idx_dev, int32_t* dist_dev);
 
+/* ---- features over a scale pyramid (byte for byte against tests/pyr_features_restate.py) -------------------
+ * Levels: w_0, h_0 the image; w_l = (5 w_{l-1} + 3) / 6 in integers, h likewise (a step of 1.2); level l is the INTER_LINEAR resize
+ *   (vp_resize_dev's arithmetic) of level l - 1.  `levels` (1..8) are asked for; those with min(w_l, h_l) >= 31 are built, possibly none.
+ * On each level: FAST-9 as vp_fast_* states it with nonmax, among the pixels that can be described (15 <= x <= w_l - 16, likewise y;
+ *   suppression compares with the level's full score map).  Budget: a_l = w_l h_l, A their sum, q_l = (max_points a_l) / A in 64-bit
+ *   integers for l >= 1, q_0 the rest; a level keeps its q_l highest scores, ties to the earlier raster position; unused quota is not
+ *   handed on.  Order of the result: level, y, x.  Descriptor: vp_describe_*'s arithmetic on the point's own level (orientation from
+ *   the level, bits from its 7 x 7 sigma-2 blur).  xy0 = (float)(((double)x_l + 0.5) * ((double)w_0 / w_l) - 0.5), y likewise.
+ * vp_pyr_features_plan: the levels built (*n_levels, then (w, h) pairs into level_wh and q_l into quota, room for 8); no device, no
+ *   context.
+ * vp_pyr_features_*: xy0_host (max_points x 2 float32), lxy_host (max_points x 3 int32: level, x, y on the level), score_host, bin_host,
+ *   desc_host (max_points x 32) are host arrays with room for max_points entries, of which the first *n_found <= max_points are
+ *   meaningful; desc_dev (nullable): a device array of max_points x 32 bytes, 8-byte aligned, that receives the descriptors too (for
+ *   vp_hamming_knn_dev).  No level or max_points == 0: *n_found = 0, nothing is launched.  The number of launches after the pyramid and
+ *   its blurs does not depend on the number of levels; synchronises once, at the end.
+ * Refused with VP_ERR_INVALID before anything is launched or written: a missing pointer, a side below 1 or above 65535, more than 2^26
+ *   pixels, a stride below the row, levels outside 1..8, a threshold outside 0..255, max_points negative or above 2^20, a misaligned
+ *   desc_dev. */
+int vp_pyr_features_plan(int w, int h, int levels, int max_points, int* n_levels, int32_t* level_wh, int32_t* quota);
+int vp_pyr_features_u8(vp_ctx* ctx, const uint8_t* src, size_t stride, int w, int h, int levels, int threshold, int max_points, float* xy0_host, int32_t* lxy_host,
+                       int32_t* score_host, uint8_t* bin_host, uint8_t* desc_host, uint8_t* desc_dev, int* n_found);
+int vp_pyr_features_dev(vp_ctx* ctx, const uint8_t* src_dev, size_t stride, int w, int h, int levels, int threshold, int max_points, float* xy0_host, int32_t* lxy_host,
+                        int32_t* score_host, uint8_t* bin_host, uint8_t* desc_host, uint8_t* desc_dev, int* n_found);
+
 /* ---- device memory helpers (so a host program needs no HIP binding of its own) --------- */
 int vp_dev_alloc(vp_ctx* ctx, size_t bytes, void** dev_ptr);
 int vp_dev_free(vp_ctx* ctx, void* dev_ptr);    /* ctx may be NULL (memory that outlived its context) */
