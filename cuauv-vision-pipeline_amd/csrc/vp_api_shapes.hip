@@ -1,6 +1,25 @@
 // C ABI of libvp.so, shapes: polygon sums, convex hull, minimum-area rectangle and the overlay rasteriser on the host, the
 // overlay, filled shapes and cv2.addWeighted on device images (kernels: vp_morph, vp_fill).
 #include "vp_api_util.h"
+#include "vp_geometry_plan.h"
+
+// The tail of the calipers, for every path that has found its edge (vp_min_area_rect_i32 below, the rows of the device pass in
+// vp_api_geometry.hip): the edge (x0, y0) -> (x1, y1), of length above 0, and the four extents amax, amin, bmax, bmin along and across
+// it -> centre, sizes, the angle and its swap loop, rounded to float once.
+void vp_min_area_rect_finish(int x0, int y0, int x1, int y1, const double* ext4, float* out5)
+{
+    const double ex = (double)x1 - (double)x0, ey = (double)y1 - (double)y0;
+    const double ln = sqrt(ex * ex + ey * ey);
+    const double ux = ex / ln, uy = ey / ln;
+    const double amax = ext4[0], amin = ext4[1], bmax = ext4[2], bmin = ext4[3];
+    double bwd = amax - amin, bht = bmax - bmin;
+    const double ca = (amax + amin) / 2, cb = (bmax + bmin) / 2;
+    const double bcx = ca * ux - cb * uy, bcy = ca * uy + cb * ux;
+    double bang = atan2(uy, ux) * (180.0 / 3.141592653589793);
+    while (bang <= 0) { bang += 90; std::swap(bwd, bht); }
+    while (bang > 90) { bang -= 90; std::swap(bwd, bht); }
+    out5[0] = (float)bcx; out5[1] = (float)bcy; out5[2] = (float)bwd; out5[3] = (float)bht; out5[4] = (float)bang;
+}
 
 extern "C" {
 
@@ -74,35 +93,24 @@ int vp_min_area_rect_i32(const int32_t* pts, int npts, float* out5)
     if (vp_convex_hull_i32(pts, npts, hull.data(), &n) != VP_OK) return VP_ERR_INVALID;
     if (n == 0) { for (int i = 0; i < 5; i++) out5[i] = 0.f; return VP_OK; }
     if (n == 1) { out5[0] = (float)hull[0]; out5[1] = (float)hull[1]; out5[2] = out5[3] = 0.f; out5[4] = 90.f; return VP_OK; }
-    bool have = false;
-    double best_area = 0, bcx = 0, bcy = 0, bwd = 0, bht = 0, bang = 0;
+    int best = -1;
+    double best_area = 0, best_ext[4] = {0, 0, 0, 0};
+    const vp_geom_hull_i32 H = {hull.data()};
     const int edges = n > 2 ? n : 1;
     for (int i = 0; i < edges; i++) {
-        const int i1 = (i + 1) % n;
-        const double ex = (double)hull[2 * i1] - (double)hull[2 * i], ey = (double)hull[2 * i1 + 1] - (double)hull[2 * i + 1];
-        const double ln = sqrt(ex * ex + ey * ey);
-        if (ln == 0) continue;
-        const double ux = ex / ln, uy = ey / ln;
-        double amax = 0, amin = 0, bmax = 0, bmin = 0;
-        for (int k = 0; k < n; k++) {
-            const double hx = (double)hull[2 * k], hy = (double)hull[2 * k + 1];
-            const double a = hx * ux + hy * uy, b = -hx * uy + hy * ux;
-            if (k == 0) { amax = amin = a; bmax = bmin = b; }
-            else { amax = std::max(amax, a); amin = std::min(amin, a); bmax = std::max(bmax, b); bmin = std::min(bmin, b); }
-        }
-        const double wd = amax - amin, ht = bmax - bmin;
-        if (!have || wd * ht < best_area) {
-            const double ca = (amax + amin) / 2, cb = (bmax + bmin) / 2;
-            have = true;
+        double ext[4];
+        int arg[4];
+        if (!vp_geom_edge_extents(H, n, i, ext, arg)) continue;
+        const double wd = ext[0] - ext[1], ht = ext[2] - ext[3];
+        if (best < 0 || wd * ht < best_area) {
+            best = i;
             best_area = wd * ht;
-            bcx = ca * ux - cb * uy; bcy = ca * uy + cb * ux; bwd = wd; bht = ht;
-            bang = atan2(uy, ux) * (180.0 / 3.141592653589793);
+            for (int k = 0; k < 4; k++) best_ext[k] = ext[k];
         }
     }
-    if (!have) { out5[0] = (float)hull[0]; out5[1] = (float)hull[1]; out5[2] = out5[3] = 0.f; out5[4] = 90.f; return VP_OK; }
-    while (bang <= 0) { bang += 90; std::swap(bwd, bht); }
-    while (bang > 90) { bang -= 90; std::swap(bwd, bht); }
-    out5[0] = (float)bcx; out5[1] = (float)bcy; out5[2] = (float)bwd; out5[3] = (float)bht; out5[4] = (float)bang;
+    if (best < 0) { out5[0] = (float)hull[0]; out5[1] = (float)hull[1]; out5[2] = out5[3] = 0.f; out5[4] = 90.f; return VP_OK; }
+    const int b1 = (best + 1) % n;
+    vp_min_area_rect_finish(hull[2 * best], hull[2 * best + 1], hull[2 * b1], hull[2 * b1 + 1], best_ext, out5);
     return VP_OK;
 }
 

@@ -378,6 +378,18 @@ int vpk_hamming_cross(vp_ctx* ctx, int32_t* d_idx, const int32_t* d_rev, int nq)
 struct vp_pyr_plan;
 int vpk_pyr_features(vp_ctx* ctx, const vp_pyr_plan& P, int threshold, const int8_t* d_pattern, uint8_t* d_ws, uint8_t* d_desc);
 
+// ---- contour geometry (vp_geometry.hip; the plan: vp_geometry_plan.h) ------------------------------------------------------
+// One launch, one wave per contour, enqueued: perimeter, hull, calipers and enclosing circle of every contour into d_rows (64-byte raw
+// rows), hull vertices into d_hull (nullable; the layout of the points).  vpk_contour_geometry: contour i is counts[i] points from point
+// first[i] of d_pts.  vpk_contour_geometry_batch: the buffers of a batched contour pass; rows are (n, max_contours).
+struct vp_geom_raw;
+int vpk_contour_geometry(vp_ctx* ctx, const int32_t* d_pts, const long long* d_first, const int32_t* d_counts, int n_contours, vp_geom_raw* d_rows,
+                         int32_t* d_hull);
+int vpk_contour_geometry_batch(vp_ctx* ctx, const int32_t* d_info, const int32_t* d_counts, const int32_t* d_offsets, const int32_t* d_points, int n,
+                               int max_contours, long long max_points, vp_geom_raw* d_rows);
+// the calipers' tail (vp_api_shapes.hip): edge (x0, y0) -> (x1, y1) and the extents amax, amin, bmax, bmin -> the five floats
+void vp_min_area_rect_finish(int x0, int y0, int x1, int y1, const double* ext4, float* out5);
+
 // ---- morphology (vp_morph.hip; the plan: vp_morph_plan.h, with vp_bitstage, vp_bitplan and vp_ww) --------------
 // u8 (non-zero = 1) -> bits; d_flags[0] |= 1 if any byte is neither 0 nor 255
 int vpk_pack_bits(vp_ctx* ctx, const uint8_t* d_src, size_t stride, int w, int h, int n, u64* d_bits,

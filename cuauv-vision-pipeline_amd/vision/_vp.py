@@ -88,6 +88,22 @@ class ContourBuffers(C.Structure):
                 ("points", C.c_void_p), ("features", C.c_void_p)]
 
 
+GEOM_OK, GEOM_HULL_CAP, GEOM_PERIMETER, GEOM_SKIPPED, GEOM_COORD = 0, 1, 2, 4, 8      # status bits of a vp_contour_geom row
+GEOM_COORD_MIN, GEOM_COORD_MAX = -32768, 32767
+
+
+class ContourGeom(C.Structure):
+    """vp_contour_geom (include/vp.h): one row of the contour-geometry pass, 80 bytes."""
+    _fields_ = [("perimeter", C.c_double), ("perimeter_open", C.c_double), ("hull_area2", C.c_int64), ("hull_count", C.c_int32),
+                ("status", C.c_uint32), ("rect", C.c_float * 5), ("circle", C.c_float * 3), ("support_count", C.c_int32),
+                ("support", C.c_int16 * 6)]
+
+
+# the same row as a numpy record, for whole tables
+CONTOUR_GEOM_DTYPE = np.dtype([("perimeter", np.float64), ("perimeter_open", np.float64), ("hull_area2", np.int64), ("hull_count", np.int32),
+                               ("status", np.uint32), ("rect", np.float32, 5), ("circle", np.float32, 3), ("support_count", np.int32),
+                               ("support", np.int16, 6)])
+
 _lib = None
 _lock = threading.Lock()
 
@@ -148,6 +164,11 @@ _SIGS = {
     "vp_convex_hull_i32": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.POINTER(C.c_int)]),
     "vp_min_area_rect_i32": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p]),
     "vp_polygon_sums_i32": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p]),
+    "vp_contour_geometry_i32": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "vp_contour_geometry_dev": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]),
+    "vp_contour_geometry_batch_dev": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]),
+    "vp_contour_geometry_plan": (C.c_int, [C.c_int64, C.c_int64, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "vp_min_enclosing_circle_i32": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]),
     "vp_draw_polylines_u8": (C.c_int, [C.c_void_p, C.c_size_t, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int]),
     "vp_cvt_color_dev": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_size_t, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
     "vp_inrange_u8_dev": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]),

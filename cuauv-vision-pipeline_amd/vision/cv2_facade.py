@@ -399,6 +399,15 @@ def _min_area_rect_loop(points):
     return (float(np.float32(cx)), float(np.float32(cy))), (float(np.float32(wd)), float(np.float32(ht))), float(np.float32(ang))
 
 
+def minEnclosingCircle(points):
+    """cv2.minEnclosingCircle for integer points: ((cx, cy), radius) of the smallest enclosing circle (vision.utils.feature.
+    min_enclosing_circle: exact support set, no safety margin on the radius)."""
+    try:
+        return _feature.min_enclosing_circle(points)
+    except ValueError as e:
+        raise error(str(e))
+
+
 def boxPoints(box):
     """Corners of a rotated rect, in OpenCV's order (RotatedRect::points): bottom-left, top-left, top-right, bottom-right."""
     (cx, cy), (w, h), ang = box

@@ -413,8 +413,157 @@ def _outside_path(name):
     return _f
 
 
-min_enclosing_circle = _outside_path("min_enclosing_circle")
 min_enclosing_ellipse = _outside_path("min_enclosing_ellipse")
+
+
+def _circle_points(contour, name):
+    """(k, 2) contiguous int32 points within the coordinate bound of the geometry routines; integer-valued floats are taken as integers"""
+    p = np.asarray(contour)
+    if p.size == 0:
+        return np.zeros((0, 2), np.int32)
+    p = p.reshape(-1, 2)
+    if not np.issubdtype(p.dtype, np.integer):
+        q = np.rint(p)
+        if not np.array_equal(q, p):
+            raise ValueError(f"{name}: integer points only (the support set is found with exact integer predicates)")
+        p = q
+    if p.min() < _vp.GEOM_COORD_MIN or p.max() > _vp.GEOM_COORD_MAX:
+        raise ValueError(f"{name}: coordinates within [{_vp.GEOM_COORD_MIN}, {_vp.GEOM_COORD_MAX}] only")
+    return np.ascontiguousarray(p, np.int32)
+
+
+def min_enclosing_circle(contour: np.ndarray):
+    """utils/feature.py:315-325 (cv2.minEnclosingCircle): ((cx, cy), radius) of the smallest circle that contains every point, by libvp's
+    host routine - exact integer predicates choose the support points, centre and radius are rounded to float32 once.  OpenCV's small
+    safety margin on the radius is not added.  A lone contour does not justify a launch; contour_geometry serves whole lists."""
+    p = _circle_points(contour, "min_enclosing_circle")
+    out = (_vp.C.c_float * 3)()
+    _vp.check(_vp.lib().vp_min_enclosing_circle_i32(p.ctypes.data, len(p), out, None))
+    return (out[0], out[1]), out[2]
+
+
+# one record per contour of contour_geometry
+GEOMETRY_DTYPE = np.dtype([("perimeter", np.float64), ("perimeter_open", np.float64), ("hull_count", np.int32), ("hull_area", np.float64),
+                           ("rect", np.float32, 5), ("circle", np.float32, 3), ("status", np.uint32)])
+
+
+def _geometry_table(raw):
+    out = np.zeros(raw.shape, GEOMETRY_DTYPE)
+    for name in ("perimeter", "perimeter_open", "hull_count", "rect", "circle", "status"):
+        out[name] = raw[name]
+    out["hull_area"] = raw["hull_area2"] * 0.5
+    return out
+
+
+def _geometry_host_row(rec, pts, hull_out=None):
+    """One contour through the host routines: what the device pass leaves to the host (status bits) and what lies outside its bound."""
+    from vision import cv2_facade
+    p = np.ascontiguousarray(np.asarray(pts).reshape(-1, 2), np.int32)
+    if len(p) == 0:
+        return                                            # no points: zeros
+    rec["perimeter"] = cv2_facade.arcLength(p, True)
+    rec["perimeter_open"] = cv2_facade.arcLength(p, False)
+    hull = np.empty((max(len(p), 1), 2), np.int32)
+    n = _vp.C.c_int(0)
+    _vp.check(_vp.lib().vp_convex_hull_i32(p.ctypes.data, len(p), hull.ctypes.data, _vp.C.byref(n)))
+    h = hull[:n.value].astype(np.int64)
+    rec["hull_count"] = n.value
+    rec["hull_area"] = abs(int(np.sum(h[:, 0] * np.roll(h[:, 1], -1) - np.roll(h[:, 0], -1) * h[:, 1]))) * 0.5 if n.value else 0.0
+    r5 = (_vp.C.c_float * 5)()
+    _vp.check(_vp.lib().vp_min_area_rect_i32(p.ctypes.data, len(p), r5))
+    rec["rect"] = np.frombuffer(r5, np.float32)
+    if len(p) and p.min() >= _vp.GEOM_COORD_MIN and p.max() <= _vp.GEOM_COORD_MAX:
+        c3 = (_vp.C.c_float * 3)()
+        _vp.check(_vp.lib().vp_min_enclosing_circle_i32(p.ctypes.data, len(p), c3, None))
+        rec["circle"] = np.frombuffer(c3, np.float32)
+    else:
+        rec["circle"] = np.nan if len(p) else 0.0     # outside the bound of the exact predicates: not computed
+    if hull_out is not None:
+        hull_out[:n.value] = hull[:n.value]
+
+
+def _geometry_flat(contours):
+    """-> (points (P, 2) int32, counts (K,) int32) of a contour list, without per-contour work where the list carries its block"""
+    flat, counts = getattr(contours, "_flat", None), getattr(contours, "_counts", None)
+    if flat is not None and counts is not None and flat.dtype == np.int32:
+        return np.ascontiguousarray(flat.reshape(-1, 2)), np.ascontiguousarray(counts, np.int32)
+    arrs = [np.asarray(c).reshape(-1, 2) for c in contours]
+    for a in arrs:
+        if a.size and not np.issubdtype(a.dtype, np.integer):
+            raise TypeError("contour_geometry: integer contours only")
+    counts = np.array([len(a) for a in arrs], np.int32)
+    flat = np.concatenate(arrs).astype(np.int32, copy=False) if arrs else np.zeros((0, 2), np.int32)
+    return np.ascontiguousarray(flat.reshape(-1, 2)), counts
+
+
+def _geometry_batch(arrs):
+    """The arrays of a batched contour pass (ChainRunner's dict: info, counts, offsets, points on the host) through the batch entry:
+    staged on the device as the chain leaves them there, (n, max_contours) records back."""
+    ctx = _vp.default_context()
+    L = _vp.lib()
+    info, counts, offsets, points = (np.ascontiguousarray(arrs[k], np.int32) for k in ("info", "counts", "offsets", "points"))
+    n, mc, mp = info.shape[0], counts.shape[1], points.shape[1]
+    cdesc = _vp.make_contour_desc(max_contours=mc, max_points=mp)
+    cb = _vp.ContourBuffers()
+    held = []
+    try:
+        for name, a in (("info", info), ("counts", counts), ("offsets", offsets), ("points", points)):
+            p = _vp.C.c_void_p()
+            _vp.check(L.vp_dev_alloc(ctx.handle, max(a.nbytes, 8), _vp.C.byref(p)), ctx.handle)
+            held.append(p)
+            _vp.check(L.vp_memcpy_h2d(ctx.handle, p, a.ctypes.data, a.nbytes), ctx.handle)
+            setattr(cb, name, p.value)
+        raw = np.zeros((n, mc), _vp.CONTOUR_GEOM_DTYPE)
+        _vp.check(L.vp_contour_geometry_batch_dev(ctx.handle, _vp.C.byref(cdesc), _vp.C.byref(cb), n, raw.ctypes.data), ctx.handle)
+    finally:
+        for p in held:
+            L.vp_dev_free(ctx.handle, p)
+    out = _geometry_table(raw)
+    for f, r in zip(*np.nonzero(raw["status"] & (_vp.GEOM_HULL_CAP | _vp.GEOM_PERIMETER))):
+        _geometry_host_row(out[f, r], points[f, offsets[f, r]:offsets[f, r] + counts[f, r]])
+    return out
+
+
+def contour_geometry(contours, hulls: bool = False):
+    """Perimeter, convex hull, minimum-area rectangle and minimum enclosing circle of every contour in one device pass (libvp
+    vp_contour_geometry_i32): a GEOMETRY_DTYPE record per contour, in the input's order - `perimeter` / `perimeter_open` as
+    cv2_facade.arcLength, `hull_count` / `hull_area` of vp_convex_hull_i32's hull, `rect` the five floats of vp_min_area_rect_i32
+    (bit for bit), `circle` centre and radius as min_enclosing_circle.  contours: what find_contours returns (its point block is
+    passed as it is), any sequence of (N, 1, 2) integer arrays, or the array dict of a batched pass (ChainRunner.carrs: records of
+    shape (frames, max_contours), rows that hold no traced contour carry status GEOM_SKIPPED).  Rows the device hands back
+    unfinished (status bits) are completed by the host routines before returning.  hulls: also the hull vertices, an int32 block
+    laid out like the points - the hull of contour k at the offset of its points, `hull_count` of them."""
+    if isinstance(contours, dict):
+        if hulls:
+            raise ValueError("contour_geometry: the batch form returns no hull vertices")
+        return _geometry_batch(contours)
+    flat, counts = _geometry_flat(contours)
+    k = len(counts)
+    raw = np.zeros(k, _vp.CONTOUR_GEOM_DTYPE)
+    hull = np.zeros_like(flat) if hulls else None
+    if flat.size and (flat.min() < _vp.GEOM_COORD_MIN or flat.max() > _vp.GEOM_COORD_MAX):
+        out, o = _geometry_table(raw), 0                      # outside the device pass's bound: the host routines, one by one
+        for i, c in enumerate(counts.tolist()):
+            _geometry_host_row(out[i], flat[o:o + c], None if hull is None else hull[o:o + c])
+            o += c
+        return (out, hull) if hulls else out
+    if k:
+        ctx = _vp.default_context()
+        _vp.check(_vp.lib().vp_contour_geometry_i32(ctx.handle, flat.ctypes.data, counts.ctypes.data, k, raw.ctypes.data,
+                                                    hull.ctypes.data if hulls else None, None), ctx.handle)
+    out = _geometry_table(raw)
+    return (out, hull) if hulls else out
+
+
+def min_enclosing_rects(contours):
+    """cv2.minAreaRect of every contour: (K, 5) float32 rows centre x, y, width, height, angle - a view of the contour_geometry table,
+    so that a filter like modules/bins.py:33-61 (area, aspect ratio) is array arithmetic over a frame's contours."""
+    return contour_geometry(contours)["rect"]
+
+
+def contour_perimeters(contours, closed: bool = True):
+    """cv2.arcLength of every contour: float64 (K,)."""
+    return contour_geometry(contours)["perimeter" if closed else "perimeter_open"]
 
 
 def canny(mat: np.ndarray, lower: int, upper: int) -> np.ndarray:

@@ -399,6 +399,55 @@ int vp_chain_run_contours(vp_ctx* ctx, const vp_chain_desc* desc, const vp_chain
 int vp_chain_run_contours_host(vp_ctx* ctx, const vp_chain_desc* desc, const vp_chain_buffers* host, const vp_contour_desc* cdesc,
                                const vp_contour_buffers* chost, int n_frames);
 
+/* ---- contour geometry: perimeter, hull, minimum-area rectangle, enclosing circle ------------------
+ * What a module computes per contour after cv2.findContours (modules/bins.py:33,61 cv2.minAreaRect, utils/feature.py:266-325
+ * cv2.arcLength / convexHull / minEnclosingCircle), for every contour of a point block in one launch: one row per contour.
+ * Points are int32 (x, y) pairs with both coordinates in [-32768, 32767].
+ *   perimeter / perimeter_open: cv2.arcLength(c, True) / (c, False) as vp's stand-in computes it - float32 segment roots summed in
+ *     float64 - bit for bit (the device adds the roots as integer counts of 2^-23, exact below 2^53).
+ *   hull_count, hull_area2: vp_convex_hull_i32's vertex count and twice its area; the vertices on request.
+ *   rect: vp_min_area_rect_i32's five floats, bit for bit (the device finds the edge and the extents, one host function finishes).
+ *   circle: centre x, y and radius of the smallest circle that contains every point, from an exact support set of 1..3 points
+ *     (support_count, support): no safety margin is added (OpenCV adds a small one).  No points: zeros.
+ *   status: 0 = finished on the device; VP_GEOM_HULL_CAP = the hull candidates passed the device slot (vp_contour_geometry_plan tells
+ *     its size) and VP_GEOM_PERIMETER = the perimeter total reached 2^53 units - vp_contour_geometry_i32 has then finished the row
+ *     with the host routines and leaves the bit set, the device forms leave hull, rect and circle (or the two perimeters) zero for
+ *     the caller to finish; VP_GEOM_SKIPPED = batch form, the contour was not traced (row zero); VP_GEOM_COORD = device forms, a
+ *     coordinate outside the bound (row zero). */
+enum { VP_GEOM_OK = 0, VP_GEOM_HULL_CAP = 1, VP_GEOM_PERIMETER = 2, VP_GEOM_SKIPPED = 4, VP_GEOM_COORD = 8 };
+typedef struct vp_contour_geom {
+    double perimeter;
+    double perimeter_open;
+    int64_t hull_area2;
+    int32_t hull_count;
+    uint32_t status;
+    float rect[5];         /* centre x, y, width, height, angle */
+    float circle[3];       /* centre x, y, radius */
+    int32_t support_count;
+    int16_t support[6];    /* (x, y) of the support points */
+} vp_contour_geom;         /* 80 bytes */
+/* Host points: counts_host[k] points of contour k, back to back in pts_host.  hull_pts_out (may be NULL, same size as pts_host)
+ * receives the hull of contour k at the place of its points, hull_counts_out (may be NULL) their number.  A coordinate outside the
+ * bound is refused with VP_ERR_UNSUPPORTED before anything is launched. */
+int vp_contour_geometry_i32(vp_ctx* ctx, const int32_t* pts_host, const int32_t* counts_host, int n_contours, vp_contour_geom* rows_out,
+                            int32_t* hull_pts_out, int32_t* hull_counts_out);
+/* Points already on the device: first_dev[k] is the index of contour k's first point (int64), pts_dev 8-byte aligned.  hull_pts_dev
+ * (may be NULL) as above, on the device.  Rows come back to the host finished; synchronises. */
+int vp_contour_geometry_dev(vp_ctx* ctx, const int32_t* pts_dev, const int64_t* first_dev, const int32_t* counts_dev, int n_contours,
+                            vp_contour_geom* rows_out_host, int32_t* hull_pts_dev);
+/* A batch as vp_chain_run_contours left it on the device: rows_out_host is (n_frames, max_contours); row k of frame f is contour k
+ * of cdev->counts / offsets for k < min(info[f][0], max_contours), VP_GEOM_SKIPPED otherwise and for a contour that overflowed
+ * max_points.  Nothing but info, counts, offsets and points is read.  Synchronises. */
+int vp_contour_geometry_batch_dev(vp_ctx* ctx, const vp_contour_desc* cdesc, const vp_contour_buffers* cdev, int n_frames,
+                                  vp_contour_geom* rows_out_host);
+/* The plan of a pass over n_contours contours of n_points points, without a context: device workspace of the host-point form,
+ * grid3 = blocks x, y and threads per block, *hull_cap = hull candidates a contour may have on the device.  Refuses what the
+ * entries refuse: negative counts (VP_ERR_INVALID), more than 2^24 contours or 2^23 points (VP_ERR_UNSUPPORTED). */
+int vp_contour_geometry_plan(int64_t n_contours, int64_t n_points, int want_hulls, uint64_t* ws_bytes, int32_t* grid3, int32_t* hull_cap);
+/* The smallest enclosing circle of integer points within the coordinate bound (host code, no context): out3 = centre x, y, radius.
+ * The single-contour form and the completion of VP_GEOM_HULL_CAP rows.  support7 (may be NULL): count and three (x, y). */
+int vp_min_enclosing_circle_i32(const int32_t* pts, int npts, float* out3, int32_t* support7);
+
 /* ---- detector pre / post-processing (BASELINE config 5) ----------------------
  * modules/yolo.py:112 `self.model.track(image)` hides these steps inside ultralytics (not in the reference tree, not
  * installed): LetterBox (scale to fit, centre, pad, BGR->RGB, HWC->CHW, /255) before the network, non-maximum suppression
