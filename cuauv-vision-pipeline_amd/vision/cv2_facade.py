@@ -807,6 +807,69 @@ def createCLAHE(clipLimit=40.0, tileGridSize=(8, 8)):
     return CLAHE(clipLimit, tileGridSize)
 
 
+# ---- stereo block matching (libvp vp_stereo.hip) ---------------------------------------------------------------
+StereoBM_PREFILTER_NORMALIZED_RESPONSE, StereoBM_PREFILTER_XSOBEL = 0, 1
+STEREO_BM_PREFILTER_NORMALIZED_RESPONSE, STEREO_BM_PREFILTER_XSOBEL = 0, 1
+
+
+class StereoBM:
+    """What cv2.StereoBM_create returns: compute() runs libvp's vp_stereo_bm_* kernels on the statement of tests/stereo_restate.py
+    (vision.utils.stereo.disparity).  Six parameters are supported; the prefilter is always XSOBEL; the speckle filter, the left-right
+    check, the ROIs and preFilterSize keep cv2's defaults and any other value is refused."""
+    # name -> (default, getter / setter suffix) of what this path does not have
+    _FIXED = {"SpeckleWindowSize": 0, "SpeckleRange": 0, "Disp12MaxDiff": -1, "PreFilterType": StereoBM_PREFILTER_XSOBEL, "PreFilterSize": 9,
+              "ROI1": (0, 0, 0, 0), "ROI2": (0, 0, 0, 0)}
+    _KEYS = {"NumDisparities": "num_disparities", "BlockSize": "block_size", "MinDisparity": "min_disparity", "PreFilterCap": "pre_filter_cap",
+             "TextureThreshold": "texture_threshold", "UniquenessRatio": "uniqueness_ratio"}
+
+    def __init__(self, numDisparities=0, blockSize=21):
+        self._p = dict(num_disparities=64, block_size=21, min_disparity=0, pre_filter_cap=31, texture_threshold=10, uniqueness_ratio=15)
+        self.setNumDisparities(numDisparities)
+        self.setBlockSize(blockSize)
+
+    def _set(self, key, value):
+        from vision.utils import stereo as _stereo
+        trial = dict(self._p, **{key: value})
+        _gather("StereoBM", _stereo._matcher, **trial)
+        self._p = trial
+
+    def setNumDisparities(self, numDisparities):
+        self._set("num_disparities", 64 if numDisparities == 0 else numDisparities)
+
+    def compute(self, left, right, disparity=None):
+        from vision.utils import stereo as _stereo
+        left, right = _grey_u8_source("StereoBM.compute", left), _grey_u8_source("StereoBM.compute", right)
+        try:
+            return _into(disparity, _gather("StereoBM.compute", _stereo.disparity, left, right, **self._p))
+        except _vp.VpError as e:
+            raise error(f"StereoBM.compute: {e}") from None
+
+
+def _stereo_bm_accessors():
+    for name, key in StereoBM._KEYS.items():
+        setattr(StereoBM, "get" + name, lambda self, key=key: self._p[key])
+        if name != "NumDisparities":
+            setattr(StereoBM, "set" + name, lambda self, value, key=key: self._set(key, value))
+    for name, default in StereoBM._FIXED.items():
+        def setter(self, value, name=name, default=default):
+            if (tuple(value) if isinstance(default, tuple) else value) != default:
+                raise error(f"StereoBM: {name} other than {default} is outside the accelerated path (DESIGN.md section 7)")
+        setattr(StereoBM, "get" + name, lambda self, default=default: default)
+        setattr(StereoBM, "set" + name, setter)
+
+
+_stereo_bm_accessors()
+
+
+def StereoBM_create(numDisparities=0, blockSize=21):
+    """cv2.StereoBM_create: block matching of a rectified uint8 pair on the GPU; numDisparities 0 means 64.  compute(left, right) gives
+    16 times the disparity as int16 ((minDisparity - 1) * 16 where there is no answer); DeviceMat images give a DeviceMat."""
+    return StereoBM(numDisparities, blockSize)
+
+
+StereoBM.create = staticmethod(StereoBM_create)
+
+
 # ---- derivative filters (libvp vp_deriv.hip) ------------------------------------------------------------------------------------------
 def _deriv_call(name, fn, src, ddepth, scale, delta, borderType, *args):
     """What cv2 rejects, and the two restrictions of this path: scale = 1 and delta = 0 only."""

@@ -1,0 +1,142 @@
+"""Stereo block matching on the GPU: what the reference's forward camera got from its vendor SDK as the `depth` plane
+(capture_sources/zed_sync.py:90-149), made here from the rectified left and right images (libvp vp_stereo.hip).
+
+`disparity` follows the design of cv2.StereoBM - capped horizontal Sobel prefilter, sums of absolute differences over a square window,
+texture and uniqueness tests, parabola subpixel - as tests/stereo_restate.py states it, byte for byte; it has not met a real OpenCV.
+The pair must be rectified (vision.utils.transform.undistorter / RemapTable apply a calibration's maps): a point of `left` at column x
+lies on the same row of `right` at column x - D.
+"""
+import ctypes as C
+
+import numpy as np
+
+from vision import _vp
+from vision.devmat import DeviceMat
+from vision.utils.helpers import device_image, image_source
+
+MAX_SIDE = 4096
+_RANGES = (("num_disparities", 16, 256), ("block_size", 5, 21), ("min_disparity", -128, 128), ("pre_filter_cap", 1, 63), ("texture_threshold", 0, 2 ** 31 - 1),
+           ("uniqueness_ratio", 0, 100))
+
+
+def _matcher(num_disparities=64, block_size=15, min_disparity=0, pre_filter_cap=31, texture_threshold=10, uniqueness_ratio=15):
+    """the six checked parameters, in the order of the C entries; everything libvp refuses is refused here, before a device is needed"""
+    given = (num_disparities, block_size, min_disparity, pre_filter_cap, texture_threshold, uniqueness_ratio)
+    out = []
+    for (name, lo, hi), v in zip(_RANGES, given):
+        if isinstance(v, bool) or not isinstance(v, (int, np.integer)):
+            raise TypeError(f"{name} must be an integer")
+        if not lo <= v <= hi:
+            raise ValueError(f"{name} must lie in {lo}..{hi}")
+        out.append(int(v))
+    if out[0] % 16:
+        raise ValueError("num_disparities must be a multiple of 16")
+    if out[1] % 2 == 0:
+        raise ValueError("block_size must be odd")
+    return tuple(out)
+
+
+def _grey(mat, which):
+    mat, cn = image_source(mat, max_side=MAX_SIDE)
+    if cn == 3:
+        from vision.utils.color import bgr_to_gray
+        mat = bgr_to_gray(mat)[0]
+    elif cn != 1:
+        raise ValueError(f"the {which} image must have one channel, or three (BGR)")
+    if mat.ndim == 3:
+        mat = mat.reshaped(mat.shape[:2]) if isinstance(mat, DeviceMat) else mat[:, :, 0]
+    return mat
+
+
+def _pair(left, right):
+    left, right = _grey(left, "left"), _grey(right, "right")
+    if tuple(left.shape) != tuple(right.shape):
+        raise ValueError("the left and right images must have one size")
+    return left, right
+
+
+def invalid_disparity(min_disparity: int = 0) -> int:
+    """the int16 value of a pixel without an answer: (min_disparity - 1) * 16"""
+    return (int(min_disparity) - 1) * 16
+
+
+def valid_rect(w: int, h: int, num_disparities: int = 64, block_size: int = 15, min_disparity: int = 0):
+    """(x, y, w, h) of the pixels `disparity` can answer - those whose window, at every disparity of the range, lies inside both images -
+    from libvp's plan (vp_stereo_bm_plan; no device needed); (0, 0, 0, 0) when there is none."""
+    n, bs, m = _matcher(num_disparities, block_size, min_disparity)[:3]
+    if not (1 <= int(w) <= MAX_SIDE and 1 <= int(h) <= MAX_SIDE):
+        raise ValueError("width and height must lie in 1..4096")
+    rect, geom, ws = (C.c_int32 * 4)(), (C.c_int32 * 5)(), C.c_size_t()
+    _vp.check(_vp.lib().vp_stereo_bm_plan(int(w), int(h), n, bs, m, rect, C.byref(ws), geom))
+    return tuple(rect)
+
+
+def _disparity_dev(ctx, left, right, params):
+    """both images on the device -> an int16 DeviceMat, enqueued"""
+    left, right = device_image(ctx, left, 1), device_image(ctx, right, 1)
+    h, w = left.shape
+    out = DeviceMat(ctx, (h, w), np.int16)
+    _vp.check(_vp.lib().vp_stereo_bm_dev(ctx.handle, left.dev_ptr, w, right.dev_ptr, w, w, h, *params, out.dev_ptr, 2 * w), ctx.handle)
+    return out
+
+
+def _depth_dev(ctx, disp, focal_px, baseline_m):
+    h, w = disp.shape
+    out = DeviceMat(ctx, (h, w), np.float32)
+    _vp.check(_vp.lib().vp_depth_from_disparity_dev(ctx.handle, disp.dev_ptr, 2 * w, w, h, focal_px, baseline_m, out.dev_ptr, 4 * w), ctx.handle)
+    return out
+
+
+def disparity(left, right, num_disparities: int = 64, block_size: int = 15, min_disparity: int = 0, pre_filter_cap: int = 31, texture_threshold: int = 10,
+              uniqueness_ratio: int = 15):
+    """16 times the disparity of every pixel of `left`, int16, `invalid_disparity(min_disparity)` where there is no answer: outside
+    `valid_rect`, where the window has too little texture, and where a second disparity is within uniqueness_ratio per cent of the
+    best.  uint8 (h, w) images of one size up to 4096 x 4096; (h, w, 3) images go through bgr_to_gray first.  num_disparities a multiple
+    of 16 in 16..256, block_size odd in 5..21, min_disparity in -128..128, pre_filter_cap in 1..63, uniqueness_ratio in 0..100.
+    numpy in gives numpy out; if either image is a DeviceMat the result is an int16 DeviceMat that stays in HBM."""
+    params = _matcher(num_disparities, block_size, min_disparity, pre_filter_cap, texture_threshold, uniqueness_ratio)
+    left, right = _pair(left, right)
+    ctx = _vp.default_context()
+    if isinstance(left, DeviceMat) or isinstance(right, DeviceMat):
+        return _disparity_dev(ctx, left, right, params)
+    left, right = np.ascontiguousarray(left), np.ascontiguousarray(right)
+    h, w = left.shape
+    out = np.empty((h, w), np.int16)
+    _vp.check(_vp.lib().vp_stereo_bm_u8(ctx.handle, left.ctypes.data, right.ctypes.data, w, h, *params, out.ctypes.data), ctx.handle)
+    return out
+
+
+def _depth_args(disp16, focal_px, baseline_m):
+    if not isinstance(disp16, (np.ndarray, DeviceMat)) or disp16.dtype != np.int16 or len(disp16.shape) != 2 or 0 in disp16.shape:
+        raise TypeError("expected a non-empty int16 (h, w) disparity image")
+    if max(disp16.shape) > MAX_SIDE:
+        raise ValueError("the disparity image must be at most 4096 x 4096")
+    return disp16, float(focal_px), float(baseline_m)
+
+
+def depth_from_disparity(disp16, focal_px: float, baseline_m: float):
+    """Metric depth of an int16 disparity image (16 times the disparity, as `disparity` returns it): float32 metres,
+    focal_px * baseline_m * 16 / disp16 as one double quotient rounded once, and 0 where disp16 <= 0 - the `depth` plane's rule for
+    pixels without an answer.  numpy in gives numpy out, a DeviceMat a DeviceMat."""
+    disp16, focal_px, baseline_m = _depth_args(disp16, focal_px, baseline_m)
+    ctx = _vp.default_context()
+    if isinstance(disp16, DeviceMat):
+        disp16.refresh_device(ctx)
+        return _depth_dev(ctx, disp16, focal_px, baseline_m)
+    disp16 = np.ascontiguousarray(disp16)
+    h, w = disp16.shape
+    out = np.empty((h, w), np.float32)
+    _vp.check(_vp.lib().vp_depth_from_disparity_i16(ctx.handle, disp16.ctypes.data, w, h, focal_px, baseline_m, out.ctypes.data), ctx.handle)
+    return out
+
+
+def stereo_depth(left, right, focal_px: float, baseline_m: float, **matcher):
+    """`depth_from_disparity(disparity(left, right, **matcher), focal_px, baseline_m)` with the disparity kept in HBM between the two:
+    numpy images are uploaded, both steps are queued, and only the float32 depth comes back (a DeviceMat if either image was one)."""
+    params = _matcher(**matcher)
+    left, right = _pair(left, right)
+    focal_px, baseline_m = float(focal_px), float(baseline_m)
+    on_device = isinstance(left, DeviceMat) or isinstance(right, DeviceMat)
+    ctx = _vp.default_context()
+    depth = _depth_dev(ctx, _disparity_dev(ctx, left, right, params), focal_px, baseline_m)
+    return depth if on_device else depth.host()

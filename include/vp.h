@@ -1068,6 +1068,39 @@ int vp_pyr_features_u8(vp_ctx* ctx, const uint8_t* src, size_t stride, int w, in
 int vp_pyr_features_dev(vp_ctx* ctx, const uint8_t* src_dev, size_t stride, int w, int h, int levels, int threshold, int max_points, float* xy0_host, int32_t* lxy_host,
                         int32_t* score_host, uint8_t* bin_host, uint8_t* desc_host, uint8_t* desc_dev, int* n_found);
 
+/* ---- stereo block matching: disparity of a rectified pair and metric depth --------------------------------
+ * The design of cv2.StereoBM, byte for byte against tests/stereo_restate.py, which is the contract (it has not met a real OpenCV).
+ * left, right: uint8, single channel, w x h, rectified: a point of left (x, y) lies at right (x - D, y).  num_disparities n: a multiple
+ * of 16 in 16..256; block_size odd in 5..21, r = block_size / 2; min_disparity m in -128..128; pre_filter_cap c in 1..63;
+ * texture_threshold >= 0; uniqueness_ratio in 0..100.
+ *   Prefilter of both images, rows reflected without the edge row (one row: itself): p = clamp(I(x+1,y-1) - I(x-1,y-1) +
+ *     2 (I(x+1,y) - I(x-1,y)) + I(x+1,y+1) - I(x-1,y+1), -c, c) + c for 1 <= x <= w - 2, and c in columns 0 and w - 1.
+ *   C(x, y, D) = sum over |i|, |j| <= r of |pL(x+i, y+j) - pR(x+i-D, y+j)|, D in [m, m + n - 1].
+ *   Candidates: r <= y <= h-1-r, r <= x <= w-1-r, x - r - (m+n-1) >= 0, x + r - m <= w - 1; every other pixel is (m - 1) * 16.
+ *   So is a candidate whose T = window sum of |pL - c| is below texture_threshold, and, for uniqueness_ratio > 0, one with a D,
+ *     |D - D*| > 1, of C(D) <= C* + C* uniqueness_ratio / 100 (integer division).  D* minimises C, ties to the larger D.
+ *   Else (D* 256 + off + 15) >> 4 with off = (pm - pp) 256 / (pm + pp - 2 C* + |pm - pp|) truncated (0 for a zero denominator),
+ *     pm = C(D* - 1), pp = C(D* + 1), the one missing at an end of the range taken as the other.  16 times the disparity, int16.
+ * Depth: float32(double(focal_px * baseline_m) * 16.0 / double(disp16)) where disp16 > 0, else 0.
+ * vp_stereo_bm_plan: no device, no context.  rect: x, y, w, h of the candidate pixels (zeros when there is none); *ws_bytes: device
+ *   scratch of a call; geometry: the matcher's strip columns, band rows, grid x, grid y and LDS bytes per block.
+ * _u8 / _i16: packed host images in and out, synchronise.  _dev: device images with strides in bytes, enqueued.  _host: the same
+ *   statement as scalar C++, host images with strides, no device and no context.
+ * Refused with VP_ERR_INVALID before anything is launched or written (the message names the reason): a missing pointer, w or h
+ *   outside 1..4096, a stride below the row or, for the int16 / float32 images, no multiple of the element size, a parameter outside
+ *   its range, a misaligned int16 / float32 image, a result that overlaps an input.  An image without a candidate pixel is no error. */
+int vp_stereo_bm_plan(int w, int h, int num_disparities, int block_size, int min_disparity, int32_t* rect, size_t* ws_bytes, int32_t* geometry);
+int vp_stereo_bm_u8(vp_ctx* ctx, const uint8_t* left, const uint8_t* right, int w, int h, int num_disparities, int block_size, int min_disparity, int pre_filter_cap,
+                    int texture_threshold, int uniqueness_ratio, int16_t* disp);
+int vp_stereo_bm_dev(vp_ctx* ctx, const uint8_t* left_dev, size_t left_stride, const uint8_t* right_dev, size_t right_stride, int w, int h, int num_disparities,
+                     int block_size, int min_disparity, int pre_filter_cap, int texture_threshold, int uniqueness_ratio, int16_t* disp_dev, size_t disp_stride);
+int vp_stereo_bm_host(const uint8_t* left, size_t left_stride, const uint8_t* right, size_t right_stride, int w, int h, int num_disparities, int block_size,
+                      int min_disparity, int pre_filter_cap, int texture_threshold, int uniqueness_ratio, int16_t* disp, size_t disp_stride);
+int vp_depth_from_disparity_i16(vp_ctx* ctx, const int16_t* disp, int w, int h, double focal_px, double baseline_m, float* depth);
+int vp_depth_from_disparity_dev(vp_ctx* ctx, const int16_t* disp_dev, size_t disp_stride, int w, int h, double focal_px, double baseline_m, float* depth_dev,
+                                size_t depth_stride);
+int vp_depth_from_disparity_host(const int16_t* disp, size_t disp_stride, int w, int h, double focal_px, double baseline_m, float* depth, size_t depth_stride);
+
 /* ---- device memory helpers (so a host program needs no HIP binding of its own) --------- */
 int vp_dev_alloc(vp_ctx* ctx, size_t bytes, void** dev_ptr);
 int vp_dev_free(vp_ctx* ctx, void* dev_ptr);    /* ctx may be NULL (memory that outlived its context) */
