@@ -148,7 +148,7 @@ void vp_adaptive_teardown(vp_ctx* ctx)
     for (int& n : ctx->agauss.n) n = 0;     // no slot holds taps any more
 }
 
-size_t vp_agauss_ws_bytes(int w, int h, int n) { return vp_align((size_t)w * h * n * 8); }
+size_t vp_agauss_tmp_bytes(int w, int h, int n) { return (size_t)w * h * n * 8; }
 
 int vpk_adaptive_threshold_gaussian(vp_ctx* ctx, const uint8_t* d_src, size_t stride, size_t fstride, int n, int w, int h, int imax, int idelta,
                                     int inv, int block, uint64_t* d_tmp, uint8_t* d_dst)

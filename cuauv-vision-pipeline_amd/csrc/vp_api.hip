@@ -369,9 +369,8 @@ int vp_memcpy_d2h(vp_ctx* ctx, void* dst, const void* src, size_t bytes)
 
 // ---- workspace ------------------------------------------------------------------------------------
 
-int vp_ws_reserve(vp_ctx* ctx, size_t bytes)
+static int vp_ws_reserve(vp_ctx* ctx, size_t bytes)
 {
-    ctx->ws_off = 0;
     if (bytes <= ctx->ws_cap) return VP_OK;
     VP_HIP(ctx, hipStreamSynchronize(ctx->stream));
     if (ctx->ws) { hipFree(ctx->ws); ctx->ws = nullptr; ctx->ws_cap = 0; }
@@ -382,12 +381,14 @@ int vp_ws_reserve(vp_ctx* ctx, size_t bytes)
     return VP_OK;
 }
 
-void* vp_ws_take(vp_ctx* ctx, size_t bytes)
+int vp_ws_commit(vp_ctx* ctx, const vp_ws_frame& W, const char* who)
 {
-    const size_t off = vp_align(ctx->ws_off);
-    if (off + bytes > ctx->ws_cap) return nullptr;
-    ctx->ws_off = off + bytes;
-    return ctx->ws + off;
+    if (W.overflowed()) return vp_fail(ctx, VP_ERR_INVALID, "too many workspace buffers");
+    if (W.wrapped) return vp_fail(ctx, VP_ERR_NOMEM, who);
+    const int rc = vp_ws_reserve(ctx, W.bytes() ? W.bytes() : 1);   // at least a byte: a frame of empty buffers still gets valid pointers
+    if (rc != VP_OK) return rc;
+    W.assign(ctx->ws);
+    return VP_OK;
 }
 
 void* vp_hstage(vp_ctx* ctx, size_t bytes)

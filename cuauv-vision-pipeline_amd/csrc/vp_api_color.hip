@@ -17,12 +17,13 @@ int vp_cvt_color_u8(vp_ctx* ctx, int code, const uint8_t* src, size_t src_stride
     uint8_t* hp[3] = {nullptr, nullptr, nullptr};
     if (planes)
         for (int c = 0; c < dcn; c++) hp[c] = planes[c];
-    VP_TRY(vp_ws_reserve(ctx, vp_align(npx * scn) + vp_align(npx * dcn) + 3 * vp_align(npx) + 4096));
-    TAKE(d_src, uint8_t*, npx * scn);
-    TAKE(d_dst, uint8_t*, npx * dcn);
+    vp_ws_frame W;
+    uint8_t* d_src; W.want(&d_src, npx * scn);
+    uint8_t* d_dst; W.want(&d_dst, npx * dcn);
     uint8_t* dp[3] = {nullptr, nullptr, nullptr};
     for (int c = 0; c < 3; c++)
-        if (hp[c]) { dp[c] = (uint8_t*)vp_ws_take(ctx, npx); if (!dp[c]) return vp_fail(ctx, VP_ERR_NOMEM, "workspace"); }
+        if (hp[c]) W.want(&dp[c], npx);
+    VP_TRY(vp_ws_commit(ctx, W, "vp_cvt_color_u8"));
     VP_TRY(h2d_rows(ctx, d_src, (size_t)w * scn, src, src_stride, (size_t)w * scn, h));
     if (code == VP_HSV2BGR) {
         if (planes) return vp_fail(ctx, VP_ERR_UNSUPPORTED, "HSV2BGR: split planes");
@@ -43,10 +44,13 @@ int vp_color_balance_u8(vp_ctx* ctx, const uint8_t* src, int w, int h, int flags
     const size_t npx = (size_t)w * h;
     const size_t tiles = (flags & VP_CB_EQUALIZE_RGB) ? (size_t)hblocks * vblocks : 1;
     if (tiles > 1024) return vp_fail(ctx, VP_ERR_UNSUPPORTED, "colour balance: too many tiles");
-    VP_TRY(vp_ws_reserve(ctx, vp_align(npx * 3) + vp_balance_ws_bytes(1, (int)tiles) + 4096));
-    TAKE(d_img, uint8_t*, npx * 3);
+    vp_ws_frame W;
+    uint8_t* d_img; W.want(&d_img, npx * 3);
+    vp_balance_ws bw;
+    vp_balance_want(W, 1, (int)tiles, flags, &bw);
+    VP_TRY(vp_ws_commit(ctx, W, "vp_color_balance_u8"));
     VP_TRY(h2d(ctx, d_img, src, npx * 3));
-    VP_TRY(vpk_color_balance(ctx, d_img, d_img, w, h, 1, flags, hblocks, vblocks));
+    VP_TRY(vpk_color_balance(ctx, d_img, d_img, w, h, 1, flags, hblocks, vblocks, bw));
     VP_TRY(d2h(ctx, dst, d_img, npx * 3));
     return vp_synchronize(ctx);
 }
@@ -70,8 +74,11 @@ int vp_color_balance_dev(vp_ctx* ctx, const uint8_t* src, uint8_t* dst, int w, i
     if (!src || !dst || w <= 0 || h <= 0 || n <= 0 || hblocks <= 0 || vblocks <= 0) return vp_fail(ctx, VP_ERR_INVALID, "vp_color_balance_dev arguments");
     const size_t tiles = (flags & VP_CB_EQUALIZE_RGB) ? (size_t)hblocks * vblocks : 1;
     if (tiles > 1024) return vp_fail(ctx, VP_ERR_UNSUPPORTED, "colour balance: too many tiles");
-    VP_TRY(vp_ws_reserve(ctx, vp_balance_ws_bytes(n, (int)tiles) + 4096));
-    return vpk_color_balance(ctx, src, dst, w, h, n, flags, hblocks, vblocks);
+    vp_ws_frame W;
+    vp_balance_ws bw;
+    vp_balance_want(W, n, (int)tiles, flags, &bw);
+    VP_TRY(vp_ws_commit(ctx, W, "vp_color_balance_dev"));
+    return vpk_color_balance(ctx, src, dst, w, h, n, flags, hblocks, vblocks, bw);
 }
 
 int vp_cvt_bgr2lab_f32(vp_ctx* ctx, const float* src, int w, int h, float* dst)
@@ -79,9 +86,10 @@ int vp_cvt_bgr2lab_f32(vp_ctx* ctx, const float* src, int w, int h, float* dst)
     VP_TRY(check_ctx(ctx));
     if (!src || !dst || w <= 0 || h <= 0) return vp_fail(ctx, VP_ERR_INVALID, "vp_cvt_bgr2lab_f32 arguments");
     const size_t npx = (size_t)w * h;
-    VP_TRY(vp_ws_reserve(ctx, 2 * vp_align(npx * 12) + 1024));
-    TAKE(d_src, float*, npx * 12);
-    TAKE(d_dst, float*, npx * 12);
+    vp_ws_frame W;
+    float* d_src; W.want(&d_src, npx * 12);
+    float* d_dst; W.want(&d_dst, npx * 12);
+    VP_TRY(vp_ws_commit(ctx, W, "vp_cvt_bgr2lab_f32"));
     VP_TRY(h2d(ctx, d_src, src, npx * 12));
     VP_TRY(vpk_bgr2lab_f32(ctx, d_src, npx, d_dst));
     VP_TRY(d2h(ctx, dst, d_dst, npx * 12));
@@ -92,9 +100,10 @@ int vp_order_stats_f32(vp_ctx* ctx, const float* src, size_t n, size_t k, float*
 {
     VP_TRY(check_ctx(ctx));
     if (!src || !v_k || n == 0 || k >= n) return vp_fail(ctx, VP_ERR_INVALID, "vp_order_stats_f32 arguments");
-    VP_TRY(vp_ws_reserve(ctx, vp_align(n * 4) + 4096));
-    TAKE(d_src, float*, n * 4);
-    TAKE(d_hist, u32*, 1024);
+    vp_ws_frame W;
+    float* d_src; W.want(&d_src, n * 4);
+    u32* d_hist; W.want(&d_hist, 1024);
+    VP_TRY(vp_ws_commit(ctx, W, "vp_order_stats_f32"));
     VP_TRY(h2d(ctx, d_src, src, n * 4));
     VP_TRY(vpk_kth_f32(ctx, d_src, n, k, d_hist, v_k));
     if (v_k1) VP_TRY(vpk_kth_f32(ctx, d_src, n, k + 1 < n ? k + 1 : n - 1, d_hist, v_k1));
@@ -110,9 +119,10 @@ int vp_inrange_u8(vp_ctx* ctx, const uint8_t* src, size_t src_stride, int w, int
     vp_range3 q;
     norm_range(cn, lo, hi, &q);
     const size_t npx = (size_t)w * h;
-    VP_TRY(vp_ws_reserve(ctx, vp_align(npx * cn) + vp_align(npx) + 1024));
-    TAKE(d_src, uint8_t*, npx * cn);
-    TAKE(d_dst, uint8_t*, npx);
+    vp_ws_frame W;
+    uint8_t* d_src; W.want(&d_src, npx * cn);
+    uint8_t* d_dst; W.want(&d_dst, npx);
+    VP_TRY(vp_ws_commit(ctx, W, "vp_inrange_u8"));
     VP_TRY(h2d_rows(ctx, d_src, (size_t)w * cn, src, src_stride, (size_t)w * cn, h));
     VP_TRY(vpk_inrange_u8(ctx, d_src, (size_t)w * cn, w, h, cn, q, d_dst));
     VP_TRY(d2h(ctx, dst, d_dst, npx));
@@ -125,9 +135,10 @@ int vp_inrange_f32(vp_ctx* ctx, const float* src, size_t src_stride_bytes, int w
     if (!src || !dst || w <= 0 || h <= 0 || h > 65535 || src_stride_bytes < (size_t)w * 4)
         return vp_fail(ctx, VP_ERR_INVALID, "vp_inrange_f32 arguments");
     const size_t npx = (size_t)w * h;
-    VP_TRY(vp_ws_reserve(ctx, vp_align(npx * 4) + vp_align(npx) + 1024));
-    TAKE(d_src, float*, npx * 4);
-    TAKE(d_dst, uint8_t*, npx);
+    vp_ws_frame W;
+    float* d_src; W.want(&d_src, npx * 4);
+    uint8_t* d_dst; W.want(&d_dst, npx);
+    VP_TRY(vp_ws_commit(ctx, W, "vp_inrange_f32"));
     VP_TRY(h2d_rows(ctx, d_src, (size_t)w * 4, src, src_stride_bytes, (size_t)w * 4, h));
     VP_TRY(vpk_inrange_f32(ctx, d_src, (size_t)w * 4, w, h, lo, hi, d_dst));
     VP_TRY(d2h(ctx, dst, d_dst, npx));
@@ -142,16 +153,15 @@ int vp_color_distance_u8(vp_ctx* ctx, const uint8_t* const* planes, int w, int h
     for (int c = 0; c < 3; c++)
         if (!(skipmask & (1 << c)) && !planes[c]) return vp_fail(ctx, VP_ERR_INVALID, "missing plane");
     const size_t npx = (size_t)w * h;
-    VP_TRY(vp_ws_reserve(ctx, 3 * vp_align(npx) + vp_align(npx * 4) + vp_align(npx) + 2048));
+    vp_ws_frame W;
     uint8_t* dp[3] = {nullptr, nullptr, nullptr};
-    for (int c = 0; c < 3; c++) {
-        if (skipmask & (1 << c)) continue;
-        dp[c] = (uint8_t*)vp_ws_take(ctx, npx);
-        if (!dp[c]) return vp_fail(ctx, VP_ERR_NOMEM, "workspace");
-        VP_TRY(h2d(ctx, dp[c], planes[c], npx));
-    }
-    TAKE(d_d2, float*, npx * 4);
-    TAKE(d_sq, uint8_t*, npx);
+    for (int c = 0; c < 3; c++)
+        if (!(skipmask & (1 << c))) W.want(&dp[c], npx);
+    float* d_d2; W.want(&d_d2, npx * 4);
+    uint8_t* d_sq; W.want(&d_sq, npx);
+    VP_TRY(vp_ws_commit(ctx, W, "vp_color_distance_u8"));
+    for (int c = 0; c < 3; c++)
+        if (dp[c]) VP_TRY(h2d(ctx, dp[c], planes[c], npx));
     VP_TRY(vpk_color_distance(ctx, dp[0], dp[1], dp[2], npx, color, wts, skipmask, d_d2, d_sq));
     if (dist2_out) VP_TRY(d2h(ctx, dist2_out, d_d2, npx * 4));
     if (sqrt_out) VP_TRY(d2h(ctx, sqrt_out, d_sq, npx));
@@ -212,12 +222,17 @@ static int wb_args(vp_ctx* ctx, const void* src, size_t src_stride, int w, int h
 }
 
 // the means go through the workspace and come back only when asked for; the device forms stay asynchronous otherwise
-static int wb_run(vp_ctx* ctx, const uint8_t* d_src, size_t stride, int w, int h, int kernel_size, uint8_t* d_dst, float* ab_mean_out)
+struct wb_bufs { float* mean; vp_whitebal_ws k; };
+static void wb_want(vp_ws_frame& W, int w, int h, int kernel_size, wb_bufs* b)
 {
-    TAKE(d_mean, float*, 8);
-    VP_TRY(vpk_white_balance(ctx, d_src, stride, w, h, kernel_size, d_dst, d_mean));
+    W.want(&b->mean, 8);
+    vp_white_balance_want(W, w, h, kernel_size, &b->k);
+}
+static int wb_run(vp_ctx* ctx, const uint8_t* d_src, size_t stride, int w, int h, int kernel_size, uint8_t* d_dst, float* ab_mean_out, const wb_bufs& b)
+{
+    VP_TRY(vpk_white_balance(ctx, d_src, stride, w, h, kernel_size, d_dst, b.mean, b.k));
     if (ab_mean_out && kernel_size == VP_WB_GLOBAL_MEAN) {
-        VP_TRY(d2h(ctx, ab_mean_out, d_mean, 8));
+        VP_TRY(d2h(ctx, ab_mean_out, b.mean, 8));
         return vp_synchronize(ctx);
     }
     return VP_OK;
@@ -228,11 +243,14 @@ int vp_white_balance_u8(vp_ctx* ctx, const uint8_t* src, size_t src_stride, int 
     VP_TRY(check_ctx(ctx));
     VP_TRY(wb_args(ctx, src, src_stride, w, h, kernel_size, dst));
     const size_t npx = (size_t)w * h;
-    VP_TRY(vp_ws_reserve(ctx, 2 * vp_align(npx * 3) + vp_align(8) + vp_white_balance_ws_bytes(w, h, kernel_size) + 4096));
-    TAKE(d_src, uint8_t*, npx * 3);
-    TAKE(d_dst, uint8_t*, npx * 3);
+    vp_ws_frame W;
+    uint8_t* d_src; W.want(&d_src, npx * 3);
+    uint8_t* d_dst; W.want(&d_dst, npx * 3);
+    wb_bufs b;
+    wb_want(W, w, h, kernel_size, &b);
+    VP_TRY(vp_ws_commit(ctx, W, "vp_white_balance_u8"));
     VP_TRY(h2d_rows(ctx, d_src, (size_t)w * 3, src, src_stride, (size_t)w * 3, h));
-    VP_TRY(wb_run(ctx, d_src, (size_t)w * 3, w, h, kernel_size, d_dst, ab_mean_out));
+    VP_TRY(wb_run(ctx, d_src, (size_t)w * 3, w, h, kernel_size, d_dst, ab_mean_out, b));
     VP_TRY(d2h(ctx, dst, d_dst, npx * 3));
     return vp_synchronize(ctx);
 }
@@ -241,8 +259,11 @@ int vp_white_balance_dev(vp_ctx* ctx, const uint8_t* d_src, size_t src_stride, i
 {
     VP_TRY(check_ctx(ctx));
     VP_TRY(wb_args(ctx, d_src, src_stride, w, h, kernel_size, d_dst));
-    VP_TRY(vp_ws_reserve(ctx, vp_align(8) + vp_white_balance_ws_bytes(w, h, kernel_size) + 4096));
-    return wb_run(ctx, d_src, src_stride, w, h, kernel_size, d_dst, ab_mean_out);
+    vp_ws_frame W;
+    wb_bufs b;
+    wb_want(W, w, h, kernel_size, &b);
+    VP_TRY(vp_ws_commit(ctx, W, "vp_white_balance_dev"));
+    return wb_run(ctx, d_src, src_stride, w, h, kernel_size, d_dst, ab_mean_out, b);
 }
 
 }  // extern "C"

@@ -4,19 +4,28 @@
 #include "vp_corners_plan.h"
 
 // Response, maximum, candidates and their order on the device; the count comes back, then the ordered words, and the greedy pass runs
-// here.  d_mask (rows of mstride bytes) and d_bits (the mask's bit plane) are nullable device pointers; the workspace is reserved by
-// the caller and holds what it staged.
+// here.  d_mask (rows of mstride bytes) and d_bits (the mask's bit plane) are nullable device pointers; the caller's frame holds b
+// beside what it staged.
+struct gf_bufs { float* resp; u64 *k0, *k1; u32* cnt; };
+static void gf_want(vp_ws_frame& W, int w, int h, gf_bufs* b)
+{
+    if (w < 3 || h < 3) return;                                  // good_features_run launches nothing
+    const size_t npx = (size_t)w * h, kcap = (size_t)(w - 2) * (h - 2);
+    W.want(&b->resp, npx * 4);
+    W.want(&b->k0, kcap * 8);
+    W.want(&b->k1, kcap * 8);
+    W.want(&b->cnt, 8);
+}
 static int good_features_run(vp_ctx* ctx, const uint8_t* d_src, size_t stride, int w, int h, int max_corners, double quality, double min_distance,
                              const uint8_t* d_mask, size_t mstride, const u64* d_bits, int block_size, int harris, double k, float* corners,
-                             int capacity, int* n_corners)
+                             int capacity, int* n_corners, const gf_bufs& b)
 {
     *n_corners = 0;
     if (w < 3 || h < 3) return VP_OK;                            // no interior pixel: cv2 returns nothing
-    const size_t npx = (size_t)w * h, kcap = (size_t)(w - 2) * (h - 2);
-    TAKE(d_resp, float*, npx * 4);
-    TAKE(d_k0, u64*, kcap * 8);
-    TAKE(d_k1, u64*, kcap * 8);
-    TAKE(d_cnt, u32*, 8);
+    const size_t kcap = (size_t)(w - 2) * (h - 2);
+    float* d_resp = b.resp;
+    u64 *d_k0 = b.k0, *d_k1 = b.k1;
+    u32* d_cnt = b.cnt;
     VP_TRY(vpk_corner_response(ctx, d_src, stride, w, h, block_size, harris, k, VP_BORDER_REFLECT_101, d_resp));
     VP_TRY(vpk_corner_candidates(ctx, d_resp, w, h, d_mask, mstride, d_bits, quality, d_cnt, d_k0, kcap));
     u32* hs = (u32*)vp_hstage(ctx, 16);
@@ -48,9 +57,10 @@ int vp_corner_response_u8(vp_ctx* ctx, const uint8_t* src, size_t stride, int w,
     if (const char* why = vp_corner_response_refusal(w, h, stride, block_size, ksize, k, border)) return vp_fail(ctx, VP_ERR_INVALID, why);
     VP_TRY(check_ctx(ctx));
     const size_t npx = (size_t)w * h;
-    VP_TRY(vp_ws_reserve(ctx, vp_align(npx) + vp_align(npx * 4) + 1024));
-    TAKE(d_src, uint8_t*, npx);
-    TAKE(d_dst, float*, npx * 4);
+    vp_ws_frame W;
+    uint8_t* d_src; W.want(&d_src, npx);
+    float* d_dst; W.want(&d_dst, npx * 4);
+    VP_TRY(vp_ws_commit(ctx, W, "vp_corner_response_u8"));
     VP_TRY(h2d_rows(ctx, d_src, (size_t)w, src, stride, (size_t)w, h));
     VP_TRY(vpk_corner_response(ctx, d_src, (size_t)w, w, h, block_size, harris != 0, k, border, d_dst));
     VP_TRY(d2h(ctx, dst, d_dst, npx * 4));
@@ -77,17 +87,17 @@ int vp_good_features_u8(vp_ctx* ctx, const uint8_t* src, size_t stride, int w, i
         return vp_fail(ctx, VP_ERR_INVALID, why);
     VP_TRY(check_ctx(ctx));
     const size_t npx = (size_t)w * h;
-    VP_TRY(vp_ws_reserve(ctx, 2 * vp_align(npx) + vp_align(npx * 4) + 2 * vp_align(npx * 8) + 4096));
-    TAKE(d_src, uint8_t*, npx);
-    VP_TRY(h2d_rows(ctx, d_src, (size_t)w, src, stride, (size_t)w, h));
+    vp_ws_frame W;
+    uint8_t* d_src; W.want(&d_src, npx);
     uint8_t* d_mask = nullptr;
-    if (mask) {
-        d_mask = (uint8_t*)vp_ws_take(ctx, npx);
-        if (!d_mask) return vp_fail(ctx, VP_ERR_NOMEM, "workspace exhausted: d_mask");
-        VP_TRY(h2d_rows(ctx, d_mask, (size_t)w, mask, mask_stride, (size_t)w, h));
-    }
+    if (mask) W.want(&d_mask, npx);
+    gf_bufs b;
+    gf_want(W, w, h, &b);
+    VP_TRY(vp_ws_commit(ctx, W, "vp_good_features_u8"));
+    VP_TRY(h2d_rows(ctx, d_src, (size_t)w, src, stride, (size_t)w, h));
+    if (mask) VP_TRY(h2d_rows(ctx, d_mask, (size_t)w, mask, mask_stride, (size_t)w, h));
     return good_features_run(ctx, d_src, (size_t)w, w, h, max_corners, quality_level, min_distance, d_mask, (size_t)w, nullptr, block_size, harris != 0, k,
-                             corners, capacity, n_corners);
+                             corners, capacity, n_corners, b);
 }
 
 int vp_good_features_dev(vp_ctx* ctx, const uint8_t* d_src, size_t stride, int w, int h, int max_corners, double quality_level, double min_distance,
@@ -101,10 +111,12 @@ int vp_good_features_dev(vp_ctx* ctx, const uint8_t* d_src, size_t stride, int w
                                                    block_size, k, capacity))
         return vp_fail(ctx, VP_ERR_INVALID, why);
     VP_TRY(check_ctx(ctx));
-    const size_t npx = (size_t)w * h;
-    VP_TRY(vp_ws_reserve(ctx, vp_align(npx * 4) + 2 * vp_align(npx * 8) + 4096));
+    vp_ws_frame W;
+    gf_bufs b;
+    gf_want(W, w, h, &b);
+    VP_TRY(vp_ws_commit(ctx, W, "vp_good_features_dev"));
     return good_features_run(ctx, d_src, stride, w, h, max_corners, quality_level, min_distance, d_mask_bits ? nullptr : d_mask, mask_stride,
-                             reinterpret_cast<const u64*>(d_mask_bits), block_size, harris != 0, k, corners, capacity, n_corners);
+                             reinterpret_cast<const u64*>(d_mask_bits), block_size, harris != 0, k, corners, capacity, n_corners, b);
 }
 
 }  // extern "C"

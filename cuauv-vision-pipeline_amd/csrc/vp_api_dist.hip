@@ -3,11 +3,10 @@
 #include "vp_api_util.h"
 #include "vp_dist_plan.h"
 
-// the search on the device, its two words back through pinned staging, decoded into *out; the workspace is reserved by the caller
+// the search on the device, its two words (d_keys: 16 bytes of workspace) back through pinned staging, decoded into *out
 static int min_max_loc_run(vp_ctx* ctx, const void* d_src, size_t stride, int w, int h, int depth, const uint8_t* d_mask, size_t mstride, const u64* d_bits,
-                           vp_min_max_loc_result* out)
+                           u64* d_keys, vp_min_max_loc_result* out)
 {
-    TAKE(d_keys, u64*, 16);
     VP_TRY(vpk_min_max_loc(ctx, d_src, stride, w, h, depth, d_mask, mstride, d_bits, d_keys));
     u64* hk = (u64*)vp_hstage(ctx, 16);
     if (!hk) return vp_fail(ctx, VP_ERR_NOMEM, "pinned staging");
@@ -27,10 +26,11 @@ int vp_distance_transform_u8(vp_ctx* ctx, const uint8_t* src, int w, int h, int 
         return vp_fail(ctx, VP_ERR_INVALID, why);
     VP_TRY(check_ctx(ctx));
     const size_t npx = (size_t)w * h;
-    VP_TRY(vp_ws_reserve(ctx, vp_align(npx) + vp_align(npx * es) + vp_align(vp_dist_ws_bytes(w, h)) + 1024));
-    TAKE(d_src, uint8_t*, npx);
-    TAKE(d_dst, uint8_t*, npx * es);
-    TAKE(d_g, uint16_t*, vp_dist_ws_bytes(w, h));
+    vp_ws_frame W;
+    uint8_t* d_src; W.want(&d_src, npx);
+    uint8_t* d_dst; W.want(&d_dst, npx * es);
+    uint16_t* d_g; W.want(&d_g, vp_dist_g_bytes(w, h));
+    VP_TRY(vp_ws_commit(ctx, W, "vp_distance_transform_u8"));
     VP_TRY(h2d(ctx, d_src, src, npx));
     VP_TRY(vpk_distance_transform(ctx, d_src, (size_t)w, w, h, nullptr, metric, dst_depth, d_g, d_dst, (size_t)w * es));
     VP_TRY(d2h(ctx, dst, d_dst, npx * es));
@@ -48,8 +48,9 @@ int vp_distance_transform_dev(vp_ctx* ctx, const uint8_t* d_src, size_t stride, 
     if ((uintptr_t)d_dst % es || dev_overlap(d_src, strided_bytes(stride, (size_t)w, h), d_dst, strided_bytes(dst_stride, (size_t)w * es, h)))
         return vp_fail(ctx, VP_ERR_INVALID, "vp_distance_transform_dev: dst is not aligned to its element, or overlaps src");
     VP_TRY(check_ctx(ctx));
-    VP_TRY(vp_ws_reserve(ctx, vp_align(vp_dist_ws_bytes(w, h)) + 1024));
-    TAKE(d_g, uint16_t*, vp_dist_ws_bytes(w, h));
+    vp_ws_frame W;
+    uint16_t* d_g; W.want(&d_g, vp_dist_g_bytes(w, h));
+    VP_TRY(vp_ws_commit(ctx, W, "vp_distance_transform_dev"));
     return vpk_distance_transform(ctx, d_src, stride, w, h, reinterpret_cast<const u64*>(d_src_bits), metric, dst_depth, d_g, d_dst, dst_stride);
 }
 
@@ -60,16 +61,15 @@ int vp_min_max_loc_u8(vp_ctx* ctx, const void* src, size_t stride, int w, int h,
     if (const char* why = vp_min_max_loc_refusal(w, h, stride, depth, mask != nullptr, mask_w, mask_h, mask_stride)) return vp_fail(ctx, VP_ERR_INVALID, why);
     VP_TRY(check_ctx(ctx));
     const size_t npx = (size_t)w * h, es = depth == VP_DEPTH_8U ? 1 : 4, row = (size_t)w * es;
-    VP_TRY(vp_ws_reserve(ctx, vp_align(npx * es) + vp_align(npx) + 1024));
-    TAKE(d_src, uint8_t*, npx * es);
-    VP_TRY(h2d_rows(ctx, d_src, row, src, stride, row, h));
+    vp_ws_frame W;
+    uint8_t* d_src; W.want(&d_src, npx * es);
     uint8_t* d_mask = nullptr;
-    if (mask) {
-        d_mask = (uint8_t*)vp_ws_take(ctx, npx);
-        if (!d_mask) return vp_fail(ctx, VP_ERR_NOMEM, "workspace exhausted: d_mask");
-        VP_TRY(h2d_rows(ctx, d_mask, (size_t)w, mask, mask_stride, (size_t)w, h));
-    }
-    return min_max_loc_run(ctx, d_src, row, w, h, depth, d_mask, (size_t)w, nullptr, (vp_min_max_loc_result*)out);
+    if (mask) W.want(&d_mask, npx);
+    u64* d_keys; W.want(&d_keys, 16);
+    VP_TRY(vp_ws_commit(ctx, W, "vp_min_max_loc_u8"));
+    VP_TRY(h2d_rows(ctx, d_src, row, src, stride, row, h));
+    if (mask) VP_TRY(h2d_rows(ctx, d_mask, (size_t)w, mask, mask_stride, (size_t)w, h));
+    return min_max_loc_run(ctx, d_src, row, w, h, depth, d_mask, (size_t)w, nullptr, d_keys, (vp_min_max_loc_result*)out);
 }
 
 int vp_min_max_loc_dev(vp_ctx* ctx, const void* d_src, size_t stride, int w, int h, int depth, const uint8_t* d_mask, size_t mask_stride, int mask_w, int mask_h,
@@ -82,9 +82,11 @@ int vp_min_max_loc_dev(vp_ctx* ctx, const void* d_src, size_t stride, int w, int
         return vp_fail(ctx, VP_ERR_INVALID, why);
     if (depth == VP_DEPTH_32F && (uintptr_t)d_src % 4) return vp_fail(ctx, VP_ERR_INVALID, "vp_min_max_loc_dev: a float32 source must be 4-byte aligned");
     VP_TRY(check_ctx(ctx));
-    VP_TRY(vp_ws_reserve(ctx, 1024));
+    vp_ws_frame W;
+    u64* d_keys; W.want(&d_keys, 16);
+    VP_TRY(vp_ws_commit(ctx, W, "vp_min_max_loc_dev"));
     return min_max_loc_run(ctx, d_src, stride, w, h, depth, d_mask_bits ? nullptr : d_mask, mask_stride, reinterpret_cast<const u64*>(d_mask_bits),
-                           (vp_min_max_loc_result*)out);
+                           d_keys, (vp_min_max_loc_result*)out);
 }
 
 }  // extern "C"

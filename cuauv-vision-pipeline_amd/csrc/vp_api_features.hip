@@ -95,8 +95,9 @@ int pyr_run(vp_ctx* ctx, const uint8_t* d_src, const uint8_t* h_src, size_t stri
 {
     VP_TRY(ft_pattern_ready(ctx));
     const uint16_t* d_taps = reinterpret_cast<const uint16_t*>(ctx->ft.pattern + FT_PATTERN_BYTES);
-    VP_TRY(vp_ws_reserve(ctx, P.ws_bytes + 1024));
-    TAKE(d_ws, uint8_t*, P.ws_bytes);
+    vp_ws_frame W;
+    uint8_t* d_ws; W.want(&d_ws, P.ws_bytes);
+    VP_TRY(vp_ws_commit(ctx, W, "pyr_run"));
     const vp_pyr_table& T = P.T;
     uint8_t* d_img = d_ws + P.off_img;
     if (h_src) {
@@ -146,31 +147,25 @@ const char* pyr_checks(const void* src, size_t stride, int w, int h, int levels,
 }
 
 // workspace of a matcher call beyond what the caller stages: the partial results of both directions and the reverse matches
-size_t hamming_ws_bytes(const vp_hamming_plan_t& P, const vp_hamming_plan_t& R, int nt, int cross_check)
+struct hamming_bufs { void *part, *rpart; int32_t *rev, *rdist; };
+void hamming_want(vp_ws_frame& W, const vp_hamming_plan_t& P, const vp_hamming_plan_t& R, int nt, int cross_check, hamming_bufs* b)
 {
-    return vp_align(P.partial_bytes) + (cross_check ? vp_align(R.partial_bytes) + 2 * vp_align((size_t)nt * 4) : 0) + 1024;
+    b->part = b->rpart = nullptr;
+    if (P.partial_bytes) W.want(&b->part, P.partial_bytes);
+    if (!cross_check) return;
+    if (R.partial_bytes) W.want(&b->rpart, R.partial_bytes);
+    W.want(&b->rev, (size_t)nt * 4);
+    W.want(&b->rdist, (size_t)nt * 4);
 }
 
-// nq, nt >= 1.  The workspace is reserved by the caller and holds what it staged.
+// nq, nt >= 1
 int hamming_run(vp_ctx* ctx, const uint8_t* d_q, size_t qstride, int nq, const uint8_t* d_t, size_t tstride, int nt, const vp_hamming_plan_t& P,
-                const vp_hamming_plan_t& R, int k, int cross_check, int32_t* d_idx, int32_t* d_dist)
+                const vp_hamming_plan_t& R, int k, int cross_check, int32_t* d_idx, int32_t* d_dist, const hamming_bufs& b)
 {
-    void* d_part = nullptr;
-    if (P.partial_bytes) {
-        d_part = vp_ws_take(ctx, P.partial_bytes);
-        if (!d_part) return vp_fail(ctx, VP_ERR_NOMEM, "workspace exhausted: d_part");
-    }
-    VP_TRY(vpk_hamming_knn(ctx, d_q, qstride, nq, d_t, tstride, nt, P, k, d_idx, d_dist, d_part));
+    VP_TRY(vpk_hamming_knn(ctx, d_q, qstride, nq, d_t, tstride, nt, P, k, d_idx, d_dist, b.part));
     if (!cross_check) return VP_OK;
-    void* d_rpart = nullptr;
-    if (R.partial_bytes) {
-        d_rpart = vp_ws_take(ctx, R.partial_bytes);
-        if (!d_rpart) return vp_fail(ctx, VP_ERR_NOMEM, "workspace exhausted: d_rpart");
-    }
-    TAKE(d_rev, int32_t*, (size_t)nt * 4);
-    TAKE(d_rdist, int32_t*, (size_t)nt * 4);
-    VP_TRY(vpk_hamming_knn(ctx, d_t, tstride, nt, d_q, qstride, nq, R, 1, d_rev, d_rdist, d_rpart));
-    return vpk_hamming_cross(ctx, d_idx, d_rev, nq);
+    VP_TRY(vpk_hamming_knn(ctx, d_t, tstride, nt, d_q, qstride, nq, R, 1, b.rev, b.rdist, b.rpart));
+    return vpk_hamming_cross(ctx, d_idx, b.rev, nq);
 }
 
 }  // namespace
@@ -192,9 +187,10 @@ int vp_fast_u8(vp_ctx* ctx, const uint8_t* src, size_t stride, int w, int h, int
     vp_fast_plan P;
     vp_fast_make_plan(w, h, capacity, &P);
     const size_t npx = (size_t)w * h;
-    VP_TRY(vp_ws_reserve(ctx, vp_align(npx) + P.ws_bytes + 1024));
-    TAKE(d_src, uint8_t*, npx);
-    TAKE(d_ws, uint8_t*, P.ws_bytes);
+    vp_ws_frame W;
+    uint8_t* d_src; W.want(&d_src, npx);
+    uint8_t* d_ws; W.want(&d_ws, P.ws_bytes);
+    VP_TRY(vp_ws_commit(ctx, W, "vp_fast_u8"));
     VP_TRY(h2d_rows(ctx, d_src, (size_t)w, src, stride, (size_t)w, h));
     return fast_run(ctx, d_src, (size_t)w, w, h, threshold, nonmax, P, d_ws, xy_host, score_host, n_found);
 }
@@ -207,8 +203,9 @@ int vp_fast_dev(vp_ctx* ctx, const uint8_t* d_src, size_t stride, int w, int h, 
     VP_TRY(check_ctx(ctx));
     vp_fast_plan P;
     vp_fast_make_plan(w, h, capacity, &P);
-    VP_TRY(vp_ws_reserve(ctx, P.ws_bytes + 1024));
-    TAKE(d_ws, uint8_t*, P.ws_bytes);
+    vp_ws_frame W;
+    uint8_t* d_ws; W.want(&d_ws, P.ws_bytes);
+    VP_TRY(vp_ws_commit(ctx, W, "vp_fast_dev"));
     return fast_run(ctx, d_src, stride, w, h, threshold, nonmax, P, d_ws, xy_host, score_host, n_found);
 }
 
@@ -230,9 +227,10 @@ int vp_describe_u8(vp_ctx* ctx, const uint8_t* src, size_t stride, int w, int h,
     vp_describe_plan P;
     vp_describe_make_plan(w, h, n, &P);
     const size_t npx = (size_t)w * h;
-    VP_TRY(vp_ws_reserve(ctx, vp_align(npx) + P.ws_bytes + 1024));
-    TAKE(d_src, uint8_t*, npx);
-    TAKE(d_ws, uint8_t*, P.ws_bytes);
+    vp_ws_frame W;
+    uint8_t* d_src; W.want(&d_src, npx);
+    uint8_t* d_ws; W.want(&d_ws, P.ws_bytes);
+    VP_TRY(vp_ws_commit(ctx, W, "vp_describe_u8"));
     VP_TRY(h2d_rows(ctx, d_src, (size_t)w, src, stride, (size_t)w, h));
     return describe_run(ctx, d_src, (size_t)w, w, h, pts, n, P, d_ws, desc, bin, status);
 }
@@ -245,8 +243,9 @@ int vp_describe_dev(vp_ctx* ctx, const uint8_t* d_src, size_t stride, int w, int
     if (n == 0) return VP_OK;
     vp_describe_plan P;
     vp_describe_make_plan(w, h, n, &P);
-    VP_TRY(vp_ws_reserve(ctx, P.ws_bytes + 1024));
-    TAKE(d_ws, uint8_t*, P.ws_bytes);
+    vp_ws_frame W;
+    uint8_t* d_ws; W.want(&d_ws, P.ws_bytes);
+    VP_TRY(vp_ws_commit(ctx, W, "vp_describe_dev"));
     return describe_run(ctx, d_src, stride, w, h, pts, n, P, d_ws, desc, bin, status);
 }
 
@@ -317,14 +316,17 @@ int vp_hamming_knn_u8(vp_ctx* ctx, const uint8_t* query, size_t qstride, int nq,
     vp_hamming_make_plan(nq, nt, D, &P);
     vp_hamming_make_plan(nt, nq, D, &R);
     const size_t qbytes = (size_t)nq * D, tbytes = (size_t)nt * D;
-    VP_TRY(vp_ws_reserve(ctx, vp_align(qbytes) + vp_align(tbytes) + 2 * vp_align(obytes) + hamming_ws_bytes(P, R, nt, cross_check)));
-    TAKE(d_q, uint8_t*, qbytes);
-    TAKE(d_t, uint8_t*, tbytes);
-    TAKE(d_idx, int32_t*, obytes);
-    TAKE(d_dist, int32_t*, obytes);
+    vp_ws_frame W;
+    uint8_t* d_q; W.want(&d_q, qbytes);
+    uint8_t* d_t; W.want(&d_t, tbytes);
+    int32_t* d_idx; W.want(&d_idx, obytes);
+    int32_t* d_dist; W.want(&d_dist, obytes);
+    hamming_bufs b;
+    hamming_want(W, P, R, nt, cross_check, &b);
+    VP_TRY(vp_ws_commit(ctx, W, "vp_hamming_knn_u8"));
     VP_TRY(h2d_rows(ctx, d_q, (size_t)D, query, qstride, (size_t)D, nq));
     VP_TRY(h2d_rows(ctx, d_t, (size_t)D, train, tstride, (size_t)D, nt));
-    VP_TRY(hamming_run(ctx, d_q, (size_t)D, nq, d_t, (size_t)D, nt, P, R, k, cross_check, d_idx, d_dist));
+    VP_TRY(hamming_run(ctx, d_q, (size_t)D, nq, d_t, (size_t)D, nt, P, R, k, cross_check, d_idx, d_dist, b));
     VP_TRY(d2h(ctx, idx, d_idx, obytes));
     VP_TRY(d2h(ctx, dist, d_dist, obytes));
     return vp_synchronize(ctx);
@@ -348,8 +350,11 @@ int vp_hamming_knn_dev(vp_ctx* ctx, const uint8_t* d_query, size_t qstride, int 
     vp_hamming_plan_t P, R;
     vp_hamming_make_plan(nq, nt, D, &P);
     vp_hamming_make_plan(nt, nq, D, &R);
-    VP_TRY(vp_ws_reserve(ctx, hamming_ws_bytes(P, R, nt, cross_check)));
-    return hamming_run(ctx, d_query, qstride, nq, d_train, tstride, nt, P, R, k, cross_check, d_idx, d_dist);
+    vp_ws_frame W;
+    hamming_bufs b;
+    hamming_want(W, P, R, nt, cross_check, &b);
+    VP_TRY(vp_ws_commit(ctx, W, "vp_hamming_knn_dev"));
+    return hamming_run(ctx, d_query, qstride, nq, d_train, tstride, nt, P, R, k, cross_check, d_idx, d_dist, b);
 }
 
 }  // extern "C"

@@ -38,9 +38,10 @@ int vp_threshold_u8(vp_ctx* ctx, const uint8_t* src, size_t n, double thresh, do
     VP_TRY(check_ctx(ctx));
     int ithresh, imaxval;
     VP_TRY(thresh_args(ctx, "vp_threshold_u8 arguments", src, dst, n, thresh, maxval, type, &ithresh, &imaxval));
-    VP_TRY(vp_ws_reserve(ctx, 2 * vp_align(n) + 1024));
-    TAKE(d_src, uint8_t*, n);
-    TAKE(d_dst, uint8_t*, n);
+    vp_ws_frame W;
+    uint8_t* d_src; W.want(&d_src, n);
+    uint8_t* d_dst; W.want(&d_dst, n);
+    VP_TRY(vp_ws_commit(ctx, W, "vp_threshold_u8"));
     VP_TRY(h2d(ctx, d_src, src, n));
     VP_TRY(vpk_threshold_u8(ctx, d_src, n, ithresh, imaxval, type, d_dst));
     VP_TRY(d2h(ctx, dst, d_dst, n));
@@ -61,10 +62,11 @@ int vp_otsu_threshold_u8(vp_ctx* ctx, const uint8_t* src, size_t n, double maxva
     VP_TRY(check_ctx(ctx));
     int imaxval;
     VP_TRY(otsu_args(ctx, "vp_otsu_threshold_u8 arguments", src, dst, n, maxval, type, &imaxval));
-    VP_TRY(vp_ws_reserve(ctx, 2 * vp_align(n) + 2048));
-    TAKE(d_src, uint8_t*, n);
-    TAKE(d_dst, uint8_t*, n);
-    TAKE(d_hist, u32*, 1024);
+    vp_ws_frame W;
+    uint8_t* d_src; W.want(&d_src, n);
+    uint8_t* d_dst; W.want(&d_dst, n);
+    u32* d_hist; W.want(&d_hist, 1024);
+    VP_TRY(vp_ws_commit(ctx, W, "vp_otsu_threshold_u8"));
     VP_TRY(h2d(ctx, d_src, src, n));
     VP_TRY(vpk_hist_u8(ctx, d_src, n, d_hist));
     u32 h[256];
@@ -100,9 +102,10 @@ int vp_otsu_threshold_dev(vp_ctx* ctx, const uint8_t* d_src, size_t n, double ma
     int imaxval;
     VP_TRY(otsu_args(ctx, "vp_otsu_threshold_dev arguments", d_src, d_dst, n, maxval, type, &imaxval));
     if (dev_overlap(d_src, n, d_dst, n)) return vp_fail(ctx, VP_ERR_INVALID, "vp_otsu_threshold_dev: dst overlaps src");
-    VP_TRY(vp_ws_reserve(ctx, 4096));
-    TAKE(d_hist, u32*, 1024);
-    TAKE(d_it, int32_t*, 4);
+    vp_ws_frame W;
+    u32* d_hist; W.want(&d_hist, 1024);
+    int32_t* d_it; W.want(&d_it, 4);
+    VP_TRY(vp_ws_commit(ctx, W, "vp_otsu_threshold_dev"));
     VP_TRY(vpk_hist_u8(ctx, d_src, n, d_hist));
     VP_TRY(vpk_otsu_scan(ctx, d_hist, n, d_thresh, d_it));
     return vpk_threshold_u8(ctx, d_src, n, 0, imaxval, type, d_dst, d_it);
@@ -112,8 +115,9 @@ int vp_hist_u8_dev(vp_ctx* ctx, const uint8_t* d_src, size_t n, uint32_t* hist)
 {
     VP_TRY(check_ctx(ctx));
     if (!d_src || !hist || n == 0 || n > 0xffffffffull) return vp_fail(ctx, VP_ERR_INVALID, "vp_hist_u8_dev arguments");
-    VP_TRY(vp_ws_reserve(ctx, 4096));
-    TAKE(d_hist, u32*, 1024);
+    vp_ws_frame W;
+    u32* d_hist; W.want(&d_hist, 1024);
+    VP_TRY(vp_ws_commit(ctx, W, "vp_hist_u8_dev"));
     VP_TRY(vpk_hist_u8(ctx, d_src, n, d_hist));
     VP_TRY(d2h(ctx, hist, d_hist, 1024));
     return vp_synchronize(ctx);
@@ -155,11 +159,12 @@ int vp_equalize_hist_u8(vp_ctx* ctx, const uint8_t* src, int w, int h, uint8_t* 
     VP_TRY(eqhist_args(ctx, "vp_equalize_hist_u8 arguments", src, dst, w, h));
     VP_TRY(check_ctx(ctx));
     const size_t n = (size_t)w * h;
-    VP_TRY(vp_ws_reserve(ctx, 2 * vp_align(n) + 4096));
-    TAKE(d_src, uint8_t*, n);
-    TAKE(d_dst, uint8_t*, n);
-    TAKE(d_hist, u32*, 1024);
-    TAKE(d_lut, uint8_t*, 256);
+    vp_ws_frame W;
+    uint8_t* d_src; W.want(&d_src, n);
+    uint8_t* d_dst; W.want(&d_dst, n);
+    u32* d_hist; W.want(&d_hist, 1024);
+    uint8_t* d_lut; W.want(&d_lut, 256);
+    VP_TRY(vp_ws_commit(ctx, W, "vp_equalize_hist_u8"));
     VP_TRY(h2d(ctx, d_src, src, n));
     VP_TRY(vpk_equalize_hist(ctx, d_src, (size_t)w, w, h, d_hist, d_lut, d_dst));
     VP_TRY(d2h(ctx, dst, d_dst, n));
@@ -172,13 +177,13 @@ int vp_equalize_hist_dev(vp_ctx* ctx, const uint8_t* d_src, size_t src_stride, i
     VP_TRY(eqhist_args(ctx, "vp_equalize_hist_dev arguments", d_src, d_dst, w, h));
     VP_TRY(plane_dev_args(ctx, "vp_equalize_hist_dev: src_stride, or dst overlaps src", d_src, src_stride, w, h, d_dst));
     VP_TRY(check_ctx(ctx));
-    VP_TRY(vp_ws_reserve(ctx, 4096));
-    TAKE(d_hist, u32*, 1024);
-    TAKE(d_lut, uint8_t*, 256);
+    vp_ws_frame W;
+    u32* d_hist; W.want(&d_hist, 1024);
+    uint8_t* d_lut; W.want(&d_lut, 256);
+    VP_TRY(vp_ws_commit(ctx, W, "vp_equalize_hist_dev"));
     return vpk_equalize_hist(ctx, d_src, src_stride, w, h, d_hist, d_lut, d_dst);
 }
 
-static size_t clahe_ws_bytes(int tiles) { return vp_align((size_t)tiles * 256) + vp_align((size_t)tiles * 1024) + 1024; }
 
 int vp_clahe_u8(vp_ctx* ctx, const uint8_t* src, int w, int h, double clip_limit, int tiles_x, int tiles_y, uint8_t* dst)
 {
@@ -187,11 +192,12 @@ int vp_clahe_u8(vp_ctx* ctx, const uint8_t* src, int w, int h, double clip_limit
     VP_TRY(check_ctx(ctx));
     const size_t n = (size_t)w * h;
     const int tiles = tiles_x * tiles_y;
-    VP_TRY(vp_ws_reserve(ctx, 2 * vp_align(n) + clahe_ws_bytes(tiles)));
-    TAKE(d_src, uint8_t*, n);
-    TAKE(d_dst, uint8_t*, n);
-    TAKE(d_luts, uint8_t*, (size_t)tiles * 256);
-    TAKE(d_part, u32*, (size_t)tiles * 1024);
+    vp_ws_frame W;
+    uint8_t* d_src; W.want(&d_src, n);
+    uint8_t* d_dst; W.want(&d_dst, n);
+    uint8_t* d_luts; W.want(&d_luts, (size_t)tiles * 256);
+    u32* d_part; W.want(&d_part, (size_t)tiles * 1024);
+    VP_TRY(vp_ws_commit(ctx, W, "vp_clahe_u8"));
     VP_TRY(h2d(ctx, d_src, src, n));
     VP_TRY(vpk_clahe(ctx, d_src, (size_t)w, w, h, tiles_x, tiles_y, P, d_part, d_luts, d_dst));
     VP_TRY(d2h(ctx, dst, d_dst, n));
@@ -205,9 +211,10 @@ int vp_clahe_dev(vp_ctx* ctx, const uint8_t* d_src, size_t src_stride, int w, in
     VP_TRY(plane_dev_args(ctx, "vp_clahe_dev: src_stride, or dst overlaps src", d_src, src_stride, w, h, d_dst));
     VP_TRY(check_ctx(ctx));
     const int tiles = tiles_x * tiles_y;
-    VP_TRY(vp_ws_reserve(ctx, clahe_ws_bytes(tiles)));
-    TAKE(d_luts, uint8_t*, (size_t)tiles * 256);
-    TAKE(d_part, u32*, (size_t)tiles * 1024);
+    vp_ws_frame W;
+    uint8_t* d_luts; W.want(&d_luts, (size_t)tiles * 256);
+    u32* d_part; W.want(&d_part, (size_t)tiles * 1024);
+    VP_TRY(vp_ws_commit(ctx, W, "vp_clahe_dev"));
     return vpk_clahe(ctx, d_src, src_stride, w, h, tiles_x, tiles_y, P, d_part, d_luts, d_dst);
 }
 
@@ -236,11 +243,12 @@ int vp_gaussian_blur_u8(vp_ctx* ctx, const uint8_t* src, int w, int h, int cn, i
     uint16_t taps[1024];
     vp_gaussian_taps(kw, sigma1, taps);
     vp_gaussian_taps(kh, sigma2, taps + kw);
-    VP_TRY(vp_ws_reserve(ctx, 2 * vp_align(nbytes) + vp_align(nbytes * 2) + 4096));
-    TAKE(d_src, uint8_t*, nbytes);
-    TAKE(d_dst, uint8_t*, nbytes);
-    TAKE(d_tmp, uint16_t*, nbytes * 2);
-    TAKE(d_taps, uint16_t*, 2048);
+    vp_ws_frame W;
+    uint8_t* d_src; W.want(&d_src, nbytes);
+    uint8_t* d_dst; W.want(&d_dst, nbytes);
+    uint16_t* d_tmp; W.want(&d_tmp, nbytes * 2);
+    uint16_t* d_taps; W.want(&d_taps, 2048);
+    VP_TRY(vp_ws_commit(ctx, W, "vp_gaussian_blur_u8"));
     VP_TRY(h2d(ctx, d_src, src, nbytes));
     VP_TRY(h2d(ctx, d_taps, taps, (size_t)(kw + kh) * 2));
     VP_HIP(ctx, hipStreamSynchronize(ctx->stream));   // taps is a local array
@@ -263,8 +271,11 @@ int vp_gaussian_blur_dev(vp_ctx* ctx, const uint8_t* d_src, size_t src_stride, i
         return VP_OK;
     }
     const bool one = vp_gaussian_onepass_fits(kw, kh) && (ctx->opt.v[VP_OPT_BLUR_ONEPASS] == 1 || (ctx->opt.v[VP_OPT_BLUR_ONEPASS] < 0 && blur_onepass_measured_faster(cn, kw, kh)));
-    VP_TRY(vp_ws_reserve(ctx, (one ? 0 : vp_align(nbytes * 2)) + 4096));
-    TAKE(d_taps, uint16_t*, 2048);
+    vp_ws_frame W;
+    uint16_t* d_taps; W.want(&d_taps, 2048);
+    uint16_t* d_tmp = nullptr;
+    if (!one) W.want(&d_tmp, nbytes * 2);
+    VP_TRY(vp_ws_commit(ctx, W, "vp_gaussian_blur_dev"));
     // the taps go over in a pinned chunk of the context's ring: the copy is enqueued, nothing waits for it
     int slot = -1;
     uint16_t* taps = reinterpret_cast<uint16_t*>(vp_ring_take(ctx, 2048, &slot));
@@ -274,10 +285,7 @@ int vp_gaussian_blur_dev(vp_ctx* ctx, const uint8_t* d_src, size_t src_stride, i
     int rc = h2d(ctx, d_taps, taps, (size_t)(kw + kh) * 2);
     if (rc == VP_OK) {
         if (one) rc = vpk_gaussian_blur_onepass(ctx, d_src, src_stride, w, h, cn, d_taps, kw, kh, d_dst);
-        else {
-            uint16_t* d_tmp = (uint16_t*)vp_ws_take(ctx, nbytes * 2);
-            rc = d_tmp ? vpk_gaussian_blur(ctx, d_src, w, h, cn, d_taps, kw, kh, d_tmp, d_dst, src_stride) : vp_fail(ctx, VP_ERR_NOMEM, "workspace exhausted: d_tmp");
-        }
+        else rc = vpk_gaussian_blur(ctx, d_src, w, h, cn, d_taps, kw, kh, d_tmp, d_dst, src_stride);
     }
     vp_ring_done(ctx, slot);
     return rc;
@@ -296,9 +304,10 @@ int vp_median_blur_u8(vp_ctx* ctx, const uint8_t* src, int w, int h, int cn, int
     VP_TRY(check_ctx(ctx));
     VP_TRY(median_args(ctx, "vp_median_blur_u8 arguments", src, dst, w, h, cn, ksize));
     const size_t rowbytes = (size_t)w * cn, nbytes = rowbytes * h;
-    VP_TRY(vp_ws_reserve(ctx, 2 * vp_align(nbytes) + 1024));
-    TAKE(d_src, uint8_t*, nbytes);
-    TAKE(d_dst, uint8_t*, nbytes);
+    vp_ws_frame W;
+    uint8_t* d_src; W.want(&d_src, nbytes);
+    uint8_t* d_dst; W.want(&d_dst, nbytes);
+    VP_TRY(vp_ws_commit(ctx, W, "vp_median_blur_u8"));
     VP_TRY(h2d(ctx, d_src, src, nbytes));
     VP_TRY(vpk_median_blur(ctx, d_src, rowbytes, w, h, cn, ksize, 0, nullptr, d_dst, nullptr, nullptr));
     VP_TRY(d2h(ctx, dst, d_dst, nbytes));
@@ -348,9 +357,10 @@ int vp_deriv_u8(vp_ctx* ctx, const uint8_t* src, int w, int h, int cn, int op, i
     vp_deriv_plan P;
     VP_TRY(deriv_args(ctx, "vp_deriv_u8 arguments", src, dst, dst, w, h, cn, op == VP_DV_OP_SPATIAL_GRADIENT ? -1 : op, dx, dy, ksize, ddepth, border, &P));
     const size_t rowbytes = (size_t)w * cn, nbytes = rowbytes * h, obytes = nbytes * P.esize;
-    VP_TRY(vp_ws_reserve(ctx, vp_align(nbytes) + vp_align(obytes) + 1024));
-    TAKE(d_src, uint8_t*, nbytes);
-    TAKE(d_dst, uint8_t*, obytes);
+    vp_ws_frame W;
+    uint8_t* d_src; W.want(&d_src, nbytes);
+    uint8_t* d_dst; W.want(&d_dst, obytes);
+    VP_TRY(vp_ws_commit(ctx, W, "vp_deriv_u8"));
     VP_TRY(h2d(ctx, d_src, src, nbytes));
     VP_TRY(vpk_deriv(ctx, d_src, rowbytes, w, h, cn, P, d_dst, nullptr));
     VP_TRY(d2h(ctx, dst, d_dst, obytes));
@@ -372,10 +382,11 @@ int vp_spatial_gradient_u8(vp_ctx* ctx, const uint8_t* src, int w, int h, int ks
     vp_deriv_plan P;
     VP_TRY(deriv_args(ctx, "vp_spatial_gradient_u8 arguments", src, dx, dy, w, h, 1, VP_DV_OP_SPATIAL_GRADIENT, 1, 1, ksize, VP_DEPTH_16S, border, &P));
     const size_t nbytes = (size_t)w * h, obytes = nbytes * 2;
-    VP_TRY(vp_ws_reserve(ctx, vp_align(nbytes) + 2 * vp_align(obytes) + 1024));
-    TAKE(d_src, uint8_t*, nbytes);
-    TAKE(d_dx, uint8_t*, obytes);
-    TAKE(d_dy, uint8_t*, obytes);
+    vp_ws_frame W;
+    uint8_t* d_src; W.want(&d_src, nbytes);
+    uint8_t* d_dx; W.want(&d_dx, obytes);
+    uint8_t* d_dy; W.want(&d_dy, obytes);
+    VP_TRY(vp_ws_commit(ctx, W, "vp_spatial_gradient_u8"));
     VP_TRY(h2d(ctx, d_src, src, nbytes));
     VP_TRY(vpk_deriv(ctx, d_src, (size_t)w, w, h, 1, P, d_dx, d_dy));
     VP_TRY(d2h(ctx, dx, d_dx, obytes));
@@ -408,9 +419,10 @@ int vp_convert_scale_abs_u8(vp_ctx* ctx, const void* src, int depth, size_t n, u
     VP_TRY(check_ctx(ctx));
     size_t esize;
     VP_TRY(csa_args(ctx, "vp_convert_scale_abs_u8 arguments", src, dst, depth, n, &esize));
-    VP_TRY(vp_ws_reserve(ctx, vp_align(n * esize) + vp_align(n) + 1024));
-    TAKE(d_src, uint8_t*, n * esize);
-    TAKE(d_dst, uint8_t*, n);
+    vp_ws_frame W;
+    uint8_t* d_src; W.want(&d_src, n * esize);
+    uint8_t* d_dst; W.want(&d_dst, n);
+    VP_TRY(vp_ws_commit(ctx, W, "vp_convert_scale_abs_u8"));
     VP_TRY(h2d(ctx, d_src, src, n * esize));
     VP_TRY(vpk_convert_scale_abs(ctx, d_src, depth, n, d_dst));
     VP_TRY(d2h(ctx, dst, d_dst, n));
@@ -471,15 +483,13 @@ int vp_box_filter_u8(vp_ctx* ctx, const uint8_t* src, int w, int h, int cn, int 
     VP_TRY(check_ctx(ctx));
     vp_box_plan P;
     VP_TRY(box_args(ctx, "vp_box_filter_u8 arguments", src, dst, w, h, cn, kw, kh, normalize, ddepth, border, &P));
-    const size_t rowbytes = (size_t)w * cn, nbytes = rowbytes * h, obytes = nbytes * P.esize, mbytes = vp_box_ws_bytes(w, h, cn, P);
-    VP_TRY(vp_ws_reserve(ctx, vp_align(nbytes) + vp_align(obytes) + vp_align(mbytes) + 1024));
-    TAKE(d_src, uint8_t*, nbytes);
-    TAKE(d_dst, uint8_t*, obytes);
+    const size_t rowbytes = (size_t)w * cn, nbytes = rowbytes * h, obytes = nbytes * P.esize, mbytes = vp_box_mid_bytes(w, h, cn, P);
+    vp_ws_frame W;
+    uint8_t* d_src; W.want(&d_src, nbytes);
+    uint8_t* d_dst; W.want(&d_dst, obytes);
     uint16_t* d_mid = nullptr;
-    if (mbytes) {
-        d_mid = (uint16_t*)vp_ws_take(ctx, mbytes);
-        if (!d_mid) return vp_fail(ctx, VP_ERR_NOMEM, "workspace exhausted: d_mid");
-    }
+    if (mbytes) W.want(&d_mid, mbytes);
+    VP_TRY(vp_ws_commit(ctx, W, "vp_box_filter_u8"));
     VP_TRY(h2d(ctx, d_src, src, nbytes));
     VP_TRY(vpk_box_filter(ctx, d_src, rowbytes, w, h, cn, P, d_mid, d_dst));
     VP_TRY(d2h(ctx, dst, d_dst, obytes));
@@ -491,14 +501,14 @@ int vp_box_filter_dev(vp_ctx* ctx, const uint8_t* d_src, size_t src_stride, int 
     VP_TRY(check_ctx(ctx));
     vp_box_plan P;
     VP_TRY(box_args(ctx, "vp_box_filter_dev arguments", d_src, d_dst, w, h, cn, kw, kh, normalize, ddepth, border, &P));
-    const size_t rowbytes = (size_t)w * cn, mbytes = vp_box_ws_bytes(w, h, cn, P);
+    const size_t rowbytes = (size_t)w * cn, mbytes = vp_box_mid_bytes(w, h, cn, P);
     VP_TRY(box_dev_args(ctx, "vp_box_filter_dev: src_stride, dst is not aligned to its element, or dst overlaps src", d_src, src_stride, rowbytes, h, d_dst,
                         rowbytes * h * P.esize, P.esize));
     uint16_t* d_mid = nullptr;
     if (mbytes) {
-        VP_TRY(vp_ws_reserve(ctx, vp_align(mbytes) + 1024));
-        d_mid = (uint16_t*)vp_ws_take(ctx, mbytes);
-        if (!d_mid) return vp_fail(ctx, VP_ERR_NOMEM, "workspace exhausted: d_mid");
+        vp_ws_frame W;
+        W.want(&d_mid, mbytes);
+        VP_TRY(vp_ws_commit(ctx, W, "vp_box_filter_dev"));
     }
     return vpk_box_filter(ctx, d_src, src_stride, w, h, cn, P, d_mid, d_dst);
 }
@@ -514,9 +524,10 @@ int vp_pyr_down_u8(vp_ctx* ctx, const uint8_t* src, int w, int h, int cn, int bo
     VP_TRY(check_ctx(ctx));
     VP_TRY(pyr_args(ctx, "vp_pyr_down_u8 arguments", src, dst, w, h, cn, border, true));
     const size_t nbytes = (size_t)w * cn * h, obytes = (size_t)((w + 1) / 2) * cn * ((h + 1) / 2);
-    VP_TRY(vp_ws_reserve(ctx, vp_align(nbytes) + vp_align(obytes) + 1024));
-    TAKE(d_src, uint8_t*, nbytes);
-    TAKE(d_dst, uint8_t*, obytes);
+    vp_ws_frame W;
+    uint8_t* d_src; W.want(&d_src, nbytes);
+    uint8_t* d_dst; W.want(&d_dst, obytes);
+    VP_TRY(vp_ws_commit(ctx, W, "vp_pyr_down_u8"));
     VP_TRY(h2d(ctx, d_src, src, nbytes));
     VP_TRY(vpk_pyr_down(ctx, d_src, (size_t)w * cn, w, h, cn, border & ~VP_BORDER_ISOLATED, d_dst));
     VP_TRY(d2h(ctx, dst, d_dst, obytes));
@@ -537,9 +548,10 @@ int vp_pyr_up_u8(vp_ctx* ctx, const uint8_t* src, int w, int h, int cn, uint8_t*
     VP_TRY(check_ctx(ctx));
     VP_TRY(pyr_args(ctx, "vp_pyr_up_u8 arguments", src, dst, w, h, cn, 0, false));
     const size_t nbytes = (size_t)w * cn * h, obytes = 4 * nbytes;
-    VP_TRY(vp_ws_reserve(ctx, vp_align(nbytes) + vp_align(obytes) + 1024));
-    TAKE(d_src, uint8_t*, nbytes);
-    TAKE(d_dst, uint8_t*, obytes);
+    vp_ws_frame W;
+    uint8_t* d_src; W.want(&d_src, nbytes);
+    uint8_t* d_dst; W.want(&d_dst, obytes);
+    VP_TRY(vp_ws_commit(ctx, W, "vp_pyr_up_u8"));
     VP_TRY(h2d(ctx, d_src, src, nbytes));
     VP_TRY(vpk_pyr_up(ctx, d_src, (size_t)w * cn, w, h, cn, d_dst));
     VP_TRY(d2h(ctx, dst, d_dst, obytes));
@@ -566,9 +578,10 @@ int vp_integral_u8(vp_ctx* ctx, const uint8_t* src, int w, int h, int cn, int32_
     VP_TRY(check_ctx(ctx));
     VP_TRY(integral_args(ctx, "vp_integral_u8 arguments", src, dst, w, h, cn));
     const size_t nbytes = (size_t)w * cn * h, obytes = (size_t)(w + 1) * cn * (h + 1) * 4;
-    VP_TRY(vp_ws_reserve(ctx, vp_align(nbytes) + vp_align(obytes) + 1024));
-    TAKE(d_src, uint8_t*, nbytes);
-    TAKE(d_dst, int32_t*, obytes);
+    vp_ws_frame W;
+    uint8_t* d_src; W.want(&d_src, nbytes);
+    int32_t* d_dst; W.want(&d_dst, obytes);
+    VP_TRY(vp_ws_commit(ctx, W, "vp_integral_u8"));
     VP_TRY(h2d(ctx, d_src, src, nbytes));
     VP_TRY(vpk_integral(ctx, d_src, (size_t)w * cn, w, h, cn, d_dst));
     VP_TRY(d2h(ctx, dst, d_dst, obytes));
@@ -597,9 +610,10 @@ int vp_resize_u8_scaled(vp_ctx* ctx, const uint8_t* src, int w, int h, int cn, i
     VP_TRY(check_ctx(ctx));
     VP_TRY(resize_args(ctx, "vp_resize_u8 arguments", src, dst, w, h, cn, dw, dh, inv_sx, inv_sy));
     const size_t sbytes = (size_t)w * h * cn, dbytes = (size_t)dw * dh * cn;
-    VP_TRY(vp_ws_reserve(ctx, vp_align(sbytes) + vp_align(dbytes) + 1024));
-    TAKE(d_src, uint8_t*, sbytes);
-    TAKE(d_dst, uint8_t*, dbytes);
+    vp_ws_frame W;
+    uint8_t* d_src; W.want(&d_src, sbytes);
+    uint8_t* d_dst; W.want(&d_dst, dbytes);
+    VP_TRY(vp_ws_commit(ctx, W, "vp_resize_u8_scaled"));
     VP_TRY(h2d(ctx, d_src, src, sbytes));
     VP_TRY(vpk_resize_u8(ctx, d_src, w, h, cn, dw, dh, inv_sx, inv_sy, d_dst));
     VP_TRY(d2h(ctx, dst, d_dst, dbytes));
@@ -643,9 +657,10 @@ int vp_warp_affine_u8(vp_ctx* ctx, const uint8_t* src, int w, int h, int cn, con
     VP_TRY(check_ctx(ctx));
     VP_TRY(warp_args(ctx, "vp_warp_affine_u8 arguments", src, dst, w, h, cn, m23, flags, border_mode, dw, dh));
     const size_t sbytes = (size_t)w * h * cn, dbytes = (size_t)dw * dh * cn;
-    VP_TRY(vp_ws_reserve(ctx, vp_align(sbytes) + vp_align(dbytes) + 1024));
-    TAKE(d_src, uint8_t*, sbytes);
-    TAKE(d_dst, uint8_t*, dbytes);
+    vp_ws_frame W;
+    uint8_t* d_src; W.want(&d_src, sbytes);
+    uint8_t* d_dst; W.want(&d_dst, dbytes);
+    VP_TRY(vp_ws_commit(ctx, W, "vp_warp_affine_u8"));
     VP_TRY(h2d(ctx, d_src, src, sbytes));
     VP_TRY(vpk_warp_affine_u8(ctx, d_src, w, h, cn, m23, (flags & VP_WARP_INVERSE_MAP) != 0, border_mode, border_value, d_dst, dw, dh));
     VP_TRY(d2h(ctx, dst, d_dst, dbytes));
@@ -729,15 +744,13 @@ int vp_remap_u8(vp_ctx* ctx, const uint8_t* src, int w, int h, int cn, const flo
     VP_TRY(gather_args(ctx, "vp_remap_u8 arguments", src, dst, w, h, cn, mw, mh, interp, border_mode));
     if (!mapx) return vp_fail(ctx, VP_ERR_INVALID, "vp_remap_u8: no map");
     const size_t n = (size_t)mw * mh, sbytes = (size_t)w * h * cn, dbytes = n * cn, xbytes = n * (mapy ? 4 : 8), ybytes = mapy ? n * 4 : 0;
-    VP_TRY(vp_ws_reserve(ctx, vp_align(sbytes) + vp_align(dbytes) + vp_align(xbytes) + vp_align(ybytes) + 1024));
-    TAKE(d_src, uint8_t*, sbytes);
-    TAKE(d_dst, uint8_t*, dbytes);
-    TAKE(d_mx, float*, xbytes);
+    vp_ws_frame W;
+    uint8_t* d_src; W.want(&d_src, sbytes);
+    uint8_t* d_dst; W.want(&d_dst, dbytes);
+    float* d_mx; W.want(&d_mx, xbytes);
     float* d_my = nullptr;
-    if (mapy) {
-        d_my = (float*)vp_ws_take(ctx, ybytes);
-        if (!d_my) return vp_fail(ctx, VP_ERR_NOMEM, "workspace exhausted: d_my");
-    }
+    if (mapy) W.want(&d_my, ybytes);
+    VP_TRY(vp_ws_commit(ctx, W, "vp_remap_u8"));
     VP_TRY(h2d(ctx, d_src, src, sbytes));
     VP_TRY(h2d(ctx, d_mx, mapx, xbytes));
     if (mapy) VP_TRY(h2d(ctx, d_my, mapy, ybytes));
@@ -761,9 +774,10 @@ int vp_warp_perspective_u8(vp_ctx* ctx, const uint8_t* src, int w, int h, int cn
     VP_TRY(check_ctx(ctx));
     VP_TRY(wp_args(ctx, "vp_warp_perspective_u8 arguments", src, dst, w, h, cn, m33, flags, border_mode, dw, dh));
     const size_t sbytes = (size_t)w * h * cn, dbytes = (size_t)dw * dh * cn;
-    VP_TRY(vp_ws_reserve(ctx, vp_align(sbytes) + vp_align(dbytes) + 1024));
-    TAKE(d_src, uint8_t*, sbytes);
-    TAKE(d_dst, uint8_t*, dbytes);
+    vp_ws_frame W;
+    uint8_t* d_src; W.want(&d_src, sbytes);
+    uint8_t* d_dst; W.want(&d_dst, dbytes);
+    VP_TRY(vp_ws_commit(ctx, W, "vp_warp_perspective_u8"));
     VP_TRY(h2d(ctx, d_src, src, sbytes));
     VP_TRY(vpk_warp_perspective(ctx, d_src, 0, w, h, cn, m33, (flags & VP_WARP_INVERSE_MAP) != 0, (flags & VP_INTER_LINEAR) != 0, border_mode, border_value, d_dst,
                                 dw, dh));
@@ -803,10 +817,11 @@ int vp_adaptive_threshold_mean_u8(vp_ctx* ctx, const uint8_t* src, int w, int h,
     VP_TRY(adaptive_args(ctx, "vp_adaptive_threshold_mean_u8 arguments", src, dst, w, h, max_value, type, block, 151, c, &imax, &idelta));
     const size_t npx = (size_t)w * h;
     if (max_value < 0) { memset(dst, 0, npx); return VP_OK; }
-    VP_TRY(vp_ws_reserve(ctx, 2 * vp_align(npx) + vp_align(npx * 2) + 1024));
-    TAKE(d_src, uint8_t*, npx);
-    TAKE(d_dst, uint8_t*, npx);
-    TAKE(d_tmp, uint16_t*, npx * 2);
+    vp_ws_frame W;
+    uint8_t* d_src; W.want(&d_src, npx);
+    uint8_t* d_dst; W.want(&d_dst, npx);
+    uint16_t* d_tmp; W.want(&d_tmp, npx * 2);
+    VP_TRY(vp_ws_commit(ctx, W, "vp_adaptive_threshold_mean_u8"));
     VP_TRY(h2d(ctx, d_src, src, npx));
     VP_TRY(vpk_adaptive_threshold_mean(ctx, d_src, w, h, imax, idelta, type == VP_THRESH_BINARY_INV, block, d_tmp, d_dst));
     VP_TRY(d2h(ctx, dst, d_dst, npx));
@@ -826,20 +841,20 @@ int vp_adaptive_threshold_mean_dev(vp_ctx* ctx, const uint8_t* d_src, size_t src
         VP_HIP(ctx, hipMemsetAsync(d_dst, 0, npx, ctx->stream));
         return VP_OK;
     }
-    VP_TRY(vp_ws_reserve(ctx, vp_align(npx * 2) + 1024));
-    TAKE(d_tmp, uint16_t*, npx * 2);
+    vp_ws_frame W;
+    uint16_t* d_tmp; W.want(&d_tmp, npx * 2);
+    VP_TRY(vp_ws_commit(ctx, W, "vp_adaptive_threshold_mean_dev"));
     return vpk_adaptive_threshold_mean(ctx, d_src, w, h, imax, idelta, type == VP_THRESH_BINARY_INV, block, d_tmp, d_dst, src_stride);
 }
 
 // n frames in HBM -> packed (n, h, w) dst in HBM, enqueued on the context's stream; max_value < 0 gives zeros, as cv2 does
 static int agauss_run(vp_ctx* ctx, const uint8_t* d_src, size_t stride, size_t fstride, int n, int w, int h, double max_value, int imax, int idelta, int inv,
-                      int block, uint8_t* d_dst)
+                      int block, uint64_t* d_tmp, uint8_t* d_dst)
 {
     if (max_value < 0) {
         VP_HIP(ctx, hipMemsetAsync(d_dst, 0, (size_t)n * w * h, ctx->stream));
         return VP_OK;
     }
-    TAKE(d_tmp, uint64_t*, vp_agauss_ws_bytes(w, h, n));
     return vpk_adaptive_threshold_gaussian(ctx, d_src, stride, fstride, n, w, h, imax, idelta, inv, block, d_tmp, d_dst);
 }
 
@@ -850,11 +865,13 @@ int vp_adaptive_threshold_gaussian_u8(vp_ctx* ctx, const uint8_t* src, int w, in
     VP_TRY(adaptive_args(ctx, "vp_adaptive_threshold_gaussian arguments", src, dst, w, h, max_value, type, block, VP_AGAUSS_MAX_BLOCK, c, &imax, &idelta));
     const size_t npx = (size_t)w * h;
     if (max_value < 0) { memset(dst, 0, npx); return VP_OK; }
-    VP_TRY(vp_ws_reserve(ctx, 2 * vp_align(npx) + vp_agauss_ws_bytes(w, h, 1) + 1024));
-    TAKE(d_src, uint8_t*, npx);
-    TAKE(d_dst, uint8_t*, npx);
+    vp_ws_frame W;
+    uint8_t* d_src; W.want(&d_src, npx);
+    uint8_t* d_dst; W.want(&d_dst, npx);
+    uint64_t* d_tmp; W.want(&d_tmp, vp_agauss_tmp_bytes(w, h, 1));
+    VP_TRY(vp_ws_commit(ctx, W, "vp_adaptive_threshold_gaussian_u8"));
     VP_TRY(h2d(ctx, d_src, src, npx));
-    VP_TRY(agauss_run(ctx, d_src, (size_t)w, npx, 1, w, h, max_value, imax, idelta, type == VP_THRESH_BINARY_INV, block, d_dst));
+    VP_TRY(agauss_run(ctx, d_src, (size_t)w, npx, 1, w, h, max_value, imax, idelta, type == VP_THRESH_BINARY_INV, block, d_tmp, d_dst));
     VP_TRY(d2h(ctx, dst, d_dst, npx));
     return vp_synchronize(ctx);
 }
@@ -866,8 +883,10 @@ int vp_adaptive_threshold_gaussian_dev(vp_ctx* ctx, const uint8_t* d_src, size_t
     int imax, idelta;
     VP_TRY(adaptive_args(ctx, "vp_adaptive_threshold_gaussian arguments", d_src, d_dst, w, h, max_value, type, block, VP_AGAUSS_MAX_BLOCK, c, &imax, &idelta));
     if (src_stride < (size_t)w) return vp_fail(ctx, VP_ERR_INVALID, "vp_adaptive_threshold_gaussian_dev src_stride");
-    VP_TRY(vp_ws_reserve(ctx, vp_agauss_ws_bytes(w, h, 1) + 1024));
-    return agauss_run(ctx, d_src, src_stride, src_stride * h, 1, w, h, max_value, imax, idelta, type == VP_THRESH_BINARY_INV, block, d_dst);
+    vp_ws_frame W;
+    uint64_t* d_tmp; W.want(&d_tmp, vp_agauss_tmp_bytes(w, h, 1));
+    VP_TRY(vp_ws_commit(ctx, W, "vp_adaptive_threshold_gaussian_dev"));
+    return agauss_run(ctx, d_src, src_stride, src_stride * h, 1, w, h, max_value, imax, idelta, type == VP_THRESH_BINARY_INV, block, d_tmp, d_dst);
 }
 
 int vp_adaptive_threshold_gaussian_batch_dev(vp_ctx* ctx, const uint8_t* d_src, size_t src_stride, size_t frame_stride, int n, int w, int h,
@@ -878,8 +897,10 @@ int vp_adaptive_threshold_gaussian_batch_dev(vp_ctx* ctx, const uint8_t* d_src, 
     VP_TRY(adaptive_args(ctx, "vp_adaptive_threshold_gaussian arguments", d_src, d_dst, w, h, max_value, type, block, VP_AGAUSS_MAX_BLOCK, c, &imax, &idelta));
     if (n <= 0 || n > 65535 || src_stride < (size_t)w || (n > 1 && frame_stride < src_stride * h))
         return vp_fail(ctx, VP_ERR_INVALID, "vp_adaptive_threshold_gaussian_batch_dev strides / frame count");
-    VP_TRY(vp_ws_reserve(ctx, vp_agauss_ws_bytes(w, h, n) + 1024));
-    return agauss_run(ctx, d_src, src_stride, frame_stride, n, w, h, max_value, imax, idelta, type == VP_THRESH_BINARY_INV, block, d_dst);
+    vp_ws_frame W;
+    uint64_t* d_tmp; W.want(&d_tmp, vp_agauss_tmp_bytes(w, h, n));
+    VP_TRY(vp_ws_commit(ctx, W, "vp_adaptive_threshold_gaussian_batch_dev"));
+    return agauss_run(ctx, d_src, src_stride, frame_stride, n, w, h, max_value, imax, idelta, type == VP_THRESH_BINARY_INV, block, d_tmp, d_dst);
 }
 
 // cv2.Canny thresholds: ordered, floored, held inside what the integer gradient magnitude can reach
@@ -899,11 +920,14 @@ int vp_canny_u8(vp_ctx* ctx, const uint8_t* src, int w, int h, int cn, double t1
     int low, high;
     VP_TRY(canny_args(ctx, "vp_canny_u8 arguments", src, dst, w, h, cn, t1, t2, &low, &high));
     const size_t npx = (size_t)w * h;
-    VP_TRY(vp_ws_reserve(ctx, vp_align(npx * cn) + vp_align(npx) + vp_canny_ws_bytes(w, h) + 1024));
-    TAKE(d_src, uint8_t*, npx * cn);
-    TAKE(d_dst, uint8_t*, npx);
+    vp_ws_frame W;
+    uint8_t* d_src; W.want(&d_src, npx * cn);
+    uint8_t* d_dst; W.want(&d_dst, npx);
+    vp_canny_ws cw;
+    vp_canny_want(W, w, h, &cw);
+    VP_TRY(vp_ws_commit(ctx, W, "vp_canny_u8"));
     VP_TRY(h2d(ctx, d_src, src, npx * cn));
-    VP_TRY(vpk_canny_u8(ctx, d_src, w, h, cn, low, high, d_dst));
+    VP_TRY(vpk_canny_u8(ctx, d_src, w, h, cn, low, high, d_dst, cw));
     VP_TRY(d2h(ctx, dst, d_dst, npx));
     return vp_synchronize(ctx);
 }
@@ -917,14 +941,18 @@ int vp_canny_u8_dev(vp_ctx* ctx, const uint8_t* d_src, size_t src_stride, int w,
     if (src_stride < (size_t)w * cn) return vp_fail(ctx, VP_ERR_INVALID, "vp_canny_u8_dev src_stride");
     const size_t npx = (size_t)w * h;
     const bool packed = src_stride == (size_t)w * cn;
-    VP_TRY(vp_ws_reserve(ctx, (packed ? 0 : vp_align(npx * cn)) + vp_canny_ws_bytes(w, h) + 1024));
+    vp_ws_frame W;
+    uint8_t* d_pk = nullptr;
+    if (!packed) W.want(&d_pk, npx * cn);
+    vp_canny_ws cw;
+    vp_canny_want(W, w, h, &cw);
+    VP_TRY(vp_ws_commit(ctx, W, "vp_canny_u8_dev"));
     const uint8_t* src = d_src;
     if (!packed) {
-        TAKE(d_pk, uint8_t*, npx * cn);
         VP_HIP(ctx, hipMemcpy2DAsync(d_pk, (size_t)w * cn, d_src, src_stride, (size_t)w * cn, h, hipMemcpyDeviceToDevice, ctx->stream));
         src = d_pk;
     }
-    return vpk_canny_u8(ctx, src, w, h, cn, low, high, d_dst);
+    return vpk_canny_u8(ctx, src, w, h, cn, low, high, d_dst, cw);
 }
 
 static int hough_args(vp_ctx* ctx, const void* src, int w, int h, float* lines, int max_lines, int* n_lines)
@@ -990,9 +1018,10 @@ int vp_letterbox_u8_f32(vp_ctx* ctx, const uint8_t* src, int w, int h, int dw, i
     VP_TRY(check_ctx(ctx));
     VP_TRY(check_lb(ctx, src, dst, w, h, dw, dh, pad));
     const size_t sbytes = (size_t)w * h * 3, dbytes = (size_t)dw * dh * 12;
-    VP_TRY(vp_ws_reserve(ctx, vp_align(sbytes) + vp_align(dbytes) + 1024));
-    TAKE(d_src, uint8_t*, sbytes);
-    TAKE(d_dst, float*, dbytes);
+    vp_ws_frame W;
+    uint8_t* d_src; W.want(&d_src, sbytes);
+    float* d_dst; W.want(&d_dst, dbytes);
+    VP_TRY(vp_ws_commit(ctx, W, "vp_letterbox_u8_f32"));
     VP_TRY(h2d(ctx, d_src, src, sbytes));
     VP_TRY(vpk_letterbox(ctx, d_src, w, h, dw, dh, pad, d_dst, geom_out));
     VP_TRY(d2h(ctx, dst, d_dst, dbytes));
@@ -1015,14 +1044,17 @@ int vp_nms_f32(vp_ctx* ctx, const float* boxes, const float* scores, int n, floa
     *n_keep_out = 0;
     if (n == 0 || max_keep == 0) return VP_OK;
     const int bs = rotated ? 5 : 4;
-    VP_TRY(vp_ws_reserve(ctx, vp_align((size_t)n * bs * 4) + vp_align((size_t)n * 4) + vp_align((size_t)max_keep * 4) + vp_nms_ws_bytes(n) + 2048));
-    TAKE(d_boxes, float*, (size_t)n * bs * 4);
-    TAKE(d_scores, float*, (size_t)n * 4);
-    TAKE(d_keep, int*, (size_t)max_keep * 4);
-    TAKE(d_nk, int*, 4);
+    vp_ws_frame W;
+    float* d_boxes; W.want(&d_boxes, (size_t)n * bs * 4);
+    float* d_scores; W.want(&d_scores, (size_t)n * 4);
+    int* d_keep; W.want(&d_keep, (size_t)max_keep * 4);
+    int* d_nk; W.want(&d_nk, 4);
+    vp_nms_ws nw;
+    vp_nms_want(W, n, &nw);
+    VP_TRY(vp_ws_commit(ctx, W, "vp_nms_f32"));
     VP_TRY(h2d(ctx, d_boxes, boxes, (size_t)n * bs * 4));
     VP_TRY(h2d(ctx, d_scores, scores, (size_t)n * 4));
-    VP_TRY(vpk_nms(ctx, d_boxes, d_scores, n, thr, rotated ? 1 : 0, max_keep, d_keep, d_nk));
+    VP_TRY(vpk_nms(ctx, d_boxes, d_scores, n, thr, rotated ? 1 : 0, max_keep, d_keep, d_nk, nw));
     VP_TRY(d2h(ctx, n_keep_out, d_nk, 4));
     VP_TRY(vp_synchronize(ctx));
     if (*n_keep_out > 0) { VP_TRY(d2h(ctx, keep_out, d_keep, (size_t)*n_keep_out * 4)); VP_TRY(vp_synchronize(ctx)); }
@@ -1034,8 +1066,11 @@ int vp_nms_dev(vp_ctx* ctx, const float* boxes, const float* scores, int n, floa
 {
     VP_TRY(check_ctx(ctx));
     if (n < 0 || max_keep <= 0 || !n_keep || !keep_out || (n > 0 && (!boxes || !scores))) return vp_fail(ctx, VP_ERR_INVALID, "vp_nms_dev arguments");
-    VP_TRY(vp_ws_reserve(ctx, vp_nms_ws_bytes(n > 0 ? n : 1) + 2048));
-    return vpk_nms(ctx, boxes, scores, n, thr, rotated ? 1 : 0, max_keep, keep_out, n_keep);
+    vp_ws_frame W;
+    vp_nms_ws nw;
+    vp_nms_want(W, n, &nw);
+    VP_TRY(vp_ws_commit(ctx, W, "vp_nms_dev"));
+    return vpk_nms(ctx, boxes, scores, n, thr, rotated ? 1 : 0, max_keep, keep_out, n_keep, nw);
 }
 
 // ---- element-wise operators on device images (kernels: vp_elementwise.hip) ----------------------------------------------------------
@@ -1107,8 +1142,9 @@ int vp_count_nonzero_u8_dev(vp_ctx* ctx, const uint8_t* d_src, size_t n, uint64_
 {
     VP_TRY(check_ctx(ctx));
     if (!d_src || !count || n == 0 || n > VP_EW_MAX) return vp_fail(ctx, VP_ERR_INVALID, "vp_count_nonzero_u8_dev arguments");
-    VP_TRY(vp_ws_reserve(ctx, 4096));
-    TAKE(d_total, u64*, 8);
+    vp_ws_frame W;
+    u64* d_total; W.want(&d_total, 8);
+    VP_TRY(vp_ws_commit(ctx, W, "vp_count_nonzero_u8_dev"));
     VP_TRY(vpk_count_nonzero_u8(ctx, d_src, n, d_total));
     VP_TRY(d2h(ctx, count, d_total, 8));
     return vp_synchronize(ctx);

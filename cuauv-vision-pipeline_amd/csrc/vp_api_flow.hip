@@ -61,13 +61,11 @@ int vp_lk_flow_dev(vp_ctx* ctx, const uint8_t* const* prev_levels, const size_t*
     }
     VP_TRY(check_ctx(ctx));
     const size_t pbytes = (size_t)n * 8, obytes = (size_t)n * LK_OUT_BYTES;
-    VP_TRY(vp_ws_reserve(ctx, vp_align(2 * pbytes) + vp_align(obytes) + 1024));
-    TAKE(d_pts, float*, 2 * pbytes);
+    vp_ws_frame W;
+    float* d_pts; W.want(&d_pts, 2 * pbytes);
     u32* d_res = (u32*)d_out;
-    if (!d_res) {
-        TAKE(d_own, u32*, obytes);
-        d_res = d_own;
-    }
+    if (!d_res) W.want(&d_res, obytes);
+    VP_TRY(vp_ws_commit(ctx, W, "vp_lk_flow_dev"));
     return lk_run(ctx, L, P, prev_pts, (flags & LK_USE_INITIAL_FLOW) ? init_pts : nullptr, n, win_w, win_h, max_count, eps, flags, min_eig_threshold, d_pts, d_res,
                   out_host);
 }
@@ -82,17 +80,19 @@ int vp_lk_flow_u8(vp_ctx* ctx, const uint8_t* prev, const uint8_t* next, int w, 
     vp_lk_plan P;
     vp_lk_make_plan(w, h, win_w, win_h, n, max_level, &P);
     const size_t pbytes = (size_t)n * 8, obytes = (size_t)n * LK_OUT_BYTES;
-    size_t need = vp_align(2 * pbytes) + vp_align(obytes) + 1024;
-    for (int l = 0; l < P.levels; l++) need += 2 * vp_align((size_t)P.cols[l] * P.rows[l]);
-    VP_TRY(vp_ws_reserve(ctx, need));
-    TAKE(d_pts, float*, 2 * pbytes);
-    TAKE(d_res, u32*, obytes);
+    vp_ws_frame W;
+    float* d_pts; W.want(&d_pts, 2 * pbytes);
+    u32* d_res; W.want(&d_res, obytes);
     vp_lk_levels L;
     memset(&L, 0, sizeof L);
     for (int l = 0; l < P.levels; l++) {
+        W.want(&L.prev[l], (size_t)P.cols[l] * P.rows[l]);
+        W.want(&L.next[l], (size_t)P.cols[l] * P.rows[l]);
+    }
+    VP_TRY(vp_ws_commit(ctx, W, "vp_lk_flow_u8"));
+    for (int l = 0; l < P.levels; l++) {
         const size_t bytes = (size_t)P.cols[l] * P.rows[l];
-        TAKE(d_p, uint8_t*, bytes);
-        TAKE(d_n, uint8_t*, bytes);
+        uint8_t *d_p = const_cast<uint8_t*>(L.prev[l]), *d_n = const_cast<uint8_t*>(L.next[l]);
         if (l == 0) {
             VP_TRY(h2d(ctx, d_p, prev, bytes));
             VP_TRY(h2d(ctx, d_n, next, bytes));
@@ -100,8 +100,6 @@ int vp_lk_flow_u8(vp_ctx* ctx, const uint8_t* prev, const uint8_t* next, int w, 
             VP_TRY(vp_pyr_down_dev(ctx, L.prev[l - 1], (size_t)P.cols[l - 1], P.cols[l - 1], P.rows[l - 1], 1, VP_BORDER_REFLECT_101, d_p));
             VP_TRY(vp_pyr_down_dev(ctx, L.next[l - 1], (size_t)P.cols[l - 1], P.cols[l - 1], P.rows[l - 1], 1, VP_BORDER_REFLECT_101, d_n));
         }
-        L.prev[l] = d_p;
-        L.next[l] = d_n;
         L.prev_stride[l] = L.next_stride[l] = (size_t)P.cols[l];
         L.cols[l] = P.cols[l];
         L.rows[l] = P.rows[l];

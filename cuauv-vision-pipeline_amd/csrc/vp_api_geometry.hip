@@ -197,16 +197,14 @@ int vp_contour_geometry_i32(vp_ctx* ctx, const int32_t* pts, const int32_t* coun
     VP_TRY(check_ctx(ctx));
     if (n_contours == 0) return VP_OK;
     const size_t n = (size_t)n_contours, np = (size_t)total;
-    VP_TRY(vp_ws_reserve(ctx, vp_geometry_ws_bytes(n_contours, total, hull_pts_out != nullptr, 1)));
-    TAKE(d_pts, int32_t*, std::max<size_t>(np, 1) * 8);
-    TAKE(d_first, long long*, n * 8);
-    TAKE(d_counts, int32_t*, n * 4);
-    TAKE(d_rows, vp_geom_raw*, n * sizeof(vp_geom_raw));
+    vp_ws_frame W;
+    int32_t* d_pts; W.want(&d_pts, std::max<size_t>(np, 1) * 8);
+    long long* d_first; W.want(&d_first, n * 8);
+    int32_t* d_counts; W.want(&d_counts, n * 4);
+    vp_geom_raw* d_rows; W.want(&d_rows, n * sizeof(vp_geom_raw));
     int32_t* d_hull = nullptr;
-    if (hull_pts_out) {
-        TAKE(d_h, int32_t*, std::max<size_t>(np, 1) * 8);
-        d_hull = d_h;
-    }
+    if (hull_pts_out) W.want(&d_hull, std::max<size_t>(np, 1) * 8);
+    VP_TRY(vp_ws_commit(ctx, W, "vp_contour_geometry_i32"));
     std::vector<long long> first(n);
     long long at = 0;
     for (size_t i = 0; i < n; i++) { first[i] = at; at += counts[i]; }
@@ -239,8 +237,9 @@ int vp_contour_geometry_dev(vp_ctx* ctx, const int32_t* d_pts, const int64_t* d_
         return vp_fail(ctx, VP_ERR_INVALID, "contour geometry: points and first indices must be 8-byte aligned");
     VP_TRY(check_ctx(ctx));
     if (n_contours == 0) return VP_OK;
-    VP_TRY(vp_ws_reserve(ctx, vp_geometry_ws_bytes(n_contours, 0, 0, 0)));
-    TAKE(d_rows, vp_geom_raw*, (size_t)n_contours * sizeof(vp_geom_raw));
+    vp_ws_frame W;
+    vp_geom_raw* d_rows; W.want(&d_rows, (size_t)n_contours * sizeof(vp_geom_raw));
+    VP_TRY(vp_ws_commit(ctx, W, "vp_contour_geometry_dev"));
     VP_TRY(vpk_contour_geometry(ctx, d_pts, reinterpret_cast<const long long*>(d_first), d_counts, n_contours, d_rows, d_hull));
     return fetch_rows(ctx, d_rows, (size_t)n_contours, rows_out, nullptr);
 }
@@ -257,8 +256,9 @@ int vp_contour_geometry_batch_dev(vp_ctx* ctx, const vp_contour_desc* cd, const 
     VP_TRY(check_ctx(ctx));
     if (n_frames == 0) return VP_OK;
     const size_t n = (size_t)cd->max_contours * n_frames;
-    VP_TRY(vp_ws_reserve(ctx, vp_geometry_ws_bytes((long long)n, 0, 0, 0)));
-    TAKE(d_rows, vp_geom_raw*, n * sizeof(vp_geom_raw));
+    vp_ws_frame W;
+    vp_geom_raw* d_rows; W.want(&d_rows, n * sizeof(vp_geom_raw));
+    VP_TRY(vp_ws_commit(ctx, W, "vp_contour_geometry_batch_dev"));
     VP_TRY(vpk_contour_geometry_batch(ctx, cb->info, cb->counts, cb->offsets, cb->points, n_frames, cd->max_contours, cd->max_points, d_rows));
     return fetch_rows(ctx, d_rows, n, rows_out, nullptr);
 }

@@ -38,16 +38,14 @@ int vp_calc_hist_u8(vp_ctx* ctx, const uint8_t* src, int w, int h, int cn, int d
     vp_hist_plan P;
     vp_hist_make_plan(w, h, cn, dims, channels, hist_size, ranges, 0, &P);
     const size_t pitch = (row + 3) / 4 * 4, cbytes = (size_t)P.total * 4;
-    VP_TRY(vp_ws_reserve(ctx, vp_align(pitch * h) + vp_align((size_t)w * h) + vp_align(cbytes) + 1024));
-    TAKE(d_src, uint8_t*, pitch * h);
-    TAKE(d_cnt, u32*, cbytes);
+    vp_ws_frame W;
+    uint8_t* d_src; W.want(&d_src, pitch * h);
+    u32* d_cnt; W.want(&d_cnt, cbytes);
     uint8_t* d_mask = nullptr;
+    if (mask) W.want(&d_mask, (size_t)w * h);
+    VP_TRY(vp_ws_commit(ctx, W, "vp_calc_hist_u8"));
     VP_TRY(h2d_rows(ctx, d_src, pitch, src, row, row, h));
-    if (mask) {
-        TAKE(d_m, uint8_t*, (size_t)w * h);
-        VP_TRY(h2d(ctx, d_m, mask, (size_t)w * h));
-        d_mask = d_m;
-    }
+    if (mask) VP_TRY(h2d(ctx, d_mask, mask, (size_t)w * h));
     VP_TRY(vpk_calc_hist(ctx, d_src, pitch, w, h, P, d_mask, (size_t)w, nullptr, d_cnt));
     std::vector<u32> cnt((size_t)P.total);
     VP_TRY(d2h(ctx, cnt.data(), d_cnt, cbytes));
@@ -73,9 +71,9 @@ int vp_calc_hist_dev(vp_ctx* ctx, const uint8_t* d_src, size_t stride, int w, in
     vp_hist_make_plan(w, h, cn, dims, channels, hist_size, ranges, 0, &P);
     u32* d_cnt = d_counts;
     if (!d_cnt) {
-        VP_TRY(vp_ws_reserve(ctx, vp_align(cbytes) + 1024));
-        TAKE(d_own, u32*, cbytes);
-        d_cnt = d_own;
+        vp_ws_frame W;
+        W.want(&d_cnt, cbytes);
+        VP_TRY(vp_ws_commit(ctx, W, "vp_calc_hist_dev"));
     }
     VP_TRY(vpk_calc_hist(ctx, d_src, stride, w, h, P, d_mask_bits ? nullptr : d_mask, mask_stride, reinterpret_cast<const u64*>(d_mask_bits), d_cnt));
     if (!counts_host) return VP_OK;
@@ -94,10 +92,11 @@ int vp_back_project_u8(vp_ctx* ctx, const uint8_t* src, int w, int h, int cn, in
     vp_hist_plan P;
     vp_hist_make_plan(w, h, cn, dims, channels, hist_size, ranges, 1, &P);
     const size_t pitch = (row + 3) / 4 * 4, dpitch = ((size_t)w + 3) / 4 * 4;
-    VP_TRY(vp_ws_reserve(ctx, vp_align(pitch * h) + vp_align(dpitch * h) + vp_align((size_t)P.total) + 1024));
-    TAKE(d_src, uint8_t*, pitch * h);
-    TAKE(d_dst, uint8_t*, dpitch * h);
-    TAKE(d_table, uint8_t*, (size_t)P.total);
+    vp_ws_frame W;
+    uint8_t* d_src; W.want(&d_src, pitch * h);
+    uint8_t* d_dst; W.want(&d_dst, dpitch * h);
+    uint8_t* d_table; W.want(&d_table, (size_t)P.total);
+    VP_TRY(vp_ws_commit(ctx, W, "vp_back_project_u8"));
     std::vector<uint8_t> table((size_t)P.total);      // the fold, on the host: the histogram is here
     for (int i = 0; i < P.total; i++) table[i] = fold_one(hist[i], scale);
     VP_TRY(h2d_rows(ctx, d_src, pitch, src, row, row, h));
@@ -128,8 +127,9 @@ int vp_back_project_dev(vp_ctx* ctx, const uint8_t* d_src, size_t stride, int w,
     VP_TRY(check_ctx(ctx));
     vp_hist_plan P;
     vp_hist_make_plan(w, h, cn, dims, channels, hist_size, ranges, 1, &P);
-    VP_TRY(vp_ws_reserve(ctx, vp_align(total) + 1024));
-    TAKE(d_table, uint8_t*, total);
+    vp_ws_frame W;
+    uint8_t* d_table; W.want(&d_table, total);
+    VP_TRY(vp_ws_commit(ctx, W, "vp_back_project_dev"));
     VP_TRY(vpk_back_project_fold(ctx, d_hist, P.total, scale, d_table));
     return vpk_back_project(ctx, d_src, stride, w, h, P, d_table, d_dst, dst_stride);
 }
@@ -156,13 +156,11 @@ int vp_mean_shift_dev(vp_ctx* ctx, const uint8_t* d_src, size_t stride, int w, i
     if (d_out && ((uintptr_t)d_out % 4 || dev_overlap(d_src, strided_bytes(stride, (size_t)w, h), d_out, obytes)))
         return vp_fail(ctx, VP_ERR_INVALID, "vp_mean_shift_dev: the result is not 4-byte aligned, or overlaps the image");
     VP_TRY(check_ctx(ctx));
-    VP_TRY(vp_ws_reserve(ctx, vp_align(wbytes) + vp_align(obytes) + 1024));
-    TAKE(d_win, int32_t*, wbytes);
+    vp_ws_frame W;
+    int32_t* d_win; W.want(&d_win, wbytes);
     int32_t* d_res = d_out;
-    if (!d_res) {
-        TAKE(d_own, int32_t*, obytes);
-        d_res = d_own;
-    }
+    if (!d_res) W.want(&d_res, obytes);
+    VP_TRY(vp_ws_commit(ctx, W, "vp_mean_shift_dev"));
     // the windows go over in a pinned chunk of the context's ring: the copy is enqueued, nothing waits for it
     int slot = -1;
     uint8_t* hp = vp_ring_take(ctx, wbytes, &slot);

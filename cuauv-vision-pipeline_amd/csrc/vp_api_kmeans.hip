@@ -3,16 +3,19 @@
 #include "vp_api_util.h"
 #include "vp_kmeans_plan.h"
 
-static size_t kmeans_ws_bytes(int k, int cn) { return vp_align(vp_kmeans_table_bytes(k, cn)) + vp_align((size_t)k * cn * 4) + 1024; }
-
 // The whole loop on the device, the optional copy of the labels to labels_host (packed), the table back through pinned staging and one
-// synchronise; the workspace is reserved by the caller.  lstride in bytes.
+// synchronise; b is in the caller's frame (kmeans_want).  lstride in bytes.
+struct kmeans_bufs { uint8_t *table, *init; };
+static void kmeans_want(vp_ws_frame& W, int k, int cn, kmeans_bufs* b)
+{
+    W.want(&b->table, vp_kmeans_table_bytes(k, cn));
+    W.want(&b->init, (size_t)k * cn * 4);
+}
 static int kmeans_run(vp_ctx* ctx, const uint8_t* d_src, size_t stride, int w, int h, int cn, int k, const float* centers_init, const int32_t* seed_index,
-                      int max_iter, double eps, int32_t* d_labels, size_t lstride, int32_t* labels_host, void* out)
+                      int max_iter, double eps, int32_t* d_labels, size_t lstride, int32_t* labels_host, void* out, const kmeans_bufs& b)
 {
     const size_t tbytes = vp_kmeans_table_bytes(k, cn);
-    TAKE(d_table, uint8_t*, tbytes);
-    TAKE(d_init, uint8_t*, (size_t)k * cn * 4);
+    uint8_t *d_table = b.table, *d_init = b.init;
     if (centers_init) VP_TRY(h2d(ctx, d_init, centers_init, (size_t)k * cn * 4));
     else VP_TRY(h2d(ctx, d_init, seed_index, (size_t)k * 4));
     VP_TRY(vpk_kmeans(ctx, d_src, stride, w, h, cn, k, centers_init ? (const float*)d_init : nullptr, centers_init ? nullptr : (const int32_t*)d_init, max_iter, eps,
@@ -46,15 +49,15 @@ int vp_kmeans_u8(vp_ctx* ctx, const uint8_t* src, int w, int h, int cn, int k, c
         return vp_fail(ctx, VP_ERR_INVALID, why);
     VP_TRY(check_ctx(ctx));
     const size_t npx = (size_t)w * h;
-    VP_TRY(vp_ws_reserve(ctx, vp_align(npx * cn) + (labels ? vp_align(npx * 4) : 0) + kmeans_ws_bytes(k, cn)));
-    TAKE(d_src, uint8_t*, npx * cn);
+    vp_ws_frame W;
+    uint8_t* d_src; W.want(&d_src, npx * cn);
     int32_t* d_labels = nullptr;
-    if (labels) {
-        d_labels = (int32_t*)vp_ws_take(ctx, npx * 4);
-        if (!d_labels) return vp_fail(ctx, VP_ERR_NOMEM, "workspace exhausted: d_labels");
-    }
+    if (labels) W.want(&d_labels, npx * 4);
+    kmeans_bufs b;
+    kmeans_want(W, k, cn, &b);
+    VP_TRY(vp_ws_commit(ctx, W, "vp_kmeans_u8"));
     VP_TRY(h2d(ctx, d_src, src, npx * cn));
-    return kmeans_run(ctx, d_src, (size_t)w * cn, w, h, cn, k, centers_init, seed_index, max_iter, eps, d_labels, (size_t)w * 4, labels, out);
+    return kmeans_run(ctx, d_src, (size_t)w * cn, w, h, cn, k, centers_init, seed_index, max_iter, eps, d_labels, (size_t)w * 4, labels, out, b);
 }
 
 int vp_kmeans_dev(vp_ctx* ctx, const uint8_t* d_src, size_t stride, int w, int h, int cn, int k, const float* centers_init, const int32_t* seed_index,
@@ -68,8 +71,11 @@ int vp_kmeans_dev(vp_ctx* ctx, const uint8_t* d_src, size_t stride, int w, int h
             return vp_fail(ctx, VP_ERR_INVALID, "vp_kmeans_dev: the labels are not 4-byte aligned, or overlap the source");
     }
     VP_TRY(check_ctx(ctx));
-    VP_TRY(vp_ws_reserve(ctx, kmeans_ws_bytes(k, cn)));
-    return kmeans_run(ctx, d_src, stride, w, h, cn, k, centers_init, seed_index, max_iter, eps, d_labels, labels_stride, nullptr, out);
+    vp_ws_frame W;
+    kmeans_bufs b;
+    kmeans_want(W, k, cn, &b);
+    VP_TRY(vp_ws_commit(ctx, W, "vp_kmeans_dev"));
+    return kmeans_run(ctx, d_src, stride, w, h, cn, k, centers_init, seed_index, max_iter, eps, d_labels, labels_stride, nullptr, out, b);
 }
 
 int vp_label_select_dev(vp_ctx* ctx, const int32_t* d_labels, size_t labels_stride, int w, int h, const uint8_t* select, int k, uint8_t* d_mask,

@@ -13,17 +13,16 @@ int vp_ccl_u8(vp_ctx* ctx, const uint8_t* src, size_t src_stride, int w, int h, 
     if (numbering != VP_CCL_BLOCK2X2 && numbering != VP_CCL_PIXEL) return vp_fail(ctx, VP_ERR_INVALID, "numbering");
     const size_t npx = (size_t)w * h;
     const size_t bitbytes = (size_t)h * vp_ww(w) * 8;
-    VP_TRY(vp_ws_reserve(ctx, vp_align(npx) + vp_align(bitbytes) + vp_align(npx * 4) + vp_align((size_t)max_labels * 20) +
-                                  vp_align((size_t)max_labels * 16) + vp_ccl_ws_bytes(w, h, 1, max_labels) + 8192));
-    TAKE(d_src, uint8_t*, npx);
-    TAKE(d_bits, u64*, bitbytes);
-    TAKE(d_labels, int32_t*, npx * 4);
-    TAKE(d_stats, int32_t*, (size_t)max_labels * 20);
-    TAKE(d_cent, double*, (size_t)max_labels * 16);
-    TAKE(d_nl, int32_t*, 4);
+    vp_ws_frame W;
+    uint8_t* d_src; W.want(&d_src, npx);
+    u64* d_bits; W.want(&d_bits, bitbytes);
+    int32_t* d_labels; W.want(&d_labels, npx * 4);
+    int32_t* d_stats; W.want(&d_stats, (size_t)max_labels * 20);
+    double* d_cent; W.want(&d_cent, (size_t)max_labels * 16);
+    int32_t* d_nl; W.want(&d_nl, 4);
     vp_ccl_ws ws;
-    vp_ccl_ws_carve(ctx, w, h, 1, max_labels, &ws);
-    if (!vp_ccl_ws_ok(ws)) return vp_fail(ctx, VP_ERR_NOMEM, "ccl workspace");
+    vp_ccl_ws_want(W, w, h, 1, max_labels, &ws);
+    VP_TRY(vp_ws_commit(ctx, W, "vp_ccl_u8"));
     VP_TRY(h2d_rows(ctx, d_src, (size_t)w, src, src_stride, (size_t)w, h));
     VP_TRY(vpk_pack_bits(ctx, d_src, (size_t)w, w, h, 1, d_bits, nullptr));
     VP_TRY(vpk_ccl(ctx, d_bits, w, h, 1, numbering, ws, labels ? d_labels : nullptr, d_stats, d_cent, max_labels, d_nl));
@@ -42,14 +41,14 @@ static int ccl_dev_impl(vp_ctx* ctx, const char* who, const uint8_t* d_src, size
     if ((!d_src && !bits_in) || w <= 0 || h <= 0 || (!bits_in && src_stride < (size_t)w) || max_labels < 1 || !nlabels) return vp_fail(ctx, VP_ERR_INVALID, who);
     if (numbering != VP_CCL_BLOCK2X2 && numbering != VP_CCL_PIXEL) return vp_fail(ctx, VP_ERR_INVALID, "numbering");
     const size_t bitbytes = (size_t)h * vp_ww(w) * 8;
-    VP_TRY(vp_ws_reserve(ctx, vp_align(bitbytes) + vp_align((size_t)max_labels * 20) + vp_align((size_t)max_labels * 16) + vp_ccl_ws_bytes(w, h, 1, max_labels) + 8192));
-    TAKE(d_bits, u64*, bitbytes);
-    TAKE(d_stats, int32_t*, (size_t)max_labels * 20);
-    TAKE(d_cent, double*, (size_t)max_labels * 16);
-    TAKE(d_nl, int32_t*, 4);
+    vp_ws_frame W;
+    u64* d_bits; W.want(&d_bits, bitbytes);
+    int32_t* d_stats; W.want(&d_stats, (size_t)max_labels * 20);
+    double* d_cent; W.want(&d_cent, (size_t)max_labels * 16);
+    int32_t* d_nl; W.want(&d_nl, 4);
     vp_ccl_ws ws;
-    vp_ccl_ws_carve(ctx, w, h, 1, max_labels, &ws);
-    if (!vp_ccl_ws_ok(ws)) return vp_fail(ctx, VP_ERR_NOMEM, "ccl workspace");
+    vp_ccl_ws_want(W, w, h, 1, max_labels, &ws);
+    VP_TRY(vp_ws_commit(ctx, W, "ccl_dev_impl"));
     const u64* bits = bits_in;
     if (!bits) {
         VP_TRY(vpk_pack_bits(ctx, d_src, src_stride, w, h, 1, d_bits, nullptr));
@@ -93,14 +92,16 @@ static int find_contours_impl(vp_ctx* ctx, const uint8_t* src, bool src_on_devic
     const bool tree = tree_entry && (mode == VP_RETR_CCOMP || mode == VP_RETR_TREE);
     const ct_hdr_layout L = ct_hdr(mc, tree);            // the result header, one block so that one copy brings it back (vp_contours_plan.h)
     const size_t hdr_bytes = L.bytes;
-    VP_TRY(vp_ws_reserve(ctx, vp_align(npx) + vp_align(bitbytes) + vp_contours_ws_bytes(w, h, 1, mc) + vp_align(hdr_bytes) +
-                                  vp_align((size_t)mp * 8) + (tree ? vp_contour_tree_ws_bytes(mc) : 0) + 8192));
-    TAKE(d_stage, uint8_t*, npx);
+    vp_ws_frame W;
+    uint8_t* d_stage; W.want(&d_stage, npx);
+    u64* d_bits; W.want(&d_bits, bitbytes);
+    uint8_t* d_hdr; W.want(&d_hdr, hdr_bytes);
+    int32_t* d_points; W.want(&d_points, (size_t)mp * 8);
+    const size_t ct_bytes = vp_contours_ws_bytes(w, h, 1, mc) + (tree ? vp_contour_tree_ws_bytes(mc) : 0);
+    uint8_t* d_ct; W.want(&d_ct, ct_bytes);              // the pass's scratch: a repeated pass uses it again
+    VP_TRY(vp_ws_commit(ctx, W, "find_contours_impl"));
     const uint8_t* d_src = d_stage;
     size_t d_stride = (size_t)w;
-    TAKE(d_bits, u64*, bitbytes);
-    TAKE(d_hdr, uint8_t*, hdr_bytes);
-    TAKE(d_points, int32_t*, (size_t)mp * 8);
     // the header's arrays in the workspace block, or in the pinned one the kernels mirror them into
     auto hdr_at = [&](uint8_t* base) {
         vp_contour_mirror m = {};
@@ -138,12 +139,10 @@ static int find_contours_impl(vp_ctx* ctx, const uint8_t* src, bool src_on_devic
     // in place of a result (0.1 ms), and the pass is repeated as launches - instead of one block working through 600 k heads in global
     // memory (9 ms at 10 % noise).  Not when a form is forced.
     bool many_now = many;
-    const size_t ws_mark = ctx->ws_off;
     const int32_t* info = nullptr;
     for (;;) {
         const bool defer = !many_now && !many_forced;
-        ctx->ws_off = ws_mark;
-        VP_TRY(vpk_find_contours(ctx, bits_use, w, h, 1, mode, method, dh.counts, dh.is_hole, dh.offsets, d_points, mc, mp, dh.info, many_now,
+        VP_TRY(vpk_find_contours(ctx, d_ct, ct_bytes, bits_use, w, h, 1, mode, method, dh.counts, dh.is_hole, dh.offsets, d_points, mc, mp, dh.info, many_now,
                                  reinterpret_cast<uint32_t*>(dh.info + 2), mirror_off ? nullptr : &hm, defer, dh.hier));
         if (mirror_off) {
             if (spec_pts && reinterpret_cast<uint8_t*>(d_points) == d_hdr + hdr_pad) {

@@ -14,11 +14,12 @@ int vp_match_template_u8(vp_ctx* ctx, const uint8_t* src, int w, int h, int cn, 
     vp_match_plan P;
     vp_match_make_plan(w, h, cn, tw, th, method, &P);
     const size_t pitch = (row + 3) / 4 * 4;              // rows on word boundaries: the correlation stages them a word at a time
-    VP_TRY(vp_ws_reserve(ctx, vp_align(pitch * h) + vp_align(trow * th) + vp_align(drow * P.rh) + vp_align(P.ws_bytes) + 1024));
-    TAKE(d_src, uint8_t*, pitch * h);
-    TAKE(d_templ, uint8_t*, trow * th);
-    TAKE(d_dst, float*, drow * P.rh);
-    TAKE(d_ws, uint8_t*, P.ws_bytes);
+    vp_ws_frame W;
+    uint8_t* d_src; W.want(&d_src, pitch * h);
+    uint8_t* d_templ; W.want(&d_templ, trow * th);
+    float* d_dst; W.want(&d_dst, drow * P.rh);
+    uint8_t* d_ws; W.want(&d_ws, P.ws_bytes);
+    VP_TRY(vp_ws_commit(ctx, W, "vp_match_template_u8"));
     VP_TRY(h2d_rows(ctx, d_src, pitch, src, row, row, h));
     VP_TRY(h2d(ctx, d_templ, templ, trow * th));
     VP_TRY(vpk_match_template(ctx, d_src, pitch, w, h, cn, d_templ, trow, tw, th, method, P, d_ws, d_dst, drow));
@@ -38,8 +39,9 @@ int vp_match_template_dev(vp_ctx* ctx, const uint8_t* d_src, size_t stride, int 
     VP_TRY(check_ctx(ctx));
     vp_match_plan P;
     vp_match_make_plan(w, h, cn, tw, th, method, &P);
-    VP_TRY(vp_ws_reserve(ctx, vp_align(P.ws_bytes) + 1024));
-    TAKE(d_ws, uint8_t*, P.ws_bytes);
+    vp_ws_frame W;
+    uint8_t* d_ws; W.want(&d_ws, P.ws_bytes);
+    VP_TRY(vp_ws_commit(ctx, W, "vp_match_template_dev"));
     return vpk_match_template(ctx, d_src, stride, w, h, cn, d_templ, templ_stride, tw, th, method, P, d_ws, d_dst, dst_stride);
 }
 

@@ -67,8 +67,9 @@ int vp_estimate_model_f32(vp_ctx* ctx, const float* src_host, const float* dst_h
     VP_TRY(check_ctx(ctx));
     vp_rs_plan P;
     vp_rs_make_plan(n, model, max_iters, &P);
-    VP_TRY(vp_ws_reserve(ctx, P.ws_bytes + 1024));
-    TAKE(d_ws, uint8_t*, P.ws_bytes);
+    vp_ws_frame W;
+    uint8_t* d_ws; W.want(&d_ws, P.ws_bytes);
+    VP_TRY(vp_ws_commit(ctx, W, "vp_estimate_model_f32"));
     // the packed form is made on the way into the pinned buffer the copy leaves from; the refit reads it there after the search
     const size_t pbytes = (size_t)n * 16;
     int slot = -1;
@@ -95,8 +96,9 @@ int vp_estimate_model_dev(vp_ctx* ctx, const float* src_dev, const float* dst_de
     VP_TRY(check_ctx(ctx));
     vp_rs_plan P;
     vp_rs_make_plan(n, model, max_iters, &P);
-    VP_TRY(vp_ws_reserve(ctx, P.ws_bytes + 1024));
-    TAKE(d_ws, uint8_t*, P.ws_bytes);
+    vp_ws_frame W;
+    uint8_t* d_ws; W.want(&d_ws, P.ws_bytes);
+    VP_TRY(vp_ws_commit(ctx, W, "vp_estimate_model_dev"));
     VP_TRY(vpk_rs_pack(ctx, src_dev, dst_dev, n, reinterpret_cast<float*>(d_ws)));
     return rs_run(ctx, P, d_ws, nullptr, n, model, threshold, max_iters, confidence, seed, model_out, inliers_host, n_inliers, n_hypotheses);
 }

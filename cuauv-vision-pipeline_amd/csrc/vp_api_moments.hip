@@ -4,19 +4,19 @@
 #include "vp_moments_plan.h"
 #include <float.h>
 
-// the table lives in the context's workspace: zeroed, added into and read back in stream order; the call returns after the read
-static int moments_run(vp_ctx* ctx, const uint8_t* d_src, size_t stride, int w, int h, int binary, const u64* d_bits, uint64_t* out10)
+// the table (d_out: ten words; d_table: label_table_bytes) lives in the caller's frame: zeroed, added into and read back in stream
+// order; the call returns after the read
+static int moments_run(vp_ctx* ctx, const uint8_t* d_src, size_t stride, int w, int h, int binary, const u64* d_bits, u64* d_out, uint64_t* out10)
 {
-    TAKE(d_out, u64*, 10 * sizeof(u64));
     VP_TRY(vpk_moments_u8(ctx, d_src, stride, w, h, binary, d_bits, d_out));
     VP_TRY(d2h(ctx, out10, d_out, 10 * sizeof(u64)));
     return vp_synchronize(ctx);
 }
 
-static int label_moments_run(vp_ctx* ctx, const int32_t* d_labels, size_t stride, int w, int h, int nlabels, uint64_t* out)
+static size_t label_table_bytes(int nlabels) { return (size_t)nlabels * 10 * sizeof(u64); }
+static int label_moments_run(vp_ctx* ctx, const int32_t* d_labels, size_t stride, int w, int h, int nlabels, u64* d_table, uint64_t* out)
 {
-    const size_t bytes = (size_t)nlabels * 10 * sizeof(u64);
-    TAKE(d_table, u64*, bytes);
+    const size_t bytes = label_table_bytes(nlabels);
     VP_TRY(vpk_label_moments_i32(ctx, d_labels, stride, w, h, nlabels, d_table));
     VP_TRY(d2h(ctx, out, d_table, bytes));
     return vp_synchronize(ctx);
@@ -39,10 +39,12 @@ int vp_moments_u8(vp_ctx* ctx, const uint8_t* src, size_t stride, int w, int h, 
     if (const char* why = vp_moments_refusal(w, h, stride, 1, binary ? 1 : 255)) return vp_fail(ctx, VP_ERR_INVALID, why);
     VP_TRY(check_ctx(ctx));
     const size_t npx = (size_t)w * h;
-    VP_TRY(vp_ws_reserve(ctx, vp_align(npx) + 4096));
-    TAKE(d_src, uint8_t*, npx);
+    vp_ws_frame W;
+    uint8_t* d_src; W.want(&d_src, npx);
+    u64* d_out; W.want(&d_out, 10 * sizeof(u64));
+    VP_TRY(vp_ws_commit(ctx, W, "vp_moments_u8"));
     VP_TRY(h2d_rows(ctx, d_src, (size_t)w, src, stride, (size_t)w, h));
-    return moments_run(ctx, d_src, (size_t)w, w, h, binary != 0, nullptr, out10);
+    return moments_run(ctx, d_src, (size_t)w, w, h, binary != 0, nullptr, d_out, out10);
 }
 
 int vp_moments_dev(vp_ctx* ctx, const uint8_t* d_src, size_t stride, int w, int h, int binary, const unsigned long long* d_bits, uint64_t* out10)
@@ -52,8 +54,10 @@ int vp_moments_dev(vp_ctx* ctx, const uint8_t* d_src, size_t stride, int w, int 
     if (d_bits && (uintptr_t)d_bits % 8) return vp_fail(ctx, VP_ERR_INVALID, "vp_moments_dev: the bit plane must be 8-byte aligned");
     if (const char* why = vp_moments_refusal(w, h, d_bits ? (size_t)w : stride, 1, binary ? 1 : 255)) return vp_fail(ctx, VP_ERR_INVALID, why);
     VP_TRY(check_ctx(ctx));
-    VP_TRY(vp_ws_reserve(ctx, 4096));
-    return moments_run(ctx, d_src, stride, w, h, binary != 0, reinterpret_cast<const u64*>(d_bits), out10);
+    vp_ws_frame W;
+    u64* d_out; W.want(&d_out, 10 * sizeof(u64));
+    VP_TRY(vp_ws_commit(ctx, W, "vp_moments_dev"));
+    return moments_run(ctx, d_src, stride, w, h, binary != 0, reinterpret_cast<const u64*>(d_bits), d_out, out10);
 }
 
 int vp_label_moments_i32(vp_ctx* ctx, const int32_t* labels, size_t stride, int w, int h, int nlabels, uint64_t* out)
@@ -61,18 +65,22 @@ int vp_label_moments_i32(vp_ctx* ctx, const int32_t* labels, size_t stride, int 
     if (const char* why = label_refusal(labels, stride, w, h, nlabels, out)) return vp_fail(ctx, VP_ERR_INVALID, why);
     VP_TRY(check_ctx(ctx));
     const size_t bytes = (size_t)w * h * 4;
-    VP_TRY(vp_ws_reserve(ctx, vp_align(bytes) + vp_align((size_t)nlabels * 80) + 4096));
-    TAKE(d_labels, int32_t*, bytes);
+    vp_ws_frame W;
+    int32_t* d_labels; W.want(&d_labels, bytes);
+    u64* d_table; W.want(&d_table, label_table_bytes(nlabels));
+    VP_TRY(vp_ws_commit(ctx, W, "vp_label_moments_i32"));
     VP_TRY(h2d_rows(ctx, d_labels, (size_t)w * 4, labels, stride, (size_t)w * 4, h));
-    return label_moments_run(ctx, d_labels, (size_t)w * 4, w, h, nlabels, out);
+    return label_moments_run(ctx, d_labels, (size_t)w * 4, w, h, nlabels, d_table, out);
 }
 
 int vp_label_moments_dev(vp_ctx* ctx, const int32_t* d_labels, size_t stride, int w, int h, int nlabels, uint64_t* out)
 {
     if (const char* why = label_refusal(d_labels, stride, w, h, nlabels, out)) return vp_fail(ctx, VP_ERR_INVALID, why);
     VP_TRY(check_ctx(ctx));
-    VP_TRY(vp_ws_reserve(ctx, vp_align((size_t)nlabels * 80) + 4096));
-    return label_moments_run(ctx, d_labels, stride, w, h, nlabels, out);
+    vp_ws_frame W;
+    u64* d_table; W.want(&d_table, label_table_bytes(nlabels));
+    VP_TRY(vp_ws_commit(ctx, W, "vp_label_moments_dev"));
+    return label_moments_run(ctx, d_labels, stride, w, h, nlabels, d_table, out);
 }
 
 // imgproc/src/moments.cpp contourMoments: Green's theorem in float64, from the last point round, in this operation order - the sums

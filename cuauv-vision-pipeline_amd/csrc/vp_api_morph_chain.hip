@@ -165,35 +165,34 @@ static int morph_basic_dev(vp_ctx* ctx, int dilate, const norm_se& se, const uin
     return VP_OK;
 }
 
-// workspace a morphology call needs besides its source / result images
-static size_t morph_ws_bytes(const norm_se& se, int w, int h, int cn)
+// temporaries a morphology call needs besides its source / result images
+struct morph_bufs { uint8_t *tab, *b, *c, *tmp; u64 *bits_a, *bits_b, *bits_c; int16_t* offs; int* flag; };
+static void morph_want(vp_ws_frame& W, const norm_se& se, int w, int h, int cn, morph_bufs* m)
 {
     const size_t nbytes = (size_t)w * h * cn;
     const size_t bitbytes = (size_t)h * vp_ww(w) * 8;
-    const size_t offbytes = ((size_t)se.kw * se.kh + se.kw + se.kh) * 4 + 64;
-    const size_t tabbytes = se.allones ? 0 : 7 * nbytes;   // running min/max tables of the span form
-    return 4 * vp_align(nbytes) + 3 * vp_align(bitbytes) + vp_align(offbytes) + vp_align(tabbytes) + 4096;
+    m->tab = nullptr;
+    if (!se.allones) W.want(&m->tab, 7 * nbytes);   // running min/max tables of the span form
+    W.want(&m->b, nbytes);
+    W.want(&m->c, nbytes);
+    W.want(&m->tmp, nbytes);
+    W.want(&m->bits_a, bitbytes);
+    W.want(&m->bits_b, bitbytes);
+    W.want(&m->bits_c, bitbytes);   // a plan of three or more launches alternates between bits_b and bits_c: bits_a is only read
+    W.want(&m->offs, ((size_t)se.kw * se.kh + se.kw + se.kh) * 4 + 64);
+    W.want(&m->flag, 4);
 }
 
-// One morphology operation between device images (d_dst may equal neither d_src nor overlap it); temporaries are carved from the
-// workspace, which the caller has reserved (morph_ws_bytes).  binary_hint: 1 = the image is known to hold only 0 / 255 (a mask this
+// One morphology operation between device images (d_dst may equal neither d_src nor overlap it); temporaries: m, in the caller's frame
+// (morph_want).  binary_hint: 1 = the image is known to hold only 0 / 255 (a mask this
 // library produced), 0 = unknown: one flag comes back from the device to decide between the bit-plane and the grey-level path.
-static int morph_core(vp_ctx* ctx, int op, const norm_se& se, const uint8_t* d_src, int w, int h, int cn, int binary_hint, uint8_t* d_dst)
+static int morph_core(vp_ctx* ctx, int op, const norm_se& se, const uint8_t* d_src, int w, int h, int cn, int binary_hint, uint8_t* d_dst, const morph_bufs& m)
 {
     const size_t nbytes = (size_t)w * h * cn;
-    const size_t bitbytes = (size_t)h * vp_ww(w) * 8;
-    const size_t offbytes = ((size_t)se.kw * se.kh + se.kw + se.kh) * 4 + 64;
-    const size_t tabbytes = se.allones ? 0 : 7 * nbytes;
-    uint8_t* d_tab = tabbytes ? (uint8_t*)vp_ws_take(ctx, tabbytes) : nullptr;
-    if (tabbytes && !d_tab) return vp_fail(ctx, VP_ERR_NOMEM, "workspace");
-    TAKE(d_b, uint8_t*, nbytes);
-    TAKE(d_c, uint8_t*, nbytes);
-    TAKE(d_tmp, uint8_t*, nbytes);
-    TAKE(bits_a, u64*, bitbytes);
-    TAKE(bits_b, u64*, bitbytes);
-    TAKE(bits_c, u64*, bitbytes);   // a plan of three or more launches alternates between bits_b and bits_c: bits_a is only read
-    TAKE(d_offs, int16_t*, offbytes);
-    TAKE(d_flag, int*, 4);
+    uint8_t *d_tab = m.tab, *d_b = m.b, *d_c = m.c, *d_tmp = m.tmp;
+    u64 *bits_a = m.bits_a, *bits_b = m.bits_b, *bits_c = m.bits_c;
+    int16_t* d_offs = m.offs;
+    int* d_flag = m.flag;
     bool binary = false;
     if (cn == 1 && se.allones) {
         // a 0/255 mask can take the bit-plane path; anything else is grey-level
@@ -238,11 +237,14 @@ int vp_morph_u8(vp_ctx* ctx, int op, const uint8_t* src, int w, int h, int cn, c
     norm_se se;
     if (normalise_se(kernel, kw, kh, ax, ay, iterations, &se) != VP_OK) return vp_fail(ctx, VP_ERR_INVALID, "structuring element");
     const size_t nbytes = (size_t)w * h * cn;
-    VP_TRY(vp_ws_reserve(ctx, 2 * vp_align(nbytes) + morph_ws_bytes(se, w, h, cn)));
-    TAKE(d_src, uint8_t*, nbytes);
-    TAKE(d_a, uint8_t*, nbytes);
+    vp_ws_frame W;
+    uint8_t* d_src; W.want(&d_src, nbytes);
+    uint8_t* d_a; W.want(&d_a, nbytes);
+    morph_bufs m;
+    morph_want(W, se, w, h, cn, &m);
+    VP_TRY(vp_ws_commit(ctx, W, "vp_morph_u8"));
     VP_TRY(h2d(ctx, d_src, src, nbytes));
-    VP_TRY(morph_core(ctx, op, se, d_src, w, h, cn, 0, d_a));
+    VP_TRY(morph_core(ctx, op, se, d_src, w, h, cn, 0, d_a, m));
     VP_TRY(d2h(ctx, dst, d_a, nbytes));
     return vp_synchronize(ctx);
 }
@@ -255,8 +257,11 @@ int vp_morph_u8_dev(vp_ctx* ctx, int op, const uint8_t* d_src, int w, int h, int
         return vp_fail(ctx, VP_ERR_INVALID, "vp_morph_u8_dev arguments");
     norm_se se;
     if (normalise_se(kernel, kw, kh, ax, ay, iterations, &se) != VP_OK) return vp_fail(ctx, VP_ERR_INVALID, "structuring element");
-    VP_TRY(vp_ws_reserve(ctx, morph_ws_bytes(se, w, h, cn)));
-    return morph_core(ctx, op, se, d_src, w, h, cn, binary_hint, d_dst);
+    vp_ws_frame W;
+    morph_bufs m;
+    morph_want(W, se, w, h, cn, &m);
+    VP_TRY(vp_ws_commit(ctx, W, "vp_morph_u8_dev"));
+    return morph_core(ctx, op, se, d_src, w, h, cn, binary_hint, d_dst, m);
 }
 
 // ---- chain -------------------------------------------------------------------------------------------
@@ -279,15 +284,6 @@ static int check_desc(vp_ctx* ctx, const vp_chain_desc* d, int n)
     return VP_OK;
 }
 
-static size_t chain_ws_bytes(const vp_chain_desc* d, int n)
-{
-    const size_t bitbytes = (size_t)n * d->height * vp_ww(d->width) * 8;
-    size_t need = 3 * vp_align(bitbytes) + vp_align((size_t)n * 4) + 8192 + 4 * 16384;
-    if (d->ccl) need += vp_ccl_ws_bytes(d->width, d->height, n, d->max_labels);
-    return need;
-}
-
-// core: all pointers device; workspace already reserved and not yet carved past `ctx->ws_off`
 // frames per contour pass: the contour scratch is about 41 B/px per frame (85 MB at 1080p: sized for the worst case of 1.25 heads per
 // pixel); a pass takes as many frames as fit a budget of 16 GiB (VP_CT_SCRATCH_MB overrides) - measured at 1080p, batch 128 (round 3): 16
 // frames per pass 2.26 ms, 64 1.57 ms, 128 1.40 ms
@@ -299,15 +295,31 @@ static int ct_group_for(int w, int h, int max_contours)
     const long long per = (long long)vp_contours_ws_bytes(w, h, 1, max_contours);
     return (int)std::max<long long>(1, std::min<long long>(budget / per, 1 << 20));
 }
-static int chain_core(vp_ctx* ctx, const vp_chain_desc* d, const vp_chain_buffers* b, int n, const vp_contour_desc* cd = nullptr,
-                      const vp_contour_buffers* cb = nullptr)
+// temporaries of a chain over n frames; with cd, the scratch of its contour passes: one region for min(n, ct_group_for) frames, which
+// every group of frames uses again (stream order keeps them apart)
+struct chain_bufs { u64 *bits_t, *bits_a, *bits_b; int32_t* nl; vp_ccl_ws ccl; uint8_t* ct; size_t ct_bytes; };
+static void chain_want(vp_ws_frame& W, const vp_chain_desc* d, int n, chain_bufs* t, const vp_contour_desc* cd = nullptr)
 {
     const int w = d->width, h = d->height;
     const size_t bitbytes = (size_t)n * h * vp_ww(w) * 8;
-    TAKE(bits_t, u64*, bitbytes);   // threshold bits
-    TAKE(bits_a, u64*, bitbytes);
-    TAKE(bits_b, u64*, bitbytes);
-    TAKE(d_nl, int32_t*, (size_t)n * 4);
+    W.want(&t->bits_t, bitbytes);   // threshold bits
+    W.want(&t->bits_a, bitbytes);
+    W.want(&t->bits_b, bitbytes);
+    W.want(&t->nl, (size_t)n * 4);
+    memset(&t->ccl, 0, sizeof t->ccl);
+    if (d->ccl) vp_ccl_ws_want(W, w, h, n, d->max_labels, &t->ccl);
+    t->ct = nullptr;
+    t->ct_bytes = cd ? vp_contours_ws_bytes(w, h, std::min(n, ct_group_for(w, h, cd->max_contours)), cd->max_contours) : 0;
+    if (cd) W.want(&t->ct, t->ct_bytes);
+}
+
+// core: all pointers device; t: its temporaries, in the frame of the caller (chain_want with the same d, n and cd)
+static int chain_core(vp_ctx* ctx, const vp_chain_desc* d, const vp_chain_buffers* b, int n, const chain_bufs& t, const vp_contour_desc* cd = nullptr,
+                      const vp_contour_buffers* cb = nullptr)
+{
+    const int w = d->width, h = d->height;
+    u64 *bits_t = t.bits_t, *bits_a = t.bits_a, *bits_b = t.bits_b;
+    int32_t* d_nl = t.nl;
     vp_range3 q;
     norm_range(d->color_mode == VP_BGR2GRAY ? 1 : 3, d->lo, d->hi, &q);
     VP_TRY(vpk_color_thresh(ctx, d->color_mode, b->bgr, (size_t)w * 3, w, h, n, q, b->threshed, bits_t));
@@ -326,12 +338,7 @@ static int chain_core(vp_ctx* ctx, const vp_chain_desc* d, const vp_chain_buffer
     const bool need_clean_bits = d->ccl == 1 || (cd && cd->source == 1);
     const u64* ccl_bits = bits_t;
     const u64* clean_bits = bits_t;   // no morphology: the cleaned mask is the threshold mask
-    vp_ccl_ws ws;
-    memset(&ws, 0, sizeof ws);
-    if (d->ccl) {
-        vp_ccl_ws_carve(ctx, w, h, n, d->max_labels, &ws);
-        if (!vp_ccl_ws_ok(ws)) return vp_fail(ctx, VP_ERR_NOMEM, "ccl workspace");
-    }
+    const vp_ccl_ws& ws = t.ccl;
     if ((!st.empty() && (need_clean_bits || b->cleaned)) || (st.empty() && b->cleaned)) {
         if (st.empty()) {
             VP_TRY(vpk_unpack_bits(ctx, bits_t, w, h, n, b->cleaned));
@@ -347,15 +354,13 @@ static int chain_core(vp_ctx* ctx, const vp_chain_desc* d, const vp_chain_buffer
         const u64* src = cd->source == 1 ? clean_bits : bits_t;
         const size_t fw = (size_t)h * vp_ww(w);
         const size_t mc = (size_t)cd->max_contours;
-        const size_t mark = ctx->ws_off;
         const int group = ct_group_for(w, h, cd->max_contours);
         // speckled frames in the last batch (its prefix kernel left the head counts in pinned memory): the bookkeeping as launches over
         // the chip instead of one block per frame (VP_CT_MANY=0 / 1: never / always)
         const bool many = ct_want_many(vp_ct_batch_hint(ctx));
         for (int f0 = 0; f0 < n; f0 += group) {
             const int g = std::min(group, n - f0);
-            ctx->ws_off = mark;   // every group reuses the same scratch (stream order keeps them apart)
-            VP_TRY(vpk_find_contours(ctx, src + (size_t)f0 * fw, w, h, g, cd->mode, cd->method, cb->counts + f0 * mc, cb->is_hole + f0 * mc,
+            VP_TRY(vpk_find_contours(ctx, t.ct, t.ct_bytes, src + (size_t)f0 * fw, w, h, g, cd->mode, cd->method, cb->counts + f0 * mc, cb->is_hole + f0 * mc,
                                      cb->offsets + f0 * mc, cb->points + 2 * (size_t)f0 * (size_t)cd->max_points, cd->max_contours,
                                      cd->max_points, cb->info + 2 * (size_t)f0, many));
         }
@@ -364,7 +369,7 @@ static int chain_core(vp_ctx* ctx, const vp_chain_desc* d, const vp_chain_buffer
     };
     // The contour pass needs the mask only, not the labelling: when the chain does both it is queued on the context's side stream as
     // soon as the mask exists and runs beside the labelling and its label write (latency-bound launches beside a bandwidth-bound one);
-    // the caller's stream joins it at the end.  One pass for the whole batch only (the scratch is carved once).  VP_CT_SIDE=0: in a row.
+    // the caller's stream joins it at the end.  One pass for the whole batch only (there is one scratch region).  VP_CT_SIDE=0: in a row.
     static const bool ct_side_off = getenv("VP_CT_SIDE") && atoi(getenv("VP_CT_SIDE")) == 0;
     const bool ct_side = cd && d->ccl && !ct_side_off && ctx->opt.v[VP_OPT_CHAIN_STREAMS] == 1 && ct_group_for(w, h, cd->max_contours) >= n;
     int rc_ct = VP_OK;
@@ -406,12 +411,23 @@ static int check_cdesc(vp_ctx* ctx, const vp_contour_desc* cd, const vp_contour_
 }
 
 // Runs the chain for n frames, split into sub-batches on the context's internal streams (fork/join around the
-// caller-visible stream).  Frames are independent, so the split changes scheduling only.
-static int chain_split(vp_ctx* ctx, const vp_chain_desc* d, const vp_chain_buffers* b, int n)
+// caller-visible stream).  Frames are independent, so the split changes scheduling only.  Each sub-batch has temporaries of its own.
+struct chain_parts { int S; int cnt[4]; chain_bufs t[4]; };
+static void chain_split_want(vp_ws_frame& W, vp_ctx* ctx, const vp_chain_desc* d, int n, chain_parts* p)
 {
-    int S = ctx->opt.v[VP_OPT_CHAIN_STREAMS];
+    int S = ctx->opt.v[VP_OPT_CHAIN_STREAMS];   // 1..4 (vp_options.h)
     if (S > n / 4) S = n / 4;      // keep sub-batches worth a launch
-    if (S <= 1) return chain_core(ctx, d, b, n);
+    if (S < 1) S = 1;
+    p->S = S;
+    for (int s = 0; s < S; s++) {
+        p->cnt[s] = n / S + (s < n % S ? 1 : 0);
+        chain_want(W, d, p->cnt[s], &p->t[s]);
+    }
+}
+static int chain_split(vp_ctx* ctx, const vp_chain_desc* d, const vp_chain_buffers* b, int n, const chain_parts& p)
+{
+    const int S = p.S;
+    if (S <= 1) return chain_core(ctx, d, b, n, p.t[0]);
     const size_t npx = (size_t)d->width * d->height;
     const size_t ml = (size_t)(d->ccl ? d->max_labels : 0);
     hipStream_t user = ctx->stream;
@@ -419,7 +435,7 @@ static int chain_split(vp_ctx* ctx, const vp_chain_desc* d, const vp_chain_buffe
     int rc = VP_OK;
     int f0 = 0;
     for (int s = 0; s < S && rc == VP_OK; s++) {
-        const int cnt = n / S + (s < n % S ? 1 : 0);
+        const int cnt = p.cnt[s];
         vp_chain_buffers sb = *b;
         sb.bgr = b->bgr + (size_t)f0 * npx * 3;
         if (b->threshed) sb.threshed = b->threshed + (size_t)f0 * npx;
@@ -431,7 +447,7 @@ static int chain_split(vp_ctx* ctx, const vp_chain_desc* d, const vp_chain_buffe
         hipError_t e = hipStreamWaitEvent(ctx->chain.aux[s], ctx->chain.ev_fork, 0);
         if (e != hipSuccess) { rc = vp_fail(ctx, VP_ERR_HIP, "hipStreamWaitEvent", e); break; }
         ctx->stream = ctx->chain.aux[s];
-        rc = chain_core(ctx, d, &sb, cnt);
+        rc = chain_core(ctx, d, &sb, cnt, p.t[s]);
         ctx->stream = user;
         // join whatever was queued on the side stream, also after an error: it must not still run when the next call reuses the workspace
         const hipError_t e1 = hipEventRecord(ctx->chain.ev_join[s], ctx->chain.aux[s]);
@@ -445,13 +461,32 @@ static int chain_split(vp_ctx* ctx, const vp_chain_desc* d, const vp_chain_buffe
     return rc;
 }
 
+// device copies of the outputs the host form was asked for (both host entries): d->x is wanted where host->x is given
+static void chain_host_want(vp_ws_frame& W, const vp_chain_desc* desc, const vp_chain_buffers* host, int n, vp_chain_buffers* d)
+{
+    const size_t npx = (size_t)n * desc->width * desc->height;
+    const size_t ml = (size_t)(desc->ccl ? desc->max_labels : 1);
+    memset(d, 0, sizeof *d);
+    W.want(&d->bgr, npx * 3);
+    if (host->threshed) W.want(&d->threshed, npx);
+    if (host->cleaned) W.want(&d->cleaned, npx);
+    if (!desc->ccl) return;
+    if (host->labels) W.want(&d->labels, npx * 4);
+    if (host->stats) W.want(&d->stats, n * ml * 20);
+    if (host->centroids) W.want(&d->centroids, n * ml * 16);
+    W.want(&d->nlabels, (size_t)n * 4);
+}
+
 int vp_chain_run(vp_ctx* ctx, const vp_chain_desc* desc, const vp_chain_buffers* dev, int n_frames)
 {
     VP_TRY(check_ctx(ctx));
     VP_TRY(check_desc(ctx, desc, n_frames));
     if (!dev || !dev->bgr) return vp_fail(ctx, VP_ERR_INVALID, "chain: bgr");
-    VP_TRY(vp_ws_reserve(ctx, chain_ws_bytes(desc, n_frames) + 4 * 65536));
-    return chain_split(ctx, desc, dev, n_frames);
+    vp_ws_frame W;
+    chain_parts p;
+    chain_split_want(W, ctx, desc, n_frames, &p);
+    VP_TRY(vp_ws_commit(ctx, W, "vp_chain_run"));
+    return chain_split(ctx, desc, dev, n_frames, p);
 }
 
 int vp_chain_run_host(vp_ctx* ctx, const vp_chain_desc* desc, const vp_chain_buffers* host, int n)
@@ -461,23 +496,14 @@ int vp_chain_run_host(vp_ctx* ctx, const vp_chain_desc* desc, const vp_chain_buf
     if (!host || !host->bgr) return vp_fail(ctx, VP_ERR_INVALID, "chain: bgr");
     const size_t npx = (size_t)n * desc->width * desc->height;
     const size_t ml = (size_t)(desc->ccl ? desc->max_labels : 1);
-    VP_TRY(vp_ws_reserve(ctx, chain_ws_bytes(desc, n) + vp_align(npx * 3) + 2 * vp_align(npx) + vp_align(npx * 4) +
-                                  vp_align(n * ml * 20) + vp_align(n * ml * 16) + vp_align((size_t)n * 4) + 8192));
+    vp_ws_frame W;
     vp_chain_buffers d;
-    memset(&d, 0, sizeof d);
-    TAKE(d_bgr, uint8_t*, npx * 3);
-    d.bgr = d_bgr;
-    if (host->threshed) { d.threshed = (uint8_t*)vp_ws_take(ctx, npx); if (!d.threshed) return vp_fail(ctx, VP_ERR_NOMEM, "workspace"); }
-    if (host->cleaned) { d.cleaned = (uint8_t*)vp_ws_take(ctx, npx); if (!d.cleaned) return vp_fail(ctx, VP_ERR_NOMEM, "workspace"); }
-    if (desc->ccl) {
-        if (host->labels) { d.labels = (int32_t*)vp_ws_take(ctx, npx * 4); if (!d.labels) return vp_fail(ctx, VP_ERR_NOMEM, "workspace"); }
-        if (host->stats) { d.stats = (int32_t*)vp_ws_take(ctx, n * ml * 20); if (!d.stats) return vp_fail(ctx, VP_ERR_NOMEM, "workspace"); }
-        if (host->centroids) { d.centroids = (double*)vp_ws_take(ctx, n * ml * 16); if (!d.centroids) return vp_fail(ctx, VP_ERR_NOMEM, "workspace"); }
-        d.nlabels = (int32_t*)vp_ws_take(ctx, (size_t)n * 4);
-        if (!d.nlabels) return vp_fail(ctx, VP_ERR_NOMEM, "workspace");
-    }
-    VP_TRY(h2d(ctx, d_bgr, host->bgr, npx * 3));
-    VP_TRY(chain_split(ctx, desc, &d, n));
+    chain_host_want(W, desc, host, n, &d);
+    chain_parts p;
+    chain_split_want(W, ctx, desc, n, &p);
+    VP_TRY(vp_ws_commit(ctx, W, "vp_chain_run_host"));
+    VP_TRY(h2d(ctx, const_cast<uint8_t*>(d.bgr), host->bgr, npx * 3));
+    VP_TRY(chain_split(ctx, desc, &d, n, p));
     if (host->threshed) VP_TRY(d2h(ctx, host->threshed, d.threshed, npx));
     if (host->cleaned) VP_TRY(d2h(ctx, host->cleaned, d.cleaned, npx));
     if (desc->ccl) {
@@ -496,9 +522,11 @@ int vp_chain_run_contours(vp_ctx* ctx, const vp_chain_desc* desc, const vp_chain
     VP_TRY(check_desc(ctx, desc, n_frames));
     VP_TRY(check_cdesc(ctx, cdesc, cdev));
     if (!dev || !dev->bgr) return vp_fail(ctx, VP_ERR_INVALID, "chain: bgr");
-    VP_TRY(vp_ws_reserve(ctx, chain_ws_bytes(desc, n_frames) + 4 * 65536 +
-                                  vp_contours_ws_bytes(desc->width, desc->height, std::min(n_frames, ct_group_for(desc->width, desc->height, cdesc->max_contours)), cdesc->max_contours)));
-    return chain_core(ctx, desc, dev, n_frames, cdesc, cdev);
+    vp_ws_frame W;
+    chain_bufs t;
+    chain_want(W, desc, n_frames, &t, cdesc);
+    VP_TRY(vp_ws_commit(ctx, W, "vp_chain_run_contours"));
+    return chain_core(ctx, desc, dev, n_frames, t, cdesc, cdev);
 }
 
 int vp_chain_run_contours_host(vp_ctx* ctx, const vp_chain_desc* desc, const vp_chain_buffers* host, const vp_contour_desc* cdesc,
@@ -511,33 +539,22 @@ int vp_chain_run_contours_host(vp_ctx* ctx, const vp_chain_desc* desc, const vp_
     const size_t npx = (size_t)n * desc->width * desc->height;
     const size_t ml = (size_t)(desc->ccl ? desc->max_labels : 1);
     const size_t mc = (size_t)cdesc->max_contours, mp = (size_t)cdesc->max_points;
-    VP_TRY(vp_ws_reserve(ctx, chain_ws_bytes(desc, n) + vp_align(npx * 3) + 2 * vp_align(npx) + vp_align(npx * 4) + vp_align(n * ml * 20) +
-                                  vp_align(n * ml * 16) + vp_align((size_t)n * 4) + vp_align((size_t)n * 8) + 2 * vp_align(n * mc * 4) +
-                                  vp_align(n * mc) + vp_align(n * mp * 8) + vp_align(n * mc * 64) + 16384 +
-                                  vp_contours_ws_bytes(desc->width, desc->height, std::min(n, ct_group_for(desc->width, desc->height, cdesc->max_contours)), cdesc->max_contours)));
+    vp_ws_frame W;
     vp_chain_buffers d;
-    memset(&d, 0, sizeof d);
-    TAKE(d_bgr, uint8_t*, npx * 3);
-    d.bgr = d_bgr;
-    if (host->threshed) { d.threshed = (uint8_t*)vp_ws_take(ctx, npx); if (!d.threshed) return vp_fail(ctx, VP_ERR_NOMEM, "workspace"); }
-    if (host->cleaned) { d.cleaned = (uint8_t*)vp_ws_take(ctx, npx); if (!d.cleaned) return vp_fail(ctx, VP_ERR_NOMEM, "workspace"); }
-    if (desc->ccl) {
-        if (host->labels) { d.labels = (int32_t*)vp_ws_take(ctx, npx * 4); if (!d.labels) return vp_fail(ctx, VP_ERR_NOMEM, "workspace"); }
-        if (host->stats) { d.stats = (int32_t*)vp_ws_take(ctx, n * ml * 20); if (!d.stats) return vp_fail(ctx, VP_ERR_NOMEM, "workspace"); }
-        if (host->centroids) { d.centroids = (double*)vp_ws_take(ctx, n * ml * 16); if (!d.centroids) return vp_fail(ctx, VP_ERR_NOMEM, "workspace"); }
-        d.nlabels = (int32_t*)vp_ws_take(ctx, (size_t)n * 4);
-        if (!d.nlabels) return vp_fail(ctx, VP_ERR_NOMEM, "workspace");
-    }
+    chain_host_want(W, desc, host, n, &d);
     vp_contour_buffers c;
-    c.info = (int32_t*)vp_ws_take(ctx, (size_t)n * 8);
-    c.counts = (int32_t*)vp_ws_take(ctx, n * mc * 4);
-    c.offsets = (int32_t*)vp_ws_take(ctx, n * mc * 4);
-    c.is_hole = (uint8_t*)vp_ws_take(ctx, n * mc);
-    c.points = (int32_t*)vp_ws_take(ctx, n * mp * 8);
-    c.features = chost->features ? (double*)vp_ws_take(ctx, n * mc * 64) : nullptr;
-    if (!c.info || !c.counts || !c.offsets || !c.is_hole || !c.points || (chost->features && !c.features)) return vp_fail(ctx, VP_ERR_NOMEM, "workspace");
-    VP_TRY(h2d(ctx, d_bgr, host->bgr, npx * 3));
-    VP_TRY(chain_core(ctx, desc, &d, n, cdesc, &c));
+    W.want(&c.info, (size_t)n * 8);
+    W.want(&c.counts, n * mc * 4);
+    W.want(&c.offsets, n * mc * 4);
+    W.want(&c.is_hole, n * mc);
+    W.want(&c.points, n * mp * 8);
+    c.features = nullptr;
+    if (chost->features) W.want(&c.features, n * mc * 64);
+    chain_bufs t;
+    chain_want(W, desc, n, &t, cdesc);
+    VP_TRY(vp_ws_commit(ctx, W, "vp_chain_run_contours_host"));
+    VP_TRY(h2d(ctx, const_cast<uint8_t*>(d.bgr), host->bgr, npx * 3));
+    VP_TRY(chain_core(ctx, desc, &d, n, t, cdesc, &c));
     if (host->threshed) VP_TRY(d2h(ctx, host->threshed, d.threshed, npx));
     if (host->cleaned) VP_TRY(d2h(ctx, host->cleaned, d.cleaned, npx));
     if (desc->ccl) {

@@ -324,9 +324,9 @@ static int polylines_dev(vp_ctx* ctx, const char* who, uint8_t* d_img, int w, in
     memcpy(hp, pts, N * 8);
     link(reinterpret_cast<int32_t*>(hp + N * 8));
     if (nfill) memcpy(hp + fill_off, fill->data(), nfill * sizeof(vp_fill_poly));
-    int rc = vp_ws_reserve(ctx, vp_align(bytes) + 4096);
-    uint8_t* d_buf = rc == VP_OK ? (uint8_t*)vp_ws_take(ctx, bytes) : nullptr;
-    if (rc == VP_OK && !d_buf) rc = vp_fail(ctx, VP_ERR_NOMEM, "workspace exhausted: overlay vertices");
+    vp_ws_frame W;
+    uint8_t* d_buf; W.want(&d_buf, bytes);
+    int rc = vp_ws_commit(ctx, W, "overlay vertices");
     if (rc == VP_OK) rc = h2d(ctx, d_buf, hp, bytes);
     if (rc == VP_OK && nfill)
         rc = vpk_fill_polys(ctx, d_img, w, h, cn, reinterpret_cast<const int32_t*>(d_buf), (int)N, reinterpret_cast<const vp_fill_poly*>(d_buf + fill_off), (int)nfill,

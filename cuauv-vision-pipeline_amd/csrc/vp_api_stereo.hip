@@ -77,8 +77,9 @@ int vp_stereo_bm_dev(vp_ctx* ctx, const uint8_t* left_dev, size_t left_stride, c
     VP_TRY(check_ctx(ctx));
     vp_stereo_plan P;
     vp_stereo_make_plan(w, h, num_disparities, block_size, min_disparity, &P);
-    VP_TRY(vp_ws_reserve(ctx, vp_align(P.ws_bytes) + 1024));
-    TAKE(d_ws, uint8_t*, P.ws_bytes);
+    vp_ws_frame W;
+    uint8_t* d_ws; W.want(&d_ws, P.ws_bytes);
+    VP_TRY(vp_ws_commit(ctx, W, "vp_stereo_bm_dev"));
     return vpk_stereo_bm(ctx, left_dev, left_stride, right_dev, right_stride, w, h, num_disparities, min_disparity, pre_filter_cap, texture_threshold, uniqueness_ratio, P,
                          d_ws, disp_dev, disp_stride);
 }
@@ -92,11 +93,12 @@ int vp_stereo_bm_u8(vp_ctx* ctx, const uint8_t* left, const uint8_t* right, int 
     VP_TRY(check_ctx(ctx));
     vp_stereo_plan P;
     vp_stereo_make_plan(w, h, num_disparities, block_size, min_disparity, &P);
-    VP_TRY(vp_ws_reserve(ctx, 2 * vp_align(row * h) + vp_align(row * 2 * h) + vp_align(P.ws_bytes) + 1024));
-    TAKE(d_left, uint8_t*, row * h);
-    TAKE(d_right, uint8_t*, row * h);
-    TAKE(d_disp, int16_t*, row * 2 * h);
-    TAKE(d_ws, uint8_t*, P.ws_bytes);
+    vp_ws_frame W;
+    uint8_t* d_left; W.want(&d_left, row * h);
+    uint8_t* d_right; W.want(&d_right, row * h);
+    int16_t* d_disp; W.want(&d_disp, row * 2 * h);
+    uint8_t* d_ws; W.want(&d_ws, P.ws_bytes);
+    VP_TRY(vp_ws_commit(ctx, W, "vp_stereo_bm_u8"));
     VP_TRY(h2d(ctx, d_left, left, row * h));
     VP_TRY(h2d(ctx, d_right, right, row * h));
     VP_TRY(vpk_stereo_bm(ctx, d_left, row, d_right, row, w, h, num_disparities, min_disparity, pre_filter_cap, texture_threshold, uniqueness_ratio, P, d_ws, d_disp, row * 2));
@@ -182,9 +184,10 @@ int vp_depth_from_disparity_i16(vp_ctx* ctx, const int16_t* disp, int w, int h, 
     const size_t n = w > 0 ? (size_t)w : 0;
     if (const char* why = depth_check(disp, n * 2, w, h, depth, n * 4)) return vp_fail(ctx, VP_ERR_INVALID, why);
     VP_TRY(check_ctx(ctx));
-    VP_TRY(vp_ws_reserve(ctx, vp_align(n * 2 * h) + vp_align(n * 4 * h) + 1024));
-    TAKE(d_disp, int16_t*, n * 2 * h);
-    TAKE(d_depth, float*, n * 4 * h);
+    vp_ws_frame W;
+    int16_t* d_disp; W.want(&d_disp, n * 2 * h);
+    float* d_depth; W.want(&d_depth, n * 4 * h);
+    VP_TRY(vp_ws_commit(ctx, W, "vp_depth_from_disparity_i16"));
     VP_TRY(h2d(ctx, d_disp, disp, n * 2 * h));
     VP_TRY(vpk_stereo_depth(ctx, d_disp, n * 2, w, h, focal_px * baseline_m, d_depth, n * 4));
     VP_TRY(d2h(ctx, depth, d_depth, n * 4 * h));

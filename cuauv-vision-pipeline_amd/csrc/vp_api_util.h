@@ -7,10 +7,6 @@
 #include <cstring>
 #include <vector>
 
-#define TAKE(var, type, bytes)                                                   \
-    type var = (type)vp_ws_take(ctx, (bytes));                                   \
-    if (!var) return vp_fail(ctx, VP_ERR_NOMEM, "workspace exhausted: " #var)
-
 #define VP_TRY(x) do { int rc__ = (x); if (rc__ != VP_OK) return rc__; } while (0)
 
 static inline int h2d(vp_ctx* ctx, void* d, const void* h, size_t n)

@@ -632,11 +632,21 @@ int vpk_hsv2bgr(vp_ctx* ctx, const uint8_t* d_src, size_t npx, uint8_t* d_dst)
     return VP_OK;
 }
 
-size_t vp_balance_ws_bytes(int n, int tiles) { return vp_align((size_t)n * tiles * 772 * 4 + 64) + vp_align((size_t)n * 1024 * 4) + vp_align((size_t)n * tiles * 768) +
-                                                      vp_align((size_t)n * 512) + vp_align(sizeof(cb_plan) * (size_t)n) + vp_align(sizeof(hsi_state) * (size_t)n) + 4096 + 2048; }
+// tiles: hblocks * vblocks as the caller passes them to vpk_color_balance (which uses one tile without VP_CB_EQUALIZE_RGB)
+void vp_balance_want(vp_ws_frame& W, int n, int tiles, int flags, vp_balance_ws* bw)
+{
+    W.want(&bw->hist, (size_t)n * tiles * 772 * 4 + 64);   // histograms | per-tile channel-equality flags | fold counter
+    W.want(&bw->svhist, (size_t)n * 1024 * 4);   // S/V histograms; reused as the four radix histograms of the HSI stage
+    W.want(&bw->lut, (size_t)n * tiles * 768);
+    W.want(&bw->svlut, (size_t)n * 512);
+    W.want(&bw->plans, sizeof(cb_plan) * (size_t)n);
+    W.want(&bw->hst, sizeof(hsi_state) * (size_t)n);
+    bw->powtab = nullptr;
+    if (flags & VP_CB_ADAPTIVE_CAST) W.want(&bw->powtab, 256 * sizeof(double));
+}
 
 // d_src / d_dst: (n, h, w, 3) packed; d_dst may equal d_src.  Frames must start 4-byte aligned (w*h*3 % 4 == 0 or n == 1).
-int vpk_color_balance(vp_ctx* ctx, const uint8_t* d_src, uint8_t* d_dst, int w, int h, int n, int flags, int hblocks, int vblocks)
+int vpk_color_balance(vp_ctx* ctx, const uint8_t* d_src, uint8_t* d_dst, int w, int h, int n, int flags, int hblocks, int vblocks, const vp_balance_ws& bw)
 {
     if (hblocks <= 0 || vblocks <= 0) return vp_fail(ctx, VP_ERR_INVALID, "colour balance: tiles");
     if ((flags & VP_CB_EQUALIZE_RGB) && (w % hblocks || h % vblocks))
@@ -647,15 +657,13 @@ int vpk_color_balance(vp_ctx* ctx, const uint8_t* d_src, uint8_t* d_dst, int w, 
     const size_t npx = (size_t)w * h;
     if (n > 1 && (npx * 3) % 4) return vp_fail(ctx, VP_ERR_UNSUPPORTED, "colour balance: batched frames must be 4-byte aligned");
     cb_params P = {w, h, n, flags, hblocks, vblocks, w / hblocks, h / vblocks};
-    u32* hist = (u32*)vp_ws_take(ctx, (size_t)n * tiles * 772 * 4 + 64);   // histograms | per-tile channel-equality flags | fold counter
-    u32* neq = hist ? hist + (size_t)n * tiles * 768 : nullptr;
-    u32* folds = neq ? neq + (size_t)n * tiles * 4 : nullptr;
-    u32* svhist = (u32*)vp_ws_take(ctx, (size_t)n * 1024 * 4);   // S/V histograms; reused as the four radix histograms of the HSI stage
-    uint8_t* lut = (uint8_t*)vp_ws_take(ctx, (size_t)n * tiles * 768);
-    uint8_t* svlut = (uint8_t*)vp_ws_take(ctx, (size_t)n * 512);
-    cb_plan* plans = (cb_plan*)vp_ws_take(ctx, sizeof(cb_plan) * (size_t)n);
-    hsi_state* hst = (hsi_state*)vp_ws_take(ctx, sizeof(hsi_state) * (size_t)n);
-    if (!hist || !svhist || !lut || !svlut || !plans || !hst) return vp_fail(ctx, VP_ERR_NOMEM, "colour balance workspace");
+    u32* hist = bw.hist;
+    u32* neq = hist + (size_t)n * tiles * 768;
+    u32* folds = neq + (size_t)n * tiles * 4;
+    u32* svhist = bw.svhist;
+    uint8_t *lut = bw.lut, *svlut = bw.svlut;
+    cb_plan* plans = (cb_plan*)bw.plans;
+    hsi_state* hst = (hsi_state*)bw.hst;
     hipStream_t s = ctx->stream;
     const bool tiled = tiles > 1, hsv = (flags & VP_CB_HSV_CONTRAST) != 0;
     // enough blocks to fill the chip, few enough that the per-block table loads and histogram flushes stay small
@@ -674,8 +682,7 @@ int vpk_color_balance(vp_ctx* ctx, const uint8_t* d_src, uint8_t* d_dst, int w, 
         static double host_tab[256];
         static std::once_flag made;                  // contexts are per thread: two of them may get here together
         std::call_once(made, [] { for (int v = 0; v < 256; v++) host_tab[v] = pow((255. - v) / 255., 0.25); });
-        powtab = (double*)vp_ws_take(ctx, sizeof host_tab);
-        if (!powtab) return vp_fail(ctx, VP_ERR_NOMEM, "colour balance workspace");
+        powtab = bw.powtab;
         VP_HIP(ctx, hipMemcpyAsync(powtab, host_tab, sizeof host_tab, hipMemcpyHostToDevice, s));
     }
     hipLaunchKernelGGL(k_cb_plan1, dim3((unsigned)n), dim3(256), 0, s, P, hist, neq, d_src, plans, lut, folds, force_fold, (const double*)powtab);

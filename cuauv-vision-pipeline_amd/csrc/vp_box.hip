@@ -167,10 +167,10 @@ __global__ __launch_bounds__(256) void k_box_cols(const uint16_t* __restrict__ m
 
 }  // namespace
 
-size_t vp_box_ws_bytes(int w, int h, int cn, const vp_box_plan& P) { return P.onepass ? 0 : (size_t)w * cn * h * 2; }
+size_t vp_box_mid_bytes(int w, int h, int cn, const vp_box_plan& P) { return P.onepass ? 0 : (size_t)w * cn * h * 2; }
 
 // P: a plan vp_box_make_plan accepted for (w, h, cn), its div filled when it normalises; sstride: bytes between source rows; d_dst
-// packed, P.esize bytes per element; d_mid: vp_box_ws_bytes of workspace (unused by the one-pass path)
+// packed, P.esize bytes per element; d_mid: vp_box_mid_bytes of workspace (unused by the one-pass path)
 int vpk_box_filter(vp_ctx* ctx, const uint8_t* d_src, size_t sstride, int w, int h, int cn, const vp_box_plan& P, uint16_t* d_mid, void* d_dst)
 {
     vp_prof_scope ps(ctx, VPK_OTHER);

@@ -73,47 +73,30 @@ size_t vp_ccl_nids(int w, int h)
 // which of the two labelling launches takes a strip (vp_ccl3.inl): one byte per (frame, strip)
 static size_t c3_items_bytes(int n, int h) { return (size_t)n * c3_strips_cap(h); }
 
-size_t vp_ccl_ws_bytes(int w, int h, int n, int max_labels)
+void vp_ccl_ws_want(vp_ws_frame& W, int w, int h, int n, int max_labels, vp_ccl_ws* out)
 {
     const size_t nids = vp_ccl_nids(w, h);
+    W.want(&out->parent, nids * 4 * n);
+    W.want(&out->seglabel, nids * 4 * n);
+    W.want(&out->flags, nids / 8 * n);
+    W.want(&out->prefix, nids / 8 * n);
+    W.want(&out->acc, sizeof(ccl_acc) * (size_t)max_labels * n);
+    W.want(&out->wordlabel, (size_t)n * h * vp_ww(w) * 4);
+    W.want(&out->bgpart, sizeof(contrib) * BG_PARTS * (size_t)n);
     const size_t ns = c2_strips_max(h) * (size_t)n;
-    return vp_align(nids * 4 * n) * 2 + vp_align(nids / 8 * n) * 2 + vp_align(sizeof(ccl_acc) * (size_t)max_labels * n) +
-           vp_align((size_t)n * h * vp_ww(w) * 4) + vp_align(sizeof(contrib) * BG_PARTS * (size_t)n) +
-           vp_align(ns * 4) + vp_align(ns * C2_RC * sizeof(contrib)) + vp_align(ns * sizeof(c2_box)) + vp_align(ns * C2_RC * 4) +
-           vp_align((size_t)n * 4) + 2 * vp_align(nids / 8 * n) + vp_align((size_t)n * 4) + 256 + vp_align((size_t)n * C3_STATE_BYTES) +
-           vp_align((size_t)n * c3_strips_cap(h) * 12) + vp_align((size_t)n * c3_strips_cap(h) * 40) + vp_align(c3_items_bytes(n, h)) + 4096 + 1024;
-}
-
-void vp_ccl_ws_carve(vp_ctx* ctx, int w, int h, int n, int max_labels, vp_ccl_ws* out)
-{
-    const size_t nids = vp_ccl_nids(w, h);
-    out->parent = (u32*)vp_ws_take(ctx, nids * 4 * n);
-    out->seglabel = (u32*)vp_ws_take(ctx, nids * 4 * n);
-    out->flags = (u32*)vp_ws_take(ctx, nids / 8 * n);
-    out->prefix = (u32*)vp_ws_take(ctx, nids / 8 * n);
-    out->acc = vp_ws_take(ctx, sizeof(ccl_acc) * (size_t)max_labels * n);
-    out->wordlabel = (u32*)vp_ws_take(ctx, (size_t)n * h * vp_ww(w) * 4);
-    out->bgpart = vp_ws_take(ctx, sizeof(contrib) * BG_PARTS * (size_t)n);
-    const size_t ns = c2_strips_max(h) * (size_t)n;
-    out->c2_ncomp = (u32*)vp_ws_take(ctx, ns * 4);
-    out->c2_recs = vp_ws_take(ctx, ns * C2_RC * sizeof(contrib));
-    out->c2_bgbox = vp_ws_take(ctx, ns * sizeof(c2_box));
-    out->c2_label = (u32*)vp_ws_take(ctx, ns * C2_RC * 4);
-    out->c2_crowded = (u32*)vp_ws_take(ctx, (size_t)n * 4);
-    out->c3_child = (u32*)vp_ws_take(ctx, nids / 8 * n);
-    out->c3_lroot = (u32*)vp_ws_take(ctx, nids / 8 * n);
-    out->c3_clist = (u32*)vp_ws_take(ctx, (size_t)n * 4);
-    out->c3_ncrowded = (u32*)vp_ws_take(ctx, 4);
-    out->c3_state = vp_ws_take(ctx, (size_t)n * C3_STATE_BYTES);
-    out->c3_tot = vp_ws_take(ctx, (size_t)n * c3_strips_cap(h) * 40);              // sizeof(contrib)
-    out->c3_barr = (u32*)vp_ws_take(ctx, (size_t)n * c3_strips_cap(h) * 12);   // per frame: boundary arrivals | boundaries done per strip | roots per strip
-    out->c3_items = (unsigned char*)vp_ws_take(ctx, c3_items_bytes(n, h));     // per (handed-over frame, strip): 1 = light labelling launch, 2 = heavy
-}
-
-bool vp_ccl_ws_ok(const vp_ccl_ws& ws)
-{
-    return ws.parent && ws.seglabel && ws.flags && ws.prefix && ws.acc && ws.wordlabel && ws.bgpart && ws.c2_ncomp && ws.c2_recs &&
-           ws.c2_bgbox && ws.c2_label && ws.c2_crowded && ws.c3_child && ws.c3_lroot && ws.c3_clist && ws.c3_ncrowded && ws.c3_state && ws.c3_barr && ws.c3_tot && ws.c3_items;
+    W.want(&out->c2_ncomp, ns * 4);
+    W.want(&out->c2_recs, ns * C2_RC * sizeof(contrib));
+    W.want(&out->c2_bgbox, ns * sizeof(c2_box));
+    W.want(&out->c2_label, ns * C2_RC * 4);
+    W.want(&out->c2_crowded, (size_t)n * 4);
+    W.want(&out->c3_child, nids / 8 * n);
+    W.want(&out->c3_lroot, nids / 8 * n);
+    W.want(&out->c3_clist, (size_t)n * 4);
+    W.want(&out->c3_ncrowded, 4);
+    W.want(&out->c3_state, (size_t)n * C3_STATE_BYTES);
+    W.want(&out->c3_tot, (size_t)n * c3_strips_cap(h) * 40);              // sizeof(contrib)
+    W.want(&out->c3_barr, (size_t)n * c3_strips_cap(h) * 12);   // per frame: boundary arrivals | boundaries done per strip | roots per strip
+    W.want(&out->c3_items, c3_items_bytes(n, h));     // per (handed-over frame, strip): 1 = light labelling launch, 2 = heavy
 }
 
 // ---- whole-image global-memory path (fallback for images too wide for the LDS strip kernel) ---------------

@@ -1404,7 +1404,7 @@ static hipError_t ctt_sort_bytes(int max_contours, size_t& bytes)
     return hipcub::DeviceRadixSort::SortPairs(nullptr, bytes, p, p, p, p, max_contours, 0, ct_key_bits(max_contours));
 }
 
-// what a pass carves: the plan's workspace table (vp_contours_plan.h), which vpk_find_contours walks
+// the scratch region a pass is given: the totals of the plan's workspace table (vp_contours_plan.h), which vpk_find_contours places in it
 size_t vp_contour_tree_ws_bytes(int max_contours)
 {
     size_t sort_bytes;
@@ -1453,8 +1453,8 @@ uint32_t vp_ct_batch_hint(vp_ctx* ctx)
 //                         pass counted very many heads - the caller's guess, the results do not depend on it)
 //   the hierarchy pass:   5 + 2 `rounds_tree` more, and the radix sort's own
 // d_nheads_out (nullable, [n]): the frames' head counts.
-int vpk_find_contours(vp_ctx* ctx, const u64* d_bits, int w, int h, int n, int mode, int method, int32_t* d_counts, uint8_t* d_is_hole,
-                      int32_t* d_offsets, int32_t* d_points, int max_contours, long long max_points, int32_t* d_info, bool many_heads,
+int vpk_find_contours(vp_ctx* ctx, uint8_t* d_ws, size_t ws_bytes, const u64* d_bits, int w, int h, int n, int mode, int method, int32_t* d_counts,
+                      uint8_t* d_is_hole, int32_t* d_offsets, int32_t* d_points, int max_contours, long long max_points, int32_t* d_info, bool many_heads,
                       uint32_t* d_nheads_out, const vp_contour_mirror* host, bool defer_big, int32_t* d_hier)
 {
     size_t sort_bytes = 0;
@@ -1463,9 +1463,13 @@ int vpk_find_contours(vp_ctx* ctx, const u64* d_bits, int w, int h, int n, int m
                                    sort_bytes);
     if (P.status != VP_OK) return vp_fail(ctx, P.status, P.why);
     void* ws[CTW_ALL] = {};
-    for (int i = 0; i < P.nws; i++)
-        if (!(ws[i] = vp_ws_take(ctx, P.ws[i].bytes)))
-            return vp_fail(ctx, VP_ERR_NOMEM, i < CTW_BASE ? "contour workspace" : "contour hierarchy workspace");
+    size_t end = 0;
+    for (int i = 0; i < P.nws; i++) {                      // the table in the plan's order, every array on a 256-byte boundary of d_ws
+        const size_t off = ct_align(end);
+        end = off + P.ws[i].bytes;
+        if (end > ws_bytes) return vp_fail(ctx, VP_ERR_NOMEM, i < CTW_BASE ? "contour workspace" : "contour hierarchy workspace");
+        ws[i] = d_ws + off;
+    }
     u64* hmaps = (u64*)ws[CTW_HMAPS];
     u32 *hbase = (u32*)ws[CTW_HBASE], *head_pix = (u32*)ws[CTW_HEAD_PIX], *hkey = (u32*)ws[CTW_HKEY], *partsum = (u32*)ws[CTW_PARTSUM];
     uint8_t* cnt8 = (uint8_t*)ws[CTW_CNT8];

@@ -1,6 +1,6 @@
 // Host arithmetic of the contour dispatch (vpk_find_contours, vp_contours.inl): what is refused, which form runs, the grid of every
-// launch, the rounds of the pointer-jumping sequences, and the workspace - ONE table of (name, bytes) in carve order that both the
-// reservation (vp_contours_ws_bytes, vp_contour_tree_ws_bytes) and the carve read.  Plain C++ - no HIP types, no kernels - so that all
+// launch, the rounds of the pointer-jumping sequences, and the workspace - ONE table of (name, bytes) in placement order that both the
+// size of the scratch region (vp_contours_ws_bytes, vp_contour_tree_ws_bytes) and its placement in vpk_find_contours read.  Plain C++ - no HIP types, no kernels - so that all
 // of it is checked without a GPU (tests/native/contours_plan_main.cpp against tests/golden/contours_plan.txt).  The layout of the
 // result header of the single-image entries (vp_api_label.hip) and the choice of the form (VP_CT_MANY) live here as well.
 #pragma once
@@ -59,7 +59,7 @@ static inline ct_hdr_layout ct_hdr(int mc, bool tree)
 }
 
 // ---- workspace ----------------------------------------------------------------------------------------------------------------
-// Carve order.  vp_ws_take aligns every array to 256 B, so a table costs the sum of ct_align(bytes) (+ slack for the first one).
+// Order in the scratch region.  Every array starts on a 256-B boundary, so a table costs the sum of ct_align(bytes) (+ slack).
 enum { CTW_HMAPS, CTW_HBASE, CTW_CNT8, CTW_HEAD_PIX, CTW_HRANK, CTW_HKEY, CTW_HEXT, CTW_NODE, CTW_NODE2, CTW_STARTS, CTW_SHEAD, CTW_AUX, CTW_PARTSUM,
        CTW_FLAGS, CTW_CSUM, CTW_BASE,
        CTW_TCOUNTS = CTW_BASE, CTW_TOFFSETS, CTW_THOLE, CTW_PAR, CTW_KEY, CTW_VAL, CTW_SKEY, CTW_SVAL, CTW_FC, CTW_NS, CTW_NW, CTW_TOUR, CTW_SORT, CTW_SPARE,

@@ -212,7 +212,7 @@ __global__ __launch_bounds__(256) void k_min_max_loc(const uint8_t* __restrict__
 }  // namespace
 
 // arguments as vp_distance_transform_refusal admitted them; d_bits (nullable): the source's bit plane, read instead of its bytes;
-// d_g: vp_dist_ws_bytes(w, h) of workspace; d_dst: rows of dstride bytes.  Two launches, enqueued.
+// d_g: vp_dist_g_bytes(w, h) of workspace; d_dst: rows of dstride bytes.  Two launches, enqueued.
 int vpk_distance_transform(vp_ctx* ctx, const uint8_t* d_src, size_t stride, int w, int h, const u64* d_bits, int metric, int depth, uint16_t* d_g, void* d_dst,
                            size_t dstride)
 {

@@ -43,7 +43,7 @@ static_assert((long long)DT_MAX_SIDE * DT_MAX_SIDE <= (1ll << 24), "min / max se
 static inline int vp_dist_staged(int h) { return h < DT_SWITCH_H; }
 static inline size_t vp_dist_lds_bytes(int h) { return vp_dist_staged(h) ? (size_t)h * DT_STRIP_COLS * 2 : 0; }
 static inline int vp_dist_g_pitch(int w) { return (w + 63) / 64 * 64; }                    // uint16 elements per row of g
-static inline size_t vp_dist_ws_bytes(int w, int h) { return (size_t)vp_dist_g_pitch(w) * h * 2; }
+static inline size_t vp_dist_g_bytes(int w, int h) { return (size_t)vp_dist_g_pitch(w) * h * 2; }
 static inline void vp_dist_grid(int w, int h, unsigned* gx, unsigned* gy)
 {
     const int cols = vp_dist_staged(h) ? DT_STRIP_COLS : DT_WIDE_COLS, rows = vp_dist_staged(h) ? DT_STRIP_ROWS : DT_WIDE_ROWS;

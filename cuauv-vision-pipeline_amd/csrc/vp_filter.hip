@@ -371,31 +371,29 @@ __global__ __launch_bounds__(256) void k_canny_out(const int32_t* __restrict__ l
     dst[i] = (l > 0 && seen[l]) ? 255 : 0;
 }
 
-size_t vp_canny_ws_bytes(int w, int h)
+void vp_canny_want(vp_ws_frame& W, int w, int h, vp_canny_ws* cw)
 {
     const size_t npx = (size_t)w * h, bitbytes = (size_t)h * vp_ww(w) * 8;
-    return vp_align(npx * 2) + vp_align(npx * 4) + 2 * vp_align(bitbytes) + vp_align(npx * 4) + vp_align(vp_ccl_nids(w, h) + 2) + vp_align(4) +
-           vp_ccl_ws_bytes(w, h, 1, 1) + 4096;
+    W.want(&cw->mag, npx * 2);
+    W.want(&cw->grad, npx * 4);
+    W.want(&cw->cand, bitbytes);
+    W.want(&cw->strong, bitbytes);
+    W.want(&cw->labels, npx * 4);
+    W.want(&cw->seen, vp_ccl_nids(w, h) + 2);          // labels are 1 .. number of components <= number of segments
+    W.want(&cw->nl, 4);
+    vp_ccl_ws_want(W, w, h, 1, 1, &cw->ccl);
 }
 
-int vpk_canny_u8(vp_ctx* ctx, const uint8_t* d_src, int w, int h, int cn, int low, int high, uint8_t* d_dst, const short2** grad_out)
+int vpk_canny_u8(vp_ctx* ctx, const uint8_t* d_src, int w, int h, int cn, int low, int high, uint8_t* d_dst, const vp_canny_ws& cw)
 {
     const size_t npx = (size_t)w * h;
     const int ww = vp_ww(w);
-    const size_t bitbytes = (size_t)h * ww * 8;
-    uint16_t* d_mag = (uint16_t*)vp_ws_take(ctx, npx * 2);
-    short2* d_grad = (short2*)vp_ws_take(ctx, npx * 4);
-    u64* d_cand = (u64*)vp_ws_take(ctx, bitbytes);
-    u64* d_strong = (u64*)vp_ws_take(ctx, bitbytes);
-    int32_t* d_labels = (int32_t*)vp_ws_take(ctx, npx * 4);
-    const size_t nseen = vp_ccl_nids(w, h) + 2;          // labels are 1 .. number of components <= number of segments
-    uint8_t* d_seen = (uint8_t*)vp_ws_take(ctx, nseen);
-    int32_t* d_nl = (int32_t*)vp_ws_take(ctx, 4);
-    vp_ccl_ws ws;
-    vp_ccl_ws_carve(ctx, w, h, 1, 1, &ws);
-    if (!d_mag || !d_grad || !d_cand || !d_strong || !d_labels || !d_seen || !d_nl || !vp_ccl_ws_ok(ws))
-        return vp_fail(ctx, VP_ERR_NOMEM, "canny workspace");
-    if (grad_out) *grad_out = d_grad;
+    const size_t nseen = vp_ccl_nids(w, h) + 2;
+    uint16_t* d_mag = cw.mag;
+    short2* d_grad = cw.grad;
+    u64 *d_cand = cw.cand, *d_strong = cw.strong;
+    int32_t *d_labels = cw.labels, *d_nl = cw.nl;
+    uint8_t* d_seen = cw.seen;
     hipStream_t s = ctx->stream;
     const dim3 grid((unsigned)((w + 255) / 256), (unsigned)h);
     {
@@ -404,7 +402,7 @@ int vpk_canny_u8(vp_ctx* ctx, const uint8_t* d_src, int w, int h, int cn, int lo
         hipLaunchKernelGGL(k_canny_nms, grid, dim3(256), 0, s, d_mag, d_grad, w, h, ww, low, high, d_cand, d_strong);
         VP_HIP(ctx, hipMemsetAsync(d_seen, 0, nseen, s));
     }
-    const int rc = vpk_ccl(ctx, d_cand, w, h, 1, VP_CCL_PIXEL, ws, d_labels, nullptr, nullptr, 1, d_nl);
+    const int rc = vpk_ccl(ctx, d_cand, w, h, 1, VP_CCL_PIXEL, cw.ccl, d_labels, nullptr, nullptr, 1, d_nl);
     if (rc != VP_OK) return rc;
     {
         vp_prof_scope ps(ctx, VPK_OTHER);

@@ -69,7 +69,8 @@ static inline const char* vp_geometry_refusal(long long n_contours, long long n_
 }
 
 static inline size_t vp_geometry_align(size_t n) { return (n + 255) / 256 * 256; }
-// device bytes of a pass that starts from host points (upload of points, first indices and counts; rows; hull block when wanted)
+// what vp_contour_geometry_plan reports: an upper bound of the device bytes of a pass that starts from host points (upload of points,
+// first indices and counts; rows; hull block when wanted).  The calls themselves declare their buffers on a vp_ws_frame.
 static inline size_t vp_geometry_ws_bytes(long long n_contours, long long n_points, int hulls, int upload)
 {
     size_t b = vp_geometry_align((size_t)n_contours * sizeof(vp_geom_raw)) + 4096;

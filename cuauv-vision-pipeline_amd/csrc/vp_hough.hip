@@ -277,23 +277,24 @@ int vp_hough_run(vp_ctx* ctx, const uint8_t* d_src, const uint8_t* h_src, size_t
         return VP_OK;
     }
     const size_t kout_cap = (size_t)n * std::min((size_t)max_lines, g.kcap);
-    const size_t bytes = vp_align((size_t)g.numangle * 8) + 2 * vp_align((size_t)n * 8) +
-                         vp_align(g.pcap * 4 * n) + vp_align(g.acc_cells * 4 * n) + 2 * vp_align(g.kcap * 8 * n) + vp_align(kout_cap * 8) +
-                         (h_src ? vp_align((size_t)w * h) : 0) + 4096;
-    rc = vp_ws_reserve(ctx, bytes);
+    vp_ws_frame W;
+    float *d_tab, *d_out;
+    u32 *d_cnt, *d_kout, *d_pts;
+    int* d_acc;
+    u64 *d_k0, *d_k1;
+    uint8_t* d_img;
+    W.want(&d_tab, (size_t)g.numangle * 8);
+    W.want(&d_cnt, (size_t)n * 8);                  // points, then peaks, per frame
+    W.want(&d_kout, (size_t)n * 8);                 // lines kept, then their offset in the output, per frame
+    W.want(&d_pts, g.pcap * 4 * n);
+    W.want(&d_acc, g.acc_cells * 4 * n);
+    W.want(&d_k0, g.kcap * 8 * n);
+    W.want(&d_k1, g.kcap * 8 * n);
+    W.want(&d_out, std::max(kout_cap, (size_t)1) * 8);
+    if (h_src) W.want(&d_img, (size_t)w * h);
+    rc = vp_ws_commit(ctx, W, "hough workspace");
     if (rc != VP_OK) return rc;
-    float* d_tab = (float*)vp_ws_take(ctx, (size_t)g.numangle * 8);
-    u32* d_cnt = (u32*)vp_ws_take(ctx, (size_t)n * 8);                  // points, then peaks, per frame
-    u32* d_kout = (u32*)vp_ws_take(ctx, (size_t)n * 8);                 // lines kept, then their offset in the output, per frame
-    u32* d_pts = (u32*)vp_ws_take(ctx, g.pcap * 4 * n);
-    int* d_acc = (int*)vp_ws_take(ctx, g.acc_cells * 4 * n);
-    u64* d_k0 = (u64*)vp_ws_take(ctx, g.kcap * 8 * n);
-    u64* d_k1 = (u64*)vp_ws_take(ctx, g.kcap * 8 * n);
-    float* d_out = (float*)vp_ws_take(ctx, std::max(kout_cap, (size_t)1) * 8);
-    if (!d_tab || !d_cnt || !d_kout || !d_pts || !d_acc || !d_k0 || !d_k1 || !d_out) return vp_fail(ctx, VP_ERR_NOMEM, "hough workspace");
     if (h_src) {
-        uint8_t* d_img = (uint8_t*)vp_ws_take(ctx, (size_t)w * h);
-        if (!d_img) return vp_fail(ctx, VP_ERR_NOMEM, "hough workspace");
         VP_HIP(ctx, hipMemcpyAsync(d_img, h_src, (size_t)w * h, hipMemcpyHostToDevice, ctx->stream));
         d_src = d_img;
     }

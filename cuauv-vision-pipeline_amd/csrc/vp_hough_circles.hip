@@ -329,39 +329,43 @@ int vp_hough_circles_run(vp_ctx* ctx, const uint8_t* d_src, const uint8_t* h_src
     const bool lds = ctx->opt.v[VP_OPT_HOUGH_CIRCLES_LDS] && (size_t)nbins * 4 <= HC_LDS_MAX;
     const size_t ocap = std::min(kcap, (size_t)max_circles);
     const bool packed = h_src || stride == (size_t)w;
-    const size_t bytes = (packed && !h_src ? 0 : vp_align(npx)) + vp_align(npx) + vp_canny_ws_bytes(w, h) + vp_align(npx * sizeof(hc_ray)) +
-                         vp_align(npx * 8) + vp_align(npx * 4) + vp_align(acells * 4) + 2 * vp_align(kcap * 8) + vp_align(16) +
-                         vp_align(kcap * 16) * 2 + vp_align(kcap * 8) + vp_align(4 + ocap * 12) + 4096;
-    int rc = vp_ws_reserve(ctx, bytes);
+    vp_ws_frame W;
+    uint8_t *d_img = nullptr, *d_edges;
+    vp_canny_ws cw;
+    hc_ray* d_rays;
+    int *d_rend, *d_acc;
+    u32 *d_pxy, *d_cnt;
+    u64 *d_k0, *d_k1;
+    float4 *d_cand, *d_sorted;
+    float2* d_kept;
+    float* d_out;
+    if (!packed || h_src) W.want(&d_img, npx);
+    W.want(&d_edges, npx);
+    vp_canny_want(W, w, h, &cw);
+    W.want(&d_rays, npx * sizeof(hc_ray));
+    W.want(&d_rend, npx * 8);
+    W.want(&d_pxy, npx * 4);
+    W.want(&d_acc, acells * 4);
+    W.want(&d_k0, kcap * 8);
+    W.want(&d_k1, kcap * 8);
+    W.want(&d_cnt, 16);                      // points, centres, supported circles
+    W.want(&d_cand, kcap * 16);
+    W.want(&d_sorted, kcap * 16);
+    W.want(&d_kept, kcap * 8);
+    W.want(&d_out, 4 + ocap * 12);
+    int rc = vp_ws_commit(ctx, W, "hough circles workspace");
     if (rc != VP_OK) return rc;
     const uint8_t* src = d_src;
-    if (!packed || h_src) {
-        uint8_t* d_img = (uint8_t*)vp_ws_take(ctx, npx);
-        if (!d_img) return vp_fail(ctx, VP_ERR_NOMEM, "hough circles workspace");
+    if (d_img) {
         if (h_src) VP_HIP(ctx, hipMemcpyAsync(d_img, h_src, npx, hipMemcpyHostToDevice, ctx->stream));
         else VP_HIP(ctx, hipMemcpy2DAsync(d_img, (size_t)w, d_src, stride, (size_t)w, h, hipMemcpyDeviceToDevice, ctx->stream));
         src = d_img;
     }
-    uint8_t* d_edges = (uint8_t*)vp_ws_take(ctx, npx);
-    if (!d_edges) return vp_fail(ctx, VP_ERR_NOMEM, "hough circles workspace");
-    const short2* d_grad = nullptr;
     int lo_t = std::max(1, canny_thresh / 2), hi_t = canny_thresh;
     if (lo_t > hi_t) std::swap(lo_t, hi_t);                      // Canny orders its thresholds (param1 < 1.5)
-    rc = vpk_canny_u8(ctx, src, w, h, 1, lo_t, hi_t, d_edges, &d_grad);
+    rc = vpk_canny_u8(ctx, src, w, h, 1, lo_t, hi_t, d_edges, cw);
     if (rc != VP_OK) return rc;
-    hc_ray* d_rays = (hc_ray*)vp_ws_take(ctx, npx * sizeof(hc_ray));
-    int* d_rend = (int*)vp_ws_take(ctx, npx * 8);
-    u32* d_pxy = (u32*)vp_ws_take(ctx, npx * 4);
-    int* d_acc = (int*)vp_ws_take(ctx, acells * 4);
-    u64* d_k0 = (u64*)vp_ws_take(ctx, kcap * 8);
-    u64* d_k1 = (u64*)vp_ws_take(ctx, kcap * 8);
-    u32* d_cnt = (u32*)vp_ws_take(ctx, 16);                      // points, centres, supported circles
-    float4* d_cand = (float4*)vp_ws_take(ctx, kcap * 16);
-    float4* d_sorted = (float4*)vp_ws_take(ctx, kcap * 16);
-    float2* d_kept = (float2*)vp_ws_take(ctx, kcap * 8);
-    float* d_out = (float*)vp_ws_take(ctx, 4 + ocap * 12);
-    if (!d_grad || !d_rays || !d_rend || !d_pxy || !d_acc || !d_k0 || !d_k1 || !d_cnt || !d_cand || !d_sorted || !d_kept || !d_out)
-        return vp_fail(ctx, VP_ERR_NOMEM, "hough circles workspace");
+    const short2* d_grad = cw.grad;
     hipStream_t s = ctx->stream;
     VP_HIP(ctx, hipMemsetAsync(d_cnt, 0, 16, s));
     {

@@ -7,6 +7,7 @@
 #include "vp_options.h"
 #include "vp_morph_plan.h"
 #include "vp_contours_plan.h"
+#include "vp_ws_frame.h"
 
 typedef unsigned long long u64;
 typedef unsigned int u32;
@@ -42,9 +43,8 @@ struct vp_runtime {           // the runtime's own (vp_api.hip); vp_ctx derives 
     void* d_tables;
     void* d_labinv;   // Lab -> BGR tables (tab.abxz / yf / invg)
     vp_tables tab;
-    uint8_t* ws;      // grow-only device workspace, carved per call
+    uint8_t* ws;      // grow-only device workspace; each call lays its buffers out in a vp_ws_frame (vp_ws_commit)
     size_t ws_cap;
-    size_t ws_off;
     uint8_t* hstage;  // grow-only pinned host staging for small results (contour lists)
     size_t hstage_cap;
     // small host -> device hand-overs that must not wait (overlay vertices): a ring of pinned chunks, each free again once the work
@@ -159,8 +159,8 @@ void vp_adaptive_teardown(vp_ctx* ctx);                    // vp_adaptive.hip
 void vp_features_teardown(vp_ctx* ctx);                    // vp_api_features.hip
 
 // ---- workspace ---------------------------------------------------------------------------
-int vp_ws_reserve(vp_ctx* ctx, size_t bytes);               // may reallocate (synchronises)
-void* vp_ws_take(vp_ctx* ctx, size_t bytes);                // 256-B aligned carve; NULL if exhausted
+// reserves W.bytes() and assigns every pointer W recorded; may reallocate (synchronises), so nothing of the call may be in flight yet
+int vp_ws_commit(vp_ctx* ctx, const vp_ws_frame& W, const char* who);
 void* vp_hstage(vp_ctx* ctx, size_t bytes);                 // pinned host staging of at least `bytes` (NULL: out of memory)
 static inline size_t vp_align(size_t n, size_t a = 256) { return (n + a - 1) / a * a; }
 int vp_fail(vp_ctx* ctx, int code, const char* what, hipError_t e = hipSuccess);
@@ -188,16 +188,18 @@ int vpk_inrange_f32(vp_ctx* ctx, const float* d_src, size_t stride_bytes, int w,
                     uint8_t* d_dst);
 int vpk_kth_f32(vp_ctx* ctx, const float* d_src, size_t n, size_t k, u32* d_hist, float* out);
 // white balance (vp_whitebal.hip): kernel_size VP_WB_GLOBAL_MEAN or an odd k; d_mean (nullable) receives the two global means
-int vpk_white_balance(vp_ctx* ctx, const uint8_t* d_src, size_t stride, int w, int h, int kernel_size, uint8_t* d_dst, float* d_mean);
-size_t vp_white_balance_ws_bytes(int w, int h, int kernel_size);
+struct vp_whitebal_ws { int2* sums; uint2 *P, *Q, *T; };   // the global form's chunk sums / the box form's prefix planes
+void vp_white_balance_want(vp_ws_frame& W, int w, int h, int kernel_size, vp_whitebal_ws* bw);
+int vpk_white_balance(vp_ctx* ctx, const uint8_t* d_src, size_t stride, int w, int h, int kernel_size, uint8_t* d_dst, float* d_mean, const vp_whitebal_ws& bw);
 int vpk_bgr2lab_f32(vp_ctx* ctx, const float* d_src, size_t npx, float* d_dst);
 int vpk_color_distance(vp_ctx* ctx, const uint8_t* p0, const uint8_t* p1, const uint8_t* p2, size_t npx,
                        const float* color, const float* wts, int skipmask, float* d2, uint8_t* sq);
 
 // ---- colour balance (vp_balance.hip) ----------------------------------------------------------
 int vpk_hsv2bgr(vp_ctx* ctx, const uint8_t* d_src, size_t npx, uint8_t* d_dst);
-size_t vp_balance_ws_bytes(int n, int tiles);
-int vpk_color_balance(vp_ctx* ctx, const uint8_t* d_src, uint8_t* d_dst, int w, int h, int n, int flags, int hblocks, int vblocks);
+struct vp_balance_ws { u32 *hist, *svhist; uint8_t *lut, *svlut; void *plans, *hst; double* powtab; };
+void vp_balance_want(vp_ws_frame& W, int n, int tiles, int flags, vp_balance_ws* bw);
+int vpk_color_balance(vp_ctx* ctx, const uint8_t* d_src, uint8_t* d_dst, int w, int h, int n, int flags, int hblocks, int vblocks, const vp_balance_ws& bw);
 
 // ---- detector pre / post-processing (vp_yolo.hip) ------------------------------------------------
 int vpk_letterbox(vp_ctx* ctx, const uint8_t* d_src, int sw, int sh, int dw, int dh, int pad, float* d_dst, float* geom_out);
@@ -205,8 +207,9 @@ int vpk_letterbox(vp_ctx* ctx, const uint8_t* d_src, int sw, int sh, int dw, int
 int vpk_resize_u8(vp_ctx* ctx, const uint8_t* d_src, int sw, int sh, int cn, int dw, int dh, double inv_sx, double inv_sy, uint8_t* d_dst, size_t sstride = 0);
 int vpk_warp_affine_u8(vp_ctx* ctx, const uint8_t* d_src, int sw, int sh, int cn, const double* M23, int inverse_map, int border,
                        const uint8_t* cval, uint8_t* d_dst, int dw, int dh, size_t sstride = 0);
-size_t vp_nms_ws_bytes(int n);
-int vpk_nms(vp_ctx* ctx, const float* d_boxes, const float* d_scores, int n, float thr, int rotated, int max_keep, int* d_keep, int* d_nkeep);
+struct vp_nms_ws { int* order; unsigned long long* mask; unsigned char* alive; };
+void vp_nms_want(vp_ws_frame& W, int n, vp_nms_ws* nw);
+int vpk_nms(vp_ctx* ctx, const float* d_boxes, const float* d_scores, int n, float thr, int rotated, int max_keep, int* d_keep, int* d_nkeep, const vp_nms_ws& nw);
 
 // ---- gathers (vp_remap.hip; the tile: vp_remap_plan.h) ------------------------------------------------
 // cv2.remap from the fixed form (d_xy: int16 x,y pairs; d_frac: fraction indices, NULL for nearest) or from float maps (d_mapy NULL:
@@ -229,10 +232,12 @@ int vpk_otsu_scan(vp_ctx* ctx, const u32* d_hist, size_t n, double* d_thresh, in
 int vpk_hist_u8(vp_ctx* ctx, const uint8_t* d_src, size_t n, u32* d_hist);   // d_hist: 256 counters
 int vpk_adaptive_threshold_mean(vp_ctx* ctx, const uint8_t* d_src, int w, int h, int imax, int idelta, int inv, int block, uint16_t* d_tmp, uint8_t* d_dst,
                                 size_t sstride = 0);   // sstride: bytes between source rows (0: packed)
-size_t vp_canny_ws_bytes(int w, int h);
-// grad_out (nullable): receives the workspace plane of the winning channel's Sobel (dx, dy), w * h short2, valid until the workspace is
-// carved anew (HoughCircles reads it for cn = 1)
-int vpk_canny_u8(vp_ctx* ctx, const uint8_t* d_src, int w, int h, int cn, int low, int high, uint8_t* d_dst, const short2** grad_out = nullptr);
+// Canny's scratch, declared on the caller's frame by vp_canny_want.  grad: the winning channel's Sobel (dx, dy), w * h short2, valid
+// until the next call commits a frame (HoughCircles reads it for cn = 1)
+struct vp_ccl_ws;
+struct vp_canny_ws;
+void vp_canny_want(vp_ws_frame& W, int w, int h, vp_canny_ws* cw);
+int vpk_canny_u8(vp_ctx* ctx, const uint8_t* d_src, int w, int h, int cn, int low, int high, uint8_t* d_dst, const vp_canny_ws& cw);
 // ---- Hough lines (vp_hough.hip) ----------------------------------------------------------------------
 // n frames of w x h u8 at d_src (row stride, frame stride; or one packed host image at h_src, staged in the workspace): lines of frame f
 // -> lines + f * max_lines * 2 (host), true counts -> n_lines; synchronises.  Checks beyond rho / theta / min_theta / max_theta are the caller's.
@@ -250,7 +255,7 @@ void vp_gaussian_taps(int n, double sigma, uint16_t* out);   // n odd, <= 511
 void vp_gaussian_kernel_f64(int n, double sigma, double* k);  // the double kernel vp_gaussian_taps rounds: n odd, 3..511
 // Gaussian adaptive threshold (vp_adaptive.hip): n frames (src row stride, frame stride) -> packed (n, h, w) dst; d_tmp: n * w * h u64
 #define VP_AGAUSS_MAX_BLOCK 511
-size_t vp_agauss_ws_bytes(int w, int h, int n);
+size_t vp_agauss_tmp_bytes(int w, int h, int n);
 int vpk_adaptive_threshold_gaussian(vp_ctx* ctx, const uint8_t* d_src, size_t stride, size_t fstride, int n, int w, int h, int imax, int idelta,
                                     int inv, int block, uint64_t* d_tmp, uint8_t* d_dst);
 int vpk_gaussian_blur(vp_ctx* ctx, const uint8_t* d_src, int w, int h, int cn, const uint16_t* d_taps, int kw, int kh, uint16_t* d_tmp, uint8_t* d_dst,
@@ -273,10 +278,10 @@ struct vp_deriv_plan;
 int vpk_deriv(vp_ctx* ctx, const uint8_t* d_src, size_t sstride, int w, int h, int cn, const vp_deriv_plan& P, void* d_dst, void* d_dst2);
 
 // ---- box filter, pyramid steps, integral (vp_box.hip, vp_pyr.hip, vp_integral.hip; the plan: vp_box_plan.h) ---------------------------
-// Arguments as the plan header's checks accepted them; sstride: bytes between source rows; destinations packed.  d_mid: vp_box_ws_bytes
+// Arguments as the plan header's checks accepted them; sstride: bytes between source rows; destinations packed.  d_mid: vp_box_mid_bytes
 // of workspace for the two-pass box path (0 for the one-pass path).
 struct vp_box_plan;
-size_t vp_box_ws_bytes(int w, int h, int cn, const vp_box_plan& P);
+size_t vp_box_mid_bytes(int w, int h, int cn, const vp_box_plan& P);
 int vpk_box_filter(vp_ctx* ctx, const uint8_t* d_src, size_t sstride, int w, int h, int cn, const vp_box_plan& P, uint16_t* d_mid, void* d_dst);
 int vpk_pyr_down(vp_ctx* ctx, const uint8_t* d_src, size_t sstride, int w, int h, int cn, int border, uint8_t* d_dst);
 int vpk_pyr_up(vp_ctx* ctx, const uint8_t* d_src, size_t sstride, int w, int h, int cn, uint8_t* d_dst);
@@ -312,7 +317,7 @@ int vpk_corner_candidates(vp_ctx* ctx, const float* d_resp, int w, int h, const 
 
 // ---- distance transform and min / max search (vp_dist.hip; the plan: vp_dist_plan.h) --------------------------
 // cv2.distanceTransform of sizes vp_distance_transform_refusal admitted: zero pixels are the sources; d_bits (nullable) is the source's
-// bit plane, read instead of its bytes; d_g: vp_dist_ws_bytes(w, h) of workspace; d_dst: rows of dstride bytes, float32 or uint8 by
+// bit plane, read instead of its bytes; d_g: vp_dist_g_bytes(w, h) of workspace; d_dst: rows of dstride bytes, float32 or uint8 by
 // depth.  Two launches, enqueued.  vpk_min_max_loc: d_out receives the two keys vp_min_max_loc_decode reads; d_mask (rows of mstride
 // bytes) or d_mbits (its bit plane) admit pixels, both nullable; one launch behind the zeroing of d_out, enqueued.
 int vpk_distance_transform(vp_ctx* ctx, const uint8_t* d_src, size_t stride, int w, int h, const unsigned long long* d_bits, int metric, int depth, uint16_t* d_g,
@@ -492,12 +497,11 @@ struct vp_ccl_ws {           // per-batch scratch, all device pointers
     u32* c3_barr;            // [n][strips + 1]        arrivals at every strip boundary
     void* c3_tot;            // [n][strips]            per strip: foreground sums and the box of its zero pixels (for the background row)
 };
-bool vp_ccl_ws_ok(const vp_ccl_ws& ws);
 size_t vp_ccl_nids(int w, int h);   // multiple of 32
-size_t vp_ccl_ws_bytes(int w, int h, int n, int max_labels);
-void vp_ccl_ws_carve(vp_ctx* ctx, int w, int h, int n, int max_labels, vp_ccl_ws* out);
-// scratch of a contour pass over n frames / of the hierarchy pass of one image: the totals of the workspace table of vp_contours_plan.h,
-// which vpk_find_contours carves entry by entry
+struct vp_canny_ws { uint16_t* mag; short2* grad; u64 *cand, *strong; int32_t* labels; uint8_t* seen; int32_t* nl; vp_ccl_ws ccl; };
+void vp_ccl_ws_want(vp_ws_frame& W, int w, int h, int n, int max_labels, vp_ccl_ws* out);   // the labelling scratch of n frames, declared on the caller's frame
+// scratch of a contour pass over n frames / of the hierarchy pass of one image: the totals of the workspace table of vp_contours_plan.h.
+// The caller wants one region of that size (both sums with the hierarchy pass) and hands it to vpk_find_contours as (d_ws, ws_bytes)
 size_t vp_contours_ws_bytes(int w, int h, int n, int max_contours);
 size_t vp_contour_tree_ws_bytes(int max_contours);
 int vpk_contour_features(vp_ctx* ctx, const int32_t* d_info, const int32_t* d_counts, const int32_t* d_offsets, const int32_t* d_points, int n,
@@ -513,8 +517,8 @@ uint32_t vp_ct_batch_hint(vp_ctx* ctx);      // largest head count the last batc
 // d_hier (n == 1 only, [max_contours][4]): RETR_CCOMP / RETR_TREE, which need it - the hierarchy rows in cv2's order (the contour arrays
 // stay in device order, reversed by the caller); the modes 0 / 1 take it as NULL.  host->hier: the same rows in the pinned buffer.
 struct vp_contour_mirror { int32_t* info; int32_t* counts; int32_t* offsets; uint8_t* is_hole; int32_t* points; long long points_cap; int32_t* hier; };
-int vpk_find_contours(vp_ctx* ctx, const u64* d_bits, int w, int h, int n, int mode, int method, int32_t* d_counts, uint8_t* d_is_hole,
-                      int32_t* d_offsets, int32_t* d_points, int max_contours, long long max_points, int32_t* d_info, bool many_heads = false,
+int vpk_find_contours(vp_ctx* ctx, uint8_t* d_ws, size_t ws_bytes, const u64* d_bits, int w, int h, int n, int mode, int method, int32_t* d_counts,
+                      uint8_t* d_is_hole, int32_t* d_offsets, int32_t* d_points, int max_contours, long long max_points, int32_t* d_info, bool many_heads = false,
                       uint32_t* d_nheads_out = nullptr, const vp_contour_mirror* host = nullptr, bool defer_big = false, int32_t* d_hier = nullptr);
 int vpk_ccl(vp_ctx* ctx, const u64* d_bits, int w, int h, int n, int numbering, const vp_ccl_ws& ws, int32_t* d_labels,
             int32_t* d_stats, double* d_centroids, int max_labels, int32_t* d_nlabels);

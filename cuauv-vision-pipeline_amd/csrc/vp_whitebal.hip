@@ -237,15 +237,17 @@ __global__ __launch_bounds__(256) void k_wbb_apply(const uint8_t* __restrict__ s
 static size_t wb_chunks(int w, int h) { return ((size_t)w * h + WB_CHUNK - 1) / WB_CHUNK; }
 static size_t wb_tiles(int h) { return ((size_t)h + WB_TILE - 1) / WB_TILE; }
 
-size_t vp_white_balance_ws_bytes(int w, int h, int kernel_size)
+void vp_white_balance_want(vp_ws_frame& W, int w, int h, int kernel_size, vp_whitebal_ws* bw)
 {
     const size_t npx = (size_t)w * h;
-    if (kernel_size == VP_WB_GLOBAL_MEAN) return vp_align(wb_chunks(w, h) * sizeof(int2)) + 256;
-    return 2 * vp_align(npx * sizeof(uint2)) + vp_align(wb_tiles(h) * w * sizeof(uint2)) + 256;
+    if (kernel_size == VP_WB_GLOBAL_MEAN) { W.want(&bw->sums, wb_chunks(w, h) * sizeof(int2)); return; }
+    W.want(&bw->P, npx * sizeof(uint2));
+    W.want(&bw->Q, npx * sizeof(uint2));
+    W.want(&bw->T, wb_tiles(h) * w * sizeof(uint2));
 }
 
-// d_mean: two floats of device memory (the global means; untouched by the box form).  Workspace: vp_white_balance_ws_bytes, carved here.
-int vpk_white_balance(vp_ctx* ctx, const uint8_t* d_src, size_t stride, int w, int h, int kernel_size, uint8_t* d_dst, float* d_mean)
+// d_mean: two floats of device memory (the global means; untouched by the box form)
+int vpk_white_balance(vp_ctx* ctx, const uint8_t* d_src, size_t stride, int w, int h, int kernel_size, uint8_t* d_dst, float* d_mean, const vp_whitebal_ws& bw)
 {
     const size_t npx = (size_t)w * h;
     if (npx >= (1ull << 31)) return vp_fail(ctx, VP_ERR_UNSUPPORTED, "white balance: image above 2^31 pixels");
@@ -253,18 +255,14 @@ int vpk_white_balance(vp_ctx* ctx, const uint8_t* d_src, size_t stride, int w, i
     vp_prof_scope prof(ctx, VPK_COLOR);
     if (kernel_size == VP_WB_GLOBAL_MEAN) {
         const size_t nchunks = wb_chunks(w, h);
-        int2* sums = (int2*)vp_ws_take(ctx, nchunks * sizeof(int2));
-        if (!sums) return vp_fail(ctx, VP_ERR_NOMEM, "workspace exhausted: white balance sums");
+        int2* sums = bw.sums;
         hipLaunchKernelGGL(k_wb_chunk_sums, dim3((unsigned)nchunks), dim3(256), 0, ctx->stream, d_src, stride, (u32)w, (u32)npx, ctx->tab, sums);
         hipLaunchKernelGGL(k_wb_fold, dim3(1), dim3(64), 0, ctx->stream, (const int2*)sums, (u32)nchunks, (u32)npx, d_mean);
         hipLaunchKernelGGL(k_wb_apply, dim3(blocks), dim3(256), 0, ctx->stream, d_src, stride, (u32)w, (u32)npx, ctx->tab, (const float*)d_mean, d_dst);
     } else {
         const int r = kernel_size / 2;
         const size_t ntiles = wb_tiles(h);
-        uint2* P = (uint2*)vp_ws_take(ctx, npx * sizeof(uint2));
-        uint2* Q = (uint2*)vp_ws_take(ctx, npx * sizeof(uint2));
-        uint2* T = (uint2*)vp_ws_take(ctx, ntiles * w * sizeof(uint2));
-        if (!P || !Q || !T) return vp_fail(ctx, VP_ERR_NOMEM, "workspace exhausted: white balance box sums");
+        uint2 *P = bw.P, *Q = bw.Q, *T = bw.T;
         const double inv_area = 1.0 / (double)(kernel_size * kernel_size);
         const unsigned cols = (unsigned)((w + 255) / 256);
         hipLaunchKernelGGL(k_wbb_row_prefix, dim3((unsigned)h), dim3(256), 0, ctx->stream, d_src, stride, w, ctx->tab, P);

@@ -394,19 +394,24 @@ __global__ __launch_bounds__(64) void k_nms_compact(const unsigned char* __restr
     if (threadIdx.x == 0) *n_keep = min(kept, max_keep);
 }
 
-size_t vp_nms_ws_bytes(int n) { const size_t words = (size_t)(n + 63) / 64; return vp_align((size_t)n * 4) + vp_align((size_t)n * words * 8) + vp_align((size_t)n) + 1024; }
+void vp_nms_want(vp_ws_frame& W, int n, vp_nms_ws* nw)
+{
+    if (n <= 0) return;                      // vpk_nms touches none of them
+    W.want(&nw->order, (size_t)n * 4);
+    W.want(&nw->mask, (size_t)n * ((n + 63) / 64) * 8);
+    W.want(&nw->alive, (size_t)n);
+}
 
 // d_boxes: (n,4) xyxy or (n,5) xywhr; d_keep: max_keep ints; d_nkeep: 1 int.  rotated = 0: greedy IoU NMS (suppress IoU > thr);
 // rotated = 1: probabilistic IoU, a box is dropped when some higher-scored box overlaps it by >= thr
-int vpk_nms(vp_ctx* ctx, const float* d_boxes, const float* d_scores, int n, float thr, int rotated, int max_keep, int* d_keep, int* d_nkeep)
+int vpk_nms(vp_ctx* ctx, const float* d_boxes, const float* d_scores, int n, float thr, int rotated, int max_keep, int* d_keep, int* d_nkeep, const vp_nms_ws& nw)
 {
     if (n <= 0) { VP_HIP(ctx, hipMemsetAsync(d_nkeep, 0, 4, ctx->stream)); return VP_OK; }
     if (n > 16384) return vp_fail(ctx, VP_ERR_UNSUPPORTED, "nms: more than 16384 candidates");
     const int words = (n + 63) / 64;
-    int* order = (int*)vp_ws_take(ctx, (size_t)n * 4);
-    unsigned long long* mask = (unsigned long long*)vp_ws_take(ctx, (size_t)n * words * 8);
-    unsigned char* alive = (unsigned char*)vp_ws_take(ctx, (size_t)n);
-    if (!order || !mask || !alive) return vp_fail(ctx, VP_ERR_NOMEM, "nms workspace");
+    int* order = nw.order;
+    unsigned long long* mask = nw.mask;
+    unsigned char* alive = nw.alive;
     hipStream_t s = ctx->stream;
     vp_prof_scope ps(ctx, VPK_OTHER);
     hipLaunchKernelGGL(k_nms_rank, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, d_scores, n, order);

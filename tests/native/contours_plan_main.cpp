@@ -27,7 +27,7 @@ static void check(const ct_case& c, const ct_plan& P, size_t ws, size_t tree_ws)
         CHECK(c, (size_t)P.nb * 256 > (size_t)c.mc && (size_t)P.tb * 256 >= 2 * (size_t)c.mc + 2);
         CHECK(c, P.key_bits >= 1 && P.key_bits <= 31 && (c.mc >= (1 << 30) || ((unsigned)c.mc + 1u) >> P.key_bits == 0));
     }
-    // the carve as vp_ws_take does it, from any 256-aligned start, ends inside the reservation; no array is empty
+    // the placement as vpk_find_contours does it, from any 256-aligned start, ends inside the region its caller wants; no array is empty
     CHECK(c, P.nws == (P.tree ? CTW_ALL : CTW_BASE));
     for (size_t start : {(size_t)0, (size_t)256, (size_t)1 << 20}) {
         size_t off = start;
