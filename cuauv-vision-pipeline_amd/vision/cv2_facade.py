@@ -870,6 +870,35 @@ def StereoBM_create(numDisparities=0, blockSize=21):
 StereoBM.create = staticmethod(StereoBM_create)
 
 
+def filterSpeckles(img, newVal, maxSpeckleSize, maxDiff, buf=None):
+    """cv2.filterSpeckles on a 2-D int16 disparity image, in place, on the GPU (libvp vp_filter_speckles_*; the rule is
+    tests/speckle_restate.py's): regions of at most maxSpeckleSize pixels become newVal.  Returns (img, buf) as
+    cv2 does; buf is not used.  A DeviceMat that lives in HBM is filtered there."""
+    from vision.devmat import DeviceMat
+    from vision.utils import stereo as _stereo
+    if not isinstance(img, (np.ndarray, DeviceMat)) or img.dtype != np.int16 or img.ndim != 2 or img.size == 0:
+        raise error("filterSpeckles: only non-empty 2-D int16 images are on the accelerated path")
+    try:
+        params = _stereo._speckle_args(img, maxSpeckleSize, maxDiff, newVal)
+        ctx = _vp.default_context()
+        if isinstance(img, DeviceMat) and img._host is None and img.device_valid_for(ctx):
+            img.dev_ptr                                  # a pending result is computed first
+            img._before_write()
+            _stereo._speckles_dev(ctx, img, params, out=img)
+            return img, buf
+        host = img.host(writable=True, escape=False) if isinstance(img, DeviceMat) else img
+        if not host.flags.writeable:
+            raise error("filterSpeckles: the image is read-only")
+        packed = host if host.flags.c_contiguous else np.ascontiguousarray(host)
+        h, w = packed.shape
+        _vp.check(_vp.lib().vp_filter_speckles_i16(ctx.handle, packed.ctypes.data, w, h, *params, packed.ctypes.data), ctx.handle)
+        if packed is not host:
+            host[...] = packed
+        return img, buf
+    except (TypeError, ValueError, _vp.VpError) as e:
+        raise error(f"filterSpeckles: {e}") from None
+
+
 # ---- derivative filters (libvp vp_deriv.hip) ------------------------------------------------------------------------------------------
 def _deriv_call(name, fn, src, ddepth, scale, delta, borderType, *args):
     """What cv2 rejects, and the two restrictions of this path: scale = 1 and delta = 0 only."""

@@ -5,6 +5,11 @@
 texture and uniqueness tests, parabola subpixel - as tests/stereo_restate.py states it, byte for byte; it has not met a real OpenCV.
 The pair must be rectified (vision.utils.transform.undistorter / RemapTable apply a calibration's maps): a point of `left` at column x
 lies on the same row of `right` at column x - D.
+
+After the matcher (libvp vp_speckle.hip): `filter_speckles` removes the small islands of wrong answers by the rule
+of cv2.filterSpeckles, as tests/speckle_restate.py states it, byte for byte (it has not met a real OpenCV either); `normals_from_depth`
+makes the reference's fourth plane, `normal` (zed_sync.py:114,132-137), by this library's own definition, bit for bit as
+tests/normals_restate.py states it; `stereo_planes` chains all four steps in HBM.
 """
 import ctypes as C
 
@@ -140,3 +145,118 @@ def stereo_depth(left, right, focal_px: float, baseline_m: float, **matcher):
     ctx = _vp.default_context()
     depth = _depth_dev(ctx, _disparity_dev(ctx, left, right, params), focal_px, baseline_m)
     return depth if on_device else depth.host()
+
+
+def _int_in(name, v, lo, hi):
+    if isinstance(v, bool) or not isinstance(v, (int, np.integer)):
+        raise TypeError(f"{name} must be an integer")
+    if not lo <= v <= hi:
+        raise ValueError(f"{name} must lie in {lo}..{hi}")
+    return int(v)
+
+
+def _speckle_args(disp16, max_speckle_size, max_diff, new_val):
+    """everything libvp refuses of a filter_speckles call, refused here before a device is needed"""
+    if not isinstance(disp16, (np.ndarray, DeviceMat)) or disp16.dtype != np.int16 or len(disp16.shape) != 2 or 0 in disp16.shape:
+        raise TypeError("expected a non-empty int16 (h, w) disparity image")
+    if max(disp16.shape) > MAX_SIDE:
+        raise ValueError("the disparity image must be at most 4096 x 4096")
+    h, w = disp16.shape
+    new_val = invalid_disparity(0) if new_val is None else new_val
+    return (_int_in("new_val", new_val, -32768, 32767), _int_in("max_speckle_size", max_speckle_size, 0, w * h), _int_in("max_diff", max_diff, 0, 65535))
+
+
+def _speckles_dev(ctx, disp, params, out=None):
+    """an int16 DeviceMat -> the filtered DeviceMat, enqueued; out: the image to write (the source itself: in place)"""
+    h, w = disp.shape
+    out = DeviceMat(ctx, (h, w), np.int16) if out is None else out
+    _vp.check(_vp.lib().vp_filter_speckles_dev(ctx.handle, disp.dev_ptr, 2 * w, w, h, *params, out.dev_ptr, 2 * w), ctx.handle)
+    return out
+
+
+def filter_speckles(disp16, max_speckle_size: int, max_diff: int, new_val=None):
+    """cv2.filterSpeckles as a function that returns a new image: every connected region of `disp16` (int16, 16 times the disparity, as
+    `disparity` returns it) of at most max_speckle_size pixels becomes new_val.  Two pixels are linked when they are 4-neighbours,
+    neither equals new_val and they differ by at most max_diff (so max_diff = 16 * speckleRange); links chain.  new_val defaults to
+    `invalid_disparity(0)`.  max_speckle_size in 0..w*h (0 copies), max_diff in 0..65535.  numpy in gives numpy out, a DeviceMat a
+    DeviceMat that stays in HBM."""
+    params = _speckle_args(disp16, max_speckle_size, max_diff, new_val)
+    ctx = _vp.default_context()
+    if isinstance(disp16, DeviceMat):
+        disp16.refresh_device(ctx)
+        return _speckles_dev(ctx, disp16, params)
+    disp16 = np.ascontiguousarray(disp16)
+    h, w = disp16.shape
+    out = np.empty((h, w), np.int16)
+    _vp.check(_vp.lib().vp_filter_speckles_i16(ctx.handle, disp16.ctypes.data, w, h, *params, out.ctypes.data), ctx.handle)
+    return out
+
+
+def _normals_args(depth, focal_px, cx, cy, max_jump_m, encode):
+    if not isinstance(depth, (np.ndarray, DeviceMat)) or depth.dtype != np.float32 or len(depth.shape) != 2 or 0 in depth.shape:
+        raise TypeError("expected a non-empty float32 (h, w) depth image")
+    if max(depth.shape) > MAX_SIDE:
+        raise ValueError("the depth image must be at most 4096 x 4096")
+    h, w = depth.shape
+    focal_px = float(focal_px)
+    cx, cy = (w - 1) / 2 if cx is None else float(cx), (h - 1) / 2 if cy is None else float(cy)
+    max_jump_m = 0.0 if max_jump_m is None else float(max_jump_m)
+    if not (np.isfinite(focal_px) and focal_px > 0):
+        raise ValueError("focal_px must be finite and positive")
+    if not (np.isfinite(cx) and np.isfinite(cy)):
+        raise ValueError("cx and cy must be finite")
+    if np.isnan(max_jump_m):
+        raise ValueError("max_jump_m is not a number")
+    return focal_px, cx, cy, max_jump_m, int(bool(encode))
+
+
+def _normals_dev(ctx, depth, params):
+    h, w = depth.shape
+    out = DeviceMat(ctx, (h, w, 3), np.float32)
+    _vp.check(_vp.lib().vp_normals_from_depth_dev(ctx.handle, depth.dev_ptr, 4 * w, w, h, *params, out.dev_ptr, 12 * w), ctx.handle)
+    return out
+
+
+def normals_from_depth(depth, focal_px: float, cx=None, cy=None, max_jump_m=None, encode: bool = False):
+    """Surface normals of a float32 depth image in metres, float32 (h, w, 3), by this library's own definition (the vendor SDK's is
+    closed).  A normal exists where the pixel and its four neighbours are inside the image with a finite depth above 0 - and, with
+    max_jump_m, none of the four differs from the centre by more than it: a depth edge gives no normal.  With P the back-projection
+    ((x - cx) Z / f, (y - cy) Z / f, Z), the normal is the unit vector of (P(x, y+1) - P(x, y-1)) x (P(x+1, y) - P(x-1, y)), which
+    faces the camera: (0, 0, -1) for a wall square to the optical axis.  cx, cy default to the image centre ((w-1)/2, (h-1)/2).
+    Without a normal the result is NaN thrice; encode=True gives the reference's `normal` plane instead, (n + 1) / 2 and 0 without a
+    normal.  numpy in gives numpy out, a DeviceMat a DeviceMat."""
+    params = _normals_args(depth, focal_px, cx, cy, max_jump_m, encode)
+    ctx = _vp.default_context()
+    if isinstance(depth, DeviceMat):
+        depth.refresh_device(ctx)
+        return _normals_dev(ctx, depth, params)
+    depth = np.ascontiguousarray(depth)
+    h, w = depth.shape
+    out = np.empty((h, w, 3), np.float32)
+    _vp.check(_vp.lib().vp_normals_from_depth_f32(ctx.handle, depth.ctypes.data, w, h, *params, out.ctypes.data), ctx.handle)
+    return out
+
+
+def stereo_planes(left, right, focal_px: float, baseline_m: float, cx=None, cy=None, speckle_window_size: int = 100, speckle_range: int = 2, max_jump_m=None,
+                  **matcher):
+    """The `depth` and `normal` planes of the reference's forward camera (zed_sync.py:148-149) from a rectified pair: `disparity`, then
+    `filter_speckles` with max_diff = 16 * speckle_range and new_val = invalid_disparity(min_disparity) (skipped when
+    speckle_window_size is 0), then `depth_from_disparity`, then `normals_from_depth(encode=True)`.  All four are queued on the device
+    and nothing visits the host in between; (depth, normal) come back as DeviceMats if either image was one, else as numpy arrays.
+    speckle_window_size = 100 and speckle_range = 2 are the middle of the range OpenCV's documentation recommends (50-200, 1-2);
+    nothing here measured them."""
+    params = _matcher(**matcher)
+    left, right = _pair(left, right)
+    focal_px, baseline_m = float(focal_px), float(baseline_m)
+    h, w = left.shape
+    window = _int_in("speckle_window_size", speckle_window_size, 0, w * h)
+    diff = 16 * _int_in("speckle_range", speckle_range, 0, 4095)
+    nparams = _normals_args(np.empty((1, 1), np.float32), focal_px, (w - 1) / 2 if cx is None else cx, (h - 1) / 2 if cy is None else cy, max_jump_m, True)
+    on_device = isinstance(left, DeviceMat) or isinstance(right, DeviceMat)
+    ctx = _vp.default_context()
+    disp = _disparity_dev(ctx, left, right, params)
+    if window:
+        disp = _speckles_dev(ctx, disp, (invalid_disparity(params[2]), window, diff), out=disp)
+    depth = _depth_dev(ctx, disp, focal_px, baseline_m)
+    normal = _normals_dev(ctx, depth, nparams)
+    return (depth, normal) if on_device else (depth.host(), normal.host())

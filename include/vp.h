@@ -1101,6 +1101,37 @@ int vp_depth_from_disparity_dev(vp_ctx* ctx, const int16_t* disp_dev, size_t dis
                                 size_t depth_stride);
 int vp_depth_from_disparity_host(const int16_t* disp, size_t disp_stride, int w, int h, double focal_px, double baseline_m, float* depth, size_t depth_stride);
 
+/* ---- after the matcher: speckle filter of a disparity image, surface normals of a depth image ---------------
+ * filter_speckles: the rule of cv2.filterSpeckles on an int16 image, byte for byte against tests/speckle_restate.py, which is the
+ *   contract (it has not met a real OpenCV).  Pixels equal to new_val belong to no region and stay.  Two other pixels are linked when
+ *   they are 4-neighbours and |a - b| <= max_diff (in int32); links chain.  Every connected region of at most max_speckle_size pixels
+ *   becomes new_val, everything else is copied.  max_speckle_size in 0..w*h (0 copies), max_diff in 0..65535, new_val any int16 value.
+ *   dst may be src itself (same pointer, same stride); any other overlap is refused.
+ * vp_filter_speckles_plan: no device, no context.  *ws_bytes: device scratch of a call (an int32 label and an int32 count per pixel);
+ *   geometry: tile width, tile height, grid x, grid y, LDS bytes per block.
+ * normals_from_depth: this library's own definition (the vendor SDK's is closed), bit for bit against tests/normals_restate.py.
+ *   depth: float32 metres; a pixel is usable iff finite and > 0.  A normal exists at (x, y) iff the pixel and its four neighbours are
+ *   inside the image and usable and, with max_jump_m > 0 and finite, no neighbour's depth differs from the centre's by more than it.
+ *   P(x, y) = ((x - cx) Z / f, (y - cy) Z / f, Z); du = P(x+1, y) - P(x-1, y); dv = P(x, y+1) - P(x, y-1); c = dv x du (towards the
+ *   camera); len = sqrt((c0 c0 + c1 c1) + c2 c2); n = float32(c / len); all in IEEE double, every operation rounded on its own.  No
+ *   normal where len is 0 (or not finite).  normals: float32, 3 per pixel; without a normal NaN (0x7fc00000) thrice.  encode != 0:
+ *   float32(float32(n + 1) / 2) instead, and 0 without a normal - the reference's `normal` plane.
+ * _i16 / _f32: packed host images in and out, synchronise.  _dev: device images with strides in bytes, enqueued.  _host: the same
+ *   statements as scalar C++, host images with strides, no device and no context.
+ * Refused with VP_ERR_INVALID before anything is launched or written (the message names the reason): a missing pointer, w or h
+ *   outside 1..4096, a stride below the row or no multiple of the element size, a misaligned image, a parameter outside its range,
+ *   focal_px not finite or not positive, cx, cy or max_jump_m not a number, a result that overlaps its input (but for dst == src). */
+int vp_filter_speckles_plan(int w, int h, size_t* ws_bytes, int32_t* geometry);
+int vp_filter_speckles_i16(vp_ctx* ctx, const int16_t* src, int w, int h, int new_val, int max_speckle_size, int max_diff, int16_t* dst);
+int vp_filter_speckles_dev(vp_ctx* ctx, const int16_t* src_dev, size_t src_stride, int w, int h, int new_val, int max_speckle_size, int max_diff, int16_t* dst_dev,
+                           size_t dst_stride);
+int vp_filter_speckles_host(const int16_t* src, size_t src_stride, int w, int h, int new_val, int max_speckle_size, int max_diff, int16_t* dst, size_t dst_stride);
+int vp_normals_from_depth_f32(vp_ctx* ctx, const float* depth, int w, int h, double focal_px, double cx, double cy, double max_jump_m, int encode, float* normals);
+int vp_normals_from_depth_dev(vp_ctx* ctx, const float* depth_dev, size_t depth_stride, int w, int h, double focal_px, double cx, double cy, double max_jump_m, int encode,
+                              float* normals_dev, size_t normals_stride);
+int vp_normals_from_depth_host(const float* depth, size_t depth_stride, int w, int h, double focal_px, double cx, double cy, double max_jump_m, int encode, float* normals,
+                               size_t normals_stride);
+
 /* ---- device memory helpers (so a host program needs no HIP binding of its own) --------- */
 int vp_dev_alloc(vp_ctx* ctx, size_t bytes, void** dev_ptr);
 int vp_dev_free(vp_ctx* ctx, void* dev_ptr);    /* ctx may be NULL (memory that outlived its context) */
