@@ -279,7 +279,7 @@ const char* vp_profile_kernel_name(int id)
 {
     static const char* names[VP_PROF_KERNELS] = {"k_color_thresh", "k_morph_bits", "k_ccl_local", "k_ccl_boundary", "k_ccl_flatten", "k_ccl_rank",
                                                   "k_ccl_bg", "k_ccl_stats", "k_ccl_final", "k_ccl_write", "memset", "other",
-                                                  "k_ccl2_local", "k_ccl2_merge", "k_ccl2_write"};
+                                                  "k_ccl2_local", "k_ccl2_merge", "k_ccl2_write", "k_sgm_cost", "k_sgm_path", "k_sgm_select"};
     return (id >= 0 && id < VP_PROF_KERNELS) ? names[id] : "?";
 }
 

@@ -29,24 +29,6 @@ static const char* depth_check(const int16_t* disp, size_t sstride, int w, int h
     return nullptr;
 }
 
-// XSOBEL of one image into rows of w bytes
-static void host_prefilter(const uint8_t* src, size_t stride, int w, int h, int cap, uint8_t* out)
-{
-    for (int y = 0; y < h; y++) {
-        const int ya = h == 1 ? 0 : (y == 0 ? 1 : y - 1), yb = h == 1 ? 0 : (y == h - 1 ? h - 2 : y + 1);
-        const uint8_t *a = src + (size_t)ya * stride, *m = src + (size_t)y * stride, *b = src + (size_t)yb * stride;
-        uint8_t* o = out + (size_t)y * w;
-        for (int x = 0; x < w; x++) {
-            int v = 0;
-            if (x >= 1 && x <= w - 2) {
-                v = (int)a[x + 1] - (int)a[x - 1] + 2 * ((int)m[x + 1] - (int)m[x - 1]) + (int)b[x + 1] - (int)b[x - 1];
-                v = std::max(-cap, std::min(cap, v));
-            }
-            o[x] = (uint8_t)(v + cap);
-        }
-    }
-}
-
 extern "C" {
 
 int vp_stereo_bm_plan(int w, int h, int num_disparities, int block_size, int min_disparity, int32_t* rect, size_t* ws_bytes, int32_t* geometry)
@@ -120,8 +102,8 @@ int vp_stereo_bm_host(const uint8_t* left, size_t left_stride, const uint8_t* ri
         for (int x = 0; x < w; x++) disp[(size_t)y * dpitch + x] = (int16_t)inv;
     if (!P.cw) return VP_OK;
     std::vector<uint8_t> pl((size_t)w * h), pr((size_t)w * h);
-    host_prefilter(left, left_stride, w, h, cap, pl.data());
-    host_prefilter(right, right_stride, w, h, cap, pr.data());
+    vp_stereo_host_prefilter(left, left_stride, w, h, cap, pl.data());
+    vp_stereo_host_prefilter(right, right_stride, w, h, cap, pr.data());
     // vertical sums over the window's rows, per disparity and column of [vx0, vx0 + vn); then one row of window sums
     const int vx0 = P.cx0 - r, vn = P.cw + 2 * r;
     std::vector<int32_t> V((size_t)nd * vn, 0), tex(vn, 0), C((size_t)nd * P.cw);

@@ -23,7 +23,8 @@ struct vp_tables {          // device copies of the OpenCV integer tables
 };
 
 enum { VPK_COLOR = 0, VPK_MORPH, VPK_CCL_LOCAL, VPK_CCL_BOUNDARY, VPK_CCL_FLATTEN, VPK_CCL_RANK, VPK_CCL_BG, VPK_CCL_STATS,
-       VPK_CCL_FINAL, VPK_CCL_WRITE, VPK_MEMSET, VPK_OTHER, VPK_CCL2_LOCAL, VPK_CCL2_MERGE, VPK_CCL2_WRITE, VPK_COUNT };
+       VPK_CCL_FINAL, VPK_CCL_WRITE, VPK_MEMSET, VPK_OTHER, VPK_CCL2_LOCAL, VPK_CCL2_MERGE, VPK_CCL2_WRITE, VPK_SGM_COST, VPK_SGM_PATH, VPK_SGM_SELECT, VPK_COUNT };
+static_assert(VPK_COUNT == VP_PROF_KERNELS, "every kernel id has a name and a slot in vp_profile_end's arrays");
 
 struct vp_prof {
     bool on;

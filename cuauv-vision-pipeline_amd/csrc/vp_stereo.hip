@@ -167,16 +167,25 @@ __global__ __launch_bounds__(256) void k_stereo_depth(const int16_t* __restrict_
     depth[(size_t)y * dstride + x] = vp_stereo_depth(fb, disp[(size_t)y * sstride + x]);
 }
 
+// both prefiltered images (rows of `pitch` bytes) and the invalid value into every pixel of the result: the first launch of the block
+// matcher and of semi-global matching (vp_sgm.hip)
+int vpk_stereo_prefilter(vp_ctx* ctx, const uint8_t* d_left, size_t lstride, const uint8_t* d_right, size_t rstride, int w, int h, int cap, int min_disp, uint8_t* pl,
+                         uint8_t* pr, size_t pitch, int16_t* d_disp, size_t dstride)
+{
+    {
+        vp_prof_scope ps(ctx, VPK_OTHER);
+        hipLaunchKernelGGL(k_stereo_prefilter, dim3((unsigned)((w + 255) / 256), (unsigned)h, 2), dim3(256), 0, ctx->stream, d_left, lstride, d_right, rstride, w, h, cap, pl,
+                           pr, pitch, d_disp, dstride / 2, (int16_t)vp_stereo_invalid(min_disp));
+    }
+    VP_HIP(ctx, hipGetLastError());
+    return VP_OK;
+}
+
 int vpk_stereo_bm(vp_ctx* ctx, const uint8_t* d_left, size_t lstride, const uint8_t* d_right, size_t rstride, int w, int h, int nd, int min_disp, int cap, int texture,
                   int uniq, const vp_stereo_plan& P, uint8_t* d_ws, int16_t* d_disp, size_t dstride)
 {
     uint8_t *pl = d_ws, *pr = d_ws + P.off_right;
-    {
-        vp_prof_scope ps(ctx, VPK_OTHER);
-        hipLaunchKernelGGL(k_stereo_prefilter, dim3((unsigned)((w + 255) / 256), (unsigned)h, 2), dim3(256), 0, ctx->stream, d_left, lstride, d_right, rstride, w, h, cap, pl,
-                           pr, P.pitch, d_disp, dstride / 2, (int16_t)vp_stereo_invalid(min_disp));
-    }
-    VP_HIP(ctx, hipGetLastError());
+    if (int rc = vpk_stereo_prefilter(ctx, d_left, lstride, d_right, rstride, w, h, cap, min_disp, pl, pr, P.pitch, d_disp, dstride)) return rc;
     if (!P.cw) return VP_OK;
     if (P.lds_bytes > SB_LDS_BYTES) return vp_fail(ctx, VP_ERR_UNSUPPORTED, "stereo: the strip's tables are above the LDS budget");
     sb_args A = {w, h, nd, min_disp, cap, texture, uniq, P};

@@ -101,6 +101,24 @@ VP_STEREO_HD static inline int16_t vp_stereo_subpixel(int cmin, int pm, int pp, 
 // fb: focal_px * baseline_m as one double product, made on the host
 VP_STEREO_HD static inline float vp_stereo_depth(double fb, int disp16) { return disp16 > 0 ? (float)(fb * 16.0 / (double)disp16) : 0.0f; }
 
+// XSOBEL of one host image into rows of w bytes: what the host routines of the block matcher and of semi-global matching start from
+static inline void vp_stereo_host_prefilter(const uint8_t* src, size_t stride, int w, int h, int cap, uint8_t* out)
+{
+    for (int y = 0; y < h; y++) {
+        const int ya = h == 1 ? 0 : (y == 0 ? 1 : y - 1), yb = h == 1 ? 0 : (y == h - 1 ? h - 2 : y + 1);
+        const uint8_t *a = src + (size_t)ya * stride, *m = src + (size_t)y * stride, *b = src + (size_t)yb * stride;
+        uint8_t* o = out + (size_t)y * w;
+        for (int x = 0; x < w; x++) {
+            int v = 0;
+            if (x >= 1 && x <= w - 2) {
+                v = (int)a[x + 1] - (int)a[x - 1] + 2 * ((int)m[x + 1] - (int)m[x - 1]) + (int)b[x + 1] - (int)b[x - 1];
+                v = v < -cap ? -cap : (v > cap ? cap : v);
+            }
+            o[x] = (uint8_t)(v + cap);
+        }
+    }
+}
+
 static inline size_t vp_stereo_align(size_t n) { return (n + 255) / 256 * 256; }
 
 // arguments as vp_stereo_geometry_refusal admitted them

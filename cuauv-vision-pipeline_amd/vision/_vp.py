@@ -58,7 +58,7 @@ DIST_L1, DIST_L2, DIST_C = 1, 2, 3
 TM_SQDIFF, TM_SQDIFF_NORMED, TM_CCORR, TM_CCORR_NORMED, TM_CCOEFF, TM_CCOEFF_NORMED = 0, 1, 2, 3, 4, 5
 WARP_INVERSE_MAP = 16
 MODEL_SIMILARITY, MODEL_AFFINE, MODEL_HOMOGRAPHY = 0, 1, 2
-PROF_KERNELS = 15
+PROF_KERNELS = 18
 
 
 class VpError(RuntimeError):
@@ -353,6 +353,13 @@ _SIGS = {
     "vp_depth_from_disparity_i16": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_double, C.c_double, C.c_void_p]),
     "vp_depth_from_disparity_dev": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_int, C.c_int, C.c_double, C.c_double, C.c_void_p, C.c_size_t]),
     "vp_depth_from_disparity_host": (C.c_int, [C.c_void_p, C.c_size_t, C.c_int, C.c_int, C.c_double, C.c_double, C.c_void_p, C.c_size_t]),
+    "vp_stereo_sgm_plan": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "vp_stereo_sgm_u8": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,
+                                   C.c_void_p]),
+    "vp_stereo_sgm_dev": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,
+                                    C.c_int, C.c_int, C.c_void_p, C.c_size_t]),
+    "vp_stereo_sgm_host": (C.c_int, [C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,
+                                     C.c_int, C.c_void_p, C.c_size_t]),
     "vp_filter_speckles_plan": (C.c_int, [C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
     "vp_filter_speckles_i16": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p]),
     "vp_filter_speckles_dev": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_size_t]),

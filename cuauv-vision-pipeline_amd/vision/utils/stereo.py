@@ -10,6 +10,10 @@ After the matcher (libvp vp_speckle.hip): `filter_speckl
 of cv2.filterSpeckles, as tests/speckle_restate.py states it, byte for byte (it has not met a real OpenCV either); `normals_from_depth`
 makes the reference's fourth plane, `normal` (zed_sync.py:114,132-137), by this library's own definition, bit for bit as
 tests/normals_restate.py states it; `stereo_planes` chains all four steps in HBM.
+
+`disparity_sgm` is the second matcher (libvp vp_sgm.hip): semi-global matching in the shape of cv2.StereoSGBM
+with a left-right check, as tests/sgm_restate.py states it, byte for byte; it does not claim OpenCV's bits.  It answers the flat
+surfaces the block matcher's texture test leaves empty.  `stereo_depth_sgm` and `stereo_planes_sgm` are the two chains on top of it.
 """
 import ctypes as C
 
@@ -135,16 +139,20 @@ def depth_from_disparity(disp16, focal_px: float, baseline_m: float):
     return out
 
 
-def stereo_depth(left, right, focal_px: float, baseline_m: float, **matcher):
-    """`depth_from_disparity(disparity(left, right, **matcher), focal_px, baseline_m)` with the disparity kept in HBM between the two:
-    numpy images are uploaded, both steps are queued, and only the float32 depth comes back (a DeviceMat if either image was one)."""
-    params = _matcher(**matcher)
+def _depth_chain(match_dev, params, left, right, focal_px, baseline_m):
+    """matcher, then depth, both queued; match_dev: _disparity_dev or _disparity_sgm_dev with its checked parameters"""
     left, right = _pair(left, right)
     focal_px, baseline_m = float(focal_px), float(baseline_m)
     on_device = isinstance(left, DeviceMat) or isinstance(right, DeviceMat)
     ctx = _vp.default_context()
-    depth = _depth_dev(ctx, _disparity_dev(ctx, left, right, params), focal_px, baseline_m)
+    depth = _depth_dev(ctx, match_dev(ctx, left, right, params), focal_px, baseline_m)
     return depth if on_device else depth.host()
+
+
+def stereo_depth(left, right, focal_px: float, baseline_m: float, **matcher):
+    """`depth_from_disparity(disparity(left, right, **matcher), focal_px, baseline_m)` with the disparity kept in HBM between the two:
+    numpy images are uploaded, both steps are queued, and only the float32 depth comes back (a DeviceMat if either image was one)."""
+    return _depth_chain(_disparity_dev, _matcher(**matcher), left, right, focal_px, baseline_m)
 
 
 def _int_in(name, v, lo, hi):
@@ -245,7 +253,11 @@ def stereo_planes(left, right, focal_px: float, baseline_m: float, cx=None, cy=N
     and nothing visits the host in between; (depth, normal) come back as DeviceMats if either image was one, else as numpy arrays.
     speckle_window_size = 100 and speckle_range = 2 are the middle of the range OpenCV's documentation recommends (50-200, 1-2);
     nothing here measured them."""
-    params = _matcher(**matcher)
+    return _planes_chain(_disparity_dev, _matcher(**matcher), left, right, focal_px, baseline_m, cx, cy, speckle_window_size, speckle_range, max_jump_m)
+
+
+def _planes_chain(match_dev, params, left, right, focal_px, baseline_m, cx, cy, speckle_window_size, speckle_range, max_jump_m):
+    """matcher, speckle filter, depth, normals, all queued; params[2] is min_disparity for both matchers"""
     left, right = _pair(left, right)
     focal_px, baseline_m = float(focal_px), float(baseline_m)
     h, w = left.shape
@@ -254,9 +266,114 @@ def stereo_planes(left, right, focal_px: float, baseline_m: float, cx=None, cy=N
     nparams = _normals_args(np.empty((1, 1), np.float32), focal_px, (w - 1) / 2 if cx is None else cx, (h - 1) / 2 if cy is None else cy, max_jump_m, True)
     on_device = isinstance(left, DeviceMat) or isinstance(right, DeviceMat)
     ctx = _vp.default_context()
-    disp = _disparity_dev(ctx, left, right, params)
+    disp = match_dev(ctx, left, right, params)
     if window:
         disp = _speckles_dev(ctx, disp, (invalid_disparity(params[2]), window, diff), out=disp)
     depth = _depth_dev(ctx, disp, focal_px, baseline_m)
     normal = _normals_dev(ctx, depth, nparams)
     return (depth, normal) if on_device else (depth.host(), normal.host())
+
+
+_SGM_RANGES = (("num_disparities", 16, 256), ("block_size", 1, 9), ("min_disparity", -128, 128), ("pre_filter_cap", 1, 63), ("p1", 0, 65535), ("p2", 0, 65535),
+               ("uniqueness_ratio", 0, 100), ("disp12_max_diff", -1, 255), ("paths", 4, 8))
+SGM_MAX_SUM = 65535
+
+
+def _matcher_sgm(num_disparities=64, block_size=5, min_disparity=0, pre_filter_cap=31, p1=None, p2=None, uniqueness_ratio=10, disp12_max_diff=1, paths=8):
+    """the nine checked parameters, in the order of the C entries; everything libvp refuses is refused here, before a device is needed"""
+    given = [num_disparities, block_size, min_disparity, pre_filter_cap, p1, p2, uniqueness_ratio, disp12_max_diff, paths]
+    for (name, _, _), v in zip(_SGM_RANGES, given):
+        if not (v is None and name in ("p1", "p2")) and (isinstance(v, bool) or not isinstance(v, (int, np.integer))):
+            raise TypeError(f"{name} must be an integer")
+    if given[4] is None:
+        given[4] = 8 * int(block_size) ** 2
+    if given[5] is None:
+        given[5] = 32 * int(block_size) ** 2
+    out = []
+    for (name, lo, hi), v in zip(_SGM_RANGES, given):
+        if not lo <= v <= hi:
+            raise ValueError(f"{name} must lie in {lo}..{hi}")
+        out.append(int(v))
+    n, bs, _, cap, p1, p2, _, _, paths = out
+    if n % 16:
+        raise ValueError("num_disparities must be a multiple of 16")
+    if bs % 2 == 0:
+        raise ValueError("block_size must be odd")
+    if paths not in (4, 8):
+        raise ValueError("paths must be 4 or 8")
+    if p1 > p2:
+        raise ValueError("p1 must not exceed p2")
+    if paths * (2 * cap * bs * bs + p2) > SGM_MAX_SUM:
+        raise ValueError(f"paths * (2 * pre_filter_cap * block_size^2 + p2) must not exceed {SGM_MAX_SUM}: the summed path costs are 16-bit")
+    return tuple(out)
+
+
+def valid_rect_sgm(w: int, h: int, num_disparities: int = 64, block_size: int = 5, min_disparity: int = 0):
+    """(x, y, w, h) of the pixels `disparity_sgm` can answer, from libvp's plan (vp_stereo_sgm_plan; no device needed): `valid_rect`'s
+    rule at this block size; (0, 0, 0, 0) when there is none."""
+    n, bs, m = _matcher_sgm(num_disparities, block_size, min_disparity, p1=0, p2=0)[:3]
+    if not (1 <= int(w) <= MAX_SIDE and 1 <= int(h) <= MAX_SIDE):
+        raise ValueError("width and height must lie in 1..4096")
+    rect, geom, ws = (C.c_int32 * 4)(), (C.c_int32 * 15)(), C.c_size_t()
+    _vp.check(_vp.lib().vp_stereo_sgm_plan(int(w), int(h), n, bs, m, 8, rect, C.byref(ws), geom))
+    return tuple(rect)
+
+
+SGM_MAX_WORKSPACE = 1 << 32
+
+
+def _sgm_pair(left, right, params):
+    """`_pair`, and the one refusal of libvp's that depends on the size: the workspace of the call"""
+    left, right = _pair(left, right)
+    h, w = left.shape
+    rect, geom, ws = (C.c_int32 * 4)(), (C.c_int32 * 15)(), C.c_size_t()
+    if _vp.lib().vp_stereo_sgm_plan(w, h, params[0], params[1], params[2], params[8], rect, C.byref(ws), geom) != 0:
+        raise ValueError(f"the workspace of this call would exceed {SGM_MAX_WORKSPACE} bytes (4 GiB): {w} x {h} at {params[0]} disparities")
+    return left, right
+
+
+def _disparity_sgm_dev(ctx, left, right, params):
+    """both images on the device -> an int16 DeviceMat, enqueued"""
+    left, right = device_image(ctx, left, 1), device_image(ctx, right, 1)
+    h, w = left.shape
+    out = DeviceMat(ctx, (h, w), np.int16)
+    _vp.check(_vp.lib().vp_stereo_sgm_dev(ctx.handle, left.dev_ptr, w, right.dev_ptr, w, w, h, *params, out.dev_ptr, 2 * w), ctx.handle)
+    return out
+
+
+def disparity_sgm(left, right, num_disparities: int = 64, block_size: int = 5, min_disparity: int = 0, pre_filter_cap: int = 31, p1=None, p2=None,
+                  uniqueness_ratio: int = 10, disp12_max_diff: int = 1, paths: int = 8):
+    """16 times the disparity of every pixel of `left` by semi-global matching, int16, `invalid_disparity(min_disparity)` where there
+    is no answer: outside `valid_rect_sgm`, where a second disparity is within uniqueness_ratio per cent of the best, and where the
+    right view's answer differs from the left's by more than disp12_max_diff (-1: not checked).  The cost is `disparity`'s window sum
+    of absolute differences of the prefiltered images, without a texture test; it is summed along `paths` (4 or 8) directions with the
+    penalty p1 for a change of disparity by one and p2 for a larger change.  p1=None means 8 * block_size^2 and p2=None
+    32 * block_size^2: the values OpenCV's documentation recommends for one channel; nothing here measured them.  uint8 (h, w) images
+    of one size up to 4096 x 4096; (h, w, 3) images go through bgr_to_gray first.  num_disparities a multiple of 16 in 16..256,
+    block_size odd in 1..9, min_disparity in -128..128, pre_filter_cap in 1..63, 0 <= p1 <= p2, uniqueness_ratio in 0..100,
+    disp12_max_diff in -1..255, and paths * (2 * pre_filter_cap * block_size^2 + p2) <= 65535, which keeps the summed costs in 16 bits.
+    The scratch of a call, 4 * num_disparities bytes per candidate pixel, must not exceed 4 GiB.  numpy in gives numpy out; if either
+    image is a DeviceMat the result is an int16 DeviceMat that stays in HBM."""
+    params = _matcher_sgm(num_disparities, block_size, min_disparity, pre_filter_cap, p1, p2, uniqueness_ratio, disp12_max_diff, paths)
+    left, right = _sgm_pair(left, right, params)
+    ctx = _vp.default_context()
+    if isinstance(left, DeviceMat) or isinstance(right, DeviceMat):
+        return _disparity_sgm_dev(ctx, left, right, params)
+    left, right = np.ascontiguousarray(left), np.ascontiguousarray(right)
+    h, w = left.shape
+    out = np.empty((h, w), np.int16)
+    _vp.check(_vp.lib().vp_stereo_sgm_u8(ctx.handle, left.ctypes.data, right.ctypes.data, w, h, *params, out.ctypes.data), ctx.handle)
+    return out
+
+
+def stereo_depth_sgm(left, right, focal_px: float, baseline_m: float, **matcher):
+    """`stereo_depth` with `disparity_sgm` as the matcher: **matcher are its parameters."""
+    params = _matcher_sgm(**matcher)
+    return _depth_chain(_disparity_sgm_dev, params, *_sgm_pair(left, right, params), focal_px, baseline_m)
+
+
+def stereo_planes_sgm(left, right, focal_px: float, baseline_m: float, cx=None, cy=None, speckle_window_size: int = 100, speckle_range: int = 2, max_jump_m=None,
+                      **matcher):
+    """`stereo_planes` with `disparity_sgm` as the matcher: **matcher are its parameters; the steps after the matcher are the same."""
+    params = _matcher_sgm(**matcher)
+    return _planes_chain(_disparity_sgm_dev, params, *_sgm_pair(left, right, params), focal_px, baseline_m, cx, cy, speckle_window_size, speckle_range, max_jump_m)

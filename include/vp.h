@@ -117,7 +117,7 @@ int vp_timer_stop(vp_ctx* ctx, float* elapsed_ms); /* records, synchronises, ret
 /* Per-kernel attribution: between vp_profile_begin and vp_profile_end every kernel the context
  * launches is bracketed by HIP events on its stream.  vp_profile_end synchronises and fills
  * total_ms[id] / launches[id] for id < VP_PROF_KERNELS (names: vp_profile_kernel_name). */
-#define VP_PROF_KERNELS 15
+#define VP_PROF_KERNELS 18
 int vp_profile_begin(vp_ctx* ctx, int max_records);
 int vp_profile_end(vp_ctx* ctx, double* total_ms, int32_t* launches);
 const char* vp_profile_kernel_name(int id);
@@ -1131,6 +1131,41 @@ int vp_normals_from_depth_dev(vp_ctx* ctx, const float* depth_dev, size_t depth_
                               float* normals_dev, size_t normals_stride);
 int vp_normals_from_depth_host(const float* depth, size_t depth_stride, int w, int h, double focal_px, double cx, double cy, double max_jump_m, int encode, float* normals,
                                size_t normals_stride);
+
+/* ---- semi-global stereo matching with a left-right check -------------------------------------------------
+ * Hirschmueller's semi-global matching in the shape of cv2.StereoSGBM, byte for byte against tests/sgm_restate.py, which is the
+ * contract; it does not claim OpenCV's bits.  Images, prefilter, C(x, y, d) (D = m + d, d in [0, n)), the candidate rectangle and the
+ * invalid value INV = (m - 1) * 16 are the block matcher's above, at this block size; there is no texture test.  num_disparities n: a
+ * multiple of 16 in 16..256; block_size odd in 1..9; min_disparity m in -128..128; pre_filter_cap c in 1..63; 0 <= p1 <= p2;
+ * uniqueness_ratio in 0..100; disp12_max_diff in -1..255 (-1: no left-right check); paths 4 or 8;
+ * paths * (2 c block_size^2 + p2) <= 65535, which keeps the summed path costs in 16 bits.
+ *   Paths: directions of travel (dy, dx) = (0,1) (0,-1) (1,0) (-1,0), with paths = 8 also (1,1) (1,-1) (-1,1) (-1,-1).  For a pixel p
+ *     whose predecessor q = p - (dy, dx) lies outside the candidate rectangle L(p, d) = C(p, d); else, with M = min over k of L(q, k),
+ *     L(p, d) = C(p, d) + min(L(q, d), L(q, d-1) + p1, L(q, d+1) + p1, M + p2) - M, a term whose d -+ 1 leaves [0, n) being absent.
+ *     S = the sum of L over the paths.  d* minimises S, ties to the larger d.
+ *   Uniqueness (ratio > 0): a d with |d - d*| > 1 and S(d) <= S* + S* ratio / 100 (integer division) gives INV.
+ *   Left-right check (disp12_max_diff >= 0): with xr = x - (m + d*), the right view's answer is the d that minimises S(xr + m + d, y, d)
+ *     over the d whose column xr + m + d is a candidate column, ties to the larger d; |d_right - d*| > disp12_max_diff gives INV.
+ *   Else the block matcher's subpixel rule on S: (D* 256 + off + 15) >> 4, int16.
+ * vp_stereo_sgm_plan: no device, no context.  rect: x, y, w, h of the candidate pixels (zeros when there is none); *ws_bytes: device
+ *   scratch of a call - both prefiltered images and the uint16 volumes C and S, 2 * 2 * rect.w * rect.h * n bytes; geometry
+ *   [VP_SGM_GEOMETRY]: cost kernel: threads, strip columns, grid x, grid y, LDS bytes; path kernel: threads, lanes that hold a pixel,
+ *   disparities per lane, lines per block, blocks of a horizontal, a vertical, a diagonal direction (0 with four paths); selection
+ *   kernel: threads, pixels per block, blocks.  A call whose workspace would exceed 4 GiB (4294967296 bytes) is refused, by every entry.
+ * _u8: packed host images in and out, synchronises.  _dev: device images with strides in bytes, enqueued.  _host: the same statement
+ *   as scalar C++, host images with strides, no device and no context.
+ * Refused with VP_ERR_INVALID before anything is launched or written (the message names the reason): a missing pointer, w or h
+ *   outside 1..4096, a stride below the row or, for the result, no multiple of 2, a parameter outside its range, p1 > p2, the 16-bit
+ *   bound, the workspace cap, a misaligned result, a result that overlaps an input.  An image without a candidate pixel is no error. */
+#define VP_SGM_GEOMETRY 15
+int vp_stereo_sgm_plan(int w, int h, int num_disparities, int block_size, int min_disparity, int paths, int32_t* rect, size_t* ws_bytes, int32_t* geometry);
+int vp_stereo_sgm_u8(vp_ctx* ctx, const uint8_t* left, const uint8_t* right, int w, int h, int num_disparities, int block_size, int min_disparity, int pre_filter_cap, int p1,
+                     int p2, int uniqueness_ratio, int disp12_max_diff, int paths, int16_t* disp);
+int vp_stereo_sgm_dev(vp_ctx* ctx, const uint8_t* left_dev, size_t left_stride, const uint8_t* right_dev, size_t right_stride, int w, int h, int num_disparities,
+                      int block_size, int min_disparity, int pre_filter_cap, int p1, int p2, int uniqueness_ratio, int disp12_max_diff, int paths, int16_t* disp_dev,
+                      size_t disp_stride);
+int vp_stereo_sgm_host(const uint8_t* left, size_t left_stride, const uint8_t* right, size_t right_stride, int w, int h, int num_disparities, int block_size,
+                       int min_disparity, int pre_filter_cap, int p1, int p2, int uniqueness_ratio, int disp12_max_diff, int paths, int16_t* disp, size_t disp_stride);
 
 /* ---- device memory helpers (so a host program needs no HIP binding of its own) --------- */
 int vp_dev_alloc(vp_ctx* ctx, size_t bytes, void** dev_ptr);
