@@ -899,6 +899,53 @@ def filterSpeckles(img, newVal, maxSpeckleSize, maxDiff, buf=None):
         raise error(f"filterSpeckles: {e}") from None
 
 
+# ---- stereo rectification and reprojection (libvp vp_rectify.hip) ---------------------------------------------
+CALIB_ZERO_DISPARITY = 1024
+
+
+def stereoRectify(cameraMatrix1, distCoeffs1, cameraMatrix2, distCoeffs2, imageSize, R, T, R1=None, R2=None, P1=None, P2=None, Q=None,
+                  flags=CALIB_ZERO_DISPARITY, alpha=-1, newImageSize=(0, 0)):
+    """cv2.stereoRectify: (R1, R2, P1, P2, Q, validPixROI1, validPixROI2) by Bouguet's algorithm, host numpy in float64
+    (vision.utils.stereo.stereo_rectify has the steps); run once per calibration.  The statement is this library's own: cv2's bits
+    are not claimed.  flags: 0 or CALIB_ZERO_DISPARITY; newImageSize (0, 0) means imageSize.  The maps come from
+    initUndistortRectifyMap with R1 / P1 and R2 / P2; vision.utils.stereo.StereoRig keeps them in HBM."""
+    from vision.utils import stereo as _stereo
+    if flags not in (0, CALIB_ZERO_DISPARITY):
+        raise error("stereoRectify: flags must be 0 or CALIB_ZERO_DISPARITY")
+    new_size = None if newImageSize is None or tuple(newImageSize) == (0, 0) else newImageSize
+    out = _gather("stereoRectify", _stereo.stereo_rectify, cameraMatrix1, distCoeffs1, cameraMatrix2, distCoeffs2, imageSize, R, T,
+                  flags == CALIB_ZERO_DISPARITY, alpha, new_size)
+    for given, made in zip((R1, R2, P1, P2, Q), out):
+        if given is not None:
+            _into(given, made)
+    return out
+
+
+def reprojectImageTo3D(disparity, Q, _3dImage=None, handleMissingValues=False, ddepth=-1):
+    """cv2.reprojectImageTo3D on the GPU (libvp vp_reproject_to_3d_*): float32 (h, w, 3) points of an int16 or float32 (h, w) disparity
+    image, (X / W, Y / W, Z / W) of Q (x, y, d, 1) in double.  As in cv2 the values of the image are the disparities as they stand: a
+    matcher's int16 result, 16 times the disparity, is divided by 16 by the caller (vision.utils.stereo.reproject_to_3d and
+    StereoRig.points take it as it is).  Pixels with W == 0 or a disparity that is not finite give three zeros.
+    handleMissingValues=True is refused: cv2's 10000-Z mark is not this library's zero convention.  ddepth: -1 or CV_32F."""
+    from vision.devmat import DeviceMat
+    from vision.utils import stereo as _stereo
+    if handleMissingValues:
+        raise error("reprojectImageTo3D: handleMissingValues marks pixels with Z = 10000; this library marks them with zeros (DESIGN.md section 7)")
+    if ddepth not in (-1, CV_32F):
+        raise error("reprojectImageTo3D: ddepth must be -1 or CV_32F")
+    disp = _as(disparity)
+    if isinstance(disp, (np.ndarray, DeviceMat)) and disp.ndim == 3 and disp.shape[2] == 1:
+        disp = disp.reshaped(disp.shape[:2]) if isinstance(disp, DeviceMat) else disp[:, :, 0]
+    if isinstance(disp, np.ndarray) and disp.dtype == np.int16:
+        disp = disp.astype(np.float32)                    # cv2 reads the int16 values as pixels; every int16 is exact in float32
+    elif isinstance(disp, DeviceMat) and disp.dtype == np.int16:
+        raise error("reprojectImageTo3D: an int16 image in HBM holds sixteenths of a pixel: vision.utils.stereo.reproject_to_3d reads it as such")
+    try:
+        return _into(_3dImage, _gather("reprojectImageTo3D", _stereo.reproject_to_3d, disp, Q))
+    except _vp.VpError as e:
+        raise error(f"reprojectImageTo3D: {e}") from None
+
+
 # ---- derivative filters (libvp vp_deriv.hip) ------------------------------------------------------------------------------------------
 def _deriv_call(name, fn, src, ddepth, scale, delta, borderType, *args):
     """What cv2 rejects, and the two restrictions of this path: scale = 1 and delta = 0 only."""

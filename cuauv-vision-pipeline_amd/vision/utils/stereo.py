@@ -14,14 +14,20 @@ tests/normals_restate.py states it; `stereo_planes` chains all four steps in HBM
 `disparity_sgm` is the second matcher (libvp vp_sgm.hip): semi-global matching in the shape of cv2.StereoSGBM
 with a left-right check, as tests/sgm_restate.py states it, byte for byte; it does not claim OpenCV's bits.  It answers the flat
 surfaces the block matcher's texture test leaves empty.  `stereo_depth_sgm` and `stereo_planes_sgm` are the two chains on top of it.
+
+The head and the tail (libvp vp_rectify.hip): `stereo_rectify` is the calibration-time geometry (Bouguet's
+algorithm in the shape of cv2.stereoRectify, host float64, the library's own statement), `rectify_pair` turns both raw eyes into the
+matcher's grey pair in one launch, byte for byte as tests/rectify_restate.py states it, `reproject_to_3d` makes XYZ points of a
+disparity image, bit for bit, and `StereoRig` ties a calibration to the chain: from one raw side-by-side frame to `depth`, `normal`
+and points, everything in HBM.
 """
 import ctypes as C
 
 import numpy as np
 
 from vision import _vp
-from vision.devmat import DeviceMat
-from vision.utils.helpers import device_image, image_source
+from vision.devmat import DeviceMat, finish_uploads
+from vision.utils.helpers import device_image, error, image_source
 
 MAX_SIDE = 4096
 _RANGES = (("num_disparities", 16, 256), ("block_size", 5, 21), ("min_disparity", -128, 128), ("pre_filter_cap", 1, 63), ("texture_threshold", 0, 2 ** 31 - 1),
@@ -377,3 +383,388 @@ def stereo_planes_sgm(left, right, focal_px: float, baseline_m: float, cx=None, 
     """`stereo_planes` with `disparity_sgm` as the matcher: **matcher are its parameters; the steps after the matcher are the same."""
     params = _matcher_sgm(**matcher)
     return _planes_chain(_disparity_sgm_dev, params, *_sgm_pair(left, right, params), focal_px, baseline_m, cx, cy, speckle_window_size, speckle_range, max_jump_m)
+
+
+# ---- the head and the tail of the stack: rectification and 3-D reprojection (libvp vp_rectify.hip; DESIGN.md section 4.37) ------------
+UNDISTORT_ITERATIONS = 100
+CALIB_ZERO_DISPARITY = 1024
+DISP_I16, DISP_F32 = 0, 1
+_INT_MIN = -2 ** 31
+
+
+def rodrigues(src):
+    """cv2.Rodrigues without the Jacobian, float64: a rotation vector (3 numbers: the axis times the angle in radians) gives its 3x3
+    matrix, a 3x3 rotation matrix gives its vector (angle in [0, pi])."""
+    a = np.asarray(src, dtype=np.float64)
+    if a.size == 3:
+        r = a.ravel()
+        theta = float(np.sqrt(r @ r))
+        if theta < 1e-300:
+            return np.eye(3)
+        k = r / theta
+        K = np.array([[0.0, -k[2], k[1]], [k[2], 0.0, -k[0]], [-k[1], k[0], 0.0]])
+        return np.cos(theta) * np.eye(3) + (1 - np.cos(theta)) * np.outer(k, k) + np.sin(theta) * K
+    if a.shape != (3, 3):
+        raise error("Rodrigues: a rotation vector of 3 numbers or a 3x3 matrix")
+    v = np.array([a[2, 1] - a[1, 2], a[0, 2] - a[2, 0], a[1, 0] - a[0, 1]]) / 2          # the axis times sin(theta)
+    s, c = float(np.sqrt(v @ v)), min(1.0, max(-1.0, (a[0, 0] + a[1, 1] + a[2, 2] - 1) / 2))
+    theta = float(np.arctan2(s, c))
+    if s >= 1e-8:
+        return v * (theta / s)
+    if c > 0:
+        return v                                                                         # theta ~ sin(theta)
+    # theta ~ pi: R + I = 2 k k^T; the signs of k from its largest component, the vector's direction either way
+    d = np.maximum((np.diag(a) + 1) / 2, 0)
+    k = np.sqrt(d)
+    i = int(np.argmax(d))
+    for j in range(3):
+        if j != i and a[i, j] + a[j, i] < 0:
+            k[j] = -k[j]
+    return k * (theta / float(np.sqrt(k @ k)))
+
+
+def _undistort_points(pts, K, k8, R=None, P=None):
+    """Pixels of the raw image -> ideal points: the rational model inverted by UNDISTORT_ITERATIONS fixed-point iterations in double
+    (x <- (x_d - tangential(x)) / radial(x), from x = x_d), then rotated by R and projected by P (3x3) where they are given."""
+    pts = np.asarray(pts, dtype=np.float64).reshape(-1, 2)
+    k1, k2, p1, p2, k3, k4, k5, k6 = k8
+    x0, y0 = (pts[:, 0] - K[0, 2]) / K[0, 0], (pts[:, 1] - K[1, 2]) / K[1, 1]
+    x, y = x0.copy(), y0.copy()
+    for _ in range(UNDISTORT_ITERATIONS):
+        r2 = x * x + y * y
+        ikr = (1 + ((k6 * r2 + k5) * r2 + k4) * r2) / (1 + ((k3 * r2 + k2) * r2 + k1) * r2)
+        dx, dy = 2 * p1 * x * y + p2 * (r2 + 2 * x * x), p1 * (r2 + 2 * y * y) + 2 * p2 * x * y
+        x, y = (x0 - dx) * ikr, (y0 - dy) * ikr
+    if R is not None:
+        X = np.stack([x, y, np.ones_like(x)], axis=0)
+        X = np.asarray(R, dtype=np.float64) @ X
+        x, y = X[0] / X[2], X[1] / X[2]
+    if P is not None:
+        x, y = P[0, 0] * x + P[0, 2], P[1, 1] * y + P[1, 2]
+    return np.stack([x, y], axis=-1)
+
+
+def _grid_rectangles(K, k8, R, P, size, n=9):
+    """inner and outer rectangle (x0, y0, x1, y1) of the n x n grid of raw pixels after undistortion, rotation and projection"""
+    w, h = size
+    gx, gy = np.meshgrid(np.arange(n) * (w - 1) / (n - 1), np.arange(n) * (h - 1) / (n - 1))
+    p = _undistort_points(np.stack([gx.ravel(), gy.ravel()], axis=-1), K, k8, R, P).reshape(n, n, 2)
+    inner = (p[:, 0, 0].max(), p[0, :, 1].max(), p[:, -1, 0].min(), p[-1, :, 1].min())
+    outer = (p[..., 0].min(), p[..., 1].min(), p[..., 0].max(), p[..., 1].max())
+    return inner, outer
+
+
+def _taps_inside(K, d, R, P, src_size, new_size):
+    """bool (h, w) of the rectified image: all four bilinear taps of the pixel, as the fixed tables place them, lie inside the source"""
+    from vision.utils import transform as _transform
+    u, v = _transform._undistort_coords("stereoRectify", K, d, R, P, new_size)
+    xy, _ = _transform._fixed_from_double(u, v)
+    sx, sy = xy[..., 0].astype(np.int64), xy[..., 1].astype(np.int64)
+    return (sx >= 0) & (sx + 1 <= src_size[0] - 1) & (sy >= 0) & (sy + 1 <= src_size[1] - 1)
+
+
+def _valid_roi(inside, x0, y0, x1, y1):
+    """(x, y, w, h): the pixels of [x0, x1] x [y0, y1] (real numbers), shrunk edge by edge until every pixel of it is `inside`"""
+    H, W = inside.shape
+    xa, ya, xb, yb = max(int(np.ceil(x0)), 0), max(int(np.ceil(y0)), 0), min(int(np.floor(x1)), W - 1), min(int(np.floor(y1)), H - 1)
+    while xa <= xb and ya <= yb:
+        bad = ~inside[ya:yb + 1, xa:xb + 1]
+        if not bad.any():
+            return int(xa), int(ya), int(xb - xa + 1), int(yb - ya + 1)
+        edges = (bad[:, 0].sum(), bad[0].sum(), bad[:, -1].sum(), bad[-1].sum())
+        if not any(edges):
+            edges = (1, 1, 1, 1)
+        worst = max(edges)
+        xa, ya, xb, yb = xa + (edges[0] == worst), ya + (edges[1] == worst), xb - (edges[2] == worst), yb - (edges[3] == worst)
+    return 0, 0, 0, 0
+
+
+def stereo_rectify(K1, d1, K2, d2, size, R, T, zero_disparity: bool = True, alpha: float = -1, new_size=None):
+    """The rectifying rotations and projections of a calibrated pair by Bouguet's algorithm, in the shape of cv2.stereoRectify:
+    (R1, R2, P1, P2, Q, roi1, roi2), float64 on the host; run once per calibration.  R, T take points of the first camera to the
+    second (X2 = R X1 + T); size = (width, height) of the raw images, new_size of the rectified ones (default: size).
+
+      1. half the relative rotation goes to each camera (r = rodrigues(-rodrigues(R) / 2));
+      2. a second rotation takes the rotated baseline t = r T onto the x axis, or onto the y axis when |t.y| >= |t.x| (a vertical rig);
+         R1 = w r^T, R2 = w r;
+      3. the focal length is the mean of the two cameras' (fy for a horizontal rig, fx for a vertical one);
+      4. each principal point centres the four undistorted image corners; with zero_disparity both cameras share the mean of the
+         two, otherwise only the coordinate across the baseline is shared;
+      5. alpha scales the result about the principal points: 0 makes the inner rectangle of a 9 x 9 grid of undistorted points fill
+         the rectified image (no invalid pixel), 1 makes the outer rectangle fit (no source pixel lost), values between blend the two
+         scales, -1 keeps the scale - times new_size / size across the baseline when new_size is given;
+      6. roi1, roi2 = (x, y, w, h): the inner rectangle in rectified pixels, shrunk until all four bilinear taps of every pixel lie
+         inside the source.
+
+    Q takes (x, y, disparity, 1) of the first rectified image to homogeneous points in the first rectified camera's frame
+    (`reproject_to_3d`).  Distortion: the 8-coefficient rational model of cv2 (4, 5 or 8 numbers); thin-prism and tilt coefficients
+    raise, as everywhere in this library.  Distortion is inverted by 100 fixed-point iterations in double (UNDISTORT_ITERATIONS).
+    The statement is this library's own after the published algorithm: bit parity with cv2 is not claimed."""
+    from vision.utils import transform as _transform
+    A1, k1 = _transform._camera("stereoRectify", K1, d1)
+    A2, k2 = _transform._camera("stereoRectify", K2, d2)
+    try:
+        w, h = int(size[0]), int(size[1])
+        nw, nh = (w, h) if new_size is None else (int(new_size[0]), int(new_size[1]))
+    except (TypeError, ValueError, IndexError):
+        raise error("stereoRectify: the sizes must be (width, height)") from None
+    if w <= 0 or h <= 0 or nw <= 0 or nh <= 0:
+        raise error("stereoRectify: the sizes must be positive")
+    R = np.asarray(R, dtype=np.float64)
+    if R.size == 3:
+        R = rodrigues(R)
+    T = np.asarray(T, dtype=np.float64).ravel()
+    if R.shape != (3, 3) or not np.isfinite(R).all() or np.abs(R.T @ R - np.eye(3)).sum(axis=1).max() > 1e-6:
+        raise error("stereoRectify: R must be a finite orthonormal 3x3 matrix")
+    if T.shape != (3,) or not np.isfinite(T).all() or not T.any():
+        raise error("stereoRectify: T must be three finite numbers, not all zero")
+    alpha = float(alpha)
+    if not (alpha == -1 or 0 <= alpha <= 1):
+        raise error("stereoRectify: alpha must be -1 or lie in 0..1")
+
+    r = rodrigues(-0.5 * rodrigues(R))
+    t = r @ T
+    idx = 0 if abs(t[0]) > abs(t[1]) else 1
+    uu = np.zeros(3)
+    uu[idx] = 1.0 if t[idx] > 0 else -1.0
+    ww = np.cross(t, uu)
+    nww = float(np.sqrt(ww @ ww))
+    if nww > 0:
+        ww = ww * (np.arccos(min(1.0, abs(t[idx]) / float(np.sqrt(t @ t)))) / nww)
+    wr = rodrigues(ww)
+    R1, R2 = wr @ r.T, wr @ r
+    t = R2 @ T
+
+    fc = (A1[idx ^ 1, idx ^ 1] + A2[idx ^ 1, idx ^ 1]) / 2
+    corners = np.array([[0, 0], [w - 1, 0], [0, h - 1], [w - 1, h - 1]], dtype=np.float64)
+    cc = []
+    for A, k8, Rk in ((A1, k1, R1), (A2, k2, R2)):
+        p = _undistort_points(corners, A, k8, Rk) * fc
+        cc.append(np.array([(w - 1) / 2, (h - 1) / 2]) - p.mean(axis=0))
+    mean = (cc[0] + cc[1]) / 2
+    if zero_disparity:
+        cc = [mean.copy(), mean.copy()]
+    else:
+        cc[0][idx ^ 1] = cc[1][idx ^ 1] = mean[idx ^ 1]
+
+    # the scale about the principal points, and the principal points in the new image
+    P0 = [np.array([[fc, 0, c[0]], [0, fc, c[1]], [0, 0, 1.0]]) for c in cc]
+    rects = [_grid_rectangles(A, k8, Rk, Pk, (w, h)) for A, k8, Rk, Pk in ((A1, k1, R1, P0[0]), (A2, k2, R2, P0[1]))]
+    cn = [np.array([c[0] * (nw - 1) / (w - 1) if w > 1 else 0.0, c[1] * (nh - 1) / (h - 1) if h > 1 else 0.0]) for c in cc]
+    if alpha < 0:
+        s = (nw / w) if idx == 1 else (nh / h)
+    else:
+        def fit(rect, c0, c1, pick):
+            x0, y0, x1, y1 = rect
+            with np.errstate(divide="ignore", invalid="ignore"):
+                return pick(c1[0] / (c0[0] - x0), c1[1] / (c0[1] - y0), (nw - 1 - c1[0]) / (x1 - c0[0]), (nh - 1 - c1[1]) / (y1 - c0[1]))
+        s0 = max(fit(rects[k][0], cc[k], cn[k], max) for k in (0, 1))
+        s1 = min(fit(rects[k][1], cc[k], cn[k], min) for k in (0, 1))
+        s = float(s0 * (1 - alpha) + s1 * alpha)
+        if not (np.isfinite(s) and s > 0):
+            raise error("stereoRectify: the undistorted images do not surround their principal points: no scale fits")
+    f = fc * s
+    P1 = np.array([[f, 0, cn[0][0], 0], [0, f, cn[0][1], 0], [0, 0, 1.0, 0]])
+    P2 = np.array([[f, 0, cn[1][0], 0], [0, f, cn[1][1], 0], [0, 0, 1.0, 0]])
+    P2[idx, 3] = t[idx] * f
+    Q = np.array([[1.0, 0, 0, -cn[0][0]], [0, 1.0, 0, -cn[0][1]], [0, 0, 0, f], [0, 0, -1.0 / t[idx], (cn[0][idx] - cn[1][idx]) / t[idx]]])
+    rois = []
+    for k, (A, d, Rk, Pk) in enumerate(((K1, d1, R1, P1), (K2, d2, R2, P2))):
+        x0, y0, x1, y1 = rects[k][0]
+        inside = _taps_inside(A, d, Rk, Pk, (w, h), (nw, nh))
+        rois.append(_valid_roi(inside, (x0 - cc[k][0]) * s + cn[k][0], (y0 - cc[k][1]) * s + cn[k][1], (x1 - cc[k][0]) * s + cn[k][0], (y1 - cc[k][1]) * s + cn[k][1]))
+    return R1, R2, P1, P2, Q, rois[0], rois[1]
+
+
+def reprojection_matrix(focal_px: float, cx: float, cy: float, baseline_m: float, cx_right=None):
+    """Q of a pair that arrives rectified: the left camera's focal length and principal point in pixels, the distance between the
+    cameras in metres, and the right camera's principal column where it differs (a pair rectified without zero disparity).  With it
+    `reproject_to_3d` gives X = (x - cx) Z / f, Y = (y - cy) Z / f, Z = f b / (d - (cx - cx_right)): `depth_from_disparity`'s Z."""
+    focal_px, cx, cy, baseline_m = float(focal_px), float(cx), float(cy), float(baseline_m)
+    cxr = cx if cx_right is None else float(cx_right)
+    if not (np.isfinite(focal_px) and focal_px > 0 and np.isfinite(baseline_m) and baseline_m > 0 and np.isfinite(cx) and np.isfinite(cy) and np.isfinite(cxr)):
+        raise ValueError("focal_px and baseline_m must be finite and positive, the principal point finite")
+    return np.array([[1.0, 0, 0, -cx], [0, 1.0, 0, -cy], [0, 0, 0, focal_px], [0, 0, 1.0 / baseline_m, -(cx - cxr) / baseline_m]])
+
+
+def _table(t, which):
+    from vision.utils.transform import RemapTable
+    if not isinstance(t, RemapTable) or t.nearest or t.frac is None:
+        raise TypeError(f"the {which} table must be a bilinear RemapTable")
+    return t
+
+
+def _rectify_dev(ctx, lptr, lstride, rptr, rstride, w, h, cn, tl, tr, colour):
+    """one launch (vp_rectify_pair_dev) from two device pointers, whose images the caller holds.  -> grey left, grey right[, colour left, right]"""
+    oh, ow = tl.shape
+    if tuple(tr.shape) != (oh, ow):
+        raise ValueError("the two tables must have one size")
+    if max(w, h, ow, oh) > MAX_SIDE:
+        raise ValueError("the images and the tables must be at most 4096 x 4096")
+    grey = [DeviceMat(ctx, (oh, ow), np.uint8) for _ in range(2)]
+    col = [DeviceMat(ctx, (oh, ow) if cn == 1 else (oh, ow, cn), np.uint8) for _ in range(2)] if colour else [None, None]
+    for t in (tl, tr):
+        t.xy.refresh_device(ctx)
+        t.frac.refresh_device(ctx)
+    _vp.check(_vp.lib().vp_rectify_pair_dev(ctx.handle, lptr, lstride, rptr, rstride, w, h, cn, tl.xy.dev_ptr, tl.frac.dev_ptr, tr.xy.dev_ptr, tr.frac.dev_ptr, ow, oh,
+                                            grey[0].dev_ptr, ow, grey[1].dev_ptr, ow, None if col[0] is None else col[0].dev_ptr, ow * cn,
+                                            None if col[1] is None else col[1].dev_ptr, ow * cn), ctx.handle)
+    return tuple(grey) + (tuple(col) if colour else ())
+
+
+def _raw_eye(mat, which):
+    mat, cn = image_source(mat, max_side=MAX_SIDE)
+    if cn not in (1, 3, 4):
+        raise ValueError(f"the {which} image must have 1, 3 (BGR) or 4 (BGRA) channels")
+    return mat, cn
+
+
+def rectify_pair(left, right, table_left, table_right, colour: bool = False):
+    """Both raw eyes of a stereo camera to the matcher's inputs in one launch (libvp vp_rectify_pair_dev): (grey_left, grey_right), or
+    with colour=True (grey_left, grey_right, colour_left, colour_right).  left, right: uint8 images of one size and 1, 3 (BGR) or 4
+    (BGRA) channels; the tables: bilinear RemapTables of one size (`StereoRig` builds them).  Each colour result is
+    `table.apply(eye)`; each grey result is cv2's BGR2GRAY / BGRA2GRAY of that colour result (the colour result itself for one
+    channel), byte for byte.  numpy in gives numpy out; if either image is a DeviceMat the results are DeviceMats that stay in HBM."""
+    tl, tr = _table(table_left, "left"), _table(table_right, "right")
+    (left, cn), (right, cnr) = _raw_eye(left, "left"), _raw_eye(right, "right")
+    if tuple(left.shape) != tuple(right.shape) or cn != cnr:
+        raise ValueError("the left and right images must have one size and one channel count")
+    on_device = isinstance(left, DeviceMat) or isinstance(right, DeviceMat)
+    ctx = _vp.default_context()
+    h, w = left.shape[:2]
+    up = []
+    try:
+        dl, dr = device_image(ctx, left, 0, pending=up), device_image(ctx, right, 0, pending=up)
+        out = _rectify_dev(ctx, dl.dev_ptr, w * cn, dr.dev_ptr, w * cn, w, h, cn, tl, tr, colour)
+    finally:
+        finish_uploads(ctx, up)
+    return out if on_device else tuple(m.host() for m in out)
+
+
+def _reproject_args(disp, Q, invalid):
+    if not isinstance(disp, (np.ndarray, DeviceMat)) or disp.dtype not in (np.dtype(np.int16), np.dtype(np.float32)) or len(disp.shape) != 2 or 0 in disp.shape:
+        raise TypeError("expected a non-empty int16 or float32 (h, w) disparity image")
+    if max(disp.shape) > MAX_SIDE:
+        raise ValueError("the disparity image must be at most 4096 x 4096")
+    q = np.ascontiguousarray(np.asarray(Q, dtype=np.float64))
+    if q.shape != (4, 4) or not (np.abs(q) <= 1e100).all():
+        raise ValueError("Q must be a finite 4x4 matrix with entries of at most 1e100 in magnitude")
+    kind = DISP_I16 if disp.dtype == np.int16 else DISP_F32
+    if invalid is None:
+        invalid = _INT_MIN
+    elif kind == DISP_F32:
+        raise ValueError("invalid= belongs to int16 disparities: a float32 disparity without an answer is NaN or infinite")
+    else:
+        invalid = _int_in("invalid", invalid, -32768, 32767)
+    return q, kind, invalid
+
+
+def _reproject_dev(ctx, disp, q, kind, invalid):
+    h, w = disp.shape
+    out = DeviceMat(ctx, (h, w, 3), np.float32)
+    _vp.check(_vp.lib().vp_reproject_to_3d_dev(ctx.handle, disp.dev_ptr, disp.itemsize * w, kind, w, h, q.ctypes.data, invalid, out.dev_ptr, 12 * w), ctx.handle)
+    return out
+
+
+def reproject_to_3d(disp, Q, invalid=None):
+    """cv2.reprojectImageTo3D by this library's conventions: the float32 (h, w, 3) points (X / W, Y / W, Z / W) of
+    (X, Y, Z, W) = Q (x, y, d, 1), in double with one rounding per operation, bit for bit as tests/rectify_restate.py states it.
+    disp: int16 sixteenths of a pixel, as the matchers return them (d = value / 16), or float32 pixels.  Three zeros - the `depth`
+    plane's "unknown" - where an int16 pixel equals `invalid` (`invalid_disparity(min_disparity)` for a matcher's result; None: no such
+    value), where W is 0 and where a float32 disparity is not finite.  numpy in gives numpy out, a DeviceMat a DeviceMat."""
+    q, kind, invalid = _reproject_args(disp, Q, invalid)
+    ctx = _vp.default_context()
+    if isinstance(disp, DeviceMat):
+        disp.refresh_device(ctx)
+        return _reproject_dev(ctx, disp, q, kind, invalid)
+    disp = np.ascontiguousarray(disp)
+    h, w = disp.shape
+    out = np.empty((h, w, 3), np.float32)
+    if kind == DISP_I16:
+        _vp.check(_vp.lib().vp_reproject_to_3d_i16(ctx.handle, disp.ctypes.data, w, h, q.ctypes.data, invalid, out.ctypes.data), ctx.handle)
+    else:
+        _vp.check(_vp.lib().vp_reproject_to_3d_f32(ctx.handle, disp.ctypes.data, w, h, q.ctypes.data, out.ctypes.data), ctx.handle)
+    return out
+
+
+class StereoRig:
+    """A calibrated stereo pair, built once: `stereo_rectify`'s R1 R2 P1 P2 Q roi1 roi2, the rectified focal_px, cx, cy and the
+    baseline_m = |T|, and the two RemapTables (initUndistortRectifyMap with R1 / P1 and R2 / P2) in HBM.  Its methods take raw frames -
+    two images, or one side-by-side frame of width 2 * size[0], which is split by pointer and not copied - and run the existing chain on
+    them; everything between the raw frame and the last result stays in HBM.  A DeviceMat in gives DeviceMats out, numpy gives numpy.
+    Rectified with zero disparity, so depth = focal_px * baseline_m / disparity holds; a vertical rig (|T.y| largest after the
+    half rotation) is refused: the matchers search along rows."""
+    _MATCHERS = {"bm": (_disparity_dev, _matcher), "sgm": (_disparity_sgm_dev, _matcher_sgm)}
+
+    def __init__(self, K1, d1, K2, d2, size, R, T, alpha: float = 0, new_size=None):
+        from vision.utils import transform as _transform
+        self.size = (int(size[0]), int(size[1]))
+        self.new_size = self.size if new_size is None else (int(new_size[0]), int(new_size[1]))
+        self.R1, self.R2, self.P1, self.P2, self.Q, self.roi1, self.roi2 = stereo_rectify(K1, d1, K2, d2, self.size, R, T, True, alpha, self.new_size)
+        if self.P2[0, 3] == 0:
+            raise ValueError("a vertical rig: the matchers search along rows")
+        if max(self.size + self.new_size) > MAX_SIDE:
+            raise ValueError("the raw and the rectified images must be at most 4096 x 4096")
+        self.focal_px, self.cx, self.cy = float(self.P1[0, 0]), float(self.P1[0, 2]), float(self.P1[1, 2])
+        self.baseline_m = float(abs(self.P2[0, 3]) / self.focal_px)
+        self.tables = []
+        for K, d, Rk, Pk in ((K1, d1, self.R1, self.P1), (K2, d2, self.R2, self.P2)):
+            u, v = _transform._undistort_coords("initUndistortRectifyMap", K, d, Rk, Pk, self.new_size)
+            self.tables.append(_transform.RemapTable(u.astype(np.float32), v.astype(np.float32)))
+
+    def rectify(self, left, right=None, colour: bool = False):
+        """`rectify_pair` with the rig's tables; right=None: `left` is a side-by-side frame (left eye first)."""
+        if right is not None:
+            (left, _), (right, _) = _raw_eye(left, "left"), _raw_eye(right, "right")
+            if tuple(left.shape[:2]) != self.size[::-1] or tuple(right.shape[:2]) != self.size[::-1]:
+                raise ValueError("the images do not have the rig's size")
+            return rectify_pair(left, right, self.tables[0], self.tables[1], colour)
+        frame, cn = _raw_eye(left, "side-by-side")
+        w, h = self.size
+        if tuple(frame.shape[:2]) != (h, 2 * w):
+            raise ValueError("a side-by-side frame is twice the rig's width")
+        ctx = _vp.default_context()
+        up = []
+        try:
+            dev = device_image(ctx, frame, 0, pending=up)
+            out = _rectify_dev(ctx, dev.dev_ptr, 2 * w * cn, dev.dev_ptr + w * cn, 2 * w * cn, w, h, cn, self.tables[0], self.tables[1], colour)
+        finally:
+            finish_uploads(ctx, up)
+        return out if isinstance(frame, DeviceMat) else tuple(m.host() for m in out)
+
+    def _matched(self, left, right, matcher, args):
+        """(match_dev, checked parameters, rectified grey DeviceMats, results stay on the device)"""
+        if matcher not in self._MATCHERS:
+            raise ValueError('matcher must be "bm" or "sgm"')
+        match_dev, check = self._MATCHERS[matcher]
+        params = check(**args)
+        on_device = isinstance(left, DeviceMat) or isinstance(right, DeviceMat)
+        as_dev = lambda m: m if isinstance(m, DeviceMat) else DeviceMat.from_host(_vp.default_context(), m)
+        gl, gr = self.rectify(as_dev(left), None if right is None else as_dev(right))
+        if matcher == "sgm":
+            gl, gr = _sgm_pair(gl, gr, params)
+        return match_dev, params, gl, gr, on_device
+
+    def disparity(self, left, right=None, matcher: str = "bm", **matcher_args):
+        """`disparity` (matcher="bm") or `disparity_sgm` ("sgm") of the rectified pair: int16, 16 times the disparity."""
+        match_dev, params, gl, gr, on_device = self._matched(left, right, matcher, matcher_args)
+        out = match_dev(_vp.default_context(), gl, gr, params)
+        return out if on_device else out.host()
+
+    def depth(self, left, right=None, matcher: str = "bm", **matcher_args):
+        """`stereo_depth` / `stereo_depth_sgm` of the rectified pair with the rig's focal length and baseline: float32 metres."""
+        match_dev, params, gl, gr, on_device = self._matched(left, right, matcher, matcher_args)
+        out = _depth_chain(match_dev, params, gl, gr, self.focal_px, self.baseline_m)
+        return out if on_device else out.host()
+
+    def planes(self, left, right=None, matcher: str = "bm", speckle_window_size: int = 100, speckle_range: int = 2, max_jump_m=None, **matcher_args):
+        """`stereo_planes` / `stereo_planes_sgm` of the rectified pair with the rig's focal_px, cx, cy and baseline_m: (depth, normal)."""
+        match_dev, params, gl, gr, on_device = self._matched(left, right, matcher, matcher_args)
+        out = _planes_chain(match_dev, params, gl, gr, self.focal_px, self.baseline_m, self.cx, self.cy, speckle_window_size, speckle_range, max_jump_m)
+        return out if on_device else tuple(m.host() for m in out)
+
+    def points(self, disp, min_disparity: int = 0):
+        """`reproject_to_3d` of a matcher's int16 result with the rig's Q and the matcher's invalid value: float32 (h, w, 3) metres in
+        the rectified left camera's frame.  A float32 disparity image has no invalid value."""
+        invalid = invalid_disparity(min_disparity) if getattr(disp, "dtype", None) == np.int16 else None
+        return reproject_to_3d(disp, self.Q, invalid)

@@ -1167,6 +1167,48 @@ int vp_stereo_sgm_dev(vp_ctx* ctx, const uint8_t* left_dev, size_t left_stride, 
 int vp_stereo_sgm_host(const uint8_t* left, size_t left_stride, const uint8_t* right, size_t right_stride, int w, int h, int num_disparities, int block_size,
                        int min_disparity, int pre_filter_cap, int p1, int p2, int uniqueness_ratio, int disp12_max_diff, int paths, int16_t* disp, size_t disp_stride);
 
+/* ---- stereo rectification and 3-D reprojection: the head and the tail of the stereo stack ------------------
+ * vp_rectify_pair_*: both eyes of a raw frame to what the matchers read, in one launch.  left and right: uint8 images of w x h pixels
+ *   and cn channels - 1, 3 (BGR) or 4 (BGRA) - each with its own stride, so the two halves of a side-by-side frame are two pointers
+ *   into one buffer and nothing is copied.  The tables are the fixed form of cv2.convertMaps for INTER_LINEAR, out_w x out_h entries,
+ *   packed: xy int16 x 2 and frac uint16 (what vp_convert_maps_dev writes).  Byte for byte against tests/rectify_restate.py:
+ *     each colour result = vp_remap_fixed_dev(eye, table, VP_INTER_LINEAR, VP_BORDER_CONSTANT, 0): every channel interpolated and
+ *       rounded (sum + 2^14) >> 15; a tap outside [0, w) x [0, h) of its own eye is 0, whatever lies beside the eye in memory;
+ *     each grey result = vp_cvt_color_dev(VP_BGR2GRAY / VP_BGRA2GRAY) of that rounded colour result, (B 1868 + G 9617 + R 4899 + 8192)
+ *       >> 14; with cn = 1 it is the remapped image itself.
+ *   A colour result that is NULL is not written and costs no traffic.  No workspace.
+ * vp_rectify_pair_plan: no device, no context.  geometry[6]: tile columns, tile rows, pixels per lane, grid x, grid y, grid z (the eyes).
+ * vp_reproject_to_3d_*: (X, Y, Z, W) = Q (x, y, d, 1) per pixel of a disparity image in double, each row ((q0 x + q1 y) + q2 d) + q3
+ *   with one rounding per product and sum, then X / W, Y / W, Z / W as double quotients rounded once more to float32: an (h, w, 3)
+ *   float32 image, bit for bit against tests/rectify_restate.py.  disp_type VP_DISP_I16: int16 sixteenths of a pixel, as the matchers
+ *   write them (d = value / 16); VP_DISP_F32: float32 pixels.  q16: the 4 x 4 matrix, row-major doubles in host memory; it travels as a
+ *   kernel argument.  Three zeros - the library's "unknown", as in vp_depth_from_disparity_* - where the pixel equals invalid_disp
+ *   (int16 images; INT_MIN: no such value), where W == 0 and where a float32 disparity is not finite.
+ * _u8 / _i16 / _f32: packed host images (and host tables) in and out, synchronises.  _dev: device images with strides in bytes,
+ *   enqueued.  _host: the same statements as scalar C++, host images with strides, no device and no context.
+ * Refused with VP_ERR_INVALID before anything is launched or written (the message names the reason): a missing source, table, grey
+ *   result, disparity, Q or result; a width or height outside 1..4096; cn outside {1, 3, 4}; a stride below the row or, for int16 and
+ *   float32 images, no multiple of the element size; a misaligned table, int16 or float32 image; any result that overlaps a source,
+ *   a table or another result; a Q that is not finite or has an entry above 1e100 in magnitude; an unknown disp_type; an invalid_disp
+ *   that is neither INT_MIN nor an int16 value, or that is given with a float32 image. */
+enum { VP_DISP_I16 = 0, VP_DISP_F32 = 1 };
+int vp_rectify_pair_plan(int w, int h, int cn, int out_w, int out_h, int32_t* geometry);
+int vp_rectify_pair_dev(vp_ctx* ctx, const uint8_t* left_dev, size_t left_stride, const uint8_t* right_dev, size_t right_stride, int w, int h, int cn,
+                        const int16_t* xy_left_dev, const uint16_t* frac_left_dev, const int16_t* xy_right_dev, const uint16_t* frac_right_dev, int out_w, int out_h,
+                        uint8_t* grey_left_dev, size_t grey_left_stride, uint8_t* grey_right_dev, size_t grey_right_stride, uint8_t* colour_left_dev,
+                        size_t colour_left_stride, uint8_t* colour_right_dev, size_t colour_right_stride);
+int vp_rectify_pair_u8(vp_ctx* ctx, const uint8_t* left, const uint8_t* right, int w, int h, int cn, const int16_t* xy_left, const uint16_t* frac_left,
+                       const int16_t* xy_right, const uint16_t* frac_right, int out_w, int out_h, uint8_t* grey_left, uint8_t* grey_right, uint8_t* colour_left,
+                       uint8_t* colour_right);
+int vp_rectify_pair_host(const uint8_t* left, size_t left_stride, const uint8_t* right, size_t right_stride, int w, int h, int cn, const int16_t* xy_left,
+                         const uint16_t* frac_left, const int16_t* xy_right, const uint16_t* frac_right, int out_w, int out_h, uint8_t* grey_left, size_t grey_left_stride,
+                         uint8_t* grey_right, size_t grey_right_stride, uint8_t* colour_left, size_t colour_left_stride, uint8_t* colour_right, size_t colour_right_stride);
+int vp_reproject_to_3d_dev(vp_ctx* ctx, const void* disp_dev, size_t disp_stride, int disp_type, int w, int h, const double* q16, int invalid_disp, float* xyz_dev,
+                           size_t xyz_stride);
+int vp_reproject_to_3d_i16(vp_ctx* ctx, const int16_t* disp, int w, int h, const double* q16, int invalid_disp, float* xyz);
+int vp_reproject_to_3d_f32(vp_ctx* ctx, const float* disp, int w, int h, const double* q16, float* xyz);
+int vp_reproject_to_3d_host(const void* disp, size_t disp_stride, int disp_type, int w, int h, const double* q16, int invalid_disp, float* xyz, size_t xyz_stride);
+
 /* ---- device memory helpers (so a host program needs no HIP binding of its own) --------- */
 int vp_dev_alloc(vp_ctx* ctx, size_t bytes, void** dev_ptr);
 int vp_dev_free(vp_ctx* ctx, void* dev_ptr);    /* ctx may be NULL (memory that outlived its context) */
