@@ -58,6 +58,8 @@ DIST_L1, DIST_L2, DIST_C = 1, 2, 3
 TM_SQDIFF, TM_SQDIFF_NORMED, TM_CCORR, TM_CCORR_NORMED, TM_CCOEFF, TM_CCOEFF_NORMED = 0, 1, 2, 3, 4, 5
 WARP_INVERSE_MAP = 16
 MODEL_SIMILARITY, MODEL_AFFINE, MODEL_HOMOGRAPHY = 0, 1, 2
+PLANE_PERP, PLANE_ALONG_Z = 0, 1
+PLANE_RESULT, PLANE_COUNTS = 12, 4
 PROF_KERNELS = 18
 
 
@@ -379,6 +381,15 @@ _SIGS = {
     "vp_reproject_to_3d_i16": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_void_p]),
     "vp_reproject_to_3d_f32": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
     "vp_reproject_to_3d_host": (C.c_int, [C.c_void_p, C.c_size_t, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_size_t]),
+    "vp_fit_plane_plan": (C.c_int, [C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "vp_fit_plane_dev": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_size_t, C.c_int, C.c_double, C.c_int, C.c_double,
+                                   C.c_uint32, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p]),
+    "vp_fit_plane_f32": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_double, C.c_int, C.c_double, C.c_uint32, C.c_void_p,
+                                   C.c_void_p, C.c_void_p]),
+    "vp_fit_plane_host": (C.c_int, [C.c_void_p, C.c_size_t, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_size_t, C.c_int, C.c_double, C.c_int, C.c_double, C.c_uint32,
+                                    C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p]),
+    "vp_plane_hypothesis": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_uint32, C.c_int, C.c_void_p, C.c_void_p]),
+    "vp_plane_refit": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p]),
 }
 
 

@@ -20,8 +20,14 @@ algorithm in the shape of cv2.stereoRectify, host float64, the library's own sta
 matcher's grey pair in one launch, byte for byte as tests/rectify_restate.py states it, `reproject_to_3d` makes XYZ points of a
 disparity image, bit for bit, and `StereoRig` ties a calibration to the chain: from one raw side-by-side frame to `depth`, `normal`
 and points, everything in HBM.
+
+The quantity a mission consumes (libvp vp_plane.hip): `fit_plane` finds one plane through the usable points
+of an image by RANSAC - normal, distance, inlier count and inlier mask - bit for bit as tests/plane_restate.py states the search;
+`fit_planes` peels several; `StereoRig.fit_plane` searches in disparity space, where stereo noise is uniform, and answers in metres;
+`plane_distance` and `plane_angles` read a result.
 """
 import ctypes as C
+import dataclasses
 
 import numpy as np
 
@@ -768,3 +774,196 @@ class StereoRig:
         the rectified left camera's frame.  A float32 disparity image has no invalid value."""
         invalid = invalid_disparity(min_disparity) if getattr(disp, "dtype", None) == np.int16 else None
         return reproject_to_3d(disp, self.Q, invalid)
+
+    def fit_plane(self, disp, box=None, mask=None, space: str = "disparity", threshold=None, min_disparity: int = 0, **search):
+        """One plane through the surface a disparity image shows inside `box` / `mask` (`fit_plane`'s arguments; **search: max_iters,
+        confidence, seed, return_mask) -> PlaneFit in metres, in the rectified left camera's frame.
+        space="disparity" (the default): the search runs on the points (x, y, d) - the pixel and its disparity - with the residual
+        taken along d and `threshold` in pixels of disparity (default 0.5): stereo noise is uniform there, while in metres it grows
+        with Z squared, and a plane in space is a plane in (x, y, d) too.  The plane found, a row vector pi, is carried to the metric
+        frame as pi Q^-1 (host float64), normalised and oriented towards the camera; `centroid` is carried through Q.  `hypothesis`
+        stays in disparity space, as the search left it, and `rms` stays in pixels of disparity.  A pixel with x = y = d = 0 counts
+        as unknown.
+        space="metric": `fit_plane` on `self.points(disp)`, `threshold` in metres (default 0.02)."""
+        if space == "metric":
+            return fit_plane(self.points(disp, min_disparity), box, mask, 0.02 if threshold is None else threshold, along_z=False, **search)
+        if space != "disparity":
+            raise ValueError('space must be "disparity" or "metric"')
+        invalid = invalid_disparity(min_disparity) if getattr(disp, "dtype", None) == np.int16 else None
+        fit = fit_plane(reproject_to_3d(disp, np.eye(4), invalid), box, mask, 0.5 if threshold is None else threshold, along_z=True, **search)
+        if not fit.found:
+            return fit
+        pi = np.append(fit.normal, fit.d) @ np.linalg.inv(self.Q)
+        pi = pi / np.linalg.norm(pi[:3])
+        if pi[3] < 0:
+            pi = -pi
+        c = self.Q @ np.append(fit.centroid, 1.0)
+        return dataclasses.replace(fit, normal=pi[:3], d=float(pi[3]), centroid=c[:3] / c[3])
+
+
+# ---- planes through 3-D points (libvp vp_plane.hip; DESIGN.md section 4.38) ------------------------------------------------------------
+PLANE_MAX_ITERS = 65536
+
+
+@dataclasses.dataclass
+class PlaneFit:
+    """What `fit_plane` found: the plane normal . P + d = 0 with |normal| = 1 and d > 0 (the normal points from the surface towards
+    the camera's side, d is the camera's distance from the plane).  found False: no plane; everything else is zero then."""
+    found: bool
+    normal: np.ndarray          # (3,) float64, the least-squares refit over the inliers
+    d: float
+    hypothesis: np.ndarray      # (4,) float64, the best three-point hypothesis of the search (bit for bit the statement's)
+    centroid: np.ndarray        # (3,) float64, the inliers' mean
+    rms: float                  # root mean square residual of the inliers from the refit plane
+    inliers: int
+    usable: int                 # points the search saw
+    hypotheses: int             # hypotheses taken
+    mask: object = None         # with return_mask: uint8 (h, w), 255 at every inlier; numpy for numpy in, a DeviceMat for a DeviceMat
+
+
+def _plane_points(points):
+    """the (h, w, 3) float32 image the library reads: an image as it is, (n, 3) points laid into rows of at most 4096, padded with zero triples"""
+    if not isinstance(points, (np.ndarray, DeviceMat)) or points.dtype != np.float32 or len(points.shape) not in (2, 3) or points.shape[-1] != 3 or 0 in points.shape:
+        raise TypeError("expected float32 points: an (h, w, 3) image or an (n, 3) array")
+    if len(points.shape) == 3:
+        if max(points.shape[:2]) > MAX_SIDE:
+            raise ValueError("fit plane: the image must be 1 to 4096 pixels wide and high")
+        return points, None
+    n = points.shape[0]
+    if n > MAX_SIDE * MAX_SIDE:
+        raise ValueError("fit plane: at most 4096 x 4096 points")
+    w = min(n, MAX_SIDE)
+    h = (n + w - 1) // w
+    flat = points.host_copy() if isinstance(points, DeviceMat) else points
+    img = np.zeros((h * w, 3), np.float32)
+    img[:n] = flat
+    return img.reshape(h, w, 3), n
+
+
+def _plane_args(shape, box, mask, threshold, max_iters, confidence, seed):
+    h, w = shape[:2]
+    if box is not None:
+        box = np.array([_int_in("box", v, -2 ** 31, 2 ** 31 - 1) for v in box], np.int32)
+        if box.shape != (4,):
+            raise ValueError("box must be (x0, y0, width, height)")
+        if box[2] < 1 or box[3] < 1:
+            raise ValueError("fit plane: the box is empty")
+        if box[0] < 0 or box[1] < 0 or box[0] > w - box[2] or box[1] > h - box[3]:
+            raise ValueError("fit plane: the box leaves the image")
+    if mask is not None and (not isinstance(mask, (np.ndarray, DeviceMat)) or mask.dtype != np.uint8 or tuple(mask.shape) != (h, w)):
+        raise TypeError("the mask must be a uint8 image of the points' size")
+    threshold, confidence = float(threshold), float(confidence)
+    if not (np.isfinite(threshold) and threshold > 0):
+        raise ValueError("fit plane: the threshold must be finite and above 0")
+    max_iters = _int_in("max_iters", max_iters, -2 ** 31, 2 ** 31 - 1)
+    if not 1 <= max_iters <= PLANE_MAX_ITERS:
+        raise ValueError("fit plane: max_iters must be 1 to 65536")
+    if not 0 < confidence < 1:
+        raise ValueError("fit plane: the confidence must be above 0 and below 1")
+    return box, threshold, max_iters, confidence, _int_in("seed", seed, 0, 2 ** 32 - 1)
+
+
+def _fit_plane_dev(ctx, pts, box, mask, metric, threshold, max_iters, confidence, seed, want_mask):
+    """vp_fit_plane_dev on DeviceMats -> (result (12,), counts (4,), inlier DeviceMat or None)"""
+    h, w = pts.shape[:2]
+    out = DeviceMat(ctx, (h, w), np.uint8, binary=True) if want_mask else None
+    result, counts = np.zeros(_vp.PLANE_RESULT, np.float64), np.zeros(_vp.PLANE_COUNTS, np.int32)
+    _vp.check(_vp.lib().vp_fit_plane_dev(ctx.handle, pts.dev_ptr, 12 * w, w, h, None if box is None else box.ctypes.data, None if mask is None else mask.dev_ptr, w,
+                                         metric, threshold, max_iters, confidence, seed, None if out is None else out.dev_ptr, w, result.ctypes.data,
+                                         counts.ctypes.data), ctx.handle)
+    return result, counts, out
+
+
+def _plane_fit(result, counts, mask):
+    return PlaneFit(found=bool(counts[3] >= 0), normal=result[0:3].copy(), d=float(result[3]), hypothesis=result[4:8].copy(), centroid=result[8:11].copy(),
+                    rms=float(result[11]), inliers=int(counts[1]), usable=int(counts[0]), hypotheses=int(counts[2]), mask=mask)
+
+
+def fit_plane(points, box=None, mask=None, threshold: float = 0.02, max_iters: int = 1000, confidence: float = 0.99, seed: int = 0, along_z: bool = False,
+              return_mask: bool = False):
+    """One plane through the usable 3-D points of an image, by RANSAC on the GPU (libvp vp_fit_plane_*; the statement:
+    tests/plane_restate.py) -> PlaneFit.  points: float32 (h, w, 3), as `reproject_to_3d` and `StereoRig.points` give them - a
+    pixel whose three floats are zero (the library's "unknown") or not finite is skipped - or an (n, 3) array.  box (x0, y0, width,
+    height) and mask (uint8 (h, w), numpy or DeviceMat, non-zero where a pixel may be used) select the pixels.  threshold: the
+    largest distance of an inlier from the plane, in the points' unit; along_z: the distance is taken along the third axis instead of
+    perpendicularly (points whose noise lives in the third coordinate, such as (x, y, disparity)).  The search is a pure function of
+    its arguments and `seed`.  return_mask: PlaneFit.mask is the inlier image - numpy for numpy points, a DeviceMat for a DeviceMat,
+    (h, w) of the image, or (n,) for an (n, 3) array."""
+    img, n = _plane_points(points)
+    if n is not None and (box is not None or mask is not None):
+        raise ValueError("box and mask belong to an image of points")
+    box, threshold, max_iters, confidence, seed = _plane_args(img.shape, box, mask, threshold, max_iters, confidence, seed)
+    metric = _vp.PLANE_ALONG_Z if along_z else _vp.PLANE_PERP
+    ctx = _vp.default_context()
+    on_device = isinstance(points, DeviceMat) and n is None
+    if on_device or isinstance(mask, DeviceMat):
+        up = []
+        try:
+            if isinstance(img, DeviceMat):
+                img.refresh_device(ctx)
+            dp = img if isinstance(img, DeviceMat) else DeviceMat.from_host(ctx, np.ascontiguousarray(img), pending=up)
+            dm = None if mask is None else device_image(ctx, mask, 1, pending=up)
+            if isinstance(dm, DeviceMat):
+                dm.refresh_device(ctx)
+            result, counts, out = _fit_plane_dev(ctx, dp, box, dm, metric, threshold, max_iters, confidence, seed, return_mask)
+        finally:
+            finish_uploads(ctx, up)
+        if out is not None and not on_device:
+            out = out.host()
+        return _plane_fit(result, counts, out)
+    h, w = img.shape[:2]
+    img = np.ascontiguousarray(img)
+    mask = None if mask is None else np.ascontiguousarray(mask)
+    out = np.empty((h, w), np.uint8) if return_mask else None
+    result, counts = np.zeros(_vp.PLANE_RESULT, np.float64), np.zeros(_vp.PLANE_COUNTS, np.int32)
+    _vp.check(_vp.lib().vp_fit_plane_f32(ctx.handle, img.ctypes.data, w, h, None if box is None else box.ctypes.data, None if mask is None else mask.ctypes.data, metric,
+                                         threshold, max_iters, confidence, seed, None if out is None else out.ctypes.data, result.ctypes.data, counts.ctypes.data),
+              ctx.handle)
+    if out is not None and n is not None:
+        out = out.reshape(-1)[:n]
+    return _plane_fit(result, counts, out)
+
+
+def fit_planes(points, k: int, min_inliers: int, box=None, mask=None, **search):
+    """Up to k planes, largest first as the search finds them: after each `fit_plane` its inliers leave the candidate mask
+    (candidates & ~inliers, with the device mask operators: no image visits the host), and the next fit sees the rest.  Stops at the
+    first fit that finds no plane or fewer than min_inliers inliers; that fit is not returned.  points: an (h, w, 3) image, numpy or
+    DeviceMat; every PlaneFit carries its mask, numpy for numpy points and a DeviceMat for a DeviceMat.  **search: `fit_plane`'s
+    threshold, max_iters, confidence, seed, along_z."""
+    from vision.devmat import bitwise
+    k, min_inliers = _int_in("k", k, 1, 1024), _int_in("min_inliers", min_inliers, 3, 2 ** 31 - 1)
+    search.pop("return_mask", None)
+    img, n = _plane_points(points)
+    if n is not None:
+        raise ValueError("fit_planes takes an (h, w, 3) image of points")
+    ctx = _vp.default_context()
+    on_device = isinstance(points, DeviceMat)
+    dp = points if on_device else DeviceMat.from_host(ctx, np.ascontiguousarray(img))
+    h, w = img.shape[:2]
+    if mask is None:
+        cand = DeviceMat.from_host(ctx, np.full((h, w), 255, np.uint8), binary=True)
+    else:
+        _plane_args(img.shape, box, mask, 1.0, 1, 0.5, 0)
+        cand = mask if isinstance(mask, DeviceMat) else DeviceMat.from_host(ctx, np.ascontiguousarray(mask))
+    fits = []
+    for _ in range(k):
+        fit = fit_plane(dp, box, cand, return_mask=True, **search)
+        if not fit.found or fit.inliers < min_inliers:
+            break
+        cand = bitwise(_vp.BITWISE_AND, cand, bitwise(_vp.BITWISE_NOT, fit.mask))
+        fits.append(fit if on_device else dataclasses.replace(fit, mask=fit.mask.host()))
+    return fits
+
+
+def plane_distance(fit, point):
+    """Signed distance of a point (or an (n, 3) array of points) from a PlaneFit's plane, positive on the camera's side; host float64."""
+    p = np.asarray(point, np.float64)
+    return p @ np.asarray(fit.normal, np.float64) + float(fit.d)
+
+
+def plane_angles(fit):
+    """(yaw, pitch) in radians of the direction the surface faces, -normal seen from the camera, against the optical axis +Z: yaw about
+    the vertical axis (positive: the surface is turned towards +X), pitch about the horizontal one (positive: towards +Y); both 0 for
+    a surface that faces the camera squarely.  Host float64."""
+    n = -np.asarray(fit.normal, np.float64)
+    return float(np.arctan2(n[0], n[2])), float(np.arctan2(n[1], np.hypot(n[0], n[2])))

@@ -1209,6 +1209,50 @@ int vp_reproject_to_3d_i16(vp_ctx* ctx, const int16_t* disp, int w, int h, const
 int vp_reproject_to_3d_f32(vp_ctx* ctx, const float* disp, int w, int h, const double* q16, float* xyz);
 int vp_reproject_to_3d_host(const void* disp, size_t disp_stride, int disp_type, int w, int h, const double* q16, int invalid_disp, float* xyz, size_t xyz_stride);
 
+/* ---- robust plane fitting to the 3-D points of an image: where a surface is and which way it faces ----------
+ * RANSAC for one plane n.P + d = 0 over the usable points of an XYZ image (float32, three floats a pixel, rows of xyz_stride bytes, as
+ * vp_reproject_to_3d_* writes it).  The contract is the statement tests/plane_restate.py, reproduced bit for bit in the best hypothesis,
+ * its index, the counts and the inlier image.  A pixel is a candidate inside box (x0, y0, rw, rh; NULL: the image) where the mask byte
+ * (mask NULL: none) is not 0; a candidate is usable when its three floats are finite and not all three zero.  The points are the
+ * usable candidates in raster order.  Hypothesis j draws three distinct point indices from the counter-based sampler of
+ * vp_estimate_model_* (seed, j); the plane through them is formed in double in one written order and oriented towards the camera
+ * (d > 0); void: a sample whose angle has a sine below 1e-6, a plane through the origin, a number that is not finite, and with
+ * VP_PLANE_ALONG_Z a normal with |n2| <= 1e-6.  e = ((n0 x + n1 y) + n2 z) + d; inlier iff e e <= t t (VP_PLANE_PERP) or
+ * e e <= (t t) (n2 n2) (VP_PLANE_ALONG_Z: the residual is taken along the third axis, which is what a disparity image needs).  The
+ * score is the integer inlier count, ties go to the lowest j; rounds and the stop rule are those of vp_estimate_model_* for a sample of
+ * three; with fewer than three points nothing is searched.
+ * result (VP_PLANE_RESULT doubles): the refit plane (4), the best hypothesis (4), the inliers' centroid (3), the rms residual.  The
+ *   refit is the smallest eigenvector of the inliers' scatter (PERP) or the regression of z on x and y (ALONG_Z), closed on the host
+ *   from ten sums the device adds in a free order: it is not bit-exact by design; a degenerate refit repeats the best hypothesis.
+ * counts (VP_PLANE_COUNTS): usable points, inliers, hypotheses taken, index of the best hypothesis.  No model: result is zeros,
+ *   counts[1] is 0, counts[3] is -1 and the inlier image is zeros.
+ * inliers (nullable): uint8 w x h, 255 at the pixel of every inlier and 0 elsewhere; bytes between rows are left alone.
+ * vp_fit_plane_dev reads device images and writes a device image; it enqueues every launch, the number of points never leaves the
+ *   device before the end, and it synchronises once to hand back result and counts.  vp_fit_plane_f32 stages host images (rows
+ *   packed).  vp_fit_plane_host is the same statement as a host loop: host images with strides, no device, no context.
+ * vp_fit_plane_plan: the workspace a call on this image and box reserves at most, and geometry[8]: the compaction's run length, the
+ *   points a scoring block stages, the hypotheses a scoring block tests, the block size, the round size, the candidates of the box,
+ *   the compaction's blocks, the scoring grid's chunks.
+ * vp_plane_hypothesis: hypothesis j over n packed points (x, y, z, one float that is ignored) as the kernel forms it - sample3 and
+ *   plane4; returns 1, or 0 for a void hypothesis (zeros).  vp_plane_refit: the refit alone over the packed points whose keep byte is
+ *   not 0 (keep NULL: all), its sums taken about the first kept point in index order; returns 1, or 0 (zeros) when it is degenerate.
+ * Refused with VP_ERR_INVALID before anything is launched or written (the message names the reason): a missing xyz, result or counts;
+ *   w or h outside 1..4096; a box that is empty or leaves the image; a stride below the row; an xyz stride that is no multiple of 4; a
+ *   misaligned xyz; an unknown metric; a threshold that is not finite and above 0; max_iters outside 1..65536; a confidence outside
+ *   (0, 1); a hypothesis index outside 0..65535; an inlier image that overlaps xyz or the mask. */
+enum { VP_PLANE_PERP = 0, VP_PLANE_ALONG_Z = 1 };
+#define VP_PLANE_RESULT 12
+#define VP_PLANE_COUNTS 4
+int vp_fit_plane_plan(int w, int h, const int32_t* box, size_t* ws_bytes, int32_t* geometry);
+int vp_fit_plane_dev(vp_ctx* ctx, const float* xyz_dev, size_t xyz_stride, int w, int h, const int32_t* box, const uint8_t* mask_dev, size_t mask_stride, int metric,
+                     double threshold, int max_iters, double confidence, uint32_t seed, uint8_t* inliers_dev, size_t inliers_stride, double* result, int32_t* counts);
+int vp_fit_plane_f32(vp_ctx* ctx, const float* xyz, int w, int h, const int32_t* box, const uint8_t* mask, int metric, double threshold, int max_iters, double confidence,
+                     uint32_t seed, uint8_t* inliers, double* result, int32_t* counts);
+int vp_fit_plane_host(const float* xyz, size_t xyz_stride, int w, int h, const int32_t* box, const uint8_t* mask, size_t mask_stride, int metric, double threshold,
+                      int max_iters, double confidence, uint32_t seed, uint8_t* inliers, size_t inliers_stride, double* result, int32_t* counts);
+int vp_plane_hypothesis(const float* pts4, int n, int metric, uint32_t seed, int j, int32_t* sample3, double* plane4);
+int vp_plane_refit(const float* pts4, int n, const uint8_t* keep, int metric, double* result);
+
 /* ---- device memory helpers (so a host program needs no HIP binding of its own) --------- */
 int vp_dev_alloc(vp_ctx* ctx, size_t bytes, void** dev_ptr);
 int vp_dev_free(vp_ctx* ctx, void* dev_ptr);    /* ctx may be NULL (memory that outlived its context) */
