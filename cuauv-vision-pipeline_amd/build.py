@@ -13,7 +13,7 @@ CSRC = os.path.join(HERE, "csrc")
 LIBDIR = os.path.join(HERE, "lib")
 HIPCC = os.environ.get("HIPCC") or shutil.which("hipcc") or "/opt/rocm/bin/hipcc"
 
-VP_SOURCES = ["vp_api.hip", "vp_api_color.hip", "vp_api_morph_chain.hip", "vp_api_shapes.hip", "vp_api_label.hip", "vp_api_filter.hip", "vp_api_moments.hip", "vp_api_corners.hip", "vp_api_dist.hip", "vp_api_kmeans.hip", "vp_api_match.hip", "vp_api_hist.hip", "vp_api_flow.hip", "vp_api_model.hip", "vp_api_features.hip", "vp_api_geometry.hip", "vp_geometry.hip", "vp_api_stereo.hip", "vp_stereo.hip", "vp_api_speckle.hip", "vp_speckle.hip", "vp_api_sgm.hip", "vp_sgm.hip", "vp_api_rectify.hip", "vp_rectify.hip", "vp_api_plane.hip", "vp_plane.hip", "vp_color.hip", "vp_morph.hip", "vp_fill.hip", "vp_ccl.hip", "vp_balance.hip", "vp_yolo.hip", "vp_filter.hip", "vp_feed.hip", "vp_post.hip", "vp_hough.hip", "vp_hough_circles.hip", "vp_whitebal.hip", "vp_adaptive.hip", "vp_elementwise.hip", "vp_median.hip", "vp_deriv.hip", "vp_clahe.hip", "vp_remap.hip", "vp_box.hip", "vp_pyr.hip", "vp_integral.hip", "vp_moments.hip", "vp_corners.hip", "vp_dist.hip", "vp_kmeans.hip", "vp_match.hip", "vp_hist.hip", "vp_flow.hip", "vp_model.hip", "vp_features.hip", "vp_tables.cpp"]
+VP_SOURCES = ["vp_api.hip", "vp_api_color.hip", "vp_api_morph_chain.hip", "vp_api_shapes.hip", "vp_api_label.hip", "vp_api_filter.hip", "vp_api_moments.hip", "vp_api_corners.hip", "vp_api_dist.hip", "vp_api_kmeans.hip", "vp_api_match.hip", "vp_api_hist.hip", "vp_api_flow.hip", "vp_api_model.hip", "vp_api_features.hip", "vp_api_geometry.hip", "vp_geometry.hip", "vp_api_stereo.hip", "vp_stereo.hip", "vp_api_speckle.hip", "vp_speckle.hip", "vp_api_sgm.hip", "vp_sgm.hip", "vp_api_rectify.hip", "vp_rectify.hip", "vp_api_plane.hip", "vp_plane.hip", "vp_api_rigid.hip", "vp_rigid.hip", "vp_color.hip", "vp_morph.hip", "vp_fill.hip", "vp_ccl.hip", "vp_balance.hip", "vp_yolo.hip", "vp_filter.hip", "vp_feed.hip", "vp_post.hip", "vp_hough.hip", "vp_hough_circles.hip", "vp_whitebal.hip", "vp_adaptive.hip", "vp_elementwise.hip", "vp_median.hip", "vp_deriv.hip", "vp_clahe.hip", "vp_remap.hip", "vp_box.hip", "vp_pyr.hip", "vp_integral.hip", "vp_moments.hip", "vp_corners.hip", "vp_dist.hip", "vp_kmeans.hip", "vp_match.hip", "vp_hist.hip", "vp_flow.hip", "vp_model.hip", "vp_features.hip", "vp_tables.cpp"]
 
 
 def _stale(target, deps):

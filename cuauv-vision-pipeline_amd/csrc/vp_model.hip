@@ -7,6 +7,7 @@
 // without floating-point contraction.
 #include "vp_internal.h"
 #include "vp_model_plan.h"
+#include "vp_ransac_dev.h"
 
 // (x, y) of both arrays side by side: what every other kernel reads
 __global__ __launch_bounds__(RS_THREADS) void k_rs_pack(const float2* __restrict__ src, const float2* __restrict__ dst, int n, float4* __restrict__ pts)
@@ -39,14 +40,9 @@ __global__ __launch_bounds__(RS_THREADS) void k_rs_select(const float4* __restri
     } else {
         if (state->done) return;             // the same word in every thread: all return or none
         const int c = valid[t] ? counts[t] : -1;
-        s_key[t] = ((u32)(c + 1) << 8) | (u32)(RS_THREADS - 1 - t);
-        __syncthreads();
-        for (int w = RS_THREADS / 2; w >= 1; w >>= 1) {
-            if (t < w && s_key[t + w] > s_key[t]) s_key[t] = s_key[t + w];
-            __syncthreads();
-        }
+        const u32 top = vp_rsd_block_max<RS_THREADS>(s_key, t, ((u32)(c + 1) << 8) | (u32)(RS_THREADS - 1 - t));
         if (t == 0) {
-            const int bc = (int)(s_key[0] >> 8) - 1, bt = RS_THREADS - 1 - (int)(s_key[0] & 255u);
+            const int bc = (int)(top >> 8) - 1, bt = RS_THREADS - 1 - (int)(top & 255u);
             int best = state->best_count;
             if (bc > best) {
                 best = bc;

@@ -9,6 +9,7 @@
 // without floating-point contraction.
 #include "vp_internal.h"
 #include "vp_plane_plan.h"
+#include "vp_ransac_dev.h"
 
 struct pl_image {
     const float* xyz; size_t xstride;        // bytes
@@ -76,20 +77,7 @@ __global__ __launch_bounds__(PL_THREADS) void k_pl_compact(pl_image I, int32_t* 
 __global__ __launch_bounds__(PL_THREADS) void k_pl_scan(const int32_t* __restrict__ run_count, int runs, int32_t* __restrict__ run_off, vp_pl_state* __restrict__ state)
 {
     __shared__ int s_sum[PL_THREADS];
-    const int t = threadIdx.x, per = (runs + PL_THREADS - 1) / PL_THREADS;
-    const int lo = t * per < runs ? t * per : runs, hi = lo + per < runs ? lo + per : runs;
-    int c = 0;
-    for (int i = lo; i < hi; i++) c += run_count[i];
-    s_sum[t] = c;
-    __syncthreads();
-    if (t == 0) {
-        int acc = 0;
-        for (int k = 0; k < PL_THREADS; k++) { const int v = s_sum[k]; s_sum[k] = acc; acc += v; }
-        state->n_usable = acc;
-    }
-    __syncthreads();
-    int acc = s_sum[t];
-    for (int i = lo; i < hi; i++) { run_off[i] = acc; acc += run_count[i]; }
+    vp_rsd_scan_runs<PL_THREADS>(run_count, runs, run_off, &state->n_usable, s_sum);
 }
 
 // One block, one thread per hypothesis of a round.  round >= 0: closes that round - the best count with the lowest index, folded
@@ -116,14 +104,9 @@ __global__ __launch_bounds__(PL_THREADS) void k_pl_select(const float4* __restri
     } else {
         if (state->done) return;             // the same word in every thread: all return or none
         const int c = valid[t] ? counts[t] : -1;
-        s_key[t] = ((u64)(c + 1) << 8) | (u64)(PL_THREADS - 1 - t);
-        __syncthreads();
-        for (int w = PL_THREADS / 2; w >= 1; w >>= 1) {
-            if (t < w && s_key[t + w] > s_key[t]) s_key[t] = s_key[t + w];
-            __syncthreads();
-        }
+        const u64 top = vp_rsd_block_max<PL_THREADS>(s_key, t, ((u64)(c + 1) << 8) | (u64)(PL_THREADS - 1 - t));
         if (t == 0) {
-            const int bc = (int)(s_key[0] >> 8) - 1, bt = PL_THREADS - 1 - (int)(s_key[0] & 255u);
+            const int bc = (int)(top >> 8) - 1, bt = PL_THREADS - 1 - (int)(top & 255u);
             int best = state->best_count;
             if (bc > best) {
                 best = bc;
@@ -184,13 +167,6 @@ __global__ __launch_bounds__(PL_THREADS) void k_pl_score(const float4* __restric
     }
 }
 
-__device__ __forceinline__ double pl_wave_sum(double v)
-{
-#pragma unroll
-    for (int o = 32; o >= 1; o >>= 1) v += __shfl_down(v, o, 64);
-    return v;
-}
-
 // the inlier bytes of the best plane, 255 at the pixel of every inlier (the image was cleared in front of this launch; inl NULL: none
 // wanted), and the nine sums of the refit about the best sample's first point: a wave adds its lanes, lane 0 adds to the state
 __global__ __launch_bounds__(PL_THREADS) void k_pl_finish(const float4* __restrict__ pts, int metric, double t2, int w, vp_pl_state* __restrict__ state,
@@ -226,7 +202,7 @@ __global__ __launch_bounds__(PL_THREADS) void k_pl_finish(const float4* __restri
     if (!__ballot(in)) return;               // a wave without inliers has nothing to add
 #pragma unroll
     for (int k = 0; k < PL_SUMS; k++) {
-        const double s = pl_wave_sum(S[k]);
+        const double s = vp_rsd_wave_sum(S[k]);
         if ((threadIdx.x & 63) == 0) atomicAdd(&state->sums[k], s);
     }
 }

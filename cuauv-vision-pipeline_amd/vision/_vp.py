@@ -60,6 +60,8 @@ WARP_INVERSE_MAP = 16
 MODEL_SIMILARITY, MODEL_AFFINE, MODEL_HOMOGRAPHY = 0, 1, 2
 PLANE_PERP, PLANE_ALONG_Z = 0, 1
 PLANE_RESULT, PLANE_COUNTS = 12, 4
+RIGID_EUCLID, RIGID_DISPARITY = 0, 1
+RIGID_RESULT, RIGID_COUNTS = 31, 4
 PROF_KERNELS = 18
 
 
@@ -390,6 +392,21 @@ _SIGS = {
                                     C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p]),
     "vp_plane_hypothesis": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_uint32, C.c_int, C.c_void_p, C.c_void_p]),
     "vp_plane_refit": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p]),
+    "vp_fit_rigid_plan": (C.c_int, [C.c_int, C.c_void_p, C.c_void_p]),
+    "vp_fit_rigid_dev": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_double, C.c_double, C.c_double, C.c_int, C.c_double, C.c_uint32,
+                                   C.c_void_p, C.c_void_p, C.c_void_p]),
+    "vp_fit_rigid_f32": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_double, C.c_double, C.c_double, C.c_int, C.c_double, C.c_uint32,
+                                   C.c_void_p, C.c_void_p, C.c_void_p]),
+    "vp_fit_rigid_host": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_double, C.c_double, C.c_double, C.c_int, C.c_double, C.c_uint32, C.c_void_p,
+                                    C.c_void_p, C.c_void_p]),
+    "vp_fit_rigid_tracks_dev": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_int,
+                                          C.c_double, C.c_double, C.c_double, C.c_int, C.c_double, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "vp_fit_rigid_tracks_f32": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_double, C.c_double,
+                                          C.c_double, C.c_int, C.c_double, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "vp_fit_rigid_tracks_host": (C.c_int, [C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_double,
+                                           C.c_double, C.c_double, C.c_int, C.c_double, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "vp_rigid_hypothesis": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_uint32, C.c_int, C.c_void_p, C.c_void_p]),
+    "vp_rigid_refit": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]),
 }
 
 

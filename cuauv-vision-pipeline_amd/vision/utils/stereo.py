@@ -25,6 +25,11 @@ The quantity a mission consumes (libvp vp_plane.hip): `f
 of an image by RANSAC - normal, distance, inlier count and inlier mask - bit for bit as tests/plane_restate.py states the search;
 `fit_planes` peels several; `StereoRig.fit_plane` searches in disparity space, where stereo noise is uniform, and answers in metres;
 `plane_distance` and `plane_angles` read a result.
+
+How the scene moved between two frames (libvp vp_rigid.hip): `fit_rigid` finds one rigid motion
+q = R p + t through paired 3-D points by RANSAC, bit for bit as tests/rigid_restate.py states the search, with the distance taken in
+metres or as a stereo rig sees it; `rigid_from_tracks` takes its pairs from two point images at the ends of point tracks;
+`StereoRig.ego_motion` runs it from two disparity images.
 """
 import ctypes as C
 import dataclasses
@@ -800,6 +805,26 @@ class StereoRig:
         c = self.Q @ np.append(fit.centroid, 1.0)
         return dataclasses.replace(fit, normal=pi[:3], d=float(pi[3]), centroid=c[:3] / c[3])
 
+    def ego_motion(self, disp_prev, disp_cur, prev_pts, next_pts, status=None, space: str = "disparity", threshold=None, min_disparity: int = 0, **search):
+        """How the scene moved between two frames of the rig -> RigidFit, in metres, in the rectified left camera's frame:
+        `rigid_from_tracks` on `self.points()` of both disparity images and the point tracks prev_pts -> next_pts between the two
+        rectified left images (`track_points`' arguments and results; status as it returns it).  The fit maps the scene's points
+        from the previous frame to the current one, P_cur = R P_prev + t: for a static scene that is the previous camera's pose
+        seen from the current camera.  `inverse()` of it is the current camera's pose in the previous camera's frame - how the
+        vehicle moved.  space="disparity" (the default): the residual is taken in pixels and pixels of disparity with the rig's
+        focal_px and baseline_m, `threshold` in pixels (default 1.0); space="metric": in metres (default 0.02).  **search:
+        max_iters, confidence, seed, return_mask.  Both point images are made and used in HBM."""
+        if space not in ("disparity", "metric"):
+            raise ValueError('space must be "disparity" or "metric"')
+        camera = (self.focal_px, self.baseline_m) if space == "disparity" else None
+        if threshold is None:
+            threshold = 1.0 if space == "disparity" else 0.02
+        as_dev = lambda m: m if isinstance(m, DeviceMat) or not isinstance(m, np.ndarray) else DeviceMat.from_host(_vp.default_context(), np.ascontiguousarray(m))
+        _track_args(prev_pts, next_pts, status)
+        _rigid_args(threshold, search.get("max_iters", 1000), search.get("confidence", 0.99), search.get("seed", 0), camera)
+        return rigid_from_tracks(self.points(as_dev(disp_prev), min_disparity), self.points(as_dev(disp_cur), min_disparity), prev_pts, next_pts, status,
+                                 threshold=threshold, camera=camera, **search)
+
 
 # ---- planes through 3-D points (libvp vp_plane.hip; DESIGN.md section 4.38) ------------------------------------------------------------
 PLANE_MAX_ITERS = 65536
@@ -967,3 +992,157 @@ def plane_angles(fit):
     a surface that faces the camera squarely.  Host float64."""
     n = -np.asarray(fit.normal, np.float64)
     return float(np.arctan2(n[0], n[2])), float(np.arctan2(n[1], np.hypot(n[0], n[2])))
+
+
+# ---- rigid motion between paired 3-D points (libvp vp_rigid.hip; DESIGN.md section 4.39) ------------------------------------------------
+RIGID_MAX_PAIRS = 1 << 20
+
+
+@dataclasses.dataclass
+class RigidFit:
+    """What `fit_rigid` found: the motion q = R p + t that carries the source points onto the destination points, R a rotation
+    (det +1).  found False: no motion; everything else is zero then."""
+    found: bool
+    R: np.ndarray               # (3, 3) float64, the least-squares refit over the inliers
+    t: np.ndarray               # (3,) float64
+    hypothesis: np.ndarray      # (3, 4) float64 [R | t], the best three-pair hypothesis of the search (bit for bit the statement's)
+    n_usable: int               # pairs the search saw
+    n_inliers: int
+    n_hypotheses: int           # hypotheses taken
+    best_index: int             # index of the best hypothesis, -1 when there is none
+    centroids: np.ndarray       # (2, 3) float64, the inliers' mean on the source and on the destination side
+    rms: float                  # root mean square distance |R p + t - q| of the inliers, in the points' unit under both metrics
+    mask: object = None         # with return_mask: uint8 (n,), 1 at every inlier pair (or track)
+
+    @property
+    def matrix(self):
+        """(4, 4) float64: [R t; 0 0 0 1]"""
+        m = np.eye(4)
+        m[:3, :3], m[:3, 3] = self.R, self.t
+        return m
+
+    def inverse(self):
+        """The motion the other way round, p = R^T q - R^T t (the search's counts, hypothesis and mask stay as they are; the
+        centroids swap)."""
+        Ri = self.R.T.copy()
+        return dataclasses.replace(self, R=Ri, t=-(Ri @ self.t), centroids=self.centroids[::-1].copy())
+
+
+def _rigid_args(threshold, max_iters, confidence, seed, camera):
+    threshold, confidence = float(threshold), float(confidence)
+    if not (np.isfinite(threshold) and threshold > 0):
+        raise ValueError("fit rigid: the threshold must be finite and above 0")
+    focal, baseline = 0.0, 0.0
+    if camera is not None:
+        if len(camera) != 2:
+            raise ValueError("camera must be (focal_px, baseline_m)")
+        focal, baseline = float(camera[0]), float(camera[1])
+        if not (np.isfinite(focal) and focal > 0):
+            raise ValueError("fit rigid: focal_px must be finite and above 0")
+        if not (np.isfinite(baseline) and baseline > 0):
+            raise ValueError("fit rigid: the baseline must be finite and above 0")
+    max_iters = _int_in("max_iters", max_iters, -2 ** 31, 2 ** 31 - 1)
+    if not 1 <= max_iters <= PLANE_MAX_ITERS:
+        raise ValueError("fit rigid: max_iters must be 1 to 65536")
+    if not 0 < confidence < 1:
+        raise ValueError("fit rigid: the confidence must be above 0 and below 1")
+    metric = _vp.RIGID_EUCLID if camera is None else _vp.RIGID_DISPARITY
+    return metric, threshold, focal, baseline, max_iters, confidence, _int_in("seed", seed, 0, 2 ** 32 - 1)
+
+
+def _track_args(prev_pts, next_pts, status):
+    """(prev float32 (n, 2), rows uint32 (n, 4): x, y, err 0, status) - the rows vp_lk_flow_dev leaves"""
+    prev = np.ascontiguousarray(np.asarray(prev_pts, dtype=np.float32).reshape(-1, 2))
+    cur = np.ascontiguousarray(np.asarray(next_pts, dtype=np.float32).reshape(-1, 2))
+    n = len(prev)
+    if len(cur) != n or not 1 <= n <= RIGID_MAX_PAIRS:
+        raise ValueError("fit rigid: 1 to 1048576 tracks, as many next_pts as prev_pts")
+    rows = np.zeros((n, 4), np.uint32)
+    rows[:, :2] = cur.view(np.uint32)
+    if status is None:
+        rows[:, 3] = 1
+    else:
+        st = np.asarray(status).reshape(-1)
+        if len(st) != n:
+            raise ValueError("fit rigid: one status per track")
+        rows[:, 3] = st != 0
+    return prev, rows
+
+
+def _rigid_fit(result, counts, mask):
+    found = bool(counts[3] >= 0)
+    return RigidFit(found=found, R=result[0:9].reshape(3, 3).copy(), t=result[9:12].copy(), hypothesis=np.concatenate([result[12:21].reshape(3, 3), result[21:24, None]], 1),
+                    n_usable=int(counts[0]), n_inliers=int(counts[1]), n_hypotheses=int(counts[2]), best_index=int(counts[3]),
+                    centroids=result[24:30].reshape(2, 3).copy(), rms=float(result[30]), mask=mask)
+
+
+def fit_rigid(src, dst, threshold: float = 0.02, max_iters: int = 1000, confidence: float = 0.99, seed: int = 0, camera=None, return_mask: bool = False):
+    """One rigid motion dst = R src + t through paired 3-D points, by RANSAC on the GPU (libvp vp_fit_rigid_*; the statement:
+    tests/rigid_restate.py) -> RigidFit.  src, dst: float32 (n, 3); a pair with a point that is not finite or is the three zeros (the
+    library's "unknown") is skipped.  threshold: the largest distance |R p + t - q| of an inlier, in the points' unit.
+    camera=(focal_px, baseline_m): the distance is taken as a rectified stereo rig of that focal length and baseline sees it - pixels
+    in the image and pixels of disparity, `threshold` in pixels; points behind the camera (Z <= 0) are outliers.  Stereo noise is
+    uniform there, while in metres it grows with Z squared.  The refit is least squares in the points' unit under both metrics.
+    The search is a pure function of its arguments and `seed`.  return_mask: RigidFit.mask is uint8 (n,), 1 at every inlier."""
+    for a in (src, dst):
+        if not isinstance(a, np.ndarray) or a.dtype != np.float32 or a.ndim != 2 or a.shape[1] != 3:
+            raise TypeError("expected float32 (n, 3) arrays of points")
+    n = src.shape[0]
+    if dst.shape[0] != n or not 1 <= n <= RIGID_MAX_PAIRS:
+        raise ValueError("fit rigid: 1 to 1048576 pairs, as many dst as src")
+    metric, threshold, focal, baseline, max_iters, confidence, seed = _rigid_args(threshold, max_iters, confidence, seed, camera)
+    ctx = _vp.default_context()
+    src, dst = np.ascontiguousarray(src), np.ascontiguousarray(dst)
+    out = np.empty(n, np.uint8) if return_mask else None
+    result, counts = np.zeros(_vp.RIGID_RESULT, np.float64), np.zeros(_vp.RIGID_COUNTS, np.int32)
+    _vp.check(_vp.lib().vp_fit_rigid_f32(ctx.handle, src.ctypes.data, dst.ctypes.data, n, metric, threshold, focal, baseline, max_iters, confidence, seed,
+                                         None if out is None else out.ctypes.data, result.ctypes.data, counts.ctypes.data), ctx.handle)
+    return _rigid_fit(result, counts, out)
+
+
+def rigid_from_tracks(points_prev, points_cur, prev_pts, next_pts, status=None, threshold: float = 0.02, max_iters: int = 1000, confidence: float = 0.99, seed: int = 0,
+                      camera=None, return_mask: bool = False):
+    """`fit_rigid` between the 3-D points two frames show at the ends of point tracks -> RigidFit of the motion from the previous
+    frame's points to the current frame's.  points_prev, points_cur: float32 (h, w, 3) images of the same size, numpy or DeviceMat,
+    as `reproject_to_3d` and `StereoRig.points` give them; a DeviceMat is used where it lies and no point image is downloaded.
+    prev_pts, next_pts: (n, 2) pixel positions in the two images, status (n,) non-zero where a track was found - `track_points`'
+    arguments and results.  A track gives a pair when its status is set, its coordinates are finite, both positions round to a
+    pixel inside the image (the nearest pixel: interpolating points across a depth edge would invent some) and both points are
+    known.  The mask is per track.  The other arguments are `fit_rigid`'s."""
+    for a in (points_prev, points_cur):
+        if not isinstance(a, (np.ndarray, DeviceMat)) or a.dtype != np.float32 or len(a.shape) != 3 or a.shape[2] != 3 or 0 in a.shape:
+            raise TypeError("expected float32 (h, w, 3) images of points")
+    if tuple(points_prev.shape) != tuple(points_cur.shape):
+        raise ValueError("fit rigid: the two point images must have one size")
+    h, w = points_prev.shape[:2]
+    if max(h, w) > MAX_SIDE:
+        raise ValueError("fit rigid: the images must be 1 to 4096 pixels wide and high")
+    prev, rows = _track_args(prev_pts, next_pts, status)
+    metric, threshold, focal, baseline, max_iters, confidence, seed = _rigid_args(threshold, max_iters, confidence, seed, camera)
+    n = len(prev)
+    ctx = _vp.default_context()
+    result, counts = np.zeros(_vp.RIGID_RESULT, np.float64), np.zeros(_vp.RIGID_COUNTS, np.int32)
+    if isinstance(points_prev, DeviceMat) or isinstance(points_cur, DeviceMat):
+        up = []
+        try:
+            dev = []
+            for a in (points_prev, points_cur):
+                if isinstance(a, DeviceMat):
+                    a.refresh_device(ctx)
+                    dev.append(a)
+                else:
+                    dev.append(DeviceMat.from_host(ctx, np.ascontiguousarray(a), pending=up))
+            drows = DeviceMat.from_host(ctx, rows, pending=up)
+            out = DeviceMat(ctx, (n,), np.uint8) if return_mask else None
+            _vp.check(_vp.lib().vp_fit_rigid_tracks_dev(ctx.handle, dev[0].dev_ptr, 12 * w, dev[1].dev_ptr, 12 * w, w, h, prev.ctypes.data, drows.dev_ptr, n, metric,
+                                                        threshold, focal, baseline, max_iters, confidence, seed, None if out is None else out.dev_ptr,
+                                                        result.ctypes.data, counts.ctypes.data), ctx.handle)
+        finally:
+            finish_uploads(ctx, up)
+        return _rigid_fit(result, counts, None if out is None else out.host())
+    a, b = np.ascontiguousarray(points_prev), np.ascontiguousarray(points_cur)
+    out = np.empty(n, np.uint8) if return_mask else None
+    _vp.check(_vp.lib().vp_fit_rigid_tracks_f32(ctx.handle, a.ctypes.data, b.ctypes.data, w, h, prev.ctypes.data, rows.ctypes.data, n, metric, threshold, focal, baseline,
+                                                max_iters, confidence, seed, None if out is None else out.ctypes.data, result.ctypes.data, counts.ctypes.data),
+              ctx.handle)
+    return _rigid_fit(result, counts, out)

@@ -1253,6 +1253,68 @@ int vp_fit_plane_host(const float* xyz, size_t xyz_stride, int w, int h, const i
 int vp_plane_hypothesis(const float* pts4, int n, int metric, uint32_t seed, int j, int32_t* sample3, double* plane4);
 int vp_plane_refit(const float* pts4, int n, const uint8_t* keep, int metric, double* result);
 
+/* ---- robust rigid 3-D motion between paired 3-D points: how the scene moved between two stereo frames --------
+ * RANSAC for one motion q = R p + t (R a rotation, never a reflection) over n pairs of float32 3-vectors.  The contract is the
+ * statement tests/rigid_restate.py, reproduced bit for bit in the best hypothesis, its index, the counts and the inlier bytes.  A pair
+ * is usable when both points pass the plane fit's point test (three finite floats, not all three zero); the search runs over the
+ * usable pairs in index order.  Hypothesis j draws three distinct pair indices from the counter-based sampler of vp_estimate_model_*
+ * (seed, j); each side's triad gives an orthonormal frame (u1 along e1 = p1 - p0, u3 along e1 x e2, u2 = u3 x u1), R carries the source
+ * frame onto the destination frame and t carries the source triad's mean onto the destination's, in double in one written order;
+ * void: a triad on either side whose angle has a sine below 1e-6, or a number that is not finite.  With m = R p + t a pair is an
+ * inlier iff |m - q|^2 <= T^2 (VP_RIGID_EUCLID, T in the points' unit) or, with VP_RIGID_DISPARITY, iff m_z > 0, q_z > 0 and
+ * (du^2 + dv^2) + dd^2 <= T^2 with du = f (m_x / m_z - q_x / q_z), dv likewise with y, dd = f b (1 / m_z - 1 / q_z): the distance in
+ * pixels and pixels of disparity a rectified rig of focal length f = focal_px and baseline b sees, T in pixels (focal_px and baseline
+ * are ignored under VP_RIGID_EUCLID).  The score is the integer inlier count, ties go to the lowest j; rounds and the stop rule are
+ * those of vp_fit_plane_*; with fewer than three usable pairs nothing is searched.
+ * result (VP_RIGID_RESULT doubles): the refit R (9, row-major) and t (3), the best hypothesis R (9) and t (3), the inliers' source and
+ *   destination centroids (3 + 3), the rms residual of the refit over the inliers (the points' unit, under both metrics).  The refit
+ *   is the least-squares rotation by Horn's quaternion, closed on the host from seventeen sums the device adds in a free order: it is
+ *   not bit-exact by design; a degenerate refit (the inliers lie on a line) repeats the best hypothesis.
+ * counts (VP_RIGID_COUNTS): usable pairs, inliers, hypotheses taken, index of the best hypothesis.  No model: result is zeros,
+ *   counts[1] is 0, counts[3] is -1 and the inlier bytes are zeros.
+ * inliers (nullable): n bytes by original pair index, 1 for an inlier and 0 otherwise; all n are written and nothing beyond them.
+ * vp_fit_rigid_dev reads device arrays (n rows of three float32 each) and writes device bytes; it enqueues every launch, the number of
+ *   usable pairs never leaves the device before the end, and it synchronises once to hand back result and counts.  vp_fit_rigid_f32
+ *   stages host arrays.  vp_fit_rigid_host is the same statement as a host loop: no device, no context.
+ * vp_fit_rigid_tracks_*: the pairs come from two XYZ images (float32, three floats a pixel, rows of a stride in bytes, both w x h, as
+ *   vp_reproject_to_3d_* writes them) and n tracks: prev_pts, n (x, y) float32 pairs on the host, and the n four-word rows x, y, err,
+ *   status that vp_lk_flow_dev leaves in out_dev (device memory for _dev, host memory otherwise).  Track i gives the pair (point of
+ *   the previous image at prev_pts[i], point of the current image at its row's x, y) when its status is not 0, its four coordinates
+ *   are finite, both positions round to a pixel inside the image - ix = floor(x + 0.5f), admitted iff x >= -0.5f and x < w - 0.5f,
+ *   the same for y: the nearest pixel, never an interpolation across a depth edge - and both points are usable.  The inlier bytes
+ *   are per track row.  _f32 takes packed host images.
+ * vp_fit_rigid_plan: the workspace a call on n pairs or tracks reserves at most (without the copies _f32 stages), and geometry[8]: the
+ *   compaction's run length, the pairs a scoring block stages, the hypotheses a scoring block tests, the block size, the round size,
+ *   n, the compaction's blocks, the scoring grid's chunks.
+ * vp_rigid_hypothesis: hypothesis j over n pairs (all taken as usable) as the kernel forms it - sample3 and motion12 (R, t); returns
+ *   1, or 0 for a void hypothesis (zeros).  vp_rigid_refit: the refit alone over the pairs whose keep byte is not 0 (keep NULL: all),
+ *   its sums taken about the first kept pair in index order; returns 1, or 0 (zeros) when it is degenerate.
+ * Refused with VP_ERR_INVALID before anything is launched or written (the message names the reason): a missing pointer; n outside
+ *   1..2^20; w or h outside 1..4096; a stride below the row or no multiple of 4; a misaligned input; an unknown metric; a threshold
+ *   that is not finite and above 0, and under VP_RIGID_DISPARITY a focal_px or baseline that is not; max_iters outside 1..65536; a
+ *   confidence outside (0, 1); a hypothesis index outside 0..65535; inlier bytes that overlap an input. */
+enum { VP_RIGID_EUCLID = 0, VP_RIGID_DISPARITY = 1 };
+#define VP_RIGID_RESULT 31
+#define VP_RIGID_COUNTS 4
+int vp_fit_rigid_plan(int n, size_t* ws_bytes, int32_t* geometry);
+int vp_fit_rigid_dev(vp_ctx* ctx, const float* src_dev, const float* dst_dev, int n, int metric, double threshold, double focal_px, double baseline, int max_iters,
+                     double confidence, uint32_t seed, uint8_t* inliers_dev, double* result, int32_t* counts);
+int vp_fit_rigid_f32(vp_ctx* ctx, const float* src, const float* dst, int n, int metric, double threshold, double focal_px, double baseline, int max_iters,
+                     double confidence, uint32_t seed, uint8_t* inliers, double* result, int32_t* counts);
+int vp_fit_rigid_host(const float* src, const float* dst, int n, int metric, double threshold, double focal_px, double baseline, int max_iters, double confidence,
+                      uint32_t seed, uint8_t* inliers, double* result, int32_t* counts);
+int vp_fit_rigid_tracks_dev(vp_ctx* ctx, const float* xyz_prev_dev, size_t xyz_prev_stride, const float* xyz_cur_dev, size_t xyz_cur_stride, int w, int h,
+                            const float* prev_pts_host, const void* tracks_dev, int n, int metric, double threshold, double focal_px, double baseline, int max_iters,
+                            double confidence, uint32_t seed, uint8_t* inliers_dev, double* result, int32_t* counts);
+int vp_fit_rigid_tracks_f32(vp_ctx* ctx, const float* xyz_prev, const float* xyz_cur, int w, int h, const float* prev_pts, const void* tracks, int n, int metric,
+                            double threshold, double focal_px, double baseline, int max_iters, double confidence, uint32_t seed, uint8_t* inliers, double* result,
+                            int32_t* counts);
+int vp_fit_rigid_tracks_host(const float* xyz_prev, size_t xyz_prev_stride, const float* xyz_cur, size_t xyz_cur_stride, int w, int h, const float* prev_pts,
+                             const void* tracks, int n, int metric, double threshold, double focal_px, double baseline, int max_iters, double confidence, uint32_t seed,
+                             uint8_t* inliers, double* result, int32_t* counts);
+int vp_rigid_hypothesis(const float* src3, const float* dst3, int n, uint32_t seed, int j, int32_t* sample3, double* motion12);
+int vp_rigid_refit(const float* src3, const float* dst3, int n, const uint8_t* keep, double* result);
+
 /* ---- device memory helpers (so a host program needs no HIP binding of its own) --------- */
 int vp_dev_alloc(vp_ctx* ctx, size_t bytes, void** dev_ptr);
 int vp_dev_free(vp_ctx* ctx, void* dev_ptr);    /* ctx may be NULL (memory that outlived its context) */
